@@ -5,18 +5,22 @@ A "step" is one pass of the whole hot path (match -> 8-point RANSAC -> decomposi
 over one resident batch of synthetic pairs (default 512 pairs of 2000 keypoints, 50 000 hypotheses
 each = BASELINE.json configs[2] per GPU; configs[3] is the same workload on 8 GPUs).  Inputs are
 uploaded to HBM before the timed region.  Rank 0's LAST stdout line is ONE compact JSON object (< 4 KB: the contract's
-fields, `roofline`, `cpu_baseline`, one scalar per side leg -- what the driver parses); the full object goes to
+fields, `roofline`, `cpu_baseline`, one scalar per side leg -- what the driver parses).
+
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if --dump-outputs DIR is given, and
+prints the line; its side-leg members are null.  --full adds everything else (below) and writes the full object to
 bench_detail.json beside this file (--detail PATH; --print-detail also prints it as an earlier line).
 
     python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full --dump-outputs out/
     python bench.py --gpus 8                       # spawns its own 8 rank processes (no launcher needed)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-The detail object carries (rank 0, N = 1): `roofline.per_kernel` (executed work per kernel, registers / LDS / occupancy as
-the runtime reports them), `reference_threshold` (the SURVEY 8(d) threshold 5e-2/K00/K11 in its own wall-clock loop with
-its own roofline), `sensitivity` (24 cells), and the rows either side of the path: `sequence` (BASELINE configs[4]),
-`refine`, `extract`.
+With --full the detail object carries (rank 0, N = 1): `roofline.per_kernel` (executed work per kernel, registers / LDS /
+occupancy as the runtime reports them), `reference_threshold` (the SURVEY 8(d) threshold 5e-2/K00/K11 in its own wall-clock
+loop with its own roofline), `sensitivity` (24 cells), the CPU baselines, and the rows either side of the path: `sequence`
+(BASELINE configs[4]), `refine`, `extract`.
 """
 import argparse
 import json
@@ -586,6 +590,38 @@ def write_detail(out, path):
         return None
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(path, batch, first, np, capi):
+    """--dump-outputs: what the timed path handed back in its last step -- the batch's result records, matches, inlier
+    masks, triangulated points and their match indices, as mvs_batch_download returns them -- one <path>/<name>.npy per
+    array and record field.  float64, except the integer match / point indices, the mask and the f32 match distance, which
+    are exact in float32.  Rows past a pair's counts are zero (the download's contract), so two builds compare array for
+    array.  A batch larger than DUMP_LIMIT_BYTES is written as a fixed, seeded sample of pairs; pair_index.npy holds the
+    global pair index of every row."""
+    assert batch.max_kp <= 1 << 24, "indices would not be exact in float32"
+    dl = batch.download()
+    res = dl["results"]
+    arrays = {"pair_index": np.arange(first, first + batch.n_pairs, dtype=np.float64)}
+    for name in capi.RESULT_DTYPE.names:
+        arrays["results_" + name] = res[name].astype(np.float64)
+    for name in capi.MATCH_DTYPE.names:
+        arrays["matches_" + name] = dl["matches"][name].astype(np.float32)
+    arrays["mask"] = dl["mask"].astype(np.float32)
+    arrays["points"] = dl["points"].astype(np.float64)
+    arrays["point_idx"] = dl["point_idx"].astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = max(1, DUMP_LIMIT_BYTES * batch.n_pairs // total)
+        sel = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(batch.n_pairs, size=keep, replace=False))
+        arrays = {k: a[sel] for k, a in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def profiler_preload_active():
     """True under rocprofv3 & co.: the tool's preloaded library has initialised the GPU before this program started, so
     starting a child process from here is the exec the pool forbids."""
@@ -646,9 +682,17 @@ def main():
     ap.add_argument("--seq-cpu-frames", type=int, default=48)
     ap.add_argument("--launch-timeout", type=float, default=None, help="seconds before a self-launched run is abandoned")
     ap.add_argument("--detail", default=os.path.join(ROOT, DETAIL_NAME),
-                    help="where rank 0 writes the full (bulky) result object; the LAST stdout line is the compact one")
+                    help="where rank 0 writes the full (bulky) result object with --full; the LAST stdout line is the "
+                         "compact one")
     ap.add_argument("--print-detail", action="store_true", help="also print the full object as an EARLIER stdout line")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the ImagePair probe, per-kernel tables and "
+                    "rooflines, the reference-threshold, single-pair, transfer-inclusive and --sections legs, the CPU "
+                    "baselines and the --detail file (a plain run times the steps and prints the line, nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one "
+                    "computed (rank 0's batch) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
@@ -666,7 +710,7 @@ def main():
     # the ImagePair-constructor probe is a child process: it runs BEFORE this process initialises the GPU,
     # alone on the device, and its JSON is kept for the line
     probe_result = None
-    if rank == 0 and world == 1 and not args.no_single_pair:
+    if args.full and rank == 0 and world == 1 and not args.no_single_pair:
         probe_result = image_pair_probe(args.kp, args.hyp)
 
     import numpy as np
@@ -769,7 +813,41 @@ def main():
     total_pairs = n_local * world
     value = total_pairs * args.steps / elapsed
 
+    out = None
     if rank == 0:
+        if args.dump_outputs:   # before anything else runs on the batch: these are the last timed step's outputs
+            dump_outputs(args.dump_outputs, batch, first, np, capi)
+        out = {
+            "metric": "image-pairs/sec (2k kp, 50k RANSAC hyp)", "value": round(value, 2), "unit": "pairs/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {
+                "workload": "%d independent synthetic 640x480 pairs per GPU, %d keypoints (256-bit descriptors), "
+                            "%d 8-point hypotheses per pair, full match+RANSAC+decompose+triangulate"
+                            % (n_local, args.kp, args.hyp),
+                "pairs_per_gpu": n_local, "keypoints": args.kp, "hypotheses": args.hyp, "noise_px": args.noise_px,
+                "max_error_sq": args.max_error_sq, "parallelism": "pairs sharded, dp%d" % world,
+                "streams": 1 if args.one_stream else 2,
+                "launch_plan": ("every launch covers the rank's whole batch, one stream (--one-stream)" if args.one_stream else
+                                "the rank's batch runs as two independent halves on two HIP streams (mvs_ctx_set_half_batches, "
+                                "default): the latency-bound kernels of one half run under the throughput-bound kernels of "
+                                "the other; the per-kernel table and `roofline` time whole-batch launches on one stream"),
+                "threshold_note": "headline threshold 1e-2 (a consensus set exists: ~1100 inliers per pair, every stage "
+                                  "runs); SURVEY 8(d)'s literal 5e-2/K00/K11 is timed in `reference_threshold`",
+                "arithmetic_note": "results are the f64 contract's, bit for bit; the pre-screen's approximate F and the inlier "
+                                   "COUNT BOUNDS that decide which hypotheses are solved exactly are computed in f64 / binary32 "
+                                   "/ split bf16 (matrix cores) with certified error terms (DESIGN.md 4.3e)"},
+            "ranks_seen": ranks_seen,
+            "ms_per_step_ranks": {"min": round(min(rank_ms), 3), "max": round(max(rank_ms), 3)},
+        }
+        if gather_us is not None:
+            out["gather_us"] = gather_us
+            out["gather_note"] = "all-gather of the %d-byte pose records (%d per rank), timed with its own events inside the timed steps; max over ranks" % (rec_bytes, n_local)
+        if world > 1 and gathered is not None:
+            allrec = mdist.records_to_numpy(gathered, capi.RESULT_DTYPE)
+            out["work"] = {"gathered_records": int(len(allrec)), "gathered_valid": int(allrec["valid"].sum())}
+
+    if rank == 0 and args.full:
         # ---- per-kernel HIP-event timing on the kernels' own stream + work statistics (outside the timed region)
         _, kern_ms = batch.time(prm, steps=min(args.steps, 5), warmup=0)
         ksteps = min(args.steps, 5)
@@ -791,26 +869,7 @@ def main():
                 traffic_src = "recorded: profiles/%s (rocprofv3 --pmc pass of this workload; RANSAC stage, per launch " \
                               "sequence)" % tname
                 break
-        out = {
-            "metric": "image-pairs/sec (2k kp, 50k RANSAC hyp)", "value": round(value, 2), "unit": "pairs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {
-                "workload": "%d independent synthetic 640x480 pairs per GPU, %d keypoints (256-bit descriptors), "
-                            "%d 8-point hypotheses per pair, full match+RANSAC+decompose+triangulate"
-                            % (n_local, args.kp, args.hyp),
-                "pairs_per_gpu": n_local, "keypoints": args.kp, "hypotheses": args.hyp, "noise_px": args.noise_px,
-                "max_error_sq": args.max_error_sq, "parallelism": "pairs sharded, dp%d" % world,
-                "streams": 1 if args.one_stream else 2,
-                "launch_plan": ("every launch covers the rank's whole batch, one stream (--one-stream)" if args.one_stream else
-                                "the rank's batch runs as two independent halves on two HIP streams (mvs_ctx_set_half_batches, "
-                                "default): the latency-bound kernels of one half run under the throughput-bound kernels of "
-                                "the other; the per-kernel table and `roofline` time whole-batch launches on one stream"),
-                "threshold_note": "headline threshold 1e-2 (a consensus set exists: ~1100 inliers per pair, every stage "
-                                  "runs); SURVEY 8(d)'s literal 5e-2/K00/K11 is timed in `reference_threshold`",
-                "arithmetic_note": "results are the f64 contract's, bit for bit; the pre-screen's approximate F and the inlier "
-                                   "COUNT BOUNDS that decide which hypotheses are solved exactly are computed in f64 / binary32 "
-                                   "/ split bf16 (matrix cores) with certified error terms (DESIGN.md 4.3e)"},
+        out.update({
             "roofline": roofline_object(table, stats, traffic, traffic_src),
             "hbm_roofline": {
                 "achieved": round(bytes_pair * (n_local / (ms_per_step * 1e-3)) / 1e9, 3), "peak": HBM_PEAK_GBS,
@@ -821,20 +880,11 @@ def main():
             "kernel_ms_note": "stage times of whole-batch launches on one stream (events between the stages); with two half "
                               "batches on two streams (`ms_per_step`, the default) the stages of the halves overlap, so these do "
                               "not add up to the step",
-            "work": {"avg_matches": round(m_avg, 1), "avg_inliers": round(float(res["n_inliers"].mean()), 1),
-                     "avg_points": round(float(res["n_points"].mean()), 1), "valid_pairs": int(res["valid"].sum()),
-                     "rotations9_per_hyp": round(stats["rotations9"] / max(stats["hypotheses"], 1), 2),
-                     "pairs9_per_hyp": round(stats["pairs9"] / max(stats["hypotheses"], 1), 2)},
-            "ranks_seen": ranks_seen,
-            "ms_per_step_ranks": {"min": round(min(rank_ms), 3), "max": round(max(rank_ms), 3)},
-        }
-        if gather_us is not None:
-            out["gather_us"] = gather_us
-            out["gather_note"] = "all-gather of the %d-byte pose records (%d per rank), timed with its own events inside the timed steps; max over ranks" % (rec_bytes, n_local)
-        if world > 1 and gathered is not None:
-            allrec = mdist.records_to_numpy(gathered, capi.RESULT_DTYPE)
-            out["work"]["gathered_records"] = int(len(allrec))
-            out["work"]["gathered_valid"] = int(allrec["valid"].sum())
+            "work": dict({"avg_matches": round(m_avg, 1), "avg_inliers": round(float(res["n_inliers"].mean()), 1),
+                          "avg_points": round(float(res["n_points"].mean()), 1), "valid_pairs": int(res["valid"].sum()),
+                          "rotations9_per_hyp": round(stats["rotations9"] / max(stats["hypotheses"], 1), 2),
+                          "pairs9_per_hyp": round(stats["pairs9"] / max(stats["hypotheses"], 1), 2)}, **out.get("work", {})),
+        })
         # ---- the SURVEY 8(d) threshold (5e-2 / K00 / K11, sfm-solve.cpp:311: ~5 inliers, ties decided by the residual sum,
         # nothing to prune) with the same kernels: its own wall-clock loop, its own per-kernel table and roofline
         if args.max_error_sq > 0 and not args.no_ref_threshold and world == 1:
@@ -950,7 +1000,7 @@ def main():
 
     batch.close()
     ctx.close()
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if "sensitivity" in sections:
             out["sensitivity"] = bench_sensitivity(capi, synth, np, dev, args)
         if "sequence" in sections:
@@ -958,7 +1008,7 @@ def main():
         if "extract" in sections:
             out["extract"] = bench_extract(capi, np, dev, args)
     if rank == 0:
-        detail_rel = write_detail(out, args.detail)
+        detail_rel = write_detail(out, args.detail) if args.full else None
         if args.print_detail:
             print(json.dumps(out), flush=True)
         print(compact_line(out, detail_rel), flush=True)   # the LAST stdout line: what the driver parses

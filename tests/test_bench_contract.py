@@ -129,3 +129,80 @@ def test_committed_compact_line_of_this_round():
     assert abs(d["value"] - d["config"]["pairs_per_gpu"] / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
     assert d["cpu_baseline"]["kind"] == "port" and d["valid_pairs"] == d["config"]["pairs_per_gpu"]
     assert 0 < d["max_sweeps9"] <= 30
+
+
+class _FakeBatch:
+    """Stands in for capi.Batch in the --dump-outputs writer: download() in mvs_batch_download's layout, zero tails."""
+
+    def __init__(self, n_pairs, max_kp, seed=3):
+        from mvslam_amd import capi
+        import numpy as np
+
+        self.n_pairs, self.max_kp = n_pairs, max_kp
+        rng = np.random.default_rng(seed)
+        res = np.zeros(n_pairs, dtype=capi.RESULT_DTYPE)
+        res["valid"] = 1
+        res["n_matches"] = rng.integers(8, max_kp, n_pairs)
+        res["n_points"] = res["n_matches"] // 2
+        res["R"] = rng.normal(size=(n_pairs, 3, 3))
+        mt = np.zeros((n_pairs, max_kp), dtype=capi.MATCH_DTYPE)
+        mt["queryIdx"] = rng.integers(0, max_kp, mt.shape)
+        mt["distance"] = rng.integers(0, 11, mt.shape)
+        self.dl = dict(results=res, matches=mt, mask=rng.integers(0, 2, (n_pairs, max_kp)).astype(np.uint8),
+                       points=rng.normal(size=(n_pairs, max_kp, 3)),
+                       point_idx=rng.integers(0, max_kp, (n_pairs, max_kp)).astype(np.int64))
+
+    def download(self):
+        return self.dl
+
+
+def _read_dump(path):
+    import numpy as np
+
+    return {f[:-4]: np.load(os.path.join(path, f)) for f in sorted(os.listdir(path)) if f.endswith(".npy")}
+
+
+def test_dump_outputs_writes_every_array_exactly_in_float32_or_float64(tmp_path):
+    import sys
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    from mvslam_amd import capi
+
+    b = _FakeBatch(6, 40)
+    bench.dump_outputs(str(tmp_path / "d"), b, 100, np, capi)
+    d = _read_dump(str(tmp_path / "d"))
+    names = {"pair_index", "mask", "points", "point_idx"} | {"results_" + n for n in capi.RESULT_DTYPE.names} | \
+        {"matches_" + n for n in capi.MATCH_DTYPE.names}
+    assert set(d) == names
+    for k, a in d.items():
+        assert a.dtype in (np.float32, np.float64), k
+        assert len(a) == 6, k
+    assert np.array_equal(d["pair_index"], np.arange(100, 106))
+    for n in capi.RESULT_DTYPE.names:
+        assert np.array_equal(d["results_" + n], b.dl["results"][n]), n
+    for n in capi.MATCH_DTYPE.names:
+        assert np.array_equal(d["matches_" + n], b.dl["matches"][n]), n
+    for n in ("mask", "points", "point_idx"):
+        assert np.array_equal(d[n], b.dl[n]), n
+
+
+def test_dump_outputs_samples_a_large_batch_the_same_way_every_time(tmp_path, monkeypatch):
+    import sys
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    from mvslam_amd import capi
+
+    b = _FakeBatch(50, 40)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20000)
+    bench.dump_outputs(str(tmp_path / "a"), b, 0, np, capi)
+    bench.dump_outputs(str(tmp_path / "b"), b, 0, np, capi)
+    da, db = _read_dump(str(tmp_path / "a")), _read_dump(str(tmp_path / "b"))
+    assert 0 < sum(a.nbytes for a in da.values()) <= 20000
+    rows = da["pair_index"].astype(np.int64)
+    assert 0 < len(rows) < 50 and np.all(np.diff(rows) > 0)
+    for k in da:
+        assert np.array_equal(da[k], db[k]), k
+    assert np.array_equal(da["points"], b.dl["points"][rows])
+    assert np.array_equal(da["results_n_matches"], b.dl["results"]["n_matches"][rows])

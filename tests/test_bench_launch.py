@@ -84,7 +84,7 @@ def test_two_rank_bench_through_the_plain_entry_point():
     detail = os.path.join(tempfile.mkdtemp(prefix="mvs_bench_"), "detail.json")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--pairs", "8",
                         "--hyp", "512", "--kp", "500", "--steps", "2", "--warmup", "1", "--launch-timeout", "600",
-                        "--detail", detail],
+                        "--detail", detail, "--full"],
                        env=env, cwd=ROOT, timeout=900, capture_output=True, text=True)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [ln for ln in p.stdout.splitlines() if ln.strip()][-1]      # the LAST stdout line is the compact one
@@ -102,3 +102,37 @@ def test_two_rank_bench_through_the_plain_entry_point():
     r = full["ms_per_step_ranks"]
     assert 0 < r["min"] <= r["max"] and abs(r["max"] - d["ms_per_step"]) < 0.5 * d["ms_per_step"] + 1.0
     assert "cpu_baseline" not in full
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_prints_the_headline_and_dumps_the_same_outputs_every_time():
+    """A plain run (no --full): the line carries the headline fields with the side legs null, writes no detail file, and
+    --dump-outputs writes the last timed step's outputs -- identical in two runs with the same arguments."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    tmp = tempfile.mkdtemp(prefix="mvs_bench_")
+    detail = os.path.join(tmp, "detail.json")
+    dumps = []
+    for run in range(2):
+        dump = os.path.join(tmp, "out%d" % run)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--pairs", "8", "--hyp", "512",
+                            "--kp", "500", "--steps", "3", "--warmup", "1", "--detail", detail, "--dump-outputs", dump],
+                           env=env, cwd=ROOT, timeout=600, capture_output=True, text=True)
+        assert p.returncode == 0, p.stderr[-2000:]
+        d = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][-1])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["dtype"] == "f64"
+        assert d["unit"] == "pairs/s" and d["higher_is_better"] is True and d["ms_per_step"] > 0
+        assert abs(d["value"] - 8 / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
+        assert d["cpu_baseline"] is None and d["sequence_frames_per_s"] is None and d["roofline"]["bound"] is None
+        assert d["detail"] is None and not os.path.exists(detail)
+        files = sorted(f for f in os.listdir(dump) if f.endswith(".npy"))
+        arrays = {f: np.load(os.path.join(dump, f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 * 10 ** 6
+        assert arrays["results_valid.npy"].shape == (8,) and arrays["results_valid.npy"].sum() > 0
+        assert arrays["points.npy"].shape == (8, 500, 3)
+        dumps.append(arrays)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

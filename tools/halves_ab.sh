@@ -2,7 +2,7 @@
 # A/B on the GPU box: half batches on two streams (default) against every launch on one stream (bench.py --one-stream),
 # alternating, + a kernel trace of the default for the timeline.  bash tools/halves_ab.sh [repeats]
 export TMPDIR=/tmp
-B="python3 bench.py --no-cpu-baseline --no-single-pair --no-pcie --no-ref-threshold --sections main,sequence"
+B="python3 bench.py --full --no-cpu-baseline --no-single-pair --no-pcie --no-ref-threshold --sections main,sequence"
 for ((i = 0; i < ${1:-2}; i++)); do
   for V in "" "--one-stream"; do
     $B $V > gpurun_out/hab.json 2> gpurun_out/hab.err || exit 1

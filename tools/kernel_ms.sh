@@ -1,7 +1,7 @@
 #!/bin/bash
 # per-kernel ms of whole-batch launches (bench.py's own HIP-event table), two repeats: bash tools/kernel_ms.sh [pattern]
 for i in 1 2; do
-python3 bench.py --no-cpu-baseline --no-single-pair --no-pcie --no-ref-threshold --sections main 2>/dev/null | python3 -c "
+python3 bench.py --full --no-cpu-baseline --no-single-pair --no-pcie --no-ref-threshold --sections main 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 pk = d['roofline']['per_kernel']
