@@ -7,6 +7,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -14,6 +16,21 @@
 #include "kernels.hpp"
 
 using namespace mvs;
+
+// ---- device memory: every block has one owner, whose destructor frees it ---------------------------------------------
+struct HipFree {
+    void operator()(void *p) const { (void)hipFree(p); }
+};
+using DevPtr = std::unique_ptr<void, HipFree>;
+// the blocks of a batch, a sequence or a probe's temporaries, allocated group by group (DevGroup)
+using DevBlocks = std::vector<DevPtr>;
+// one grow-only workspace of a context (ws_grow)
+struct DevWorkspace {
+    DevPtr p;
+    size_t bytes = 0;
+    template <typename T = char>
+    T *ptr() const { return static_cast<T *>(p.get()); }
+};
 
 struct mvs_ctx {
     int device = 0;
@@ -28,20 +45,15 @@ struct mvs_ctx {
     int cu_count = 256;   // hipDeviceAttributeMultiprocessorCount of `device` (mvs_ctx_create); MI355X: 256
     std::string err;
     mvs_batch *scratch = nullptr;  // batch of one pair backing the single-shot entry points
-    double *d_uv1 = nullptr, *d_uv2 = nullptr;
-    int uv_cap = 0;
-    double *d_small = nullptr;  // 64 doubles of staging (fundamental_kernel)
-    unsigned char *d_single = nullptr;   // gathered outputs of a single-shot call (one device-to-host copy)
-    size_t single_cap = 0;
-    unsigned char *d_single_in = nullptr;   // packed inputs of mvs_image_pair (one host-to-device copy)
-    size_t single_in_cap = 0;
-    void *d_pnp = nullptr;      // pnp_solve workspace
-    size_t pnp_bytes = 0;
-    void *d_ref = nullptr;      // sfm_refine / pnp_refine workspace
-    size_t ref_bytes = 0;
-    void *d_orb = nullptr;      // extraction workspace
+    // workspaces, freed by their destructors
+    DevWorkspace uv;          // image points of a single-shot call: [max_kp][2] of camera 1, then the same of camera 2
+    DevWorkspace small;       // 64 doubles of staging (fundamental_kernel)
+    DevWorkspace single;      // gathered outputs of a single-shot call (one device-to-host copy)
+    DevWorkspace single_in;   // packed inputs of mvs_image_pair (one host-to-device copy)
+    DevWorkspace pnp;         // pnp_solve workspace
+    DevWorkspace ref;         // sfm_refine / pnp_refine workspace
+    DevWorkspace orb;         // extraction workspace: orb_graph points into it
     int32_t *h_orb_ovf = nullptr;   // pinned: the extraction's overflow flag travels with the outputs (one stream wait per call)
-    size_t orb_bytes = 0;
     bool orb_ready = false;
     // the ~50 launches of one extraction, captured once per (batch shape, parameters, buffers) and replayed
     hipGraphExec_t orb_graph = nullptr;
@@ -60,14 +72,15 @@ struct mvs_seq;
 struct mvs_batch {
     mvs_ctx *ctx = nullptr;
     BatchDev d{};
-    std::vector<void *> allocs;
+    DevBlocks blocks;
     double *uv1 = nullptr, *uv2 = nullptr;   // [n_pairs][max_kp][2] staging of mvs_batch_run_points (first use)
-    int hyp_table_cap = 0;  // capacity of the optional per-hypothesis tables
-    int32_t *allocs_hc = nullptr;
-    double *allocs_hr = nullptr;
+    // the optional per-hypothesis tables of mvs_ransac_fundamental (d.hyp_count / d.hyp_residual during that call only)
+    int hyp_table_cap = 0;
+    int32_t *hyp_table_count = nullptr;
+    double *hyp_table_residual = nullptr;
     hipEvent_t ev[8]{};
     RefineDev refine{};     // allocated by the first mvs_batch_refine
-    bool refine_ready = false, refine_ran = false;
+    bool refine_ran = false;
     // pinned staging of the per-pair parameters derived on the host (K^-1, default indices): two slot sets used in turn,
     // each guarded by an event recorded behind its copies, so an asynchronous upload waits for the copies of the upload
     // before last at most -- never for the kernels or downloads queued on the stream in between
@@ -80,13 +93,13 @@ struct mvs_batch {
 struct mvs_seq {
     mvs_ctx *ctx = nullptr;
     mvs_batch *batch = nullptr;  // n_frames - 1 pairs viewing the frame arrays
-    int n_frames = 0, n_tracks = 0, stride = 0, rec_groups = 0;
+    int n_frames = 0, n_tracks = 0, stride = 0;
     SeqJoinDev join{};
     PnpDev pnp{};
     SeqChainDev chain{};
     RefineDev refit{};          // pnp_solve's refit over the inliers of every track (mvs_pnp_params.refit), allocated on demand
-    bool refit_ready = false, refit_on = false;
-    std::vector<void *> allocs;
+    bool refit_on = false;
+    DevBlocks blocks;
 };
 
 #define HIP_TRY(ctx_, expr)                                                                    \
@@ -198,42 +211,94 @@ static void mat3_inverse(const double *K, double *inv)
 
 static bool affine_K(const double *K) { return K[6] == 0.0 && K[7] == 0.0 && K[8] == 1.0 && K[0] != 0.0 && K[4] != 0.0; }
 
-template <typename T>
-static mvs_status dev_alloc(mvs_batch *b, T **ptr, size_t count)
-{
-    void *p = nullptr;
-    HIP_TRY(b->ctx, hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
-    b->allocs.push_back(p);
-    *ptr = static_cast<T *>(p);
-    return MVS_OK;
-}
-
-template <typename T>
-static mvs_status seq_alloc(mvs_seq *q, T **ptr, size_t count)
-{
-    void *p = nullptr;
-    HIP_TRY(q->ctx, hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
-    q->allocs.push_back(p);
-    *ptr = static_cast<T *>(p);
-    return MVS_OK;
-}
-
-// release one block of a batch early (superseded by a larger one); the stream must be idle
-static void dev_release(mvs_batch *b, void *p)
-{
-    if (!p)
-        return;
-    for (size_t i = 0; i < b->allocs.size(); ++i)
-        if (b->allocs[i] == p) {
-            b->allocs.erase(b->allocs.begin() + i);
-            (void)hipFree(p);
-            return;
+// One all-or-nothing group of device blocks for an owner.  add() allocates max(count, 1) elements for a destination
+// pointer (nothing more after a failure); commit() then either reports the failure -- the partial blocks are freed, no
+// pointer has changed -- or points every destination at its new block, hands the blocks to the owner and only then frees
+// the owner's blocks they supersede (the stream must be idle for that).
+class DevGroup {
+public:
+    DevGroup(mvs_ctx *ctx, DevBlocks &owner) : ctx_(ctx), owner_(owner) {}
+    template <typename T>
+    DevGroup &add(T *&dst, size_t count)
+    {
+        void *p = nullptr;
+        if (e_ == hipSuccess && (e_ = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T))) == hipSuccess)
+            parts_.emplace_back(DevPtr(p), [&dst](void *q) -> const void * {
+                const void *old = dst;
+                dst = static_cast<T *>(q);
+                return old;
+            });
+        return *this;
+    }
+    mvs_status commit()
+    {
+        if (e_ != hipSuccess) {
+            ctx_->err = std::string("hipMalloc: ") + hipGetErrorString(e_);
+            return MVS_ERR_HIP;
         }
+        std::vector<const void *> old;
+        for (auto &part : parts_) {
+            old.push_back(part.second(part.first.get()));
+            owner_.push_back(std::move(part.first));
+        }
+        for (const void *o : old)
+            for (auto it = owner_.begin(); o && it != owner_.end(); ++it)
+                if (it->get() == o) {
+                    owner_.erase(it);
+                    break;
+                }
+        return MVS_OK;
+    }
+
+private:
+    mvs_ctx *ctx_;
+    DevBlocks &owner_;
+    hipError_t e_ = hipSuccess;
+    std::vector<std::pair<DevPtr, std::function<const void *(void *)>>> parts_;
+};
+
+// Grows a context workspace to at least `bytes` (first size: max(bytes, floor)).  Growing waits for the ctx stream, frees
+// the old block and marks the workspace empty before it allocates: a failed growth leaves no block behind.
+static mvs_status ws_grow(mvs_ctx *ctx, DevWorkspace &w, size_t bytes, size_t floor = 0)
+{
+    if (w.bytes >= bytes)
+        return MVS_OK;
+    HIP_TRY(ctx, sync_stream(ctx));
+    w.p.reset();
+    w.bytes = 0;
+    void *p = nullptr;
+    HIP_TRY(ctx, hipMalloc(&p, std::max(bytes, floor)));
+    w.p.reset(p);
+    w.bytes = std::max(bytes, floor);
+    return MVS_OK;
 }
 
-// per-hypothesis buffers of the RANSAC stage, sized for the largest hypothesis count seen so far.  All new blocks are
-// allocated before any pointer is switched (a failed allocation leaves the batch as it was, its partial blocks owned by
-// allocs until destroy); the superseded blocks are freed at once: 77 B x hypotheses x pairs is 2 GB at the bench size.
+// the captured extraction graph points into the extraction workspace: dropped before that block is freed or replaced
+static void drop_orb_graph(mvs_ctx *ctx)
+{
+    if (ctx->orb_graph)
+        (void)hipGraphExecDestroy(ctx->orb_graph);
+    ctx->orb_graph = nullptr;
+    ctx->orb_graph_valid = false;
+}
+
+// Layout of a workspace as consecutive parts: take() returns the offset of the next part, rounded up to `align` (a power of
+// two); end is where the last part ends, total() the same rounded up.
+struct Carve {
+    size_t align, end = 0;
+    size_t up(size_t x) const { return (x + align - 1) & ~(align - 1); }
+    size_t take(size_t bytes)
+    {
+        const size_t o = up(end);
+        end = o + bytes;
+        return o;
+    }
+    size_t total() const { return up(end); }
+};
+
+// per-hypothesis buffers of the RANSAC stage, sized for the largest hypothesis count seen so far: one group, so a failed
+// allocation leaves the batch as it was; the superseded blocks are freed at once: 77 B x hypotheses x pairs is 2 GB at the
+// bench size.
 static mvs_status ensure_groups(mvs_batch *b, int num_hypotheses)
 {
     const int G = (num_hypotheses + kHypPerBlock - 1) / kHypPerBlock;
@@ -243,47 +308,61 @@ static mvs_status ensure_groups(mvs_batch *b, int num_hypotheses)
     const size_t P = (size_t)b->d.n_pairs, Hp = (size_t)G * kHypPerBlock;
     if (P * Hp >= (size_t(1) << 32))
         return MVS_ERR_CAPACITY;   // the exact solve's work list holds flat 32-bit record indices
-    WgBest *p = nullptr;
-    double *hf = nullptr;   // record of every hypothesis (F + counting threshold): 80 B x hypotheses x pairs
-    uint8_t *ho = nullptr;
-    int32_t *hc = nullptr;
-    uint32_t *xl = nullptr;
-    float *h32 = nullptr;   // single-precision pre-screen records (mode 1): 48 B x hypotheses x pairs
-    mvs_status st;
-    if ((st = dev_alloc(b, &p, P * G)) != MVS_OK) return st;
-    if ((st = dev_alloc(b, &hf, P * kHypRec * Hp)) != MVS_OK) return st;
-    if ((st = dev_alloc(b, &h32, P * kHypRec32 * Hp)) != MVS_OK) return st;
-    if ((st = dev_alloc(b, &ho, P * Hp)) != MVS_OK) return st;
-    if ((st = dev_alloc(b, &hc, P * Hp)) != MVS_OK) return st;
-    if ((st = dev_alloc(b, &xl, P * Hp)) != MVS_OK) return st;
-    uint32_t *cl = nullptr;
-    if ((st = dev_alloc(b, &cl, 2 * P * Hp)) != MVS_OK) return st;   // the list + its sorted copy
-    if (!b->d.bound && (st = dev_alloc(b, &b->d.bound, P)) != MVS_OK) return st;
-    if (!b->d.box && (st = dev_alloc(b, &b->d.box, P * 8)) != MVS_OK) return st;
-    if (!b->d.mode && (st = dev_alloc(b, &b->d.mode, P)) != MVS_OK) return st;
-    if (!b->d.dense_n1 && (st = dev_alloc(b, &b->d.dense_n1, P)) != MVS_OK) return st;
-    if (!b->d.ccount && (st = dev_alloc(b, &b->d.ccount, P)) != MVS_OK) return st;
-    if (!b->d.pcount && (st = dev_alloc(b, &b->d.pcount, P)) != MVS_OK) return st;
-    if (!b->d.cpos && (st = dev_alloc(b, &b->d.cpos, P * kSortBins)) != MVS_OK) return st;
-    if (!b->d.m0list && (st = dev_alloc(b, &b->d.m0list, 2 * (P + 1))) != MVS_OK) return st;   // one list per half (batch_view)
-    if (!b->d.xcount && (st = dev_alloc(b, &b->d.xcount, 4)) != MVS_OK) return st;
-    dev_release(b, b->d.wgbest);
-    dev_release(b, b->d.hyp_F);
-    dev_release(b, b->d.hyp_r32);
-    dev_release(b, b->d.hyp_okf);
-    dev_release(b, b->d.hyp_cnt);
-    dev_release(b, b->d.xlist);
-    dev_release(b, b->d.clist);
-    b->d.wgbest = p;
-    b->d.hyp_F = hf;
-    b->d.hyp_r32 = h32;
-    b->d.hyp_okf = ho;
-    b->d.hyp_cnt = hc;
-    b->d.xlist = xl;
-    b->d.clist = cl;
-    b->d.clist2 = cl + P * Hp;
-    b->d.max_groups = G;
+    BatchDev &d = b->d;
+    DevGroup g(b->ctx, b->blocks);
+    g.add(d.wgbest, P * G);
+    g.add(d.hyp_F, P * kHypRec * Hp);       // record of every hypothesis (F + counting threshold): 80 B x hypotheses x pairs
+    g.add(d.hyp_r32, P * kHypRec32 * Hp);   // single-precision pre-screen records (mode 1): 48 B x hypotheses x pairs
+    g.add(d.hyp_okf, P * Hp);
+    g.add(d.hyp_cnt, P * Hp);
+    g.add(d.xlist, P * Hp);
+    g.add(d.clist, 2 * P * Hp);   // the list + its sorted copy
+    if (!d.bound) g.add(d.bound, P);
+    if (!d.box) g.add(d.box, P * 8);
+    if (!d.mode) g.add(d.mode, P);
+    if (!d.dense_n1) g.add(d.dense_n1, P);
+    if (!d.ccount) g.add(d.ccount, P);
+    if (!d.pcount) g.add(d.pcount, P);
+    if (!d.cpos) g.add(d.cpos, P * kSortBins);
+    if (!d.m0list) g.add(d.m0list, 2 * (P + 1));   // one list per half (batch_view)
+    if (!d.xcount) g.add(d.xcount, 4);
+    const mvs_status st = g.commit();
+    if (st != MVS_OK)
+        return st;
+    d.clist2 = d.clist + P * Hp;
+    d.max_groups = G;
     return MVS_OK;
+}
+
+// the device arrays of `problems` refinement problems of `stride` points seen by `frames` frames (two: the batch's
+// problems, with marginal covariances; one: a sequence's refit), allocated as one group; K is the caller's
+static mvs_status alloc_refine(mvs_ctx *ctx, DevBlocks &owner, RefineDev &d, int problems, int stride, int frames,
+                               const double *K)
+{
+    const size_t T = problems, S = stride;
+    RefineDev r{};
+    r.n_problems = problems;
+    r.stride = stride;
+    r.n_frames = frames;
+    r.K = K;
+    DevGroup g(ctx, owner);
+    for (int f = 0; f < frames; ++f) {
+        g.add(r.obs[f], T * S * 2);
+        g.add(r.oinfo[f], T * S * 3);
+    }
+    g.add(r.pts0, T * S * 3);
+    g.add(r.pinfo, T * S * 6);
+    g.add(r.pts, T * S * 3);
+    g.add(r.pts_tmp, T * S * 3);
+    if (frames == 2)
+        g.add(r.point_cov, T * S * 9);
+    g.add(r.pose0, T * 12);
+    g.add(r.m, T);
+    g.add(r.out, T);
+    const mvs_status st = g.commit();
+    if (st == MVS_OK)
+        d = r;
+    return st;
 }
 
 #ifdef MVS_DEBUG_HOOKS
@@ -293,10 +372,15 @@ static int probe_io(mvs_ctx *ctx, const void *const *in, const size_t *in_bytes,
                     int n_out, Launch launch)
 {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void *d[8] = {};
+    unsigned char *d[8] = {};
+    DevBlocks tmp;
+    DevGroup g(ctx, tmp);
+    for (int k = 0; k < n_in + n_out; ++k)
+        g.add(d[k], k < n_in ? in_bytes[k] : out_bytes[k - n_in]);
+    const mvs_status st = g.commit();
+    if (st != MVS_OK)
+        return st;
     hipError_t e = hipSuccess;
-    for (int k = 0; k < n_in + n_out && e == hipSuccess; ++k)
-        e = hipMalloc(&d[k], k < n_in ? in_bytes[k] : out_bytes[k - n_in]);
     for (int k = 0; k < n_in && e == hipSuccess; ++k)
         e = hipMemcpy(d[k], in[k], in_bytes[k], hipMemcpyHostToDevice);
     if (e == hipSuccess) {
@@ -307,9 +391,6 @@ static int probe_io(mvs_ctx *ctx, const void *const *in, const size_t *in_bytes,
         e = sync_stream(ctx);
     for (int k = 0; k < n_out && e == hipSuccess; ++k)
         e = hipMemcpy(outp[k], d[n_in + k], out_bytes[k], hipMemcpyDeviceToHost);
-    for (int k = 0; k < n_in + n_out; ++k)
-        if (d[k])
-            (void)hipFree(d[k]);
     if (e != hipSuccess) {
         ctx->err = std::string("probe: ") + hipGetErrorString(e);
         return MVS_ERR_HIP;
@@ -337,18 +418,16 @@ int mvs_debug_fastmath_check(mvs_ctx *ctx, const double *x, const double *y, int
     double *dx = nullptr, *dy = nullptr;
     unsigned long long *dc = nullptr;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMalloc((void **)&dx, (size_t)n * 8));
-    HIP_TRY(ctx, hipMalloc((void **)&dy, (size_t)n * 8));
-    HIP_TRY(ctx, hipMalloc((void **)&dc, 32));
+    DevBlocks tmp;
+    const mvs_status st = DevGroup(ctx, tmp).add(dx, n).add(dy, n).add(dc, 4).commit();
+    if (st != MVS_OK)
+        return st;
     HIP_TRY(ctx, hipMemcpyAsync(dx, x, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(dy, y, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(dc, 0, 32, ctx->stream));
     launch_fastmath_check(dx, dy, n, dc, ctx->stream);
     HIP_TRY(ctx, hipMemcpyAsync(counts, dc, 32, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, sync_stream(ctx));
-    (void)hipFree(dx);
-    (void)hipFree(dy);
-    (void)hipFree(dc);
     return MVS_OK;
 }
 
@@ -362,11 +441,10 @@ int mvs_debug_pairstep_check(mvs_ctx *ctx, const double *rows, int n, unsigned l
     double *dr = nullptr;
     unsigned long long *dc = nullptr;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMalloc((void **)&dr, (size_t)n * 48));
-    if (hipMalloc((void **)&dc, 32) != hipSuccess) {
-        (void)hipFree(dr);
-        return MVS_ERR_HIP;
-    }
+    DevBlocks tmp;
+    const mvs_status st = DevGroup(ctx, tmp).add(dr, (size_t)n * 6).add(dc, 4).commit();
+    if (st != MVS_OK)
+        return st;
     hipError_t e = hipMemcpyAsync(dr, rows, (size_t)n * 48, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess)
         e = hipMemsetAsync(dc, 0, 32, ctx->stream);
@@ -376,8 +454,6 @@ int mvs_debug_pairstep_check(mvs_ctx *ctx, const double *rows, int n, unsigned l
     }
     if (e == hipSuccess)
         e = sync_stream(ctx);
-    (void)hipFree(dr);
-    (void)hipFree(dc);
     return e == hipSuccess ? MVS_OK : MVS_ERR_HIP;
 }
 
@@ -405,18 +481,16 @@ int mvs_debug_mfma_probe(mvs_ctx *ctx, const uint16_t *a, const uint16_t *b, flo
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint16_t *da = nullptr, *db = nullptr;
     float *dout = nullptr;
-    HIP_TRY(ctx, hipMalloc(&da, 1024 * sizeof(uint16_t)));
-    HIP_TRY(ctx, hipMalloc(&db, 1024 * sizeof(uint16_t)));
-    HIP_TRY(ctx, hipMalloc(&dout, 1024 * sizeof(float)));
+    DevBlocks tmp;
+    const mvs_status st = DevGroup(ctx, tmp).add(da, 1024).add(db, 1024).add(dout, 1024).commit();
+    if (st != MVS_OK)
+        return st;
     HIP_TRY(ctx, hipMemcpy(da, a, 1024 * sizeof(uint16_t), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(db, b, 1024 * sizeof(uint16_t), hipMemcpyHostToDevice));
     launch_mfma_probe(da, db, dout, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, sync_stream(ctx));
     HIP_TRY(ctx, hipMemcpy(out, dout, 1024 * sizeof(float), hipMemcpyDeviceToHost));
-    (void)hipFree(da);
-    (void)hipFree(db);
-    (void)hipFree(dout);
     return MVS_OK;
 }
 
@@ -514,11 +588,9 @@ int mvs_debug_audit(mvs_batch *b, const mvs_params *params, int n_active, int ph
     const RunParams rp = to_run(*params);
     unsigned long long *dc = nullptr;
     int32_t *dm = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&dc, 16 * sizeof(unsigned long long)));
-    if (hipMalloc((void **)&dm, (size_t)n_active * sizeof(int32_t)) != hipSuccess) {
-        (void)hipFree(dc);
-        return MVS_ERR_HIP;
-    }
+    DevBlocks tmp;
+    if ((st = DevGroup(ctx, tmp).add(dc, 16).add(dm, n_active).commit()) != MVS_OK)
+        return st;
     hipError_t e = hipMemsetAsync(dc, 0, 16 * sizeof(unsigned long long), ctx->stream);
     if (e == hipSuccess)
         e = hipMemsetAsync(dm, 0xff, (size_t)n_active * sizeof(int32_t), ctx->stream);
@@ -536,8 +608,6 @@ int mvs_debug_audit(mvs_batch *b, const mvs_params *params, int n_active, int ph
         e = hipMemcpy(bound, b->d.bound, (size_t)n_active * sizeof(int32_t), hipMemcpyDeviceToHost);
     if (e == hipSuccess && mode)
         e = hipMemcpy(mode, b->d.mode, (size_t)n_active * sizeof(int32_t), hipMemcpyDeviceToHost);
-    (void)hipFree(dc);
-    (void)hipFree(dm);
     if (e != hipSuccess) {
         ctx->err = std::string("mvs_debug_audit: ") + hipGetErrorString(e);
         return MVS_ERR_HIP;
@@ -571,11 +641,10 @@ int mvs_debug_audit_state(mvs_ctx *ctx, const void *state, size_t state_bytes, c
     const RunParams rp = to_run(*params);
     unsigned long long *dc = nullptr;
     int32_t *dm = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&dc, 16 * sizeof(unsigned long long)));
-    if (hipMalloc((void **)&dm, (size_t)n_active * sizeof(int32_t)) != hipSuccess) {
-        (void)hipFree(dc);
-        return MVS_ERR_HIP;
-    }
+    DevBlocks tmp;
+    const mvs_status st = DevGroup(ctx, tmp).add(dc, 16).add(dm, n_active).commit();
+    if (st != MVS_OK)
+        return st;
     hipError_t e = hipMemsetAsync(dc, 0, 16 * sizeof(unsigned long long), ctx->stream);
     if (e == hipSuccess)
         e = hipMemsetAsync(dm, 0xff, (size_t)n_active * sizeof(int32_t), ctx->stream);
@@ -591,8 +660,6 @@ int mvs_debug_audit_state(mvs_ctx *ctx, const void *state, size_t state_bytes, c
         e = hipMemcpy(bound, d.bound, (size_t)n_active * sizeof(int32_t), hipMemcpyDeviceToHost);
     if (e == hipSuccess && mode)
         e = hipMemcpy(mode, d.mode, (size_t)n_active * sizeof(int32_t), hipMemcpyDeviceToHost);
-    (void)hipFree(dc);
-    (void)hipFree(dm);
     if (e != hipSuccess) {
         ctx->err = std::string("mvs_debug_audit_state: ") + hipGetErrorString(e);
         return MVS_ERR_HIP;
@@ -646,11 +713,13 @@ int mvs_debug_count_only(mvs_batch *b, const mvs_params *params, int n_active, i
         return st;
     const size_t Hp = (size_t)b->d.max_groups * kHypPerBlock;
     int32_t *dk = nullptr;
+    DevBlocks tmp;
     if (keep) {
         for (int p = 0; p < n_active; ++p)
             if (keep[p] >= (int32_t)Hp)
                 return MVS_ERR_INVALID_ARG;
-        HIP_TRY(ctx, hipMalloc((void **)&dk, (size_t)n_active * sizeof(int32_t)));
+        if ((st = DevGroup(ctx, tmp).add(dk, n_active).commit()) != MVS_OK)
+            return st;
         HIP_TRY(ctx, hipMemcpy(dk, keep, (size_t)n_active * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     HIP_TRY(ctx, hipMemsetAsync(b->d.dense_n1, 0, (size_t)n_active * sizeof(int32_t), ctx->stream));
@@ -666,8 +735,6 @@ int mvs_debug_count_only(mvs_batch *b, const mvs_params *params, int n_active, i
         e = hipMemcpy(bound_out, b->d.bound, (size_t)n_active * sizeof(int32_t), hipMemcpyDeviceToHost);
     if (e == hipSuccess && n1_out)
         e = hipMemcpy(n1_out, b->d.dense_n1, (size_t)n_active * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (dk)
-        (void)hipFree(dk);
     if (e != hipSuccess) {
         ctx->err = std::string("mvs_debug_count_only: ") + hipGetErrorString(e);
         return MVS_ERR_HIP;
@@ -686,7 +753,7 @@ int mvs_debug_indicator_probe(mvs_ctx *ctx, const float *a, const float *tu, con
     const size_t ib[4] = {nb, nb, nb, nb};
     void *out[3] = {ind_u, ind_l, scale};
     const size_t ob[3] = {nb, nb, nb};
-    return probe_io(ctx, in, ib, 4, out, ob, 3, [&](void **d) {
+    return probe_io(ctx, in, ib, 4, out, ob, 3, [&](unsigned char **d) {
         launch_indicator_probe((const float *)d[0], (const float *)d[1], (const float *)d[2], (const float *)d[3], n, (float *)d[4],
                                (float *)d[5], (float *)d[6], ctx->stream);
     });
@@ -702,7 +769,7 @@ int mvs_debug_rounding_probe(mvs_ctx *ctx, const double *in19, int n, double *ou
     void *out[1] = {out2};
     const size_t ob[1] = {(size_t)n * 2 * sizeof(double)};
     return probe_io(ctx, in, ib, 1, out, ob, 1,
-                    [&](void **d) { launch_rounding_probe((const double *)d[0], n, (double *)d[1], ctx->stream); });
+                    [&](unsigned char **d) { launch_rounding_probe((const double *)d[0], n, (double *)d[1], ctx->stream); });
 }
 #endif  // MVS_DEBUG_HOOKS
 
@@ -778,7 +845,7 @@ mvs_status mvs_ctx_create_on_stream(int device_id, void *hip_stream, mvs_ctx **o
             return MVS_ERR_NO_DEVICE;
         }
     }
-    if (hipMalloc((void **)&c->d_small, 64 * sizeof(double)) != hipSuccess ||
+    if (ws_grow(c, c->small, 64 * sizeof(double)) != MVS_OK ||
         hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
@@ -799,15 +866,7 @@ void mvs_ctx_destroy(mvs_ctx *ctx)
     (void)sync_stream(ctx);
     if (ctx->scratch)
         mvs_batch_destroy(ctx->scratch);
-    if (ctx->d_uv1) (void)hipFree(ctx->d_uv1);
-    if (ctx->d_uv2) (void)hipFree(ctx->d_uv2);
-    if (ctx->d_small) (void)hipFree(ctx->d_small);
-    if (ctx->d_pnp) (void)hipFree(ctx->d_pnp);
-    if (ctx->d_ref) (void)hipFree(ctx->d_ref);
-    if (ctx->d_single) (void)hipFree(ctx->d_single);
-    if (ctx->d_single_in) (void)hipFree(ctx->d_single_in);
-    if (ctx->orb_graph) (void)hipGraphExecDestroy(ctx->orb_graph);
-    if (ctx->d_orb) (void)hipFree(ctx->d_orb);
+    drop_orb_graph(ctx);
     if (ctx->h_orb_ovf) (void)hipHostFree(ctx->h_orb_ovf);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
     if (ctx->side) {
@@ -818,7 +877,7 @@ void mvs_ctx_destroy(mvs_ctx *ctx)
     if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
     if (ctx->own_stream)
         (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;   // the workspaces' destructors free them
 }
 
 void *mvs_ctx_stream(mvs_ctx *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
@@ -861,75 +920,55 @@ static mvs_status batch_create_impl(mvs_ctx *ctx, int n_pairs, int max_kp, int d
     d.max_groups = 0;
     d.cu_count = ctx->cu_count;
     const size_t P = n_pairs, N = max_kp;
-    mvs_status st = MVS_OK;
-    uint32_t *desc1, *desc2;
-    float *kp1, *kp2;
-    uint8_t *oct1, *oct2;
-    int32_t *n1, *n2;
-    double *Kinv, *K;
-    int64_t *gidx;
-#define ALLOC(ptr, cnt)                                \
-    if (st == MVS_OK) st = dev_alloc(b, &(ptr), (cnt));
+    uint32_t *desc1 = nullptr, *desc2 = nullptr;
+    float *kp1 = nullptr, *kp2 = nullptr;
+    uint8_t *oct1 = nullptr, *oct2 = nullptr;
+    int32_t *n1 = nullptr, *n2 = nullptr;
+    double *Kinv = nullptr, *K = nullptr;
+    int64_t *gidx = nullptr;
     const size_t NI = n_frames ? (size_t)n_frames : P;  // images held by desc1 / kp1 / n1
-    ALLOC(desc1, NI * N * d.desc_words);
-    ALLOC(kp1, NI * N * 2);
-    ALLOC(oct1, NI * N);
-    ALLOC(n1, NI);
+    DevGroup g(ctx, b->blocks);
+    g.add(desc1, NI * N * d.desc_words);
+    g.add(kp1, NI * N * 2);
+    g.add(oct1, NI * N);
+    g.add(n1, NI);
+    if (!n_frames) {
+        g.add(desc2, P * N * d.desc_words);
+        g.add(kp2, P * N * 2);
+        g.add(oct2, P * N);
+        g.add(n2, P);
+    }
+    g.add(Kinv, P * 9);
+    g.add(K, P * 9);
+    g.add(gidx, P);
+    g.add(d.knn_train, P * N);
+    g.add(d.knn_dist, P * N);
+    g.add(d.M, P);
+    g.add(d.matches, P * N);
+    g.add(d.pts, P * N * 4);
+    g.add(d.cand_pts, P * 4 * N * 3);
+    g.add(d.fin, P);
+    g.add(d.inl, P * N);
+    g.add(d.okf, P * 4 * N);
+    g.add(d.results, P);
+    g.add(d.mask, P * N);
+    g.add(d.points, P * N * 3);
+    g.add(d.point_idx, P * N);
+    g.add(d.stats, 16);
+    const mvs_status st = g.commit();
+    if (st != MVS_OK) {
+        mvs_batch_destroy(b);
+        return st;
+    }
     if (n_frames) {  // pair k's second image is frame k + 1
         desc2 = desc1 + N * d.desc_words;
         kp2 = kp1 + N * 2;
         oct2 = oct1 + N;
         n2 = n1 + 1;
-    } else {
-        ALLOC(desc2, P * N * d.desc_words);
-        ALLOC(kp2, P * N * 2);
-        ALLOC(oct2, P * N);
-        ALLOC(n2, P);
-    }
-    ALLOC(Kinv, P * 9);
-    ALLOC(K, P * 9);
-    ALLOC(gidx, P);
-    ALLOC(d.knn_train, P * N);
-    ALLOC(d.knn_dist, P * N);
-    ALLOC(d.M, P);
-    ALLOC(d.matches, P * N);
-    ALLOC(d.pts, P * N * 4);
-    ALLOC(d.cand_pts, P * 4 * N * 3);
-    ALLOC(d.fin, P);
-    ALLOC(d.inl, P * N);
-    ALLOC(d.okf, P * 4 * N);
-    ALLOC(d.results, P);
-    ALLOC(d.mask, P * N);
-    ALLOC(d.points, P * N * 3);
-    ALLOC(d.point_idx, P * N);
-    ALLOC(d.stats, 16);
-#undef ALLOC
-    if (st != MVS_OK) {
-        mvs_batch_destroy(b);
-        return st;
     }
     d.desc1 = desc1; d.desc2 = desc2; d.kp1 = kp1; d.kp2 = kp2; d.n1 = n1; d.n2 = n2;
     d.oct1 = oct1; d.oct2 = oct2;
-    d.Kinv = Kinv; d.K = K; d.gidx = gidx;
-    d.wgbest = nullptr;
-    d.hyp_F = nullptr;
-    d.hyp_r32 = nullptr;
-    d.hyp_okf = nullptr;
-    d.hyp_cnt = nullptr;
-    d.bound = nullptr;
-    d.box = nullptr;
-    d.mode = nullptr;
-    d.dense_n1 = nullptr;
-    d.clist = nullptr;
-    d.clist2 = nullptr;
-    d.cpos = nullptr;
-    d.ccount = nullptr;
-    d.pcount = nullptr;
-    d.m0list = nullptr;
-    d.xlist = nullptr;
-    d.xcount = nullptr;
-    d.hyp_count = nullptr;
-    d.hyp_residual = nullptr;
+    d.Kinv = Kinv; d.K = K; d.gidx = gidx;   // the RANSAC stage's blocks stay null until ensure_groups
     hipStream_t s = ctx->stream;
     // deterministic contents for rows the caller never uploads
     (void)hipMemsetAsync(desc1, 0, NI * N * d.desc_words * 4, s);
@@ -966,8 +1005,6 @@ void mvs_batch_destroy(mvs_batch *b)
         return;
     (void)hipSetDevice(b->ctx->device);
     (void)sync_stream(b->ctx);
-    for (void *p : b->allocs)
-        (void)hipFree(p);
     for (auto &e : b->ev)
         if (e)
             (void)hipEventDestroy(e);
@@ -1213,14 +1250,9 @@ mvs_status mvs_batch_run_points(mvs_batch *b, const mvs_params *params, int n_ac
     if (st != MVS_OK)
         return st;
     if (!b->uv1) {   // staging for the image points, allocated on first use and owned by the batch
-        const size_t bytes = (size_t)b->d.n_pairs * N * 2 * sizeof(double);
-        void *a = nullptr, *c = nullptr;
-        HIP_TRY(ctx, hipMalloc(&a, bytes));
-        b->allocs.push_back(a);
-        HIP_TRY(ctx, hipMalloc(&c, bytes));
-        b->allocs.push_back(c);
-        b->uv1 = static_cast<double *>(a);
-        b->uv2 = static_cast<double *>(c);
+        const size_t count = (size_t)b->d.n_pairs * N * 2;
+        if ((st = DevGroup(ctx, b->blocks).add(b->uv1, count).add(b->uv2, count).commit()) != MVS_OK)
+            return st;
     }
     hipStream_t s = ctx->stream;
     const size_t pb = (size_t)n_active * N * 2 * sizeof(double);
@@ -1230,7 +1262,7 @@ mvs_status mvs_batch_run_points(mvs_batch *b, const mvs_params *params, int n_ac
     HIP_TRY(ctx, hipMemsetAsync(b->d.matches, 0, (size_t)n_active * N * sizeof(mvs_match), s));
     // the host buffers are the caller's: they may change as soon as this call returns (pageable copies are staged by the
     // runtime before hipMemcpyAsync returns; pinned ones are not) -- wait for the three copies, not for the kernels
-    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, sync_stream(ctx));
     launch_prep_points(b->d, b->uv1, b->uv2, n_active, s);
     b->d.hyp_count = nullptr;
     b->d.hyp_residual = nullptr;
@@ -1604,20 +1636,6 @@ static mvs_status ensure_scratch(mvs_ctx *ctx, int max_kp, int desc_bytes)
     return mvs_batch_create(ctx, 1, max_kp, desc_bytes, &ctx->scratch);
 }
 
-static mvs_status ensure_uv(mvs_ctx *ctx, int cap)
-{
-    if (ctx->uv_cap >= cap)
-        return MVS_OK;
-    if (ctx->d_uv1) (void)hipFree(ctx->d_uv1);
-    if (ctx->d_uv2) (void)hipFree(ctx->d_uv2);
-    ctx->d_uv1 = ctx->d_uv2 = nullptr;
-    ctx->uv_cap = 0;
-    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_uv1, (size_t)cap * 2 * sizeof(double)));
-    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_uv2, (size_t)cap * 2 * sizeof(double)));
-    ctx->uv_cap = cap;
-    return MVS_OK;
-}
-
 // stage image points + camera of a single-shot call; leaves normalised points in batch->pts
 static mvs_status stage_points(mvs_ctx *ctx, const double *p1_uv, const double *p2_uv, int m, const double K[9])
 {
@@ -1628,9 +1646,10 @@ static mvs_status stage_points(mvs_ctx *ctx, const double *p1_uv, const double *
     if (st != MVS_OK)
         return st;
     mvs_batch *b = ctx->scratch;
-    st = ensure_uv(ctx, b->d.max_kp);
-    if (st != MVS_OK)
+    const size_t half = (size_t)b->d.max_kp * 2;   // doubles of one camera's points
+    if ((st = ws_grow(ctx, ctx->uv, 2 * half * sizeof(double))) != MVS_OK)
         return st;
+    double *d_uv1 = ctx->uv.ptr<double>(), *d_uv2 = d_uv1 + half;
     hipStream_t s = ctx->stream;
     double kinv[9];
     mat3_inverse(K, kinv);
@@ -1640,13 +1659,13 @@ static mvs_status stage_points(mvs_ctx *ctx, const double *p1_uv, const double *
     // results come back through the same arena (fetch_single): size it for both directions now
     if ((st = pin_begin(ctx, 2 * pb + 1024 + sizeof(mvs_pair_result) + (size_t)b->d.max_kp * (1 + 24 + 4 + 16) + 512)) != MVS_OK)
         return st;
-    if ((st = up_async(ctx, ctx->d_uv1, p1_uv, pb)) != MVS_OK) return st;
-    if ((st = up_async(ctx, ctx->d_uv2, p2_uv, pb)) != MVS_OK) return st;
+    if ((st = up_async(ctx, d_uv1, p1_uv, pb)) != MVS_OK) return st;
+    if ((st = up_async(ctx, d_uv2, p2_uv, pb)) != MVS_OK) return st;
     if ((st = up_async(ctx, const_cast<double *>(b->d.K), K, 9 * sizeof(double))) != MVS_OK) return st;
     if ((st = up_async(ctx, const_cast<double *>(b->d.Kinv), kinv, 9 * sizeof(double))) != MVS_OK) return st;
     if ((st = up_async(ctx, const_cast<int64_t *>(b->d.gidx), &zero, sizeof(zero))) != MVS_OK) return st;
     if ((st = up_async(ctx, b->d.M, &M, sizeof(M))) != MVS_OK) return st;
-    launch_prep_points(b->d, ctx->d_uv1, ctx->d_uv2, 1, s);
+    launch_prep_points(b->d, d_uv1, d_uv2, 1, s);
     return MVS_OK;
 }
 
@@ -1663,20 +1682,14 @@ static mvs_status fetch_single(mvs_ctx *ctx, int m, mvs_pair_result *res, double
     const int flags = ((mask && rows) ? 1 : 0) | ((points_xyz && rows) ? 2 : 0) | ((point_idx && rows) ? 4 : 0) |
                       ((matches && rows) ? 8 : 0);
     const SingleLayout L = single_layout((int)rows, flags);
-    if (ctx->single_cap < L.total) {
-        HIP_TRY(ctx, sync_stream(ctx));
-        if (ctx->d_single)
-            (void)hipFree(ctx->d_single);
-        ctx->d_single = nullptr;
-        ctx->single_cap = 0;
-        const size_t cap = std::max<size_t>(L.total, single_layout(b->d.max_kp, 15).total);
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_single, cap));
-        ctx->single_cap = cap;
-    }
+    mvs_status st = ws_grow(ctx, ctx->single, L.total, single_layout(b->d.max_kp, 15).total);
+    if (st != MVS_OK)
+        return st;
+    unsigned char *d_single = ctx->single.ptr<unsigned char>();
     unsigned char *h_all = static_cast<unsigned char *>(pin_get(ctx, L.total));
     PIN_TRY(ctx, h_all);
-    launch_single_gather(b->d, (int)rows, flags, ctx->d_single, s);
-    HIP_TRY(ctx, hipMemcpyAsync(h_all, ctx->d_single, L.total, hipMemcpyDeviceToHost, s));
+    launch_single_gather(b->d, (int)rows, flags, d_single, s);
+    HIP_TRY(ctx, hipMemcpyAsync(h_all, d_single, L.total, hipMemcpyDeviceToHost, s));
     const mvs_pair_result *h_res = reinterpret_cast<const mvs_pair_result *>(h_all);
     const uint8_t *h_mask = (flags & 1) ? h_all + L.mask : nullptr;
     const double *h_pts = (flags & 2) ? reinterpret_cast<const double *>(h_all + L.points) : nullptr;
@@ -1835,26 +1848,18 @@ mvs_status mvs_image_pair(mvs_ctx *ctx, const uint8_t *base_desc, const float *b
     // DMA whatever memory the caller's cv::Mat / std::vector lives in -- as ONE block [desc1 | desc2 | kp1 | kp2] and one copy
     // command; the kernel that receives the pair's scalars as arguments also puts the parts in place
     {
-        auto up16 = [](size_t x) { return (x + 15) & ~size_t(15); };
-        const size_t total = up16(db1) + up16(db2) + up16(kb1) + up16(kb2);
-        if (ctx->single_in_cap < total) {
-            HIP_TRY(ctx, sync_stream(ctx));
-            if (ctx->d_single_in)
-                (void)hipFree(ctx->d_single_in);
-            ctx->d_single_in = nullptr;
-            ctx->single_in_cap = 0;
-            const size_t cap = std::max<size_t>(total, (size_t)b->d.max_kp * (2 * 64 + 2 * 8) + 64);
-            HIP_TRY(ctx, hipMalloc((void **)&ctx->d_single_in, cap));
-            ctx->single_in_cap = cap;
-        }
+        Carve L{16};
+        const size_t o_desc1 = L.take(db1), o_desc2 = L.take(db2), o_kp1 = L.take(kb1), o_kp2 = L.take(kb2);
+        const size_t total = L.total();
+        if ((st = ws_grow(ctx, ctx->single_in, total, (size_t)b->d.max_kp * (2 * 64 + 2 * 8) + 64)) != MVS_OK)
+            return st;
         unsigned char *h_in = static_cast<unsigned char *>(pin_get(ctx, total));
         PIN_TRY(ctx, h_in);
-        size_t o = 0;
-        std::memcpy(h_in + o, base_desc, db1); o += up16(db1);
-        std::memcpy(h_in + o, pair_desc, db2); o += up16(db2);
-        std::memcpy(h_in + o, base_kp, kb1); o += up16(kb1);
-        std::memcpy(h_in + o, pair_kp, kb2);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_single_in, h_in, total, hipMemcpyHostToDevice, ctx->stream));
+        std::memcpy(h_in + o_desc1, base_desc, db1);
+        std::memcpy(h_in + o_desc2, pair_desc, db2);
+        std::memcpy(h_in + o_kp1, base_kp, kb1);
+        std::memcpy(h_in + o_kp2, pair_kp, kb2);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->single_in.ptr(), h_in, total, hipMemcpyHostToDevice, ctx->stream));
         SingleParams sp;
         sp.n1 = n1;
         sp.n2 = n2;
@@ -1865,7 +1870,7 @@ mvs_status mvs_image_pair(mvs_ctx *ctx, const uint8_t *base_desc, const float *b
         }
         sp.part_bytes[0] = (uint32_t)db1; sp.part_bytes[1] = (uint32_t)db2;
         sp.part_bytes[2] = (uint32_t)kb1; sp.part_bytes[3] = (uint32_t)kb2;
-        launch_single_params(b->d, sp, ctx->d_single_in, ctx->stream);
+        launch_single_params(b->d, sp, ctx->single_in.ptr(), ctx->stream);
     }
     if ((st = enqueue_pipeline(b, to_run(*params), 1, false, nullptr)) != MVS_OK)
         return st;
@@ -1957,7 +1962,7 @@ mvs_status mvs_find_fundamental_matrix(mvs_ctx *ctx, const double p1_xy[16], con
         return MVS_ERR_INVALID_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    double *d = ctx->d_small;  // [0,16) p1, [16,32) p2, [32,41) F, [48] ok flag (as int)
+    double *d = ctx->small.ptr<double>();  // [0,16) p1, [16,32) p2, [32,41) F, [48] ok flag (as int)
     HIP_TRY(ctx, hipMemcpyAsync(d, p1_xy, 16 * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemcpyAsync(d + 16, p2_xy, 16 * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, sync_stream(ctx));
@@ -2013,19 +2018,14 @@ mvs_status mvs_ransac_fundamental(mvs_ctx *ctx, const double *p1_xy, const doubl
     if ((st = up_async(ctx, const_cast<double *>(b->d.Kinv), eye, sizeof(eye))) != MVS_OK) return st;
     if (count || residual) {
         if (b->hyp_table_cap < num_hypotheses) {
-            int32_t *hc;
-            double *hr;
-            if ((st = dev_alloc(b, &hc, (size_t)num_hypotheses)) != MVS_OK) return st;
-            if ((st = dev_alloc(b, &hr, (size_t)num_hypotheses)) != MVS_OK) return st;
-            b->d.hyp_count = hc;
-            b->d.hyp_residual = hr;
+            HIP_TRY(ctx, sync_stream(ctx));   // the tables it replaces are freed
+            const size_t H = num_hypotheses;
+            if ((st = DevGroup(ctx, b->blocks).add(b->hyp_table_count, H).add(b->hyp_table_residual, H).commit()) != MVS_OK)
+                return st;
             b->hyp_table_cap = num_hypotheses;
-            b->allocs_hc = hc;
-            b->allocs_hr = hr;
-        } else {
-            b->d.hyp_count = b->allocs_hc;
-            b->d.hyp_residual = b->allocs_hr;
         }
+        b->d.hyp_count = b->hyp_table_count;
+        b->d.hyp_residual = b->hyp_table_residual;
     } else {
         b->d.hyp_count = nullptr;
         b->d.hyp_residual = nullptr;
@@ -2075,28 +2075,27 @@ mvs_status mvs_seq_create(mvs_ctx *ctx, int n_frames, int max_kp, int desc_bytes
     }
     q->stride = std::min(max_kp, kPnpMaxPoints);
     const size_t T = q->n_tracks, S = q->stride;
-    double *X, *uv, *xy, *fb, *K, *Kinv;
-    int32_t *n_corr, *inl;
-    int64_t *gidx;
-    PnpOut *po;
-#define SALLOC(ptr, cnt) if (st == MVS_OK) st = seq_alloc(q, &(ptr), (cnt));
-    SALLOC(X, T * S * 3);
-    SALLOC(uv, T * S * 2);
-    SALLOC(xy, T * S * 2);
-    SALLOC(fb, T * S * 3);
-    SALLOC(K, T * 9);
-    SALLOC(Kinv, T * 9);
-    SALLOC(n_corr, T);
-    SALLOC(inl, T * S);
-    SALLOC(gidx, T);
-    SALLOC(po, T);
+    double *X = nullptr, *uv = nullptr, *xy = nullptr, *fb = nullptr, *K = nullptr, *Kinv = nullptr;
+    int32_t *n_corr = nullptr, *inl = nullptr;
+    int64_t *gidx = nullptr;
+    PnpOut *po = nullptr;
     double *traj_R = nullptr, *traj_t = nullptr, *traj_s = nullptr, *trk_s = nullptr;   // scale-propagation fold outputs
-    SALLOC(traj_R, (size_t)n_frames * 9);
-    SALLOC(traj_t, (size_t)n_frames * 3);
-    SALLOC(traj_s, (size_t)n_frames);
-    SALLOC(trk_s, (size_t)n_frames);
-#undef SALLOC
-    if (st != MVS_OK) {
+    DevGroup grp(ctx, q->blocks);
+    grp.add(X, T * S * 3);
+    grp.add(uv, T * S * 2);
+    grp.add(xy, T * S * 2);
+    grp.add(fb, T * S * 3);
+    grp.add(K, T * 9);
+    grp.add(Kinv, T * 9);
+    grp.add(n_corr, T);
+    grp.add(inl, T * S);
+    grp.add(gidx, T);
+    grp.add(po, T);
+    grp.add(traj_R, (size_t)n_frames * 9);
+    grp.add(traj_t, (size_t)n_frames * 3);
+    grp.add(traj_s, (size_t)n_frames);
+    grp.add(trk_s, (size_t)n_frames);
+    if ((st = grp.commit()) != MVS_OK) {
         mvs_seq_destroy(q);
         return st;
     }
@@ -2161,8 +2160,6 @@ void mvs_seq_destroy(mvs_seq *q)
     (void)sync_stream(q->ctx);
     if (q->batch)
         mvs_batch_destroy(q->batch);
-    for (void *p : q->allocs)
-        (void)hipFree(p);
     delete q;
 }
 
@@ -2228,14 +2225,11 @@ static mvs_status seq_prepare(mvs_seq *q, const mvs_params *tv, const mvs_pnp_pa
     if ((st = ensure_groups(q->batch, tv->num_hypotheses)) != MVS_OK)
         return st;
     const int G = (pp->num_hypotheses + 255) / 256;
-    if (G > q->rec_groups) {
-        HIP_TRY(q->ctx, sync_stream(q->ctx));
-        PnpRec *rec;
-        if ((st = seq_alloc(q, &rec, (size_t)q->n_tracks * G)) != MVS_OK)
+    if (G > q->pnp.max_groups) {
+        HIP_TRY(q->ctx, sync_stream(q->ctx));   // the records it replaces are freed
+        if ((st = DevGroup(q->ctx, q->blocks).add(q->pnp.rec, (size_t)q->n_tracks * G).commit()) != MVS_OK)
             return st;
-        q->pnp.rec = rec;
         q->pnp.max_groups = G;
-        q->rec_groups = G;
     }
     q->batch->d.hyp_count = nullptr;
     q->batch->d.hyp_residual = nullptr;
@@ -2245,37 +2239,9 @@ static mvs_status seq_prepare(mvs_seq *q, const mvs_params *tv, const mvs_pnp_pa
     q->pnp.seed = pp->seed;
     q->pnp.thr2 = pp->reproj_error * pp->reproj_error;
     q->refit_on = pp->refit != 0;
-    if (q->refit_on && !q->refit_ready) {
-        const size_t T = q->n_tracks, S = q->stride;
-        double *obs0, *oi0, *p0, *pi, *pts, *tmp, *pose;
-        int32_t *m;
-        mvs_refine_result *out;
-        if ((st = seq_alloc(q, &obs0, T * S * 2)) != MVS_OK) return st;
-        if ((st = seq_alloc(q, &oi0, T * S * 3)) != MVS_OK) return st;
-        if ((st = seq_alloc(q, &p0, T * S * 3)) != MVS_OK) return st;
-        if ((st = seq_alloc(q, &pi, T * S * 6)) != MVS_OK) return st;
-        if ((st = seq_alloc(q, &pts, T * S * 3)) != MVS_OK) return st;
-        if ((st = seq_alloc(q, &tmp, T * S * 3)) != MVS_OK) return st;
-        if ((st = seq_alloc(q, &pose, T * 12)) != MVS_OK) return st;
-        if ((st = seq_alloc(q, &m, T)) != MVS_OK) return st;
-        if ((st = seq_alloc(q, &out, T)) != MVS_OK) return st;
-        RefineDev &d = q->refit;
-        d = RefineDev{};
-        d.n_problems = (int)T;
-        d.stride = (int)S;
-        d.n_frames = 1;
-        d.m = m;
-        d.K = q->pnp.K;
-        d.pose0 = pose;
-        d.obs[0] = obs0;
-        d.oinfo[0] = oi0;
-        d.pts0 = p0;
-        d.pinfo = pi;
-        d.pts = pts;
-        d.pts_tmp = tmp;
-        d.out = out;
-        q->refit_ready = true;
-    }
+    if (q->refit_on && !q->refit.out &&
+        (st = alloc_refine(q->ctx, q->blocks, q->refit, q->n_tracks, q->stride, 1, q->pnp.K)) != MVS_OK)
+        return st;
     if (q->refit_on) {
         mvs_refine_params rp;
         mvs_refine_params_default(&rp);
@@ -2466,21 +2432,17 @@ mvs_status mvs_pnp_solve(mvs_ctx *ctx, const double *world_xyz, const double *im
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int G = (params->num_hypotheses + 255) / 256;
     // workspace layout: X[3n] uv[2n] xy[2n] fb[3n] | K[9] Kinv[9] | rec[G] | out | inliers[n] n
-    const size_t nd = (size_t)n * 10 * sizeof(double);
-    const size_t off_k = (nd + 63) & ~size_t(63);
-    const size_t off_rec = (off_k + 18 * sizeof(double) + 63) & ~size_t(63);
-    const size_t off_out = (off_rec + (size_t)G * sizeof(PnpRec) + 63) & ~size_t(63);
-    const size_t off_inl = (off_out + sizeof(PnpOut) + 63) & ~size_t(63);
-    const size_t total = off_inl + ((size_t)n + 1) * sizeof(int32_t);
-    if (ctx->pnp_bytes < total) {
-        if (ctx->d_pnp) (void)hipFree(ctx->d_pnp);
-        ctx->d_pnp = nullptr;
-        ctx->pnp_bytes = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_pnp, total));
-        ctx->pnp_bytes = total;
-    }
-    char *base = static_cast<char *>(ctx->d_pnp);
-    double *dX = reinterpret_cast<double *>(base), *duv = dX + 3 * (size_t)n, *dxy = duv + 2 * (size_t)n, *dfb = dxy + 2 * (size_t)n;
+    Carve L{64};
+    const size_t off_x = L.take((size_t)n * 10 * sizeof(double));
+    const size_t off_k = L.take(18 * sizeof(double));
+    const size_t off_rec = L.take((size_t)G * sizeof(PnpRec));
+    const size_t off_out = L.take(sizeof(PnpOut));
+    const size_t off_inl = L.take(((size_t)n + 1) * sizeof(int32_t));
+    const mvs_status st = ws_grow(ctx, ctx->pnp, L.end);
+    if (st != MVS_OK)
+        return st;
+    char *base = ctx->pnp.ptr();
+    double *dX = reinterpret_cast<double *>(base + off_x), *duv = dX + 3 * (size_t)n, *dxy = duv + 2 * (size_t)n, *dfb = dxy + 2 * (size_t)n;
     double *dK = reinterpret_cast<double *>(base + off_k);
     int32_t *dinl = reinterpret_cast<int32_t *>(base + off_inl);
     hipStream_t s = ctx->stream;
@@ -2623,26 +2585,22 @@ static mvs_status refine_single(mvs_ctx *ctx, int frames, const double *obs_a, c
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t M = (size_t)m;
     // doubles: obs0 2 obs1 2 oinfo0 3 oinfo1 3 pts0 3 pinfo 6 pts 3 tmp 3 pcov 9 cov2a 4 cov2b 4 cov3 9 = 51 per point
-    const size_t nd = M * 51 + 9 + 12 + 24;
-    const size_t off_out = (nd * sizeof(double) + 63) & ~size_t(63);
-    const size_t off_all = (off_out + sizeof(mvs_refine_result) + 63) & ~size_t(63);
-    const size_t off_m = (off_all + 2 * sizeof(mvs_refine_result) + 63) & ~size_t(63);
-    const size_t off_valid = off_m + 64;
-    const size_t total = off_valid + 2 * ((M + 63) & ~size_t(63));
-    if (ctx->ref_bytes < total) {
-        if (ctx->d_ref) (void)hipFree(ctx->d_ref);
-        ctx->d_ref = nullptr;
-        ctx->ref_bytes = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_ref, total));
-        ctx->ref_bytes = total;
-    }
-    char *base = static_cast<char *>(ctx->d_ref);
-    double *w = reinterpret_cast<double *>(base);
+    Carve L{64};
+    const size_t off_w = L.take((M * 51 + 9 + 12 + 24) * sizeof(double));
+    const size_t off_out = L.take(sizeof(mvs_refine_result));
+    const size_t off_all = L.take(2 * sizeof(mvs_refine_result));
+    const size_t off_m = L.take(64);
+    const size_t off_valid0 = L.take(M), off_valid1 = L.take(M);
+    const mvs_status st = ws_grow(ctx, ctx->ref, L.total());
+    if (st != MVS_OK)
+        return st;
+    char *base = ctx->ref.ptr();
+    double *w = reinterpret_cast<double *>(base + off_w);
     double *obs0 = w, *obs1 = obs0 + 2 * M, *oinfo0 = obs1 + 2 * M, *oinfo1 = oinfo0 + 3 * M, *dp0 = oinfo1 + 3 * M;
     double *pinfo = dp0 + 3 * M, *dpts = pinfo + 6 * M, *dtmp = dpts + 3 * M, *dpcov = dtmp + 3 * M;
     double *c2a = dpcov + 9 * M, *c2b = c2a + 4 * M, *c3 = c2b + 4 * M, *dK = c3 + 9 * M, *dpose = dK + 9, *dpose_all = dpose + 12;
     int32_t *dm = reinterpret_cast<int32_t *>(base + off_m);
-    uint8_t *dv0 = reinterpret_cast<uint8_t *>(base + off_valid), *dv1 = dv0 + ((M + 63) & ~size_t(63));
+    uint8_t *dv0 = reinterpret_cast<uint8_t *>(base + off_valid0), *dv1 = reinterpret_cast<uint8_t *>(base + off_valid1);
     hipStream_t s = ctx->stream;
     const int32_t m32 = m;
     double pose[12];
@@ -2786,45 +2744,10 @@ mvs_status mvs_batch_refine(mvs_batch *b, const mvs_refine_params *params, doubl
     const BatchDev &bd = b->d;
     const size_t P = bd.n_pairs, N = bd.max_kp;
     RefineDev &d = b->refine;
-    if (!b->refine_ready) {
-        auto grab = [&](size_t bytes, void **out) -> hipError_t {
-            hipError_t e = hipMalloc(out, bytes);
-            if (e == hipSuccess)
-                b->allocs.push_back(*out);
-            return e;
-        };
-        double *obs0, *obs1, *oi0, *oi1, *p0, *pi, *pts, *tmp, *pc, *pose;
-        int32_t *m;
-        mvs_refine_result *out;
-        HIP_TRY(ctx, grab(P * N * 2 * sizeof(double), (void **)&obs0));
-        HIP_TRY(ctx, grab(P * N * 2 * sizeof(double), (void **)&obs1));
-        HIP_TRY(ctx, grab(P * N * 3 * sizeof(double), (void **)&oi0));
-        HIP_TRY(ctx, grab(P * N * 3 * sizeof(double), (void **)&oi1));
-        HIP_TRY(ctx, grab(P * N * 3 * sizeof(double), (void **)&p0));
-        HIP_TRY(ctx, grab(P * N * 6 * sizeof(double), (void **)&pi));
-        HIP_TRY(ctx, grab(P * N * 3 * sizeof(double), (void **)&pts));
-        HIP_TRY(ctx, grab(P * N * 3 * sizeof(double), (void **)&tmp));
-        HIP_TRY(ctx, grab(P * N * 9 * sizeof(double), (void **)&pc));
-        HIP_TRY(ctx, grab(P * 12 * sizeof(double), (void **)&pose));
-        HIP_TRY(ctx, grab(P * sizeof(int32_t), (void **)&m));
-        HIP_TRY(ctx, grab(P * sizeof(mvs_refine_result), (void **)&out));
-        d.n_problems = (int)P;
-        d.stride = (int)N;
-        d.n_frames = 2;
-        d.m = m;
-        d.K = bd.K;
-        d.pose0 = pose;
-        d.obs[0] = obs0;
-        d.obs[1] = obs1;
-        d.oinfo[0] = oi0;
-        d.oinfo[1] = oi1;
-        d.pts0 = p0;
-        d.pinfo = pi;
-        d.pts = pts;
-        d.pts_tmp = tmp;
-        d.point_cov = pc;
-        d.out = out;
-        b->refine_ready = true;
+    if (!d.out) {
+        mvs_status st = alloc_refine(ctx, b->blocks, d, (int)P, (int)N, 2, bd.K);
+        if (st != MVS_OK)
+            return st;
     }
     d.cfg = to_cfg(*params, 2);
     hipStream_t s = ctx->stream;
@@ -3025,11 +2948,10 @@ static mvs_status orb_run(mvs_ctx *ctx, const uint8_t *images, int n, int w, int
         HIP_TRY(ctx, orb_prepare());
         ctx->orb_ready = true;
     }
-    const size_t B = (size_t)n, L = (size_t)prm.nlevels, NF = (size_t)prm.nfeatures;
-    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
-    size_t off = 0;
-    const size_t o_pyr = off; off = up(off + T * B);
-    const size_t o_blur = off; off = up(off + T * B);
+    const size_t B = (size_t)n, NL = (size_t)prm.nlevels, NF = (size_t)prm.nfeatures;
+    Carve L{256};
+    const size_t o_pyr = L.take(T * B);
+    const size_t o_blur = L.take(T * B);
     // resize tables: for every level >= 1, {source index, 11-bit weight} per destination column, then per row.  Their layout
     // is part of the key, their contents are built only when the key is new (below)
     size_t tab_entries = 0;
@@ -3055,7 +2977,7 @@ static mvs_status orb_run(mvs_ctx *ctx, const uint8_t *images, int n, int w, int
             }
         }
     };
-    const size_t o_tab = off; off = up(off + std::max<size_t>(tab_entries, 1) * sizeof(int2));
+    const size_t o_tab = L.take(std::max<size_t>(tab_entries, 1) * sizeof(int2));
     // candidate lists: a level's list holds the non-maximum suppression's own bound -- strict 3x3 maxima of the detection
     // area, at most one per 2x2 block -- so it cannot overflow; only when 2 n_l exceeds what the selection holds in LDS the
     // list is capped there (and a fuller level is reported as MVS_ERR_CAPACITY, as every level was in rounds 2-4)
@@ -3076,23 +2998,21 @@ static mvs_status orb_run(mvs_ctx *ctx, const uint8_t *images, int n, int w, int
         cand_total += (size_t)cap;
     }
     d.cand_stride = cand_total;
-    const size_t o_keys = off; off = up(off + B * cand_total * 8);
-    const size_t o_cc = off; off = up(off + B * L * 4);
-    const size_t o_sel = off; off = up(off + B * L * NF * sizeof(OrbSel));
-    const size_t o_sc = off; off = up(off + B * L * 4);
-    const size_t o_ovf = off; off = up(off + 4);
-    const size_t o_pat = off; off = up(off + 1024);
-    const size_t o_kp = off; off = up(off + B * NF * sizeof(mvs_keypoint));
-    const size_t o_desc = off; off = up(off + B * NF * 32);
-    const size_t o_n = off; off = up(off + B * 4);
-    if (ctx->orb_bytes < off) {
-        if (ctx->d_orb) (void)hipFree(ctx->d_orb);
-        ctx->d_orb = nullptr;
-        ctx->orb_bytes = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_orb, off));
-        ctx->orb_bytes = off;
-    }
-    char *base = static_cast<char *>(ctx->d_orb);
+    const size_t o_keys = L.take(B * cand_total * 8);
+    const size_t o_cc = L.take(B * NL * 4);
+    const size_t o_sel = L.take(B * NL * NF * sizeof(OrbSel));
+    const size_t o_sc = L.take(B * NL * 4);
+    const size_t o_ovf = L.take(4);
+    const size_t o_pat = L.take(1024);
+    const size_t o_kp = L.take(B * NF * sizeof(mvs_keypoint));
+    const size_t o_desc = L.take(B * NF * 32);
+    const size_t o_n = L.take(B * 4);
+    if (ctx->orb.bytes < L.total())
+        drop_orb_graph(ctx);   // before its workspace is freed: a failed growth must not leave it behind
+    const mvs_status st = ws_grow(ctx, ctx->orb, L.total());
+    if (st != MVS_OK)
+        return st;
+    char *base = ctx->orb.ptr();
     d.n_images = n;
     d.n_levels = prm.nlevels;
     d.nfeatures = prm.nfeatures;
@@ -3139,10 +3059,8 @@ static mvs_status orb_run(mvs_ctx *ctx, const uint8_t *images, int n, int w, int
     if (no_graph) {
         launch_orb(d, s);
     } else {
-        if (!ctx->orb_graph_valid || std::memcmp(&ctx->orb_graph_key, &d, sizeof(d)) != 0) {
-            if (ctx->orb_graph) (void)hipGraphExecDestroy(ctx->orb_graph);
-            ctx->orb_graph = nullptr;
-            ctx->orb_graph_valid = false;
+        if (!same_key) {
+            drop_orb_graph(ctx);
             hipGraph_t graph = nullptr;
             HIP_TRY(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
             launch_orb(d, s);

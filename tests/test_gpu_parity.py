@@ -770,3 +770,53 @@ def test_gpu_against_golden_vectors(ctx):
         assert np.array_equal(out["point_idx"][i][:npts], g["point_idx_%d" % i])
         assert out["points"][i][:npts].tobytes() == g["points_%d" % i].tobytes()
         assert r["R"].tobytes() == g["R_%d" % i].tobytes() and r["t"].tobytes() == g["t_%d" % i].tobytes()
+
+
+# ----------------------------------------------------------------------------- context workspaces
+def _bytes_of(r):
+    """every value of an entry point's result as raw bytes (bit-for-bit comparison)"""
+    if isinstance(r, dict):
+        return {k: _bytes_of(v) for k, v in r.items()}
+    if isinstance(r, (list, tuple)):
+        return [_bytes_of(v) for v in r]
+    return np.asarray(r).tobytes()
+
+
+def test_one_context_same_answers_while_its_workspaces_grow():
+    """small -> clearly larger -> small again on ONE fresh context: every single-shot entry point regrows its workspace
+    (and the extraction re-captures its graph for a second image shape), and the third call equals the first bit for bit."""
+    K = np.array([[525.0, 0, 320], [0, 525, 240], [0, 0, 1]])
+    rng = np.random.default_rng(31)
+    images = {shape: np.kron(rng.integers(0, 256, size=(shape[0], shape[1] // 6, shape[2] // 6)).astype(np.uint8),
+                             np.ones((1, 6, 6), dtype=np.uint8)) for shape in ((1, 120, 162), (2, 480, 642))}
+
+    def run_all(c, m, H, n_kp, shape):
+        rng = np.random.default_rng(m)
+        p1, p2 = _scene(1000 + m, m, 2e-4)
+        uv1, uv2 = p1 * 525 + np.array([320, 240.0]), p2 * 525 + np.array([320, 240.0])
+        prm = capi.default_params(num_hypotheses=H, sampler=capi.SAMPLER_PHILOX, seed=9, max_error_sq=2e-3)
+        pair = synth.make_pair(5 + n_kp, n_kp=n_kp)
+        X = np.stack([rng.uniform(-2, 2, m), rng.uniform(-1.5, 1.5, m), rng.uniform(4, 9, m)], axis=1)
+        R, t = o.rodrigues(np.array([0.02, -0.05, 0.01])), np.array([0.2, -0.1, 0.3])
+        uv = o.project_points(K, R, t, X)
+        Xc = X / X[:, 2:3]
+        cov = np.tile(np.eye(2).reshape(4) * 0.25, (m, 1))
+        ex = c.extract(images[shape], capi.default_orb_params(nfeatures=300 if shape[0] == 1 else 1500))
+        return dict(
+            two_view=c.two_view(uv1, uv2, K, prm),
+            image_pair=c.image_pair(pair["desc1"], pair["kp1"], pair["desc2"], pair["kp2"], pair["K"], prm),
+            pnp_solve=c.pnp_solve(X, uv, K, capi.default_pnp_params(num_hypotheses=H // 4, seed=3)),
+            sfm_refine=c.sfm_refine(Xc[:, :2] * 525 + [320, 240], cov, uv, cov, K, R, t, X),
+            ransac_fundamental=c.ransac_fundamental(p1, p2, 2e-3, H, capi.SAMPLER_PHILOX, seed=17, per_hyp=True),
+            # the rows past an image's n keypoints are not outputs
+            extract=[(n, ex["kp"][i][:n], ex["desc"][i][:n]) for i, n in enumerate(ex["n"].tolist())])
+
+    c = capi.Context(0)
+    try:
+        first = _bytes_of(run_all(c, 60, 256, 300, (1, 120, 162)))
+        run_all(c, 2500, 4096, 3000, (2, 480, 642))
+        again = _bytes_of(run_all(c, 60, 256, 300, (1, 120, 162)))
+    finally:
+        c.close()
+    for name in first:
+        assert again[name] == first[name], name
