@@ -152,6 +152,11 @@ def main():
                   kp2=seq["kp"][1:F], n2=seq["n_kp"][1:F], K=np.tile(np.asarray(seq["K"]).reshape(1, 9), (F - 1, 1)),
                   global_index=np.arange(F - 1, dtype=np.int64))
         cases.append(run_case(ctx, lib, "configs[4] pairs 0..127 @1e-2", sq, F - 1, N, H, 1e-2))
+        # a mixed batch: pair i drawn with camera family i mod 5 (tests/helpers.py CAMERAS), so that the stage decides on
+        # ideal-coordinate boxes other than the default camera's (one-sided, +-5.3 x +-4.0, +-0.08) and K changes per pair
+        import helpers
+
+        cases.append(run_case(ctx, lib, "mixed cameras: 20 pairs @1e-2", helpers.mixed_batch(0, 20, n_kp=N), 20, N, H, 1e-2))
     # negative control: the same audit must TRIP when the stage and the audit disagree about the threshold (the stage ran at
     # 1e-2, the audit scores at 2e-2: dropped hypotheses then reach the bound, the winner's count differs)
     Pc, Nc, Hc = 4, 500, 2048

@@ -8,33 +8,17 @@ every pair / track, the trajectory fold against the oracle's fold, and full orac
 The 8-GPU config (configs[3]) is these 512 pairs per rank: the rank-local part is what runs here; the gather is covered
 by tests/test_dist_gloo.py and tests/test_gather.py.
 """
-import threading
-
 import numpy as np
 import pytest
 
+import helpers
 import oracle_lib as o
 from mvslam_amd import synth
 
 pytestmark = pytest.mark.gpu
 
 
-def _threads(fn, items, n=16):
-    out, err = [None] * len(items), []
-
-    def work(k0):
-        try:
-            for k in range(k0, len(items), n):
-                out[k] = fn(items[k])
-        except Exception as e:   # surface oracle-side failures in the main thread
-            err.append(e)
-
-    ths = [threading.Thread(target=work, args=(k,)) for k in range(min(n, len(items)))]
-    [t.start() for t in ths]
-    [t.join() for t in ths]
-    if err:
-        raise err[0]
-    return out
+_threads = helpers.threads
 
 
 _BATCH512 = {}

@@ -14,8 +14,8 @@ from mvslam_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
 
-REL_TOL = 1e-4   # north_star tolerance for pose / points
-TIGHT = 1e-12    # what the shared arithmetic contract actually delivers
+REL_TOL, TIGHT = helpers.REL_TOL, helpers.TIGHT
+_run_batch, _check_batch_against_oracle = helpers.run_batch, helpers.check_batch_against_oracle
 
 
 def _rand_desc(rng, n, nbytes=32):
@@ -503,44 +503,6 @@ def test_two_view_errors(ctx):
 
 
 # ----------------------------------------------------------------------------- batched pipeline
-def _run_batch(ctx, first, count, n_kp, prm, **gen):
-    data = synth.make_batch(first, count, n_kp=n_kp, **gen)
-    b = capi.Batch(ctx, count, n_kp, 32)
-    b.upload(0, data["desc1"], data["kp1"], data["n1"], data["desc2"], data["kp2"], data["n2"], data["K"],
-             data["global_index"])
-    b.run(prm)
-    b.sync()
-    out = b.download()
-    b.close()
-    return data, out
-
-
-def _check_batch_against_oracle(data, out, prm, n1=None, n2=None):
-    count = len(out["results"])
-    for i in range(count):
-        a1 = data["n1"][i] if n1 is None else n1[i]
-        a2 = data["n2"][i] if n2 is None else n2[i]
-        oprm = o.make_params(prm.num_hypotheses, prm.sampler, prm.seed + int(data["global_index"][i]),
-                             prm.max_error_sq, prm.min_inliers)
-        ref = o.image_pair(data["desc1"][i][:a1], data["kp1"][i][:a1], data["desc2"][i][:a2], data["kp2"][i][:a2],
-                           data["K"][i].reshape(3, 3), oprm, prm.ratio, prm.max_dist)
-        r = out["results"][i]
-        M = ref["n_matches"]
-        assert r["n_matches"] == M
-        assert out["matches"][i][:M].tobytes() == ref["matches"].tobytes()           # match list: bit-exact
-        assert bool(r["valid"]) == ref["ok"]
-        assert r["best_hyp"] == ref["best_hyp"] and r["best_count"] == ref["best_count"]
-        assert np.array_equal(out["mask"][i][:M], ref["mask"])                        # inlier set: bit-exact
-        if ref["ok"]:
-            n = ref["n_points"]
-            assert r["n_points"] == n and r["n_inliers"] == ref["n_inliers"]
-            assert np.array_equal(out["point_idx"][i][:n], ref["point_idx"])
-            assert helpers.rel_err(out["points"][i][:n], ref["points"]) <= REL_TOL
-            assert helpers.rel_err(r["R"], ref["R"]) <= REL_TOL and helpers.rel_err(r["t"], ref["t"]) <= REL_TOL
-            assert helpers.rel_err(out["points"][i][:n], ref["points"]) <= TIGHT
-            assert helpers.rel_err(r["R"], ref["R"]) <= TIGHT and helpers.rel_err(r["t"], ref["t"]) <= TIGHT
-
-
 def test_batch_pipeline_parity_healthy(ctx):
     """8 pairs x 600 keypoints, 0.5 px noise, explicit threshold: the whole path incl. triangulation."""
     prm = capi.default_params(num_hypotheses=1024, sampler=capi.SAMPLER_PHILOX, seed=0x5EED0000, max_error_sq=1e-2)

@@ -270,7 +270,7 @@ def test_full_population_device_audit():
     assert p.returncode == 0, (p.stdout[-3000:], p.stderr[-3000:])
     st = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     print(json.dumps(st))
-    assert st["ok"] and len(st["cases"]) == 3
+    assert st["ok"] and len(st["cases"]) == 4
     assert st["stage_binary"] == "libmvslam_hip.so" and st["audit_binary"] == "libmvslam_hip_dbg.so"
     assert st["negative_control"]["count_viol"] > 0          # the checker trips when it should
     c3 = st["cases"][0]
@@ -281,3 +281,9 @@ def test_full_population_device_audit():
     assert st["cases"][1]["pairs_mode"][0] == 64                                # the reference threshold: every pair exact
     for c in st["cases"]:
         assert c["phase1"]["count_viol"] == 0 and c["phase1"]["max_sweeps9"] <= 30
+    mixed = st["cases"][3]                                                        # a K per pair, five camera families
+    assert mixed["pairs"] == 20 and mixed["hypotheses"] == 20 * 50000
+    for ph in ("phase1", "phase2"):
+        c = mixed[ph]
+        assert c["count_viol"] == 0 and c["band_viol"] == 0 and c["upper_viol"] == 0, (ph, c)
+        assert c["worst_ratio"] < 1.0 and c["checked"] > 0, (ph, c)

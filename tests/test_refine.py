@@ -69,7 +69,16 @@ def sfm_residuals(pb, prm_sig=(1e-5, 1e-2, 1e-2)):
 
 
 def test_oracle_sfm_refine_is_the_minimiser():
-    pb = two_view_problem(1, 12)
+    _check_sfm_minimiser(two_view_problem(1, 12))
+
+
+@pytest.mark.parametrize("name", list(h.K_REFINE))
+def test_oracle_sfm_refine_is_the_minimiser_at_general_K(name):
+    """the same check at a skewed, anisotropic K and at a short lens with the principal point far off centre"""
+    _check_sfm_minimiser(two_view_problem(1, 12, K=h.K_REFINE[name]))
+
+
+def _check_sfm_minimiser(pb):
     res = o.sfm_refine(pb["p1"], pb["cov"], pb["p2"], pb["cov"], pb["K"], pb["Rg"], pb["tg"], pb["Xg"])
     assert res["ok"] and res["iterations"] < 20
     resid, x0 = sfm_residuals(pb)
@@ -84,8 +93,16 @@ def test_oracle_sfm_refine_is_the_minimiser():
 
 
 def test_oracle_covariances_match_finite_difference_hessian():
-    pb = two_view_problem(2, 10)
-    m = 10
+    _check_covariances(two_view_problem(2, 10))
+
+
+@pytest.mark.parametrize("name", list(h.K_REFINE))
+def test_oracle_covariances_match_finite_difference_hessian_at_general_K(name):
+    _check_covariances(two_view_problem(2, 10, K=h.K_REFINE[name]))
+
+
+def _check_covariances(pb):
+    m = len(pb["Xg"])
     res = o.sfm_refine(pb["p1"], pb["cov"], pb["p2"], pb["cov"], pb["K"], pb["Rg"], pb["tg"], pb["Xg"])
     K, Rg, tg, Xg, sig = pb["K"], pb["Rg"], pb["tg"], pb["Xg"], pb["sig"]
 
@@ -162,8 +179,16 @@ def pnp_problem(seed, m, K=None):
 
 
 def test_oracle_pnp_refine_is_the_minimiser():
-    pb = pnp_problem(5, 20)
-    m = 20
+    _check_pnp_minimiser(pnp_problem(5, 20))
+
+
+@pytest.mark.parametrize("name", list(h.K_REFINE))
+def test_oracle_pnp_refine_is_the_minimiser_at_general_K(name):
+    _check_pnp_minimiser(pnp_problem(5, 20, K=h.K_REFINE[name]))
+
+
+def _check_pnp_minimiser(pb):
+    m = len(pb["X"])
     res = o.pnp_refine(pb["X"], pb["wcov"], pb["uv"], pb["icov"], pb["K"], pb["Rg"], pb["tg"])
     assert res["ok"]
     Lw = np.linalg.cholesky(np.linalg.inv(pb["wcov"]))   # info = L L^T -> whitened residual L^T d
@@ -193,18 +218,17 @@ def test_oracle_cheirality_point_does_not_break_the_solve():
     assert np.abs(res["t"] - pb["t_true"]).max() < 0.05
 
 
-def track_refine_problem(seed, m, n_new):
+def track_refine_problem(seed, m, n_new, K=None, sig=0.5):
     """the shape of VisualOdometer::track_refine (front-end/visual-odometer.cpp:618-800): the last frame anchored at its
     own pose, the new frame regularised, tracked points with isotropic priors, n_new new points without any, and each
     frame missing some observations (every point keeps at least one; prior-less points keep both)"""
     rng = np.random.default_rng(seed)
-    K = np.array([[525.0, 0, 320], [0, 525, 240], [0, 0, 1]])
+    K = np.array([[525.0, 0, 320], [0, 525, 240], [0, 0, 1]]) if K is None else K
     X = np.stack([rng.uniform(-2, 2, m), rng.uniform(-1.5, 1.5, m), rng.uniform(4, 9, m)], 1)
     Ra = Rot.from_rotvec([0.02, -0.1, 0.03]).as_matrix()
     ta = np.array([0.4, -0.1, 0.2])
     Rb = Ra @ Rot.from_rotvec(rng.normal(0, 0.02, 3)).as_matrix()
     tb = ta + np.array([0.3, 0.02, 0.05])
-    sig = 0.5
     obs = [proj(K, Ra, ta, X) + rng.normal(0, sig, (m, 2)), proj(K, Rb, tb, X) + rng.normal(0, sig, (m, 2))]
     cov = np.tile((np.eye(2) * sig ** 2).reshape(4), (m, 1))
     has_prior = np.ones(m, bool)
@@ -224,8 +248,27 @@ def track_refine_problem(seed, m, n_new):
 
 
 def test_oracle_ba_refine_general_two_frame_problem_is_the_minimiser():
-    pb = track_refine_problem(3, 24, 5)
-    m = 24
+    _check_ba_minimiser(track_refine_problem(3, 24, 5))
+    # sfm_refine is the special case: camera 1 at the identity, sigma 1e-5 / 1e-2, all points with sigma 1e-2
+    tv = two_view_problem(1, 12)
+    a = o.sfm_refine(tv["p1"], tv["cov"], tv["p2"], tv["cov"], tv["K"], tv["Rg"], tv["tg"], tv["Xg"])
+    poses = np.stack([np.concatenate([np.eye(3).reshape(9), np.zeros(3)]), np.concatenate([tv["Rg"].reshape(9), tv["tg"]])])
+    b = o.ba_refine(tv["K"], poses, np.stack([np.full(6, 1e-10), np.full(6, 1e-4)]), tv["Xg"],
+                    np.tile((np.eye(3) * 1e-4).reshape(9), (12, 1)), [tv["p1"], tv["p2"]], [tv["cov"], tv["cov"]], [None, None])
+    assert np.abs(a["R"] - b["R"][1]).max() < 1e-12 and np.abs(a["t"] - b["t"][1]).max() < 1e-12
+    assert np.abs(a["pose_cov"] - b["pose_cov"][1]).max() <= 1e-9 * np.abs(a["pose_cov"]).max()
+
+
+@pytest.mark.parametrize("name", list(h.K_REFINE))
+def test_oracle_ba_refine_general_two_frame_problem_is_the_minimiser_at_general_K(name):
+    K = h.K_REFINE[name]
+    # the same angular noise as at f = 525 (0.5 px there): a short lens at 0.5 px leaves a valley so flat that the LM stopping
+    # point and scipy's differ by ~1e-8 in t at equal cost (2e-14 relative)
+    _check_ba_minimiser(track_refine_problem(3, 24, 5, K=K, sig=0.5 * K[0, 0] / 525.0))
+
+
+def _check_ba_minimiser(pb):
+    m = len(pb["Xg"])
     res = o.ba_refine(pb["K"], pb["poses"], pb["var"], pb["Xg"], pb["pcov"], pb["obs"], pb["cov"], pb["valid"])
     assert res["ok"]
     Rg = [pb["poses"][f][:9].reshape(3, 3) for f in range(2)]
@@ -253,14 +296,6 @@ def test_oracle_ba_refine_general_two_frame_problem_is_the_minimiser():
     assert np.abs(sol.x[12:].reshape(m, 3) - res["points"]).max() < 1e-7
     # the anchored frame barely moves, the new frame gets close to the truth
     assert np.abs(res["t"][0] - tg[0]).max() < 1e-3 and np.abs(res["t"][1] - pb["tb"]).max() < 0.02
-    # sfm_refine is the special case: camera 1 at the identity, sigma 1e-5 / 1e-2, all points with sigma 1e-2
-    tv = two_view_problem(1, 12)
-    a = o.sfm_refine(tv["p1"], tv["cov"], tv["p2"], tv["cov"], tv["K"], tv["Rg"], tv["tg"], tv["Xg"])
-    poses = np.stack([np.concatenate([np.eye(3).reshape(9), np.zeros(3)]), np.concatenate([tv["Rg"].reshape(9), tv["tg"]])])
-    b = o.ba_refine(tv["K"], poses, np.stack([np.full(6, 1e-10), np.full(6, 1e-4)]), tv["Xg"],
-                    np.tile((np.eye(3) * 1e-4).reshape(9), (12, 1)), [tv["p1"], tv["p2"]], [tv["cov"], tv["cov"]], [None, None])
-    assert np.abs(a["R"] - b["R"][1]).max() < 1e-12 and np.abs(a["t"] - b["t"][1]).max() < 1e-12
-    assert np.abs(a["pose_cov"] - b["pose_cov"][1]).max() <= 1e-9 * np.abs(a["pose_cov"]).max()
 
 
 def _golden():
