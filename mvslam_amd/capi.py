@@ -13,7 +13,7 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "lib", "libmvslam_hip.so")
 # diagnostics build with the mvs_debug_* hooks (make -C mvslam_amd/csrc): never loaded by this package unless a tool asks
-# for it explicitly with MVS_USE_DEBUG_LIB=1 (tools/ab_ransac.py) -- tests load it side by side through ctypes
+# for it explicitly with MVS_USE_DEBUG_LIB=1 (tools/margin_sweep.py) -- tests load it side by side through ctypes
 DBG_LIB_PATH = os.path.join(_PKG, "lib", "libmvslam_hip_dbg.so")
 if os.environ.get("MVS_USE_DEBUG_LIB") == "1":
     LIB_PATH = DBG_LIB_PATH

@@ -457,15 +457,7 @@ int mvs_debug_pairstep_check(mvs_ctx *ctx, const double *rows, int n, unsigned l
     return e == hipSuccess ? MVS_OK : MVS_ERR_HIP;
 }
 
-// diagnostics only (not in the public header): pick a co-compiled ransac_kernel variant for A/B timing
-int mvs_debug_set_ransac_variant(int v)
-{
-    const int old = get_ransac_variant();
-    set_ransac_variant(v);
-    return old;
-}
-
-// diagnostics only: the per-hypothesis F records the solve launch handed to the scoring launch (pair `pair` of a batch)
+// diagnostics only (not in the public header): the counting variant of the pre-screened stage (kernels.hpp: set_count_dense)
 int mvs_debug_set_count_dense(int v)
 {
     set_count_dense(v);

@@ -73,23 +73,9 @@ MVS_DEV double sqrt_fast(double x)
     return (x == 0.0 || x == __builtin_inf()) ? x : g;
 }
 // sqrt_fast for operands known to be finite and non-zero (inside a guarded range): without the final 0 / inf select
-// (v_cmp_class + two v_cndmask).  The result for such x is the same correctly rounded root.
-MVS_DEV double sqrt_fast_nz(double x)
-{
-    const double y = __builtin_amdgcn_rsq(x);
-    double g = x * y;
-    double h = y * 0.5;
-    const double r = dfma(-h, g, 0.5);
-    g = dfma(g, r, g);
-    h = dfma(h, r, h);
-    double d = dfma(-g, g, x);
-    g = dfma(d, h, g);
-    d = dfma(-g, g, x);
-    g = dfma(d, h, g);
-    return g;
-}
-// sqrt_fast_nz that also hands out its by-product h ~ 1 / (2 sqrt(x)): the refined half reciprocal root of the
-// sequence (relative error ~2^-50 after the one quadratic refinement of the 2^-26 v_rsq_f64 seed)
+// (v_cmp_class + two v_cndmask); the result for such x is the same correctly rounded root.  It also hands out its
+// by-product h ~ 1 / (2 sqrt(x)): the refined half reciprocal root of the sequence (relative error ~2^-50 after the one
+// quadratic refinement of the 2^-26 v_rsq_f64 seed)
 MVS_DEV double sqrt_fast_nz_h(double x, double &h_out)
 {
     const double y = __builtin_amdgcn_rsq(x);
@@ -149,8 +135,9 @@ MVS_DEV double div_fast(double n, double d)
 //     and 4p^2 = 4q exactly, so q >= 2^-398 gives both lower bounds; and g2 <= (a + b)^2 (Cauchy-Schwarz), where a + b
 //     is bounded by the squared Frobenius norm of the matrix, which rotations preserve: checked ONCE before the sweeps
 //     (jacobi_svd_core: sum W <= 2^198).  Exec-masked lanes do not update the minimum, exactly like the flag.
-// (3) (gamma - beta) * 0.5 for beta < 0 and gamma + beta otherwise are both (gamma + |beta|) times an exact power of
-//     two: one add and one multiply by a selected constant replace two candidates and a 64-bit select (same for den).
+// (3) ((gamma - beta) / 2) / gamma for beta < 0 and (gamma + beta) / (2 gamma) otherwise are the same real number
+//     (t / 2) / gamma, t = gamma + |beta|: one add replaces two candidates and a 64-bit select, and the two divisions take
+//     their reciprocal estimates from the by-products of the two square roots (div_seeded).
 constexpr double kJacobiE2Hi = (kJacobiEps * kJacobiEps) * (1.0 + 2e-14);
 constexpr double kJacobiE2Lo = (kJacobiEps * kJacobiEps) * (1.0 - 2e-14);
 constexpr double kJacobiTau = 0x1p-900;
@@ -160,7 +147,7 @@ constexpr double kGuardWSumMax = 0x1p198;
 // v_min_f64 without the canonicalising v_max x, x that __builtin_fmin emits for each operand
 MVS_DEV void running_min(double &m, double x) { asm("v_min_f64 %0, %0, %1" : "+v"(m) : "v"(x)); }
 
-template <int M, int N, bool HAS_V, bool INPLACE, bool FAST, bool CHEAP = false>
+template <int M, int N, bool INPLACE, bool FAST, bool CHEAP = false>
 MVS_DEV void jacobi_pair(double (&Ai)[M], double (&Aj)[M], double (&Vi)[N], double (&Vj)[N], double &Wi, double &Wj,
                          bool &changed, unsigned &rot, bool &bad, double &qmin)
 {
@@ -200,7 +187,6 @@ MVS_DEV void jacobi_pair(double (&Ai)[M], double (&Aj)[M], double (&Vi)[N], doub
         if (FAST) {
             // with gamma and |p| in [2^-200, 2^200] every sqrt / div operand below is far from the ends of the
             // exponent range (num, den in [gamma/2, 2 gamma]; num/den in [1/2, 1]); otherwise flag the lane
-            double num, den;
             if (CHEAP) {
                 running_min(qmin, q);
             } else {
@@ -208,7 +194,6 @@ MVS_DEV void jacobi_pair(double (&Ai)[M], double (&Aj)[M], double (&Vi)[N], doub
             }
             // CHEAP: g2 >= 2^-400 and num / den in [1/2, 1] are guarded (a violated guard recomputes the wavefront with
             // the full sequences), so neither root needs sqrt_fast's zero / infinity select
-#ifndef MVS_NO_SEEDED_DIV
             if (CHEAP) {
                 // ((gamma - beta) / 2) / gamma for beta < 0 and (gamma + beta) / (2 gamma) otherwise are the SAME real
                 // number (t / 2) / gamma, t = gamma + |beta| (the halvings / doublings are exact inside the guard, so
@@ -219,22 +204,12 @@ MVS_DEV void jacobi_pair(double (&Ai)[M], double (&Aj)[M], double (&Vi)[N], doub
                 const double t = gamma + dabs(beta);
                 x = sqrt_fast_nz_h(div_seeded(t * 0.5, gamma, hg + hg), hx);   // hx ~ 1 / (2 x)
                 y = div_seeded(p, gamma * x * 2.0, (hg * hx) * 2.0);
-            } else
-#endif
-            {
-            const double gamma = CHEAP ? sqrt_fast_nz(g2) : sqrt_fast(g2);
-            if (CHEAP) {
-                // gamma - beta == gamma + |beta| for beta < 0, and the halving / doubling are exact inside the guard:
-                // one add and one multiply by a selected power of two replace two candidates and a 64-bit select
-                const double t = gamma + dabs(beta);
-                num = t * __hiloint2double(neg ? 0x3fe00000 : 0x3ff00000, 0);
-                den = gamma * __hiloint2double(neg ? 0x3ff00000 : 0x40000000, 0);
             } else {
-                num = neg ? (gamma - beta) * 0.5 : (gamma + beta);
-                den = neg ? gamma : gamma * 2.0;
-            }
-            x = CHEAP ? sqrt_fast_nz(div_fast(num, den)) : sqrt_fast(div_fast(num, den));
-            y = div_fast(p, gamma * x * 2.0);
+                const double gamma = sqrt_fast(g2);
+                const double num = neg ? (gamma - beta) * 0.5 : (gamma + beta);
+                const double den = neg ? gamma : gamma * 2.0;
+                x = sqrt_fast(div_fast(num, den));
+                y = div_fast(p, gamma * x * 2.0);
             }
         } else {
             const double gamma = dsqrt(g2);
@@ -264,17 +239,15 @@ MVS_DEV void jacobi_pair(double (&Ai)[M], double (&Aj)[M], double (&Vi)[N], doub
         Wj = b;
         changed = true;
         ++rot;
-        if (HAS_V) {
 #pragma unroll
-            for (int k = 0; k < N; ++k) {
-                if (INPLACE) {
-                    rotate_inplace(Vi[k], Vj[k], c, s);
-                } else {
-                    const double t0 = dfma(c, Vi[k], s * Vj[k]);
-                    const double t1 = dfma(c, Vj[k], -(s * Vi[k]));
-                    Vi[k] = t0;
-                    Vj[k] = t1;
-                }
+        for (int k = 0; k < N; ++k) {
+            if (INPLACE) {
+                rotate_inplace(Vi[k], Vj[k], c, s);
+            } else {
+                const double t0 = dfma(c, Vi[k], s * Vj[k]);
+                const double t1 = dfma(c, Vj[k], -(s * Vi[k]));
+                Vi[k] = t0;
+                Vj[k] = t1;
             }
         }
     }
@@ -282,7 +255,7 @@ MVS_DEV void jacobi_pair(double (&Ai)[M], double (&Aj)[M], double (&Vi)[N], doub
 
 // Sweeps until a sweep without rotation (at most max(M, 30)); W ends as singular values.
 // At: N rows of length M.  Vt: N x N, initialised to identity here.
-template <int M, int N, bool INPLACE = false, bool FAST = false, bool HAS_V = true, bool CHEAP = false>
+template <int M, int N, bool INPLACE = false, bool FAST = false, bool CHEAP = false>
 MVS_DEV void jacobi_svd_core(double (&At)[N][M], double (&Vt)[N][N], double (&W)[N], unsigned &rot, unsigned &pairs,
                              bool &bad)
 {
@@ -307,8 +280,7 @@ MVS_DEV void jacobi_svd_core(double (&At)[N][M], double (&Vt)[N][N], double (&W)
         for (int i = 0; i < N - 1; ++i) {
 #pragma unroll
             for (int j = i + 1; j < N; ++j)
-                jacobi_pair<M, N, HAS_V, INPLACE, FAST, CHEAP>(At[i], At[j], Vt[i], Vt[j], W[i], W[j], changed, rot, bad,
-                                                               qmin);
+                jacobi_pair<M, N, INPLACE, FAST, CHEAP>(At[i], At[j], Vt[i], Vt[j], W[i], W[j], changed, rot, bad, qmin);
         }
         pairs += N * (N - 1) / 2;
         if (!changed)
@@ -373,257 +345,13 @@ MVS_DEV void select_row(const double (&Mx)[N][N], int row, double (&out)[N])
     }
 }
 
-// ---------------------------------------------------------------------------------
-// A / V wavefront pair (ransac_solve_av_kernel).  The 9x9 solve of one hypothesis per lane needs A^T (81) + V^T (81)
-// doubles = 324 registers: one wavefront per SIMD, a third of V^T parked in AGPRs, ~50 accumulator moves per rotation,
-// and at one wave per SIMD every instruction of any kind costs a full issue slot.  Split by ROLE instead: the A-wave
-// owns A^T, decides and computes every rotation (c, s) exactly as jacobi_pair does and applies it to A^T; the V-wave
-// (same lanes = same hypotheses, same SIMD) owns V^T and applies the SAME (c, s) to it.  Each fits in 256 registers,
-// so both are resident on the SIMD: two waves per SIMD, no AGPR traffic, and the V-wave's 36 fp64 instructions per
-// rotation issue in the shadow of the A-wave's dependent sqrt / div chains.  Every rotation is the same operation on
-// the same operands in the same order as in the single-wave form: bit-identical results.
-//
-// Channel (LDS, one per pair): a ring of kAvRing slots, slot = visit number mod kAvRing.  Per (i, j) visit the A-wave
-// writes (c, s) of its rotating lanes, then the 64-bit mask of rotating lanes, then the slot's sequence number
-// (release); the V-wave polls the sequence number (acquire), reads the mask and, where set, (c, s).  Both walk the
-// same static (i, j) order; the V-wave derives the end of the loop from the masks (a sweep without any rotation).
-// LDS operations of one wavefront execute in order, so data -> mask -> sequence needs no further fence than the
-// compiler-level release / acquire.  Every spin is bounded: a stuck partner raises `abort`, both leave, the
-// hypotheses are reported as failed -- the grid always drains.
-constexpr int kAvRing = 8;
-constexpr unsigned kAvSpinLimit = 1u << 22;
-
-typedef double av_dbl2 __attribute__((ext_vector_type(2)));   // plain vector type: volatile LDS accesses (ds_*_b128)
-
-struct AvChannel {
-    av_dbl2 cs[kAvRing][64];
-    unsigned long long mask[kAvRing];
-    unsigned seq[kAvRing];
-    unsigned cons;     // visits the V-wave has consumed (published every 4th visit)
-    unsigned abort;
-    unsigned fin_a, fin_v;
-    int tag8[64];
-    double f[9][64];
-};
-
-// LDS operations of one wavefront are executed in program order by the LDS unit, so "data, then mask, then sequence
-// number" needs no s_waitcnt between the stores: plain volatile accesses plus a compiler barrier (an atomic release
-// store would drain lgkmcnt before every sequence-number write: ~250 stalls of an LDS round trip per hypothesis)
-MVS_DEV unsigned av_load(const unsigned *p)
-{
-    const unsigned v = *(const volatile unsigned *)p;
-    asm volatile("" ::: "memory");
-    return (unsigned)__builtin_amdgcn_readfirstlane((int)v);
-}
-MVS_DEV void av_store(unsigned *p, unsigned v)
-{
-    asm volatile("" ::: "memory");
-    *(volatile unsigned *)p = v;
-}
-// wait until *p - want >= 0 (wrap-safe); false = gave up (abort raised).  SLEEP: s_sleep argument between polls (x 64
-// clocks): the V-wave has ~400 clocks of slack per visit, every poll costs a VALU slot (v_readfirstlane)
-template <int SLEEP = 1>
-MVS_DEV bool av_wait_ge(AvChannel &ch, const unsigned *p, unsigned want)
-{
-    unsigned spins = 0;
-#pragma nounroll
-    while ((int)(av_load(p) - want) < 0) {
-        __builtin_amdgcn_s_sleep(SLEEP);
-        if ((++spins & 63u) == 0 && (spins > kAvSpinLimit || av_load(&ch.abort))) {
-            av_store(&ch.abort, 1u);
-            return false;
-        }
-    }
-    return true;
-}
-
-// The 36 (i, j) visits of a sweep are expanded by template recursion: every row index is a compile-time constant, so
-// A^T / V^T stay in registers (with #pragma unroll the outer loop was not unrolled around the spin loops and the
-// matrices were demoted to scratch memory).
-struct AState {
-    double W[9];
-    double qmin;
-    unsigned visit, cons_seen;
-    bool active, alive, changed;
-};
-
-template <int I, int J>
-MVS_DEV void av_A_visit(double (&At)[9][9], AState &st, AvChannel &ch, int lane)
-{
-    double (&Ai)[9] = At[I];
-    double (&Aj)[9] = At[J];
-    double a = st.W[I], b = st.W[J], p = 0.0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-        p = dfma(Ai[k], Aj[k], p);
-    const double ab = a * b;
-    const double q = p * p;
-    const bool hi = q > dfma(ab, kJacobiE2Hi, kJacobiTau);
-    const bool lo = q < dfma(ab, kJacobiE2Lo, -kJacobiTau);
-    bool rotate = hi;
-    if (__builtin_expect(__any(!hi && !lo), 0))
-        rotate = !(dabs(p) <= kJacobiEps * dsqrt(a * b));
-    rotate = rotate && st.active;
-    const unsigned long long m = __ballot(rotate);
-    const unsigned slot = st.visit & (kAvRing - 1);
-    if (__builtin_expect(st.visit - st.cons_seen >= (unsigned)kAvRing, 0)) {   // ring full as far as this wave knows
-        st.alive = st.alive && av_wait_ge(ch, &ch.cons, st.visit - kAvRing + 1);
-        st.cons_seen = av_load(&ch.cons);
-    }
-    if (rotate) {
-        p *= 2.0;
-        const double beta = a - b;
-        const double g2 = dfma(p, p, beta * beta);
-        const bool neg = beta < 0.0;
-        running_min(st.qmin, q);
-        const double gamma = sqrt_fast_nz(g2);
-        const double t = gamma + dabs(beta);
-        const double num = t * __hiloint2double(neg ? 0x3fe00000 : 0x3ff00000, 0);
-        const double den = gamma * __hiloint2double(neg ? 0x3ff00000 : 0x40000000, 0);
-        const double x = sqrt_fast_nz(div_fast(num, den));
-        const double y = div_fast(p, gamma * x * 2.0);
-        const double c = neg ? y : x;
-        const double s = neg ? x : y;
-        const av_dbl2 csv = {c, s};
-        *(volatile av_dbl2 *)&ch.cs[slot][lane] = csv;
-        a = 0.0;
-        b = 0.0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            rotate_inplace(Ai[k], Aj[k], c, s);
-            a = dfma(Ai[k], Ai[k], a);
-            b = dfma(Aj[k], Aj[k], b);
-        }
-        st.W[I] = a;
-        st.W[J] = b;
-        st.changed = true;
-    }
-    if (lane == 0) {
-        *(volatile unsigned long long *)&ch.mask[slot] = m;
-        av_store(&ch.seq[slot], st.visit + 1);
-    }
-    ++st.visit;
-    if constexpr (J < 8)
-        av_A_visit<I, J + 1>(At, st, ch, lane);
-    else if constexpr (I < 7)
-        av_A_visit<I + 1, I + 2>(At, st, ch, lane);
-}
-
-// A-wave: jacobi_svd_core<9, 9, INPLACE, FAST, /*HAS_V*/ false, CHEAP> with a wave-uniform sweep loop (a converged
-// lane stays in the loop, inactive: it would not rotate again anyway -- its state no longer changes) and the channel
-// writes.  W ends as the singular values.  Returns false if the partner was lost.
-MVS_DEV bool jacobi_A_wave(double (&At)[9][9], double (&W)[9], AvChannel &ch, int lane, bool &bad)
-{
-    AState st;
-    double wsum = 0.0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        double sd = 0.0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-            sd = dfma(At[i][k], At[i][k], sd);
-        st.W[i] = sd;
-        wsum += sd;
-    }
-    st.qmin = 0x1p1000;
-    st.visit = 0;
-    st.cons_seen = 0;
-    st.active = true;
-    st.alive = true;
-    for (int iter = 0; iter < 30; ++iter) {
-        st.changed = false;
-        av_A_visit<0, 1>(At, st, ch, lane);
-        st.active = st.active && st.changed;
-        if (!__any(st.active) || !st.alive)
-            break;
-    }
-    bad = bad || !((st.qmin >= kGuardQMin) && (wsum <= kGuardWSumMax));
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        double sd = 0.0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-            sd = dfma(At[i][k], At[i][k], sd);
-        W[i] = dsqrt(sd);
-    }
-    return st.alive;
-}
-
-struct VState {
-    unsigned visit;
-    unsigned long long any;
-    bool alive;
-};
-
-template <int I, int J>
-MVS_DEV void av_V_visit(double (&Vt)[9][9], VState &st, AvChannel &ch, int lane)
-{
-    const unsigned slot = st.visit & (kAvRing - 1);
-    st.alive = st.alive && av_wait_ge<1>(ch, &ch.seq[slot], st.visit + 1);
-    const unsigned long long mv = *(const volatile unsigned long long *)&ch.mask[slot];
-    // the builtin returns a SIGNED int: widen through unsigned, or bit 31 smears over the upper half of the mask
-    const unsigned m_hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(mv >> 32));
-    const unsigned m_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)mv);
-    const unsigned long long m = ((unsigned long long)m_hi << 32) | (unsigned long long)m_lo;
-    st.any |= m;
-    if (st.alive && ((m >> lane) & 1ull)) {
-        const av_dbl2 cs = *(const volatile av_dbl2 *)&ch.cs[slot][lane];
-        const double c = cs.x, s = cs.y;
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-            rotate_inplace(Vt[I][k], Vt[J][k], c, s);
-    }
-    ++st.visit;
-    if ((st.visit & 3u) == 0 && lane == 0)
-        av_store(&ch.cons, st.visit);
-    if constexpr (J < 8)
-        av_V_visit<I, J + 1>(Vt, st, ch, lane);
-    else if constexpr (I < 7)
-        av_V_visit<I + 1, I + 2>(Vt, st, ch, lane);
-}
-
-// V-wave: follows the A-wave's rotations on V^T (initialised to the identity here), then hands back the row of V^T the
-// A-wave names (the right singular vector of the smallest singular value).
-MVS_DEV void jacobi_V_wave(AvChannel &ch, int lane)
-{
-    double Vt[9][9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i)
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-            Vt[i][k] = (i == k) ? 1.0 : 0.0;
-    VState st;
-    st.visit = 0;
-    st.alive = true;
-    for (int iter = 0; iter < 30; ++iter) {
-        st.any = 0;
-        av_V_visit<0, 1>(Vt, st, ch, lane);
-        if (st.any == 0 || !st.alive)
-            break;
-    }
-    if (lane == 0)
-        av_store(&ch.cons, st.visit + kAvRing);   // nothing left to wait for on the A side
-    if (!(st.alive && av_wait_ge(ch, &ch.fin_a, 1u)))
-        return;
-    const int row = ch.tag8[lane];
-    double f[9];
-    select_row<9>(Vt, row, f);
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-        ch.f[k][lane] = f[k];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (lane == 0)
-        av_store(&ch.fin_v, 1u);
-}
-
 // Null vector of a symmetric 9x9 matrix B (= A^T A): last row of vt of cv::SVDecomp(B).
-// HAS_V = false: TIMING EXPERIMENT ONLY (V is never rotated, the result is meaningless)
-template <bool INPLACE, bool FAST, bool HAS_V = true, bool CHEAP = false>
+template <bool INPLACE, bool FAST, bool CHEAP = false>
 MVS_DEV void svd9_last_vt_row(double (&At)[9][9], double (&f)[9], unsigned &rot, unsigned &pairs, bool &bad)
 {
     double Vt[9][9], W[9];
     int tag[9];
-    jacobi_svd_core<9, 9, INPLACE, FAST, HAS_V, CHEAP>(At, Vt, W, rot, pairs, bad);
+    jacobi_svd_core<9, 9, INPLACE, FAST, CHEAP>(At, Vt, W, rot, pairs, bad);
     sort_tags_desc<9>(W, tag);
     select_row<9>(Vt, tag[8], f);
 }
@@ -636,7 +364,7 @@ MVS_DEV void svd4_last_vt_row(double (&At)[4][4], double (&x)[4], unsigned &rot,
 {
     double Vt[4][4], W[4];
     int tag[4];
-    jacobi_svd_core<4, 4, GUARDED, GUARDED, true, GUARDED>(At, Vt, W, rot, pairs, bad);
+    jacobi_svd_core<4, 4, GUARDED, GUARDED, GUARDED>(At, Vt, W, rot, pairs, bad);
     sort_tags_desc<4>(W, tag);
     select_row<4>(Vt, tag[3], x);
 }
@@ -667,7 +395,7 @@ MVS_DEV void svd3_full(const double (&A)[3][3], double (&w)[3], double (&U)[3][3
 #pragma unroll
         for (int k = 0; k < 3; ++k)
             At[i][k] = A[k][i];
-    jacobi_svd_core<3, 3, INPLACE, FAST, true, CHEAP>(At, Vt, W, rot, pairs, bad3);
+    jacobi_svd_core<3, 3, INPLACE, FAST, CHEAP>(At, Vt, W, rot, pairs, bad3);
     // selection sort with physical row swaps (N = 3: cheap)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -914,10 +642,20 @@ MVS_DEV void denormalise_exact(const double (&Fn)[3][3], const EightNorm &nm, do
     }
 }
 
+// The three configurations of the eight-point solve.  All three compute the same F bit for bit wherever the guards hold;
+// they differ in what one Jacobi pair step costs.  The 9x9 solve rotates in place (rotate_inplace) in all of them.
+//   Ieee          the compiler's fully scaled sqrt / div sequences in both SVDs: the contract itself.  The recompute of a
+//                 wavefront after a raised `bad` flag, and the reference of the audit.
+//   Guarded       9x9: the unscaled sequences (sqrt_fast / div_fast) behind per-operand range guards; a violated guard
+//                 raises `bad` and the caller recomputes with Ieee.  3x3: as Ieee.  The instrumented replay of the fused
+//                 kernel runs it (its rotation counters feed the benchmark's flop model).
+//   GuardedCheap  the product solve: the CHEAP pair step (sqrt-free convergence test, one running minimum as the range
+//                 guard, seeded divisions; see jacobi_pair) in the 9x9 and, in place, in the 3x3 SVD too.
+enum class Solve { Ieee, Guarded, GuardedCheap };
+
 // back half: rank-2 enforcement (:127-136) and de-normalisation (:245) of the null vector f
-// VAR bit 1024 (with 32 and 128): the 3x3 SVD with the unscaled sequences too
 // wout: the singular values of reshape(f) as the 3x3 Jacobi computed them (the pre-screen's gap test reads them)
-template <int VAR = 0>
+template <Solve S>
 MVS_DEV void eight_point_back(const double (&f)[9], const EightNorm &nm, double (&F)[9], bool &bad, double (&wout)[3])
 {
     double Fn[3][3];
@@ -925,8 +663,8 @@ MVS_DEV void eight_point_back(const double (&f)[9], const EightNorm &nm, double 
         double Fp[3][3] = {{f[0], f[1], f[2]}, {f[3], f[4], f[5]}, {f[6], f[7], f[8]}};
         double w[3], U[3][3], Vt[3][3];
         unsigned r3 = 0, p3 = 0;
-        constexpr bool F3 = (VAR & (32 | 128 | 1024)) == (32 | 128 | 1024);
-        svd3_full<F3 && (VAR & 16) != 0, F3, F3>(Fp, w, U, Vt, r3, p3, bad);
+        constexpr bool kCheap = S == Solve::GuardedCheap;
+        svd3_full<kCheap, kCheap, kCheap>(Fp, w, U, Vt, r3, p3, bad);
         wout[0] = w[0]; wout[1] = w[1]; wout[2] = w[2];
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -939,16 +677,14 @@ MVS_DEV void eight_point_back(const double (&f)[9], const EightNorm &nm, double 
     denormalise_exact(Fn, nm, F);
 }
 
-template <int VAR = 0>
+template <Solve S>
 MVS_DEV void eight_point_back(const double (&f)[9], const EightNorm &nm, double (&F)[9], bool &bad)
 {
     double w[3];
-    eight_point_back<VAR>(f, nm, F, bad, w);
+    eight_point_back<S>(f, nm, F, bad, w);
 }
 
-// VAR: 16 = in-place rotation; 32 = unscaled sqrt / div sequences (flag + recompute);
-// 128 (with 32) = sqrt-free convergence test, range record instead of per-operand flags, selected power-of-two factors
-template <int VAR>
+template <Solve S>
 MVS_DEV bool eight_point(const double (&x1)[8], const double (&y1)[8], const double (&x2)[8], const double (&y2)[8],
                          double (&F)[9], unsigned &rot9, unsigned &pairs9, bool &bad)
 {
@@ -958,9 +694,9 @@ MVS_DEV bool eight_point(const double (&x1)[8], const double (&y1)[8], const dou
     {
         double At[9][9];
         ok = eight_point_front(x1, y1, x2, y2, At, nm);
-        svd9_last_vt_row<(VAR & 16) != 0, (VAR & 32) != 0, (VAR & 256) == 0, (VAR & 128) != 0>(At, f, rot9, pairs9, bad);
+        svd9_last_vt_row<true, S != Solve::Ieee, S == Solve::GuardedCheap>(At, f, rot9, pairs9, bad);
     }
-    eight_point_back<VAR>(f, nm, F, bad);
+    eight_point_back<S>(f, nm, F, bad);
     return ok;
 }
 

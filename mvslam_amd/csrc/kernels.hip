@@ -462,11 +462,8 @@ __device__ __forceinline__ double pair_max_error_sq(const BatchDev &b, const Run
     return 5e-2 / K[0] / K[4];  // sfm-solve.cpp:311
 }
 
-// VAR (co-compiled A/B variants): 8 = point stream staged in LDS (broadcast ds_read_b128: in order, so the compiler
-// keeps many in flight; scalar loads return out of order and drain at every batch), 16 = in-place rotation,
-// 32 = unscaled sqrt/div behind a range guard, 64 = mask-multiply residual accumulation
-// sample 8 matches, gather them, fit F (one hypothesis, one lane)
-template <int VAR>
+// sample 8 matches, gather them, fit F (one hypothesis, one lane); S: the configuration of the solve (device_math.hpp)
+template <Solve S>
 __device__ __forceinline__ bool solve_hypothesis(uint64_t seed, uint32_t hyp, int M, int sampler, const double *P,
                                                  double (&F)[9], unsigned &rot, unsigned &pairs, bool &bad)
 {
@@ -478,10 +475,13 @@ __device__ __forceinline__ bool solve_hypothesis(uint64_t seed, uint32_t hyp, in
         const double4 p = *reinterpret_cast<const double4 *>(P + (size_t)idx[k] * 4);
         x1[k] = p.x; y1[k] = p.y; x2[k] = p.z; y2[k] = p.w;
     }
-    return eight_point<VAR>(x1, y1, x2, y2, F, rot, pairs, bad);
+    return eight_point<S>(x1, y1, x2, y2, F, rot, pairs, bad);
 }
 
-template <bool STATS, int VAR>
+// The fused kernel: solve + hypothesis-per-lane scoring in one launch.  STAGED: the pair's point stream is staged in LDS and
+// scored with broadcast ds_read_b128 (LDS returns in order, so the compiler keeps many reads in flight; scalar loads return out
+// of order and drain at every batch); both instantiations that are launched stage.
+template <bool STATS, bool STAGED, Solve S>
 __global__ __launch_bounds__(256, 1) void ransac_kernel(BatchDev b, RunParams rp)
 {
     const int pair = blockIdx.y, g = blockIdx.x, tid = threadIdx.x;
@@ -503,9 +503,9 @@ __global__ __launch_bounds__(256, 1) void ransac_kernel(BatchDev b, RunParams rp
     const double *P = b.pts + (size_t)pair * b.max_kp * 4;
 
     // rows 1..8 of every lane's Vt (72 doubles x 256 lanes = 144 KB: one workgroup per CU, one wave per SIMD)
-    constexpr int kLdsDoubles = (VAR & 8) ? kMaxKp * 4 : 2;
+    constexpr int kLdsDoubles = STAGED ? kMaxKp * 4 : 2;
     __shared__ __attribute__((aligned(16))) double s_vt[kLdsDoubles];
-    if (VAR & 8) {
+    if (STAGED) {
         // stage the pair's M point pairs (32 B each) in LDS once per workgroup, BEFORE the solve: all four waves
         // arrive here together, so the barrier is free (after the solve it would add the waves' run-time skew)
         const double2 *src = reinterpret_cast<const double2 *>(P);
@@ -517,13 +517,13 @@ __global__ __launch_bounds__(256, 1) void ransac_kernel(BatchDev b, RunParams rp
     double F[9];
     unsigned rot = 0, pairs = 0;
     bool bad = false;
-    bool ok = solve_hypothesis<VAR>(seed, hh, M, rp.sampler, P, F, rot, pairs, bad);
-    if ((VAR & 32) && __builtin_expect(__any(bad), 0)) {
+    bool ok = solve_hypothesis<S>(seed, hh, M, rp.sampler, P, F, rot, pairs, bad);
+    if (S != Solve::Ieee && __builtin_expect(__any(bad), 0)) {
         // an operand left the range in which the unscaled sqrt / div sequences are provably IEEE-exact:
         // recompute this wave's hypotheses with the compiler's fully scaled sequences
         rot = 0;
         pairs = 0;
-        ok = solve_hypothesis<(VAR & ~(32 | 128))>(seed, hh, M, rp.sampler, P, F, rot, pairs, bad);
+        ok = solve_hypothesis<Solve::Ieee>(seed, hh, M, rp.sampler, P, F, rot, pairs, bad);
     }
 
     // score against all M matches.  Every lane reads the SAME point: the address is wave-uniform, but it is made
@@ -534,7 +534,7 @@ __global__ __launch_bounds__(256, 1) void ransac_kernel(BatchDev b, RunParams rp
     const double thr = pair_max_error_sq(b, rp, pair);
     int cnt = 0;
     double res = 0.0;
-    if (VAR & 8) {
+    if (STAGED) {
         // every lane reads the SAME LDS address (broadcast).  LDS returns in order, so the compiler keeps many
         // reads in flight (counted lgkmcnt) instead of draining the scalar-load queue every batch.
         const double4 *L4 = reinterpret_cast<const double4 *>(s_vt);
@@ -621,13 +621,12 @@ __global__ __launch_bounds__(256, 1) void ransac_kernel(BatchDev b, RunParams rp
     }
 }
 
-// ---- split variant (VAR & 512): the solve and the scoring as two launches -----------------------------------------
+// ---- the solve and the scoring as separate launches ------------------------------------------------------------------
 // The fused kernel runs at 1 wave/SIMD (380 registers for the solve), where every non-fp64 instruction of the scoring
 // loop costs a full fp64 issue slot (profiles/r01_fp64_issue_microbench.txt).  Scoring needs 18 registers of state: as
 // its own kernel it runs at 4 waves/SIMD and the compare / count / mask instructions overlap with other waves' FMAs.
 // Price: F of every hypothesis goes through HBM once (72 B x 50 000 x 512 pairs = 1.8 GB written + read per batch).
-// one hypothesis per lane: exact solve, record, state byte
-template <int VAR>
+// one hypothesis per lane: exact solve (the product configuration; Ieee after a raised guard), record, state byte
 __device__ __forceinline__ void solve_record(const BatchDev &b, const RunParams &rp, int pair, int M, uint32_t h)
 {
     const int H = rp.num_hypotheses;
@@ -637,11 +636,11 @@ __device__ __forceinline__ void solve_record(const BatchDev &b, const RunParams 
     double F[9];
     unsigned rot = 0, pairs = 0;
     bool bad = false;
-    bool ok = solve_hypothesis<VAR>(seed, hh, M, rp.sampler, P, F, rot, pairs, bad);
-    if ((VAR & 32) && __builtin_expect(__any(bad), 0)) {
+    bool ok = solve_hypothesis<Solve::GuardedCheap>(seed, hh, M, rp.sampler, P, F, rot, pairs, bad);
+    if (__builtin_expect(__any(bad), 0)) {
         rot = 0;
         pairs = 0;
-        ok = solve_hypothesis<(VAR & ~(32 | 128))>(seed, hh, M, rp.sampler, P, F, rot, pairs, bad);
+        ok = solve_hypothesis<Solve::Ieee>(seed, hh, M, rp.sampler, P, F, rot, pairs, bad);
     }
     const size_t Hp = (size_t)b.max_groups * kHypPerBlock;
     double *Fo = b.hyp_F + ((size_t)pair * Hp + h) * kHypRec;   // one contiguous record per hypothesis (scalar loads in
@@ -689,13 +688,12 @@ __global__ __launch_bounds__(256) void mode0_list_kernel(BatchDev b, int n_activ
 
 // exact solve of every hypothesis of the listed pairs: persistent single-wavefront workgroups striding over
 // (listed pair, block of 64 hypotheses); the list length is fixed before the launch
-template <int VAR>
 __global__ __launch_bounds__(256, 1) void ransac_solve_list_kernel(BatchDev b, RunParams rp, int blocks_per_pair)
 {
     const int n_items = b.m0list[0] * blocks_per_pair;
     for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
         const int pair = b.m0list[1 + item / blocks_per_pair];
-        solve_record<VAR>(b, rp, pair, b.M[pair], (uint32_t)(item % blocks_per_pair) * 64u + threadIdx.x);
+        solve_record(b, rp, pair, b.M[pair], (uint32_t)(item % blocks_per_pair) * 64u + threadIdx.x);
     }
 }
 
@@ -706,10 +704,10 @@ typedef __attribute__((address_space(4))) double CDouble;
 // ---- sound pre-screen of the hypotheses (prescreen.hpp) -------------------------------------------------
 // pair_prepare   grid P          bounding box of the pair's matches; probe of the first 64 hypotheses: a pair is pre-screened
 //                                only if the certified band is useful at its threshold for most of them (otherwise every
-//                                hypothesis of the pair is solved exactly by ransac_solve_kernel, as before)
+//                                hypothesis of the pair is solved exactly by ransac_solve_list_kernel)
 // prescreen      grid (G', P)    approximate F + band per hypothesis -> record; hypotheses without a certificate -> work list
 // exact_list     persistent      exact solve of the listed hypotheses, records overwritten in place (band 0)
-// count2         grid (wg, P)    ransac_count_kernel with one counting threshold per hypothesis: upper bounds prune, lower
+// count2         grid (wg, P)    pruned point-per-lane counting, one counting threshold per hypothesis: upper bounds prune, lower
 //                                bounds of the hypotheses that finish raise the pair's bound
 // survivors      flat            approximate records whose upper bound reaches the final bound -> work list (-> exact_list)
 // select         grid P          exact count + residual of everything at or above the bound (ransac_select_kernel)
@@ -723,17 +721,14 @@ __device__ __forceinline__ PairBox load_box(const BatchDev &b, int pair)
 }
 
 // sample + gather + pre-screen of one hypothesis (one lane)
-template <int VAR>
 __device__ __forceinline__ int prescreen_sample(uint64_t seed, uint32_t hyp, int M, int sampler, const double *P, double *park,
                                                 const PairBox &bx, double thr, double (&F)[9], double &band, double &e32,
                                                 bool &bad3)
 {
     int idx[8];
     sample8(seed, hyp, M, sampler, idx);
-    return prescreen_hypothesis<VAR>(P, idx, park, bx, thr, F, band, e32, bad3);
+    return prescreen_hypothesis(P, idx, park, bx, thr, F, band, e32, bad3);
 }
-
-constexpr int kPsVar = 16 + 32 + 128 + 1024;   // the 3x3 SVD of the pre-screen runs the solve's guarded pair step
 
 __global__ __launch_bounds__(256) void pair_prepare_kernel(BatchDev b, RunParams rp, int force_mode)
 {
@@ -802,8 +797,8 @@ __global__ __launch_bounds__(256) void pair_prepare_kernel(BatchDev b, RunParams
         const uint32_t hh = (uint32_t)min(lane, H - 1);
         double F[9], band, e32;
         bool bad3 = false;
-        int flag = prescreen_sample<kPsVar>(seed, hh, M, rp.sampler, reinterpret_cast<const double *>(P4), s_park + lane, bx, thr,
-                                            F, band, e32, bad3);
+        int flag = prescreen_sample(seed, hh, M, rp.sampler, reinterpret_cast<const double *>(P4), s_park + lane, bx, thr, F, band, e32,
+                                    bad3);
         if (bad3 && flag == kPsApprox)
             flag = kPsNeedExact;
         const bool live = lane < H;
@@ -839,7 +834,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
     const double thr = pair_max_error_sq(b, rp, pair);
     double F[9], band, e32;
     bool bad3 = false;
-    int flag = prescreen_sample<kPsVar>(seed, hh, M, rp.sampler, P, s_park + lane, bx, thr, F, band, e32, bad3);
+    int flag = prescreen_sample(seed, hh, M, rp.sampler, P, s_park + lane, bx, thr, F, band, e32, bad3);
     const int mode = b.mode[pair];
     const double btot = mode == 1 ? band + e32 : band;   // what the counting kernel of this pair has to allow for
     if (flag == kPsApprox && (bad3 || !(btot <= kPsBandFrac * thr)))
@@ -877,7 +872,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
 // exact solve of the hypotheses on the work list (flat indices pair * Hp + h; list `which`).  Persistent grid: wavefront
 // w takes entries [64 w, 64 w + 64), then strides by the grid; the list length is fixed before the launch, so every
 // wavefront reaches its exit.
-template <int VAR>
 __global__ __launch_bounds__(64, 1) void ransac_exact_list_kernel(BatchDev b, RunParams rp, int which)
 {
     const unsigned n = b.xcount[which];
@@ -894,11 +888,11 @@ __global__ __launch_bounds__(64, 1) void ransac_exact_list_kernel(BatchDev b, Ru
         double F[9];
         unsigned rot = 0, pairs = 0;
         bool bad = false;
-        bool ok = solve_hypothesis<VAR>(seed, h, M, rp.sampler, P, F, rot, pairs, bad);
-        if ((VAR & 32) && __builtin_expect(__any(bad), 0)) {
+        bool ok = solve_hypothesis<Solve::GuardedCheap>(seed, h, M, rp.sampler, P, F, rot, pairs, bad);
+        if (__builtin_expect(__any(bad), 0)) {
             rot = 0;
             pairs = 0;
-            ok = solve_hypothesis<(VAR & ~(32 | 128))>(seed, h, M, rp.sampler, P, F, rot, pairs, bad);
+            ok = solve_hypothesis<Solve::Ieee>(seed, h, M, rp.sampler, P, F, rot, pairs, bad);
         }
         if (live) {
             double *Fo = b.hyp_F + (size_t)rec * kHypRec;
@@ -917,11 +911,32 @@ __device__ __forceinline__ int count_block_thr(const double (&F)[9], const doubl
     return __popcll(__ballot(r < thr));   // NaN (padding lanes, degenerate F) compares false
 }
 
-// ransac_count_kernel with one counting threshold per hypothesis (record[9] = thr + band).  The running counts are UPPER
-// bounds of the exact counts: a slot dies when even its upper bound can no longer reach the pair's bound.  A slot that
-// survives all blocks is counted once more against thr - band: a LOWER bound of its exact count, and only lower bounds
-// raise the pair's bound.  Exact records have band 0: upper = lower = exact, no second pass -- the kernel then does
-// exactly what ransac_count_kernel does.
+// ---- pruned counting in double precision ------------------------------------------------------------------------------
+// The reference keeps the hypothesis with the most inliers, ties by the smaller residual sum, then by the smaller index
+// (estimator-RANSAC.cpp:76-84).  A hypothesis whose count can no longer reach a count that SOME hypothesis of the pair
+// has already achieved in full cannot be that winner, whatever its residual: it is dropped the moment
+//     count so far + points not yet visited  <  bound          (strict: ties stay in)
+// and the result is the same hypothesis, bit for bit, as scoring everything.  On the bench workload 97 % of the
+// hypotheses are contaminated and die after ~1/3 of the points.
+//
+// Mapping (the opposite of the solve): LANES ARE POINTS.  A wavefront takes four hypotheses at a time; their F are
+// wave-uniform (scalar loads of the records the solve wrote, SGPR operands of v_fma_f64), each lane reads PPL points of
+// the current block from LDS (two planes of double2, (x1, y1) and (x2, y2), NaN padded: a 16-byte lane stride is
+// conflict-free where the 32-byte AoS form spent as many cycles in bank conflicts as the kernel was busy) and evaluates
+// them for the hypotheses still alive, v_cmp writes the inlier mask straight to an SGPR pair and s_bcnt1 counts it: 9 VALU
+// instructions per 64 evaluations (the hypothesis-per-lane scoring loop needs 15), no cross-lane traffic, and the exit
+// test is scalar code.  Four hypotheses in flight amortise the LDS read and keep the SALU / branch latency of the exit
+// tests off the critical path; two points per lane amortise the scalar work per (hypothesis, block) over 18 vector
+// instructions (a dying hypothesis is noticed up to 64 points later).
+// The bound is per pair: LDS copy per workgroup + one word in global memory (atomicMax, refreshed once per group
+// with the load issued a group ahead).  Which hypotheses get dropped depends on timing; the winner does not.
+// Residual sums are not accumulated here: ransac_select_kernel computes them, in the reference's index order, for the
+// hypotheses that tie at the final maximum only.
+//
+// One counting threshold per hypothesis (record[9] = thr + band).  The running counts are UPPER bounds of the exact
+// counts: a slot dies when even its upper bound can no longer reach the pair's bound.  A slot that survives all blocks is
+// counted once more against thr - band: a LOWER bound of its exact count, and only lower bounds raise the pair's bound.
+// Exact records have band 0: upper = lower = exact, no second pass.
 template <int CNT_THREADS, int PPL, bool STATS = false>
 __global__ __launch_bounds__(CNT_THREADS) void ransac_count2_kernel(BatchDev b, RunParams rp, int wg_per_pair)
 {
@@ -1085,284 +1100,9 @@ __global__ __launch_bounds__(CNT_THREADS) void ransac_count2_kernel(BatchDev b, 
         atomicAdd(&b.stats[2], visits * (unsigned long long)BW);
 }
 
-// Single-precision form of ransac_count2_kernel for pairs in mode 1: the record holds F~ as 9 floats and the two counting
-// thresholds, already widened by the pre-screen's band AND by the bound on the binary32 evaluation error (prescreen.hpp),
-// the points are rounded to binary32 in LDS (16 bytes per point: one ds_read_b128).  v_fma_f32 issues at twice the rate of
-// v_fma_f64, the residual is the same nine instructions.  Exact records do not occur in these pairs before the selection
-// (hypotheses without a certificate wait for the exact solve with an "infinite" count).
-typedef __attribute__((address_space(4))) float CFloat;
+typedef float f32x2 __attribute__((ext_vector_type(2)));   // two binary32 in a register pair: the operands of v_pk_*_f32
 
-// Packed single precision.  A plain v_fma_f32 issues at the rate of v_fma_f64 on this part (16 lanes per clock and SIMD);
-// the fp32 vector peak is v_pk_fma_f32's: two FMAs per lane and instruction.  Each lane therefore carries TWO points per
-// packed register pair -- the LDS block is laid out so that (x2 of point l, x2 of point l + 64) arrive adjacent -- and F comes
-// straight out of the scalar registers the record was loaded into: op_sel picks the low or the high float of an aligned SGPR
-// pair for both halves, so nothing is duplicated or moved.  Written as inline asm: left to itself hipcc's SLP vectoriser does
-// emit v_pk_fma_f32, but with F splatted into vector register pairs first (200 v_mov per 192 packed FMAs; this file is built
-// with -fno-slp-vectorize).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(4))) unsigned long long CU64;
-
-// d = a * s.lo + c  /  d = a * s.hi + c  (both halves of a, c; s = an aligned scalar register pair holding two floats)
-__device__ __forceinline__ f32x2 pk_fma_slo(f32x2 a, unsigned long long s, f32x2 c)
-{
-    f32x2 d;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(d) : "v"(a), "s"(s), "v"(c));
-    return d;
-}
-__device__ __forceinline__ f32x2 pk_fma_shi(f32x2 a, unsigned long long s, f32x2 c)
-{
-    f32x2 d;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(d) : "v"(a), "s"(s), "v"(c));
-    return d;
-}
-__device__ __forceinline__ f32x2 pk_fma_vv(f32x2 a, f32x2 b, f32x2 c)
-{
-    f32x2 d;
-    asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-
-struct Rec32 {                 // one single-precision record as it sits in scalar registers
-    unsigned long long q01, q23, q45;   // (F0, F1), (F2, F3), (F4, F5)
-    f32x2 f6, f7, f8;                   // (F6, F6), (F7, F7), (F8, F8): the inner addends, in vector registers
-    float tu, tl;
-};
-
-// inliers among the 128 points a wavefront's lanes hold as two packed planes: A = (x1a, x1b, y1a, y1b), B = (x2a, x2b, y2a, y2b)
-__device__ __forceinline__ int count_pair32(const Rec32 &r, const float4 &A, const float4 &B, float thr)
-{
-    const f32x2 X1 = {A.x, A.y}, Y1 = {A.z, A.w}, X2 = {B.x, B.y}, Y2 = {B.z, B.w};
-    const f32x2 u0 = pk_fma_slo(X2, r.q01, pk_fma_shi(Y2, r.q23, r.f6));   // x2 F0 + (y2 F3 + F6)
-    const f32x2 u1 = pk_fma_shi(X2, r.q01, pk_fma_slo(Y2, r.q45, r.f7));   // x2 F1 + (y2 F4 + F7)
-    const f32x2 u2 = pk_fma_slo(X2, r.q23, pk_fma_shi(Y2, r.q45, r.f8));   // x2 F2 + (y2 F5 + F8)
-    const f32x2 e = pk_fma_vv(u0, X1, pk_fma_vv(u1, Y1, u2));
-    // NaN (padding lanes) compares false
-    return __popcll(__ballot(__builtin_fabsf(e.x) < thr)) + __popcll(__ballot(__builtin_fabsf(e.y) < thr));
-}
-
-constexpr int kPilotHyp = 256;   // hypotheses of a pair the (vector, diagnostics) pilot counts in full
-constexpr int kPilotMfmaHyp = 1024;   // ... and the matrix-core pilot (ransac_finish_mfma_kernel<., true>)
-// phase: 0 = the PILOT (hypotheses [0, kPilotHyp) counted in full: their best lower bound is the pair's first bound, from
-// which the dense phase derives how many points it has to look at); 2 = the FINISH (every hypothesis resumes behind the
-// points[0, n1) the dense matrix-core phase has already counted: hyp_cnt holds that partial upper-bound count); 1 = everything
-// in one go (no dense phase)
-template <int CNT_THREADS, int PPL, int SLOTS, int phase, bool STATS = false>
-__global__ __launch_bounds__(CNT_THREADS) void ransac_count32_kernel(BatchDev b, RunParams rp, int wg_per_pair)
-{
-    static_assert(SLOTS == 4 && PPL % 2 == 0, "four records per group; points come in packed pairs");
-    extern __shared__ __attribute__((aligned(16))) double s_cpts[];
-    __shared__ int s_bound;
-    const int pair = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
-    const int M = min(b.M[pair], b.max_kp);
-    if (M < 8 || b.mode[pair] != 1)
-        return;
-    const int Hall = rp.num_hypotheses;
-    const int H = phase == 0 ? min(Hall, kPilotHyp) : Hall;
-    const size_t Hp = (size_t)b.max_groups * kHypPerBlock;
-    constexpr int BW = 64 * PPL;                  // points per block
-    constexpr int NP = PPL / 2;                   // packed pairs per lane and block
-    const int nblk = (M + BW - 1) / BW;
-    // points [0, n1) were counted by the dense phase (n1 = dense_points(M, the pilot's bound), a multiple of 32): the finish
-    // starts in the block that holds point n1 and blanks the points before it
-    const int n1 = phase == 2 ? b.dense_n1[pair] : 0;
-    const int blk0 = n1 / BW;
-    // phase 2 works through the pair's list of hypotheses the dense phase left alive, four list entries per group
-    const uint32_t *clist = b.clist + (size_t)pair * Hp;
-    const int n_list = phase == 2 ? b.ccount[pair] : 0;
-    // LDS: [block][pair u][plane A / B][lane] float4; point i = blk * BW + u * 128 + half * 64 + lane sits in half `half`
-    float *s_f = reinterpret_cast<float *>(s_cpts);
-    {
-        const double4 *src = reinterpret_cast<const double4 *>(b.pts + (size_t)pair * b.max_kp * 4);
-        const float qnan = __builtin_nanf("");
-        for (int i = tid; i < nblk * BW; i += CNT_THREADS) {
-            float x1 = qnan, y1 = qnan, x2 = qnan, y2 = qnan;
-            if (i < M) {
-                const double4 p = src[i];
-                x1 = (float)p.x; y1 = (float)p.y; x2 = (float)p.z; y2 = (float)p.w;
-            }
-            const int blk = i / BW, w = i - blk * BW, u = w >> 7, half = (w >> 6) & 1, l = w & 63;
-            float *A = s_f + ((((size_t)blk * NP + u) * 2 + 0) * 64 + l) * 4;
-            float *Bp = s_f + ((((size_t)blk * NP + u) * 2 + 1) * 64 + l) * 4;
-            A[half] = x1; A[2 + half] = y1;
-            Bp[half] = x2; Bp[2 + half] = y2;
-        }
-    }
-    int *gbound = b.bound + pair;
-    if (tid == 0)
-        s_bound = __hip_atomic_load(gbound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const float *Fp = b.hyp_r32 + (size_t)pair * Hp * kHypRec32;   // 48-byte single-precision records
-    const uint32_t *okp = reinterpret_cast<const uint32_t *>(b.hyp_okf + (size_t)pair * Hp);
-    int32_t *cntp = b.hyp_cnt + (size_t)pair * Hp;
-    const float4 *L = reinterpret_cast<const float4 *>(s_f) + lane;   // plane stride 64, pair stride 128, block stride 128 NP
-    const int n_groups = phase == 2 ? (n_list + SLOTS - 1) / SLOTS : (H + SLOTS - 1) / SLOTS;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n_waves = wg_per_pair * (CNT_THREADS / 64);
-    int B = 0;
-    unsigned long long visits = 0;
-    for (int g = blockIdx.x * (CNT_THREADS / 64) + wave; g < n_groups; g += n_waves) {
-        const int h0 = g * SLOTS;
-        const int gb = __hip_atomic_load(gbound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        B = __builtin_amdgcn_readfirstlane(max(B, *(volatile int *)&s_bound));
-        // the four hypotheses of the group: consecutive ones, or (finish) four entries of the list
-        int hq[SLOTS];
-        if (phase == 2) {
-            const uint32_t mine = lane < SLOTS && h0 + lane < n_list ? clist[h0 + lane] : 0u;
-#pragma unroll
-            for (int q = 0; q < SLOTS; ++q)
-                hq[q] = __builtin_amdgcn_readlane((int)mine, q);
-        } else {
-#pragma unroll
-            for (int q = 0; q < SLOTS; ++q)
-                hq[q] = h0 + q;
-        }
-        Rec32 R[SLOTS];
-#pragma unroll
-        for (int q = 0; q < SLOTS; ++q) {
-            // (one base + constant offsets when the four records are neighbours: the loads coalesce)
-            const CU64 *f = phase == 2 ? (const CU64 *)(uintptr_t)(Fp + (size_t)hq[q] * kHypRec32)
-                                       : (const CU64 *)(uintptr_t)(Fp + (size_t)h0 * kHypRec32) + q * (kHypRec32 / 2);
-            R[q].q01 = f[0];
-            R[q].q23 = f[1];
-            R[q].q45 = f[2];
-            const unsigned long long q67 = f[3], q8u = f[4], ql = f[5];
-            const float f6 = __uint_as_float((unsigned)q67), f7 = __uint_as_float((unsigned)(q67 >> 32));
-            const float f8 = __uint_as_float((unsigned)q8u);
-            R[q].f6 = f32x2{f6, f6};
-            R[q].f7 = f32x2{f7, f7};
-            R[q].f8 = f32x2{f8, f8};
-            R[q].tu = __uint_as_float((unsigned)(q8u >> 32));
-            R[q].tl = __uint_as_float((unsigned)ql);
-        }
-        unsigned alive = 0, wait = 0;
-        int c[SLOTS];
-#pragma unroll
-        for (int q = 0; q < SLOTS; ++q)
-            c[q] = 0;
-        if (phase == 2) {
-            // resume: every listed hypothesis is an approximate record; the dense phase left its upper-bound count over
-            // points [0, n1) in hyp_cnt.  A slot that cannot reach the bound (it may have risen since the list was
-            // written) even if every remaining point were an inlier is dead on arrival
-            const int have = lane < SLOTS && h0 + lane < n_list ? cntp[clist[h0 + lane]] : 0;
-#pragma unroll
-            for (int q = 0; q < SLOTS; ++q) {
-                c[q] = __builtin_amdgcn_readlane(have, q);
-                if (h0 + q < n_list && !(c[q] + (M - n1) < B))
-                    alive |= 1u << q;
-            }
-        } else {
-            const uint32_t ok4 = __builtin_amdgcn_readfirstlane(okp[g]);
-#pragma unroll
-            for (int k = 0; k < SLOTS; ++k) {
-                const unsigned st = (ok4 >> (8 * k)) & 0xffu;
-                alive |= (st == kPsApprox && h0 + k < H) ? (1u << k) : 0u;
-                wait |= (st == kPsNeedExact && h0 + k < H) ? (1u << k) : 0u;
-            }
-        }
-        float4 pa[PPL], pb[PPL];   // [2 u] = plane A, [2 u + 1] = plane B of packed pair u
-        auto load = [&](float4 (&p)[PPL], int blk) {
-            const int nb = min(blk, nblk - 1) * (128 * NP);
-#pragma unroll
-            for (int u = 0; u < PPL; ++u)
-                p[u] = L[nb + u * 64];
-            if (blk == blk0 && n1 > blk0 * BW) {
-                // the dense phase has already counted the points of this block below n1: blank them (NaN is no inlier).
-                // p[2 u] / p[2 u + 1] hold points blk BW + 128 u + lane (x, z components) and + 64 (y, w components)
-                const float qnan = __builtin_nanf("");
-#pragma unroll
-                for (int u = 0; u < NP; ++u) {
-                    const int i0 = blk * BW + u * 128 + lane;
-                    if (i0 < n1) { p[2 * u].x = qnan; p[2 * u + 1].x = qnan; }
-                    if (i0 + 64 < n1) { p[2 * u].y = qnan; p[2 * u + 1].y = qnan; }
-                }
-            }
-        };
-        auto process = [&](const float4 (&p)[PPL], int blk) {
-            const int need = B - max(M - (blk + 1) * BW, 0);   // a slot whose count stays below this cannot reach B
-            if (STATS)
-                visits += (unsigned)__builtin_popcount(alive);
-            if (alive == (1u << SLOTS) - 1u) {
-                // all four alive (the usual state until they die together): one straight-line stretch, so that the
-                // scheduler interleaves the slots' independent FMA chains -- slot by slot behind uniform branches a
-                // wavefront has two short dependent chains in flight and the SIMD waits on latencies
-                int add[SLOTS];
-#pragma unroll
-                for (int q = 0; q < SLOTS; ++q) {
-                    add[q] = 0;
-#pragma unroll
-                    for (int u = 0; u < NP; ++u)
-                        add[q] += count_pair32(R[q], p[2 * u], p[2 * u + 1], R[q].tu);
-                }
-#pragma unroll
-                for (int q = 0; q < SLOTS; ++q) {
-                    c[q] += add[q];
-                    alive &= (c[q] < need) ? ~(1u << q) : ~0u;
-                }
-            } else {
-#pragma unroll
-                for (int q = 0; q < SLOTS; ++q) {
-                    if (alive & (1u << q)) {
-#pragma unroll
-                        for (int u = 0; u < NP; ++u)
-                            c[q] += count_pair32(R[q], p[2 * u], p[2 * u + 1], R[q].tu);
-                        if (c[q] < need) alive &= ~(1u << q);
-                    }
-                }
-            }
-        };
-        if (alive)
-            load(pa, blk0);
-        for (int blk = blk0; blk < nblk && alive; blk += 2) {
-            load(pb, blk + 1);
-            process(pa, blk);
-            if (!(blk + 1 < nblk && alive))
-                break;
-            load(pa, blk + 2);
-            process(pb, blk + 1);
-        }
-        // lower bounds of the slots that saw every point: one more pass against the lower threshold
-        int v[SLOTS], lo[SLOTS];
-        int cm = -1;
-#pragma unroll
-        for (int q = 0; q < SLOTS; ++q) {
-            const bool al = (alive >> q) & 1u;
-            v[q] = al ? c[q] : ((wait >> q) & 1u) ? 0x7fffffff : -1;
-            lo[q] = -1;
-            if (al) {
-                int cl = 0;
-                for (int blk = 0; blk < nblk; ++blk) {
-#pragma unroll
-                    for (int u = 0; u < NP; ++u)
-                        cl += count_pair32(R[q], L[blk * (128 * NP) + (2 * u) * 64], L[blk * (128 * NP) + (2 * u + 1) * 64], R[q].tl);
-                }
-                if (STATS)
-                    visits += (unsigned)nblk;
-                lo[q] = cl;
-            }
-            cm = max(cm, lo[q]);
-        }
-        if (lane < SLOTS && (phase != 2 || h0 + lane < n_list)) {
-            int mine = v[0], where = hq[0];
-#pragma unroll
-            for (int q = 1; q < SLOTS; ++q) {
-                mine = lane == q ? v[q] : mine;
-                where = lane == q ? hq[q] : where;
-            }
-            cntp[where] = mine;
-        }
-        cm = __builtin_amdgcn_readfirstlane(cm);
-        if (cm > B) {
-            B = cm;
-            if (lane == 0) {
-                atomicMax(&s_bound, cm);
-                __hip_atomic_fetch_max(gbound, cm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        B = max(B, __builtin_amdgcn_readfirstlane(gb));
-    }
-    if (STATS && lane == 0 && b.stats)
-        atomicAdd(&b.stats[3], visits * (unsigned long long)BW);   // executed single-precision evaluations
-}
+constexpr int kPilotMfmaHyp = 1024;   // hypotheses of a pair the pilot (ransac_finish_mfma_kernel<., true>) counts in full
 
 // ---- dense counting on the matrix cores --------------------------------------------------------------------------------
 // The residuals of a block of points under a block of hypotheses are one GEMM: r[i][h] = Phi(point i) . F~(h) with the nine
@@ -1380,14 +1120,14 @@ __global__ __launch_bounds__(CNT_THREADS) void ransac_count32_kernel(BatchDev b,
 // exact count like every other.  A tile cannot drop single hypotheses, so the phase takes NO exit tests: it counts points
 // [0, n1) for every approximate record,
 //     n1 = dense_points(M, B0) = the multiple of 32 that covers M - B0 + 32 points, clamped to [0, M rounded down],
-// B0 = the bound the PILOT (the first kPilotHyp hypotheses counted in full by ransac_count32_kernel) has established: a
-// hypothesis cannot be dropped before M - B points have been seen, so nothing is wasted except on the few per cent that go on.
-// ransac_count32_kernel then resumes behind n1 for the hypotheses that can still reach the bound.
+// B0 = the bound the PILOT (the first kPilotMfmaHyp hypotheses counted in full by ransac_finish_mfma_kernel<., true>) has
+// established: a hypothesis cannot be dropped before M - B points have been seen, so nothing is wasted except on the few per cent
+// that go on.  The finish kernels then resume behind n1 for the hypotheses that can still reach the bound.
 // Wavefront = 2 x 32 hypotheses (the B operands: 16 VGPRs, built once) x all point tiles (A operands: two ds_read_b128 per
 // tile); the accumulator tile has the hypothesis on the lane and 16 points in the registers.
 constexpr int kDenseThreads = 512;   // dense phase: 8 wavefronts x 64 hypotheses share one staged chunk of points; with 672-point
                                      // chunks two workgroups fit a CU = 4 wavefronts per SIMD (what the 102 registers allow).
-                                     // A/B on the bench batch (tools/dense_ab.py, profiles/r04_dense_ab.json), same box: 256 x 8
+                                     // A/B on the bench batch (profiles/r04_dense_ab.json), same box: 256 x 8
                                      // threads x batches with 768-point chunks (2 per SIMD) 1.36 ms, 512 x 4 / 768 (one workgroup
                                      // per CU) 1.44, 512 x 4 / 640 1.22, 512 x 4 / 672 1.19; the three-stage software pipeline
                                      // 1.43 / 1.97 / 1.58 at 256 / 384 / 512 threads
@@ -2380,7 +2120,7 @@ __global__ __launch_bounds__(kSelThreads) void ransac_select_kernel(BatchDev b, 
             scan += n;
             __syncthreads();
         } else {
-            // (no candidate list: the diagnostics ladder's launches) collect the hypotheses whose count reaches the pair's
+            // (no candidate list: no launch asks for this since the experiment ladder went) collect the hypotheses whose count reaches the pair's
             // bound, appended per wavefront with one LDS atomic, no barrier inside a segment of kSelSeg hypotheses; the list
             // order is immaterial, candidates are compared by (count, residual, index)
             while (scan < H) {
@@ -2665,9 +2405,9 @@ __global__ __launch_bounds__(64, 1) void fundamental_kernel(const double *p1, co
     bool bad = false;
     // the pair step of the RANSAC solve (unscaled sequences, sqrt-free test, 9x9 and 3x3), so that the bitwise F
     // tests of this entry point cover exactly the arithmetic the hot kernel runs
-    bool ok = eight_point<16 + 32 + 128 + 1024>(x1, y1, x2, y2, F, rot, pairs, bad);
+    bool ok = eight_point<Solve::GuardedCheap>(x1, y1, x2, y2, F, rot, pairs, bad);
     if (bad)
-        ok = eight_point<16>(x1, y1, x2, y2, F, rot, pairs, bad);
+        ok = eight_point<Solve::Ieee>(x1, y1, x2, y2, F, rot, pairs, bad);
 #pragma unroll
     for (int k = 0; k < 9; ++k)
         Fout[k] = F[k];
@@ -3150,9 +2890,9 @@ __global__ __launch_bounds__(kFinThreads) void finalize_select_kernel(BatchDev b
     }
 }
 
-// The retired kernels of the experiment ladder (rounds 1-3: ransac_solve / ransac_score / ransac_solve_av / ransac_count and the
-// device-side probes of the matrix-core tile and of the unscaled sequences) live in their own file, which ONLY the diagnostics
-// build compiles: libmvslam_hip.so contains none of it (tests/test_abi.py reads its symbol table).
+// The vector form of the single-precision counting (ransac_count32_kernel, the reference two GPU checks compare the matrix-core
+// counting with) and the device-side probes of the matrix-core tile and of the unscaled sequences live in their own file, which
+// ONLY the diagnostics build compiles: libmvslam_hip.so contains none of it (tests/test_abi.py reads its symbol table).
 #ifdef MVS_DEBUG_HOOKS
 #include "kernels_experiments.hip"
 #endif
@@ -3178,16 +2918,6 @@ static bool prescreened_launch(const BatchDev &b, int n_active, int H)
 {
     const int cus = b.cu_count > 0 ? b.cu_count : 256;
     return n_active >= kSplitMinPairs || (kSplitMinPairs == 3 && n_active == 2 && 2 * ((H + kHypPerBlock - 1) / kHypPerBlock) > cus);
-}
-
-
-constexpr int kCnt32Threads = 768;
-constexpr int kCnt32Slots = 4;     // hypotheses a wavefront carries at a time
-constexpr int kCnt32Ppl = 4;       // single-precision counting: four points per lane and block (scalar work per evaluation halves)
-static size_t count32_lds_bytes(int max_kp)
-{
-    const int bw = 64 * kCnt32Ppl;
-    return (size_t)((max_kp + bw - 1) / bw) * bw * 4 * sizeof(float);
 }
 
 static size_t count_lds_bytes(int max_kp)
@@ -3218,13 +2948,13 @@ bool kernel_desc(int id, int max_kp, int desc_words, KernelDesc *out)
         d.threads = 1024;
         break;
     case kKRansacFused:
-        d.name = "ransac_kernel<false, 1272>";
-        d.fn = reinterpret_cast<const void *>(ransac_kernel<false, 248 + 1024>);
+        d.name = "ransac_kernel<false, true, (mvs::Solve)2>";
+        d.fn = reinterpret_cast<const void *>(ransac_kernel<false, true, Solve::GuardedCheap>);
         d.threads = kHypPerBlock;
         break;
     case kKRansacSolve:
-        d.name = "ransac_solve_list_kernel<1264>";   // (+ the one-workgroup mode0_list_kernel in front of it)
-        d.fn = reinterpret_cast<const void *>(ransac_solve_list_kernel<240 + 1024>);
+        d.name = "ransac_solve_list_kernel";   // (+ the one-workgroup mode0_list_kernel in front of it)
+        d.fn = reinterpret_cast<const void *>(ransac_solve_list_kernel);
         d.threads = kSolveBlock;
         break;
     case kKRansacSelect:
@@ -3244,8 +2974,8 @@ bool kernel_desc(int id, int max_kp, int desc_words, KernelDesc *out)
         d.threads = 64;
         break;
     case kKRansacExactList:
-        d.name = "ransac_exact_list_kernel<1264>";
-        d.fn = reinterpret_cast<const void *>(ransac_exact_list_kernel<240 + 1024>);
+        d.name = "ransac_exact_list_kernel";
+        d.fn = reinterpret_cast<const void *>(ransac_exact_list_kernel);
         d.threads = 64;
         break;
     case kKRansacCount2:
@@ -3298,18 +3028,7 @@ bool kernel_desc(int id, int max_kp, int desc_words, KernelDesc *out)
         d.fn = reinterpret_cast<const void *>(finalize_select_kernel);
         d.threads = kFinThreads;
         break;
-#ifdef MVS_DEBUG_HOOKS   // kernels of the experiment ladder: ids behind kKernelCountProduct, diagnostics build only
-    case kKRansacScore:
-        d.name = "ransac_score_kernel";
-        d.fn = reinterpret_cast<const void *>(ransac_score_kernel);
-        d.threads = kHypPerBlock;
-        break;
-    case kKRansacCount:
-        d.name = "ransac_count_kernel<768, 2>";
-        d.fn = reinterpret_cast<const void *>(ransac_count_kernel<kCntThreads, kCntPpl>);
-        d.threads = kCntThreads;
-        d.dynamic_lds = count_lds_bytes(max_kp);
-        break;
+#ifdef MVS_DEBUG_HOOKS   // the id behind kKernelCountProduct: diagnostics build only
     case kKRansacCount32:
         d.name = "ransac_count32_kernel<768, 4, 4, 1, false>";
         d.fn = reinterpret_cast<const void *>(ransac_count32_kernel<kCnt32Threads, kCnt32Ppl, kCnt32Slots, 1>);
@@ -3330,8 +3049,6 @@ hipError_t prepare_kernels()
 {
     const void *fns[] = {
 #ifdef MVS_DEBUG_HOOKS
-                         reinterpret_cast<const void *>(ransac_count_kernel<kCntThreads, kCntPpl>),
-                         reinterpret_cast<const void *>(ransac_count_kernel<kCntThreads, kCntPpl, true>),
                          reinterpret_cast<const void *>(ransac_count32_kernel<kCnt32Threads, kCnt32Ppl, kCnt32Slots, 1>),
                          reinterpret_cast<const void *>(ransac_count32_kernel<kCnt32Threads, kCnt32Ppl, kCnt32Slots, 1, true>),
                          reinterpret_cast<const void *>(ransac_count32_kernel<kCnt32Threads, kCnt32Ppl, kCnt32Slots, 2>),
@@ -3339,18 +3056,8 @@ hipError_t prepare_kernels()
 #endif
                          reinterpret_cast<const void *>(ransac_count2_kernel<kCntThreads, kCntPpl>),
                          reinterpret_cast<const void *>(ransac_count2_kernel<kCntThreads, kCntPpl, true>),
-                         reinterpret_cast<const void *>(ransac_count32_kernel<kCnt32Threads, kCnt32Ppl, kCnt32Slots, 0>),
-                         reinterpret_cast<const void *>(ransac_count32_kernel<kCnt32Threads, kCnt32Ppl, kCnt32Slots, 0, true>),
                          reinterpret_cast<const void *>(ransac_count_mfma_kernel<false, kDenseThreads, kDenseBatches>),
                          reinterpret_cast<const void *>(ransac_count_mfma_kernel<true, kDenseThreads, kDenseBatches>),
-#ifdef MVS_DEBUG_HOOKS
-                         reinterpret_cast<const void *>(ransac_count_mfma_kernel<false, 256, 8, 768>),
-                         reinterpret_cast<const void *>(ransac_count_mfma_kernel<false, 384, 6, 768>),
-                         reinterpret_cast<const void *>(ransac_count_mfma_kernel<false, 512, 4, 768>),
-                         reinterpret_cast<const void *>(ransac_count_mfma_kernel<false, 512, 4, 640>),
-                         reinterpret_cast<const void *>(ransac_count_mfma_kernel<false, 512, 4, 672>),
-                         reinterpret_cast<const void *>(ransac_count_mfma_kernel<false, 512, 2, 672>),
-#endif
                          reinterpret_cast<const void *>(ransac_finish_mfma_kernel<false>),
                          reinterpret_cast<const void *>(ransac_finish_mfma_kernel<true>),
                          reinterpret_cast<const void *>(ransac_finish_mfma_kernel<false, true>),
@@ -3368,7 +3075,7 @@ hipError_t prepare_kernels()
 
 // The product library has ONE path and no process-global mutable state: the switches below are compile-time constants there.
 // Only the diagnostics build (-DMVS_DEBUG_HOOKS: kernels_dbg.o -> libmvslam_hip_dbg.so) turns them into variables with
-// setters, and only that build contains the experiment ladder's kernels (tools/ab_ransac.py, tests/prescreen_gpu_check.py).
+// setters, and only that build contains the reference kernel and the probes of kernels_experiments.hip and the audit.
 #ifdef MVS_DEBUG_HOOKS
 static int g_match_mfma = 1;   // 1 = by batch size (below); diagnostics: 0 = always the VALU kernel, 2 = always the matrix-core one
 void set_match_mfma(int v) { g_match_mfma = v; }
@@ -3429,54 +3136,6 @@ void launch_prep_points(const BatchDev &b, const double *uv1, const double *uv2,
     hipLaunchKernelGGL(prep_points_kernel, dim3((b.max_kp + 255) / 256, n_active), dim3(256), 0, stream, b, uv1, uv2);
 }
 
-// 9000 (default, round 3) = the pre-screened stage: pair_prepare -> prescreen (+ the exact solve for pairs the probe sends
-// there) -> exact solve of the hypotheses without a certificate -> count with per-hypothesis thresholds -> survivors ->
-// their exact solve -> select.
-// 120 fused; 632 = solve + hypothesis-per-lane scoring as two launches (round 1); 1784 = solve (with the sqrt-free
-// convergence test, bit 128 of the kernel's VAR, for the 9x9 and -- kernel bit 1024 -- the 3x3 SVD) + pruned
-// point-per-lane scoring (bit 1024 of the launch variant): ransac_count + ransac_select
-#ifdef MVS_DEBUG_HOOKS
-static int g_ransac_variant = 9000;
-void set_ransac_variant(int v) { g_ransac_variant = v; }
-int get_ransac_variant() { return g_ransac_variant; }
-#endif
-
-template <int VAR>
-static void launch_ransac_var(const BatchDev &b, const RunParams &rp, dim3 grid, dim3 block, bool stats, hipStream_t stream,
-                              LaunchTimer *lt)
-{
-    if (lt) lt->mark(kKRansacFused);
-    if (stats)
-        hipLaunchKernelGGL((ransac_kernel<true, VAR>), grid, block, 0, stream, b, rp);
-    else
-        hipLaunchKernelGGL((ransac_kernel<false, VAR>), grid, block, 0, stream, b, rp);
-}
-
-#ifdef MVS_DEBUG_HOOKS   // round 2's pruned scoring (variants 1656 / 1784 / 3832)
-static void launch_pruned_scoring(const BatchDev &b, const RunParams &rp, int n_active, hipStream_t stream, LaunchTimer *lt,
-                                  bool stats = false)
-{
-    // enough workgroups to fill the chip for a small launch, few enough that every wavefront works through many
-    // groups of four hypotheses (the bound only helps once the first groups have finished)
-    const int n_groups4 = (rp.num_hypotheses + kCntSlots - 1) / kCntSlots;
-    const int wpw = kCntThreads / 64;
-    int wg = (512 + n_active - 1) / n_active;
-    wg = std::max(wg, 4);
-    wg = std::min(wg, std::max(1, (n_groups4 + wpw - 1) / wpw));
-    const size_t lds_cnt = count_lds_bytes(b.max_kp);
-    const size_t lds_sel = (size_t)b.max_kp * 4 * sizeof(double);
-    const dim3 grid(wg, n_active);
-    if (lt) lt->mark(kKRansacCount);
-    if (stats)
-        hipLaunchKernelGGL((ransac_count_kernel<kCntThreads, kCntPpl, true>), grid, dim3(kCntThreads), lds_cnt, stream, b, rp, wg);
-    else
-        hipLaunchKernelGGL((ransac_count_kernel<kCntThreads, kCntPpl>), grid, dim3(kCntThreads), lds_cnt, stream, b, rp, wg);
-    if (lt) lt->mark(kKRansacSelect);
-    hipLaunchKernelGGL(ransac_select_kernel, dim3(n_active), dim3(kSelThreads), lds_sel, stream, b, rp, 0);
-}
-
-#endif
-
 #ifdef MVS_DEBUG_HOOKS
 static int g_count_dense = 1;   // 1 = pilot + dense matrix-core phase + matrix-core finish; diagnostics: 0 = one
                                 // ransac_count32 launch, 2 = pilot + dense phase + the vector finish (ransac_count32, phase 2)
@@ -3499,15 +3158,20 @@ void launch_prescreen_only(const BatchDev &b, const RunParams &rp, int n_active,
     hipLaunchKernelGGL(pair_prepare_kernel, dim3(n_active), dim3(256), 0, stream, b, rp, mode);
     hipLaunchKernelGGL(ransac_prescreen_kernel, dim3((rp.num_hypotheses + 63) / 64, n_active), dim3(64), 0, stream, b, rp);
 }
-#else
-constexpr int g_count_dense = 1;
+#else   // (no g_count_dense: the product sequence is the only one in launch_counting)
 constexpr int g_dense_margin = kDenseMargin;
 constexpr int g_pilot_hyp = kPilotMfmaHyp;
 constexpr int g_force_mode = -1;
 #endif
 
-// the counting part of the pre-screened stage: upper / lower count bounds of every record, the pair's bound (mode 1: pilot ->
-// dense matrix-core phase -> sorted list -> matrix-core finish; modes 0 / 2: ransac_count2_kernel)
+// the counting part of the pre-screened stage: upper / lower count bounds of every record, the pair's bound.  Single precision
+// for the pairs in mode 1, double precision (ransac_count2_kernel) for the others; each launch's workgroups leave at once for
+// the pairs of the other kind.  The single-precision counting is a sequence of launches: pilot (the first 1024 hypotheses in
+// full -> the pair's first bound) -> dense phase on the matrix cores in split bf16 (every hypothesis x the points that must be
+// seen before anything can be dropped, no exit tests) -> sorted list -> finish (the listed hypotheses that can still reach the
+// bound, from there on).  The diagnostics library can put ransac_count32_kernel in the place of the whole sequence
+// (g_count_dense = 0) or of the finish (2) -- byte-identical results, 5.2 ms against 0.2 + 2.0 + 1.4 per 512 pairs
+// (profiles/r03_count32_experiments.md).
 static void launch_counting(const BatchDev &b, const RunParams &rp, int n_active, hipStream_t stream, LaunchTimer *lt, bool stats)
 {
     const int H = rp.num_hypotheses;
@@ -3518,36 +3182,14 @@ static void launch_counting(const BatchDev &b, const RunParams &rp, int n_active
     wg = std::min(wg, std::max(1, (n_groups4 + wpw - 1) / wpw));
     const size_t lds_cnt = count_lds_bytes(b.max_kp);
 #ifdef MVS_DEBUG_HOOKS
-    const size_t lds_c32 = count32_lds_bytes(b.max_kp);   // the vector counting kernels are diagnostics-only since round 4
-#endif
-    // counting: single precision for the pairs in mode 1, double precision for the others (each launch's workgroups leave
-    // at once for the pairs of the other kind)
-    // single-precision counting of the pairs in mode 1, three launches: pilot (the first 256 hypotheses in full -> the pair's
-    // first bound) -> dense phase on the matrix cores in split bf16 (every hypothesis x the points that must be seen before
-    // anything can be dropped, no exit tests) -> finish (the listed hypotheses that can still reach the bound, from there on).
-    // g_count_dense = 0 (diagnostics library only): ransac_count32_kernel over everything in one launch -- byte-identical
-    // results, 5.2 ms against 0.2 + 2.0 + 1.4 per 512 pairs (profiles/r03_count32_experiments.md).
-#ifdef MVS_DEBUG_HOOKS
-    if (!g_count_dense) {
+    if (g_count_dense == 0) {
         if (lt) lt->mark(kKRansacCount32);
-        if (stats)
-            hipLaunchKernelGGL((ransac_count32_kernel<kCnt32Threads, kCnt32Ppl, kCnt32Slots, 1, true>), dim3(wg, n_active),
-                               dim3(kCnt32Threads), lds_c32, stream, b, rp, wg);
-        else
-            hipLaunchKernelGGL((ransac_count32_kernel<kCnt32Threads, kCnt32Ppl, kCnt32Slots, 1>), dim3(wg, n_active),
-                               dim3(kCnt32Threads), lds_c32, stream, b, rp, wg);
+        launch_count32<1>(b, rp, wg, n_active, stats, stream);
     } else
 #endif
     {
         if (lt) lt->mark(kKRansacCountPilot);
         const dim3 pilot_grid(n_active, (std::min(H, g_pilot_hyp) + kFinishThreads - 1) / kFinishThreads);
-#ifdef MVS_DEBUG_HOOKS
-        if (g_count_dense == 3) {   // diagnostics: round 3's vector pilot over the first 256 hypotheses
-            const int wg_pilot = std::max(1, std::min(wg, (kPilotHyp / kCnt32Slots) / (kCnt32Threads / 64)));
-            hipLaunchKernelGGL((ransac_count32_kernel<kCnt32Threads, kCnt32Ppl, kCnt32Slots, 0>), dim3(wg_pilot, n_active),
-                               dim3(kCnt32Threads), lds_c32, stream, b, rp, wg_pilot);
-        } else
-#endif
         if (stats)
             hipLaunchKernelGGL((ransac_finish_mfma_kernel<true, true>), pilot_grid, dim3(kFinishThreads), (size_t)kDenseChunk * 64,
                                stream, b, rp, 0);
@@ -3555,36 +3197,22 @@ static void launch_counting(const BatchDev &b, const RunParams &rp, int n_active
             hipLaunchKernelGGL((ransac_finish_mfma_kernel<false, true>), pilot_grid, dim3(kFinishThreads), (size_t)kDenseChunk * 64,
                                stream, b, rp, 0);
         if (lt) lt->mark(kKRansacCountMfma);
-        auto dense = [&](auto kern, int threads, int batches, int chunk = kDenseChunkD) {
-            const size_t lds = (size_t)chunk * 64 + (size_t)(threads / 64) * kDenseWin * 16;
-            const dim3 grid(((H + threads - 1) / threads + batches - 1) / batches, n_active);
-            hipLaunchKernelGGL(kern, grid, dim3(threads), lds, stream, b, rp, g_dense_margin);
-        };
-#ifdef MVS_DEBUG_HOOKS
-        // A/B of the dense phase's shape: mvs_debug_set_count_dense(10 + k)
-        if (g_count_dense == 10) dense(ransac_count_mfma_kernel<false, 256, 8, 768>, 256, 8, 768);
-        else if (g_count_dense == 11) dense(ransac_count_mfma_kernel<false, 384, 6, 768>, 384, 6, 768);
-        else if (g_count_dense == 15) dense(ransac_count_mfma_kernel<false, 512, 4, 768>, 512, 4, 768);
-        else if (g_count_dense == 16) dense(ransac_count_mfma_kernel<false, 512, 4, 640>, 512, 4, 640);
-        else if (g_count_dense == 17) dense(ransac_count_mfma_kernel<false, 512, 4, 672>, 512, 4, 672);
-        else if (g_count_dense == 18) dense(ransac_count_mfma_kernel<false, 512, 2, 672>, 512, 2, 672);
-        else
-#endif
+        const size_t lds_dense = (size_t)kDenseChunkD * 64 + (size_t)(kDenseThreads / 64) * kDenseWin * 16;
+        const dim3 dense_grid(((H + kDenseThreads - 1) / kDenseThreads + kDenseBatches - 1) / kDenseBatches, n_active);
         if (stats)
-            dense(ransac_count_mfma_kernel<true, kDenseThreads, kDenseBatches>, kDenseThreads, kDenseBatches);
+            hipLaunchKernelGGL((ransac_count_mfma_kernel<true, kDenseThreads, kDenseBatches>), dense_grid, dim3(kDenseThreads),
+                               lds_dense, stream, b, rp, g_dense_margin);
         else
-            dense(ransac_count_mfma_kernel<false, kDenseThreads, kDenseBatches>, kDenseThreads, kDenseBatches);
+            hipLaunchKernelGGL((ransac_count_mfma_kernel<false, kDenseThreads, kDenseBatches>), dense_grid, dim3(kDenseThreads),
+                               lds_dense, stream, b, rp, g_dense_margin);
         if (lt) lt->mark(kKRansacCountFinish);
-        const dim3 fin_grid(n_active, (H + kFinishThreads - 1) / kFinishThreads);   // workgroups past the list's end leave at once
-        if (g_count_dense != 2)
-            hipLaunchKernelGGL(ransac_list_sort_kernel, dim3(n_active), dim3(kSortThreads), 0, stream, b);
 #ifdef MVS_DEBUG_HOOKS
-        if (g_count_dense == 2) {   // diagnostics: the vector finish (ransac_count32_kernel, phase 2)
-            hipLaunchKernelGGL((ransac_count32_kernel<kCnt32Threads, kCnt32Ppl, kCnt32Slots, 2>), dim3(wg, n_active),
-                               dim3(kCnt32Threads), lds_c32, stream, b, rp, wg);
+        if (g_count_dense == 2) {   // the vector finish, on the dense phase's unsorted list
+            launch_count32<2>(b, rp, wg, n_active, stats, stream);
         } else
 #endif
         {
+            hipLaunchKernelGGL(ransac_list_sort_kernel, dim3(n_active), dim3(kSortThreads), 0, stream, b);
             // two launches: the first batch of every pair (the 256 largest partial counts: the winner is nearly always among
             // them, so the pair's bound is final afterwards: upper and lower bounds over every point), then the rest of the
             // list: upper counts only, over the points behind the dense phase
@@ -3594,7 +3222,7 @@ static void launch_counting(const BatchDev &b, const RunParams &rp, int n_active
             else
                 hipLaunchKernelGGL(ransac_finish_mfma_kernel<false>, dim3(n_active, 1), dim3(kFinishThreads), (size_t)kDenseChunk * 64,
                                    stream, b, rp, 0);
-            if (fin_grid.y > 1) {
+            if ((H + kFinishThreads - 1) / kFinishThreads > 1) {   // the list can be longer than its first batch
                 const size_t lds_up = (size_t)kFinUpperChunk * 64 + (size_t)(kFinUpperThreads / 64) * kDenseWin * 16;
                 if (lt) lt->mark(kKRansacCountFinishRest);
                 if (stats)
@@ -3615,7 +3243,9 @@ static void launch_counting(const BatchDev &b, const RunParams &rp, int n_active
                            b, rp, wg);
 }
 
-// the pre-screened RANSAC stage (variant 9000)
+// the pre-screened RANSAC stage: pair_prepare -> prescreen (+ the exact solve of every hypothesis for the pairs
+// the probe sends there) -> counting with per-hypothesis thresholds -> survivors -> exact solve of the hypotheses without a
+// certificate and of the survivors -> select
 static void launch_prescreened(const BatchDev &b, const RunParams &rp, int n_active, hipStream_t stream, LaunchTimer *lt,
                                bool stats)
 {
@@ -3629,108 +3259,38 @@ static void launch_prescreened(const BatchDev &b, const RunParams &rp, int n_act
     if (lt) lt->mark(kKRansacSolve);
     hipLaunchKernelGGL(mode0_list_kernel, dim3(1), dim3(256), 0, stream, b, n_active);
     static_assert(kSolveBlock == 64, "ransac_solve_list_kernel takes blocks of 64 hypotheses");
-    hipLaunchKernelGGL((ransac_solve_list_kernel<240 + 1024>), dim3(2048), dim3(64), 0, stream, b, rp,
+    hipLaunchKernelGGL(ransac_solve_list_kernel, dim3(2048), dim3(64), 0, stream, b, rp,
                        G * (kHypPerBlock / kSolveBlock));
     launch_counting(b, rp, n_active, stream, lt, stats);
     if (lt) lt->mark(kKRansacSurvivors);
     hipLaunchKernelGGL(ransac_survivors_kernel, dim3(kSurvWg, n_active), dim3(256), 0, stream, b, rp, n_active);
     // one exact solve over the whole work list: what the pre-screen flagged + the survivors of the counting
     if (lt) lt->mark(kKRansacExactList);
-    hipLaunchKernelGGL((ransac_exact_list_kernel<240 + 1024>), dim3(1024), dim3(64), 0, stream, b, rp, 0);
+    hipLaunchKernelGGL(ransac_exact_list_kernel, dim3(1024), dim3(64), 0, stream, b, rp, 0);
     if (lt) lt->mark(kKRansacSelect);
     hipLaunchKernelGGL(ransac_select_kernel, dim3(n_active), dim3(kSelThreads), (size_t)b.max_kp * 4 * sizeof(double), stream,
                        b, rp, 1);
 }
 
 // the pre-screened stage, or -- for one or two pairs, the per-hypothesis tables and the instrumented replay's rotation
-// counters -- the fused hypothesis-per-lane kernel
-static void launch_ransac_product(const BatchDev &b, const RunParams &rp, int n_active, bool stats, hipStream_t stream,
-                                  LaunchTimer *lt, dim3 grid, dim3 block)
+// counters -- the fused hypothesis-per-lane kernel.  The replay runs the fused kernel with the Guarded solve: the flop model of
+// the benchmark was derived with its rotation counters.
+void launch_ransac(const BatchDev &b, const RunParams &rp, int n_active, bool stats, hipStream_t stream, LaunchTimer *lt)
 {
+    const int G = (rp.num_hypotheses + kHypPerBlock - 1) / kHypPerBlock;
+    const dim3 grid(G, n_active), block(kHypPerBlock);
     const bool split_ok = !stats && b.hyp_F && prescreened_launch(b, n_active, rp.num_hypotheses);
     if (!split_ok || b.hyp_count) {
+        if (lt) lt->mark(kKRansacFused);
         if (!stats)
-            launch_ransac_var<248 + 1024>(b, rp, grid, block, false, stream, lt);
+            hipLaunchKernelGGL((ransac_kernel<false, true, Solve::GuardedCheap>), grid, block, 0, stream, b, rp);
         else
-            launch_ransac_var<120>(b, rp, grid, block, true, stream, lt);
+            hipLaunchKernelGGL((ransac_kernel<true, true, Solve::Guarded>), grid, block, 0, stream, b, rp);
         if (stats && b.hyp_F && !b.hyp_count && prescreened_launch(b, n_active, rp.num_hypotheses))
             launch_prescreened(b, rp, n_active, stream, nullptr, true);   // + the product path's own counters
     } else {
         launch_prescreened(b, rp, n_active, stream, lt, false);
     }
-}
-
-void launch_ransac(const BatchDev &b, const RunParams &rp, int n_active, bool stats, hipStream_t stream, LaunchTimer *lt)
-{
-    const int G = (rp.num_hypotheses + kHypPerBlock - 1) / kHypPerBlock;
-    const dim3 grid(G, n_active), block(kHypPerBlock);
-#ifndef MVS_DEBUG_HOOKS
-    launch_ransac_product(b, rp, n_active, stats, stream, lt, grid, block);
-#else
-    // diagnostics build: the experiment ladder of rounds 1-2 behind mvs_debug_set_ransac_variant (tools/ab_ransac.py)
-    const bool split_ok = !stats && b.hyp_F && prescreened_launch(b, n_active, rp.num_hypotheses);
-    switch (g_ransac_variant) {
-    case 9000: launch_ransac_product(b, rp, n_active, stats, stream, lt, grid, block); break;
-    case 0: launch_ransac_var<0>(b, rp, grid, block, stats, stream, lt); break;
-    case 376: launch_ransac_var<376>(b, rp, grid, block, stats, stream, lt); break;   // timing experiment: no V rotations
-    case 632:
-        if (!split_ok) {
-            launch_ransac_var<120>(b, rp, grid, block, stats, stream, lt);
-        } else {
-            hipLaunchKernelGGL((ransac_solve_kernel<112>), grid, block, 0, stream, b, rp, 0);
-            hipLaunchKernelGGL(ransac_score_kernel, grid, block, 0, stream, b, rp);
-        }
-        break;
-    case 760:   // 632 + sqrt-free convergence test
-        if (!split_ok) {
-            launch_ransac_var<120>(b, rp, grid, block, stats, stream, lt);
-        } else {
-            hipLaunchKernelGGL((ransac_solve_kernel<240>), grid, block, 0, stream, b, rp, 0);
-            hipLaunchKernelGGL(ransac_score_kernel, grid, block, 0, stream, b, rp);
-        }
-        break;
-    case 3832:  // 1784 with the solve as A / V wavefront pairs
-        if (!split_ok || b.hyp_count) {
-            launch_ransac_var<120>(b, rp, grid, block, stats, stream, lt);
-        } else {
-            hipLaunchKernelGGL((ransac_solve_av_kernel<240>), grid, dim3(512), 0, stream, b, rp);
-            launch_pruned_scoring(b, rp, n_active, stream, lt);
-        }
-        break;
-    case 1656:  // 632 + pruned scoring
-    case 1784:  // 760 + pruned scoring (+ the 3x3 SVD on the unscaled sequences): the default
-        if (!split_ok) {
-            // one or two pairs, per-hypothesis tables: the fused kernel (with the same sqrt-free pair step for 1784);
-            // the instrumented replay stays on variant 120, whose counters the flop model was derived with
-            if (g_ransac_variant == 1784 && !stats)
-                launch_ransac_var<248 + 1024>(b, rp, grid, block, false, stream, lt);
-            else
-                launch_ransac_var<120>(b, rp, grid, block, stats, stream, lt);
-            if (stats && b.hyp_F && !b.hyp_count && prescreened_launch(b, n_active, rp.num_hypotheses) && g_ransac_variant == 1784) {
-                // the instrumented replay also runs the product path once with the counting kernel's evaluation counter
-                // (stats[2]): the roofline quotes EXECUTED evaluations for the pruned kernel, not the H x M it avoids
-                hipLaunchKernelGGL((ransac_solve_kernel<240 + 1024>), dim3(G * (kHypPerBlock / kSolveBlock), n_active),
-                                   dim3(kSolveBlock), 0, stream, b, rp, 0);
-                launch_pruned_scoring(b, rp, n_active, stream, nullptr, true);
-            }
-        } else {
-            if (lt) lt->mark(kKRansacSolve);
-            if (g_ransac_variant == 1784)
-                hipLaunchKernelGGL((ransac_solve_kernel<240 + 1024>), dim3(G * (kHypPerBlock / kSolveBlock), n_active),
-                                   dim3(kSolveBlock), 0, stream, b, rp, 0);
-            else
-                hipLaunchKernelGGL((ransac_solve_kernel<112>), grid, block, 0, stream, b, rp, 0);
-            if (b.hyp_count) {
-                if (lt) lt->mark(kKRansacScore);
-                hipLaunchKernelGGL(ransac_score_kernel, grid, block, 0, stream, b, rp);
-            } else {
-                launch_pruned_scoring(b, rp, n_active, stream, lt);
-            }
-        }
-        break;
-    default: launch_ransac_var<120>(b, rp, grid, block, stats, stream, lt); break;
-    }
-#endif
 }
 
 void launch_finalize(const BatchDev &b, const RunParams &rp, int n_active, int mode, hipStream_t stream, LaunchTimer *lt)

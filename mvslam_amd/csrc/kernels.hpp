@@ -324,7 +324,7 @@ enum KernelId : int {
     kKRansacPrescreen, // approximate F + certified band per hypothesis
     kKRansacExactList, // exact solve of the listed hypotheses (flagged by the pre-screen / survivors of the count)
     kKRansacCount2,    // pruned counting with per-hypothesis thresholds (upper / lower bounds of the exact count)
-    kKRansacCountPilot,  // ransac_count32_kernel, phase 0: the first kPilotHyp hypotheses in full -> the pair's first bound
+    kKRansacCountPilot,  // ransac_finish_mfma_kernel<., true>: the first kPilotMfmaHyp hypotheses in full -> the pair's first bound
     kKRansacCountMfma,   // dense counting of the points that must be seen before anything can be dropped: split bf16 on the
                          // matrix cores, no exit tests
     kKRansacCountFinish, // the first batch of every pair's list (largest partial counts): upper and lower count bounds, matrix cores
@@ -335,10 +335,8 @@ enum KernelId : int {
     kKFinSelect,
     kKMatchTopkVec,    // match_topk_kernel<8>: the vector 2-NN kernel when a 256-bit launch is too small for the matrix-core one
     kKernelCountProduct,   // the product library's table ends here
-    // kernels of the experiment ladder: they exist in the diagnostics build (-DMVS_DEBUG_HOOKS) only
-    kKRansacScore = kKernelCountProduct,   // hypothesis-per-lane scoring of stored F records
-    kKRansacCount,     // round 2's pruned counting (one threshold per pair)
-    kKRansacCount32,   // single-precision counting, everything in one launch (A/B: mvs_debug_set_count_dense(0))
+    // exists in the diagnostics build (-DMVS_DEBUG_HOOKS) only
+    kKRansacCount32 = kKernelCountProduct,   // vector single-precision counting, everything in one launch (mvs_debug_set_count_dense(0))
     kKernelCount
 };
 struct LaunchTimer {
@@ -375,16 +373,16 @@ void launch_finalize(const BatchDev &b, const RunParams &rp, int n_active, int m
 // opt-in to > 64 KB of dynamic LDS for the kernels that need it, once per device; hipSuccess or the first error
 hipError_t prepare_kernels();
 #ifdef MVS_DEBUG_HOOKS
-// diagnostics build only (libmvslam_hip_dbg.so): process-global switches, the experiment ladder, checkers
+// diagnostics build only (libmvslam_hip_dbg.so): process-global switches, the reference counting kernel, probes, the audit.
+// (The experiment ladder of rounds 1-3 and its variant switch are gone from the tree; their code is in git history at 77282af.)
 // pair_prepare + ransac_prescreen only, every pair forced into the pre-screened mode
 void launch_prescreen_only(const BatchDev &b, const RunParams &rp, int n_active, int mode, hipStream_t stream);
 void launch_mfma_probe(const uint16_t *A, const uint16_t *B, float *out, hipStream_t stream);
-void set_count_dense(int v);      // 1 = single-precision counting as pilot + dense MFMA phase + finish
+void set_count_dense(int v);      // 1 = single-precision counting as pilot + dense MFMA phase + finish (the product), 0 = one
+                                  // ransac_count32 launch, 2 = ransac_count32 as the finish; 1000 + margin, 100000 + pilot size
 void set_match_mfma(int v);       // 1 (default) 256-bit descriptors on the matrix cores by batch size, 0 the VALU kernel
 void set_prescreen_force(int m);   // -1 probe decides (default), 0 every pair exact, 1 every pair pre-screened
 void set_split_min_pairs(int v);  // launches with fewer pairs stay on the fused hypothesis-per-lane kernel (default 3)
-void set_ransac_variant(int v);  // A/B switch between co-compiled ransac_kernel variants
-int get_ransac_variant();
 void launch_fastmath_check(const double *x, const double *y, int n, unsigned long long *out, hipStream_t stream);
 void launch_pairstep_check(const double *rows, int n, unsigned long long *out, hipStream_t stream);
 // full-population audit of the pre-screened stage (kernels.hip: audit_kernel); out: 16 counters, maxc: [n_active]

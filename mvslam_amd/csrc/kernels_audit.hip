@@ -39,8 +39,8 @@ __global__ __launch_bounds__(256) void pairstep_check_kernel(const double *rows,
     bool ch0 = false, ch1 = false, bad0 = false, bad1 = false;
     unsigned r0 = 0, r1 = 0;
     double q0 = 0x1p1000, q1 = 0x1p1000;
-    jacobi_pair<3, 3, true, true, true, true>(A[0][0], A[0][1], V[0][0], V[0][1], W[0][0], W[0][1], ch0, r0, bad0, q0);
-    jacobi_pair<3, 3, true, false, false, false>(A[1][0], A[1][1], V[1][0], V[1][1], W[1][0], W[1][1], ch1, r1, bad1, q1);
+    jacobi_pair<3, 3, true, true, true>(A[0][0], A[0][1], V[0][0], V[0][1], W[0][0], W[0][1], ch0, r0, bad0, q0);
+    jacobi_pair<3, 3, false, false, false>(A[1][0], A[1][1], V[1][0], V[1][1], W[1][0], W[1][1], ch1, r1, bad1, q1);
     if (ch0 != ch1) {
         atomicAdd(&out[2], 1ull);
         return;
@@ -113,11 +113,11 @@ __global__ __launch_bounds__(256, 1) void audit_kernel(BatchDev b, RunParams rp,
     double F[9];
     unsigned rot = 0, pairs = 0;
     bool bad = false;
-    bool ok = solve_hypothesis<240 + 1024>(seed, hh, M, rp.sampler, P, F, rot, pairs, bad);
+    bool ok = solve_hypothesis<Solve::GuardedCheap>(seed, hh, M, rp.sampler, P, F, rot, pairs, bad);
     if (__builtin_expect(__any(bad), 0)) {
         rot = 0;
         pairs = 0;
-        ok = solve_hypothesis<(240 + 1024) & ~(32 | 128)>(seed, hh, M, rp.sampler, P, F, rot, pairs, bad);
+        ok = solve_hypothesis<Solve::Ieee>(seed, hh, M, rp.sampler, P, F, rot, pairs, bad);
     }
     const unsigned sweeps = pairs / 36u;
     const double thr = pair_max_error_sq(b, rp, pair);

@@ -1,366 +1,277 @@
-// kernels_experiments.hip -- retired experiment kernels and device-side probes.  NOT a translation unit of its own: included
-// by kernels.hip under -DMVS_DEBUG_HOOKS only (libmvslam_hip_dbg.so), after every device function of the product path and in
-// front of the launch wrappers.  Nothing here is reachable from libmvslam_hip.so.  What each kernel was, and why it lost, is in
-// docs/DESIGN_rounds_1_2.md and DESIGN.md 4.3; tools/ab_ransac.py and tests/prescreen_gpu_check.py still run them as A/B
-// references (byte-identical results are asserted against the product path).
+// kernels_experiments.hip -- reference kernels and device-side probes of the diagnostics build.  NOT a translation unit of its
+// own: included by kernels.hip under -DMVS_DEBUG_HOOKS only (libmvslam_hip_dbg.so), after every device function of the product
+// path and in front of the launch wrappers.  Nothing here is reachable from libmvslam_hip.so.  What is here:
+//   ransac_count32_kernel   the vector form of the single-precision counting, which the matrix-core kernels replaced in the
+//                           product.  tests/prescreen_gpu_check.py and tests/constants_gpu_check.py compare
+//                           the product's counting with it: everything in one launch (mvs_debug_set_count_dense(0)) and as
+//                           the finish behind the dense phase (2); byte-identical results are asserted.
+//   mfma_probe_kernel, fastmath_check_kernel   probes of the matrix-core tile and of the unscaled sqrt / div sequences
+//                           (pairstep_check_kernel, the third probe, sits with the audit in kernels_audit.hip).
+// The experiment ladder of rounds 1-3 (ransac_solve / ransac_score / ransac_solve_av / ransac_count behind a variant switch) is
+// gone from the tree; what each kernel was, and why it lost, is in docs/DESIGN_rounds_1_2.md and DESIGN.md 4.3.
 #ifndef MVS_DEBUG_HOOKS
 #error "kernels_experiments.hip belongs to the diagnostics build"
 #endif
 
-template <int VAR>
-__global__ __launch_bounds__(256, 1) void ransac_solve_kernel(BatchDev b, RunParams rp, int respect_mode)
+// Single-precision form of ransac_count2_kernel for pairs in mode 1: the record holds F~ as 9 floats and the two counting
+// thresholds, already widened by the pre-screen's band AND by the bound on the binary32 evaluation error (prescreen.hpp),
+// the points are rounded to binary32 in LDS (16 bytes per point: one ds_read_b128).  v_fma_f32 issues at twice the rate of
+// v_fma_f64, the residual is the same nine instructions.  Exact records do not occur in these pairs before the selection
+// (hypotheses without a certificate wait for the exact solve with an "infinite" count).
+// Packed single precision.  A plain v_fma_f32 issues at the rate of v_fma_f64 on this part (16 lanes per clock and SIMD);
+// the fp32 vector peak is v_pk_fma_f32's: two FMAs per lane and instruction.  Each lane therefore carries TWO points per
+// packed register pair -- the LDS block is laid out so that (x2 of point l, x2 of point l + 64) arrive adjacent -- and F comes
+// straight out of the scalar registers the record was loaded into: op_sel picks the low or the high float of an aligned SGPR
+// pair for both halves, so nothing is duplicated or moved.  Written as inline asm: left to itself hipcc's SLP vectoriser does
+// emit v_pk_fma_f32, but with F splatted into vector register pairs first (200 v_mov per 192 packed FMAs; this file is built
+// with -fno-slp-vectorize).
+typedef __attribute__((address_space(4))) unsigned long long CU64;
+
+// d = a * s.lo + c  /  d = a * s.hi + c  (both halves of a, c; s = an aligned scalar register pair holding two floats)
+__device__ __forceinline__ f32x2 pk_fma_slo(f32x2 a, unsigned long long s, f32x2 c)
 {
-    const int pair = blockIdx.y, tid = threadIdx.x;
-    const int M = b.M[pair];
-    if (M < 8)
-        return;
-    if (respect_mode && b.mode[pair] != 0)
-        return;   // this pair's hypotheses are pre-screened (ransac_prescreen_kernel)
-    solve_record<VAR>(b, rp, pair, M, blockIdx.x * blockDim.x + tid);   // any block size that divides 256 (the launch picks it)
+    f32x2 d;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(d) : "v"(a), "s"(s), "v"(c));
+    return d;
+}
+__device__ __forceinline__ f32x2 pk_fma_shi(f32x2 a, unsigned long long s, f32x2 c)
+{
+    f32x2 d;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(d) : "v"(a), "s"(s), "v"(c));
+    return d;
+}
+__device__ __forceinline__ f32x2 pk_fma_vv(f32x2 a, f32x2 b, f32x2 c)
+{
+    f32x2 d;
+    asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+    return d;
 }
 
+struct Rec32 {                 // one single-precision record as it sits in scalar registers
+    unsigned long long q01, q23, q45;   // (F0, F1), (F2, F3), (F4, F5)
+    f32x2 f6, f7, f8;                   // (F6, F6), (F7, F7), (F8, F8): the inner addends, in vector registers
+    float tu, tl;
+};
 
-// counting without per-hypothesis thresholds -- diagnostics build only (tools/ab_ransac.py)
-constexpr int kScoreChunk = 1024;   // points staged per pass: 32 KB of LDS -> 4 workgroups per CU
-__global__ __launch_bounds__(256) void ransac_score_kernel(BatchDev b, RunParams rp)
+// inliers among the 128 points a wavefront's lanes hold as two packed planes: A = (x1a, x1b, y1a, y1b), B = (x2a, x2b, y2a, y2b)
+__device__ __forceinline__ int count_pair32(const Rec32 &r, const float4 &A, const float4 &B, float thr)
 {
-    const int pair = blockIdx.y, g = blockIdx.x, tid = threadIdx.x;
-    const int M = b.M[pair];
-    WgBest *out = b.wgbest + (size_t)pair * b.max_groups + g;
-    if (M < 8) {  // estimator-RANSAC.cpp:25-29
-        if (tid == 0) {
-            out->count = -1;
-            out->hyp = 0xffffffffu;
-            out->residual = 0.0;
-        }
-        return;
-    }
-    const int H = rp.num_hypotheses;
-    const uint32_t h = (uint32_t)g * kHypPerBlock + tid;
-    const bool live = h < (uint32_t)H;
-    const size_t Hp = (size_t)b.max_groups * kHypPerBlock;
-    const double *Fi = b.hyp_F + ((size_t)pair * Hp + h) * kHypRec;
-    double F[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-        F[k] = Fi[k];
-    const bool ok = b.hyp_okf[(size_t)pair * Hp + h] != 0;
-    const double *P = b.pts + (size_t)pair * b.max_kp * 4;
-    __shared__ __attribute__((aligned(16))) double s_pts[kScoreChunk * 4];
-    const double thr = pair_max_error_sq(b, rp, pair);
-    int cnt = 0;
-    double res = 0.0;
-    for (int c0 = 0; c0 < M; c0 += kScoreChunk) {
-        const int n = min(kScoreChunk, M - c0);
-        __syncthreads();
-        const double2 *src = reinterpret_cast<const double2 *>(P + (size_t)c0 * 4);
-        double2 *dst = reinterpret_cast<double2 *>(s_pts);
-        for (int i = tid; i < 2 * n; i += kHypPerBlock)
-            dst[i] = src[i];
-        __syncthreads();
-        const double4 *L4 = reinterpret_cast<const double4 *>(s_pts);
-#pragma unroll 8
-        for (int i = 0; i < n; ++i) {   // same order and the same operations as the fused kernel: same bits
-            const double4 p = L4[i];
-            const double r = epipolar_residual(F, p.x, p.y, p.z, p.w);
-            const bool in = r < thr;
-            cnt += in ? 1 : 0;
-            res += in ? r : 0.0;   // NaN-safe (a NaN residual is no inlier and adds nothing, as in the reference)
-        }
-    }
-    if (!ok || !live) {
-        cnt = -1;
-        res = 0.0;
-    }
-    if (b.hyp_count && live) {
-        b.hyp_count[(size_t)pair * H + h] = cnt;
-        b.hyp_residual[(size_t)pair * H + h] = res;
-    }
-    // workgroup arg-best
-    Cand me{cnt, h, res};
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        Cand other;
-        other.cnt = __shfl_xor(me.cnt, o);
-        other.hyp = __shfl_xor(me.hyp, o);
-        other.res = __shfl_xor(me.res, o);
-        if (cand_better(other, me))
-            me = other;
-    }
-    __shared__ Cand s_c[4];
-    __shared__ uint32_t s_win;
-    if ((tid & 63) == 0)
-        s_c[tid >> 6] = me;
-    __syncthreads();
-    if (tid == 0) {
-        Cand best = s_c[0];
-#pragma unroll
-        for (int w2 = 1; w2 < 4; ++w2)
-            if (cand_better(s_c[w2], best))
-                best = s_c[w2];
-        s_win = best.hyp;
-        out->count = best.cnt;
-        out->hyp = best.hyp;
-        out->residual = best.res;
-    }
-    __syncthreads();
-    if (h == s_win) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-            out->F[k] = F[k];
-    }
+    const f32x2 X1 = {A.x, A.y}, Y1 = {A.z, A.w}, X2 = {B.x, B.y}, Y2 = {B.z, B.w};
+    const f32x2 u0 = pk_fma_slo(X2, r.q01, pk_fma_shi(Y2, r.q23, r.f6));   // x2 F0 + (y2 F3 + F6)
+    const f32x2 u1 = pk_fma_shi(X2, r.q01, pk_fma_slo(Y2, r.q45, r.f7));   // x2 F1 + (y2 F4 + F7)
+    const f32x2 u2 = pk_fma_slo(X2, r.q23, pk_fma_shi(Y2, r.q45, r.f8));   // x2 F2 + (y2 F5 + F8)
+    const f32x2 e = pk_fma_vv(u0, X1, pk_fma_vv(u1, Y1, u2));
+    // NaN (padding lanes) compares false
+    return __popcll(__ballot(__builtin_fabsf(e.x) < thr)) + __popcll(__ballot(__builtin_fabsf(e.y) < thr));
 }
 
-// ---- A / V wavefront pairs (device_math.hpp: jacobi_A_wave / jacobi_V_wave) --------------------------------------------
-// grid (G, P) as ransac_solve_kernel, but 512 threads: wavefronts 0..3 solve the 256 hypotheses of the group (A role),
-// wavefronts 4..7 carry V^T of the same lanes (V role).  Wavefront w and w + 4 share a SIMD (wavefronts of a workgroup
-// are dealt round-robin to the four SIMDs), each needs <= 256 registers, so the SIMD holds two waves instead of one and
-// nothing lives in AGPRs.  Same F bits as ransac_solve_kernel (the rotations are the same operations in the same
-// order); a violated fast-math guard or a lost partner falls back to the single-wave solve of that wavefront.
-template <int VAR>
-__global__ __launch_bounds__(512, 1) void ransac_solve_av_kernel(BatchDev b, RunParams rp)
+// phase: 1 = everything in one go (no pilot, no dense phase); 2 = the FINISH (every hypothesis resumes behind the points
+// [0, n1) the dense matrix-core phase has already counted: hyp_cnt holds that partial upper-bound count)
+template <int CNT_THREADS, int PPL, int SLOTS, int phase, bool STATS = false>
+__global__ __launch_bounds__(CNT_THREADS) void ransac_count32_kernel(BatchDev b, RunParams rp, int wg_per_pair)
 {
-    __shared__ AvChannel s_ch[4];
-    const int pair = blockIdx.y, g = blockIdx.x, tid = threadIdx.x;
-    const int M = b.M[pair];
-    if (M < 8)
-        return;
-    const int wave = tid >> 6, lane = tid & 63, role = wave >> 2, pidx = wave & 3;
-    if (tid < 4) {
-        AvChannel &c = s_ch[tid];
-#pragma unroll
-        for (int k = 0; k < kAvRing; ++k)
-            c.seq[k] = 0u;
-        c.cons = 0u;
-        c.abort = 0u;
-        c.fin_a = 0u;
-        c.fin_v = 0u;
-    }
-    __syncthreads();
-    AvChannel &ch = s_ch[pidx];
-    if (role == 1) {
-        jacobi_V_wave(ch, lane);
-        return;
-    }
-    const int H = rp.num_hypotheses;
-    const int ta = pidx * 64 + lane;
-    const uint32_t h = (uint32_t)g * kHypPerBlock + ta;
-    const uint32_t hh = h < (uint32_t)H ? h : (uint32_t)(H - 1);
-    const uint64_t seed = rp.seed + (uint64_t)b.gidx[pair];
-    const double *P = b.pts + (size_t)pair * b.max_kp * 4;
-    double F[9];
-    bool bad = false, ok, alive;
-    {
-        int idx[8];
-        sample8(seed, hh, M, rp.sampler, idx);
-        double x1[8], y1[8], x2[8], y2[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const double4 p = *reinterpret_cast<const double4 *>(P + (size_t)idx[k] * 4);
-            x1[k] = p.x; y1[k] = p.y; x2[k] = p.z; y2[k] = p.w;
-        }
-        EightNorm nm;
-        double f[9];
-        {
-            double At[9][9], W[9];
-            ok = eight_point_front(x1, y1, x2, y2, At, nm);
-            alive = jacobi_A_wave(At, W, ch, lane, bad);
-            int tag[9];
-            sort_tags_desc<9>(W, tag);
-            ch.tag8[lane] = tag[8];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (lane == 0)
-            av_store(&ch.fin_a, 1u);
-        alive = alive && av_wait_ge(ch, &ch.fin_v, 1u);
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-            f[k] = ch.f[k][lane];
-        bool bad3 = false;
-        eight_point_back<0>(f, nm, F, bad3);
-    }
-    if (__builtin_expect(__any(bad) || !alive, 0)) {
-        // a fast-math guard was violated (never for Hartley-normalised samples) or the partner was lost: this wavefront
-        // recomputes its 64 hypotheses alone with the compiler's fully scaled sqrt / div (spills to scratch: cold)
-        unsigned rot = 0, pairs = 0;
-        bool bad2 = false;
-        ok = solve_hypothesis<16>(seed, hh, M, rp.sampler, P, F, rot, pairs, bad2);
-    }
-    const size_t Hp = (size_t)b.max_groups * kHypPerBlock;
-    double *Fo = b.hyp_F + ((size_t)pair * Hp + h) * kHypRec;
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-        Fo[k] = F[k];
-    Fo[9] = pair_max_error_sq(b, rp, pair);
-    b.hyp_okf[(size_t)pair * Hp + h] = ok ? kPsExact : kPsInvalid;
-    if (g == 0 && tid == 0)
-        b.bound[pair] = 0;
-}
-
-// ---- pruned scoring: ransac_count_kernel + ransac_select_kernel ------------------------------------------------------
-// The reference keeps the hypothesis with the most inliers, ties by the smaller residual sum, then by the smaller index
-// (estimator-RANSAC.cpp:76-84).  A hypothesis whose count can no longer reach a count that SOME hypothesis of the pair
-// has already achieved in full cannot be that winner, whatever its residual: it is dropped the moment
-//     count so far + points not yet visited  <  bound          (strict: ties stay in)
-// and the result is the same hypothesis, bit for bit, as scoring everything.  On the bench workload 97 % of the
-// hypotheses are contaminated and die after ~1/3 of the points.
-//
-// Mapping (the opposite of the solve): LANES ARE POINTS.  A wavefront takes four hypotheses at a time; their F are
-// wave-uniform (scalar loads of the 72-byte records the solve wrote, SGPR operands of v_fma_f64), each lane reads one
-// point of the current 64-point block from LDS and evaluates it for the hypotheses still alive, v_cmp writes the
-// inlier mask straight to an SGPR pair and s_bcnt1 counts it: 9 VALU instructions per 64 evaluations (the
-// hypothesis-per-lane scoring loop needs 15), no cross-lane traffic, and the exit test is scalar code.  Four
-// hypotheses in flight amortise the LDS read and keep the SALU / branch latency of the exit tests off the critical
-// path (the first attempt in round 1 had one hypothesis in flight and was latency-bound).
-// The bound is per pair: LDS copy per workgroup + one word in global memory (atomicMax, refreshed once per group
-// with the load issued a group ahead).  Which hypotheses get dropped depends on timing; the winner does not.
-// Residual sums are not accumulated here: ransac_select_kernel computes them, in the reference's index order, for the
-// hypotheses that tie at the final maximum only.
-
-__device__ __forceinline__ int count_block(const double (&F)[9], const double4 &p, double thr)
-{
-    const double r = epipolar_residual(F, p.x, p.y, p.z, p.w);
-    return __popcll(__ballot(r < thr));   // NaN (padding lanes, degenerate F) compares false
-}
-
-// PPL = points per lane and block (1: 64-point blocks, 2: 128-point blocks).  With two points per lane the scalar work per
-// (hypothesis, block) -- count add, exit test, slot skip: the scalar unit is shared by the four SIMDs and was ~70 % busy
-// with 8 scalar instructions per 9 vector ones -- is amortised over 18 vector instructions; a dying hypothesis is noticed
-// up to 64 points later.
-template <int CNT_THREADS, int PPL, bool STATS = false>
-__global__ __launch_bounds__(CNT_THREADS) void ransac_count_kernel(BatchDev b, RunParams rp, int wg_per_pair)
-{
-    // two planes of double2, [nblk * 64] each: (x1, y1) and (x2, y2), NaN padded.  A lane reads one element of each with
-    // ds_read_b128 at a 16-byte lane stride = 1 KB contiguous per wavefront: conflict-free (the AoS form, 32-byte
-    // stride, spent as many cycles in bank conflicts as the kernel was busy: profiles/r02_pmc_summary.json history)
+    static_assert(SLOTS == 4 && PPL % 2 == 0, "four records per group; points come in packed pairs");
+    static_assert(phase == 1 || phase == 2, "one launch over everything, or the finish behind the dense phase");
     extern __shared__ __attribute__((aligned(16))) double s_cpts[];
     __shared__ int s_bound;
     const int pair = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     const int M = min(b.M[pair], b.max_kp);
-    if (M < 8)
+    if (M < 8 || b.mode[pair] != 1)
         return;
     const int H = rp.num_hypotheses;
     const size_t Hp = (size_t)b.max_groups * kHypPerBlock;
     constexpr int BW = 64 * PPL;                  // points per block
+    constexpr int NP = PPL / 2;                   // packed pairs per lane and block
     const int nblk = (M + BW - 1) / BW;
-    double2 *s_p1 = reinterpret_cast<double2 *>(s_cpts);
-    double2 *s_p2 = s_p1 + nblk * BW;
+    // points [0, n1) were counted by the dense phase (n1 = dense_points(M, the pilot's bound), a multiple of 32): the finish
+    // starts in the block that holds point n1 and blanks the points before it
+    const int n1 = phase == 2 ? b.dense_n1[pair] : 0;
+    const int blk0 = n1 / BW;
+    // phase 2 works through the pair's list of hypotheses the dense phase left alive, four list entries per group
+    const uint32_t *clist = b.clist + (size_t)pair * Hp;
+    const int n_list = phase == 2 ? b.ccount[pair] : 0;
+    // LDS: [block][pair u][plane A / B][lane] float4; point i = blk * BW + u * 128 + half * 64 + lane sits in half `half`
+    float *s_f = reinterpret_cast<float *>(s_cpts);
     {
         const double4 *src = reinterpret_cast<const double4 *>(b.pts + (size_t)pair * b.max_kp * 4);
-        const double qnan = __builtin_nan("");
+        const float qnan = __builtin_nanf("");
         for (int i = tid; i < nblk * BW; i += CNT_THREADS) {
-            const double4 p = i < M ? src[i] : make_double4(qnan, qnan, qnan, qnan);
-            s_p1[i] = make_double2(p.x, p.y);
-            s_p2[i] = make_double2(p.z, p.w);
+            float x1 = qnan, y1 = qnan, x2 = qnan, y2 = qnan;
+            if (i < M) {
+                const double4 p = src[i];
+                x1 = (float)p.x; y1 = (float)p.y; x2 = (float)p.z; y2 = (float)p.w;
+            }
+            const int blk = i / BW, w = i - blk * BW, u = w >> 7, half = (w >> 6) & 1, l = w & 63;
+            float *A = s_f + ((((size_t)blk * NP + u) * 2 + 0) * 64 + l) * 4;
+            float *Bp = s_f + ((((size_t)blk * NP + u) * 2 + 1) * 64 + l) * 4;
+            A[half] = x1; A[2 + half] = y1;
+            Bp[half] = x2; Bp[2 + half] = y2;
         }
     }
     int *gbound = b.bound + pair;
     if (tid == 0)
         s_bound = __hip_atomic_load(gbound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
-    const double thr = pair_max_error_sq(b, rp, pair);
-    const double *Fp = b.hyp_F + (size_t)pair * Hp * kHypRec;
+    const float *Fp = b.hyp_r32 + (size_t)pair * Hp * kHypRec32;   // 48-byte single-precision records
     const uint32_t *okp = reinterpret_cast<const uint32_t *>(b.hyp_okf + (size_t)pair * Hp);
     int32_t *cntp = b.hyp_cnt + (size_t)pair * Hp;
-    const double2 *L1 = s_p1 + lane, *L2 = s_p2 + lane;
-    const int n_groups = (H + kCntSlots - 1) / kCntSlots;
+    const float4 *L = reinterpret_cast<const float4 *>(s_f) + lane;   // plane stride 64, pair stride 128, block stride 128 NP
+    const int n_groups = phase == 2 ? (n_list + SLOTS - 1) / SLOTS : (H + SLOTS - 1) / SLOTS;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n_waves = wg_per_pair * (CNT_THREADS / 64);
     int B = 0;
-    unsigned long long visits = 0;   // STATS: (hypothesis, block) evaluations this wavefront executed
+    unsigned long long visits = 0;
     for (int g = blockIdx.x * (CNT_THREADS / 64) + wave; g < n_groups; g += n_waves) {
-        const int h0 = g * kCntSlots;
-        // the pair's bound as other workgroups see it: load now, use after this group
+        const int h0 = g * SLOTS;
         const int gb = __hip_atomic_load(gbound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         B = __builtin_amdgcn_readfirstlane(max(B, *(volatile int *)&s_bound));
-        // constant address space: wave-uniform scalar loads (s_load_dwordx16 through the scalar cache) instead of 18
-        // same-address vector loads per group, which kept the texture-address unit busier than the VALU.  The records
-        // were written by the solve launch; nothing writes them while this kernel runs.
-        double F0[9], F1[9], F2[9], F3[9];
-        const CDouble *f = (const CDouble *)(uintptr_t)(Fp + (size_t)h0 * kHypRec);
+        // the four hypotheses of the group: consecutive ones, or (finish) four entries of the list
+        int hq[SLOTS];
+        if (phase == 2) {
+            const uint32_t mine = lane < SLOTS && h0 + lane < n_list ? clist[h0 + lane] : 0u;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            F0[k] = f[k];
-            F1[k] = f[kHypRec + k];
-            F2[k] = f[2 * kHypRec + k];
-            F3[k] = f[3 * kHypRec + k];
+            for (int q = 0; q < SLOTS; ++q)
+                hq[q] = __builtin_amdgcn_readlane((int)mine, q);
+        } else {
+#pragma unroll
+            for (int q = 0; q < SLOTS; ++q)
+                hq[q] = h0 + q;
         }
-        // a v_fma_f64 takes one SGPR operand: keep the addend of the inner FMA (F[6..8]) in VGPRs for the whole group,
-        // otherwise it is copied there again for every block
+        Rec32 R[SLOTS];
 #pragma unroll
-        for (int k = 6; k < 9; ++k) {
-            asm volatile("" : "+v"(F0[k]));
-            asm volatile("" : "+v"(F1[k]));
-            asm volatile("" : "+v"(F2[k]));
-            asm volatile("" : "+v"(F3[k]));
+        for (int q = 0; q < SLOTS; ++q) {
+            // (one base + constant offsets when the four records are neighbours: the loads coalesce)
+            const CU64 *f = phase == 2 ? (const CU64 *)(uintptr_t)(Fp + (size_t)hq[q] * kHypRec32)
+                                       : (const CU64 *)(uintptr_t)(Fp + (size_t)h0 * kHypRec32) + q * (kHypRec32 / 2);
+            R[q].q01 = f[0];
+            R[q].q23 = f[1];
+            R[q].q45 = f[2];
+            const unsigned long long q67 = f[3], q8u = f[4], ql = f[5];
+            const float f6 = __uint_as_float((unsigned)q67), f7 = __uint_as_float((unsigned)(q67 >> 32));
+            const float f8 = __uint_as_float((unsigned)q8u);
+            R[q].f6 = f32x2{f6, f6};
+            R[q].f7 = f32x2{f7, f7};
+            R[q].f8 = f32x2{f8, f8};
+            R[q].tu = __uint_as_float((unsigned)(q8u >> 32));
+            R[q].tl = __uint_as_float((unsigned)ql);
         }
-        const uint32_t ok4 = __builtin_amdgcn_readfirstlane(okp[g]);
-        unsigned alive = 0;
+        unsigned alive = 0, wait = 0;
+        int c[SLOTS];
 #pragma unroll
-        for (int k = 0; k < kCntSlots; ++k)
-            alive |= (((ok4 >> (8 * k)) & 0xffu) != 0 && h0 + k < H) ? (1u << k) : 0u;
-        int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-        // two register sets for the block's points, used alternately: the next block's points are requested before this
-        // block's arithmetic (the uniform branches keep the compiler from hoisting the loads) and the LDS round trip hides
-        // under the four slots; with one set plus a "next" set the loop carried eight v_mov_b64 per block, a fifth of
-        // its vector instructions once two of the four slots have died
-        double2 pa0[PPL], pb0[PPL], pa1[PPL], pb1[PPL];
-        auto load = [&](double2 (&pa)[PPL], double2 (&pb)[PPL], int blk) {
-            const int nb = min(blk, nblk - 1) * BW;
+        for (int q = 0; q < SLOTS; ++q)
+            c[q] = 0;
+        if (phase == 2) {
+            // resume: every listed hypothesis is an approximate record; the dense phase left its upper-bound count over
+            // points [0, n1) in hyp_cnt.  A slot that cannot reach the bound (it may have risen since the list was
+            // written) even if every remaining point were an inlier is dead on arrival
+            const int have = lane < SLOTS && h0 + lane < n_list ? cntp[clist[h0 + lane]] : 0;
 #pragma unroll
-            for (int u = 0; u < PPL; ++u) {
-                pa[u] = L1[nb + u * 64];
-                pb[u] = L2[nb + u * 64];
+            for (int q = 0; q < SLOTS; ++q) {
+                c[q] = __builtin_amdgcn_readlane(have, q);
+                if (h0 + q < n_list && !(c[q] + (M - n1) < B))
+                    alive |= 1u << q;
             }
-        };
-        auto process = [&](const double2 (&pa)[PPL], const double2 (&pb)[PPL], int blk) {
-            double4 p[PPL];
+        } else {
+            const uint32_t ok4 = __builtin_amdgcn_readfirstlane(okp[g]);
+#pragma unroll
+            for (int k = 0; k < SLOTS; ++k) {
+                const unsigned st = (ok4 >> (8 * k)) & 0xffu;
+                alive |= (st == kPsApprox && h0 + k < H) ? (1u << k) : 0u;
+                wait |= (st == kPsNeedExact && h0 + k < H) ? (1u << k) : 0u;
+            }
+        }
+        float4 pa[PPL], pb[PPL];   // [2 u] = plane A, [2 u + 1] = plane B of packed pair u
+        auto load = [&](float4 (&p)[PPL], int blk) {
+            const int nb = min(blk, nblk - 1) * (128 * NP);
 #pragma unroll
             for (int u = 0; u < PPL; ++u)
-                p[u] = make_double4(pa[u].x, pa[u].y, pb[u].x, pb[u].y);
+                p[u] = L[nb + u * 64];
+            if (blk == blk0 && n1 > blk0 * BW) {
+                // the dense phase has already counted the points of this block below n1: blank them (NaN is no inlier).
+                // p[2 u] / p[2 u + 1] hold points blk BW + 128 u + lane (x, z components) and + 64 (y, w components)
+                const float qnan = __builtin_nanf("");
+#pragma unroll
+                for (int u = 0; u < NP; ++u) {
+                    const int i0 = blk * BW + u * 128 + lane;
+                    if (i0 < n1) { p[2 * u].x = qnan; p[2 * u + 1].x = qnan; }
+                    if (i0 + 64 < n1) { p[2 * u].y = qnan; p[2 * u + 1].y = qnan; }
+                }
+            }
+        };
+        auto process = [&](const float4 (&p)[PPL], int blk) {
             const int need = B - max(M - (blk + 1) * BW, 0);   // a slot whose count stays below this cannot reach B
             if (STATS)
                 visits += (unsigned)__builtin_popcount(alive);
-            if (alive & 1u) {
+            if (alive == (1u << SLOTS) - 1u) {
+                // all four alive (the usual state until they die together): one straight-line stretch, so that the
+                // scheduler interleaves the slots' independent FMA chains -- slot by slot behind uniform branches a
+                // wavefront has two short dependent chains in flight and the SIMD waits on latencies
+                int add[SLOTS];
 #pragma unroll
-                for (int u = 0; u < PPL; ++u)
-                    c0 += count_block(F0, p[u], thr);
-                if (c0 < need) alive &= ~1u;
-            }
-            if (alive & 2u) {
+                for (int q = 0; q < SLOTS; ++q) {
+                    add[q] = 0;
 #pragma unroll
-                for (int u = 0; u < PPL; ++u)
-                    c1 += count_block(F1, p[u], thr);
-                if (c1 < need) alive &= ~2u;
-            }
-            if (alive & 4u) {
+                    for (int u = 0; u < NP; ++u)
+                        add[q] += count_pair32(R[q], p[2 * u], p[2 * u + 1], R[q].tu);
+                }
 #pragma unroll
-                for (int u = 0; u < PPL; ++u)
-                    c2 += count_block(F2, p[u], thr);
-                if (c2 < need) alive &= ~4u;
-            }
-            if (alive & 8u) {
+                for (int q = 0; q < SLOTS; ++q) {
+                    c[q] += add[q];
+                    alive &= (c[q] < need) ? ~(1u << q) : ~0u;
+                }
+            } else {
 #pragma unroll
-                for (int u = 0; u < PPL; ++u)
-                    c3 += count_block(F3, p[u], thr);
-                if (c3 < need) alive &= ~8u;
+                for (int q = 0; q < SLOTS; ++q) {
+                    if (alive & (1u << q)) {
+#pragma unroll
+                        for (int u = 0; u < NP; ++u)
+                            c[q] += count_pair32(R[q], p[2 * u], p[2 * u + 1], R[q].tu);
+                        if (c[q] < need) alive &= ~(1u << q);
+                    }
+                }
             }
         };
-        load(pa0, pb0, 0);
-        for (int blk = 0; blk < nblk && alive; blk += 2) {
-            load(pa1, pb1, blk + 1);
-            process(pa0, pb0, blk);
+        if (alive)
+            load(pa, blk0);
+        for (int blk = blk0; blk < nblk && alive; blk += 2) {
+            load(pb, blk + 1);
+            process(pa, blk);
             if (!(blk + 1 < nblk && alive))
                 break;
-            load(pa0, pb0, blk + 2);
-            process(pa1, pb1, blk + 1);
+            load(pa, blk + 2);
+            process(pb, blk + 1);
         }
-        // a slot that is still alive has seen every point: its count is final
-        const int v0 = (alive & 1u) ? c0 : -1, v1 = (alive & 2u) ? c1 : -1;
-        const int v2 = (alive & 4u) ? c2 : -1, v3 = (alive & 8u) ? c3 : -1;
-        if (lane < kCntSlots)
-            cntp[h0 + lane] = lane == 0 ? v0 : lane == 1 ? v1 : lane == 2 ? v2 : v3;
-        const int cm = __builtin_amdgcn_readfirstlane(max(max(v0, v1), max(v2, v3)));
+        // lower bounds of the slots that saw every point: one more pass against the lower threshold
+        int v[SLOTS], lo[SLOTS];
+        int cm = -1;
+#pragma unroll
+        for (int q = 0; q < SLOTS; ++q) {
+            const bool al = (alive >> q) & 1u;
+            v[q] = al ? c[q] : ((wait >> q) & 1u) ? 0x7fffffff : -1;
+            lo[q] = -1;
+            if (al) {
+                int cl = 0;
+                for (int blk = 0; blk < nblk; ++blk) {
+#pragma unroll
+                    for (int u = 0; u < NP; ++u)
+                        cl += count_pair32(R[q], L[blk * (128 * NP) + (2 * u) * 64], L[blk * (128 * NP) + (2 * u + 1) * 64], R[q].tl);
+                }
+                if (STATS)
+                    visits += (unsigned)nblk;
+                lo[q] = cl;
+            }
+            cm = max(cm, lo[q]);
+        }
+        if (lane < SLOTS && (phase != 2 || h0 + lane < n_list)) {
+            int mine = v[0], where = hq[0];
+#pragma unroll
+            for (int q = 1; q < SLOTS; ++q) {
+                mine = lane == q ? v[q] : mine;
+                where = lane == q ? hq[q] : where;
+            }
+            cntp[where] = mine;
+        }
+        cm = __builtin_amdgcn_readfirstlane(cm);
         if (cm > B) {
             B = cm;
             if (lane == 0) {
@@ -371,7 +282,28 @@ __global__ __launch_bounds__(CNT_THREADS) void ransac_count_kernel(BatchDev b, R
         B = max(B, __builtin_amdgcn_readfirstlane(gb));
     }
     if (STATS && lane == 0 && b.stats)
-        atomicAdd(&b.stats[2], visits * (unsigned long long)BW);   // executed (hypothesis, point) evaluations incl. padding
+        atomicAdd(&b.stats[3], visits * (unsigned long long)BW);   // executed single-precision evaluations
+}
+
+constexpr int kCnt32Threads = 768;
+constexpr int kCnt32Slots = 4;     // hypotheses a wavefront carries at a time
+constexpr int kCnt32Ppl = 4;       // single-precision counting: four points per lane and block (scalar work per evaluation halves)
+static size_t count32_lds_bytes(int max_kp)
+{
+    const int bw = 64 * kCnt32Ppl;
+    return (size_t)((max_kp + bw - 1) / bw) * bw * 4 * sizeof(float);
+}
+template <int phase>
+static void launch_count32(const BatchDev &b, const RunParams &rp, int wg, int n_active, bool stats, hipStream_t stream)
+{
+    const dim3 grid(wg, n_active), block(kCnt32Threads);
+    const size_t lds = count32_lds_bytes(b.max_kp);
+    if (stats)
+        hipLaunchKernelGGL((ransac_count32_kernel<kCnt32Threads, kCnt32Ppl, kCnt32Slots, phase, true>), grid, block, lds, stream, b,
+                           rp, wg);
+    else
+        hipLaunchKernelGGL((ransac_count32_kernel<kCnt32Threads, kCnt32Ppl, kCnt32Slots, phase>), grid, block, lds, stream, b, rp,
+                           wg);
 }
 
 
@@ -432,4 +364,3 @@ __global__ __launch_bounds__(256) void fastmath_check_kernel(const double *x, co
             atomicAdd(&out[1], 1ull);
     }
 }
-

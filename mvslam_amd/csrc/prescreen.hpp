@@ -236,7 +236,6 @@ MVS_DEV constexpr int ps_tri(int i, int k) { return k * (k - 1) / 2 + i; }   // 
 // a fresh gather of point j, the reflectors 0 .. j-1 are applied to it, its entries above the diagonal are final entries of
 // R and are parked in LDS, the rest defines reflector j.  Neither A nor the normalised sample ever exists as a whole in
 // registers: live state is the reflectors (44 doubles) + one column, and the kernel fits two wavefronts per SIMD.
-template <int VAR>
 MVS_DEV int prescreen_hypothesis(const double *P, int (&idx)[8], double *park, const PairBox &bx, double thr, double (&F)[9],
                                  double &band_out, double &e32_out, bool &bad3)
 {

@@ -114,15 +114,18 @@ def test_synthetic_generator_is_deterministic():
 
 
 def test_product_library_has_one_path_and_no_experiment_ladder():
-    """the co-compiled kernel variants of rounds 1-2 (one of which computes wrong results by design), the
-    process-global variant switches and the checkers live in the diagnostics library only.  The product library's symbol
-    table AND its embedded device code hold neither; the diagnostics library holds all of them (so the check is not
-    vacuous)."""
+    """process-global switches, the reference counting kernel and the checkers live in the diagnostics library
+    only.  The product library's symbol table AND its embedded device code hold none of them; the diagnostics library holds
+    all of them (so the check is not vacuous).  The experiment ladder of rounds 1-3 (one of whose variants computed wrong
+    results by design) and its variant switch are in neither library any more, and the fused kernel exists in the two
+    instantiations that are launched (product: not instrumented, Solve::GuardedCheap = 2; replay: instrumented,
+    Solve::Guarded = 1), not in the other two combinations."""
     from mvslam_amd import capi
 
-    gone = ["ransac_solve_av_kernel", "ransac_score_kernel", "set_ransac_variant", "set_count_dense", "set_prescreen_force",
-            "set_match_mfma", "g_ransac_variant", "g_force_mode", "g_count_dense", "g_match_mfma", "fastmath_check_kernel",
-            "pairstep_check_kernel", "mfma_probe_kernel", "mvs_debug_", "ransac_kernelILb0ELi376", "ransac_kernelILb0ELi0"]
+    gone = ["set_count_dense", "set_prescreen_force", "set_match_mfma", "g_force_mode", "g_count_dense", "g_match_mfma",
+            "fastmath_check_kernel", "pairstep_check_kernel", "mfma_probe_kernel", "mvs_debug_", "ransac_count32_kernel"]
+    nowhere = ["ransac_solve_av_kernel", "ransac_score_kernel", "set_ransac_variant", "g_ransac_variant", "ransac_kernelILb0ELi376",
+               "ransac_kernelILb0ELi0", "ransac_kernelILb0ELb1ELNS_5SolveE1E", "ransac_kernelILb1ELb1ELNS_5SolveE2E"]
 
     def names(path):
         sym = subprocess.check_output(["nm", "-a", path]).decode()
@@ -133,9 +136,13 @@ def test_product_library_has_one_path_and_no_experiment_ladder():
     for g in gone:
         assert g not in prod, "libmvslam_hip.so still contains %s" % g
         assert g in dbg, "libmvslam_hip_dbg.so lost %s" % g
+    for g in nowhere:
+        assert g not in prod, "libmvslam_hip.so still contains %s" % g
+        assert g not in dbg, "libmvslam_hip_dbg.so still contains %s" % g
     # ... and what the product path launches is there
     for k in ("ransac_prescreen_kernel", "ransac_count_mfma_kernel", "ransac_exact_list_kernel", "ransac_select_kernel",
-              "match_mfma_kernel", "finalize_model_kernel"):
+              "match_mfma_kernel", "finalize_model_kernel", "ransac_kernelILb0ELb1ELNS_5SolveE2E",
+              "ransac_kernelILb1ELb1ELNS_5SolveE1E"):
         assert k in prod, k
 
 
@@ -156,7 +163,7 @@ def test_hot_kernels_do_not_spill():
     for k, v in one("ransac_prescreen_kernel").items():
         assert v["scratch_bytes_per_lane"] == 0 and v["vgpr_spills"] == 0 and v["occupancy_waves_per_simd"] >= 3, (k, v)
     for prefix in ("ransac_count_mfma_kernelILb0", "ransac_finish_mfma_kernelILb0", "ransac_finish_upper_kernelILb0",
-                   "ransac_count32_kernel", "ransac_count2_kernel", "match_mfma_kernel", "triangulate_kernel"):
+                   "ransac_count2_kernel", "match_mfma_kernel", "triangulate_kernel"):
         for k, v in one(prefix).items():
             assert v["scratch_bytes_per_lane"] == 0, (k, v)
             assert v["agprs"] == 0 or "mfma" not in prefix, (k, v)     # MFMA results stay in VGPRs (no v_accvgpr_read per use)

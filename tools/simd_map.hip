@@ -1,5 +1,5 @@
 // Which SIMD does wavefront w of a 512-thread workgroup land on?  (HW_ID.SIMD_ID, bits 5:4 of hwreg 4 on gfx9-family.)
-// The A / V wavefront pairs of ransac_solve_av_kernel assume that wavefronts w and w + 4 share a SIMD.
+// (Round 2's A / V wavefront-pair experiment, since removed, assumed that wavefronts w and w + 4 share a SIMD.)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 __global__ __launch_bounds__(512) void k(unsigned *out)
