@@ -139,48 +139,76 @@ __global__ __launch_bounds__(1024) void match_topk_kernel(BatchDev b, double rat
 
 // ---------------------------------------------------------------------------------------------
 // match_mfma (256-bit descriptors): the same 2-NN on the matrix cores.  Hamming(q, t) = |q| + |t| - 2 q.t with the bits as
-// {0, 1} int8: the all-pairs dot products of a pair are one [train x 256] . [256 x query] GEMM, exact in the i32
-// accumulators of v_mfma_i32_32x32x32_i8 (8 k-steps per 32 x 32 tile).  grid (ceil(N / 256), P), block 512 = 8 wavefronts;
-// wavefront w owns 32 queries (the MFMA's columns = lanes) whose unpacked bits stay in registers for the whole scan (the B
-// operand: 8 x 4 VGPRs); trains go by in tiles of 32 rows (the A operand), unpacked ONCE per workgroup into LDS (bit ->
-// byte: a nibble times 0x00204081, masked with 0x01010101, is its four bits as four bytes) and read by every wavefront
-// with ds_read_b128.  The accumulator tile has the query on the lane and 16 trains in the registers: key = ((|t| + 256) << 16
-// | index) - (dot << 17) is ONE v_mad_i32_i24 per element (the query's own popcount, equal for all its keys, is added at the
-// end; unique keys ordered like (distance, index), as in match_topk), inserted into the lane's running top-2 with v_min_u32 +
-// v_med3_u32.  Lanes l and l + 32 hold the same query over different rows and merge at the end.  Both operands take the
-// same (lane half, element) -> bit mapping, so the dot product does not depend on the k order inside a step.
+// {0, 1}: the all-pairs dot products of a pair are one [train x 256] . [256 x query] GEMM, done in FP4 (e2m1) on the block-scaled
+// v_mfma_scale_f32_32x32x64_f8f6f4 (4 k-steps per 32 x 32 tile; the same cycles as the int8 form's 32-deep step) and exact in
+// its binary32 accumulators (below).  grid (ceil(N / 256), P), block kMmThreads; wavefront w owns kMmBlocks x 32 queries (the
+// MFMA's columns = lanes) whose unpacked bits stay in registers for the whole scan (the B operand: 4 x 4 VGPRs per block);
+// trains go by in tiles of 32 rows (the A operand), unpacked ONCE per workgroup into LDS and read by every wavefront with
+// ds_read_b128.  The accumulator tile has the query on the lane and 16 trains in the registers; the matrix core leaves the
+// finished keys there (the query's own popcount, equal for all its keys, is added at the end; unique keys ordered like
+// (distance, index), as in match_topk), inserted into the lane's running top-2 with v_min_u32 + v_med3_u32 on the raw bits.
+// Lanes l and l + 32 hold the same query over different rows and merge at the end.  Both operands take the same
+// (lane half, element) -> bit mapping (step s, lane half h: descriptor dword 2 s + h, nibble_of below), so the dot product
+// does not depend on the k order inside a step.
+//
+// Exactness.  Train bit 1 -> e2m1 +1.0 (0b0010), query bit 1 -> e2m1 -1.0 (0b1010), 0 -> 0; the train operand's E8M0 block
+// scale is 2^13, the query's 2^0: a common bit adds exactly -8192 = -(2 << 12).  The C operand of a chain's first step is the
+// row's key base (|t| + 257) << 12 | index as a float: below 2^22 (kMaxKp <= 4096, static_assert), so exact.  Every product is
+// 0 or -8192 and every partial sum lies in (-2^22, 2^23) and is an integer, so every sum in any order is exact in binary32:
+// the tile leaves key = (|t| + 257 - 2 dot) * 4096 + index exactly.  dot <= |t| <= 256 makes the distance field >= 1, so a key
+// is a positive float (never a cancelled, possibly signed, zero), and the bit patterns of positive floats order like their
+// values: v_min3_u32 / v_min_u32 / v_med3_u32 on the accumulator bits, the group minima and the cap test against the cap
+// key's float pattern need no conversion; only the two keys written out are converted back to integers.  Rows past the end
+// have all-zero bits and the base kMmKeyNone (2^24, above every key): the key stays kMmKeyNone, never selected.  The
+// argument rests on the matrix core summing exactly; tests/test_match_fp4.py checks the extremes on the device.
 // ---------------------------------------------------------------------------------------------
-constexpr int kMmThreads = 256;
-constexpr int kMmQpw = 64;                           // queries per wavefront: two 32-column blocks share every A fragment read
-constexpr int kMmQueries = kMmQpw * (kMmThreads / 64);   // 256 queries per workgroup
-constexpr int kMmRowBytes = 256 + 16;                // unpacked row of a train tile, padded: ds_read_b128 of 32 rows spread over the banks
-constexpr int kMmKeyShift = 12;                      // key = distance field << 12 | train index: one int8 product (64 x -128) is -(2 << 12)
+constexpr int kMmBlocks = 2;                         // 32-query blocks per wavefront: every A fragment read feeds kMmBlocks chains
+constexpr int kMmQueries = 256;                      // queries per workgroup
+constexpr int kMmThreads = 64 * kMmQueries / (32 * kMmBlocks);
+constexpr int kMmRowBytes = 128 + 16;                // unpacked row of a train tile (256 nibbles), padded: a ds_read_b128 of 16
+                                                     // rows at a 36-dword stride covers all 64 banks once
+constexpr int kMmKeyShift = 12;                      // key = distance field << 12 | train index: one product is -(2 << 12)
+constexpr int kMmKeyBias = 257;                      // distance field = |t| + 257 - 2 dot >= 1
+constexpr uint32_t kMmKeyNone = 0x4b800000u;         // 2^24 as a float: the key of no row
+constexpr int kMmScaleTrain = 127 + 13, kMmScaleQuery = 127;   // E8M0 block scales: 2^13 and 2^0
 static_assert(kMaxKp <= (1 << kMmKeyShift), "the train index must fit below the distance field of a match_mfma key");
+static_assert((kMmKeyBias + 256 + 1) << kMmKeyShift <= (1 << 22), "match_mfma keys must stay exact binary32 integers");
+static_assert(kMmThreads <= 256 && 256 % kMmThreads == 0, "the staging maps 32 rows x 8 dwords onto the workgroup");
 typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef float v16f __attribute__((ext_vector_type(16)));
 
-// 16 bits -> 16 bytes (element j = bit j), each byte 0 or 1 << SH.  A nibble times 0x00204081 has bit i of the nibble at
-// positions i + 7 k (k = 0..3: no two terms meet, no carries); the mask keeps bit 0 of every byte, the shift moves it to bit
-// SH.  SH = 6: the train operand (0 / 64); SH = 7: the query operand (0 / 0x80 = -128 as int8), so that one product is
-// -8192 = -(2 << 12): the accumulator counts the dot product in units of the key's distance field (below).  The product is a
-// 4-bit by 22-bit one: v_mul_u32_u24 (full rate; v_mul_lo_u32 issues at a quarter of it -- eight of them per thread and tile
-// were a third of the staging's issue slots).
-template <int SH>
-__device__ __forceinline__ v4i unpack16(uint32_t bits)
+// 32 bits -> 32 e2m1 nibbles, each 0 or +1.0 (0b0010): output dword j holds byte j, nibble 2 i = bit 8 j + i, nibble 2 i + 1 =
+// bit 8 j + 4 + i.  A nibble times 0x00408102 (= 2 x 0x00204081) has bit i of the nibble at positions i + 7 k + 1 (k = 0..3: no
+// two terms meet, no carries); the mask keeps bit 1 of every byte, and the high nibble's bits go four above the low one's.  The
+// product is a 4-bit by 23-bit one: v_mul_u32_u24 (full rate; v_mul_lo_u32 issues at a quarter of it).  The merge is inline
+// asm: hipcc otherwise folds the high nibble's shift into its multiplier (0x04081020, past 24 bits: v_mul_lo_u32).
+__device__ __forceinline__ uint32_t lshl4_or(uint32_t hi, uint32_t lo)
+{
+    uint32_t r;
+    asm("v_lshl_or_b32 %0, %1, 4, %2" : "=v"(r) : "v"(hi), "v"(lo));
+    return r;
+}
+__device__ __forceinline__ v4i unpack32_fp4(uint32_t bits)
 {
     v4i r;
-    r.x = (int)((__umul24((bits >> 0) & 0xfu, 0x00204081u) & 0x01010101u) << SH);
-    r.y = (int)((__umul24((bits >> 4) & 0xfu, 0x00204081u) & 0x01010101u) << SH);
-    r.z = (int)((__umul24((bits >> 8) & 0xfu, 0x00204081u) & 0x01010101u) << SH);
-    r.w = (int)((__umul24((bits >> 12) & 0xfu, 0x00204081u) & 0x01010101u) << SH);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t lo = __umul24((bits >> (8 * j)) & 0xfu, 0x00408102u) & 0x02020202u;
+        const uint32_t hi = __umul24((bits >> (8 * j + 4)) & 0xfu, 0x00408102u) & 0x02020202u;
+        r[j] = (int)lshl4_or(hi, lo);
+    }
     return r;
 }
 
-__device__ __forceinline__ uint32_t umin3(uint32_t a, uint32_t b, uint32_t c)
+// The matrix-core kernel reads its accumulators with compiler-visible min / max only (hipcc forms v_min3_u32 itself): the
+// hazard recognizer inserts no wait states in front of inline asm, and an inline-asm v_med3_u32 straight after the last MFMA
+// of a chain read accumulator registers the matrix core had not finished writing (nondeterministic lists).
+__device__ __forceinline__ uint32_t umin3(uint32_t a, uint32_t b, uint32_t c) { return min(min(a, b), c); }
+__device__ __forceinline__ void key_insert_mm(uint32_t &k0, uint32_t &k1, uint32_t k)
 {
-    uint32_t r;
-    asm("v_min3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
+    k1 = min(k1, max(k0, k));
+    k0 = min(k0, k);
 }
 
 // CAPPED (round 5): the caller's max_dist >= 0 makes most keys irrelevant.  A query passes iff D0 <= max_dist and
@@ -197,8 +225,8 @@ __global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(3, 8
                                                                                                             double max_dist, int cap_dist)
 {
     __shared__ __attribute__((aligned(16))) unsigned char s_tile[2][32 * kMmRowBytes];   // unpacked train tiles (double buffer)
-    __shared__ __attribute__((aligned(16))) uint32_t s_key[2][32];                        // (|t| + 256) << 12 | train index
-    __shared__ uint32_t s_k0[2][kMmThreads], s_k1[2][kMmThreads];
+    __shared__ __attribute__((aligned(16))) float s_key[2][32];                           // (|t| + 257) << 12 | train index
+    __shared__ uint32_t s_k0[kMmBlocks][kMmThreads], s_k1[kMmBlocks][kMmThreads];
     const int pair = blockIdx.y;
     const int n1 = min(b.n1[pair], b.max_kp), n2 = min(b.n2[pair], b.max_kp);
     const int q0 = blockIdx.x * kMmQueries;
@@ -206,84 +234,96 @@ __global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(3, 8
         return;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, col = lane & 31, half = lane >> 5;
     const size_t base = (size_t)pair * b.max_kp;
-    // B operands: this lane's 16-bit slices of its two queries (column blocks 0 and 1), one per k-step, unpacked once
-    v4i Bf[2][8];
-    int qn[2];
+    // B operands: this lane's 32-bit slices of its queries (one per column block), one per k-step, unpacked once.  The query
+    // form is the train form's nibbles times 5: 0b0010 -> 0b1010 (-1.0).  Only the low four registers of an FP4 operand are read.
+    v8i Bf[kMmBlocks][4];
+    int qn[kMmBlocks];
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const int q = q0 + w * kMmQpw + c * 32 + col;
+    for (int c = 0; c < kMmBlocks; ++c) {
+        const int q = q0 + w * 32 * kMmBlocks + c * 32 + col;
         const uint32_t *qd = b.desc2 + (base + (q < n2 ? q : q0)) * 8;
         const uint4 lo = *reinterpret_cast<const uint4 *>(qd), hi = *reinterpret_cast<const uint4 *>(qd + 4);
         const uint32_t d[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
         qn[c] = 0;
 #pragma unroll
-        for (int s8 = 0; s8 < 8; ++s8) {
-            qn[c] += __popc(d[s8]);
-            Bf[c][s8] = unpack16<7>(d[s8] >> (16 * half));
+        for (int s = 0; s < 8; ++s)
+            qn[c] += __popc(d[s]);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const v4i t = unpack32_fp4((uint32_t)((((uint64_t)d[2 * s + 1] << 32) | d[2 * s]) >> (32 * half)));
+            const v4i m = t | (t << 2);   // once per kernel: hipcc's v_mul_lo_u32 by 5 here is harmless
+            Bf[c][s] = __builtin_shufflevector(m, m, 0, 1, 2, 3, -1, -1, -1, -1);
         }
     }
     const uint32_t *tr = b.desc1 + base * 8;
-    // stage tile `t` (trains [32 t, 32 t + 32)) into buffer `buf`: thread = (row, dword): 32 bits -> 32 bytes
+    // stage tile `t` (trains [32 t, 32 t + 32)) into buffer `buf`: work item = (row, dword): 32 bits -> 32 nibbles = 16 bytes
     auto stage = [&](int t, int buf) {
-        const int row = tid >> 3, dw = tid & 7;
-        const int tr_i = t * 32 + row;
-        const uint32_t bits = tr_i < n1 ? tr[(size_t)tr_i * 8 + dw] : 0u;
-        unsigned char *dst = &s_tile[buf][row * kMmRowBytes + dw * 32];
-        *reinterpret_cast<v4i *>(dst) = unpack16<6>(bits);
-        *reinterpret_cast<v4i *>(dst + 16) = unpack16<6>(bits >> 16);
-        // the tile's key bases: |t| of the row, summed over its 8 dwords (8 adjacent lanes)
-        int tn = __popc(bits);
-        tn += __shfl_xor(tn, 1);
-        tn += __shfl_xor(tn, 2);
-        tn += __shfl_xor(tn, 4);
-        if (dw == 0)
-            s_key[buf][row] = tr_i < n1 ? (((uint32_t)(tn + 256) << kMmKeyShift) | (uint32_t)tr_i) : 0xffffffffu;
+#pragma unroll
+        for (int i = 0; i < 256 / kMmThreads; ++i) {
+            const int it = tid + i * kMmThreads, row = it >> 3, dw = it & 7;
+            const int tr_i = t * 32 + row;
+            const uint32_t bits = tr_i < n1 ? tr[(size_t)tr_i * 8 + dw] : 0u;
+            *reinterpret_cast<v4i *>(&s_tile[buf][row * kMmRowBytes + dw * 16]) = unpack32_fp4(bits);
+            // the tile's key bases: |t| of the row, summed over its 8 dwords (8 adjacent lanes)
+            int tn = __popc(bits);
+            tn += __shfl_xor(tn, 1);
+            tn += __shfl_xor(tn, 2);
+            tn += __shfl_xor(tn, 4);
+            if (dw == 0)
+                s_key[buf][row] = tr_i < n1 ? (float)(((tn + kMmKeyBias) << kMmKeyShift) | tr_i) : __uint_as_float(kMmKeyNone);
+        }
     };
     const int n_tiles = (n1 + 31) / 32;
-    uint32_t k0[2] = {kKeyNone, kKeyNone}, k1[2] = {kKeyNone, kKeyNone};
-    // relevant keys of this lane's two queries: distance = (key >> 12) - 256 + |q| < cap_dist
-    const uint32_t capk[2] = {(uint32_t)(cap_dist + 256 - qn[0]) << kMmKeyShift, (uint32_t)(cap_dist + 256 - qn[1]) << kMmKeyShift};
+    uint32_t k0[kMmBlocks], k1[kMmBlocks], capk[kMmBlocks];
+#pragma unroll
+    for (int c = 0; c < kMmBlocks; ++c) {
+        k0[c] = k1[c] = kMmKeyNone;
+        // relevant keys of this lane's queries: distance = (key >> 12) - 257 + |q| < cap_dist.  The cap key as a float pattern;
+        // a negative bound has the sign bit set, above every key: every key is relevant (exact, merely slow)
+        capk[c] = __float_as_uint((float)((cap_dist + kMmKeyBias - qn[c]) * (1 << kMmKeyShift)));
+    }
     stage(0, 0);
     __syncthreads();
     for (int t = 0; t < n_tiles; ++t) {
         const int buf = t & 1;
         if (t + 1 < n_tiles)
             stage(t + 1, buf ^ 1);
-        // The accumulators START as the rows' key bases and the products are -(2 << 12) per common bit, so the tile product
-        // leaves the finished keys: key = ((|t| + 256 - 2 dot) << 12 | index) -- no vector instruction per element beyond the
-        // insertion itself (round 4: one v_mad_i32_i24 per element on top; 96 -> 64 vector instructions per tile pair).
         // accumulator: column = lane & 31 (this lane's query), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (the train):
-        // registers 4 g4 .. 4 g4 + 3 are rows 8 g4 + 4 half + (0 .. 3), whose key bases are 16 consecutive bytes.  Rows past
-        // the end have all-zero bits and the base 0xffffffff: the key stays kKeyNone, never selected.
-        v16i kb;
+        // registers 4 g4 .. 4 g4 + 3 are rows 8 g4 + 4 half + (0 .. 3), whose key bases are 16 consecutive bytes.
+        v16f kb;
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
-            const v4i kb4 = *reinterpret_cast<const v4i *>(&s_key[buf][8 * g4 + 4 * half]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                kb[4 * g4 + e] = kb4[e];
+            const float4 kb4 = *reinterpret_cast<const float4 *>(&s_key[buf][8 * g4 + 4 * half]);
+            kb[4 * g4] = kb4.x;
+            kb[4 * g4 + 1] = kb4.y;
+            kb[4 * g4 + 2] = kb4.z;
+            kb[4 * g4 + 3] = kb4.w;
         }
-        v16i acc0, acc1;
-        const unsigned char *arow = &s_tile[buf][col * kMmRowBytes + half * 16];   // A: row = lane & 31, k = 16 half + j
+        v16f acc[kMmBlocks];
+        const unsigned char *arow = &s_tile[buf][col * kMmRowBytes + half * 16];   // A: row = lane & 31, dword 2 s + half
 #pragma unroll
-        for (int s8 = 0; s8 < 8; ++s8) {
-            const v4i Af = *reinterpret_cast<const v4i *>(arow + s8 * 32);
-            // two independent accumulation chains; the first step of each reads the key bases as its C operand
-            acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(Af, Bf[0][s8], s8 == 0 ? kb : acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(Af, Bf[1][s8], s8 == 0 ? kb : acc1, 0, 0, 0);
+        for (int s = 0; s < 4; ++s) {
+            const v4i a4 = *reinterpret_cast<const v4i *>(arow + s * 32);
+            const v8i Af = __builtin_shufflevector(a4, a4, 0, 1, 2, 3, -1, -1, -1, -1);
+            // kMmBlocks independent accumulation chains; the first step of each reads the key bases as its C operand
+#pragma unroll
+            for (int c = 0; c < kMmBlocks; ++c)
+                acc[c] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(Af, Bf[c][s], s == 0 ? kb : acc[c], 4, 4, 0, kMmScaleTrain,
+                                                                         0, kMmScaleQuery);
         }
         if (!CAPPED) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                key_insert(k0[0], k1[0], (uint32_t)acc0[r]);
-                key_insert(k0[1], k1[1], (uint32_t)acc1[r]);
-            }
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int c = 0; c < kMmBlocks; ++c)
+                    key_insert_mm(k0[c], k1[c], __float_as_uint(acc[c][r]));
         } else {
-            auto lazy = [&](const v16i &acc, uint32_t &a0, uint32_t &a1, uint32_t cap) {
+            auto lazy = [&](const v16f &a, uint32_t &a0, uint32_t &a1, uint32_t cap) {
                 uint32_t g[4];
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4)
-                    g[q4] = min(umin3((uint32_t)acc[4 * q4], (uint32_t)acc[4 * q4 + 1], (uint32_t)acc[4 * q4 + 2]), (uint32_t)acc[4 * q4 + 3]);
+                    g[q4] = min(umin3(__float_as_uint(a[4 * q4]), __float_as_uint(a[4 * q4 + 1]), __float_as_uint(a[4 * q4 + 2])),
+                                __float_as_uint(a[4 * q4 + 3]));
                 const uint32_t tm = min(umin3(g[0], g[1], g[2]), g[3]);
                 if (__any(tm < cap)) {       // wave-uniform: some lane has a relevant key in this tile
 #pragma unroll
@@ -291,35 +331,37 @@ __global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(3, 8
                         if (__any(g[q4] < cap)) {
 #pragma unroll
                             for (int e = 0; e < 4; ++e)
-                                key_insert(a0, a1, (uint32_t)acc[4 * q4 + e]);
+                                key_insert_mm(a0, a1, __float_as_uint(a[4 * q4 + e]));
                         }
                 }
             };
-            lazy(acc0, k0[0], k1[0], capk[0]);
-            lazy(acc1, k0[1], k1[1], capk[1]);
+#pragma unroll
+            for (int c = 0; c < kMmBlocks; ++c)
+                lazy(acc[c], k0[c], k1[c], capk[c]);
         }
         __syncthreads();
     }
     // lanes l and l + 32 of a wavefront saw the same query over different rows: merge through LDS
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
+    for (int c = 0; c < kMmBlocks; ++c) {
         s_k0[c][tid] = k0[c];
         s_k1[c][tid] = k1[c];
     }
     __syncthreads();
     if (half == 0) {
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int q = q0 + w * kMmQpw + c * 32 + col;
+        for (int c = 0; c < kMmBlocks; ++c) {
+            const int q = q0 + w * 32 * kMmBlocks + c * 32 + col;
             if (q >= n2)
                 continue;
             uint32_t m0 = k0[c], m1 = k1[c];
-            key_insert(m0, m1, s_k0[c][tid + 32]);
-            key_insert(m0, m1, s_k1[c][tid + 32]);
-            // distance = (key >> 12) - 256 + |q|
-            const int D0 = m0 == kKeyNone ? 0x7fffffff : (int)(m0 >> kMmKeyShift) - 256 + qn[c];
-            const int D1 = m1 == kKeyNone ? 0x7fffffff : (int)(m1 >> kMmKeyShift) - 256 + qn[c];
-            const int I0 = m0 == kKeyNone ? -1 : (int)(m0 & ((1u << kMmKeyShift) - 1u));
+            key_insert_mm(m0, m1, s_k0[c][tid + 32]);
+            key_insert_mm(m0, m1, s_k1[c][tid + 32]);
+            // the integer keys (exact: below 2^22); distance = (key >> 12) - 257 + |q|
+            const uint32_t i0 = (uint32_t)__uint_as_float(m0), i1 = (uint32_t)__uint_as_float(m1);
+            const int D0 = m0 == kMmKeyNone ? 0x7fffffff : (int)(i0 >> kMmKeyShift) - kMmKeyBias + qn[c];
+            const int D1 = m1 == kMmKeyNone ? 0x7fffffff : (int)(i1 >> kMmKeyShift) - kMmKeyBias + qn[c];
+            const int I0 = m0 == kMmKeyNone ? -1 : (int)(i0 & ((1u << kMmKeyShift) - 1u));
             // Lowe ratio in double on float distances (visual-feature.cpp:67-68)
             const float f0 = (float)D0, f1 = (float)D1;
             const bool check1 = (double)f0 < ratio * (double)f1;
