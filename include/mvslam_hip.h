@@ -33,6 +33,8 @@ extern "C" {
  * and every other struct is unchanged from version 2 */
 /* 4 (round 5): two entry points added -- mvs_batch_device_state (read-only diagnostics view, below) and mvs_batch_run_points
  * (a batch of sfm_solve calls on caller-supplied point pairs); nothing else changed */
+/* still 4: mvs_ba_window, mvs_ba_refine_window and mvs_ba_refine_windows are additions (new symbols only); no existing entry
+ * point or struct changed */
 #define MVS_ABI_VERSION 4
 
 typedef enum mvs_status {
@@ -408,7 +410,8 @@ mvs_status mvs_pnp_refine(mvs_ctx *ctx, const double *world, const double *world
 /* ba_frame_pose_and_point (vision/ba.hpp:25-36, ba.cpp:26-156) for the configurations the reference builds -- one or two
  * frames: besides sfm_refine / pnp_refine that is VisualOdometer::track_refine (front-end/visual-odometer.cpp:618-800:
  * last frame anchored at ITS pose, new frame regularised, tracked points with priors, new points without, each frame
- * observing a subset of the points).  All pointers are host memory. */
+ * observing a subset of the points).  All pointers are host memory.  Windows of up to eight frames: mvs_ba_window and
+ * mvs_ba_refine_window / mvs_ba_refine_windows below. */
 typedef struct mvs_ba_problem {
     int32_t n_frames;               /* 1 or 2 */
     int32_t n_points;               /* 1 .. 4096 */
@@ -427,6 +430,39 @@ typedef struct mvs_ba_problem {
  * points_out n_points x 3, point_cov_out n_points x 9 (may be NULL).  Only the LM fields of params are used. */
 mvs_status mvs_ba_refine(mvs_ctx *ctx, const mvs_ba_problem *problem, const mvs_refine_params *params,
                          mvs_refine_result *frames_out, double *points_out, double *point_cov_out);
+/* ba_frame_pose_and_point for any frame set of 1 .. 8 frames (the reference takes sets and maps keyed by frame id and loops
+ * over whatever it is given, ba.cpp:26-156): a sliding window.  The fields are mvs_ba_problem's; the per-frame arrays are
+ * arrays of n_frames pointers, so the frame count is not part of the layout.  ba.cpp:43 demands two priors (the gauge must
+ * be fixed: e.g. an anchor on frame 0 and a scale-fixing prior on another frame or on points). */
+typedef struct mvs_ba_window {
+    int32_t n_frames;                 /* 1 .. 8 */
+    int32_t n_points;                 /* 1 .. 4096 */
+    const double *K;                  /* 9, affine */
+    const double *frame_pose;         /* n_frames x 12 */
+    const double *frame_prior_var;    /* n_frames x 6, an entry <= 0 = no prior on that coordinate */
+    const double *points;             /* n_points x 3 */
+    const double *point_prior_cov;    /* n_points x 9 or NULL; first entry <= 0 = no prior on that point */
+    const double *const *obs;         /* n_frames pointers: n_points x 2 image points */
+    const double *const *obs_cov;     /* NULL, or n_frames pointers: n_points x 4 covariances or NULL = identity */
+    const uint8_t *const *obs_valid;  /* NULL, or n_frames pointers: n_points flags or NULL = the frame sees every point */
+} mvs_ba_window;
+/* One window.  n_frames 1 or 2 is forwarded to mvs_ba_refine (the same bytes out); 3 .. 8 runs the window kernel (DESIGN.md
+ * section 4.7); more than 8 frames or 4096 points: MVS_ERR_CAPACITY; the other argument errors as mvs_ba_refine.  MVS_NO_MODEL
+ * (ok = 0 in every frame record) if the problem has no unique minimum to working precision: the reduced camera system or a
+ * point's 3 x 3 block is not positive definite -- no prior fixes the gauge, or a point is neither observed nor has a prior.
+ * frames_out[n_frames], points_out n_points x 3 (may be NULL), point_cov_out n_points x 9 (may be NULL). */
+mvs_status mvs_ba_refine_window(mvs_ctx *ctx, const mvs_ba_window *problem, const mvs_refine_params *params,
+                                mvs_refine_result *frames_out, double *points_out, double *point_cov_out);
+/* A batch of windows that may differ in frames and points: one upload, ONE launch (one workgroup per window), one
+ * synchronisation and one download for all its windows of three and more frames; its windows of one or two frames go through
+ * mvs_ba_refine one by one, so that every window returns the bytes the single call returns.  Output strides are the batch's
+ * largest frame and point counts (Fmax, Mmax): frames_out[n_problems x Fmax], points_out n_problems x Mmax x 3,
+ * point_cov_out n_problems x Mmax x 9 (either may be NULL); rows beyond a window's own counts are not written.  frames_out is
+ * zeroed once the frame counts have been checked, also when the call then returns an argument error.  An argument error in any
+ * window fails the call before anything runs.  MVS_NO_MODEL if at least one window has
+ * ok = 0 (frames_out[p * Fmax].ok tells which). */
+mvs_status mvs_ba_refine_windows(mvs_ctx *ctx, const mvs_ba_window *problems, int n_problems, const mvs_refine_params *params,
+                                 mvs_refine_result *frames_out, double *points_out, double *point_cov_out);
 /* Batched ImagePair::refine (front-end/image-pair.cpp:176-238) on a batch that has been run: every valid pair is refined
  * from its own results on the device.  Observations = the matched keypoints with the covariance
  * VisualFeature::get_point_estimates gives them (vision/visual-feature.cpp:192-207): stddev = (1 << kp.octave) * 0.5 px,

@@ -2,8 +2,9 @@
 // translation unit of the front end that talks to GTSAM.  The same cost (diagonal pose priors, point priors, one
 // projection factor per observation with the keypoint's covariance) is minimised by the library's batched
 // Schur-complement Levenberg-Marquardt kernel; marginal covariances from the linearised system at the
-// estimate, final_error = the optimiser's error, as :130-155.  Supported: what the reference builds -- ONE or TWO frames
-// (sfm-refine.cpp:20-139, pnp-refine.cpp:14-108, VisualOdometer::track_refine visual-odometer.cpp:618-800).
+// estimate, final_error = the optimiser's error, as :130-155.  Supported: frame sets of ONE to EIGHT frames -- what the
+// reference builds (sfm-refine.cpp:20-139, pnp-refine.cpp:14-108, VisualOdometer::track_refine visual-odometer.cpp:618-800:
+// one or two frames) and sliding windows on top of it (mvs_ba_refine_window).
 // With this file in place sfm-refine.cpp, pnp-refine.cpp and visual-odometer.cpp stay untouched and GTSAM leaves the
 // front end's link line.
 #include <vision/ba.hpp>
@@ -27,7 +28,7 @@ void ba_frame_pose_and_point(const CameraIntrinsics &ci, const std::unordered_se
                              std::unordered_map<Id::Type, TransformationEstimate> &frame_pose_estimate,
                              std::unordered_map<Id::Type, Point3Estimate> &point_estimate, ScalarType &final_error)
 {
-    assert(frame_id.size() > 0 && frame_id.size() <= 2);   // ba.cpp:39; more than two frames: the reference builds none
+    assert(frame_id.size() > 0 && frame_id.size() <= 8);   // ba.cpp:39; the window kernel's capacity
     assert(point_id.size() > 0);
     assert(frame_pose_guess.size() == frame_id.size() && point_guess.size() == point_id.size());
     assert(frame_pose_prior.size() + point_prior.size() >= 2);   // ba.cpp:43
@@ -39,8 +40,10 @@ void ba_frame_pose_and_point(const CameraIntrinsics &ci, const std::unordered_se
     for (int i = 0; i < m; ++i)
         pidx[pids[i]] = i;
     std::vector<double> pose(12 * (size_t)F), var(6 * (size_t)F, 0.0), pts(3 * (size_t)m), pcov(9 * (size_t)m, 0.0);
-    std::vector<double> obs[2], ocov[2];
-    std::vector<uint8_t> valid[2];
+    std::vector<std::vector<double>> obs(F), ocov(F);
+    std::vector<std::vector<uint8_t>> valid(F);
+    std::vector<const double *> obs_p(F), ocov_p(F);
+    std::vector<const uint8_t *> valid_p(F);
     for (int f = 0; f < F; ++f) {
         const Transformation &T = frame_pose_guess.at(fids[f]);
         hip::to_row_major(T.rotation().get_matrix(), &pose[12 * f]);
@@ -70,7 +73,7 @@ void ba_frame_pose_and_point(const CameraIntrinsics &ci, const std::unordered_se
     }
     double Kr[9];
     hip::to_row_major(ci, Kr);
-    mvs_ba_problem pb;
+    mvs_ba_window pb;
     std::memset(&pb, 0, sizeof(pb));
     pb.n_frames = F;
     pb.n_points = m;
@@ -80,15 +83,18 @@ void ba_frame_pose_and_point(const CameraIntrinsics &ci, const std::unordered_se
     pb.points = pts.data();
     pb.point_prior_cov = pcov.data();
     for (int f = 0; f < F; ++f) {
-        pb.obs[f] = obs[f].data();
-        pb.obs_cov[f] = ocov[f].data();
-        pb.obs_valid[f] = valid[f].data();
+        obs_p[f] = obs[f].data();
+        ocov_p[f] = ocov[f].data();
+        valid_p[f] = valid[f].data();
     }
+    pb.obs = obs_p.data();
+    pb.obs_cov = ocov_p.data();
+    pb.obs_valid = valid_p.data();
     mvs_refine_params prm;
     mvs_refine_params_default(&prm);
     std::vector<mvs_refine_result> res(F);
     std::vector<double> po(3 * (size_t)m), pc(9 * (size_t)m);
-    if (mvs_ba_refine(hip::context(), &pb, &prm, res.data(), po.data(), pc.data()) != MVS_OK)
+    if (mvs_ba_refine_window(hip::context(), &pb, &prm, res.data(), po.data(), pc.data()) != MVS_OK)
         throw std::runtime_error("ba_frame_pose_and_point: indeterminate system");   // GTSAM throws here as well
     frame_pose_estimate.clear();
     for (int f = 0; f < F; ++f) {

@@ -89,6 +89,15 @@ class BaProblem(C.Structure):
                 ("obs_valid", C.POINTER(C.c_uint8) * 2)]
 
 
+class BaWindow(C.Structure):
+    """mvs_ba_window: BaProblem's fields with the per-frame arrays as arrays of n_frames pointers"""
+    _fields_ = [("n_frames", C.c_int32), ("n_points", C.c_int32), ("K", C.POINTER(C.c_double)),
+                ("frame_pose", C.POINTER(C.c_double)), ("frame_prior_var", C.POINTER(C.c_double)),
+                ("points", C.POINTER(C.c_double)), ("point_prior_cov", C.POINTER(C.c_double)),
+                ("obs", C.POINTER(C.POINTER(C.c_double))), ("obs_cov", C.POINTER(C.POINTER(C.c_double))),
+                ("obs_valid", C.POINTER(C.POINTER(C.c_uint8)))]
+
+
 REFINE_DTYPE = np.dtype([("ok", "<i4"), ("iterations", "<i4"), ("error", "<f8"), ("R", "<f8", (3, 3)),
                          ("t", "<f8", (3,)), ("pose_cov", "<f8", (6, 6))])
 
@@ -133,6 +142,7 @@ EXPORTS = [
     "mvs_batch_upload_async", "mvs_batch_download_async", "mvs_host_alloc", "mvs_host_free", "mvs_image_pair",
     "mvs_batch_gather_results", "mvs_seq_time_stages", "mvs_batch_time_kernels", "mvs_kernel_info_get",
     "mvs_extract_time", "mvs_ctx_set_half_batches", "mvs_batch_device_state", "mvs_batch_run_points",
+    "mvs_ba_refine_window", "mvs_ba_refine_windows",
 ]
 
 
@@ -527,6 +537,87 @@ class Context:
         self._check(st, "mvs_ba_refine", allow_no_model=True)
         return dict(ok=st == MVS_OK, R=res["R"].copy(), t=res["t"].copy(), pose_cov=res["pose_cov"].copy(), points=pts,
                     point_cov=ptc, error=float(res["error"][0]), iterations=int(res["iterations"][0]))
+
+    @staticmethod
+    def _ba_window(pb, keep):
+        """mvs_ba_window of one problem dict (K, frame_pose, frame_prior_var, points, point_prior_cov, obs, obs_cov, obs_valid;
+        the last three are lists over the frames, obs_cov / obs_valid may be None or hold None); the arrays it points to
+        are appended to `keep`"""
+        fp, fv = _f64(pb["frame_pose"]).reshape(-1, 12), _f64(pb["frame_prior_var"]).reshape(-1, 6)
+        pg = _f64(pb["points"]).reshape(-1, 3)
+        F, m = len(fp), len(pg)
+        K = _f64(pb["K"], (9,))
+        keep += [fp, fv, pg, K]
+        w = BaWindow()
+        w.n_frames, w.n_points = F, m
+        w.K, w.frame_pose, w.frame_prior_var, w.points = (_ptr(K, C.c_double), _ptr(fp, C.c_double), _ptr(fv, C.c_double),
+                                                          _ptr(pg, C.c_double))
+        if pb.get("point_prior_cov") is not None:
+            keep.append(_f64(pb["point_prior_cov"], (m, 9)))
+            w.point_prior_cov = _ptr(keep[-1], C.c_double)
+        obs = (C.POINTER(C.c_double) * F)()
+        for f in range(F):
+            keep.append(_f64(pb["obs"][f], (m, 2)))
+            obs[f] = _ptr(keep[-1], C.c_double)
+        keep.append(obs)
+        w.obs = C.cast(obs, C.POINTER(C.POINTER(C.c_double)))
+        if pb.get("obs_cov") is not None:
+            cov = (C.POINTER(C.c_double) * F)()
+            for f in range(F):
+                if pb["obs_cov"][f] is not None:
+                    keep.append(_f64(pb["obs_cov"][f], (m, 4)))
+                    cov[f] = _ptr(keep[-1], C.c_double)
+            keep.append(cov)
+            w.obs_cov = C.cast(cov, C.POINTER(C.POINTER(C.c_double)))
+        if pb.get("obs_valid") is not None:
+            val = (C.POINTER(C.c_uint8) * F)()
+            for f in range(F):
+                if pb["obs_valid"][f] is not None:
+                    keep.append(np.ascontiguousarray(pb["obs_valid"][f], dtype=np.uint8).reshape(m))
+                    val[f] = _ptr(keep[-1], C.c_uint8)
+            keep.append(val)
+            w.obs_valid = C.cast(val, C.POINTER(C.POINTER(C.c_uint8)))
+        return w
+
+    # ba_frame_pose_and_point on windows of 1 .. 8 frames, a batch of them in one launch
+    def ba_refine_windows(self, problems, params=None, point_cov=True):
+        """problems: list of dicts (see _ba_window).  Returns one result dict per window (the layout of ba_refine's);
+        `status` in each is the window's own (MVS_OK, or MVS_NO_MODEL where ok = 0)."""
+        params = params or default_refine_params()
+        keep = []
+        n = len(problems)
+        arr = (BaWindow * n)(*[self._ba_window(pb, keep) for pb in problems])
+        Fmax = max([w.n_frames for w in arr] + [1])
+        Mmax = max([w.n_points for w in arr] + [1])
+        res = np.zeros((n, Fmax), dtype=REFINE_DTYPE)
+        pts = np.zeros((n, Mmax, 3))
+        ptc = np.zeros((n, Mmax, 3, 3)) if point_cov else None
+        st = lib().mvs_ba_refine_windows(self._h, arr, C.c_int(n), C.byref(params), res.ctypes.data_as(C.c_void_p),
+                                         _ptr(pts, C.c_double), _ptr(ptc, C.c_double))
+        self._check(st, "mvs_ba_refine_windows", allow_no_model=True)
+        out = []
+        for p, w in enumerate(arr):
+            F, m = w.n_frames, w.n_points
+            r = res[p, :F]
+            out.append(dict(ok=bool(r["ok"][0]), status=MVS_OK if r["ok"][0] else MVS_NO_MODEL, R=r["R"].copy(), t=r["t"].copy(), pose_cov=r["pose_cov"].copy(),
+                            points=pts[p, :m].copy(), point_cov=None if ptc is None else ptc[p, :m].copy(),
+                            error=float(r["error"][0]), iterations=int(r["iterations"][0]), raw=r.tobytes()))
+        return out
+
+    def ba_refine_window(self, K, frame_pose, frame_prior_var, points, point_prior_cov, obs, obs_cov, obs_valid, params=None):
+        """one window through mvs_ba_refine_window; arguments and result as ba_refine"""
+        params = params or default_refine_params()
+        keep = []
+        w = self._ba_window(dict(K=K, frame_pose=frame_pose, frame_prior_var=frame_prior_var, points=points,
+                                 point_prior_cov=point_prior_cov, obs=obs, obs_cov=obs_cov, obs_valid=obs_valid), keep)
+        F, m = w.n_frames, w.n_points
+        res = np.zeros(max(F, 1), dtype=REFINE_DTYPE)
+        pts, ptc = np.zeros((max(m, 1), 3)), np.zeros((max(m, 1), 3, 3))
+        st = lib().mvs_ba_refine_window(self._h, C.byref(w), C.byref(params), res.ctypes.data_as(C.c_void_p),
+                                        _ptr(pts, C.c_double), _ptr(ptc, C.c_double))
+        self._check(st, "mvs_ba_refine_window", allow_no_model=True)
+        return dict(ok=st == MVS_OK, R=res["R"].copy(), t=res["t"].copy(), pose_cov=res["pose_cov"].copy(), points=pts[:m],
+                    point_cov=ptc[:m], error=float(res["error"][0]), iterations=int(res["iterations"][0]), raw=res[:F].tobytes())
 
     def find_fundamental_matrix(self, p1, p2):
         p1, p2 = _f64(p1, (16,)), _f64(p2, (16,))

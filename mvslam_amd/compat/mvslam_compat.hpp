@@ -732,8 +732,8 @@ public:
 };
 using PointIdToPoint2Estimate = std::unordered_map<Id::Type, Point2Estimate>;
 
-// Same signature as the reference.  Supported: the configurations the reference builds -- one or two frames
-// (sfm_refine, pnp_refine, VisualOdometer::track_refine); diagonal frame priors.  With this one function forwarded,
+// Same signature as the reference.  Supported: one to eight frames (the reference itself builds one or two: sfm_refine,
+// pnp_refine, VisualOdometer::track_refine; more is a sliding window, mvs_ba_refine_window); diagonal frame priors.  With this one function forwarded,
 // sfm-refine.cpp, pnp-refine.cpp and visual-odometer.cpp stay untouched and GTSAM leaves the link line.
 inline void ba_frame_pose_and_point(const CameraIntrinsics &ci, const std::unordered_set<Id::Type> &frame_id,
                                     const std::unordered_set<Id::Type> &point_id,
@@ -745,7 +745,7 @@ inline void ba_frame_pose_and_point(const CameraIntrinsics &ci, const std::unord
                                     std::unordered_map<Id::Type, TransformationEstimate> &frame_pose_estimate,
                                     std::unordered_map<Id::Type, Point3Estimate> &point_estimate, ScalarType &final_error)
 {
-    assert(frame_id.size() > 0 && frame_id.size() <= 2);   // ba.cpp:39; more than two frames: not built
+    assert(frame_id.size() > 0 && frame_id.size() <= 8);   // ba.cpp:39; the window kernel's capacity
     assert(point_id.size() > 0);
     assert(frame_pose_guess.size() == frame_id.size() && point_guess.size() == point_id.size());
     assert(frame_pose_prior.size() + point_prior.size() >= 2);   // ba.cpp:43
@@ -757,8 +757,10 @@ inline void ba_frame_pose_and_point(const CameraIntrinsics &ci, const std::unord
     for (int i = 0; i < m; ++i)
         pidx[pids[i]] = i;
     std::vector<double> pose(12 * (size_t)F), var(6 * (size_t)F, 0.0), pts(3 * (size_t)m), pcov(9 * (size_t)m, 0.0);
-    std::vector<double> obs[2], ocov[2];
-    std::vector<uint8_t> valid[2];
+    std::vector<std::vector<double>> obs(F), ocov(F);
+    std::vector<std::vector<uint8_t>> valid(F);
+    std::vector<const double *> obs_p(F), ocov_p(F);
+    std::vector<const uint8_t *> valid_p(F);
     for (int f = 0; f < F; ++f) {
         const Transformation &T = frame_pose_guess.at(fids[f]);
         std::memcpy(&pose[12 * f], T.rotation().get_matrix().m, 9 * sizeof(double));
@@ -785,7 +787,7 @@ inline void ba_frame_pose_and_point(const CameraIntrinsics &ci, const std::unord
         if (pr != point_prior.end())
             std::memcpy(&pcov[9 * i], pr->second.m, 9 * sizeof(double));
     }
-    mvs_ba_problem pb;
+    mvs_ba_window pb;
     std::memset(&pb, 0, sizeof(pb));
     pb.n_frames = F;
     pb.n_points = m;
@@ -795,13 +797,16 @@ inline void ba_frame_pose_and_point(const CameraIntrinsics &ci, const std::unord
     pb.points = pts.data();
     pb.point_prior_cov = pcov.data();
     for (int f = 0; f < F; ++f) {
-        pb.obs[f] = obs[f].data();
-        pb.obs_cov[f] = ocov[f].data();
-        pb.obs_valid[f] = valid[f].data();
+        obs_p[f] = obs[f].data();
+        ocov_p[f] = ocov[f].data();
+        valid_p[f] = valid[f].data();
     }
+    pb.obs = obs_p.data();
+    pb.obs_cov = ocov_p.data();
+    pb.obs_valid = valid_p.data();
     std::vector<mvs_refine_result> res(F);
     std::vector<double> po(3 * (size_t)m), pc(9 * (size_t)m);
-    const mvs_status st = mvs_ba_refine(hip::context(), &pb, &hip::refine_config(), res.data(), po.data(), pc.data());
+    const mvs_status st = mvs_ba_refine_window(hip::context(), &pb, &hip::refine_config(), res.data(), po.data(), pc.data());
     hip::check(st, "ba_frame_pose_and_point");
     if (st != MVS_OK)
         throw std::runtime_error("ba_frame_pose_and_point: indeterminate system");   // GTSAM throws here as well

@@ -52,6 +52,7 @@ struct mvs_ctx {
     DevWorkspace single_in;   // packed inputs of mvs_image_pair (one host-to-device copy)
     DevWorkspace pnp;         // pnp_solve workspace
     DevWorkspace ref;         // sfm_refine / pnp_refine workspace
+    DevWorkspace win;         // mvs_ba_refine_windows workspace
     DevWorkspace orb;         // extraction workspace: orb_graph points into it
     int32_t *h_orb_ovf = nullptr;   // pinned: the extraction's overflow flag travels with the outputs (one stream wait per call)
     bool orb_ready = false;
@@ -2725,6 +2726,193 @@ mvs_status mvs_ba_refine(mvs_ctx *ctx, const mvs_ba_problem *pb, const mvs_refin
     const double *pose_last = pb->frame_pose + 12 * (pb->n_frames - 1);
     return refine_single(ctx, pb->n_frames, pb->obs[0], pb->obs_cov[0], pb->obs[1], pb->obs_cov[1], pb->points, pc,
                          pb->n_points, pb->K, pose_last, pose_last + 9, params, &last, points_out, point_cov_out, ex);
+}
+
+// ---- windows of up to eight frames --------------------------------------------------------------------------------------
+// argument errors of one window, in mvs_ba_refine's order (the frame count has been checked by the caller)
+static mvs_status window_check(const mvs_ba_window *w)
+{
+    if (!w->K || !w->frame_pose || !w->frame_prior_var || !w->points || !w->obs)
+        return MVS_ERR_INVALID_ARG;
+    for (int f = 0; f < w->n_frames; ++f)
+        if (!w->obs[f])
+            return MVS_ERR_INVALID_ARG;
+    if (w->n_points < 1)
+        return MVS_ERR_INVALID_ARG;
+    if (w->n_points > kMaxKp)
+        return MVS_ERR_CAPACITY;
+    if (!affine_K(w->K))
+        return MVS_ERR_BAD_INTRINSICS;
+    return MVS_OK;
+}
+
+// the inputs of one window in the layout refine_window_kernel reads (WinProblem::in_off); covariances become information
+// matrices here, with refine_prep_kernel's formulas
+static void window_pack(const mvs_ba_window *w, std::vector<double> &in)
+{
+    const size_t F = (size_t)w->n_frames, m = (size_t)w->n_points;
+    const size_t o_cam = in.size();
+    in.resize(o_cam + 8 + 18 * F + 9 * m + 5 * F * m, 0.0);
+    double *cam = in.data() + o_cam, *pose = cam + 8, *wt = pose + 12 * F, *p0 = wt + 6 * F, *pinfo = p0 + 3 * m;
+    double *obs = pinfo + 6 * m, *oinfo = obs + 2 * F * m;
+    cam[0] = w->K[0], cam[1] = w->K[1], cam[2] = w->K[2], cam[3] = w->K[4], cam[4] = w->K[5];
+    std::memcpy(pose, w->frame_pose, 12 * F * sizeof(double));
+    for (size_t k = 0; k < 6 * F; ++k)
+        wt[k] = w->frame_prior_var[k] > 0.0 ? 1.0 / w->frame_prior_var[k] : 0.0;   // <= 0: no prior on this coordinate
+    std::memcpy(p0, w->points, 3 * m * sizeof(double));
+    for (size_t i = 0; i < m && w->point_prior_cov; ++i) {
+        const double *C = w->point_prior_cov + 9 * i;
+        if (!(C[0] > 0.0))
+            continue;   // no prior on this point
+        const double a[6] = {C[0], 0.5 * (C[1] + C[3]), 0.5 * (C[2] + C[6]), C[4], 0.5 * (C[5] + C[7]), C[8]};
+        const double c00 = a[3] * a[5] - a[4] * a[4], c01 = a[2] * a[4] - a[1] * a[5], c02 = a[1] * a[4] - a[2] * a[3];
+        const double id = 1.0 / ((a[0] * c00 + a[1] * c01) + a[2] * c02);
+        double *L = pinfo + 6 * i;
+        L[0] = c00 * id, L[1] = c01 * id, L[2] = c02 * id;
+        L[3] = (a[0] * a[5] - a[2] * a[2]) * id, L[4] = (a[1] * a[2] - a[0] * a[4]) * id, L[5] = (a[0] * a[3] - a[1] * a[1]) * id;
+    }
+    for (size_t f = 0; f < F; ++f) {
+        std::memcpy(obs + 2 * m * f, w->obs[f], 2 * m * sizeof(double));
+        const double *cv = w->obs_cov ? w->obs_cov[f] : nullptr;
+        const uint8_t *vd = w->obs_valid ? w->obs_valid[f] : nullptr;
+        double *o = oinfo + 3 * m * f;
+        for (size_t i = 0; i < m; ++i, o += 3) {
+            if (vd && !vd[i])
+                continue;   // not seen: zero information
+            if (!cv) {
+                o[0] = 1.0, o[2] = 1.0;
+            } else {
+                const double a = cv[4 * i], b = 0.5 * (cv[4 * i + 1] + cv[4 * i + 2]), dd = cv[4 * i + 3];
+                const double id = 1.0 / (a * dd - b * b);
+                o[0] = dd * id, o[1] = -(b * id), o[2] = a * id;
+            }
+        }
+    }
+}
+
+mvs_status mvs_ba_refine_windows(mvs_ctx *ctx, const mvs_ba_window *problems, int n_problems, const mvs_refine_params *params,
+                                 mvs_refine_result *frames_out, double *points_out, double *point_cov_out)
+{
+    if (!ctx || !problems || n_problems < 1 || !frames_out || !refine_params_ok(params))
+        return MVS_ERR_INVALID_ARG;
+    int Fmax = 0, Mmax = 0;
+    for (int p = 0; p < n_problems; ++p) {
+        if (problems[p].n_frames < 1)
+            return MVS_ERR_INVALID_ARG;
+        if (problems[p].n_frames > kWinMaxFrames)
+            return MVS_ERR_CAPACITY;
+        Fmax = std::max(Fmax, problems[p].n_frames);
+    }
+    std::memset(frames_out, 0, (size_t)n_problems * Fmax * sizeof(mvs_refine_result));
+    for (int p = 0; p < n_problems; ++p) {
+        const mvs_status st = window_check(&problems[p]);
+        if (st != MVS_OK)
+            return st;
+        Mmax = std::max(Mmax, problems[p].n_points);
+    }
+    bool all_ok = true;
+    // the batch's windows of three and more frames: one upload, one launch, one download
+    std::vector<WinProblem> desc;
+    std::vector<int> which;
+    std::vector<double> in;
+    size_t n_pts = 0, n_fr = 0;
+    for (int p = 0; p < n_problems; ++p) {
+        const mvs_ba_window &w = problems[p];
+        if (w.n_frames <= 2)
+            continue;
+        WinProblem d{};
+        d.n_frames = w.n_frames;
+        d.n_points = w.n_points;
+        d.in_off = (int64_t)in.size();
+        d.pt_off = (int64_t)n_pts;
+        d.fr_off = (int64_t)n_fr;
+        window_pack(&w, in);
+        n_pts += (size_t)w.n_points;
+        n_fr += (size_t)w.n_frames;
+        desc.push_back(d);
+        which.push_back(p);
+    }
+    if (!desc.empty()) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t G = desc.size(), head = (G * sizeof(WinProblem) + 63) & ~size_t(63);
+        // outputs first and contiguous (frames, points, covariances: the download is their prefix), then the candidate
+        // points and the uploaded block (descriptors, then inputs)
+        Carve L{64};
+        const size_t off_out = L.take(n_fr * sizeof(mvs_refine_result));
+        const size_t off_pts = L.take(n_pts * 3 * sizeof(double));
+        const size_t off_cov = L.take(n_pts * 9 * sizeof(double));
+        const size_t off_tmp = L.take(n_pts * 3 * sizeof(double));
+        const size_t off_up = L.take(head + in.size() * sizeof(double));
+        const mvs_status st = ws_grow(ctx, ctx->win, L.total());
+        if (st != MVS_OK)
+            return st;
+        char *base = ctx->win.ptr();
+        std::vector<char> up(head + in.size() * sizeof(double));
+        std::memcpy(up.data(), desc.data(), G * sizeof(WinProblem));
+        std::memcpy(up.data() + head, in.data(), in.size() * sizeof(double));
+        hipStream_t s = ctx->stream;
+        HIP_TRY(ctx, hipMemcpyAsync(base + off_up, up.data(), up.size(), hipMemcpyHostToDevice, s));
+        WinDev d{};
+        d.n_problems = (int)G;
+        d.cfg = to_cfg(*params, 1);
+        d.prob = reinterpret_cast<const WinProblem *>(base + off_up);
+        d.in = reinterpret_cast<const double *>(base + off_up + head);
+        d.pts = reinterpret_cast<double *>(base + off_pts);
+        d.pts_tmp = reinterpret_cast<double *>(base + off_tmp);
+        d.point_cov = point_cov_out ? reinterpret_cast<double *>(base + off_cov) : nullptr;
+        d.out = reinterpret_cast<mvs_refine_result *>(base + off_out);
+        launch_refine_window(d, s);
+        HIP_TRY(ctx, hipGetLastError());
+        const size_t down = point_cov_out ? off_cov + n_pts * 9 * sizeof(double) : points_out ? off_cov : off_pts;
+        std::vector<char> host(down);
+        HIP_TRY(ctx, hipMemcpyAsync(host.data(), base, down, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, sync_stream(ctx));
+        for (size_t g = 0; g < G; ++g) {
+            const int p = which[g];
+            const size_t F = (size_t)desc[g].n_frames, m = (size_t)desc[g].n_points;
+            mvs_refine_result *fo = frames_out + (size_t)p * Fmax;
+            std::memcpy(fo, host.data() + off_out + (size_t)desc[g].fr_off * sizeof(mvs_refine_result), F * sizeof(mvs_refine_result));
+            all_ok = all_ok && fo[0].ok;
+            if (points_out)
+                std::memcpy(points_out + (size_t)p * Mmax * 3, host.data() + off_pts + (size_t)desc[g].pt_off * 3 * sizeof(double),
+                            m * 3 * sizeof(double));
+            if (point_cov_out)
+                std::memcpy(point_cov_out + (size_t)p * Mmax * 9, host.data() + off_cov + (size_t)desc[g].pt_off * 9 * sizeof(double),
+                            m * 9 * sizeof(double));
+        }
+    }
+    // windows of one or two frames go through mvs_ba_refine, one call each: the bytes mvs_ba_refine returns
+    for (int p = 0; p < n_problems; ++p) {
+        const mvs_ba_window &w = problems[p];
+        if (w.n_frames > 2)
+            continue;
+        mvs_ba_problem pb{};
+        pb.n_frames = w.n_frames;
+        pb.n_points = w.n_points;
+        pb.K = w.K;
+        pb.frame_pose = w.frame_pose;
+        pb.frame_prior_var = w.frame_prior_var;
+        pb.points = w.points;
+        pb.point_prior_cov = w.point_prior_cov;
+        for (int f = 0; f < w.n_frames; ++f) {
+            pb.obs[f] = w.obs[f];
+            pb.obs_cov[f] = w.obs_cov ? w.obs_cov[f] : nullptr;
+            pb.obs_valid[f] = w.obs_valid ? w.obs_valid[f] : nullptr;
+        }
+        const mvs_status st = mvs_ba_refine(ctx, &pb, params, frames_out + (size_t)p * Fmax,
+                                            points_out ? points_out + (size_t)p * Mmax * 3 : nullptr,
+                                            point_cov_out ? point_cov_out + (size_t)p * Mmax * 9 : nullptr);
+        if (st != MVS_OK && st != MVS_NO_MODEL)
+            return st;
+        all_ok = all_ok && st == MVS_OK;
+    }
+    return all_ok ? MVS_OK : MVS_NO_MODEL;
+}
+
+mvs_status mvs_ba_refine_window(mvs_ctx *ctx, const mvs_ba_window *problem, const mvs_refine_params *params,
+                                mvs_refine_result *frames_out, double *points_out, double *point_cov_out)
+{
+    return mvs_ba_refine_windows(ctx, problem, 1, params, frames_out, points_out, point_cov_out);
 }
 
 mvs_status mvs_batch_refine(mvs_batch *b, const mvs_refine_params *params, double sigma_px)

@@ -238,6 +238,30 @@ void launch_refine_gather(const BatchDev &b, int n_active, double sigma_px, doub
                           double *pose0, double *obs0, double *obs1, double *oinfo0, double *oinfo1, double *pts0,
                           double *pinfo, hipStream_t stream);
 
+// ---- ba_frame_pose_and_point on windows of 3 .. 8 frames (refine_window_kernel) ---------------------------------
+constexpr int kWinMaxFrames = 8;
+struct WinProblem {      // one window of a batch; windows differ in frames and points, so every array is ragged
+    int32_t n_frames;    // F
+    int32_t n_points;    // m
+    int64_t in_off;      // first double of the window's inputs in WinDev::in: camera fx sk cx fy cy (5, padded to 8), poses
+                         // F x 12 (guess = prior mean), pose prior weights F x 6, point guesses m x 3, point prior information
+                         // m x 6 (xx xy xz yy yz zz), observations F x m x 2, their information F x m x 3 (0 0 0 = not seen)
+    int64_t pt_off;      // first point of the window in pts / pts_tmp / point_cov
+    int64_t fr_off;      // first frame of the window in out
+};
+static_assert(sizeof(WinProblem) == 32, "WinProblem layout");
+struct WinDev {
+    int n_problems;
+    RefineCfg cfg;       // the Levenberg-Marquardt fields; the prior weights travel with each window
+    const WinProblem *prob;
+    const double *in;
+    double *pts;         // [sum m][3] refined points (out)
+    double *pts_tmp;     // [sum m][3] candidate buffer
+    double *point_cov;   // [sum m][9] marginal covariances (out), may be null
+    mvs_refine_result *out;   // [sum F]
+};
+void launch_refine_window(const WinDev &d, hipStream_t stream);
+
 // ---- VisualFeature::extract (row f3): ORB-style extraction for a batch of equally sized images ----------------
 constexpr int kOrbMaxLevels = 16;
 constexpr int kOrbSelCap = 16384;    // keys of one (image, level) the selection can hold in LDS (128 KB): 2 n_l <= this, or the

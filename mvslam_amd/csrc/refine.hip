@@ -908,6 +908,632 @@ __global__ __launch_bounds__(kRefineThreads) void refine_kernel(RefineDev d)
     }
 }
 
+// ---- windows of 3 .. 8 frames (mvs_ba_refine_window / mvs_ba_refine_windows) ----------------------
+// One workgroup per window, F a run-time argument: the reduced camera system has order 6F <= 48, far too many entries for
+// per-thread accumulators, so the work is laid out the other way round from refine_kernel.
+//   Linearisation: thread = (point slot il = tid / 8 of the current chunk of 32 points, frame f = tid % 8).  The eight
+//   lanes of a point are neighbours in one wavefront: V = Hpp (+ prior, + lambda) and g_p are summed over the frames with
+//   three DPP steps ((f0 + f1) + (f2 + f3)) + ((f4 + f5) + (f6 + f7)), every lane factors V = L L^T (3 x 3 Cholesky) and
+//   writes Z_f = Hcp_f L^-T (6 x 3) to LDS; lane 0 adds the row L^-1 g_p.  Nothing else per point is kept.
+//   Schur complement: thread = up to five ENTRIES (a, c) of {S packed lower, b}; it walks the chunk's points in index order
+//   and subtracts Z[a] . Z[c] (adds Z[a] . L^-1 g_p for b).  Every entry is therefore one sequential sum over the points
+//   0 .. m - 1: no tree, no atomics, the same bits on every run.
+//   The frames' own blocks Hcc_f / g_f are accumulated by the (il, f) threads in registers, in a pass of their own, and
+//   summed over il at its end: xor 8, 16, 32 inside the wavefront, then (w0 + w1) + (w2 + w3) through LDS.
+//   S is factored in LDS by the whole workgroup (right-looking Cholesky, the trailing update spread over the entry owners);
+//   the triangular solves run in one wavefront, lane k holding component k (readlane, no barrier).
+// A pivot must exceed kWinPivotTol times the entry's value before elimination (the accumulated rounding error of the
+// eliminations is of that size): a gauge that no prior fixes, or a point that nothing determines, leaves pivots that are
+// rounding noise of either sign, and they are reported as "not positive definite" whichever sign they have.
+constexpr int kWinThreads = 256;
+constexpr int kWinChunk = kWinThreads / kWinMaxFrames;   // 32 points per chunk
+constexpr int kWinNC = 6 * kWinMaxFrames;                // 48
+constexpr int kWinNL = kWinNC * (kWinNC + 1) / 2;        // 1176
+constexpr int kWinRows = kWinNC + 1;                     // Z rows of one point: the camera rows, then L^-1 g_p
+constexpr int kWinEnt = (kWinNL + kWinNC + kWinThreads - 1) / kWinThreads;   // entries per thread: 5
+constexpr double kWinPivotTol = 1.0 / (double)(1ll << 42);   // 2.3e-13 ~ 16 x 48 x 2^-52
+
+// sum over the eight lanes tid / 8 shares (the frames of one point), the same value in each of them
+__device__ __forceinline__ double oct_sum(double x)
+{
+    x = x + dpp_f64<0xb1>(x);    // quad_perm [1, 0, 3, 2]
+    x = x + dpp_f64<0x4e>(x);    // quad_perm [2, 3, 0, 1]
+    x = x + dpp_f64<0x141>(x);   // row_half_mirror: quads are uniform, lane 7 - i holds the other quad's sum
+    return x;
+}
+
+__device__ __forceinline__ double obs_cost(const Cam &cam, const double (&R)[9], const double (&t)[3], const double (&p)[3],
+                                           double u, double v, double W0, double W1, double W2)
+{
+    double r[2], Jc[12], Jp[6];
+    project_lin<false>(cam, R, t, p, u, v, r, Jc, Jp);
+    const double wr0 = fd2(W0, r[0], W1, r[1]), wr1 = fd2(W1, r[0], W2, r[1]);
+    return fma(r[1], wr1, r[0] * wr0);
+}
+
+__device__ __forceinline__ double point_prior_cost(const double (&L)[6], const double (&p0)[3], const double (&p)[3])
+{
+    const double d0 = p[0] - p0[0], d1 = p[1] - p0[1], d2 = p[2] - p0[2];
+    return fd3(d0, fd3(L[0], d0, L[1], d1, L[2], d2), d1, fd3(L[1], d0, L[3], d1, L[4], d2), d2,
+               fd3(L[2], d0, L[4], d1, L[5], d2));
+}
+
+// One (point, frame) lane: linearise the observation (on = the frame sees the point), sum the point's blocks over the
+// frame lanes, factor V + lam I = L L^T.  Z = Hcp_f L^-T, Li = L^-1 (l00 l10 l11 l20 l21 l22), gh = L^-1 g_p.
+// Returns false (and Z = Li = gh = 0) if V is not positive definite.
+__device__ __forceinline__ bool win_linearize(const Cam &cam, bool on, const double (&R)[9], const double (&t)[3],
+                                              const double (&p)[3], const double (&p0)[3], const double (&L)[6], double u,
+                                              double v, double W0, double W1, double W2, double lam, double (&Z)[6][3],
+                                              double (&Li)[6], double (&gh)[3])
+{
+    double Hcp[6][3], Hpp[6], gp[3];
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            Hcp[a][k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+        Hpp[k] = 0.0;
+    gp[0] = gp[1] = gp[2] = 0.0;
+    if (on) {
+        double r[2], Jc[12], Jp[6];
+        project_lin<true>(cam, R, t, p, u, v, r, Jc, Jp);
+        const double wr0 = fd2(W0, r[0], W1, r[1]), wr1 = fd2(W1, r[0], W2, r[1]);
+        double WJp[6];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            WJp[k] = fd2(W0, Jp[k], W1, Jp[3 + k]);
+            WJp[3 + k] = fd2(W1, Jp[k], W2, Jp[3 + k]);
+        }
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                Hcp[a][k] = fd2(Jc[a], WJp[k], Jc[6 + a], WJp[3 + k]);
+        Hpp[0] = fd2(Jp[0], WJp[0], Jp[3], WJp[3]);
+        Hpp[1] = fd2(Jp[0], WJp[1], Jp[3], WJp[4]);
+        Hpp[2] = fd2(Jp[0], WJp[2], Jp[3], WJp[5]);
+        Hpp[3] = fd2(Jp[1], WJp[1], Jp[4], WJp[4]);
+        Hpp[4] = fd2(Jp[1], WJp[2], Jp[4], WJp[5]);
+        Hpp[5] = fd2(Jp[2], WJp[2], Jp[5], WJp[5]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            gp[k] = fd2(Jp[k], wr0, Jp[3 + k], wr1);
+    }
+    // the point's own blocks: prior + the frames in the fixed tree of oct_sum
+    const double d0 = p[0] - p0[0], d1 = p[1] - p0[1], d2 = p[2] - p0[2];
+    double V[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+        V[k] = L[k] + oct_sum(Hpp[k]);
+    const double g0 = fd3(L[0], d0, L[1], d1, L[2], d2) + oct_sum(gp[0]);
+    const double g1 = fd3(L[1], d0, L[3], d1, L[4], d2) + oct_sum(gp[1]);
+    const double g2 = fd3(L[2], d0, L[4], d1, L[5], d2) + oct_sum(gp[2]);
+    const double v0 = V[0] + lam, v3 = V[3] + lam, v5 = V[5] + lam;
+    // V = L L^T, then L^-1
+    const double inf = __builtin_inf();
+    bool ok = v0 > 0.0 && v0 < inf;
+    const double i0 = 1.0 / sqrt(v0);
+    const double l10 = V[1] * i0, l20 = V[2] * i0;
+    const double e1 = fma(-l10, l10, v3);
+    ok = ok && e1 > kWinPivotTol * v3 && e1 < inf;
+    const double i1 = 1.0 / sqrt(e1);
+    const double l21 = fma(-l20, l10, V[4]) * i1;
+    const double e2 = fma(-l21, l21, fma(-l20, l20, v5));
+    ok = ok && e2 > kWinPivotTol * v5 && e2 < inf;
+    const double i2 = 1.0 / sqrt(e2);
+    const double m10 = -(l10 * i0) * i1, m21 = -(l21 * i1) * i2, m20 = -fd2(l20, i0, l21, m10) * i2;
+    Li[0] = ok ? i0 : 0.0;
+    Li[1] = ok ? m10 : 0.0;
+    Li[2] = ok ? i1 : 0.0;
+    Li[3] = ok ? m20 : 0.0;
+    Li[4] = ok ? m21 : 0.0;
+    Li[5] = ok ? i2 : 0.0;
+    gh[0] = Li[0] * g0;
+    gh[1] = fd2(Li[1], g0, Li[2], g1);
+    gh[2] = fd3(Li[3], g0, Li[4], g1, Li[5], g2);
+    if (!ok)
+        gh[0] = gh[1] = gh[2] = 0.0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        Z[a][0] = Hcp[a][0] * Li[0];
+        Z[a][1] = fd2(Hcp[a][0], Li[1], Hcp[a][1], Li[2]);
+        Z[a][2] = fd3(Hcp[a][0], Li[3], Hcp[a][1], Li[4], Hcp[a][2], Li[5]);
+    }
+    return ok;
+}
+
+// the frame's own blocks of one observation: U += Jc^T W Jc (packed lower 6 x 6), g += Jc^T W r
+__device__ __forceinline__ void win_frame_block(const Cam &cam, const double (&R)[9], const double (&t)[3],
+                                                const double (&p)[3], double u, double v, double W0, double W1, double W2,
+                                                double (&U)[21], double (&g)[6])
+{
+    double r[2], Jc[12], Jp[6];
+    project_lin<true>(cam, R, t, p, u, v, r, Jc, Jp);
+    const double wr0 = fd2(W0, r[0], W1, r[1]), wr1 = fd2(W1, r[0], W2, r[1]);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        const double w0 = fd2(W0, Jc[a], W1, Jc[6 + a]), w1 = fd2(W1, Jc[a], W2, Jc[6 + a]);
+#pragma unroll
+        for (int b = a; b < 6; ++b)
+            U[lidx(b, a)] = U[lidx(b, a)] + fd2(Jc[b], w0, Jc[6 + b], w1);
+        g[a] = g[a] + fd2(Jc[a], wr0, Jc[6 + a], wr1);
+    }
+}
+
+// x = S^-1 rhs for one wavefront: lane k holds component k of the right-hand side (zero above `first`) and returns
+// component k of the solution.  Sf: the factor (strict lower triangle), dinv: 1 / l_jj.
+__device__ __forceinline__ double win_solve(const double *Sf, const double *dinv, int NC, int first, double bk)
+{
+    const int lane = threadIdx.x & 63;
+    for (int i = first; i < NC; ++i) {
+        const double xi = readlane_f64(bk, i) * dinv[i];
+        if (lane == i)
+            bk = xi;
+        else if (lane > i && lane < NC)
+            bk = fma(-Sf[lidx(lane, i)], xi, bk);
+    }
+    for (int i = NC - 1; i >= 0; --i) {
+        const double xi = readlane_f64(bk, i) * dinv[i];
+        if (lane == i)
+            bk = xi;
+        else if (lane < i)
+            bk = fma(-Sf[lidx(i, lane)], xi, bk);
+    }
+    return bk;
+}
+
+__global__ __launch_bounds__(kWinThreads) void refine_window_kernel(WinDev d)
+{
+    __shared__ double sS[kWinNL + kWinNC];               // reduced system: packed lower triangle, then b
+    __shared__ double sInv[kWinNL];                      // S^-1 (packed lower) at the estimate
+    __shared__ double sZ[kWinChunk * kWinRows * 3];      // Z of the chunk's points
+    __shared__ double sPose[3][kWinMaxFrames][12];       // prior mean (= guess), current, trial: R (9), t (3)
+    __shared__ double sW[kWinMaxFrames][6];              // pose prior weights
+    __shared__ double sDiag[kWinNC], sDinv[kWinNC], sDelta[kWinNC];
+    __shared__ double sRed[4];
+    __shared__ int sBad;
+    const int tid = threadIdx.x, il = tid >> 3, f = tid & 7, lane = tid & 63, wave = tid >> 6;
+    const WinProblem pb = d.prob[blockIdx.x];
+    const int F = pb.n_frames, m = pb.n_points;
+    if (F < 1 || F > kWinMaxFrames || m < 1)
+        return;   // the host has checked: nothing to write to
+    const int NC = 6 * F, NL = NC * (NC + 1) / 2;
+    const RefineCfg &cfg = d.cfg;
+    // inputs of the window: camera (5, padded to 8), poses F x 12, prior weights F x 6, point guesses m x 3, point prior
+    // information m x 6, then per frame observations m x 2 and their information m x 3
+    const double *in = d.in + pb.in_off;
+    Cam cam;
+    cam.fx = in[0], cam.sk = in[1], cam.cx = in[2], cam.fy = in[3], cam.cy = in[4];
+    const double *pose_in = in + 8, *w_in = pose_in + 12 * (size_t)F, *pts0 = w_in + 6 * (size_t)F;
+    const double *pinfo = pts0 + 3 * (size_t)m, *obs = pinfo + 6 * (size_t)m + 2 * (size_t)m * f;
+    const double *oinfo = pinfo + 6 * (size_t)m + 2 * (size_t)m * F + 3 * (size_t)m * f;
+    double *pts = d.pts + 3 * pb.pt_off, *pts_new = d.pts_tmp + 3 * pb.pt_off;
+    for (int k = tid; k < 12 * F; k += kWinThreads) {
+        const double x = pose_in[k];
+        sPose[0][0][k] = x;
+        sPose[1][0][k] = x;
+    }
+    if (tid < 6 * F)
+        sW[0][tid] = w_in[tid];
+    if (tid == 0)
+        sBad = 0;
+    for (int k = tid; k < 3 * m; k += kWinThreads)
+        pts[k] = pts0[k];
+    // the entries of {S, b} this thread owns: row * 3 and column * 3 into a point's Z (b's "column" is the row of L^-1 g_p)
+    int ea[kWinEnt], ec[kWinEnt];
+#pragma unroll
+    for (int k = 0; k < kWinEnt; ++k) {
+        const int e = tid + kWinThreads * k;
+        int a = 0, c = kWinNC;
+        if (e < NL) {
+            while ((a + 1) * (a + 2) / 2 <= e)
+                ++a;
+            c = e - a * (a + 1) / 2;
+        } else if (e < NL + NC) {
+            a = e - NL;
+        } else {
+            a = -1;
+        }
+        ea[k] = a;
+        ec[k] = c;
+    }
+    __syncthreads();   // also orders the copy of the guesses into pts before the first read by another thread
+
+    const bool fon = f < F;
+    const int nchunk = (m + kWinChunk - 1) / kWinChunk;
+
+    // this lane's observation of point i (on: the frame sees it) and the point's prior
+    auto load = [&](const double *cur_pts, int i, double (&p)[3], double (&p0)[3], double (&L)[6], double &u, double &v,
+                    double &W0, double &W1, double &W2) -> bool {
+        const bool in_m = i < m;
+        const int j = in_m ? i : 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            p[k] = cur_pts[3 * (size_t)j + k];
+            p0[k] = pts0[3 * (size_t)j + k];
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+            L[k] = pinfo[6 * (size_t)j + k];
+        u = v = W0 = W1 = W2 = 0.0;
+        if (in_m && fon) {
+            u = obs[2 * (size_t)j], v = obs[2 * (size_t)j + 1];
+            W0 = oinfo[3 * (size_t)j], W1 = oinfo[3 * (size_t)j + 1], W2 = oinfo[3 * (size_t)j + 2];
+        }
+        return in_m && fon && (W0 != 0.0 || W1 != 0.0 || W2 != 0.0);
+    };
+    auto get_pose = [&](int which, double (&R)[9], double (&t)[3]) {
+        const int ff = fon ? f : 0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k)
+            R[k] = sPose[which][ff][k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            t[k] = sPose[which][ff][9 + k];
+    };
+    // 1/2-free cost (sum of squared Mahalanobis norms) of poses `which` and points cur_pts
+    auto total_cost = [&](int which, const double *cur_pts) -> double {
+        double R[9], t[3];
+        get_pose(which, R, t);
+        double c = 0.0;
+        for (int ch = 0; ch < nchunk; ++ch) {
+            const int i = ch * kWinChunk + il;
+            double p[3], p0[3], L[6], u, v, W0, W1, W2;
+            const bool on = load(cur_pts, i, p, p0, L, u, v, W0, W1, W2);
+            if (on)
+                c = c + obs_cost(cam, R, t, p, u, v, W0, W1, W2);
+            if (f == 0 && i < m)
+                c = c + point_prior_cost(L, p0, p);
+        }
+        return c;
+    };
+    auto pose_prior_cost = [&](int which) -> double {   // threads 0 .. F - 1: one frame each
+        double c = 0.0;
+        if (tid < F) {
+            double R0[9], t0[3], R[9], t[3], e[6], Jw[9], Jv[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k)
+                R0[k] = sPose[0][tid][k], R[k] = sPose[which][tid][k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                t0[k] = sPose[0][tid][9 + k], t[k] = sPose[which][tid][9 + k];
+            pose_prior<false>(R0, t0, R, t, e, Jw, Jv);
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+                c = c + (e[k] * e[k]) * sW[tid][k];
+        }
+        return c;
+    };
+
+    // {S, b} at (current poses, pts) with damping lam, then S = L L^T in place.  False if some V or S is not positive definite.
+    auto build_and_factor = [&](const double *cur_pts, double lam) -> bool {
+        double R[9], t[3];
+        get_pose(1, R, t);
+        double acc[kWinEnt];
+#pragma unroll
+        for (int k = 0; k < kWinEnt; ++k)
+            acc[k] = 0.0;
+        bool bad = false;
+        for (int ch = 0; ch < nchunk; ++ch) {
+            const int i = ch * kWinChunk + il;
+            double p[3], p0[3], L[6], u, v, W0, W1, W2, Z[6][3], Li[6], gh[3];
+            const bool on = load(cur_pts, i, p, p0, L, u, v, W0, W1, W2);
+            const bool ok = win_linearize(cam, on, R, t, p, p0, L, u, v, W0, W1, W2, lam, Z, Li, gh);
+            bad = bad || (i < m && !ok);
+            double *zp = sZ + (size_t)il * (kWinRows * 3);
+            if (fon) {
+#pragma unroll
+                for (int a = 0; a < 6; ++a)
+#pragma unroll
+                    for (int k = 0; k < 3; ++k)
+                        zp[(6 * f + a) * 3 + k] = Z[a][k];
+            }
+            if (f == 0) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    zp[kWinNC * 3 + k] = gh[k];
+            }
+            __syncthreads();
+            const int cnt = min(kWinChunk, m - ch * kWinChunk);
+            for (int q = 0; q < cnt; ++q) {
+                const double *zq = sZ + (size_t)q * (kWinRows * 3);
+#pragma unroll
+                for (int k = 0; k < kWinEnt; ++k)
+                    if (ea[k] >= 0) {
+                        const double *za = zq + 3 * ea[k], *zc = zq + 3 * ec[k];
+                        acc[k] = fma(za[2], zc[2], fma(za[1], zc[1], fma(za[0], zc[0], acc[k])));
+                    }
+            }
+            __syncthreads();
+        }
+        if (bad)
+            sBad = 1;
+#pragma unroll
+        for (int k = 0; k < kWinEnt; ++k)
+            if (ea[k] >= 0)
+                sS[tid + kWinThreads * k] = ec[k] == kWinNC ? acc[k] : -acc[k];
+        // the frames' own blocks Hcc_f, g_f in a pass of their own (54 accumulator registers fewer in the pass above, at the
+        // price of projecting every observation once more), then their sum over the point slots il: lanes f, f + 8, ... of a
+        // wavefront, then the four wavefronts
+        double U[21], g[6];
+#pragma unroll
+        for (int k = 0; k < 21; ++k)
+            U[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+            g[k] = 0.0;
+        for (int ch = 0; ch < nchunk; ++ch) {
+            const int i = ch * kWinChunk + il;
+            double p[3], p0[3], L[6], u, v, W0, W1, W2;
+            if (load(cur_pts, i, p, p0, L, u, v, W0, W1, W2))
+                win_frame_block(cam, R, t, p, u, v, W0, W1, W2, U, g);
+        }
+#pragma unroll
+        for (int k = 0; k < 27; ++k) {
+            double x = k < 21 ? U[k] : g[k - 21];
+            x = x + __shfl_xor(x, 8);
+            x = x + __shfl_xor(x, 16);
+            x = x + __shfl_xor(x, 32);
+            if (lane < kWinMaxFrames)
+                sZ[(wave * kWinMaxFrames + lane) * 27 + k] = x;
+        }
+        __syncthreads();
+        if (tid < F) {   // frame tid: its own block, its prior and the damping
+            double R0[9], t0[3], Rf[9], tf[3], e[6], Jw[9], Jv[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k)
+                R0[k] = sPose[0][tid][k], Rf[k] = sPose[1][tid][k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                t0[k] = sPose[0][tid][9 + k], tf[k] = sPose[1][tid][9 + k];
+            pose_prior<true>(R0, t0, Rf, tf, e, Jw, Jv);
+            auto tot = [&](int k) {
+                const double *r = sZ + tid * 27 + k;
+                return (r[0] + r[kWinMaxFrames * 27]) + (r[2 * kWinMaxFrames * 27] + r[3 * kWinMaxFrames * 27]);
+            };
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                const int half = a / 3, a3 = a % 3;
+                const double *J = half ? Jv : Jw;
+                const double w0 = sW[tid][3 * half], w1 = sW[tid][3 * half + 1], w2 = sW[tid][3 * half + 2];
+#pragma unroll
+                for (int c = 0; c <= a; ++c) {
+                    double h = tot(lidx(a, c));
+                    if (c / 3 == half) {
+                        const int c3 = c % 3;
+                        h = h + ((J[a3] * w0 * J[c3] + J[3 + a3] * w1 * J[3 + c3]) + J[6 + a3] * w2 * J[6 + c3]);
+                    }
+                    if (c == a) {
+                        h = h + lam;
+                        sDiag[6 * tid + a] = h;
+                    }
+                    sS[lidx(6 * tid + a, 6 * tid + c)] = sS[lidx(6 * tid + a, 6 * tid + c)] + h;
+                }
+                const double gpr = (J[a3] * w0 * e[3 * half] + J[3 + a3] * w1 * e[3 * half + 1]) + J[6 + a3] * w2 * e[3 * half + 2];
+                sS[NL + 6 * tid + a] = sS[NL + 6 * tid + a] - (tot(21 + a) + gpr);
+            }
+        }
+        __syncthreads();
+        if (sBad)   // uniform: written before the barriers above
+            return false;
+        // right-looking Cholesky; column j is final when step j starts
+        for (int j = 0; j < NC; ++j) {
+            const double dj = sS[lidx(j, j)];
+            if (!(dj > kWinPivotTol * sDiag[j] && dj < __builtin_inf()))
+                return false;   // uniform: every thread reads the same value
+            const double inv = 1.0 / sqrt(dj);
+            if (tid == j)
+                sDinv[j] = inv;
+            else if (tid > j && tid < NC)
+                sS[lidx(tid, j)] = sS[lidx(tid, j)] * inv;
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < kWinEnt; ++k) {
+                const int a = ea[k], c = ec[k];
+                if (a >= 0 && c != kWinNC && c > j)
+                    sS[tid + kWinThreads * k] = fma(-sS[lidx(a, j)], sS[lidx(c, j)], sS[tid + kWinThreads * k]);
+            }
+            __syncthreads();
+        }
+        return true;
+    };
+
+    // cost at the guess
+    double cur = block_reduce1(total_cost(1, pts) + pose_prior_cost(1), sRed);
+    double lam = cfg.lambda_initial;
+    int it = 0;
+    const bool ok0 = cur < __builtin_inf() && cur == cur;
+    while (ok0 && it < cfg.max_iterations) {
+        bool accepted = false;
+        double cand = 0.0;
+        const bool solved = build_and_factor(pts, lam);
+        if (solved) {   // uniform
+            if (wave == 0) {
+                const double x = win_solve(sS, sDinv, NC, 0, lane < NC ? sS[NL + lane] : 0.0);
+                if (lane < NC)
+                    sDelta[lane] = x;
+            }
+            __syncthreads();
+            if (tid < F) {
+                const double *dl = sDelta + 6 * tid, *Rc = sPose[1][tid];
+                const double dw[3] = {dl[0], dl[1], dl[2]};
+                double E[9];
+                so3_exp(dw, E);
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+                        sPose[2][tid][3 * r + c] = (Rc[3 * r] * E[c] + Rc[3 * r + 1] * E[3 + c]) + Rc[3 * r + 2] * E[6 + c];
+                    sPose[2][tid][9 + r] = Rc[9 + r] + ((Rc[3 * r] * dl[3] + Rc[3 * r + 1] * dl[4]) + Rc[3 * r + 2] * dl[5]);
+                }
+            }
+            __syncthreads();
+            // points: dp = -L^-T (L^-1 g_p + Z^T dc)
+            double R[9], t[3], dc[6];
+            get_pose(1, R, t);
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+                dc[k] = fon ? sDelta[6 * f + k] : 0.0;
+            for (int ch = 0; ch < nchunk; ++ch) {
+                const int i = ch * kWinChunk + il;
+                double p[3], p0[3], L[6], u, v, W0, W1, W2, Z[6][3], Li[6], gh[3];
+                const bool on = load(pts, i, p, p0, L, u, v, W0, W1, W2);
+                win_linearize(cam, on, R, t, p, p0, L, u, v, W0, W1, W2, lam, Z, Li, gh);
+                double s[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    double x = 0.0;
+#pragma unroll
+                    for (int a = 0; a < 6; ++a)
+                        x = fma(Z[a][k], dc[a], x);
+                    s[k] = gh[k] + oct_sum(x);
+                }
+                const double dp[3] = {fd3(Li[0], s[0], Li[1], s[1], Li[3], s[2]), fd2(Li[2], s[1], Li[4], s[2]), Li[5] * s[2]};
+                if (f == 0 && i < m) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k)
+                        pts_new[3 * (size_t)i + k] = p[k] - dp[k];
+                }
+            }
+            __syncthreads();   // the trial points are read by the other frame lanes
+            cand = block_reduce1(total_cost(2, pts_new) + pose_prior_cost(2), sRed);
+            accepted = cand <= cur;
+        } else {
+            __syncthreads();   // every thread has read sBad
+            if (tid == 0)
+                sBad = 0;
+            __syncthreads();
+        }
+        ++it;
+        if (accepted) {
+            for (int k = tid; k < 12 * F; k += kWinThreads)
+                sPose[1][0][k] = sPose[2][0][k];
+            __syncthreads();
+            double *sw = pts;
+            pts = pts_new;
+            pts_new = sw;
+            const double dec = 0.5 * (cur - cand);
+            const bool done = dec <= cfg.abs_tol || dec <= cfg.rel_tol * (0.5 * cur);
+            cur = cand;
+            lam = lam / cfg.lambda_factor;
+            if (done)
+                break;
+        } else {
+            // a trial within the tolerances ABOVE the current error: at the minimum to rounding, stop
+            const double inc = 0.5 * (cand - cur);
+            if (solved && (inc <= cfg.abs_tol || inc <= cfg.rel_tol * (0.5 * cur)))
+                break;
+            lam = lam * cfg.lambda_factor;
+            if (lam > cfg.lambda_upper)
+                break;
+        }
+    }
+
+    // marginal covariances at the estimate (lambda = 0)
+    bool ok = ok0 && build_and_factor(pts, 0.0);
+    if (ok) {
+        for (int j = wave; j < NC; j += 4) {   // wavefront w: columns w, w + 4, ... of S^-1
+            const double x = win_solve(sS, sDinv, NC, j, lane == j ? 1.0 : 0.0);
+            if (lane >= j && lane < NC)
+                sInv[lidx(lane, j)] = x;
+        }
+        __syncthreads();
+        if (d.point_cov) {
+            double *pc = d.point_cov + 9 * pb.pt_off;
+            double R[9], t[3];
+            get_pose(1, R, t);
+            for (int ch = 0; ch < nchunk; ++ch) {
+                const int i = ch * kWinChunk + il;
+                double p[3], p0[3], L[6], u, v, W0, W1, W2, Z[6][3], Li[6], gh[3];
+                const bool on = load(pts, i, p, p0, L, u, v, W0, W1, W2);
+                win_linearize(cam, on, R, t, p, p0, L, u, v, W0, W1, W2, 0.0, Z, Li, gh);
+                double *zp = sZ + (size_t)il * (kWinRows * 3);
+                if (fon) {
+#pragma unroll
+                    for (int a = 0; a < 6; ++a)
+#pragma unroll
+                        for (int k = 0; k < 3; ++k)
+                            zp[(6 * f + a) * 3 + k] = Z[a][k];
+                }
+                __syncthreads();
+                // M = Z^T S^-1 Z: this lane's share is Z_f^T (rows 6f .. 6f + 5 of S^-1 Z)
+                double M[9];
+#pragma unroll
+                for (int k = 0; k < 9; ++k)
+                    M[k] = 0.0;
+                if (on) {
+#pragma unroll
+                    for (int a = 0; a < 6; ++a) {
+                        const int ra = 6 * f + a;
+                        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+                        for (int c = 0; c < NC; ++c) {
+                            const double sv = sInv[ra >= c ? lidx(ra, c) : lidx(c, ra)];
+                            s0 = fma(sv, zp[3 * c], s0);
+                            s1 = fma(sv, zp[3 * c + 1], s1);
+                            s2 = fma(sv, zp[3 * c + 2], s2);
+                        }
+#pragma unroll
+                        for (int r = 0; r < 3; ++r) {
+                            const double z = zp[3 * ra + r];
+                            M[3 * r] = fma(z, s0, M[3 * r]);
+                            M[3 * r + 1] = fma(z, s1, M[3 * r + 1]);
+                            M[3 * r + 2] = fma(z, s2, M[3 * r + 2]);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 9; ++k)
+                    M[k] = oct_sum(M[k]);
+                if (f == 0 && i < m) {   // L^-T (I + M) L^-1
+                    const double B[9] = {1.0 + M[0], 0.5 * (M[1] + M[3]), 0.5 * (M[2] + M[6]), 0.0, 1.0 + M[4],
+                                         0.5 * (M[5] + M[7]), 0.0, 0.0, 1.0 + M[8]};
+                    const double b00 = B[0], b01 = B[1], b02 = B[2], b11 = B[4], b12 = B[5], b22 = B[8];
+                    // T = B L^-1 (B symmetric, L^-1 lower: rows l0 = (Li0), l1 = (Li1, Li2), l2 = (Li3, Li4, Li5))
+                    const double T00 = fd3(b00, Li[0], b01, Li[1], b02, Li[3]), T01 = fd2(b01, Li[2], b02, Li[4]), T02 = b02 * Li[5];
+                    const double T10 = fd3(b01, Li[0], b11, Li[1], b12, Li[3]), T11 = fd2(b11, Li[2], b12, Li[4]), T12 = b12 * Li[5];
+                    const double T20 = fd3(b02, Li[0], b12, Li[1], b22, Li[3]), T21 = fd2(b12, Li[2], b22, Li[4]), T22 = b22 * Li[5];
+                    // C = L^-T T: C[r][c] = sum_l Li[l][r] T[l][c]
+                    const double C00 = fd3(Li[0], T00, Li[1], T10, Li[3], T20);
+                    const double C01 = fd3(Li[0], T01, Li[1], T11, Li[3], T21);
+                    const double C02 = fd3(Li[0], T02, Li[1], T12, Li[3], T22);
+                    const double C11 = fd2(Li[2], T11, Li[4], T21);
+                    const double C12 = fd2(Li[2], T12, Li[4], T22);
+                    const double C22 = Li[5] * T22;
+                    double *o = pc + 9 * (size_t)i;
+                    o[0] = C00, o[1] = C01, o[2] = C02, o[3] = C01, o[4] = C11, o[5] = C12, o[6] = C02, o[7] = C12, o[8] = C22;
+                }
+                __syncthreads();
+            }
+        }
+    }
+
+    // the estimate ends in d.pts whichever buffer the last accepted step wrote
+    double *dst = d.pts + 3 * pb.pt_off;
+    if (pts != dst) {
+        for (int k = tid; k < 3 * m; k += kWinThreads)
+            dst[k] = pts[k];
+    }
+    if (tid < F) {
+        mvs_refine_result *o = d.out + pb.fr_off + tid;
+        o->ok = ok ? 1 : 0;
+        o->iterations = it;
+        o->error = 0.5 * cur;
+#pragma unroll
+        for (int k = 0; k < 9; ++k)
+            o->R[k] = sPose[1][tid][k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            o->t[k] = sPose[1][tid][9 + k];
+        for (int r = 0; r < 6; ++r)
+            for (int c = 0; c < 6; ++c) {
+                const int a = 6 * tid + (r >= c ? r : c), b = 6 * tid + (r >= c ? c : r);
+                o->pose_cov[6 * r + c] = ok ? sInv[lidx(a, b)] : 0.0;
+            }
+    }
+}
+
 // covariance -> information, one thread per point slot
 // valid0 / valid1: optional per-observation flags (0 = frame f does not see the point: zero information);
 // a 3x3 covariance whose first entry is <= 0 means "no prior on this point" (zero information)
@@ -1070,6 +1696,13 @@ void launch_refine(const RefineDev &d, hipStream_t stream)
         hipLaunchKernelGGL(refine_kernel<2>, dim3(d.n_problems), dim3(kRefineThreads), 0, stream, d);
     else
         hipLaunchKernelGGL(refine_kernel<1>, dim3(d.n_problems), dim3(kRefineThreads), 0, stream, d);
+}
+
+void launch_refine_window(const WinDev &d, hipStream_t stream)
+{
+    if (d.n_problems <= 0)
+        return;
+    hipLaunchKernelGGL(refine_window_kernel, dim3(d.n_problems), dim3(kWinThreads), 0, stream, d);
 }
 
 void launch_refine_gather(const BatchDev &b, int n_active, double sigma_px, double point_sigma, int stride, int32_t *m,
