@@ -35,6 +35,8 @@ extern "C" {
  * (a batch of sfm_solve calls on caller-supplied point pairs); nothing else changed */
 /* still 4: mvs_ba_window, mvs_ba_refine_window and mvs_ba_refine_windows are additions (new symbols only); no existing entry
  * point or struct changed */
+/* still 4: mvs_seq_window_params, mvs_seq_window_info, mvs_seq_refine_windows, mvs_seq_window_count and
+ * mvs_seq_download_windows are additions (new symbols only) */
 #define MVS_ABI_VERSION 4
 
 typedef enum mvs_status {
@@ -483,6 +485,47 @@ mvs_status mvs_seq_refine_pairs(mvs_seq *s, const mvs_refine_params *params, dou
 /* octaves of the keypoints of frames [first, first + count) uploaded with mvs_seq_upload: count x max_kp bytes */
 mvs_status mvs_seq_upload_octaves(mvs_seq *s, int first, int count, const uint8_t *octave);
 mvs_status mvs_seq_download_refined(mvs_seq *s, mvs_refine_result *refined, double *points_xyz, double *point_cov);
+
+/* Bundle adjustment of sliding windows of a sequence that has been run, assembled on the device from what mvs_seq_run left
+ * resident (the bookkeeping VisualOdometer::track does per frame with hash maps,
+ * front-end/visual-odometer.cpp:417-445,618-800).  Window w covers frames [w * stride, w * stride + window_frames).
+ *   links   an inlier match row of a valid pair k joins keypoint trainIdx of frame k to keypoint queryIdx of frame k + 1; of
+ *           several rows with one trainIdx the smallest row is kept, so tracks are simple chains;
+ *   points  a track that starts in frames a .. a + F - 2 of the window (at frame a it may come from before), cut at frame
+ *           a + F - 1, is a point of the window if one of its links inside the window was triangulated; the first such pair k
+ *           gives the guess X = traj_R[k] (pair_scale[k] x) + traj_t[k].  Points are numbered by (first frame, keypoint); the
+ *           first max_points are kept;
+ *   problem poses = the trajectory, frame a carries params->anchor_sigma, the others pose_sigma, every point the prior
+ *           point_sigma^2 I at its guess, an observation the covariance (sigma_px * 2^octave)^2 I.
+ * One launch of the window kernel of mvs_ba_refine_windows solves all windows. */
+typedef struct mvs_seq_window_params {
+    int32_t window_frames;  /* F: 3 .. 8 */
+    int32_t stride;         /* >= 1 */
+    int32_t max_points;     /* 1 .. 4096: point capacity of one window */
+    int32_t reserved;
+    double sigma_px;        /* as mvs_batch_refine */
+} mvs_seq_window_params;
+typedef struct mvs_seq_window_info {
+    int32_t first_frame, n_frames, n_points, n_tracks_found;   /* n_points = min(n_tracks_found, max_points) */
+} mvs_seq_window_info;
+/* W = (n_frames - F) / stride + 1; 0 if the sequence is shorter than a window or window_frames, stride or max_points is out
+ * of range (sigma_px is not looked at) */
+int mvs_seq_window_count(const mvs_seq *s, const mvs_seq_window_params *wp);
+/* Asynchronous on the ctx stream, after mvs_seq_run; the results stay resident until downloaded.  MVS_ERR_INVALID_ARG for
+ * window_frames outside 3 .. 8, stride < 1, max_points outside 1 .. 4096, sigma_px <= 0, a sequence that has not been run or
+ * that is shorter than one window.
+ * Memory: the link tables, the windows' problems and their results live in one block owned by the SEQUENCE (the context's
+ * window workspace would be overwritten by the next mvs_ba_refine_windows while these results are resident).  The block only
+ * grows and is freed by mvs_seq_destroy; every window owns (8 + 18 F + (9 + 5 F) max_points + 18 max_points) doubles and
+ * F max_points int32 of it whatever it holds: about 0.5 GB for 249 windows of F = 8 and max_points = 4096.  A caller with
+ * many sequences chooses max_points accordingly. */
+mvs_status mvs_seq_refine_windows(mvs_seq *s, const mvs_seq_window_params *wp, const mvs_refine_params *params);
+/* Any pointer may be NULL.  info[W], frames[W][F], points[W][max_points][3], point_cov[W][max_points][9],
+ * track_kp[W][max_points][F] (keypoint of the point in frame first_frame + f, -1 = not seen), point_guess[W][max_points][3];
+ * rows [n_points, max_points) of a window are zero (track_kp: -1).  MVS_NO_MODEL if at least one window has ok = 0, which a
+ * window without points has (frames[w * F].ok tells which): the convention of mvs_ba_refine_windows. */
+mvs_status mvs_seq_download_windows(mvs_seq *s, mvs_seq_window_info *info, mvs_refine_result *frames, double *points,
+                                    double *point_cov, int32_t *track_kp, double *point_guess);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Row f3: keypoint + descriptor extraction.  Replaces VisualFeature::extract

@@ -102,6 +102,18 @@ REFINE_DTYPE = np.dtype([("ok", "<i4"), ("iterations", "<i4"), ("error", "<f8"),
                          ("t", "<f8", (3,)), ("pose_cov", "<f8", (6, 6))])
 
 
+class SeqWindowParams(C.Structure):
+    _fields_ = [("window_frames", C.c_int32), ("stride", C.c_int32), ("max_points", C.c_int32), ("reserved", C.c_int32),
+                ("sigma_px", C.c_double)]
+
+
+class SeqWindowInfo(C.Structure):
+    _fields_ = [("first_frame", C.c_int32), ("n_frames", C.c_int32), ("n_points", C.c_int32), ("n_tracks_found", C.c_int32)]
+
+
+WINDOW_INFO_DTYPE = np.dtype([("first_frame", "<i4"), ("n_frames", "<i4"), ("n_points", "<i4"), ("n_tracks_found", "<i4")])
+
+
 class OrbParams(C.Structure):
     _fields_ = [("nfeatures", C.c_int32), ("nlevels", C.c_int32), ("edge_threshold", C.c_int32),
                 ("fast_threshold", C.c_int32)]
@@ -142,7 +154,8 @@ EXPORTS = [
     "mvs_batch_upload_async", "mvs_batch_download_async", "mvs_host_alloc", "mvs_host_free", "mvs_image_pair",
     "mvs_batch_gather_results", "mvs_seq_time_stages", "mvs_batch_time_kernels", "mvs_kernel_info_get",
     "mvs_extract_time", "mvs_ctx_set_half_batches", "mvs_batch_device_state", "mvs_batch_run_points",
-    "mvs_ba_refine_window", "mvs_ba_refine_windows",
+    "mvs_ba_refine_window", "mvs_ba_refine_windows", "mvs_seq_refine_windows", "mvs_seq_window_count",
+    "mvs_seq_download_windows",
 ]
 
 
@@ -195,6 +208,7 @@ def lib():
         _lib.mvs_ctx_destroy.argtypes = [C.c_void_p]
         _lib.mvs_batch_destroy.argtypes = [C.c_void_p]
         _lib.mvs_seq_destroy.argtypes = [C.c_void_p]
+        _lib.mvs_seq_window_count.argtypes = [C.c_void_p, C.c_void_p]
     return _lib
 
 
@@ -847,6 +861,7 @@ class Sequence:
         ctx._check(lib().mvs_seq_create(ctx._h, C.c_int(n_frames), C.c_int(max_kp), C.c_int(desc_bytes),
                                         C.byref(self._h)), "mvs_seq_create")
         ctx._children.add(self)
+        self._windows = None   # SeqWindowParams of the last refine_windows()
 
     def close(self):
         if self._h:
@@ -922,6 +937,41 @@ class Sequence:
         st = lib().mvs_seq_download_refined(self._h, res.ctypes.data_as(C.c_void_p), _ptr(pts, C.c_double), _ptr(pc, C.c_double))
         self.ctx._check(st, "mvs_seq_download_refined")
         return dict(refined=res, points=pts, point_cov=pc)
+
+    def refine_windows(self, window_frames, stride, max_points=4096, params=None, sigma_px=0.5):
+        """bundle-adjust the windows [w * stride, w * stride + window_frames) of a sequence that has been run, assembled on
+        the device from the resident matches, points and trajectory (asynchronous; download_windows() fetches the results)"""
+        params = params or default_refine_params()
+        wp = SeqWindowParams(int(window_frames), int(stride), int(max_points), 0, float(sigma_px))
+        self.ctx._check(lib().mvs_seq_refine_windows(self._h, C.byref(wp), C.byref(params)), "mvs_seq_refine_windows")
+        self._windows = wp
+
+    def download_windows(self):
+        """one dict per window, shaped like Context.ba_refine_windows's, plus first_frame, n_tracks_found, track_kp
+        [n_points][F] (keypoint of the point in frame first_frame + f, -1 = not seen) and point_guess [n_points][3]"""
+        wp = self._windows
+        if wp is None:
+            raise MvsError(MVS_ERR_INVALID_ARG, "mvs_seq_download_windows")
+        W, F, cap = lib().mvs_seq_window_count(self._h, C.byref(wp)), wp.window_frames, wp.max_points
+        info = np.zeros(W, dtype=WINDOW_INFO_DTYPE)
+        res = np.zeros((W, F), dtype=REFINE_DTYPE)
+        pts, ptc = np.zeros((W, cap, 3)), np.zeros((W, cap, 3, 3))
+        tkp = np.zeros((W, cap, F), dtype=np.int32)
+        guess = np.zeros((W, cap, 3))
+        st = lib().mvs_seq_download_windows(self._h, info.ctypes.data_as(C.c_void_p), res.ctypes.data_as(C.c_void_p),
+                                            _ptr(pts, C.c_double), _ptr(ptc, C.c_double), _ptr(tkp, C.c_int32),
+                                            _ptr(guess, C.c_double))
+        self.ctx._check(st, "mvs_seq_download_windows", allow_no_model=True)
+        out = []
+        for w in range(W):
+            r, m = res[w], int(info[w]["n_points"])
+            out.append(dict(ok=bool(r["ok"][0]), status=MVS_OK if r["ok"][0] else MVS_NO_MODEL, R=r["R"].copy(), t=r["t"].copy(),
+                            pose_cov=r["pose_cov"].copy(), points=pts[w, :m].copy(), point_cov=ptc[w, :m].copy(),
+                            error=float(r["error"][0]), iterations=int(r["iterations"][0]), raw=r.tobytes(),
+                            first_frame=int(info[w]["first_frame"]), n_frames=int(info[w]["n_frames"]), n_points=m,
+                            n_tracks_found=int(info[w]["n_tracks_found"]), track_kp=tkp[w, :m].copy(),
+                            point_guess=guess[w, :m].copy()))
+        return out
 
     def download_pairs(self):
         P, N = self.n_frames - 1, self.max_kp

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -101,6 +102,11 @@ struct mvs_seq {
     RefineDev refit{};          // pnp_solve's refit over the inliers of every track (mvs_pnp_params.refit), allocated on demand
     bool refit_on = false;
     DevBlocks blocks;
+    bool ran = false;           // mvs_seq_run has filled the pairs, the tracks and the trajectory
+    // mvs_seq_refine_windows: link tables, the windows' problems and their results, resident until the next call
+    DevWorkspace win;
+    SeqWinDev wd{};             // n_windows = 0 until the first call
+    WinDev ws{};
 };
 
 #define HIP_TRY(ctx_, expr)                                                                    \
@@ -2256,6 +2262,8 @@ static mvs_status seq_enqueue(mvs_seq *q, const RunParams &rp)
     q->chain.n_corr = q->pnp.n;
     launch_seq_chain(q->chain, q->ctx->stream);
     HIP_TRY(q->ctx, hipGetLastError());
+    q->ran = true;
+    q->wd.n_windows = 0;   // windows of an earlier run are not this run's
     return MVS_OK;
 }
 
@@ -2746,8 +2754,25 @@ static mvs_status window_check(const mvs_ba_window *w)
     return MVS_OK;
 }
 
+// covariance -> information with refine_prep_kernel's formulas: a 2 x 2 observation covariance (row-major) to (xx xy yy), a
+// 3 x 3 point prior covariance to (xx xy xz yy yz zz)
+static void obs_cov_to_info(const double *cv, double *o)
+{
+    const double a = cv[0], b = 0.5 * (cv[1] + cv[2]), dd = cv[3];
+    const double id = 1.0 / (a * dd - b * b);
+    o[0] = dd * id, o[1] = -(b * id), o[2] = a * id;
+}
+static void point_cov_to_info(const double *C, double *L)
+{
+    const double a[6] = {C[0], 0.5 * (C[1] + C[3]), 0.5 * (C[2] + C[6]), C[4], 0.5 * (C[5] + C[7]), C[8]};
+    const double c00 = a[3] * a[5] - a[4] * a[4], c01 = a[2] * a[4] - a[1] * a[5], c02 = a[1] * a[4] - a[2] * a[3];
+    const double id = 1.0 / ((a[0] * c00 + a[1] * c01) + a[2] * c02);
+    L[0] = c00 * id, L[1] = c01 * id, L[2] = c02 * id;
+    L[3] = (a[0] * a[5] - a[2] * a[2]) * id, L[4] = (a[1] * a[2] - a[0] * a[4]) * id, L[5] = (a[0] * a[3] - a[1] * a[1]) * id;
+}
+
 // the inputs of one window in the layout refine_window_kernel reads (WinProblem::in_off); covariances become information
-// matrices here, with refine_prep_kernel's formulas
+// matrices here
 static void window_pack(const mvs_ba_window *w, std::vector<double> &in)
 {
     const size_t F = (size_t)w->n_frames, m = (size_t)w->n_points;
@@ -2764,12 +2789,7 @@ static void window_pack(const mvs_ba_window *w, std::vector<double> &in)
         const double *C = w->point_prior_cov + 9 * i;
         if (!(C[0] > 0.0))
             continue;   // no prior on this point
-        const double a[6] = {C[0], 0.5 * (C[1] + C[3]), 0.5 * (C[2] + C[6]), C[4], 0.5 * (C[5] + C[7]), C[8]};
-        const double c00 = a[3] * a[5] - a[4] * a[4], c01 = a[2] * a[4] - a[1] * a[5], c02 = a[1] * a[4] - a[2] * a[3];
-        const double id = 1.0 / ((a[0] * c00 + a[1] * c01) + a[2] * c02);
-        double *L = pinfo + 6 * i;
-        L[0] = c00 * id, L[1] = c01 * id, L[2] = c02 * id;
-        L[3] = (a[0] * a[5] - a[2] * a[2]) * id, L[4] = (a[1] * a[2] - a[0] * a[4]) * id, L[5] = (a[0] * a[3] - a[1] * a[1]) * id;
+        point_cov_to_info(C, pinfo + 6 * i);
     }
     for (size_t f = 0; f < F; ++f) {
         std::memcpy(obs + 2 * m * f, w->obs[f], 2 * m * sizeof(double));
@@ -2779,13 +2799,10 @@ static void window_pack(const mvs_ba_window *w, std::vector<double> &in)
         for (size_t i = 0; i < m; ++i, o += 3) {
             if (vd && !vd[i])
                 continue;   // not seen: zero information
-            if (!cv) {
+            if (!cv)
                 o[0] = 1.0, o[2] = 1.0;
-            } else {
-                const double a = cv[4 * i], b = 0.5 * (cv[4 * i + 1] + cv[4 * i + 2]), dd = cv[4 * i + 3];
-                const double id = 1.0 / (a * dd - b * b);
-                o[0] = dd * id, o[1] = -(b * id), o[2] = a * id;
-            }
+            else
+                obs_cov_to_info(cv + 4 * i, o);
         }
     }
 }
@@ -2982,6 +2999,148 @@ mvs_status mvs_seq_download_trajectory(mvs_seq *q, double *R, double *t, double 
 mvs_status mvs_seq_refine_pairs(mvs_seq *q, const mvs_refine_params *params, double sigma_px)
 {
     return q ? mvs_batch_refine(q->batch, params, sigma_px) : MVS_ERR_INVALID_ARG;
+}
+
+// ---- sliding windows of a sequence that has been run ------------------------------------------------------------------
+// the fields that shape the windows (sigma_px only weighs the observations: mvs_seq_refine_windows checks it)
+static bool seq_window_shape_ok(const mvs_seq_window_params *wp)
+{
+    return wp && wp->window_frames >= 3 && wp->window_frames <= kWinMaxFrames && wp->stride >= 1 && wp->max_points >= 1 &&
+           wp->max_points <= kMaxKp;
+}
+
+int mvs_seq_window_count(const mvs_seq *q, const mvs_seq_window_params *wp)
+{
+    if (!q || !seq_window_shape_ok(wp) || q->n_frames < wp->window_frames)
+        return 0;
+    return (q->n_frames - wp->window_frames) / wp->stride + 1;
+}
+
+mvs_status mvs_seq_refine_windows(mvs_seq *q, const mvs_seq_window_params *wp, const mvs_refine_params *params)
+{
+    if (!q || !seq_window_shape_ok(wp) || !(wp->sigma_px > 0.0) || !refine_params_ok(params) || !q->ran ||
+        q->n_frames < wp->window_frames)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const BatchDev &bd = q->batch->d;
+    const size_t W = (size_t)mvs_seq_window_count(q, wp), F = (size_t)wp->window_frames, cap = (size_t)wp->max_points;
+    const size_t NF = (size_t)q->n_frames, N = (size_t)bd.max_kp;
+    const size_t in_stride = 8 + 18 * F + 9 * cap + 5 * F * cap;
+    // every window owns a fixed share of each array, so the offsets are known before the device has counted a point.
+    // Outputs first (what the download reads), then the candidate points, the problems and the link tables
+    Carve L{64};
+    const size_t off_info = L.take(W * sizeof(mvs_seq_window_info));
+    const size_t off_out = L.take(W * F * sizeof(mvs_refine_result));
+    const size_t off_pts = L.take(W * cap * 3 * sizeof(double));
+    const size_t off_cov = L.take(W * cap * 9 * sizeof(double));
+    const size_t off_tkp = L.take(W * cap * F * sizeof(int32_t));
+    const size_t off_guess = L.take(W * cap * 3 * sizeof(double));
+    const size_t off_zero_end = off_tkp;   // records, points and covariances are cleared before every solve
+    const size_t off_tmp = L.take(W * cap * 3 * sizeof(double));
+    const size_t off_prob = L.take(W * sizeof(WinProblem));
+    const size_t off_in = L.take(W * in_stride * sizeof(double));
+    const size_t off_succ = L.take((NF - 1) * N * sizeof(int32_t));
+    const size_t off_pred = L.take(NF * N * sizeof(int32_t));
+    const size_t off_rtp = L.take((NF - 1) * N * sizeof(int32_t));
+    q->wd.n_windows = 0;   // growing frees the block an earlier call's results live in
+    const mvs_status st = ws_grow(ctx, q->win, L.total());
+    if (st != MVS_OK)
+        return st;
+    char *base = q->win.ptr();
+    SeqWinDev d{};
+    d.n_frames = q->n_frames;
+    d.max_kp = bd.max_kp;
+    d.F = wp->window_frames;
+    d.stride = wp->stride;
+    d.max_points = wp->max_points;
+    d.n_windows = (int)W;
+    d.results = bd.results;
+    d.matches = bd.matches;
+    d.mask = bd.mask;
+    d.points = bd.points;
+    d.point_idx = bd.point_idx;
+    d.kp = bd.kp1;
+    d.oct = bd.oct1;
+    d.K = bd.K;
+    d.traj_R = q->chain.traj_R;
+    d.traj_t = q->chain.traj_t;
+    d.traj_sigma = q->chain.traj_sigma;
+    d.succ = reinterpret_cast<int32_t *>(base + off_succ);
+    d.pred = reinterpret_cast<int32_t *>(base + off_pred);
+    d.row_to_point = reinterpret_cast<int32_t *>(base + off_rtp);
+    // the prior weights as mvs_seq_refine_pairs applies them (to_cfg), the information matrices as window_pack derives them
+    // from the covariances sigma^2 I
+    const RefineCfg two = to_cfg(*params, 2);
+    for (int k = 0; k < 6; ++k) {
+        d.w_anchor[k] = two.w[0][k];
+        d.w_pose[k] = two.w[1][k];
+    }
+    const double pv = params->point_sigma * params->point_sigma;
+    const double pc[9] = {pv, 0.0, 0.0, 0.0, pv, 0.0, 0.0, 0.0, pv};
+    point_cov_to_info(pc, d.pinfo);
+    for (int oc = 0; oc <= kSeqWinMaxOctave; ++oc) {
+        const double sd = std::ldexp(wp->sigma_px, oc);   // VisualFeature::get_point_estimates: stddev = 2^octave * sigma_px
+        const double cv[4] = {sd * sd, 0.0, 0.0, sd * sd};
+        obs_cov_to_info(cv, d.oinfo[oc]);
+    }
+    d.prob = reinterpret_cast<WinProblem *>(base + off_prob);
+    d.in = reinterpret_cast<double *>(base + off_in);
+    d.in_stride = (int64_t)in_stride;
+    d.info = reinterpret_cast<mvs_seq_window_info *>(base + off_info);
+    d.track_kp = reinterpret_cast<int32_t *>(base + off_tkp);
+    d.point_guess = reinterpret_cast<double *>(base + off_guess);
+    WinDev s{};
+    s.n_problems = (int)W;
+    s.cfg = to_cfg(*params, 1);
+    s.prob = d.prob;
+    s.in = d.in;
+    s.pts = reinterpret_cast<double *>(base + off_pts);
+    s.pts_tmp = reinterpret_cast<double *>(base + off_tmp);
+    s.point_cov = reinterpret_cast<double *>(base + off_cov);
+    s.out = reinterpret_cast<mvs_refine_result *>(base + off_out);
+    hipStream_t stream = ctx->stream;
+    // a window without points is left alone by the window kernel: its records read ok = 0
+    HIP_TRY(ctx, hipMemsetAsync(base + off_out, 0, off_zero_end - off_out, stream));
+    launch_seq_windows(d, stream);
+    launch_refine_window(s, stream);
+    HIP_TRY(ctx, hipGetLastError());
+    q->wd = d;
+    q->ws = s;
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_download_windows(mvs_seq *q, mvs_seq_window_info *info, mvs_refine_result *frames, double *points,
+                                    double *point_cov, int32_t *track_kp, double *point_guess)
+{
+    if (!q || q->wd.n_windows < 1)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const SeqWinDev &d = q->wd;
+    const size_t W = (size_t)d.n_windows, F = (size_t)d.F, cap = (size_t)d.max_points;
+    hipStream_t s = ctx->stream;
+    std::vector<mvs_refine_result> own;
+    if (!frames) {   // the status needs the records
+        own.resize(W * F);
+        frames = own.data();
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(frames, q->ws.out, W * F * sizeof(mvs_refine_result), hipMemcpyDeviceToHost, s));
+    if (info)
+        HIP_TRY(ctx, hipMemcpyAsync(info, d.info, W * sizeof(mvs_seq_window_info), hipMemcpyDeviceToHost, s));
+    if (points)
+        HIP_TRY(ctx, hipMemcpyAsync(points, q->ws.pts, W * cap * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (point_cov)
+        HIP_TRY(ctx, hipMemcpyAsync(point_cov, q->ws.point_cov, W * cap * 9 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (track_kp)
+        HIP_TRY(ctx, hipMemcpyAsync(track_kp, d.track_kp, W * cap * F * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (point_guess)
+        HIP_TRY(ctx, hipMemcpyAsync(point_guess, d.point_guess, W * cap * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    for (size_t w = 0; w < W; ++w)
+        if (!frames[w * F].ok)
+            return MVS_NO_MODEL;
+    return MVS_OK;
 }
 
 mvs_status mvs_batch_upload_octaves(mvs_batch *b, int first, int count, const uint8_t *base_octave,

@@ -262,6 +262,41 @@ struct WinDev {
 };
 void launch_refine_window(const WinDev &d, hipStream_t stream);
 
+// ---- sliding windows of a resident sequence (mvs_seq_refine_windows) -------------------------
+// seq_link_kernel chains the inlier matches of consecutive pairs into tracks (every keypoint gets at most one successor and
+// one predecessor); seq_window_assemble_kernel turns the tracks of window w = frames [w * stride, w * stride + F) into the
+// inputs refine_window_kernel reads.  Every window owns in_stride doubles of `in` and max_points points, whatever it holds.
+constexpr int kSeqWinMaxOctave = 30;   // mvs_seq_upload_octaves admits no more
+struct SeqWinDev {
+    int n_frames, max_kp;              // the sequence: frames, keypoint capacity N of a frame
+    int F, stride, max_points, n_windows;
+    // resident state of the sequence (mvs_seq_run)
+    const mvs_pair_result *results;    // [n_frames - 1]
+    const mvs_match *matches;          // [n_frames - 1][N]
+    const uint8_t *mask;               // [n_frames - 1][N]
+    const double *points;              // [n_frames - 1][N][3]
+    const int32_t *point_idx;          // [n_frames - 1][N]
+    const float *kp;                   // [n_frames][N][2]
+    const uint8_t *oct;                // [n_frames][N]
+    const double *K;                   // [9] the sequence's camera
+    const double *traj_R, *traj_t, *traj_sigma;   // SeqChainDev's outputs
+    // links (seq_link_kernel): pair k joins keypoint i of frame k to keypoint matches[k][succ[k][i]].queryIdx of frame k + 1
+    int32_t *succ;                     // [n_frames - 1][N] match row of the link out of keypoint i, -1 = none
+    int32_t *pred;                     // [n_frames][N] keypoint of the previous frame linked to keypoint i, -1 = none
+    int32_t *row_to_point;             // [n_frames - 1][N] inverse of point_idx: triangulated point of a match row, -1 = none
+    // what every window shares: prior weights of frame a and of the other frames, the points' prior information (xx xy xz yy
+    // yz zz) and the observations' information (xx xy yy) per octave, all worked out on the host
+    double w_anchor[6], w_pose[6], pinfo[6], oinfo[kSeqWinMaxOctave + 1][3];
+    // outputs
+    WinProblem *prob;                  // [n_windows]
+    double *in;                        // [n_windows][in_stride]
+    int64_t in_stride;
+    mvs_seq_window_info *info;         // [n_windows]
+    int32_t *track_kp;                 // [n_windows][max_points][F] keypoint of the track in frame a + f, -1 = not seen
+    double *point_guess;               // [n_windows][max_points][3]
+};
+void launch_seq_windows(const SeqWinDev &d, hipStream_t stream);
+
 // ---- VisualFeature::extract (row f3): ORB-style extraction for a batch of equally sized images ----------------
 constexpr int kOrbMaxLevels = 16;
 constexpr int kOrbSelCap = 16384;    // keys of one (image, level) the selection can hold in LDS (128 KB): 2 n_l <= this, or the

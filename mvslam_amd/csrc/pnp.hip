@@ -541,6 +541,211 @@ void launch_seq_join(const SeqJoinDev &j, hipStream_t stream)
     hipLaunchKernelGGL(seq_join_kernel, dim3(j.n_tracks), dim3(256), 0, stream, j);
 }
 
+// ---- sliding windows of a sequence: links between consecutive frames, then the windows' problems 
+// grid n_frames - 1, block 256.  Pair k: a link is an inlier row r < n_matches of a valid pair; it joins keypoint trainIdx of
+// frame k to keypoint queryIdx of frame k + 1.  Rows that share a trainIdx: the smallest row wins (a minimum does not depend
+// on the order the rows arrive in), the others are dropped; queryIdx values are unique within one match list.  So every
+// keypoint has at most one successor and one predecessor.  Also inverts point_idx: row_to_point[k][r].
+__global__ __launch_bounds__(256) void seq_link_kernel(SeqWinDev d)
+{
+    __shared__ int s_row[kMaxKp];
+    const int k = blockIdx.x, tid = threadIdx.x, N = d.max_kp;
+    const size_t o = (size_t)k * N;
+    const mvs_pair_result &res = d.results[k];
+    const bool valid = res.valid != 0;
+    const int M = valid ? min(max(res.n_matches, 0), N) : 0, npts = valid ? min(max(res.n_points, 0), N) : 0;
+    int32_t *pred = d.pred + o + N;   // of frame k + 1
+    for (int i = tid; i < N; i += 256) {
+        s_row[i] = INT_MAX;
+        pred[i] = -1;
+        d.row_to_point[o + i] = -1;
+        if (k == 0)
+            d.pred[i] = -1;           // frame 0 has no predecessors
+    }
+    __syncthreads();
+    auto link = [&](int r, mvs_match &mt) {
+        mt = d.matches[o + r];
+        return d.mask[o + r] == 1 && (unsigned)mt.trainIdx < (unsigned)N && (unsigned)mt.queryIdx < (unsigned)N;
+    };
+    for (int r = tid; r < M; r += 256) {
+        mvs_match mt;
+        if (link(r, mt))
+            atomicMin(&s_row[mt.trainIdx], r);
+    }
+    for (int j = tid; j < npts; j += 256) {
+        const int r = d.point_idx[o + j];
+        if ((unsigned)r < (unsigned)M)
+            d.row_to_point[o + r] = j;   // point_idx holds every row once
+    }
+    __syncthreads();
+    for (int r = tid; r < M; r += 256) {
+        mvs_match mt;
+        if (link(r, mt) && s_row[mt.trainIdx] == r)
+            pred[mt.queryIdx] = mt.trainIdx;
+    }
+    for (int i = tid; i < N; i += 256)
+        d.succ[o + i] = s_row[i] == INT_MAX ? -1 : s_row[i];
+}
+
+// grid n_windows, block 256.  Window w = frames a .. a + F - 1, a = w * stride.  Pass 1 flags the heads -- (frame j <= a + F - 2,
+// keypoint i) with a link out of pair j and, for j > a, none into it -- whose chain, cut at frame a + F - 1, holds a
+// triangulated link, and numbers them by a workgroup prefix sum in the order (j, i): no atomic decides an index, two runs give
+// the same bytes.  Pass 2: every kept head walks its chain (at most F - 1 steps) and writes its rows straight into the layout
+// refine_window_kernel reads, for m = min(heads, max_points) points.
+__global__ __launch_bounds__(256) void seq_window_assemble_kernel(SeqWinDev d)
+{
+    __shared__ uint16_t s_head[kMaxKp];   // kept heads: (j - a) << 12 | i
+    __shared__ int s_tot[4];
+    const int w = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int N = d.max_kp, F = d.F, a = w * d.stride, cap = d.max_points;
+    int basepos = 0;
+    for (int g = 0; g < F - 1; ++g) {
+        const size_t o = (size_t)(a + g) * N;
+        for (int start = 0; start < N; start += 256) {
+            const int i = start + tid;
+            bool flag = false;
+            if (i < N) {
+                int r = d.succ[o + i];
+                if (r >= 0 && (g == 0 || d.pred[o + i] < 0)) {
+                    size_t of = o;
+                    for (int f = g;;) {
+                        if (d.row_to_point[of + r] >= 0) {
+                            flag = true;
+                            break;
+                        }
+                        if (++f > F - 2)
+                            break;
+                        const int cur = d.matches[of + r].queryIdx;
+                        of += N;
+                        r = d.succ[of + cur];
+                        if (r < 0)
+                            break;
+                    }
+                }
+            }
+            const unsigned long long bal = __ballot(flag);
+            const int pre = __popcll(bal & ((1ull << lane) - 1ull));
+            if (lane == 0)
+                s_tot[wave] = __popcll(bal);
+            __syncthreads();
+            int off = basepos, tot = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int v = s_tot[k];
+                off += (k < wave) ? v : 0;
+                tot += v;
+            }
+            const int pos = off + pre;
+            if (flag && pos < cap)
+                s_head[pos] = (uint16_t)((g << 12) | i);
+            basepos += tot;
+            __syncthreads();
+        }
+    }
+    const int m = min(basepos, cap);
+    // the window's inputs: camera (5, padded to 8), poses F x 12, prior weights F x 6, guesses m x 3, point information m x 6,
+    // observations F x m x 2, their information F x m x 3
+    double *in = d.in + (size_t)w * d.in_stride;
+    double *pose = in + 8, *wt = pose + 12 * (size_t)F, *p0 = wt + 6 * (size_t)F, *pinfo = p0 + 3 * (size_t)m;
+    double *obs = pinfo + 6 * (size_t)m, *oinfo = obs + 2 * (size_t)F * m;
+    if (tid < 8)
+        in[tid] = tid < 5 ? d.K[tid < 3 ? tid : tid + 1] : 0.0;   // fx sk cx fy cy = K[0 1 2 4 5]
+    for (int k = tid; k < 12 * F; k += 256) {
+        const int f = k / 12, e = k - 12 * f;
+        pose[k] = e < 9 ? d.traj_R[9 * (size_t)(a + f) + e] : d.traj_t[3 * (size_t)(a + f) + (e - 9)];
+    }
+    if (tid < 6 * F)
+        wt[tid] = tid < 6 ? d.w_anchor[tid] : d.w_pose[tid % 6];
+    if (tid == 0) {
+        WinProblem pb;
+        pb.n_frames = F;
+        pb.n_points = m;
+        pb.in_off = (int64_t)w * d.in_stride;
+        pb.pt_off = (int64_t)w * cap;
+        pb.fr_off = (int64_t)w * F;
+        d.prob[w] = pb;
+        mvs_seq_window_info wi;
+        wi.first_frame = a;
+        wi.n_frames = F;
+        wi.n_points = m;
+        wi.n_tracks_found = basepos;
+        d.info[w] = wi;
+    }
+    int32_t *tkp = d.track_kp + (size_t)w * cap * F;
+    double *guess = d.point_guess + (size_t)w * cap * 3;
+    for (int p = tid; p < cap; p += 256) {
+        if (p >= m) {   // rows past the window's points: the download is the whole capacity
+            for (int f = 0; f < F; ++f)
+                tkp[(size_t)p * F + f] = -1;
+            guess[3 * p] = guess[3 * p + 1] = guess[3 * p + 2] = 0.0;
+            continue;
+        }
+        const int g0 = s_head[p] >> 12, i0 = s_head[p] & 4095;
+        int cur = -1, tri_k = -1, tri_j = 0;
+        int kpi[kWinMaxFrames];
+#pragma unroll
+        for (int g = 0; g < kWinMaxFrames; ++g) {
+            if (g == g0)
+                cur = i0;
+            kpi[g] = g < F ? cur : -1;
+            if (cur >= 0 && g < F - 1) {
+                const size_t of = (size_t)(a + g) * N;
+                const int r = d.succ[of + cur];
+                if (r >= 0) {
+                    const int j = d.row_to_point[of + r];
+                    if (tri_k < 0 && j >= 0) {
+                        tri_k = a + g;
+                        tri_j = j;
+                    }
+                    cur = d.matches[of + r].queryIdx;
+                } else {
+                    cur = -1;
+                }
+            }
+        }
+        // the first triangulated link gives the guess: pair tri_k's point, scaled and moved into the trajectory's frame
+        tri_k = max(tri_k, a);   // pass 1 kept the head for its triangulated link: tri_k is one of the window's pairs
+        const double *x = d.points + 3 * ((size_t)tri_k * N + tri_j), *R = d.traj_R + 9 * (size_t)tri_k;
+        const double *t = d.traj_t + 3 * (size_t)tri_k, sg = d.traj_sigma[tri_k];
+        const double s0 = sg * x[0], s1 = sg * x[1], s2 = sg * x[2];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const double X = ((R[3 * i] * s0 + R[3 * i + 1] * s1) + R[3 * i + 2] * s2) + t[i];
+            p0[3 * (size_t)p + i] = X;
+            guess[3 * p + i] = X;
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+            pinfo[6 * (size_t)p + k] = d.pinfo[k];
+#pragma unroll
+        for (int g = 0; g < kWinMaxFrames; ++g) {
+            if (g >= F)
+                continue;
+            const int i = kpi[g];
+            tkp[(size_t)p * F + g] = i;
+            double u = 0.0, v = 0.0, W0 = 0.0, W1 = 0.0, W2 = 0.0;   // not seen: zero information
+            if (i >= 0) {
+                const size_t s = (size_t)(a + g) * N + i;
+                u = (double)d.kp[2 * s];
+                v = (double)d.kp[2 * s + 1];
+                const int oc = min((int)d.oct[s], kSeqWinMaxOctave);
+                W0 = d.oinfo[oc][0], W1 = d.oinfo[oc][1], W2 = d.oinfo[oc][2];
+            }
+            double *ob = obs + 2 * ((size_t)m * g + p), *oi = oinfo + 3 * ((size_t)m * g + p);
+            ob[0] = u, ob[1] = v;
+            oi[0] = W0, oi[1] = W1, oi[2] = W2;
+        }
+    }
+}
+
+void launch_seq_windows(const SeqWinDev &d, hipStream_t stream)
+{
+    if (d.n_windows <= 0)
+        return;
+    hipLaunchKernelGGL(seq_link_kernel, dim3(d.n_frames - 1), dim3(256), 0, stream, d);
+    hipLaunchKernelGGL(seq_window_assemble_kernel, dim3(d.n_windows), dim3(256), 0, stream, d);
+}
+
 void launch_pnp(const PnpDev &p, hipStream_t stream)
 {
     const int Q = p.n_problems;
