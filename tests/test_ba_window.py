@@ -38,11 +38,11 @@ BOUND = {k: 10.0 * v for k, v in MEASURED.items()}
 K_GENERAL = np.array([[525.0, 1.5, 320.0], [0.0, 510.0, 240.0], [0.0, 0.0, 1.0]])
 
 
-def window_problem(seed, F, m, K=K_GENERAL, sig=0.5, rot_sig=5e-3):
+def window_problem(seed, F, m, K=K_GENERAL, sig=0.5, rot_sig=5e-3, far=1.0):
     """F cameras along a gently turning track in front of m points; ragged visibility (each point seen by 2 .. F frames,
     every tenth by one frame only, and those have a prior), priors on about half of the other points, an anchor on
     frame 0 and a scale-fixing prior on frame 1 (ba.cpp:43), no prior on the other frames.  Guesses: the truth perturbed
-    by 5e-3 in translation and points and by rot_sig in rotation."""
+    by 5e-3 in translation and points and by rot_sig in rotation, all times `far` (the same random draws at every factor)."""
     rng = np.random.default_rng(seed)
     X = np.stack([rng.uniform(-2, 2, m), rng.uniform(-1.5, 1.5, m), rng.uniform(4, 9, m)], 1)
     R, t = [Rot.from_rotvec([0.02, -0.1, 0.03]).as_matrix()], [np.array([0.4, -0.1, 0.2])]
@@ -61,11 +61,11 @@ def window_problem(seed, F, m, K=K_GENERAL, sig=0.5, rot_sig=5e-3):
     pcov = np.zeros((m, 9))
     pcov[has_prior] = (np.eye(3) * 1e-2 ** 2).reshape(9)
     cov = np.tile((np.eye(2) * sig ** 2).reshape(4), (m, 1))
-    Xg = X + rng.normal(0, 5e-3, X.shape)
+    Xg = X + far * rng.normal(0, 5e-3, X.shape)
     poses = []
     for f in range(F):
-        Rg = R[f] if f == 0 else R[f] @ Rot.from_rotvec(rng.normal(0, rot_sig, 3)).as_matrix()
-        tg = t[f] if f == 0 else t[f] + rng.normal(0, 5e-3, 3)
+        Rg = R[f] if f == 0 else R[f] @ Rot.from_rotvec(far * rng.normal(0, rot_sig, 3)).as_matrix()
+        tg = t[f] if f == 0 else t[f] + far * rng.normal(0, 5e-3, 3)
         poses.append(np.concatenate([Rg.reshape(9), tg]))
     var = np.zeros((F, 6))
     var[0] = 1e-5
@@ -80,11 +80,38 @@ def as_window(pb):
                 obs=pb["obs"], obs_cov=pb["cov"], obs_valid=pb["valid"])
 
 
-def model_solve(pb, cov=True):
+def full_whiteners(pb):
+    """Cholesky factors of the information matrices of a problem with full covariances: Lo[f] [m, 2, 2] from pb["cov"][f]
+    (None: identity; the two off-diagonal entries averaged, as the device, the host helper and the oracle do) and Lp
+    [m, 3, 3] from pb["pcov"] (None or a first entry <= 0: no prior, zero).  info = L L^T, whitened residual L^T e."""
+    F, m = len(pb["poses"]), len(pb["Xg"])
+    Lo = []
+    for f in range(F):
+        if pb["cov"][f] is None:
+            Lo.append(np.tile(np.eye(2), (m, 1, 1)))
+        else:
+            S = np.asarray(pb["cov"][f], float).reshape(m, 2, 2)
+            Lo.append(np.linalg.cholesky(np.linalg.inv(0.5 * (S + S.transpose(0, 2, 1)))))
+    Lp = np.zeros((m, 3, 3))
+    if pb["pcov"] is not None:
+        S = np.asarray(pb["pcov"], float).reshape(m, 3, 3)
+        has = S[:, 0, 0] > 0
+        Lp[has] = np.linalg.cholesky(np.linalg.inv(0.5 * (S[has] + S[has].transpose(0, 2, 1))))
+    return Lo, Lp
+
+
+def _wt(L, e):
+    return np.einsum("mji,mj->mi", L, e)
+
+
+def model_solve(pb, cov=True, full=False):
     """The F-frame cost of DESIGN.md section 4.7 minimised by scipy (trf, all tolerances 1e-15), as
     test_refine._check_ba_minimiser does for two frames; covariances from inv(J^T J) at the optimum, J by central
-    differences in the local (rotation, translation; right perturbation) parametrisation, as test_refine._check_covariances."""
+    differences in the local (rotation, translation; right perturbation) parametrisation, as test_refine._check_covariances.
+    full: whiten every observation and point prior with the Cholesky factor of its own information matrix (pb["cov"],
+    pb["pcov"]; full_whiteners) instead of the scalars pb["sig"] and 1e-2."""
     F, m = len(pb["poses"]), len(pb["Xg"])
+    Lo, Lp = full_whiteners(pb) if full else (None, None)
     K, sig = pb["K"], pb["sig"]
     Rg = [pb["poses"][f][:9].reshape(3, 3) for f in range(F)]
     tg = [pb["poses"][f][9:] for f in range(F)]
@@ -94,9 +121,15 @@ def model_solve(pb, cov=True):
         r = []
         for f in range(F):
             r += [Rot.from_matrix(Rg[f].T @ Rs[f]).as_rotvec() * wsd[f][:3], Rg[f].T @ (ts[f] - tg[f]) * wsd[f][3:]]
-            e = (tr.proj(K, Rs[f], ts[f], P) - pb["obs"][f]) / sig
-            r.append((e * pb["valid"][f][:, None]).ravel())
-        r.append((((P - pb["Xg"]) / 1e-2) * pb["has_prior"][:, None]).ravel())
+            if full:
+                e = _wt(Lo[f], tr.proj(K, Rs[f], ts[f], P) - pb["obs"][f])
+            else:
+                e = (tr.proj(K, Rs[f], ts[f], P) - pb["obs"][f]) / sig
+            r.append(e.ravel() if pb["valid"][f] is None else (e * pb["valid"][f][:, None]).ravel())
+        if full:
+            r.append(_wt(Lp, P - pb["Xg"]).ravel())
+        else:
+            r.append((((P - pb["Xg"]) / 1e-2) * pb["has_prior"][:, None]).ravel())
         return np.concatenate(r)
 
     def resid(x):
@@ -141,12 +174,13 @@ def _jr_inv(phi):
     return np.eye(3) + 0.5 * S + g * (S @ S)
 
 
-def model_blocks(pb, Rs, ts, P):
+def model_blocks(pb, Rs, ts, P, full=False):
     """The same whitened residual vector as model_solve's, linearised ANALYTICALLY in the local parametrisation (rotation,
     translation; right perturbation) and kept as the blocks of its sparse Jacobian: per frame the prior rows (6 x 6), per
     observation Jc (2 x 6) and Jp (2 x 3), per point the prior rows.  Returns the cost and the blocks of J^T J and J^T r:
-    A (F x 6 x 6), gc (F x 6), D (m x 3 x 3), gp (m x 3), W (F x m x 6 x 3)."""
+    A (F x 6 x 6), gc (F x 6), D (m x 3 x 3), gp (m x 3), W (F x m x 6 x 3).  full: as model_solve."""
     F, m = len(pb["poses"]), len(pb["Xg"])
+    Lo, Lp = full_whiteners(pb) if full else (None, None)
     K, sig = pb["K"], pb["sig"]
     A, gc = np.zeros((F, 6, 6)), np.zeros((F, 6))
     D, gp, W = np.zeros((m, 3, 3)), np.zeros((m, 3)), np.zeros((F, m, 6, 3))
@@ -162,7 +196,7 @@ def model_blocks(pb, Rs, ts, P):
         A[f] += Jpr.T @ Jpr
         gc[f] += Jpr.T @ e
         cost += e @ e
-        v = pb["valid"][f].astype(bool)
+        v = np.ones(m, bool) if pb["valid"][f] is None else pb["valid"][f].astype(bool)
         q = (P[v] - ts[f]) @ Rs[f]
         iz = 1.0 / q[:, 2]
         x, y = q[:, 0] * iz, q[:, 1] * iz
@@ -173,15 +207,27 @@ def model_blocks(pb, Rs, ts, P):
         Sq = np.zeros((len(q), 3, 3))                      # [q]x: q' = q + q x dw
         Sq[:, 0, 1], Sq[:, 0, 2], Sq[:, 1, 0] = -q[:, 2], q[:, 1], q[:, 2]
         Sq[:, 1, 2], Sq[:, 2, 0], Sq[:, 2, 1] = -q[:, 0], -q[:, 1], q[:, 0]
-        Jc = np.concatenate([Aq @ Sq, -Aq], axis=2) / sig  # (n, 2, 6)
-        Jp = (Aq @ Rs[f].T) / sig                          # (n, 2, 3)
-        r = r / sig
+        if full:
+            LT = Lo[f][v].transpose(0, 2, 1)
+            Jc = LT @ np.concatenate([Aq @ Sq, -Aq], axis=2)
+            Jp = LT @ (Aq @ Rs[f].T)
+            r = _wt(Lo[f][v], r)
+        else:
+            Jc = np.concatenate([Aq @ Sq, -Aq], axis=2) / sig  # (n, 2, 6)
+            Jp = (Aq @ Rs[f].T) / sig                          # (n, 2, 3)
+            r = r / sig
         A[f] += np.einsum("nia,nib->ab", Jc, Jc)
         gc[f] += np.einsum("nia,ni->a", Jc, r)
         D[v] += np.einsum("nia,nib->nab", Jp, Jp)
         gp[v] += np.einsum("nia,ni->na", Jp, r)
         W[f][v] = np.einsum("nia,nib->nab", Jc, Jp)
         cost += np.sum(r * r)
+    if full:
+        ep = _wt(Lp, P - pb["Xg"])
+        D += Lp @ Lp.transpose(0, 2, 1)
+        gp += np.einsum("mij,mj->mi", Lp, ep)
+        cost += np.sum(ep * ep)
+        return 0.5 * cost, A, gc, D, gp, W
     hp = pb["has_prior"].astype(float)
     ep = (P - pb["Xg"]) / 1e-2 * hp[:, None]
     D += (hp / 1e-4)[:, None, None] * np.eye(3)
@@ -190,7 +236,7 @@ def model_blocks(pb, Rs, ts, P):
     return 0.5 * cost, A, gc, D, gp, W
 
 
-def model_solve_blocks(pb, cov=True):
+def model_solve_blocks(pb, cov=True, full=False):
     """The minimiser of the same cost by Gauss-Newton on the block-sparse normal equations (points eliminated block by block),
     for sizes where scipy's dense Jacobian is out of reach; steps are halved while the cost does not decrease, and the
     iteration ends two steps after a step stops changing the cost.  Covariances: the blocks of inv(J^T J) by the same
@@ -208,7 +254,7 @@ def model_solve_blocks(pb, cov=True):
             S[6 * f:6 * f + 6, 6 * f:6 * f + 6] += A[f]
         return Di, Y, S
 
-    cur, A, gc, D, gp, W = model_blocks(pb, Rs, ts, P)
+    cur, A, gc, D, gp, W = model_blocks(pb, Rs, ts, P, full)
     guess, flat = cur, 0
     for _ in range(60):
         Di, Y, S = reduce(A, gc, D, gp, W)
@@ -220,7 +266,7 @@ def model_solve_blocks(pb, cov=True):
             Rn = np.stack([Rs[f] @ Rot.from_rotvec(step * dc[f, :3]).as_matrix() for f in range(F)])
             tn = np.stack([ts[f] + Rs[f] @ (step * dc[f, 3:]) for f in range(F)])
             Pn = P + step * dp
-            new = model_blocks(pb, Rn, tn, Pn)
+            new = model_blocks(pb, Rn, tn, Pn, full)
             if new[0] <= cur:
                 moved = True
                 break

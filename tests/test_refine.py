@@ -29,7 +29,9 @@ def proj(K, R, t, X):
     return np.stack([K[0, 0] * xn[:, 0] + K[0, 1] * xn[:, 1] + K[0, 2], K[1, 1] * xn[:, 1] + K[1, 2]], axis=1)
 
 
-def two_view_problem(seed, m, K=None, sig=None, baseline=1.0, depth=(2.0, 4.0)):
+def two_view_problem(seed, m, K=None, sig=None, baseline=1.0, depth=(2.0, 4.0), far=1.0):
+    """far: the factor by which the guess lies further from the truth than the usual (1e-2 rotation, 5e-3 translation and
+    points); the same random draws at every factor"""
     rng = np.random.default_rng(seed)
     K = np.eye(3) if K is None else K
     f = K[0, 0]
@@ -40,9 +42,9 @@ def two_view_problem(seed, m, K=None, sig=None, baseline=1.0, depth=(2.0, 4.0)):
     p1 = proj(K, np.eye(3), np.zeros(3), X) + rng.normal(0, sig, (m, 2))
     p2 = proj(K, R_true, t_true, X) + rng.normal(0, sig, (m, 2))
     cov = np.tile((np.eye(2) * sig ** 2).reshape(4), (m, 1))
-    Rg = R_true @ Rot.from_rotvec(rng.normal(0, 1e-2, 3)).as_matrix()
-    tg = t_true + rng.normal(0, 5e-3, 3)
-    Xg = X + rng.normal(0, 5e-3, X.shape)
+    Rg = R_true @ Rot.from_rotvec(far * rng.normal(0, 1e-2, 3)).as_matrix()
+    tg = t_true + far * rng.normal(0, 5e-3, 3)
+    Xg = X + far * rng.normal(0, 5e-3, X.shape)
     return dict(K=K, X=X, R_true=R_true, t_true=t_true, p1=p1, p2=p2, cov=cov, Rg=Rg, tg=tg, Xg=Xg, sig=sig)
 
 
@@ -101,10 +103,21 @@ def test_oracle_covariances_match_finite_difference_hessian_at_general_K(name):
     _check_covariances(two_view_problem(2, 10, K=h.K_REFINE[name]))
 
 
-def _check_covariances(pb):
+def _check_covariances(pb, cov1=None, cov2=None):
+    """cov1 / cov2: full 2 x 2 observation covariances [m, 4] per image instead of sig^2 I (the two off-diagonal entries are
+    averaged, as the oracle does); the residuals are then whitened by the Cholesky factor of each information matrix"""
     m = len(pb["Xg"])
-    res = o.sfm_refine(pb["p1"], pb["cov"], pb["p2"], pb["cov"], pb["K"], pb["Rg"], pb["tg"], pb["Xg"])
+    c1, c2 = pb["cov"] if cov1 is None else cov1, pb["cov"] if cov2 is None else cov2
+    res = o.sfm_refine(pb["p1"], c1, pb["p2"], c2, pb["K"], pb["Rg"], pb["tg"], pb["Xg"])
+    assert res["ok"]
     K, Rg, tg, Xg, sig = pb["K"], pb["Rg"], pb["tg"], pb["Xg"], pb["sig"]
+
+    def white(e, cov):
+        if cov is None:
+            return e / sig
+        S = np.asarray(cov, float).reshape(m, 2, 2)
+        L = np.linalg.cholesky(np.linalg.inv(0.5 * (S + S.transpose(0, 2, 1))))   # info = L L^T -> whitened residual L^T e
+        return np.einsum("mji,mj->mi", L, e)
 
     def local(d):  # right perturbation (rotation, translation) at the estimate; camera 1 sits at its anchor
         R0 = Rot.from_rotvec(d[0:3]).as_matrix()
@@ -114,8 +127,8 @@ def _check_covariances(pb):
         P = res["points"] + d[12:].reshape(m, 3)
         return np.concatenate([
             Rot.from_matrix(R0).as_rotvec() / 1e-5, t0 / 1e-5, Rot.from_matrix(Rg.T @ R1).as_rotvec() / 1e-2,
-            Rg.T @ (t1 - tg) / 1e-2, ((P - Xg) / 1e-2).ravel(), ((proj(K, R0, t0, P) - pb["p1"]) / sig).ravel(),
-            ((proj(K, R1, t1, P) - pb["p2"]) / sig).ravel()])
+            Rg.T @ (t1 - tg) / 1e-2, ((P - Xg) / 1e-2).ravel(), white(proj(K, R0, t0, P) - pb["p1"], cov1).ravel(),
+            white(proj(K, R1, t1, P) - pb["p2"], cov2).ravel()])
 
     n, hh = 12 + 3 * m, 1e-6
     J = np.stack([(local(np.eye(n)[k] * hh) - local(-np.eye(n)[k] * hh)) / (2 * hh) for k in range(n)], 1)
@@ -161,7 +174,7 @@ def test_oracle_reference_kat_sfm_refine_L_shape(seed):
     assert np.abs(res["points"] - pb["X"]).max() < 0.025                    # test-sfm.cpp:280-285
 
 
-def pnp_problem(seed, m, K=None):
+def pnp_problem(seed, m, K=None, far=1.0):
     rng = np.random.default_rng(seed)
     K = np.array([[525.0, 0, 320], [0, 525, 240], [0, 0, 1]]) if K is None else K
     X = np.stack([rng.uniform(-1, 1, m), rng.uniform(-1, 1, m), rng.uniform(3, 6, m)], 1)
@@ -173,8 +186,8 @@ def pnp_problem(seed, m, K=None):
     A = rng.normal(0, 1, (m, 3, 3))
     wcov = 1e-4 * (np.eye(3) + 0.2 * (A @ A.transpose(0, 2, 1)))          # full SPD covariances
     Xn = X + np.einsum("mij,mj->mi", np.linalg.cholesky(wcov), rng.normal(0, 1, (m, 3)))
-    Rg = R_true @ Rot.from_rotvec(rng.normal(0, 5e-3, 3)).as_matrix()
-    tg = t_true + rng.normal(0, 5e-3, 3)
+    Rg = R_true @ Rot.from_rotvec(far * rng.normal(0, 5e-3, 3)).as_matrix()
+    tg = t_true + far * rng.normal(0, 5e-3, 3)
     return dict(K=K, X=Xn, wcov=wcov, uv=uv, icov=icov, Rg=Rg, tg=tg, sig=sig, R_true=R_true, t_true=t_true)
 
 
@@ -218,7 +231,7 @@ def test_oracle_cheirality_point_does_not_break_the_solve():
     assert np.abs(res["t"] - pb["t_true"]).max() < 0.05
 
 
-def track_refine_problem(seed, m, n_new, K=None, sig=0.5):
+def track_refine_problem(seed, m, n_new, K=None, sig=0.5, far=1.0):
     """the shape of VisualOdometer::track_refine (front-end/visual-odometer.cpp:618-800): the last frame anchored at its
     own pose, the new frame regularised, tracked points with isotropic priors, n_new new points without any, and each
     frame missing some observations (every point keeps at least one; prior-less points keep both)"""
@@ -238,9 +251,9 @@ def track_refine_problem(seed, m, n_new, K=None, sig=0.5):
         valid[int(rng.integers(0, 2))][i] = 0
     pcov = np.zeros((m, 9))
     pcov[has_prior] = (np.eye(3) * 1e-2 ** 2).reshape(9)
-    Xg = X + rng.normal(0, 5e-3, X.shape)
-    Rbg = Rb @ Rot.from_rotvec(rng.normal(0, 5e-3, 3)).as_matrix()
-    tbg = tb + rng.normal(0, 5e-3, 3)
+    Xg = X + far * rng.normal(0, 5e-3, X.shape)
+    Rbg = Rb @ Rot.from_rotvec(far * rng.normal(0, 5e-3, 3)).as_matrix()
+    tbg = tb + far * rng.normal(0, 5e-3, 3)
     poses = np.stack([np.concatenate([Ra.reshape(9), ta]), np.concatenate([Rbg.reshape(9), tbg])])
     var = np.stack([np.full(6, 1e-5), np.full(6, 1e-2)])     # the reference passes the stddev as the variance (:687-699)
     return dict(K=K, X=X, poses=poses, var=var, Xg=Xg, pcov=pcov, obs=obs, cov=[cov, cov], valid=valid, has_prior=has_prior,
