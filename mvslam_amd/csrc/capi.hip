@@ -325,7 +325,7 @@ static mvs_status ensure_groups(mvs_batch *b, int num_hypotheses)
     g.add(d.xlist, P * Hp);
     g.add(d.clist, 2 * P * Hp);   // the list + its sorted copy
     if (!d.bound) g.add(d.bound, P);
-    if (!d.box) g.add(d.box, P * 8);
+    if (!d.box) g.add(d.box, P * kBoxRec);
     if (!d.mode) g.add(d.mode, P);
     if (!d.dense_n1) g.add(d.dense_n1, P);
     if (!d.ccount) g.add(d.ccount, P);
@@ -1140,7 +1140,7 @@ static BatchDev batch_view(const BatchDev &b, int first, int count, int half)
     v.wgbest += f * b.max_groups;
     v.hyp_F += f * Hp * kHypRec; v.hyp_r32 += f * Hp * kHypRec32;
     v.hyp_okf += f * Hp; v.hyp_cnt += f * Hp;
-    v.bound += f; v.box += f * 8; v.mode += f;
+    v.bound += f; v.box += f * kBoxRec; v.mode += f;
     v.clist += f * Hp; v.clist2 += f * Hp; v.cpos += f * kSortBins;
     v.ccount += f; v.pcount += f; v.dense_n1 += f;
     v.m0list += (size_t)half * ((size_t)b.n_pairs + 1);

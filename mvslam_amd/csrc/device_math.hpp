@@ -484,70 +484,10 @@ MVS_DEV void svd3_full(const double (&A)[3][3], double (&w)[3], double (&U)[3][3
     svd3_full<false, false, false>(A, w, U, Vt, rot, pairs, bad3);
 }
 
-// ---------------------------------------------------------------------------------
-// Philox4x32-10 and the 8-of-M sampler
-// ---------------------------------------------------------------------------------
-MVS_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                           uint32_t (&out)[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        // one 64-bit product each (v_mad_u64_u32) instead of a high and a low 32-bit multiply: full-width integer multiplies
-        // issue at a quarter of the vector rate, and the two Philox calls of a sample were 80 of them
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// idx[k]: k-th draw = slot (w_k * (M - k)) >> 32 among the not yet chosen indices.
-MVS_DEV void sample8(uint64_t seed, uint32_t hyp, int M, int sampler, int (&idx)[8])
-{
-    if (sampler == 0) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            idx[k] = k;
-        return;
-    }
-    uint32_t w[8];
-    {
-        uint32_t o[4];
-        philox4x32_10(hyp, 0u, 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), o);
-        w[0] = o[0]; w[1] = o[1]; w[2] = o[2]; w[3] = o[3];
-        philox4x32_10(hyp, 1u, 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), o);
-        w[4] = o[0]; w[5] = o[1]; w[6] = o[2]; w[7] = o[3];
-    }
-    // sorted[] kept ascending with static indices only
-    int sorted[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-        sorted[k] = 0x7fffffff;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        uint32_t r = __umulhi(w[k], (uint32_t)(M - k));
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-            if (t < k && r >= (uint32_t)sorted[t])
-                ++r;
-        idx[k] = (int)r;
-        // insert r: everything greater shifts up by one
-        int carry = (int)r;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            if (t <= k) {
-                const int cur = sorted[t];
-                const bool sw = carry < cur;
-                sorted[t] = sw ? carry : cur;
-                carry = sw ? cur : carry;
-            }
-        }
-    }
-}
+// Philox4x32-10 and the 8-of-M sampler: sampler.hpp (plain C++, also compiled for the host by tests/cpp/sample8_host.cpp)
+}  // namespace mvs
+#include "sampler.hpp"
+namespace mvs {
 
 // ---------------------------------------------------------------------------------
 // find_fundamental_matrix (vision/fundamental-matrix.cpp:18-54,56-140,204-267)

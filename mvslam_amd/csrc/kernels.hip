@@ -755,10 +755,11 @@ typedef __attribute__((address_space(4))) double CDouble;
 // select         grid P          exact count + residual of everything at or above the bound (ransac_select_kernel)
 __device__ __forceinline__ PairBox load_box(const BatchDev &b, int pair)
 {
-    const double *q = b.box + (size_t)pair * 8;
+    const double *q = b.box + (size_t)pair * kBoxRec;
     PairBox bx;
     bx.x1lo = q[0]; bx.x1hi = q[1]; bx.y1lo = q[2]; bx.y1hi = q[3];
     bx.x2lo = q[4]; bx.x2hi = q[5]; bx.y2lo = q[6]; bx.y2hi = q[7];
+    bx.ax1 = q[8]; bx.ay1 = q[9]; bx.ax2 = q[10]; bx.ay2 = q[11];
     return bx;
 }
 
@@ -828,8 +829,12 @@ __global__ __launch_bounds__(256) void pair_prepare_kernel(BatchDev b, RunParams
         }
         bx.x1lo = q[0]; bx.x1hi = q[1]; bx.y1lo = q[2]; bx.y1hi = q[3];
         bx.x2lo = q[4]; bx.x2hi = q[5]; bx.y2lo = q[6]; bx.y2hi = q[7];
+        box_abs_max(bx);   // every thread, for the probe below; threads 8 .. 11 store them
+        const double a[4] = {bx.ax1, bx.ay1, bx.ax2, bx.ay2};
         if (tid < 8)
-            b.box[(size_t)pair * 8 + tid] = q[tid];
+            b.box[(size_t)pair * kBoxRec + tid] = q[tid];
+        else if (tid < kBoxRec)
+            b.box[(size_t)pair * kBoxRec + tid] = tid == 8 ? a[0] : tid == 9 ? a[1] : tid == 10 ? a[2] : a[3];
     }
     // probe: the first 64 hypotheses of the pair through the pre-screen
     if (w == 0) {
@@ -2267,7 +2272,9 @@ __global__ __launch_bounds__(kSelThreads) void ransac_select_kernel(BatchDev b, 
             int n_ties = 0;
             for (int q0 = 0; q0 < n_list; q0 += kSelThreads) {
                 const int q = q0 + tid;
-                const bool tie = q < n_list && s_cnt[q] == target;
+                // (target < 0: every listed hypothesis was rejected by its exact solve and there is no best yet -- their count
+                // is the marker -1, which must not "tie": a rejected sample is no candidate)
+                const bool tie = q < n_list && target >= 0 && s_cnt[q] == target;
                 const uint32_t hq = q < n_list ? s_list[q] : 0u;
                 const unsigned long long bal = __ballot(tie);
                 if (lane == 0)

@@ -7,6 +7,7 @@
 
 namespace mvs {
 
+constexpr int kBoxRec = 12;          // doubles per pair in BatchDev::box
 constexpr int kMaxKp = 4096;          // capacity limit of one image (LDS lists in finalize/compact)
 constexpr int kSortBins = kMaxKp + 1;  // counts 0 .. kMaxKp (ransac_list_sort_kernel)
 constexpr int kHypPerBlock = 256;     // hypotheses per RANSAC workgroup (one per lane, 4 waves)
@@ -74,7 +75,9 @@ struct BatchDev {
                          // for the exact solve, 3 exact F
     int32_t *hyp_cnt;    // [P][max_groups * 256] full (upper-bound) inlier count of a hypothesis that can still win, -1 otherwise
     int32_t *bound;      // [P] largest full (lower-bound) count seen so far: the pruning bound of the counting kernel
-    double *box;         // [P][8] bounding box of the pair's matches (x1lo, x1hi, y1lo, y1hi, x2lo, x2hi, y2lo, y2hi)
+    double *box;         // [P][kBoxRec] bounding box of the pair's matches (x1lo, x1hi, y1lo, y1hi, x2lo, x2hi, y2lo, y2hi) and
+                         // its absolute maxima max(|lo|, |hi|) per coordinate (x1, y1, x2, y2): what the pre-screen's bounds
+                         // need of the box alone, once per pair instead of once per hypothesis
     int32_t *mode;       // [P] 0: every hypothesis is solved exactly; 1: pre-screened, counted in single precision; 2: pre-
                          // screened, counted in double precision
     uint32_t *clist;     // [P][max_groups * 256] hypotheses of the pair the dense counting phase left alive (for the finish)

@@ -24,7 +24,15 @@ namespace mvs {
 // bounding box of ALL matches of a pair in ideal-camera coordinates (pair_prepare_kernel)
 struct PairBox {
     double x1lo, x1hi, y1lo, y1hi, x2lo, x2hi, y2lo, y2hi;
+    double ax1, ay1, ax2, ay2;   // max(|lo|, |hi|) per coordinate: functions of the box alone (box_abs_max), stored with it
 };
+MVS_DEV void box_abs_max(PairBox &bx)
+{
+    bx.ax1 = fmax(dabs(bx.x1lo), dabs(bx.x1hi));
+    bx.ay1 = fmax(dabs(bx.y1lo), dabs(bx.y1hi));
+    bx.ax2 = fmax(dabs(bx.x2lo), dabs(bx.x2hi));
+    bx.ay2 = fmax(dabs(bx.y2lo), dabs(bx.y2hi));
+}
 
 constexpr double kPsU = 0x1p-53;          // unit roundoff
 constexpr double kPsTauC = 2.0e-12;       // >= 2.001 (8000 u + 8.01 u): <= 1080 Jacobi rotations + forming A^T A
@@ -107,6 +115,35 @@ MVS_DEV bool sample_norm(const double (&px)[8], const double (&py)[8], double &s
     const bool ok = sc > kEps;
     scale = kSqrt2 / sc;
     return ok;
+}
+
+// The same normalisation for a sample whose sixteen q = dx^2 + dy^2 are all normal numbers >= 2^-767 -- every sample of
+// distinct matches: the roots are sqrt_fast's sequence without its 0 / inf select (sqrt_fast_nz_h, by-product dropped: the
+// same bits for such q), and instead of a range test per root the caller gets the running minimum of q.  The caller decides
+// from qmin and the returned sum of roots (NaN here as soon as a q is inf or NaN) whether sample_norm has to be run instead.
+MVS_DEV double sample_norm_nz(const double (&px)[8], const double (&py)[8], double &scale, double &mx, double &my, double &qmin)
+{
+    mx = 0.0;
+    my = 0.0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        mx += px[i];
+        my += py[i];
+    }
+    mx *= 0.125;
+    my *= 0.125;
+    double sc = 0.0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const double dx = px[i] - mx, dy = py[i] - my;
+        const double q = dx * dx + dy * dy;
+        qmin = fmin(qmin, q);
+        double h;
+        sc += sqrt_fast_nz_h(q, h);
+    }
+    sc *= 0.125;
+    scale = kSqrt2 / sc;
+    return sc;
 }
 
 // The rank-2 step of the pre-screen.  G = reshape(n~) (row-major 3x3, ||G||_F = 1).  The exact path takes the 3x3 Jacobi
@@ -241,15 +278,32 @@ MVS_DEV int prescreen_hypothesis(const double *P, int (&idx)[8], double *park, c
 {
     EightNorm nm;
     bool ok, tiny = false;
+    // byte offsets of the sample's points, once for both gathers: an index is below 2^24, so idx * 32 fits 32 bits and a
+    // gather is the wave-uniform base P plus a 32-bit lane offset (no 64-bit address arithmetic per load)
+    uint32_t off[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        off[k] = (uint32_t)idx[k] << 5;
+    const char *Pb = reinterpret_cast<const char *>(P);
     {
         double x1[8], y1[8], x2[8], y2[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const double4 p = *reinterpret_cast<const double4 *>(P + (size_t)idx[k] * 4);
+            const double4 p = *reinterpret_cast<const double4 *>(Pb + off[k]);
             x1[k] = p.x; y1[k] = p.y; x2[k] = p.z; y2[k] = p.w;
         }
-        ok = sample_norm(x1, y1, nm.s1, nm.m1x, nm.m1y, tiny);
-        ok = sample_norm(x2, y2, nm.s2, nm.m2x, nm.m2y, tiny) && ok;
+        // all sixteen roots without their per-root fix-ups; one test on the smallest q (and on the sums, which a q = inf or
+        // NaN turns into NaN) decides whether any lane of the wavefront needs the guarded normalisation instead.  Written
+        // so that a NaN raises the flag
+        double qmin = __builtin_inf();
+        const double sc1 = sample_norm_nz(x1, y1, nm.s1, nm.m1x, nm.m1y, qmin);
+        const double sc2 = sample_norm_nz(x2, y2, nm.s2, nm.m2x, nm.m2y, qmin);
+        ok = (sc1 > kEps) && (sc2 > kEps);
+        const bool redo = !(qmin >= 0x1p-767) || !(sc1 + sc2 < __builtin_inf());
+        if (__builtin_expect(__any(redo), 0)) {   // wave-uniform; never taken for samples of distinct matches
+            ok = sample_norm(x1, y1, nm.s1, nm.m1x, nm.m1y, tiny);
+            ok = sample_norm(x2, y2, nm.s2, nm.m2x, nm.m2y, tiny) && ok;
+        }
     }
     band_out = 0.0;
     e32_out = 0.0;
@@ -269,14 +323,14 @@ MVS_DEV int prescreen_hypothesis(const double *P, int (&idx)[8], double *park, c
         double col[9];
         {
             // a fresh gather: the first one's values must not stay alive across the QR, and the scheduler must not hoist the
-            // later columns above the earlier reflectors (it would rebuild the whole matrix in registers): the index is
+            // later columns above the earlier reflectors (it would rebuild the whole matrix in registers): the offset is
             // made opaque AND tied to the previous reflector's scale
             // ... of the column before the previous one: the gather of column j is in flight while column j - 1 is reduced
             if (j < 2)
-                asm volatile("" : "+v"(idx[j]));
+                asm volatile("" : "+v"(off[j]));
             else
-                asm volatile("" : "+v"(idx[j]) : "v"(beta[j > 1 ? j - 2 : 0]));
-            const double4 p = *reinterpret_cast<const double4 *>(P + (size_t)idx[j] * 4);
+                asm volatile("" : "+v"(off[j]) : "v"(beta[j > 1 ? j - 2 : 0]));
+            const double4 p = *reinterpret_cast<const double4 *>(Pb + off[j]);
             const double a1 = (p.x - nm.m1x) * nm.s1, b1 = (p.y - nm.m1y) * nm.s1;   // normalise8's own operations
             const double a2 = (p.z - nm.m2x) * nm.s2, b2 = (p.w - nm.m2y) * nm.s2;
             // design matrix row (fundamental-matrix.cpp:78-87), the exact path's products
@@ -406,10 +460,10 @@ MVS_DEV int prescreen_hypothesis(const double *P, int (&idx)[8], double *park, c
     const double d1y = fmax(dabs(nm.m1y - bx.y1lo), dabs(nm.m1y - bx.y1hi));
     const double d2x = fmax(dabs(nm.m2x - bx.x2lo), dabs(nm.m2x - bx.x2hi));
     const double d2y = fmax(dabs(nm.m2y - bx.y2lo), dabs(nm.m2y - bx.y2hi));
-    const double e1x = fmax(dabs(bx.x1lo), dabs(bx.x1hi)) + dabs(nm.m1x);
-    const double e1y = fmax(dabs(bx.y1lo), dabs(bx.y1hi)) + dabs(nm.m1y);
-    const double e2x = fmax(dabs(bx.x2lo), dabs(bx.x2hi)) + dabs(nm.m2x);
-    const double e2y = fmax(dabs(bx.y2lo), dabs(bx.y2hi)) + dabs(nm.m2y);
+    const double e1x = bx.ax1 + dabs(nm.m1x);
+    const double e1y = bx.ay1 + dabs(nm.m1y);
+    const double e2x = bx.ax2 + dabs(nm.m2x);
+    const double e2y = bx.ay2 + dabs(nm.m2y);
     const double s1q = nm.s1 * nm.s1, s2q = nm.s2 * nm.s2;
     // N1^2 N2^2 and N1'^2 N2'^2 first, one square root each
     const double n12 = dfma(s1q, dfma(d1x, d1x, d1y * d1y), 1.0) * dfma(s2q, dfma(d2x, d2x, d2y * d2y), 1.0);
@@ -422,8 +476,7 @@ MVS_DEV int prescreen_hypothesis(const double *P, int (&idx)[8], double *park, c
     // chain over the ten k: at most 14):
     // | r32 - r(F~, p) | <= 16 * 2^-24 * T,  T = sum |p2_j| |F_jk| |p1_k| <= [X2 Y2 1] |F~| [X1 Y1 1]^T over the pair's box
     {
-        const double X1 = fmax(dabs(bx.x1lo), dabs(bx.x1hi)), Y1 = fmax(dabs(bx.y1lo), dabs(bx.y1hi));
-        const double X2 = fmax(dabs(bx.x2lo), dabs(bx.x2hi)), Y2 = fmax(dabs(bx.y2lo), dabs(bx.y2hi));
+        const double X1 = bx.ax1, Y1 = bx.ay1, X2 = bx.ax2, Y2 = bx.ay2;
         const double t0 = dfma(X2, dabs(F[0]), dfma(Y2, dabs(F[3]), dabs(F[6])));
         const double t1 = dfma(X2, dabs(F[1]), dfma(Y2, dabs(F[4]), dabs(F[7])));
         const double t2 = dfma(X2, dabs(F[2]), dfma(Y2, dabs(F[5]), dabs(F[8])));
