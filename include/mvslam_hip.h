@@ -37,6 +37,8 @@ extern "C" {
  * point or struct changed */
 /* still 4: mvs_seq_window_params, mvs_seq_window_info, mvs_seq_refine_windows, mvs_seq_window_count and
  * mvs_seq_download_windows are additions (new symbols only) */
+/* still 4: mvs_five_point, mvs_ransac_essential, mvs_two_view_essential and mvs_batch_run_points_essential are additions (new
+ * symbols only): the five-point essential-matrix RANSAC beside the 8-point one */
 #define MVS_ABI_VERSION 4
 
 typedef enum mvs_status {
@@ -163,6 +165,38 @@ mvs_status mvs_ransac_fundamental(mvs_ctx *ctx, const double *p1_xy, const doubl
                                   uint8_t *inlier_mask, int *best_hyp, int *best_count, double *best_residual,
                                   int32_t *count, double *residual);
 
+/* ---- find_essential_matrix under USE_OPENCV_ESSENTIAL_MATRIX (vision/sfm-solve.cpp:42-63; the reference's default build,
+ *      SConstruct:81-82): a calibrated five-point RANSAC with a Sampson-distance threshold of sqrt(max_error_sq).  The reference
+ *      forwards to cv::findEssentialMat, whose arithmetic is not in its tree; this is the build's own, fully specified estimator
+ *      (mvslam_amd/csrc/five_point.hpp, essential5.hip):
+ *        sample   the first five indices of the 8-of-M draw of hypothesis h (MVS_SAMPLER_IDENTITY: matches 0 .. 4); m >= 8 as
+ *                 sfm-solve.cpp:37 asserts;
+ *        solve    Nister's five-point solver: up to ten essential matrices per hypothesis, ordered by ascending root (the ROOT
+ *                 INDEX), each with Frobenius norm sqrt(2) and its largest entry positive;
+ *        score    match i is an inlier iff its squared Sampson distance num / den satisfies den > 0 and
+ *                 num <= max_error_sq * den (binary64, operation order in five_point.hpp);
+ *        select   most inliers; then the smaller residual (ONE sequential binary64 sum of num / den over the inliers, i ascending;
+ *                 estimator-RANSAC.cpp:76-84); then the smaller hypothesis id; then the smaller root index;
+ *        every hypothesis runs: VF_MATCH_CONFIDENCE_LEVEL (sfm-solve.cpp:58) is unused; no refit, no projection (:62-63). ---- */
+
+/* The minimal solver alone.  p1_xy / p2_xy: 5 x (x, y) ideal-camera points.  E_out: [10][9] row-major, rows [*n, 10) zero.
+ * *n = 0 for a degenerate sample; never a non-finite matrix. */
+mvs_status mvs_five_point(mvs_ctx *ctx, const double p1_xy[10], const double p2_xy[10], double E_out[90], int *n);
+
+/* The RANSAC stage alone (the five-point counterpart of mvs_ransac_fundamental).  p1 / p2: m x (x, y) ideal-camera points,
+ * 8 <= m <= 4096 (fewer: MVS_NO_MODEL, more: MVS_ERR_CAPACITY).  Outputs (any may be NULL): E of the winner, inlier_mask[m],
+ * its hypothesis id, root index, inlier count and residual; n_roots[num_hypotheses] and count[num_hypotheses][10] (-1 past
+ * n_roots): the optional per-hypothesis tables. */
+mvs_status mvs_ransac_essential(mvs_ctx *ctx, const double *p1_xy, const double *p2_xy, int m, double max_error_sq,
+                                int num_hypotheses, int sampler, uint64_t seed, double E[9], uint8_t *inlier_mask, int *best_hyp,
+                                int *best_root, int *best_count, double *best_residual, int32_t *n_roots, int32_t *count);
+
+/* sfm_solve (vision/sfm-solve.cpp:285-368) with the five-point branch: arguments and return codes of mvs_two_view.  In the
+ * result F and E both hold the winner (returned as is, sfm-solve.cpp:62-63) and best_hyp is its hypothesis id. */
+mvs_status mvs_two_view_essential(mvs_ctx *ctx, const double *p1_uv, const double *p2_uv, int m, const double K[9],
+                                  const mvs_params *params, double R[9], double t[3], double *points_xyz, int64_t *point_idx,
+                                  int *n_points, uint8_t *inlier_mask, mvs_pair_result *result);
+
 /* pnp_solve(world_points, image_points, K, pose, inlier_point_indexes) (vision/pnp-solve.cpp:16-104, decl pnp.hpp:22-26).
  * The reference forwards to cv::solvePnPRansac(SOLVEPNP_P3P, 100, 0.05, 0.95); this is the build's own P3P-RANSAC
  * (Grunert P3P on 3 points + 1 disambiguation point, reprojection-error inlier count over all points, first
@@ -224,6 +258,12 @@ mvs_status mvs_batch_sync(mvs_batch *b);
  * rows of uv1 / uv2) and cleared match rows. */
 mvs_status mvs_batch_run_points(mvs_batch *b, const mvs_params *params, int n_active, const double *uv1, const double *uv2,
                                 const int32_t *m);
+
+/* mvs_batch_run_points with the five-point branch of find_essential_matrix (mvs_two_view_essential for pairs [0, n_active)):
+ * same arguments, same resident intrinsics and sampler key offsets, followed by the usual mvs_batch_download.  One stream, plain
+ * launches: no half batches, no captured graph. */
+mvs_status mvs_batch_run_points_essential(mvs_batch *b, const mvs_params *params, int n_active, const double *uv1,
+                                          const double *uv2, const int32_t *m);
 
 /* Timed replay: `warmup` untimed + `steps` timed passes over the resident inputs, bracketed by HIP events
  * on the ctx stream.  ms_total: wall ms of the `steps` passes.  ms_kernel[5]: summed ms per kernel over the

@@ -1,6 +1,7 @@
 // Replaces source/vision/sfm-solve.cpp of the reference (sfm_solve :285-368, sfm_triangulate :370-394; decl
-// vision/sfm.hpp:30-53).  Build WITHOUT -DUSE_OPENCV_ESSENTIAL_MATRIX (SConstruct:82): this is the reference's own
-// FundamentalMatrixEstimatorRANSAC branch (:64-90), run on the GPU.
+// vision/sfm.hpp:30-53).  Without -DUSE_OPENCV_ESSENTIAL_MATRIX (SConstruct:82) this is the reference's own
+// FundamentalMatrixEstimatorRANSAC branch (:64-90), run on the GPU; with it (the reference's default build) the calibrated
+// five-point RANSAC that stands in for cv::findEssentialMat (:42-63; mvs_two_view_essential).
 #include <vision/sfm.hpp>
 
 #include <cassert>
@@ -24,7 +25,12 @@ bool sfm_solve(const std::vector<ImagePoint> &p1, const std::vector<ImagePoint> 
     std::vector<int64_t> idx(m);
     int n = 0;
     // cv::Point_<double> is two packed doubles: &p1[0].x is an m x 2 row-major array
+#ifdef USE_OPENCV_ESSENTIAL_MATRIX
+    if (mvs_two_view_essential(hip::context(), &p1[0].x, &p2[0].x, m, Kr, &prm, R, t, pts.data(), idx.data(), &n, nullptr,
+                               nullptr) != MVS_OK)
+#else
     if (mvs_two_view(hip::context(), &p1[0].x, &p2[0].x, m, Kr, &prm, R, t, pts.data(), idx.data(), &n, nullptr, nullptr) != MVS_OK)
+#endif
         return false;                 // < 8 points, no model, < 8 inliers, no candidate with points (:319-356)
     pose2in1_scaled = hip::se3_from_arrays(R, t);
     std::vector<Point3> P(n);

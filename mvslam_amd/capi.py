@@ -155,7 +155,8 @@ EXPORTS = [
     "mvs_batch_gather_results", "mvs_seq_time_stages", "mvs_batch_time_kernels", "mvs_kernel_info_get",
     "mvs_extract_time", "mvs_ctx_set_half_batches", "mvs_batch_device_state", "mvs_batch_run_points",
     "mvs_ba_refine_window", "mvs_ba_refine_windows", "mvs_seq_refine_windows", "mvs_seq_window_count",
-    "mvs_seq_download_windows",
+    "mvs_seq_download_windows", "mvs_five_point", "mvs_ransac_essential", "mvs_two_view_essential",
+    "mvs_batch_run_points_essential",
 ]
 
 
@@ -413,6 +414,54 @@ class Context:
         self._check(st, "mvs_two_view", allow_no_model=True)
         out = self._unpack(res, mask, pts, idx, m)
         out["ok"] = st == MVS_OK
+        return out
+
+    # sfm_solve with find_essential_matrix's five-point branch (USE_OPENCV_ESSENTIAL_MATRIX, sfm-solve.cpp:42-63)
+    def two_view_essential(self, uv1, uv2, K, params):
+        uv1, uv2 = _f64(uv1).reshape(-1, 2), _f64(uv2).reshape(-1, 2)
+        m = len(uv1)
+        R, t = np.zeros(9), np.zeros(3)
+        pts = np.zeros((max(m, 1), 3))
+        idx = np.zeros(max(m, 1), dtype=np.int64)
+        mask = np.zeros(max(m, 1), dtype=np.uint8)
+        n = C.c_int(0)
+        res = PairResult()
+        st = lib().mvs_two_view_essential(self._h, _ptr(uv1, C.c_double), _ptr(uv2, C.c_double), C.c_int(m),
+                                          _ptr(_f64(K, (9,)), C.c_double), C.byref(params), _ptr(R, C.c_double),
+                                          _ptr(t, C.c_double), _ptr(pts, C.c_double), _ptr(idx, C.c_int64), C.byref(n),
+                                          _ptr(mask, C.c_uint8), C.byref(res))
+        self._check(st, "mvs_two_view_essential", allow_no_model=True)
+        out = self._unpack(res, mask, pts, idx, m)
+        out["ok"] = st == MVS_OK
+        out["raw"] = bytes(res)
+        return out
+
+    def five_point(self, p1, p2):
+        """the minimal solver on the device: (n, E[10][3][3]) for 5 x (x, y) ideal-camera points (mvs_five_point)"""
+        p1, p2 = _f64(p1, (10,)), _f64(p2, (10,))
+        E = np.zeros((10, 3, 3))
+        n = C.c_int(0)
+        st = lib().mvs_five_point(self._h, _ptr(p1, C.c_double), _ptr(p2, C.c_double), _ptr(E, C.c_double), C.byref(n))
+        self._check(st, "mvs_five_point")
+        return n.value, E
+
+    def ransac_essential(self, p1, p2, max_error_sq, H, sampler=SAMPLER_PHILOX, seed=0, per_hyp=False):
+        p1, p2 = _f64(p1).reshape(-1, 2), _f64(p2).reshape(-1, 2)
+        m = len(p1)
+        E = np.zeros((3, 3))
+        mask = np.zeros(max(m, 1), dtype=np.uint8)
+        bh, bt, bc, br = C.c_int(-1), C.c_int(-1), C.c_int(0), C.c_double(0)
+        nr = np.zeros(H, dtype=np.int32) if per_hyp else None
+        cnt = np.zeros((H, 10), dtype=np.int32) if per_hyp else None
+        st = lib().mvs_ransac_essential(
+            self._h, _ptr(p1, C.c_double), _ptr(p2, C.c_double), C.c_int(m), C.c_double(max_error_sq), C.c_int(H),
+            C.c_int(sampler), C.c_uint64(seed), _ptr(E, C.c_double), _ptr(mask, C.c_uint8), C.byref(bh), C.byref(bt),
+            C.byref(bc), C.byref(br), _ptr(nr, C.c_int32), _ptr(cnt, C.c_int32))
+        self._check(st, "mvs_ransac_essential", allow_no_model=True)
+        out = dict(ok=st == MVS_OK, E=E, mask=mask[:m], best_hyp=bh.value, best_root=bt.value, best_count=bc.value,
+                   best_residual=br.value)
+        if per_hyp:
+            out["n_roots"], out["count"] = nr, cnt
         return out
 
     # sfm_triangulate with T_1_to_2 composed by the caller
@@ -756,6 +805,22 @@ class Batch:
         st = lib().mvs_batch_run_points(self._h, C.byref(params), C.c_int(count), _ptr(u1, C.c_double), _ptr(u2, C.c_double),
                                         _ptr(m, C.c_int32))
         self.ctx._check(st, "mvs_batch_run_points")
+
+    def run_points_essential(self, params, uv1, uv2, m):
+        """run_points() with the five-point essential-matrix RANSAC in place of the 8-point one (mvs_batch_run_points_essential)"""
+        m = np.ascontiguousarray(m, dtype=np.int32)
+        count, N = len(m), self.max_kp
+
+        def pad(a):
+            a = _f64(a)
+            out = np.zeros((count, N, 2))
+            out[:, :a.shape[1]] = a.reshape(count, -1, 2)
+            return out
+
+        u1, u2 = pad(uv1), pad(uv2)
+        st = lib().mvs_batch_run_points_essential(self._h, C.byref(params), C.c_int(count), _ptr(u1, C.c_double),
+                                                  _ptr(u2, C.c_double), _ptr(m, C.c_int32))
+        self.ctx._check(st, "mvs_batch_run_points_essential")
 
     def device_state(self):
         """opaque bytes of the batch's device-resident state (mvs_batch_device_state): for the diagnostics library's audit"""

@@ -611,8 +611,15 @@ inline bool sfm_solve(const std::vector<ImagePoint> &p1, const std::vector<Image
     double R[9], t[3];
     int n = 0;
     const mvs_params prm = make_params_();
+#ifdef MVSLAM_USE_ESSENTIAL_5POINT
+    // find_essential_matrix's five-point branch (sfm-solve.cpp:42-63 under USE_OPENCV_ESSENTIAL_MATRIX, the reference's default
+    // build): the same tail behind a calibrated five-point RANSAC
+    const mvs_status st = mvs_two_view_essential(hip::context(), m ? &p1[0].x : nullptr, m ? &p2[0].x : nullptr, m, K.data(),
+                                                 &prm, R, t, pts.data(), idx.data(), &n, nullptr, nullptr);
+#else
     const mvs_status st = mvs_two_view(hip::context(), m ? &p1[0].x : nullptr, m ? &p2[0].x : nullptr, m, K.data(), &prm,
                                        R, t, pts.data(), idx.data(), &n, nullptr, nullptr);
+#endif
     hip::check(st, "sfm_solve");
     if (st != MVS_OK)
         return false;
@@ -932,10 +939,34 @@ public:
         std::vector<double> pts(3 * (size_t)nq);
         std::vector<int64_t> idx(nq);
         mvs_pair_result res;
+#ifdef MVSLAM_USE_ESSENTIAL_5POINT
+        // reconstruct() with sfm_solve's five-point branch: the reference's own two calls (image-pair.cpp:57-65,116-174),
+        // match -> gather on the host -> mvs_two_view_essential (the one-pass mvs_image_pair is the 8-point path)
+        int nm = 0;
+        mvs_status st = (int)vb.size() >= 2 && nq >= 1
+                            ? mvs_match_hamming(hip::context(), vb.get_descriptors().data.data(), (int)vb.size(),
+                                                vp.get_descriptors().data.data(), nq, vb.get_descriptors().cols, prm.ratio,
+                                                prm.max_dist, matches.data(), &nm)
+                            : MVS_NO_MODEL;
+        if (st == MVS_OK) {
+            std::vector<double> u1(2 * (size_t)(nm ? nm : 1)), u2(2 * (size_t)(nm ? nm : 1));
+            for (int k = 0; k < nm; ++k) {
+                u1[2 * k] = kb[2 * matches[k].trainIdx];
+                u1[2 * k + 1] = kb[2 * matches[k].trainIdx + 1];
+                u2[2 * k] = kq[2 * matches[k].queryIdx];
+                u2[2 * k + 1] = kq[2 * matches[k].queryIdx + 1];
+            }
+            int npts = 0;
+            st = nm >= 1 ? mvs_two_view_essential(hip::context(), u1.data(), u2.data(), nm, K.data(), &prm, nullptr, nullptr,
+                                                  pts.data(), idx.data(), &npts, nullptr, &res)
+                         : MVS_NO_MODEL;
+        }
+#else
         const mvs_status st = mvs_image_pair(hip::context(), vb.get_descriptors().data.data(), kb.data(), (int)vb.size(),
                                              vp.get_descriptors().data.data(), kq.data(), nq, vb.get_descriptors().cols,
                                              K.data(), &prm, &res, matches.data(), nullptr,
                                              pts.data(), idx.data());
+#endif
         hip::check(st, "ImagePair");
         valid = st == MVS_OK;
         if (valid) {

@@ -48,7 +48,7 @@ struct mvs_ctx {
     mvs_batch *scratch = nullptr;  // batch of one pair backing the single-shot entry points
     // workspaces, freed by their destructors
     DevWorkspace uv;          // image points of a single-shot call: [max_kp][2] of camera 1, then the same of camera 2
-    DevWorkspace small;       // 64 doubles of staging (fundamental_kernel)
+    DevWorkspace small;       // 128 doubles of staging (fundamental_kernel, five_point_kernel)
     DevWorkspace single;      // gathered outputs of a single-shot call (one device-to-host copy)
     DevWorkspace single_in;   // packed inputs of mvs_image_pair (one host-to-device copy)
     DevWorkspace pnp;         // pnp_solve workspace
@@ -80,6 +80,11 @@ struct mvs_batch {
     int hyp_table_cap = 0;
     int32_t *hyp_table_count = nullptr;
     double *hyp_table_residual = nullptr;
+    // tables of the five-point RANSAC (essential5.hip), sized for the largest hypothesis count seen so far (first use)
+    int e5_cap = 0;
+    int32_t *e5_nroots = nullptr;   // [n_pairs][e5_cap]
+    int32_t *e5_count = nullptr;    // [n_pairs][e5_cap][10]
+    int32_t *e5_root = nullptr;     // [n_pairs] root index of the winner
     hipEvent_t ev[8]{};
     RefineDev refine{};     // allocated by the first mvs_batch_refine
     bool refine_ran = false;
@@ -834,7 +839,9 @@ mvs_status mvs_ctx_create_on_stream(int device_id, void *hip_stream, mvs_ctx **o
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && cus > 0)
             c->cu_count = cus;
         const hipError_t e1 = hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device_id);
-        const hipError_t e2 = e1 == hipSuccess && lds >= 160 * 1024 ? prepare_kernels() : hipErrorInvalidDevice;
+        hipError_t e2 = e1 == hipSuccess && lds >= 160 * 1024 ? prepare_kernels() : hipErrorInvalidDevice;
+        if (e2 == hipSuccess)
+            e2 = essential5_prepare();
         if (e2 != hipSuccess) {
             std::fprintf(stderr, "mvs_ctx_create: device %d offers %d bytes of LDS per workgroup (%s); this library is built "
                                  "for gfx950 (160 KB)\n", device_id, lds, hipGetErrorString(e1 != hipSuccess ? e1 : e2));
@@ -844,7 +851,7 @@ mvs_status mvs_ctx_create_on_stream(int device_id, void *hip_stream, mvs_ctx **o
             return MVS_ERR_NO_DEVICE;
         }
     }
-    if (ws_grow(c, c->small, 64 * sizeof(double)) != MVS_OK ||
+    if (ws_grow(c, c->small, 128 * sizeof(double)) != MVS_OK ||
         hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
@@ -1266,6 +1273,63 @@ mvs_status mvs_batch_run_points(mvs_batch *b, const mvs_params *params, int n_ac
     b->d.hyp_count = nullptr;
     b->d.hyp_residual = nullptr;
     return enqueue_pipeline(b, to_run(*params), n_active, false, nullptr, nullptr, false);
+}
+
+// the tables of the five-point stage: one group, so a failed allocation leaves the batch as it was
+static mvs_status ensure_e5(mvs_batch *b, int num_hypotheses)
+{
+    if (num_hypotheses <= b->e5_cap)
+        return MVS_OK;
+    HIP_TRY(b->ctx, sync_stream(b->ctx));
+    const size_t P = (size_t)b->d.n_pairs, H = (size_t)num_hypotheses;
+    DevGroup g(b->ctx, b->blocks);
+    g.add(b->e5_nroots, P * H);
+    g.add(b->e5_count, P * H * kE5MaxRoots);
+    if (!b->e5_root) g.add(b->e5_root, P);
+    const mvs_status st = g.commit();
+    if (st != MVS_OK)
+        return st;
+    b->e5_cap = num_hypotheses;
+    return MVS_OK;
+}
+
+// mvs_batch_run_points with find_essential_matrix's five-point branch (sfm-solve.cpp:42-63) in place of the 8-point RANSAC:
+// normalise -> five-point RANSAC (essential5.hip) -> decomposition -> triangulation, plain launches on the one stream (no half
+// batches, no captured graph).
+mvs_status mvs_batch_run_points_essential(mvs_batch *b, const mvs_params *params, int n_active, const double *uv1,
+                                          const double *uv2, const int32_t *m)
+{
+    if (!b || !uv1 || !uv2 || !m || n_active < 1 || n_active > b->d.n_pairs)
+        return MVS_ERR_INVALID_ARG;
+    mvs_status st = check_params(params);
+    if (st != MVS_OK)
+        return st;
+    const size_t N = (size_t)b->d.max_kp;
+    for (int p = 0; p < n_active; ++p)
+        if (m[p] < 0 || m[p] > (int)N)
+            return MVS_ERR_CAPACITY;
+    mvs_ctx *ctx = b->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((st = ensure_e5(b, params->num_hypotheses)) != MVS_OK)
+        return st;
+    if (!b->uv1) {   // staging for the image points, allocated on first use and owned by the batch
+        const size_t count = (size_t)b->d.n_pairs * N * 2;
+        if ((st = DevGroup(ctx, b->blocks).add(b->uv1, count).add(b->uv2, count).commit()) != MVS_OK)
+            return st;
+    }
+    hipStream_t s = ctx->stream;
+    const size_t pb = (size_t)n_active * N * 2 * sizeof(double);
+    HIP_TRY(ctx, hipMemcpyAsync(b->uv1, uv1, pb, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(b->uv2, uv2, pb, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(b->d.M, m, (size_t)n_active * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(b->d.matches, 0, (size_t)n_active * N * sizeof(mvs_match), s));
+    HIP_TRY(ctx, sync_stream(ctx));   // the host buffers are the caller's again (as in mvs_batch_run_points)
+    launch_prep_points(b->d, b->uv1, b->uv2, n_active, s);
+    const RunParams rp = to_run(*params);
+    launch_essential5(b->d, rp, n_active, b->e5_nroots, b->e5_count, b->e5_cap, b->e5_root, s);
+    launch_finalize(b->d, rp, n_active, kFinalizeEssential, s);
+    HIP_TRY(ctx, hipGetLastError());
+    return MVS_OK;
 }
 
 mvs_status mvs_batch_sync(mvs_batch *b)
@@ -2049,6 +2113,141 @@ mvs_status mvs_ransac_fundamental(mvs_ctx *ctx, const double *p1_xy, const doubl
     if (st != MVS_OK)
         return st;
     if (F) std::memcpy(F, res.F, sizeof(res.F));
+    if (best_hyp) *best_hyp = res.best_hyp;
+    if (best_count) *best_count = res.best_count;
+    if (best_residual) *best_residual = res.best_residual;
+    return res.best_count > 0 ? MVS_OK : MVS_NO_MODEL;  // estimator-RANSAC.cpp:89
+}
+
+// sfm_solve with find_essential_matrix's five-point branch (sfm-solve.cpp:42-63,285-368): mvs_two_view with the five-point
+// RANSAC of essential5.hip in front of the same tail.  No refit and no projection: F and E of the result both hold the winner.
+mvs_status mvs_two_view_essential(mvs_ctx *ctx, const double *p1_uv, const double *p2_uv, int m, const double K[9],
+                                  const mvs_params *params, double R[9], double t[3], double *points_xyz, int64_t *point_idx,
+                                  int *n_points, uint8_t *inlier_mask, mvs_pair_result *result)
+{
+    if (!ctx || !p1_uv || !p2_uv || !K || m < 0)
+        return MVS_ERR_INVALID_ARG;
+    mvs_status st = check_params(params);
+    if (st != MVS_OK)
+        return st;
+    if (n_points)
+        *n_points = 0;
+    mvs_pair_result res;
+    std::memset(&res, 0, sizeof(res));
+    res.best_hyp = -1;
+    res.n_matches = m;
+    if (m < 8) {  // sfm-solve.cpp:37 asserts
+        if (result)
+            *result = res;
+        return m < 1 ? MVS_ERR_INVALID_ARG : MVS_NO_MODEL;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = stage_points(ctx, p1_uv, p2_uv, m, K);
+    if (st != MVS_OK)
+        return st;
+    mvs_batch *b = ctx->scratch;
+    if ((st = ensure_e5(b, params->num_hypotheses)) != MVS_OK)
+        return st;
+    const RunParams rp = to_run(*params);
+    launch_essential5(b->d, rp, 1, b->e5_nroots, b->e5_count, b->e5_cap, b->e5_root, ctx->stream);
+    launch_finalize(b->d, rp, 1, kFinalizeEssential, ctx->stream);
+    st = fetch_single(ctx, m, &res, points_xyz, point_idx, inlier_mask);
+    if (st != MVS_OK)
+        return st;
+    if (result)
+        *result = res;
+    if (!res.valid)
+        return MVS_NO_MODEL;
+    if (R) std::memcpy(R, res.R, sizeof(res.R));
+    if (t) std::memcpy(t, res.t, sizeof(res.t));
+    if (n_points) *n_points = res.n_points;
+    return MVS_OK;
+}
+
+// The minimal solver on the device (five_point.hpp): what cv::findEssentialMat runs per sample.
+mvs_status mvs_five_point(mvs_ctx *ctx, const double p1_xy[10], const double p2_xy[10], double E_out[90], int *n)
+{
+    if (!ctx || !p1_xy || !p2_xy || !E_out || !n)
+        return MVS_ERR_INVALID_ARG;
+    *n = 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    double *d = ctx->small.ptr<double>();  // [0,10) p1, [10,20) p2, [20,110) E, [110] n (as int)
+    HIP_TRY(ctx, hipMemcpyAsync(d, p1_xy, 10 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d + 10, p2_xy, 10 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    launch_five_point(d, d + 10, d + 20, reinterpret_cast<int *>(d + 110), s);
+    HIP_TRY(ctx, sync_stream(ctx));
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpy(E_out, d + 20, 90 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(n, d + 110, sizeof(int), hipMemcpyDeviceToHost));
+    return MVS_OK;
+}
+
+// The RANSAC stage alone on ideal-camera points (the five-point counterpart of mvs_ransac_fundamental).
+mvs_status mvs_ransac_essential(mvs_ctx *ctx, const double *p1_xy, const double *p2_xy, int m, double max_error_sq,
+                                int num_hypotheses, int sampler, uint64_t seed, double E[9], uint8_t *inlier_mask, int *best_hyp,
+                                int *best_root, int *best_count, double *best_residual, int32_t *n_roots, int32_t *count)
+{
+    if (!ctx || !p1_xy || !p2_xy || m < 0 || num_hypotheses < 1 ||
+        (sampler != MVS_SAMPLER_IDENTITY && sampler != MVS_SAMPLER_PHILOX))
+        return MVS_ERR_INVALID_ARG;
+    if (!(max_error_sq > 2.220446049250313e-16))  // estimator-RANSAC.cpp:12
+        return MVS_ERR_INVALID_ARG;
+    if (best_hyp) *best_hyp = -1;
+    if (best_root) *best_root = -1;
+    if (best_count) *best_count = 0;
+    if (best_residual) *best_residual = 0.0;
+    if (m < 8)
+        return MVS_NO_MODEL;  // sfm-solve.cpp:37
+    if (m > kMaxKp)
+        return MVS_ERR_CAPACITY;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int desc_bytes = ctx->scratch ? ctx->scratch->d.desc_words * 4 : 32;
+    mvs_status st = ensure_scratch(ctx, m, desc_bytes);
+    if (st != MVS_OK)
+        return st;
+    mvs_batch *b = ctx->scratch;
+    if ((st = ensure_e5(b, num_hypotheses)) != MVS_OK)
+        return st;
+    hipStream_t s = ctx->stream;
+    std::vector<double> packed((size_t)m * 4);  // ideal-camera points are already normalised: pure packing
+    for (int i = 0; i < m; ++i) {
+        packed[4 * i] = p1_xy[2 * i];
+        packed[4 * i + 1] = p1_xy[2 * i + 1];
+        packed[4 * i + 2] = p2_xy[2 * i];
+        packed[4 * i + 3] = p2_xy[2 * i + 1];
+    }
+    const int32_t M = m;
+    const int64_t zero = 0;
+    const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if ((st = pin_begin(ctx, packed.size() * sizeof(double) + 2048 + single_layout(b->d.max_kp, 15).total + 512)) != MVS_OK)
+        return st;
+    if ((st = up_async(ctx, b->d.pts, packed.data(), packed.size() * sizeof(double))) != MVS_OK) return st;
+    if ((st = up_async(ctx, b->d.M, &M, sizeof(M))) != MVS_OK) return st;
+    if ((st = up_async(ctx, const_cast<int64_t *>(b->d.gidx), &zero, sizeof(zero))) != MVS_OK) return st;
+    if ((st = up_async(ctx, const_cast<double *>(b->d.K), eye, sizeof(eye))) != MVS_OK) return st;
+    if ((st = up_async(ctx, const_cast<double *>(b->d.Kinv), eye, sizeof(eye))) != MVS_OK) return st;
+    RunParams rp{};
+    rp.max_error_sq = max_error_sq;
+    rp.num_hypotheses = num_hypotheses;
+    rp.sampler = sampler;
+    rp.seed = seed;
+    rp.min_inliers = 0x7fffffff;  // stop after the mask: no decomposition / triangulation wanted here
+    launch_essential5(b->d, rp, 1, b->e5_nroots, b->e5_count, b->e5_cap, b->e5_root, s);
+    launch_finalize(b->d, rp, 1, kFinalizeEssential, s);
+    mvs_pair_result res;
+    st = fetch_single(ctx, m, &res, nullptr, nullptr, inlier_mask);
+    if (st != MVS_OK)
+        return st;
+    const size_t H = (size_t)num_hypotheses;
+    if (n_roots)
+        HIP_TRY(ctx, hipMemcpy(n_roots, b->e5_nroots, H * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (count)
+        HIP_TRY(ctx, hipMemcpy(count, b->e5_count, H * kE5MaxRoots * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (best_root)
+        HIP_TRY(ctx, hipMemcpy(best_root, b->e5_root, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (E) std::memcpy(E, res.E, sizeof(res.E));
     if (best_hyp) *best_hyp = res.best_hyp;
     if (best_count) *best_count = res.best_count;
     if (best_residual) *best_residual = res.best_residual;

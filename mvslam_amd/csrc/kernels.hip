@@ -2640,9 +2640,11 @@ __global__ __launch_bounds__(kFinThreads) void finalize_model_kernel(BatchDev b,
         res->valid = 0;
         res->n_matches = M;
         res->n_points = 0;
-        res->best_hyp = -1;
-        res->best_count = 0;
-        res->best_residual = 0.0;
+        if (mode != kFinalizeEssential) {   // (there the selection of essential5.hip has written the three)
+            res->best_hyp = -1;
+            res->best_count = 0;
+            res->best_residual = 0.0;
+        }
     }
 
     // ---- ordered inlier list ----
@@ -2677,10 +2679,12 @@ __global__ __launch_bounds__(kFinThreads) void finalize_model_kernel(BatchDev b,
             }
             // compute() returns best_count > 0 (estimator-RANSAC.cpp:89); sfm_solve needs >= min inliers (:330)
             go = (res->best_count > 0) && (n_inl >= rp.min_inliers);
-        } else if (mode == kFinalizeFromE) {
+        } else if (mode == kFinalizeFromE || mode == kFinalizeEssential) {
 #pragma unroll
             for (int k = 0; k < 9; ++k)
                 s_E[k] = res->E[k];
+            if (mode == kFinalizeEssential)   // the same gate as behind the 8-point RANSAC (sfm-solve.cpp:330)
+                go = (res->best_count > 0) && (n_inl >= rp.min_inliers);
         }
         if (mode == kFinalizeTriangulate) {
             double R[3][3];

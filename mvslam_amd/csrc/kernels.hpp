@@ -113,7 +113,9 @@ struct BatchDev {
 enum FinalizeMode : int {
     kFinalizeFull = 0,      // reduce wgbest -> F -> mask -> E -> decompose -> triangulate -> pose
     kFinalizeFromE = 1,     // results[p].E and mask are given
-    kFinalizeTriangulate = 2  // results[p].R1to2 / t1to2 given, mask given; one candidate
+    kFinalizeTriangulate = 2, // results[p].R1to2 / t1to2 given, mask given; one candidate
+    kFinalizeEssential = 3    // as kFinalizeFromE, behind the five-point RANSAC (essential5.hip): its selection has also written
+                              // best_hyp / best_count / best_residual / F, which are kept, and sfm_solve's inlier gate applies
 };
 
 struct RunParams {
@@ -457,5 +459,19 @@ hipError_t launch_audit(const BatchDev &b, const RunParams &rp, int n_active, in
                         hipStream_t stream);
 #endif
 void launch_fundamental(const double *p1, const double *p2, double *F, int *ok, hipStream_t stream);
+
+// ---- five-point essential-matrix RANSAC (essential5.hip) ----------------------------------------
+constexpr int kE5MaxRoots = 10;      // models of one hypothesis (five_point.hpp)
+constexpr int kE5HypPerBlock = 64;   // hypotheses per workgroup of the solve + count kernel: one per lane of its one wavefront
+// opt-in to the kernels' LDS workspaces (> 64 KB), once per device
+hipError_t essential5_prepare();
+// pairs [0, n_active): every hypothesis solved and counted on the pair's resident normalised points, then the selection, which
+// writes results[p].{best_hyp, best_count, best_residual, F, E} and the mask (rows past M cleared); launch_finalize with
+// kFinalizeEssential completes the record.  n_roots: [P][h_stride], count: [P][h_stride][10] (-1 past n_roots);
+// best_root: [P] root index of the winner (-1: none)
+void launch_essential5(const BatchDev &b, const RunParams &rp, int n_active, int32_t *n_roots, int32_t *count, int h_stride,
+                       int32_t *best_root, hipStream_t stream);
+// the minimal solver alone: p1 / p2 5 x (x, y), E [10][9], n
+void launch_five_point(const double *p1, const double *p2, double *E, int *n, hipStream_t stream);
 
 }  // namespace mvs
