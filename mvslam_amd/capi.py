@@ -397,42 +397,33 @@ class Context:
         out["point_idx"] = idx[:n].copy()
         return out
 
-    # sfm_solve(p1, p2, K, pose2in1, points, point_indexes)
-    def two_view(self, uv1, uv2, K, params):
+    def _pose_call(self, name, uv1, uv2, K, head=(), mid=(), mask_out=True):
+        """the calls that return a pose share one argument shape:
+        name(ctx, *head, uv1, uv2, m, K, *mid, R, t, points, point_idx, n_points, [inlier_mask,] result)"""
         uv1, uv2 = _f64(uv1).reshape(-1, 2), _f64(uv2).reshape(-1, 2)
         m = len(uv1)
         R, t = np.zeros(9), np.zeros(3)
         pts = np.zeros((max(m, 1), 3))
         idx = np.zeros(max(m, 1), dtype=np.int64)
-        mask = np.zeros(max(m, 1), dtype=np.uint8)
+        mask = np.zeros(max(m, 1), dtype=np.uint8) if mask_out else None
         n = C.c_int(0)
         res = PairResult()
-        st = lib().mvs_two_view(self._h, _ptr(uv1, C.c_double), _ptr(uv2, C.c_double), C.c_int(m),
-                                _ptr(_f64(K, (9,)), C.c_double), C.byref(params), _ptr(R, C.c_double),
-                                _ptr(t, C.c_double), _ptr(pts, C.c_double), _ptr(idx, C.c_int64), C.byref(n),
-                                _ptr(mask, C.c_uint8), C.byref(res))
-        self._check(st, "mvs_two_view", allow_no_model=True)
+        tail = (_ptr(mask, C.c_uint8), C.byref(res)) if mask_out else (C.byref(res),)
+        st = getattr(lib(), name)(self._h, *head, _ptr(uv1, C.c_double), _ptr(uv2, C.c_double), C.c_int(m),
+                                  _ptr(_f64(K, (9,)), C.c_double), *mid, _ptr(R, C.c_double), _ptr(t, C.c_double),
+                                  _ptr(pts, C.c_double), _ptr(idx, C.c_int64), C.byref(n), *tail)
+        self._check(st, name, allow_no_model=True)
         out = self._unpack(res, mask, pts, idx, m)
         out["ok"] = st == MVS_OK
-        return out
+        return out, res
+
+    # sfm_solve(p1, p2, K, pose2in1, points, point_indexes)
+    def two_view(self, uv1, uv2, K, params):
+        return self._pose_call("mvs_two_view", uv1, uv2, K, mid=(C.byref(params),))[0]
 
     # sfm_solve with find_essential_matrix's five-point branch (USE_OPENCV_ESSENTIAL_MATRIX, sfm-solve.cpp:42-63)
     def two_view_essential(self, uv1, uv2, K, params):
-        uv1, uv2 = _f64(uv1).reshape(-1, 2), _f64(uv2).reshape(-1, 2)
-        m = len(uv1)
-        R, t = np.zeros(9), np.zeros(3)
-        pts = np.zeros((max(m, 1), 3))
-        idx = np.zeros(max(m, 1), dtype=np.int64)
-        mask = np.zeros(max(m, 1), dtype=np.uint8)
-        n = C.c_int(0)
-        res = PairResult()
-        st = lib().mvs_two_view_essential(self._h, _ptr(uv1, C.c_double), _ptr(uv2, C.c_double), C.c_int(m),
-                                          _ptr(_f64(K, (9,)), C.c_double), C.byref(params), _ptr(R, C.c_double),
-                                          _ptr(t, C.c_double), _ptr(pts, C.c_double), _ptr(idx, C.c_int64), C.byref(n),
-                                          _ptr(mask, C.c_uint8), C.byref(res))
-        self._check(st, "mvs_two_view_essential", allow_no_model=True)
-        out = self._unpack(res, mask, pts, idx, m)
-        out["ok"] = st == MVS_OK
+        out, res = self._pose_call("mvs_two_view_essential", uv1, uv2, K, mid=(C.byref(params),))
         out["raw"] = bytes(res)
         return out
 
@@ -479,22 +470,9 @@ class Context:
         return pts[:n.value].copy(), idx[:n.value].copy()
 
     def recover_pose(self, E, uv1, uv2, K, mask=None):
-        uv1, uv2 = _f64(uv1).reshape(-1, 2), _f64(uv2).reshape(-1, 2)
-        m = len(uv1)
-        R, t = np.zeros(9), np.zeros(3)
-        pts = np.zeros((max(m, 1), 3))
-        idx = np.zeros(max(m, 1), dtype=np.int64)
-        n = C.c_int(0)
-        res = PairResult()
         mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
-        st = lib().mvs_recover_pose(self._h, _ptr(_f64(E, (9,)), C.c_double), _ptr(uv1, C.c_double),
-                                    _ptr(uv2, C.c_double), C.c_int(m), _ptr(_f64(K, (9,)), C.c_double),
-                                    _ptr(mk, C.c_uint8), _ptr(R, C.c_double), _ptr(t, C.c_double),
-                                    _ptr(pts, C.c_double), _ptr(idx, C.c_int64), C.byref(n), C.byref(res))
-        self._check(st, "mvs_recover_pose", allow_no_model=True)
-        out = self._unpack(res, None, pts, idx, m)
-        out["ok"] = st == MVS_OK
-        return out
+        return self._pose_call("mvs_recover_pose", uv1, uv2, K, head=(_ptr(_f64(E, (9,)), C.c_double),),
+                               mid=(_ptr(mk, C.c_uint8),), mask_out=False)[0]
 
     # pnp_solve(world_points, image_points, K, pose, inlier_point_indexes)
     def pnp_solve(self, world_xyz, image_uv, K, params):
@@ -790,8 +768,7 @@ class Batch:
                                     _ptr(K, C.c_double), _ptr(gi, C.c_int64))
         self.ctx._check(st, "mvs_batch_upload")
 
-    def run_points(self, params, uv1, uv2, m):
-        """a batch of sfm_solve calls on matched image points: uv1 / uv2 [count][<= max_kp][2], m [count] (mvs_batch_run_points)"""
+    def _run_points(self, name, params, uv1, uv2, m):
         m = np.ascontiguousarray(m, dtype=np.int32)
         count, N = len(m), self.max_kp
 
@@ -802,25 +779,17 @@ class Batch:
             return out
 
         u1, u2 = pad(uv1), pad(uv2)
-        st = lib().mvs_batch_run_points(self._h, C.byref(params), C.c_int(count), _ptr(u1, C.c_double), _ptr(u2, C.c_double),
-                                        _ptr(m, C.c_int32))
-        self.ctx._check(st, "mvs_batch_run_points")
+        st = getattr(lib(), name)(self._h, C.byref(params), C.c_int(count), _ptr(u1, C.c_double), _ptr(u2, C.c_double),
+                                  _ptr(m, C.c_int32))
+        self.ctx._check(st, name)
+
+    def run_points(self, params, uv1, uv2, m):
+        """a batch of sfm_solve calls on matched image points: uv1 / uv2 [count][<= max_kp][2], m [count] (mvs_batch_run_points)"""
+        self._run_points("mvs_batch_run_points", params, uv1, uv2, m)
 
     def run_points_essential(self, params, uv1, uv2, m):
         """run_points() with the five-point essential-matrix RANSAC in place of the 8-point one (mvs_batch_run_points_essential)"""
-        m = np.ascontiguousarray(m, dtype=np.int32)
-        count, N = len(m), self.max_kp
-
-        def pad(a):
-            a = _f64(a)
-            out = np.zeros((count, N, 2))
-            out[:, :a.shape[1]] = a.reshape(count, -1, 2)
-            return out
-
-        u1, u2 = pad(uv1), pad(uv2)
-        st = lib().mvs_batch_run_points_essential(self._h, C.byref(params), C.c_int(count), _ptr(u1, C.c_double),
-                                                  _ptr(u2, C.c_double), _ptr(m, C.c_int32))
-        self.ctx._check(st, "mvs_batch_run_points_essential")
+        self._run_points("mvs_batch_run_points_essential", params, uv1, uv2, m)
 
     def device_state(self):
         """opaque bytes of the batch's device-resident state (mvs_batch_device_state): for the diagnostics library's audit"""

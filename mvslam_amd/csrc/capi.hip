@@ -346,6 +346,53 @@ static mvs_status ensure_groups(mvs_batch *b, int num_hypotheses)
     return MVS_OK;
 }
 
+// the tables of the five-point stage: one group, so a failed allocation leaves the batch as it was
+static mvs_status ensure_e5(mvs_batch *b, int num_hypotheses)
+{
+    if (num_hypotheses <= b->e5_cap)
+        return MVS_OK;
+    HIP_TRY(b->ctx, sync_stream(b->ctx));
+    const size_t P = (size_t)b->d.n_pairs, H = (size_t)num_hypotheses;
+    DevGroup g(b->ctx, b->blocks);
+    g.add(b->e5_nroots, P * H);
+    g.add(b->e5_count, P * H * kE5MaxRoots);
+    if (!b->e5_root) g.add(b->e5_root, P);
+    const mvs_status st = g.commit();
+    if (st != MVS_OK)
+        return st;
+    b->e5_cap = num_hypotheses;
+    return MVS_OK;
+}
+
+// The model stage in front of the shared tail (decomposition, triangulation): the 8-point RANSAC of kernels.hip or the
+// five-point one of essential5.hip.  Everything the two differ in on the host is in the two functions below.
+enum class Estimator { kEightPoint, kFivePoint };
+
+static mvs_status ensure_tables(mvs_batch *b, Estimator est, int num_hypotheses)
+{
+    switch (est) {
+    case Estimator::kEightPoint: return ensure_groups(b, num_hypotheses);
+    case Estimator::kFivePoint: return ensure_e5(b, num_hypotheses);
+    }
+    return MVS_ERR_INVALID_ARG;
+}
+
+// model stage + its finalize mode for pairs [0, n) on the ctx stream, plain launches (the tables are grown: ensure_tables)
+static void enqueue_model(mvs_batch *b, Estimator est, const RunParams &rp, int n)
+{
+    hipStream_t s = b->ctx->stream;
+    switch (est) {
+    case Estimator::kEightPoint:
+        launch_ransac(b->d, rp, n, false, s);
+        launch_finalize(b->d, rp, n, kFinalizeFull, s);
+        break;
+    case Estimator::kFivePoint:
+        launch_essential5(b->d, rp, n, b->e5_nroots, b->e5_count, b->e5_cap, b->e5_root, s);
+        launch_finalize(b->d, rp, n, kFinalizeEssential, s);
+        break;
+    }
+}
+
 // the device arrays of `problems` refinement problems of `stride` points seen by `frames` frames (two: the batch's
 // problems, with marginal covariances; one: a sequence's refit), allocated as one group; K is the caller's
 static mvs_status alloc_refine(mvs_ctx *ctx, DevBlocks &owner, RefineDev &d, int problems, int stride, int frames,
@@ -1227,19 +1274,14 @@ mvs_status mvs_batch_run(mvs_batch *b, const mvs_params *params, int n_active)
     st = ensure_groups(b, params->num_hypotheses);
     if (st != MVS_OK)
         return st;
-    b->d.hyp_count = nullptr;
-    b->d.hyp_residual = nullptr;
     return enqueue_pipeline(b, to_run(*params), n_active, false, nullptr);
 }
 
-// A batch of sfm_solve calls (vision/sfm.hpp:30-35, sfm-solve.cpp:285-368) on caller-supplied point pairs: the matcher is
-// skipped, everything behind it is mvs_batch_run's (normalise -> RANSAC stage -> decomposition -> triangulation, half batches
-// on two streams included).  uv1 / uv2: HOST, [n_active][max_kp][2] doubles (image points of the base / pair frame, row k of
-// pair p = match k); m[p]: matches of pair p (0 .. max_kp).  The intrinsics and the sampler's key offsets are the resident
-// ones (mvs_batch_upload with null descriptor / keypoint pointers sets just K and global_index).  `matches` rows of the
-// batch are cleared (there is no match list: point k IS match k); results / mask / points / point_idx as after mvs_batch_run.
-mvs_status mvs_batch_run_points(mvs_batch *b, const mvs_params *params, int n_active, const double *uv1, const double *uv2,
-                                const int32_t *m)
+// What the two mvs_batch_run_points* share: the checks, the estimator's tables, the caller's image points and match counts
+// on the device, normalised points in d.pts.  `matches` rows of the batch are cleared (there is no match list: point k IS
+// match k).
+static mvs_status stage_batch_points(mvs_batch *b, Estimator est, const mvs_params *params, int n_active, const double *uv1,
+                                     const double *uv2, const int32_t *m)
 {
     if (!b || !uv1 || !uv2 || !m || n_active < 1 || n_active > b->d.n_pairs)
         return MVS_ERR_INVALID_ARG;
@@ -1252,8 +1294,7 @@ mvs_status mvs_batch_run_points(mvs_batch *b, const mvs_params *params, int n_ac
             return MVS_ERR_CAPACITY;
     mvs_ctx *ctx = b->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    st = ensure_groups(b, params->num_hypotheses);
-    if (st != MVS_OK)
+    if ((st = ensure_tables(b, est, params->num_hypotheses)) != MVS_OK)
         return st;
     if (!b->uv1) {   // staging for the image points, allocated on first use and owned by the batch
         const size_t count = (size_t)b->d.n_pairs * N * 2;
@@ -1270,27 +1311,22 @@ mvs_status mvs_batch_run_points(mvs_batch *b, const mvs_params *params, int n_ac
     // runtime before hipMemcpyAsync returns; pinned ones are not) -- wait for the three copies, not for the kernels
     HIP_TRY(ctx, sync_stream(ctx));
     launch_prep_points(b->d, b->uv1, b->uv2, n_active, s);
-    b->d.hyp_count = nullptr;
-    b->d.hyp_residual = nullptr;
-    return enqueue_pipeline(b, to_run(*params), n_active, false, nullptr, nullptr, false);
+    return MVS_OK;
 }
 
-// the tables of the five-point stage: one group, so a failed allocation leaves the batch as it was
-static mvs_status ensure_e5(mvs_batch *b, int num_hypotheses)
+// A batch of sfm_solve calls (vision/sfm.hpp:30-35, sfm-solve.cpp:285-368) on caller-supplied point pairs: the matcher is
+// skipped, everything behind it is mvs_batch_run's (normalise -> RANSAC stage -> decomposition -> triangulation, half batches
+// on two streams included).  uv1 / uv2: HOST, [n_active][max_kp][2] doubles (image points of the base / pair frame, row k of
+// pair p = match k); m[p]: matches of pair p (0 .. max_kp).  The intrinsics and the sampler's key offsets are the resident
+// ones (mvs_batch_upload with null descriptor / keypoint pointers sets just K and global_index).  results / mask / points /
+// point_idx as after mvs_batch_run.
+mvs_status mvs_batch_run_points(mvs_batch *b, const mvs_params *params, int n_active, const double *uv1, const double *uv2,
+                                const int32_t *m)
 {
-    if (num_hypotheses <= b->e5_cap)
-        return MVS_OK;
-    HIP_TRY(b->ctx, sync_stream(b->ctx));
-    const size_t P = (size_t)b->d.n_pairs, H = (size_t)num_hypotheses;
-    DevGroup g(b->ctx, b->blocks);
-    g.add(b->e5_nroots, P * H);
-    g.add(b->e5_count, P * H * kE5MaxRoots);
-    if (!b->e5_root) g.add(b->e5_root, P);
-    const mvs_status st = g.commit();
+    const mvs_status st = stage_batch_points(b, Estimator::kEightPoint, params, n_active, uv1, uv2, m);
     if (st != MVS_OK)
         return st;
-    b->e5_cap = num_hypotheses;
-    return MVS_OK;
+    return enqueue_pipeline(b, to_run(*params), n_active, false, nullptr, nullptr, false);
 }
 
 // mvs_batch_run_points with find_essential_matrix's five-point branch (sfm-solve.cpp:42-63) in place of the 8-point RANSAC:
@@ -1299,36 +1335,11 @@ static mvs_status ensure_e5(mvs_batch *b, int num_hypotheses)
 mvs_status mvs_batch_run_points_essential(mvs_batch *b, const mvs_params *params, int n_active, const double *uv1,
                                           const double *uv2, const int32_t *m)
 {
-    if (!b || !uv1 || !uv2 || !m || n_active < 1 || n_active > b->d.n_pairs)
-        return MVS_ERR_INVALID_ARG;
-    mvs_status st = check_params(params);
+    const mvs_status st = stage_batch_points(b, Estimator::kFivePoint, params, n_active, uv1, uv2, m);
     if (st != MVS_OK)
         return st;
-    const size_t N = (size_t)b->d.max_kp;
-    for (int p = 0; p < n_active; ++p)
-        if (m[p] < 0 || m[p] > (int)N)
-            return MVS_ERR_CAPACITY;
-    mvs_ctx *ctx = b->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((st = ensure_e5(b, params->num_hypotheses)) != MVS_OK)
-        return st;
-    if (!b->uv1) {   // staging for the image points, allocated on first use and owned by the batch
-        const size_t count = (size_t)b->d.n_pairs * N * 2;
-        if ((st = DevGroup(ctx, b->blocks).add(b->uv1, count).add(b->uv2, count).commit()) != MVS_OK)
-            return st;
-    }
-    hipStream_t s = ctx->stream;
-    const size_t pb = (size_t)n_active * N * 2 * sizeof(double);
-    HIP_TRY(ctx, hipMemcpyAsync(b->uv1, uv1, pb, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(b->uv2, uv2, pb, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(b->d.M, m, (size_t)n_active * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemsetAsync(b->d.matches, 0, (size_t)n_active * N * sizeof(mvs_match), s));
-    HIP_TRY(ctx, sync_stream(ctx));   // the host buffers are the caller's again (as in mvs_batch_run_points)
-    launch_prep_points(b->d, b->uv1, b->uv2, n_active, s);
-    const RunParams rp = to_run(*params);
-    launch_essential5(b->d, rp, n_active, b->e5_nroots, b->e5_count, b->e5_cap, b->e5_root, s);
-    launch_finalize(b->d, rp, n_active, kFinalizeEssential, s);
-    HIP_TRY(ctx, hipGetLastError());
+    enqueue_model(b, Estimator::kFivePoint, to_run(*params), n_active);
+    HIP_TRY(b->ctx, hipGetLastError());
     return MVS_OK;
 }
 
@@ -1353,8 +1364,6 @@ mvs_status mvs_batch_time(mvs_batch *b, const mvs_params *params, int n_active, 
     st = ensure_groups(b, params->num_hypotheses);
     if (st != MVS_OK)
         return st;
-    b->d.hyp_count = nullptr;
-    b->d.hyp_residual = nullptr;
     const RunParams rp = to_run(*params);
     hipStream_t s = ctx->stream;
     for (int i = 0; i < warmup; ++i)
@@ -1399,8 +1408,6 @@ mvs_status mvs_batch_time_kernels(mvs_batch *b, const mvs_params *params, int n_
     st = ensure_groups(b, params->num_hypotheses);
     if (st != MVS_OK)
         return st;
-    b->d.hyp_count = nullptr;
-    b->d.hyp_residual = nullptr;
     const RunParams rp = to_run(*params);
     constexpr int kMaxLaunches = 32;
     cap = std::min(cap, kMaxLaunches);
@@ -1579,8 +1586,6 @@ mvs_status mvs_batch_stats(mvs_batch *b, const mvs_params *params, int n_active,
     st = ensure_groups(b, params->num_hypotheses);
     if (st != MVS_OK)
         return st;
-    b->d.hyp_count = nullptr;
-    b->d.hyp_residual = nullptr;
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx, hipMemsetAsync(b->d.stats, 0, 16 * sizeof(unsigned long long), s));
     st = enqueue_pipeline(b, to_run(*params), n_active, true, nullptr);
@@ -1699,6 +1704,10 @@ static mvs_status ensure_scratch(mvs_ctx *ctx, int max_kp, int desc_bytes)
     return mvs_batch_create(ctx, 1, max_kp, desc_bytes, &ctx->scratch);
 }
 
+// What fetch_single may reserve in the pinned arena for a scratch batch of `max_kp` rows (every output wanted, pin_get's
+// alignment and some slack on top): a call adds this to what it stages upward when it opens the arena (pin_begin).
+static size_t fetch_single_bound(int max_kp) { return single_layout(max_kp, 15).total + 512; }
+
 // stage image points + camera of a single-shot call; leaves normalised points in batch->pts
 static mvs_status stage_points(mvs_ctx *ctx, const double *p1_uv, const double *p2_uv, int m, const double K[9])
 {
@@ -1720,7 +1729,7 @@ static mvs_status stage_points(mvs_ctx *ctx, const double *p1_uv, const double *
     const int32_t M = m;
     const size_t pb = (size_t)m * 2 * sizeof(double);
     // results come back through the same arena (fetch_single): size it for both directions now
-    if ((st = pin_begin(ctx, 2 * pb + 1024 + sizeof(mvs_pair_result) + (size_t)b->d.max_kp * (1 + 24 + 4 + 16) + 512)) != MVS_OK)
+    if ((st = pin_begin(ctx, 2 * pb + 1024 + fetch_single_bound(b->d.max_kp))) != MVS_OK)
         return st;
     if ((st = up_async(ctx, d_uv1, p1_uv, pb)) != MVS_OK) return st;
     if ((st = up_async(ctx, d_uv2, p2_uv, pb)) != MVS_OK) return st;
@@ -1826,9 +1835,23 @@ mvs_status mvs_match_hamming(mvs_ctx *ctx, const uint8_t *train_desc, int n_trai
     return MVS_OK;
 }
 
-mvs_status mvs_two_view(mvs_ctx *ctx, const double *p1_uv, const double *p2_uv, int m, const double K[9],
-                        const mvs_params *params, double R[9], double t[3], double *points_xyz,
-                        int64_t *point_idx, int *n_points, uint8_t *inlier_mask, mvs_pair_result *result)
+// the end of every call that returns a pose: the record, then R / t / point count of a valid one
+static mvs_status return_pose(const mvs_pair_result &res, mvs_pair_result *result, double R[9], double t[3], int *n_points)
+{
+    if (result)
+        *result = res;
+    if (!res.valid)
+        return MVS_NO_MODEL;
+    if (R) std::memcpy(R, res.R, sizeof(res.R));
+    if (t) std::memcpy(t, res.t, sizeof(res.t));
+    if (n_points) *n_points = res.n_points;
+    return MVS_OK;
+}
+
+// sfm_solve (sfm-solve.cpp:285-368) of one pair with either estimator in front of the same tail
+static mvs_status two_view_impl(mvs_ctx *ctx, Estimator est, const double *p1_uv, const double *p2_uv, int m, const double K[9],
+                                const mvs_params *params, double R[9], double t[3], double *points_xyz, int64_t *point_idx,
+                                int *n_points, uint8_t *inlier_mask, mvs_pair_result *result)
 {
     if (!ctx || !p1_uv || !p2_uv || !K || m < 0)
         return MVS_ERR_INVALID_ARG;
@@ -1850,26 +1873,31 @@ mvs_status mvs_two_view(mvs_ctx *ctx, const double *p1_uv, const double *p2_uv, 
     st = stage_points(ctx, p1_uv, p2_uv, m, K);
     if (st != MVS_OK)
         return st;
-    mvs_batch *b = ctx->scratch;
-    st = ensure_groups(b, params->num_hypotheses);
-    if (st != MVS_OK)
+    if ((st = ensure_tables(ctx->scratch, est, params->num_hypotheses)) != MVS_OK)
         return st;
-    b->d.hyp_count = nullptr;
-    b->d.hyp_residual = nullptr;
-    const RunParams rp = to_run(*params);
-    launch_ransac(b->d, rp, 1, false, ctx->stream);
-    launch_finalize(b->d, rp, 1, kFinalizeFull, ctx->stream);
+    enqueue_model(ctx->scratch, est, to_run(*params), 1);
     st = fetch_single(ctx, m, &res, points_xyz, point_idx, inlier_mask);
     if (st != MVS_OK)
         return st;
-    if (result)
-        *result = res;
-    if (!res.valid)
-        return MVS_NO_MODEL;
-    if (R) std::memcpy(R, res.R, sizeof(res.R));
-    if (t) std::memcpy(t, res.t, sizeof(res.t));
-    if (n_points) *n_points = res.n_points;
-    return MVS_OK;
+    return return_pose(res, result, R, t, n_points);
+}
+
+mvs_status mvs_two_view(mvs_ctx *ctx, const double *p1_uv, const double *p2_uv, int m, const double K[9],
+                        const mvs_params *params, double R[9], double t[3], double *points_xyz,
+                        int64_t *point_idx, int *n_points, uint8_t *inlier_mask, mvs_pair_result *result)
+{
+    return two_view_impl(ctx, Estimator::kEightPoint, p1_uv, p2_uv, m, K, params, R, t, points_xyz, point_idx, n_points,
+                         inlier_mask, result);
+}
+
+// sfm_solve with find_essential_matrix's five-point branch (sfm-solve.cpp:42-63,285-368): mvs_two_view with the five-point
+// RANSAC of essential5.hip in front of the same tail.  No refit and no projection: F and E of the result both hold the winner.
+mvs_status mvs_two_view_essential(mvs_ctx *ctx, const double *p1_uv, const double *p2_uv, int m, const double K[9],
+                                  const mvs_params *params, double R[9], double t[3], double *points_xyz, int64_t *point_idx,
+                                  int *n_points, uint8_t *inlier_mask, mvs_pair_result *result)
+{
+    return two_view_impl(ctx, Estimator::kFivePoint, p1_uv, p2_uv, m, K, params, R, t, points_xyz, point_idx, n_points,
+                         inlier_mask, result);
 }
 
 // ImagePair::ImagePair + reconstruct (front-end/image-pair.cpp:30-71,116-174) of ONE pair in one device pass: the
@@ -1897,11 +1925,9 @@ mvs_status mvs_image_pair(mvs_ctx *ctx, const uint8_t *base_desc, const float *b
     mvs_batch *b = ctx->scratch;
     if ((st = ensure_groups(b, params->num_hypotheses)) != MVS_OK)
         return st;
-    b->d.hyp_count = nullptr;
-    b->d.hyp_residual = nullptr;
     const size_t db1 = (size_t)n_base * desc_bytes, db2 = (size_t)n_pair * desc_bytes;
     const size_t kb1 = (size_t)n_base * 2 * sizeof(float), kb2 = (size_t)n_pair * 2 * sizeof(float);
-    if ((st = pin_begin(ctx, db1 + db2 + kb1 + kb2 + 2048 + single_layout(n_pair, 15).total + 512)) != MVS_OK)
+    if ((st = pin_begin(ctx, db1 + db2 + kb1 + kb2 + 2048 + fetch_single_bound(b->d.max_kp))) != MVS_OK)
         return st;
     double kinv[9];
     mat3_inverse(K, kinv);
@@ -2009,14 +2035,7 @@ mvs_status mvs_recover_pose(mvs_ctx *ctx, const double E[9], const double *p1_uv
     st = fetch_single(ctx, m, &res, points_xyz, point_idx, nullptr);
     if (st != MVS_OK)
         return st;
-    if (result)
-        *result = res;
-    if (!res.valid)
-        return MVS_NO_MODEL;
-    if (R) std::memcpy(R, res.R, sizeof(res.R));
-    if (t) std::memcpy(t, res.t, sizeof(res.t));
-    if (n_points) *n_points = res.n_points;
-    return MVS_OK;
+    return return_pose(res, result, R, t, n_points);
 }
 
 mvs_status mvs_find_fundamental_matrix(mvs_ctx *ctx, const double p1_xy[16], const double p2_xy[16], double F[9])
@@ -2038,6 +2057,49 @@ mvs_status mvs_find_fundamental_matrix(mvs_ctx *ctx, const double p1_xy[16], con
     return ok ? MVS_OK : MVS_NO_MODEL;
 }
 
+// What the two mvs_ransac_* share behind their own argument checks: the scratch batch with the estimator's tables, the
+// ideal-camera points packed four to a row into its pts (they are already normalised: pure packing), identity intrinsics,
+// and the parameters of a RANSAC stage that stops after the mask.
+static mvs_status stage_ideal(mvs_ctx *ctx, Estimator est, const double *p1_xy, const double *p2_xy, int m, double max_error_sq,
+                              int num_hypotheses, int sampler, uint64_t seed, RunParams *rp)
+{
+    if (m > kMaxKp)
+        return MVS_ERR_CAPACITY;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int desc_bytes = ctx->scratch ? ctx->scratch->d.desc_words * 4 : 32;
+    mvs_status st = ensure_scratch(ctx, m, desc_bytes);
+    if (st != MVS_OK)
+        return st;
+    mvs_batch *b = ctx->scratch;
+    if ((st = ensure_tables(b, est, num_hypotheses)) != MVS_OK)
+        return st;
+    std::vector<double> packed((size_t)m * 4);
+    for (int i = 0; i < m; ++i) {
+        packed[4 * i] = p1_xy[2 * i];
+        packed[4 * i + 1] = p1_xy[2 * i + 1];
+        packed[4 * i + 2] = p2_xy[2 * i];
+        packed[4 * i + 3] = p2_xy[2 * i + 1];
+    }
+    const int32_t M = m;
+    const int64_t zero = 0;
+    const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if ((st = pin_begin(ctx, packed.size() * sizeof(double) + 2048 + fetch_single_bound(b->d.max_kp))) != MVS_OK)
+        return st;
+    if ((st = up_async(ctx, b->d.pts, packed.data(), packed.size() * sizeof(double))) != MVS_OK) return st;
+    if ((st = up_async(ctx, b->d.M, &M, sizeof(M))) != MVS_OK) return st;
+    if ((st = up_async(ctx, const_cast<int64_t *>(b->d.gidx), &zero, sizeof(zero))) != MVS_OK) return st;
+    if ((st = up_async(ctx, const_cast<double *>(b->d.K), eye, sizeof(eye))) != MVS_OK) return st;
+    if ((st = up_async(ctx, const_cast<double *>(b->d.Kinv), eye, sizeof(eye))) != MVS_OK) return st;
+    *rp = RunParams{};
+    rp->max_error_sq = max_error_sq;
+    rp->num_hypotheses = num_hypotheses;
+    rp->sampler = sampler;
+    rp->seed = seed;
+    rp->min_inliers = 0x7fffffff;  // stop after the mask: no decomposition / triangulation wanted here
+    return MVS_OK;
+}
+
+// `sampler` is not validated here: any non-zero value samples as Philox.
 mvs_status mvs_ransac_fundamental(mvs_ctx *ctx, const double *p1_xy, const double *p2_xy, int m, double max_error_sq,
                                   int num_hypotheses, int sampler, uint64_t seed, double F[9], uint8_t *inlier_mask,
                                   int *best_hyp, int *best_count, double *best_residual, int32_t *count,
@@ -2052,33 +2114,17 @@ mvs_status mvs_ransac_fundamental(mvs_ctx *ctx, const double *p1_xy, const doubl
     if (best_residual) *best_residual = 0.0;
     if (m < 8)
         return MVS_NO_MODEL;  // estimator-RANSAC.cpp:25-29
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int desc_bytes = ctx->scratch ? ctx->scratch->d.desc_words * 4 : 32;
-    mvs_status st = ensure_scratch(ctx, m, desc_bytes);
+    RunParams rp;
+    mvs_status st = stage_ideal(ctx, Estimator::kEightPoint, p1_xy, p2_xy, m, max_error_sq, num_hypotheses, sampler, seed, &rp);
     if (st != MVS_OK)
         return st;
     mvs_batch *b = ctx->scratch;
-    st = ensure_groups(b, num_hypotheses);
-    if (st != MVS_OK)
-        return st;
-    hipStream_t s = ctx->stream;
-    std::vector<double> packed((size_t)m * 4);  // ideal-camera points are already normalised: pure packing
-    for (int i = 0; i < m; ++i) {
-        packed[4 * i] = p1_xy[2 * i];
-        packed[4 * i + 1] = p1_xy[2 * i + 1];
-        packed[4 * i + 2] = p2_xy[2 * i];
-        packed[4 * i + 3] = p2_xy[2 * i + 1];
-    }
-    const int32_t M = m;
-    const int64_t zero = 0;
-    const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    if ((st = pin_begin(ctx, packed.size() * sizeof(double) + 2048 + sizeof(mvs_pair_result) + (size_t)m + 256)) != MVS_OK)
-        return st;
-    if ((st = up_async(ctx, b->d.pts, packed.data(), packed.size() * sizeof(double))) != MVS_OK) return st;
-    if ((st = up_async(ctx, b->d.M, &M, sizeof(M))) != MVS_OK) return st;
-    if ((st = up_async(ctx, const_cast<int64_t *>(b->d.gidx), &zero, sizeof(zero))) != MVS_OK) return st;
-    if ((st = up_async(ctx, const_cast<double *>(b->d.K), eye, sizeof(eye))) != MVS_OK) return st;
-    if ((st = up_async(ctx, const_cast<double *>(b->d.Kinv), eye, sizeof(eye))) != MVS_OK) return st;
+    // The only place a BatchDev's per-hypothesis tables are ever hooked up: whichever way this call ends they are unhooked
+    // again, so everywhere else d.hyp_count / d.hyp_residual are null.
+    struct Unhook {
+        BatchDev &d;
+        ~Unhook() { d.hyp_count = nullptr; d.hyp_residual = nullptr; }
+    } unhook{b->d};
     if (count || residual) {
         if (b->hyp_table_cap < num_hypotheses) {
             HIP_TRY(ctx, sync_stream(ctx));   // the tables it replaces are freed
@@ -2089,79 +2135,21 @@ mvs_status mvs_ransac_fundamental(mvs_ctx *ctx, const double *p1_xy, const doubl
         }
         b->d.hyp_count = b->hyp_table_count;
         b->d.hyp_residual = b->hyp_table_residual;
-    } else {
-        b->d.hyp_count = nullptr;
-        b->d.hyp_residual = nullptr;
     }
-    RunParams rp{};
-    rp.max_error_sq = max_error_sq;
-    rp.num_hypotheses = num_hypotheses;
-    rp.sampler = sampler;
-    rp.seed = seed;
-    rp.min_inliers = 0x7fffffff;  // stop after the mask: no decomposition / triangulation wanted here
-    launch_ransac(b->d, rp, 1, false, s);
-    launch_finalize(b->d, rp, 1, kFinalizeFull, s);
+    enqueue_model(b, Estimator::kEightPoint, rp, 1);
     mvs_pair_result res;
-    st = fetch_single(ctx, m, &res, nullptr, nullptr, inlier_mask);
-    if (st == MVS_OK && count)
+    if ((st = fetch_single(ctx, m, &res, nullptr, nullptr, inlier_mask)) != MVS_OK)
+        return st;
+    if (count)
         HIP_TRY(ctx, hipMemcpy(count, b->d.hyp_count, (size_t)num_hypotheses * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (st == MVS_OK && residual)
+    if (residual)
         HIP_TRY(ctx, hipMemcpy(residual, b->d.hyp_residual, (size_t)num_hypotheses * sizeof(double),
                                hipMemcpyDeviceToHost));
-    b->d.hyp_count = nullptr;
-    b->d.hyp_residual = nullptr;
-    if (st != MVS_OK)
-        return st;
     if (F) std::memcpy(F, res.F, sizeof(res.F));
     if (best_hyp) *best_hyp = res.best_hyp;
     if (best_count) *best_count = res.best_count;
     if (best_residual) *best_residual = res.best_residual;
     return res.best_count > 0 ? MVS_OK : MVS_NO_MODEL;  // estimator-RANSAC.cpp:89
-}
-
-// sfm_solve with find_essential_matrix's five-point branch (sfm-solve.cpp:42-63,285-368): mvs_two_view with the five-point
-// RANSAC of essential5.hip in front of the same tail.  No refit and no projection: F and E of the result both hold the winner.
-mvs_status mvs_two_view_essential(mvs_ctx *ctx, const double *p1_uv, const double *p2_uv, int m, const double K[9],
-                                  const mvs_params *params, double R[9], double t[3], double *points_xyz, int64_t *point_idx,
-                                  int *n_points, uint8_t *inlier_mask, mvs_pair_result *result)
-{
-    if (!ctx || !p1_uv || !p2_uv || !K || m < 0)
-        return MVS_ERR_INVALID_ARG;
-    mvs_status st = check_params(params);
-    if (st != MVS_OK)
-        return st;
-    if (n_points)
-        *n_points = 0;
-    mvs_pair_result res;
-    std::memset(&res, 0, sizeof(res));
-    res.best_hyp = -1;
-    res.n_matches = m;
-    if (m < 8) {  // sfm-solve.cpp:37 asserts
-        if (result)
-            *result = res;
-        return m < 1 ? MVS_ERR_INVALID_ARG : MVS_NO_MODEL;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    st = stage_points(ctx, p1_uv, p2_uv, m, K);
-    if (st != MVS_OK)
-        return st;
-    mvs_batch *b = ctx->scratch;
-    if ((st = ensure_e5(b, params->num_hypotheses)) != MVS_OK)
-        return st;
-    const RunParams rp = to_run(*params);
-    launch_essential5(b->d, rp, 1, b->e5_nroots, b->e5_count, b->e5_cap, b->e5_root, ctx->stream);
-    launch_finalize(b->d, rp, 1, kFinalizeEssential, ctx->stream);
-    st = fetch_single(ctx, m, &res, points_xyz, point_idx, inlier_mask);
-    if (st != MVS_OK)
-        return st;
-    if (result)
-        *result = res;
-    if (!res.valid)
-        return MVS_NO_MODEL;
-    if (R) std::memcpy(R, res.R, sizeof(res.R));
-    if (t) std::memcpy(t, res.t, sizeof(res.t));
-    if (n_points) *n_points = res.n_points;
-    return MVS_OK;
 }
 
 // The minimal solver on the device (five_point.hpp): what cv::findEssentialMat runs per sample.
@@ -2200,45 +2188,14 @@ mvs_status mvs_ransac_essential(mvs_ctx *ctx, const double *p1_xy, const double 
     if (best_residual) *best_residual = 0.0;
     if (m < 8)
         return MVS_NO_MODEL;  // sfm-solve.cpp:37
-    if (m > kMaxKp)
-        return MVS_ERR_CAPACITY;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int desc_bytes = ctx->scratch ? ctx->scratch->d.desc_words * 4 : 32;
-    mvs_status st = ensure_scratch(ctx, m, desc_bytes);
+    RunParams rp;
+    mvs_status st = stage_ideal(ctx, Estimator::kFivePoint, p1_xy, p2_xy, m, max_error_sq, num_hypotheses, sampler, seed, &rp);
     if (st != MVS_OK)
         return st;
     mvs_batch *b = ctx->scratch;
-    if ((st = ensure_e5(b, num_hypotheses)) != MVS_OK)
-        return st;
-    hipStream_t s = ctx->stream;
-    std::vector<double> packed((size_t)m * 4);  // ideal-camera points are already normalised: pure packing
-    for (int i = 0; i < m; ++i) {
-        packed[4 * i] = p1_xy[2 * i];
-        packed[4 * i + 1] = p1_xy[2 * i + 1];
-        packed[4 * i + 2] = p2_xy[2 * i];
-        packed[4 * i + 3] = p2_xy[2 * i + 1];
-    }
-    const int32_t M = m;
-    const int64_t zero = 0;
-    const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    if ((st = pin_begin(ctx, packed.size() * sizeof(double) + 2048 + single_layout(b->d.max_kp, 15).total + 512)) != MVS_OK)
-        return st;
-    if ((st = up_async(ctx, b->d.pts, packed.data(), packed.size() * sizeof(double))) != MVS_OK) return st;
-    if ((st = up_async(ctx, b->d.M, &M, sizeof(M))) != MVS_OK) return st;
-    if ((st = up_async(ctx, const_cast<int64_t *>(b->d.gidx), &zero, sizeof(zero))) != MVS_OK) return st;
-    if ((st = up_async(ctx, const_cast<double *>(b->d.K), eye, sizeof(eye))) != MVS_OK) return st;
-    if ((st = up_async(ctx, const_cast<double *>(b->d.Kinv), eye, sizeof(eye))) != MVS_OK) return st;
-    RunParams rp{};
-    rp.max_error_sq = max_error_sq;
-    rp.num_hypotheses = num_hypotheses;
-    rp.sampler = sampler;
-    rp.seed = seed;
-    rp.min_inliers = 0x7fffffff;  // stop after the mask: no decomposition / triangulation wanted here
-    launch_essential5(b->d, rp, 1, b->e5_nroots, b->e5_count, b->e5_cap, b->e5_root, s);
-    launch_finalize(b->d, rp, 1, kFinalizeEssential, s);
+    enqueue_model(b, Estimator::kFivePoint, rp, 1);
     mvs_pair_result res;
-    st = fetch_single(ctx, m, &res, nullptr, nullptr, inlier_mask);
-    if (st != MVS_OK)
+    if ((st = fetch_single(ctx, m, &res, nullptr, nullptr, inlier_mask)) != MVS_OK)
         return st;
     const size_t H = (size_t)num_hypotheses;
     if (n_roots)
@@ -2429,8 +2386,6 @@ static mvs_status seq_prepare(mvs_seq *q, const mvs_params *tv, const mvs_pnp_pa
             return st;
         q->pnp.max_groups = G;
     }
-    q->batch->d.hyp_count = nullptr;
-    q->batch->d.hyp_residual = nullptr;
     q->pnp.num_hypotheses = pp->num_hypotheses;
     q->pnp.sampler = pp->sampler;
     q->pnp.min_inliers = pp->min_inliers;

@@ -208,3 +208,63 @@ def test_batch_run_points_essential_equals_the_single_calls(ctx):
         assert not out["mask"][p][m[p]:].any() and not out["points"][p][n:].any()
         n_valid += bool(out["results"][p]["valid"])
     assert n_valid >= P // 2
+
+
+_DOWNLOAD_KEYS = ("results", "matches", "mask", "points", "point_idx")
+
+
+@pytest.mark.parametrize("P", [4, 64])
+def test_batch_run_points_of_both_estimators_alternate_on_one_batch(ctx, P):
+    """mvs_batch_run_points and mvs_batch_run_points_essential stage their points the same way and grow their own tables on
+    the same batch: alternated on one batch, each gives the bytes it gives as the first call on a fresh batch -- below the
+    half-batch threshold and at it (64 pairs: the 8-point call runs as two halves on two streams) -- also after a call
+    refused for a match count beyond the capacity.  Every byte of a download is compared but the pose (R, t, R1to2, t1to2) in
+    the record of a pair WITHOUT a model: the 8-point stage does not write it, what is there is the previous call's."""
+    N, H = 96, 40
+    rng = np.random.default_rng(78)
+    fams = list(helpers.CAMERAS)
+    Ks = np.stack([helpers.CAMERAS[fams[p % len(fams)]][0] for p in range(P)])
+    m = rng.integers(8, N + 1, size=P).astype(np.int32)
+    m[0], m[1], m[2] = 5, N, 8
+    uv1, uv2 = np.zeros((P, N, 2)), np.zeros((P, N, 2))
+    for p in range(P):
+        a, b2 = _scene(2000 + p, N, outliers=0.25, noise=1e-4)[:2]
+        h = lambda q: np.hstack([q, np.ones((N, 1))]) @ Ks[p].T   # noqa: E731
+        uv1[p], uv2[p] = h(a)[:, :2], h(b2)[:, :2]
+        uv1[p, m[p]:], uv2[p, m[p]:] = 0.0, 0.0
+    prm = capi.default_params(num_hypotheses=H, sampler=capi.SAMPLER_PHILOX, seed=500, max_error_sq=2e-3)
+
+    def new_batch():
+        b = capi.Batch(ctx, P, N, 32)
+        b.upload_intrinsics(0, Ks, global_index=np.arange(P) * 3)
+        return b
+
+    def run(b, name):
+        getattr(b, name)(prm, uv1, uv2, m)
+        b.sync()
+        out = b.download()
+        for k in ("R", "t", "R1to2", "t1to2"):
+            out["results"][k][out["results"]["valid"] == 0] = 0.0
+        return {k: out[k].tobytes() for k in _DOWNLOAD_KEYS}
+
+    fresh = {}
+    for name in ("run_points", "run_points_essential"):
+        b = new_batch()
+        fresh[name] = run(b, name)
+        b.close()
+    for name in fresh:   # most pairs have a model under either estimator (pair 0 has five matches: none), not the same one
+        valid = np.frombuffer(fresh[name]["results"], dtype=capi.RESULT_DTYPE)["valid"]
+        assert not valid[0] and valid.sum() >= P // 2, name
+    assert fresh["run_points"]["results"] != fresh["run_points_essential"]["results"]
+    b = new_batch()
+    for name in ("run_points", "run_points_essential", "run_points", "run_points_essential"):
+        assert run(b, name) == fresh[name], name
+    for name in ("run_points", "run_points_essential"):
+        for bad in (N + 1, -1):
+            m_bad = m.copy()
+            m_bad[P - 1] = bad
+            with pytest.raises(capi.MvsError) as e:
+                getattr(b, name)(prm, uv1, uv2, m_bad)
+            assert e.value.status == capi.MVS_ERR_CAPACITY, (name, bad)
+        assert run(b, name) == fresh[name], name
+    b.close()

@@ -746,7 +746,8 @@ def _bytes_of(r):
 
 def test_one_context_same_answers_while_its_workspaces_grow():
     """small -> clearly larger -> small again on ONE fresh context: every single-shot entry point regrows its workspace
-    (and the extraction re-captures its graph for a second image shape), and the third call equals the first bit for bit."""
+    (and the extraction re-captures its graph for a second image shape), and the third call equals the first bit for bit.
+    Both estimators' tables regrow beside each other on the one scratch batch."""
     K = np.array([[525.0, 0, 320], [0, 525, 240], [0, 0, 1]])
     rng = np.random.default_rng(31)
     images = {shape: np.kron(rng.integers(0, 256, size=(shape[0], shape[1] // 6, shape[2] // 6)).astype(np.uint8),
@@ -764,8 +765,15 @@ def test_one_context_same_answers_while_its_workspaces_grow():
         Xc = X / X[:, 2:3]
         cov = np.tile(np.eye(2).reshape(4) * 0.25, (m, 1))
         ex = c.extract(images[shape], capi.default_orb_params(nfeatures=300 if shape[0] == 1 else 1500))
+        # the five-point calls keep 256 hypotheses in the large round: the growth under test is in m and the 8-point tables
+        prm5 = capi.default_params(num_hypotheses=min(H, 256), sampler=capi.SAMPLER_PHILOX, seed=9, max_error_sq=2e-3)
+        tv = c.two_view(uv1, uv2, K, prm)
         return dict(
-            two_view=c.two_view(uv1, uv2, K, prm),
+            two_view=tv,
+            two_view_essential=c.two_view_essential(uv1, uv2, K, prm5),
+            ransac_essential=c.ransac_essential(p1, p2, 2e-3, min(H, 256), capi.SAMPLER_PHILOX, seed=17, per_hyp=True),
+            recover_pose=c.recover_pose(tv["E"], uv1, uv2, K, tv["mask"]),
+            triangulate=c.triangulate(uv1, uv2, K, tv["R1to2"], tv["t1to2"]),
             image_pair=c.image_pair(pair["desc1"], pair["kp1"], pair["desc2"], pair["kp2"], pair["K"], prm),
             pnp_solve=c.pnp_solve(X, uv, K, capi.default_pnp_params(num_hypotheses=H // 4, seed=3)),
             sfm_refine=c.sfm_refine(Xc[:, :2] * 525 + [320, 240], cov, uv, cov, K, R, t, X),
@@ -782,3 +790,77 @@ def test_one_context_same_answers_while_its_workspaces_grow():
         c.close()
     for name in first:
         assert again[name] == first[name], name
+
+
+def _fresh(fn):
+    c = capi.Context(0)
+    try:
+        return fn(c)
+    finally:
+        c.close()
+
+
+def test_estimators_interleaved_on_one_context():
+    """The 8-point and the five-point entry points share the context's scratch batch, its tables and the pinned arena: every
+    call gives the same bits in a fixed order, in the reverse order and alone on a context of its own.  65 points are one
+    past a wavefront, 70 hypotheses two five-point blocks of 64."""
+    m, H, thr = 65, 70, 2e-3
+    K = np.array([[525.0, 0, 320], [0, 525, 240], [0, 0, 1]])
+    p1, p2 = _scene(6500, m, 1e-4, outliers=0.1)
+    uv1, uv2 = p1 * 525 + np.array([320, 240.0]), p2 * 525 + np.array([320, 240.0])
+    prm = capi.default_params(num_hypotheses=H, sampler=capi.SAMPLER_PHILOX, seed=21, max_error_sq=thr)
+    pair = synth.make_pair(3, n_kp=128)
+    tv = _fresh(lambda c: c.two_view(uv1, uv2, K, prm))   # step 3 alone: its E, mask and pose are the inputs of steps 5 and 6
+    assert tv["ok"]
+    calls = [
+        lambda c: c.ransac_fundamental(p1, p2, thr, H, capi.SAMPLER_PHILOX, seed=17, per_hyp=True),
+        lambda c: c.two_view_essential(uv1, uv2, K, prm),
+        lambda c: c.two_view(uv1, uv2, K, prm),
+        lambda c: c.ransac_essential(p1, p2, thr, H, capi.SAMPLER_PHILOX, seed=17, per_hyp=True),
+        lambda c: c.recover_pose(tv["E"], uv1, uv2, K, tv["mask"]),
+        lambda c: c.triangulate(uv1, uv2, K, tv["R1to2"], tv["t1to2"]),
+        lambda c: c.ransac_fundamental(p1, p2, thr, H, capi.SAMPLER_PHILOX, seed=17, per_hyp=False),
+        lambda c: c.image_pair(pair["desc1"], pair["kp1"], pair["desc2"], pair["kp2"], pair["K"], prm),
+        lambda c: c.two_view_essential(uv1, uv2, K, prm),
+    ]
+    alone = [_bytes_of(_fresh(f)) for f in calls]
+    forward = _fresh(lambda c: [_bytes_of(f(c)) for f in calls])
+    backward = _fresh(lambda c: [_bytes_of(f(c)) for f in reversed(calls)])[::-1]
+    assert alone[2] == _bytes_of(tv)
+    for k in range(len(calls)):
+        assert forward[k] == alone[k], k
+        assert backward[k] == alone[k], k
+
+
+@pytest.mark.parametrize("estimator", ["eight_point", "five_point"])
+def test_two_view_and_ransac_return_codes(ctx, estimator):
+    """the status of every refused call and of too few points, the same for both estimators except where noted"""
+    two_view = ctx.two_view if estimator == "eight_point" else ctx.two_view_essential
+    ransac = ctx.ransac_fundamental if estimator == "eight_point" else ctx.ransac_essential
+    K = np.array([[525.0, 0, 320], [0, 525, 240], [0, 0, 1]])
+    p1, p2 = _scene(77, 20, 1e-4)
+    uv1, uv2 = p1 * 525 + np.array([320, 240.0]), p2 * 525 + np.array([320, 240.0])
+
+    def status_of(fn, *args, **kw):
+        with pytest.raises(capi.MvsError) as e:
+            fn(*args, **kw)
+        return e.value.status
+
+    prm = capi.default_params(num_hypotheses=8, sampler=capi.SAMPLER_PHILOX, seed=1, max_error_sq=2e-3)
+    assert status_of(two_view, uv1[:0], uv2[:0], K, prm) == capi.MVS_ERR_INVALID_ARG
+    got = two_view(uv1[:7], uv2[:7], K, prm)
+    assert not got["ok"] and got["n_matches"] == 7 and got["best_hyp"] == -1 and not got["valid"]
+    assert status_of(two_view, uv1, uv2, K, capi.default_params(num_hypotheses=0)) == capi.MVS_ERR_INVALID_ARG
+    assert status_of(two_view, uv1, uv2, K, capi.default_params(num_hypotheses=8, sampler=7)) == capi.MVS_ERR_INVALID_ARG
+    Kbad = K.copy()
+    Kbad[2, 0] = 0.1
+    assert status_of(two_view, uv1, uv2, Kbad, prm) == capi.MVS_ERR_BAD_INTRINSICS
+    # the RANSAC stage alone: only the five-point one validates the sampler, the 8-point one samples any non-zero value as Philox
+    if estimator == "five_point":
+        assert status_of(ransac, p1, p2, 2e-3, 8, sampler=7) == capi.MVS_ERR_INVALID_ARG
+    else:
+        odd = ransac(p1, p2, 2e-3, 8, sampler=7, seed=5, per_hyp=True)
+        assert odd["ok"] and _bytes_of(odd) == _bytes_of(ransac(p1, p2, 2e-3, 8, sampler=capi.SAMPLER_PHILOX, seed=5, per_hyp=True))
+    big = np.zeros((4097, 2))
+    assert status_of(ransac, big, big, 2e-3, 8) == capi.MVS_ERR_CAPACITY
+    assert status_of(ransac, p1, p2, 0.0, 8) == capi.MVS_ERR_INVALID_ARG
