@@ -39,6 +39,8 @@ extern "C" {
  * mvs_seq_download_windows are additions (new symbols only) */
 /* still 4: mvs_five_point, mvs_ransac_essential, mvs_two_view_essential and mvs_batch_run_points_essential are additions (new
  * symbols only): the five-point essential-matrix RANSAC beside the 8-point one */
+/* still 4: mvs_ctx_set_essential_confidence, mvs_ctx_essential_hypotheses_run and mvs_batch_download_hypotheses_run are additions
+ * (new symbols only): the five-point RANSAC's optional termination rule; off by default, no struct changed */
 #define MVS_ABI_VERSION 4
 
 typedef enum mvs_status {
@@ -108,6 +110,16 @@ void *mvs_ctx_stream(mvs_ctx *ctx); /* hipStream_t the kernels are launched on *
  * pairs are independent, estimator-RANSAC.cpp:76-84 runs per pair).  enable = 0 keeps every launch on the one stream.
  * Default: enabled. */
 mvs_status mvs_ctx_set_half_batches(mvs_ctx *ctx, int enable);
+/* Confidence level of the five-point essential-matrix RANSAC (the reference's VF_MATCH_CONFIDENCE_LEVEL = 0.99,
+ * sfm-solve.cpp:22-23,58), honoured by mvs_ransac_essential, mvs_two_view_essential and mvs_batch_run_points_essential; the
+ * 8-point entry points ignore it.  0 (the default): every hypothesis runs.  0 < confidence < 1: each pair stops at the first
+ * checkpoint at which the rule stated with those entry points holds.  Anything else (a NaN too): MVS_ERR_INVALID_ARG. */
+mvs_status mvs_ctx_set_essential_confidence(mvs_ctx *ctx, double confidence);
+/* n_run -- the hypotheses that took part -- of the last single-shot five-point call on this context (0: it had fewer than
+ * eight matches).  MVS_ERR_INVALID_ARG before the first such call, and after one that failed before its RANSAC was enqueued
+ * (an error status: capacity, intrinsics, allocation): nothing ran, and the call before it is no longer the last.  Without a
+ * confidence level the value is known on the host and the call touches no device. */
+mvs_status mvs_ctx_essential_hypotheses_run(mvs_ctx *ctx, int32_t *n_run);
 
 /* ---- single-shot entry points (host buffers; the reference's call surface) ------ */
 
@@ -177,7 +189,16 @@ mvs_status mvs_ransac_fundamental(mvs_ctx *ctx, const double *p1_xy, const doubl
  *                 num <= max_error_sq * den (binary64, operation order in five_point.hpp);
  *        select   most inliers; then the smaller residual (ONE sequential binary64 sum of num / den over the inliers, i ascending;
  *                 estimator-RANSAC.cpp:76-84); then the smaller hypothesis id; then the smaller root index;
- *        every hypothesis runs: VF_MATCH_CONFIDENCE_LEVEL (sfm-solve.cpp:58) is unused; no refit, no projection (:62-63). ---- */
+ *        stop     with mvs_ctx_set_essential_confidence at 0 (the default) every hypothesis runs.  With a confidence level
+ *                 p (VF_MATCH_CONFIDENCE_LEVEL, sfm-solve.cpp:22-23,58) a pair with M matches is tested at the checkpoints
+ *                 T_0 = min(64, H), T_{j+1} = min(2 T_j, H) (H = num_hypotheses): with c the largest count over the
+ *                 hypotheses h < T_j it stops at T_j iff T_j = H, or c >= 1 and (1 - (c / M)^5)^(64 2^j) <= 1 - p -- in
+ *                 binary64, one rounded operation each: w = c / M, w2 = w w, w5 = (w2 w2) w, q = 1 - w5, then q squared
+ *                 6 + j times; no logarithm (e5_confident, five_point.hpp).  The checkpoint T it stops at is the pair's
+ *                 n_run, and every output is what the same call returns with num_hypotheses = T: hypotheses >= T take no
+ *                 part.  Coarser than cv::findEssentialMat's per-iteration update on purpose: 64 hypotheses cost what one
+ *                 costs, and doubling bounds the overrun by a factor of two;
+ *        no refit, no projection (:62-63). ---- */
 
 /* The minimal solver alone.  p1_xy / p2_xy: 5 x (x, y) ideal-camera points.  E_out: [10][9] row-major, rows [*n, 10) zero.
  * *n = 0 for a degenerate sample; never a non-finite matrix. */
@@ -186,7 +207,7 @@ mvs_status mvs_five_point(mvs_ctx *ctx, const double p1_xy[10], const double p2_
 /* The RANSAC stage alone (the five-point counterpart of mvs_ransac_fundamental).  p1 / p2: m x (x, y) ideal-camera points,
  * 8 <= m <= 4096 (fewer: MVS_NO_MODEL, more: MVS_ERR_CAPACITY).  Outputs (any may be NULL): E of the winner, inlier_mask[m],
  * its hypothesis id, root index, inlier count and residual; n_roots[num_hypotheses] and count[num_hypotheses][10] (-1 past
- * n_roots): the optional per-hypothesis tables. */
+ * n_roots): the optional per-hypothesis tables; rows from the call's n_run on read n_roots = 0, count = -1. */
 mvs_status mvs_ransac_essential(mvs_ctx *ctx, const double *p1_xy, const double *p2_xy, int m, double max_error_sq,
                                 int num_hypotheses, int sampler, uint64_t seed, double E[9], uint8_t *inlier_mask, int *best_hyp,
                                 int *best_root, int *best_count, double *best_residual, int32_t *n_roots, int32_t *count);
@@ -264,6 +285,11 @@ mvs_status mvs_batch_run_points(mvs_batch *b, const mvs_params *params, int n_ac
  * launches: no half batches, no captured graph. */
 mvs_status mvs_batch_run_points_essential(mvs_batch *b, const mvs_params *params, int n_active, const double *uv1,
                                           const double *uv2, const int32_t *m);
+/* n_run[count] of pairs [first, first + count) in the batch's LAST mvs_batch_run_points_essential: num_hypotheses, or the
+ * checkpoint the pair stopped at under a confidence level (the call then waits for the ctx stream); 0 for a pair with fewer
+ * than eight matches and for a pair at or beyond that call's n_active, whatever an earlier call did with it.
+ * MVS_ERR_INVALID_ARG before the first such call. */
+mvs_status mvs_batch_download_hypotheses_run(mvs_batch *b, int first, int count, int32_t *n_run);
 
 /* Timed replay: `warmup` untimed + `steps` timed passes over the resident inputs, bracketed by HIP events
  * on the ctx stream.  ms_total: wall ms of the `steps` passes.  ms_kernel[5]: summed ms per kernel over the

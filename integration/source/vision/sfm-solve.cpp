@@ -10,6 +10,11 @@
 
 namespace mvSLAM
 {
+#if defined(USE_OPENCV_ESSENTIAL_MATRIX) && defined(MVSLAM_ESSENTIAL_CONFIDENCE)
+// what the file this one replaces hands to cv::findEssentialMat (sfm-solve.cpp:22-23,58); without MVSLAM_ESSENTIAL_CONFIDENCE
+// the five-point RANSAC runs every hypothesis
+static constexpr double VF_MATCH_CONFIDENCE_LEVEL = 0.99;
+#endif
 
 bool sfm_solve(const std::vector<ImagePoint> &p1, const std::vector<ImagePoint> &p2, const CameraIntrinsics &K,
                Transformation &pose2in1_scaled, std::vector<Point3> &pointsin1_scaled, std::vector<size_t> &point_indexes)
@@ -26,6 +31,10 @@ bool sfm_solve(const std::vector<ImagePoint> &p1, const std::vector<ImagePoint> 
     int n = 0;
     // cv::Point_<double> is two packed doubles: &p1[0].x is an m x 2 row-major array
 #ifdef USE_OPENCV_ESSENTIAL_MATRIX
+#ifdef MVSLAM_ESSENTIAL_CONFIDENCE
+    if (mvs_ctx_set_essential_confidence(hip::context(), VF_MATCH_CONFIDENCE_LEVEL) != MVS_OK)
+        return false;
+#endif
     if (mvs_two_view_essential(hip::context(), &p1[0].x, &p2[0].x, m, Kr, &prm, R, t, pts.data(), idx.data(), &n, nullptr,
                                nullptr) != MVS_OK)
 #else

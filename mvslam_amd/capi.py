@@ -156,7 +156,8 @@ EXPORTS = [
     "mvs_extract_time", "mvs_ctx_set_half_batches", "mvs_batch_device_state", "mvs_batch_run_points",
     "mvs_ba_refine_window", "mvs_ba_refine_windows", "mvs_seq_refine_windows", "mvs_seq_window_count",
     "mvs_seq_download_windows", "mvs_five_point", "mvs_ransac_essential", "mvs_two_view_essential",
-    "mvs_batch_run_points_essential",
+    "mvs_batch_run_points_essential", "mvs_ctx_set_essential_confidence", "mvs_ctx_essential_hypotheses_run",
+    "mvs_batch_download_hypotheses_run",
 ]
 
 
@@ -206,6 +207,10 @@ def lib():
         _lib.mvs_ctx_set_half_batches.restype = C.c_int
         _lib.mvs_ctx_set_half_batches.argtypes = [C.c_void_p, C.c_int]
         _lib.mvs_ctx_stream.argtypes = [C.c_void_p]
+        _lib.mvs_ctx_set_essential_confidence.restype = C.c_int
+        _lib.mvs_ctx_set_essential_confidence.argtypes = [C.c_void_p, C.c_double]
+        _lib.mvs_ctx_essential_hypotheses_run.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        _lib.mvs_batch_download_hypotheses_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]
         _lib.mvs_ctx_destroy.argtypes = [C.c_void_p]
         _lib.mvs_batch_destroy.argtypes = [C.c_void_p]
         _lib.mvs_seq_destroy.argtypes = [C.c_void_p]
@@ -316,6 +321,17 @@ class Context:
         """Large batches as two halves on two streams (default) or every launch on the one stream."""
         self._check(lib().mvs_ctx_set_half_batches(self._h, C.c_int(1 if enable else 0)), "mvs_ctx_set_half_batches")
 
+    def set_essential_confidence(self, p):
+        """Confidence level of the five-point RANSAC: 0 (default) runs every hypothesis, 0 < p < 1 stops each pair at the first
+        checkpoint (64, 128, ...) at which its best count reaches that confidence (mvs_ctx_set_essential_confidence)."""
+        self._check(lib().mvs_ctx_set_essential_confidence(self._h, C.c_double(p)), "mvs_ctx_set_essential_confidence")
+
+    def essential_hypotheses_run(self):
+        """hypotheses that took part in the last single-shot five-point call (mvs_ctx_essential_hypotheses_run)"""
+        n = C.c_int32(0)
+        self._check(lib().mvs_ctx_essential_hypotheses_run(self._h, C.byref(n)), "mvs_ctx_essential_hypotheses_run")
+        return n.value
+
     def _check(self, st, what, allow_no_model=False):
         if st == MVS_OK or (allow_no_model and st == MVS_NO_MODEL):
             return st
@@ -425,6 +441,7 @@ class Context:
     def two_view_essential(self, uv1, uv2, K, params):
         out, res = self._pose_call("mvs_two_view_essential", uv1, uv2, K, mid=(C.byref(params),))
         out["raw"] = bytes(res)
+        out["hypotheses_run"] = self.essential_hypotheses_run()
         return out
 
     def five_point(self, p1, p2):
@@ -450,7 +467,7 @@ class Context:
             C.byref(bc), C.byref(br), _ptr(nr, C.c_int32), _ptr(cnt, C.c_int32))
         self._check(st, "mvs_ransac_essential", allow_no_model=True)
         out = dict(ok=st == MVS_OK, E=E, mask=mask[:m], best_hyp=bh.value, best_root=bt.value, best_count=bc.value,
-                   best_residual=br.value)
+                   best_residual=br.value, hypotheses_run=self.essential_hypotheses_run())
         if per_hyp:
             out["n_roots"], out["count"] = nr, cnt
         return out
@@ -790,6 +807,13 @@ class Batch:
     def run_points_essential(self, params, uv1, uv2, m):
         """run_points() with the five-point essential-matrix RANSAC in place of the 8-point one (mvs_batch_run_points_essential)"""
         self._run_points("mvs_batch_run_points_essential", params, uv1, uv2, m)
+
+    def hypotheses_run(self):
+        """per pair, the hypotheses that took part in the last run_points_essential (mvs_batch_download_hypotheses_run)"""
+        out = np.zeros(self.n_pairs, dtype=np.int32)
+        self.ctx._check(lib().mvs_batch_download_hypotheses_run(self._h, C.c_int(0), C.c_int(self.n_pairs), _ptr(out, C.c_int32)),
+                        "mvs_batch_download_hypotheses_run")
+        return out
 
     def device_state(self):
         """opaque bytes of the batch's device-resident state (mvs_batch_device_state): for the diagnostics library's audit"""

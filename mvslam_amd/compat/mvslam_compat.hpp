@@ -379,6 +379,12 @@ inline mvs_ctx *context()
         const mvs_status st = mvs_ctx_create(0, &h.ctx);
         if (st != MVS_OK)
             throw std::runtime_error(std::string("mvSLAM HIP backend: ") + mvs_status_str(st));
+#ifdef MVSLAM_ESSENTIAL_CONFIDENCE
+        // the five-point RANSAC stops at this confidence level (the reference passes VF_MATCH_CONFIDENCE_LEVEL = 0.99 to
+        // cv::findEssentialMat, sfm-solve.cpp:22-23,58); undefined: every hypothesis runs
+        if (mvs_ctx_set_essential_confidence(h.ctx, MVSLAM_ESSENTIAL_CONFIDENCE) != MVS_OK)
+            throw std::runtime_error("mvSLAM HIP backend: MVSLAM_ESSENTIAL_CONFIDENCE must be 0 or in (0, 1)");
+#endif
     }
     return h.ctx;
 }

@@ -43,6 +43,12 @@ struct mvs_ctx {
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool half_batches = true;
+    double e5_confidence = 0.0;   // mvs_ctx_set_essential_confidence: 0 = every hypothesis of the five-point RANSAC runs
+    // n_run of the last single-shot five-point call: none yet, or that call failed before its RANSAC was enqueued (-1); in
+    // e5_single_run (0: known on the host -- fewer than eight matches, or no confidence level so every hypothesis ran -- or saved
+    // from a scratch batch that has been replaced since); in scratch->e5_nrun[0] (1: a confidence level was set)
+    int e5_single = -1;
+    int32_t e5_single_run = 0;
     int cu_count = 256;   // hipDeviceAttributeMultiprocessorCount of `device` (mvs_ctx_create); MI355X: 256
     std::string err;
     mvs_batch *scratch = nullptr;  // batch of one pair backing the single-shot entry points
@@ -85,6 +91,13 @@ struct mvs_batch {
     int32_t *e5_nroots = nullptr;   // [n_pairs][e5_cap]
     int32_t *e5_count = nullptr;    // [n_pairs][e5_cap][10]
     int32_t *e5_root = nullptr;     // [n_pairs] root index of the winner
+    int32_t *e5_nrun = nullptr;     // [n_pairs] checkpoint each pair stopped at, written by a call with a confidence level
+    int32_t *e5_cmax = nullptr;     // [n_pairs] largest count so far, between the rounds of such a call
+    // the last five-point call on this batch (mvs_batch_download_hypotheses_run): its pairs, hypotheses and confidence level
+    bool e5_ran = false;
+    int e5_last_n = 0;
+    double e5_last_conf = 0.0;
+    std::vector<int32_t> e5_host_run;   // n_run of that call where it had no confidence level: known without the device
     hipEvent_t ev[8]{};
     RefineDev refine{};     // allocated by the first mvs_batch_refine
     bool refine_ran = false;
@@ -356,7 +369,9 @@ static mvs_status ensure_e5(mvs_batch *b, int num_hypotheses)
     DevGroup g(b->ctx, b->blocks);
     g.add(b->e5_nroots, P * H);
     g.add(b->e5_count, P * H * kE5MaxRoots);
-    if (!b->e5_root) g.add(b->e5_root, P);
+    const bool first = !b->e5_root;
+    if (first)
+        g.add(b->e5_root, P).add(b->e5_nrun, P).add(b->e5_cmax, P);
     const mvs_status st = g.commit();
     if (st != MVS_OK)
         return st;
@@ -387,7 +402,15 @@ static void enqueue_model(mvs_batch *b, Estimator est, const RunParams &rp, int 
         launch_finalize(b->d, rp, n, kFinalizeFull, s);
         break;
     case Estimator::kFivePoint:
-        launch_essential5(b->d, rp, n, b->e5_nroots, b->e5_count, b->e5_cap, b->e5_root, s);
+        launch_essential5(b->d, rp, n, b->e5_nroots, b->e5_count, b->e5_cap, b->e5_root, b->e5_nrun, b->e5_cmax,
+                          b->ctx->e5_confidence, s);
+        b->e5_ran = true;
+        b->e5_last_n = n;
+        b->e5_last_conf = b->ctx->e5_confidence;
+        if (b == b->ctx->scratch) {   // (a single-shot call gets here with eight matches or more)
+            b->ctx->e5_single = b->e5_last_conf > 0.0 ? 1 : 0;
+            b->ctx->e5_single_run = rp.num_hypotheses;
+        }
         launch_finalize(b->d, rp, n, kFinalizeEssential, s);
         break;
     }
@@ -943,6 +966,27 @@ mvs_status mvs_ctx_set_half_batches(mvs_ctx *ctx, int enable)
     return MVS_OK;
 }
 
+mvs_status mvs_ctx_set_essential_confidence(mvs_ctx *ctx, double confidence)
+{
+    if (!ctx || !(confidence == 0.0 || (confidence > 0.0 && confidence < 1.0)))   // (a NaN fails both)
+        return MVS_ERR_INVALID_ARG;
+    ctx->e5_confidence = confidence == 0.0 ? 0.0 : confidence;   // (-0.0 is 0)
+    return MVS_OK;
+}
+
+mvs_status mvs_ctx_essential_hypotheses_run(mvs_ctx *ctx, int32_t *n_run)
+{
+    if (!ctx || !n_run || ctx->e5_single < 0)
+        return MVS_ERR_INVALID_ARG;
+    *n_run = ctx->e5_single_run;
+    if (ctx->e5_single == 0)
+        return MVS_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(n_run, ctx->scratch->e5_nrun, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, sync_stream(ctx));
+    return MVS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // batches
 // ---------------------------------------------------------------------------------------------
@@ -1339,7 +1383,33 @@ mvs_status mvs_batch_run_points_essential(mvs_batch *b, const mvs_params *params
     if (st != MVS_OK)
         return st;
     enqueue_model(b, Estimator::kFivePoint, to_run(*params), n_active);
+    if (!(b->e5_last_conf > 0.0)) {   // every hypothesis of every pair with eight matches or more (sfm-solve.cpp:37)
+        b->e5_host_run.resize(n_active);
+        for (int p = 0; p < n_active; ++p)
+            b->e5_host_run[p] = m[p] >= 8 ? params->num_hypotheses : 0;
+    }
     HIP_TRY(b->ctx, hipGetLastError());
+    return MVS_OK;
+}
+
+mvs_status mvs_batch_download_hypotheses_run(mvs_batch *b, int first, int count, int32_t *n_run)
+{
+    if (!b || !n_run || first < 0 || count < 1 || first + count > b->d.n_pairs || !b->e5_ran)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = b->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // pairs the last call did not reach: 0.  The others: the checkpoint its rounds left on the device, or, where every
+    // hypothesis ran, what the call worked out from its match counts
+    std::fill(n_run, n_run + count, 0);
+    const int reached = std::min(count, b->e5_last_n - first);
+    if (reached < 1)
+        return MVS_OK;
+    if (!(b->e5_last_conf > 0.0)) {
+        std::copy(b->e5_host_run.begin() + first, b->e5_host_run.begin() + first + reached, n_run);
+        return MVS_OK;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(n_run, b->e5_nrun + first, (size_t)reached * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }
 
@@ -1697,6 +1767,12 @@ static mvs_status ensure_scratch(mvs_ctx *ctx, int max_kp, int desc_bytes)
         return MVS_OK;
     if (ctx->scratch) {
         max_kp = std::max(max_kp, ctx->scratch->d.max_kp);
+        if (ctx->e5_single == 1) {   // mvs_ctx_essential_hypotheses_run outlives the batch it would read
+            HIP_TRY(ctx, hipMemcpyAsync(&ctx->e5_single_run, ctx->scratch->e5_nrun, sizeof(int32_t), hipMemcpyDeviceToHost,
+                                        ctx->stream));
+            HIP_TRY(ctx, sync_stream(ctx));
+            ctx->e5_single = 0;
+        }
         mvs_batch_destroy(ctx->scratch);
         ctx->scratch = nullptr;
     }
@@ -1855,6 +1931,8 @@ static mvs_status two_view_impl(mvs_ctx *ctx, Estimator est, const double *p1_uv
 {
     if (!ctx || !p1_uv || !p2_uv || !K || m < 0)
         return MVS_ERR_INVALID_ARG;
+    if (est == Estimator::kFivePoint)
+        ctx->e5_single = -1;   // a call that fails before its RANSAC is enqueued leaves no n_run behind
     mvs_status st = check_params(params);
     if (st != MVS_OK)
         return st;
@@ -1867,6 +1945,10 @@ static mvs_status two_view_impl(mvs_ctx *ctx, Estimator est, const double *p1_uv
     if (m < 8) {  // sfm-solve.cpp:37 asserts; estimator-RANSAC.cpp:25-29 returns false
         if (result)
             *result = res;
+        if (est == Estimator::kFivePoint && m >= 1) {
+            ctx->e5_single = 0;
+            ctx->e5_single_run = 0;
+        }
         return m < 1 ? MVS_ERR_INVALID_ARG : MVS_NO_MODEL;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2182,12 +2264,16 @@ mvs_status mvs_ransac_essential(mvs_ctx *ctx, const double *p1_xy, const double 
         return MVS_ERR_INVALID_ARG;
     if (!(max_error_sq > 2.220446049250313e-16))  // estimator-RANSAC.cpp:12
         return MVS_ERR_INVALID_ARG;
+    ctx->e5_single = -1;   // a call that fails before its RANSAC is enqueued leaves no n_run behind
     if (best_hyp) *best_hyp = -1;
     if (best_root) *best_root = -1;
     if (best_count) *best_count = 0;
     if (best_residual) *best_residual = 0.0;
-    if (m < 8)
+    if (m < 8) {
+        ctx->e5_single = 0;
+        ctx->e5_single_run = 0;
         return MVS_NO_MODEL;  // sfm-solve.cpp:37
+    }
     RunParams rp;
     mvs_status st = stage_ideal(ctx, Estimator::kFivePoint, p1_xy, p2_xy, m, max_error_sq, num_hypotheses, sampler, seed, &rp);
     if (st != MVS_OK)
@@ -2197,11 +2283,22 @@ mvs_status mvs_ransac_essential(mvs_ctx *ctx, const double *p1_xy, const double 
     mvs_pair_result res;
     if ((st = fetch_single(ctx, m, &res, nullptr, nullptr, inlier_mask)) != MVS_OK)
         return st;
+    // the tables: rows below the pair's n_run as counted, the rows from there on (not defined on the device) cleared
     const size_t H = (size_t)num_hypotheses;
-    if (n_roots)
-        HIP_TRY(ctx, hipMemcpy(n_roots, b->e5_nroots, H * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (count)
-        HIP_TRY(ctx, hipMemcpy(count, b->e5_count, H * kE5MaxRoots * sizeof(int32_t), hipMemcpyDeviceToHost));
+    size_t T = H;
+    if ((n_roots || count) && ctx->e5_confidence > 0.0) {
+        int32_t n_run = 0;
+        HIP_TRY(ctx, hipMemcpy(&n_run, b->e5_nrun, sizeof(int32_t), hipMemcpyDeviceToHost));
+        T = std::min(H, (size_t)std::max(n_run, 0));
+    }
+    if (n_roots) {
+        HIP_TRY(ctx, hipMemcpy(n_roots, b->e5_nroots, T * sizeof(int32_t), hipMemcpyDeviceToHost));
+        std::fill(n_roots + T, n_roots + H, 0);
+    }
+    if (count) {
+        HIP_TRY(ctx, hipMemcpy(count, b->e5_count, T * kE5MaxRoots * sizeof(int32_t), hipMemcpyDeviceToHost));
+        std::fill(count + T * kE5MaxRoots, count + H * kE5MaxRoots, -1);
+    }
     if (best_root)
         HIP_TRY(ctx, hipMemcpy(best_root, b->e5_root, sizeof(int32_t), hipMemcpyDeviceToHost));
     if (E) std::memcpy(E, res.E, sizeof(res.E));

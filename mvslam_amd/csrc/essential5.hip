@@ -8,7 +8,11 @@
 //            inliers, i ascending (a sum that is not finite counts as +infinity), worked out only for the models tied at the
 //            largest count (estimator-RANSAC.cpp:76-84); then
 //            the smaller hypothesis id; then the smaller root index;
-//   no early exit (every hypothesis runs; VF_MATCH_CONFIDENCE_LEVEL is unused), no refit, no projection (sfm-solve.cpp:62-63).
+//   stop     confidence = 0 (the default): every hypothesis runs.  0 < confidence < 1 (VF_MATCH_CONFIDENCE_LEVEL,
+//            sfm-solve.cpp:22-23,58): per pair, at the checkpoints T_0 = min(64, H), T_{j+1} = min(2 T_j, H), the rule
+//            e5_confident() of five_point.hpp on the largest count so far; a pair that stops at T (its n_run) gives exactly what
+//            the same call gives with num_hypotheses = T -- hypotheses >= T take no part, counted or not;
+//   no refit, no projection (sfm-solve.cpp:62-63).
 //
 // Layout.  essential5_solve_count_kernel: grid (hypothesis blocks, pairs), one wavefront per workgroup,
 // one hypothesis per lane.  The solver's arrays (10 x 20 elimination matrix, basis, polynomials: kE5Ws = 276 doubles) are the
@@ -17,6 +21,16 @@
 // n_roots and ten int32 counts per hypothesis go to device memory.  essential5_select_kernel: one wavefront per pair reduces the
 // count table, RE-SOLVES the hypotheses tied at the largest count with the same device function (the same bits) for their
 // residuals, re-solves the winner once more for E and writes the mask.
+//
+// Without a confidence level these two kernels are the stage, the code and the launches of before the rule existed.  With one
+// the stage is a fixed sequence of rounds, one per checkpoint (their number depends on H alone), plain launches on the one
+// stream and no host synchronisation: round 0 is essential5_solve_count_kernel on the first 64 hypotheses; round j > 0 is
+// e5_solve_count_rounds_kernel -- the same text (essential5_kernels.inc) with a first-hypothesis argument, in which a workgroup
+// of a pair that has stopped returns after reading the pair's n_run word: block-uniform, before any work -- over
+// [T_{j-1}, T_j); each round ends with e5_horizon_kernel, one wavefront per pair, which folds the new counts into the pair's
+// running maximum, applies the rule and writes n_run = T_j for a pair that stops (-1: still running).  e5_select_rounds_kernel
+// is the selection with its hypothesis bound read from n_run.  No atomics, no flag is waited for: the order of the launches on
+// the stream is the only synchronisation.
 #include "kernels.hpp"
 #include "sampler.hpp"
 #include "five_point.hpp"
@@ -49,44 +63,37 @@ __device__ __forceinline__ int e5_solve_hyp(const double *P, int M, uint64_t see
     return five_point(p1, p2, w);
 }
 
-__global__ __launch_bounds__(kE5Lanes) void essential5_solve_count_kernel(BatchDev b, RunParams rp, int32_t *n_roots, int32_t *count,
-                                                                          int h_stride)
+// Checkpoint j = [h_first, h_last) just counted.  One wavefront per pair: the largest count of the range joins the pair's running
+// maximum c_max, and the pair stops here -- n_run = h_last -- if this is the last checkpoint or e5_confident() says so; a pair
+// that goes on keeps n_run = -1.  The first checkpoint (h_first = 0) reads neither word: it initialises both, and gives the
+// pairs with fewer than eight matches n_run = 0.
+__global__ __launch_bounds__(kE5Lanes) void e5_horizon_kernel(BatchDev b, const int32_t *count, int h_stride, int h_first,
+                                                              int h_last, int is_last, int j, double confidence, int32_t *n_run,
+                                                              int32_t *c_max)
 {
-    extern __shared__ double s_w[];
-    const int pair = blockIdx.y, lane = threadIdx.x;
+    const int pair = blockIdx.x, lane = threadIdx.x;
     const int M = min(b.M[pair], b.max_kp);
-    if (M < 8)   // sfm-solve.cpp:37; the selection reports "no model" without reading the tables
-        return;
-    const int H = rp.num_hypotheses;
-    const int h = blockIdx.x * kE5Lanes + lane;
-    const bool live = h < H;
-    const double *P = b.pts + (size_t)pair * b.max_kp * 4;
-    const E5Ws w{s_w + lane, kE5Lanes};
-    const double thr = e5_max_error_sq(b, rp, pair);
-    int n = 0;
-    if (live)
-        n = e5_solve_hyp(P, M, rp.seed + (uint64_t)b.gidx[pair], (uint32_t)h, rp.sampler, w);
-    int32_t *cout = count + ((size_t)pair * h_stride + (live ? h : 0)) * kE5MaxRoots;
-    for (int r = 0; r < kE5MaxRoots; ++r) {
-        int cnt = -1;
-        if (r < n) {
-            double E[9];
-#pragma unroll
-            for (int e = 0; e < 9; ++e)
-                E[e] = w(9 * r + e);
-            cnt = 0;
-            for (int i = 0; i < M; ++i) {
-                const double4 q = *reinterpret_cast<const double4 *>(P + (size_t)i * 4);
-                double num, den;
-                e5_sampson(E, q.x, q.y, q.z, q.w, num, den);
-                cnt += e5_inlier(num, den, thr) ? 1 : 0;
-            }
-        }
-        if (live)
-            cout[r] = cnt;
+    int state = -1, c = -1;
+    if (M < 8)
+        state = 0;
+    else if (h_first > 0) {
+        state = n_run[pair];
+        c = c_max[pair];
     }
-    if (live)
-        n_roots[(size_t)pair * h_stride + h] = n;
+    if (state < 0) {   // (uniform over the wavefront: a running pair)
+        const int32_t *C = count + (size_t)pair * h_stride * kE5MaxRoots;
+        for (int k = h_first * kE5MaxRoots + lane; k < h_last * kE5MaxRoots; k += kE5Lanes)
+            c = max(c, C[k]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1)
+            c = max(c, __shfl_xor(c, o));
+        if (is_last || e5_confident(c, M, j, confidence))
+            state = h_last;
+    }
+    if (lane == 0) {
+        n_run[pair] = state;
+        c_max[pair] = c;
+    }
 }
 
 struct E5Best {
@@ -102,121 +109,15 @@ __device__ __forceinline__ bool e5_better(const E5Best &a, const E5Best &b)   //
     return a.root < b.root;
 }
 
-__global__ __launch_bounds__(kE5Lanes) void essential5_select_kernel(BatchDev b, RunParams rp, const int32_t *n_roots,
-                                                                     const int32_t *count, int h_stride, int32_t *best_root)
-{
-    extern __shared__ double s_w[];
-    __shared__ double s_E[9];
-    const int pair = blockIdx.x, lane = threadIdx.x;
-    const int M = min(b.M[pair], b.max_kp);
-    const int H = rp.num_hypotheses;
-    mvs_pair_result *res = b.results + pair;
-    uint8_t *mask = b.mask + (size_t)pair * b.max_kp;
-    const double *P = b.pts + (size_t)pair * b.max_kp * 4;
-    const int32_t *C = count + (size_t)pair * h_stride * kE5MaxRoots;
-    const E5Ws w{s_w + lane, kE5Lanes};
-
-    for (int i = M + lane; i < b.max_kp; i += kE5Lanes)   // rows past the match list: cleared (deterministic downloads)
-        mask[i] = 0;
-    if (lane < 9) {   // the pose of a pair that ends without one is zero, whatever ran on the batch before
-        res->R1to2[lane] = 0.0;
-        res->R[lane] = 0.0;
-        if (lane < 3) {
-            res->t1to2[lane] = 0.0;
-            res->t[lane] = 0.0;
-        }
-    }
-    int best = -1;
-    if (M >= 8)
-        for (int k = lane; k < H * kE5MaxRoots; k += kE5Lanes)
-            best = max(best, C[k]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        best = max(best, __shfl_xor(best, o));
-    if (best < 0) {
-        for (int i = lane; i < M; i += kE5Lanes)
-            mask[i] = 0;
-        if (lane < 9) {
-            res->F[lane] = 0.0;
-            res->E[lane] = 0.0;
-        }
-        if (lane == 0) {
-            res->best_hyp = -1;
-            res->best_count = 0;
-            res->best_residual = 0.0;
-            best_root[pair] = -1;
-        }
-        return;
-    }
-    const double thr = e5_max_error_sq(b, rp, pair);
-    const uint64_t seed = rp.seed + (uint64_t)b.gidx[pair];
-    // ---- residuals of the models tied at the largest count (lane l visits hypotheses l, l + 64, ... ascending) ----
-    E5Best me{0.0, -1, 0};
-    for (int h = lane; h < H; h += kE5Lanes) {
-        unsigned tied = 0;
-        for (int r = 0; r < kE5MaxRoots; ++r)
-            tied |= C[(size_t)h * kE5MaxRoots + r] == best ? 1u << r : 0u;
-        if (!tied)
-            continue;
-        const int n = e5_solve_hyp(P, M, seed, (uint32_t)h, rp.sampler, w);
-        for (int r = 0; r < n; ++r) {
-            if (!((tied >> r) & 1u))
-                continue;
-            double E[9];
-#pragma unroll
-            for (int e = 0; e < 9; ++e)
-                E[e] = w(9 * r + e);
-            double sum = 0.0;
-            for (int i = 0; i < M; ++i) {
-                const double4 q = *reinterpret_cast<const double4 *>(P + (size_t)i * 4);
-                double num, den;
-                e5_sampson(E, q.x, q.y, q.z, q.w, num, den);
-                if (e5_inlier(num, den, thr))
-                    sum += num / den;
-            }
-            const E5Best c{e5_residual_key(sum), h, r};
-            if (e5_better(c, me))
-                me = c;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        E5Best other;
-        other.res = __shfl_xor(me.res, o);
-        other.hyp = __shfl_xor(me.hyp, o);
-        other.root = __shfl_xor(me.root, o);
-        if (e5_better(other, me))
-            me = other;
-    }
-    // ---- the winner's E (solved once more: the same function, the same bits) and its mask ----
-    if (lane == 0) {
-        int n = 0;
-        if (me.hyp >= 0)
-            n = e5_solve_hyp(P, M, seed, (uint32_t)me.hyp, rp.sampler, w);
-        const bool ok = me.hyp >= 0 && me.root < n;
-        for (int e = 0; e < 9; ++e) {
-            const double v = ok ? w(9 * me.root + e) : 0.0;
-            s_E[e] = v;
-            res->F[e] = v;
-            res->E[e] = v;
-        }
-        res->best_hyp = ok ? me.hyp : -1;
-        res->best_count = ok ? best : 0;
-        res->best_residual = ok ? me.res : 0.0;
-        best_root[pair] = ok ? me.root : -1;
-    }
-    __syncthreads();
-    double E[9];
-#pragma unroll
-    for (int e = 0; e < 9; ++e)
-        E[e] = s_E[e];
-    for (int i = lane; i < M; i += kE5Lanes) {
-        const double4 q = *reinterpret_cast<const double4 *>(P + (size_t)i * 4);
-        double num, den;
-        e5_sampson(E, q.x, q.y, q.z, q.w, num, den);
-        mask[i] = e5_inlier(num, den, thr) ? 1 : 0;
-    }
-}
+// The solve + count kernel and the selection kernel, once as they were before the termination rule and once for its rounds
+// (essential5_kernels.inc).  The kernels of the rule are named e5_*: tests/test_five_point_host.py expects exactly three
+// kernels whose name holds "essential5" or "five_point_kernel", the ones a call without a confidence level uses.
+#define E5_ROUNDS 0
+#include "essential5_kernels.inc"
+#undef E5_ROUNDS
+#define E5_ROUNDS 1
+#include "essential5_kernels.inc"
+#undef E5_ROUNDS
 
 // mvs_five_point: one solve by lane 0 (workspace stride 1)
 __global__ __launch_bounds__(64) void five_point_kernel(const double *p1, const double *p2, double *Eout, int *nout)
@@ -241,20 +142,46 @@ hipError_t essential5_prepare()
 {
     hipError_t e = hipFuncSetAttribute((const void *)essential5_solve_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)kE5LdsBytes);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void *)essential5_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kE5LdsBytes);
+    for (const void *k : {(const void *)essential5_select_kernel, (const void *)e5_solve_count_rounds_kernel,
+                          (const void *)e5_select_rounds_kernel})
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kE5LdsBytes);
     return e;
 }
 
+static_assert(kE5Checkpoint0 == kE5HypPerBlock, "the first checkpoint is one workgroup of the solve + count kernel");
+
 void launch_essential5(const BatchDev &b, const RunParams &rp, int n_active, int32_t *n_roots, int32_t *count, int h_stride,
-                       int32_t *best_root, hipStream_t stream)
+                       int32_t *best_root, int32_t *n_run, int32_t *c_max, double confidence, hipStream_t stream)
 {
-    const int G = (rp.num_hypotheses + kE5Lanes - 1) / kE5Lanes;
-    hipLaunchKernelGGL(essential5_solve_count_kernel, dim3(G, n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp, n_roots, count,
-                       h_stride);
-    hipLaunchKernelGGL(essential5_select_kernel, dim3(n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp, n_roots, count, h_stride,
-                       best_root);
+    const int H = rp.num_hypotheses;
+    if (!(confidence > 0.0)) {   // every hypothesis runs: the two launches there were before the termination rule
+        const int G = (H + kE5Lanes - 1) / kE5Lanes;
+        hipLaunchKernelGGL(essential5_solve_count_kernel, dim3(G, n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp, n_roots,
+                           count, h_stride);
+        hipLaunchKernelGGL(essential5_select_kernel, dim3(n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp, n_roots, count,
+                           h_stride, best_root);
+        return;
+    }
+    // round j counts [first, last) and tests at last; the first round is the plain kernel on a grid of one block per pair
+    int first = 0, last = e5_checkpoint_first(H);
+    for (int j = 0;; ++j) {
+        const int G = (last - first + kE5Lanes - 1) / kE5Lanes;
+        if (j == 0)
+            hipLaunchKernelGGL(essential5_solve_count_kernel, dim3(G, n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp,
+                               n_roots, count, h_stride);
+        else
+            hipLaunchKernelGGL(e5_solve_count_rounds_kernel, dim3(G, n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp,
+                               n_roots, count, h_stride, first, n_run);
+        hipLaunchKernelGGL(e5_horizon_kernel, dim3(n_active), dim3(kE5Lanes), 0, stream, b, count, h_stride, first, last,
+                           last == H ? 1 : 0, j, confidence, n_run, c_max);
+        if (last == H)
+            break;
+        first = last;
+        last = e5_checkpoint_next(last, H);
+    }
+    hipLaunchKernelGGL(e5_select_rounds_kernel, dim3(n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp, n_roots, count, h_stride,
+                       best_root, n_run);
 }
 
 void launch_five_point(const double *p1, const double *p2, double *E, int *n, hipStream_t stream)

@@ -413,4 +413,30 @@ MVS_DEV bool e5_inlier(double num, double den, double thr) { return den > 0.0 &&
 // a residual sum that is not finite (overflowing terms) counts as the worst possible one, so that the selection order is total
 MVS_DEV double e5_residual_key(double sum) { return sum <= kE5Huge ? sum : __builtin_inf(); }
 
+// ---- the termination rule of the five-point RANSAC (essential5.hip) -----------------------------------
+// With a confidence level p in (0, 1) a pair's hypotheses are counted up to a CHECKPOINT and no further once the best count
+// seen so far makes another all-inlier sample unnecessary with probability p.  Checkpoints: T_0 = min(kE5Checkpoint0, H),
+// T_{j+1} = min(2 T_j, H) (H = num_hypotheses; kE5Checkpoint0 = one workgroup of the solve + count kernel).  At T_j < H, with
+// c the largest count over (h < T_j, root) and M the pair's matches, the pair stops iff c >= 1 and
+//   (1 - (c / M)^5)^(64 2^j) <= 1 - p,   evaluated as  w = c / M, w2 = w w, w5 = (w2 w2) w, q = 1 - w5, q squared 6 + j times;
+// at T_j = H it stops whatever c is.  Every operation is one rounded binary64 operation (no libm: a log or a pow that differs
+// in its last place between host and device would move the answer by a whole block of hypotheses; no contraction: 1 - w5 is a
+// subtraction, never the tail of an fma).  p = 0 switches the rule off: no checkpoints, every hypothesis runs.
+constexpr int kE5Checkpoint0 = 64;
+// (constexpr: the launch sequence on the host and a kernel share them)
+constexpr int e5_checkpoint_first(int H) { return H < kE5Checkpoint0 ? H : kE5Checkpoint0; }
+constexpr int e5_checkpoint_next(int T, int H) { return T >= H - T ? H : 2 * T; }   // min(2 T, H) without overflow
+MVS_DEV bool e5_confident(int c, int M, int j, double p)
+{
+    if (c < 1)
+        return false;
+    const double w = (double)c / (double)M;
+    const double w2 = w * w;
+    const double w5 = (w2 * w2) * w;
+    double x = 1.0 - w5;
+    for (int i = 0; i < 6 + j; ++i)
+        x = x * x;
+    return x <= 1.0 - p;
+}
+
 }  // namespace mvs

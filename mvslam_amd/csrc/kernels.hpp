@@ -468,9 +468,13 @@ hipError_t essential5_prepare();
 // pairs [0, n_active): every hypothesis solved and counted on the pair's resident normalised points, then the selection, which
 // writes results[p].{best_hyp, best_count, best_residual, F, E} and the mask (rows past M cleared); launch_finalize with
 // kFinalizeEssential completes the record.  n_roots: [P][h_stride], count: [P][h_stride][10] (-1 past n_roots);
-// best_root: [P] root index of the winner (-1: none)
+// best_root: [P] root index of the winner (-1: none).  confidence: 0 = every hypothesis runs; in (0, 1) = the termination rule of
+// five_point.hpp, applied per pair at the checkpoints 64, 128, ... by one round of launches each (no host synchronisation).
+// n_run: [P], written only with a confidence level: the checkpoint each pair stopped at (0: fewer than eight matches); rows
+// >= n_run of the tables are not defined.  c_max: [P] scratch of the rounds.  With confidence 0 neither is touched and the two
+// launches are those of before the rule existed
 void launch_essential5(const BatchDev &b, const RunParams &rp, int n_active, int32_t *n_roots, int32_t *count, int h_stride,
-                       int32_t *best_root, hipStream_t stream);
+                       int32_t *best_root, int32_t *n_run, int32_t *c_max, double confidence, hipStream_t stream);
 // the minimal solver alone: p1 / p2 5 x (x, y), E [10][9], n
 void launch_five_point(const double *p1, const double *p2, double *E, int *n, hipStream_t stream);
 
