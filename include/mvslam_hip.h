@@ -41,6 +41,9 @@ extern "C" {
  * symbols only): the five-point essential-matrix RANSAC beside the 8-point one */
 /* still 4: mvs_ctx_set_essential_confidence, mvs_ctx_essential_hypotheses_run and mvs_batch_download_hypotheses_run are additions
  * (new symbols only): the five-point RANSAC's optional termination rule; off by default, no struct changed */
+/* still 4: mvs_image_pair_essential, mvs_batch_run_essential, mvs_seq_run_essential, mvs_seq_download_hypotheses_run and
+ * mvs_batch_download_essential_tables are additions (new symbols only): the five-point RANSAC behind the matcher, for one pair,
+ * a batch and a sequence; no existing entry point or struct changed */
 #define MVS_ABI_VERSION 4
 
 typedef enum mvs_status {
@@ -151,6 +154,14 @@ mvs_status mvs_image_pair(mvs_ctx *ctx, const uint8_t *base_desc, const float *b
                           const uint8_t *pair_desc, const float *pair_kp, int n_pair, int desc_bytes, const double K[9],
                           const mvs_params *params, mvs_pair_result *result, mvs_match *matches, uint8_t *inlier_mask,
                           double *points_xyz, int64_t *point_idx);
+/* mvs_image_pair with the five-point branch of find_essential_matrix (sfm-solve.cpp:42-63) in place of the 8-point RANSAC:
+ * what mvs_match_hamming, a host gather of kp[trainIdx] / kp[queryIdx] and mvs_two_view_essential return, in one upload, one
+ * synchronisation and one download.  Same arguments, outputs and return codes.  Honours mvs_ctx_set_essential_confidence and
+ * feeds mvs_ctx_essential_hypotheses_run (0 for a pair with fewer than eight matches). */
+mvs_status mvs_image_pair_essential(mvs_ctx *ctx, const uint8_t *base_desc, const float *base_kp, int n_base,
+                                    const uint8_t *pair_desc, const float *pair_kp, int n_pair, int desc_bytes,
+                                    const double K[9], const mvs_params *params, mvs_pair_result *result, mvs_match *matches,
+                                    uint8_t *inlier_mask, double *points_xyz, int64_t *point_idx);
 
 /* sfm_triangulate(p1, p2, K, pose1, pose2, points, point_indexes) (sfm-solve.cpp:370-394, decl sfm.hpp:47-53).
  * R1to2 / t1to2 = (pose2^-1 * pose1), composed by the caller-side shim exactly as the reference does. */
@@ -285,11 +296,24 @@ mvs_status mvs_batch_run_points(mvs_batch *b, const mvs_params *params, int n_ac
  * launches: no half batches, no captured graph. */
 mvs_status mvs_batch_run_points_essential(mvs_batch *b, const mvs_params *params, int n_active, const double *uv1,
                                           const double *uv2, const int32_t *m);
-/* n_run[count] of pairs [first, first + count) in the batch's LAST mvs_batch_run_points_essential: num_hypotheses, or the
- * checkpoint the pair stopped at under a confidence level (the call then waits for the ctx stream); 0 for a pair with fewer
- * than eight matches and for a pair at or beyond that call's n_active, whatever an earlier call did with it.
+/* mvs_batch_run with the five-point branch: matcher -> five-point RANSAC -> decomposition -> triangulation on the resident
+ * descriptors and keypoints of pairs [0, n_active), no host round trip in between.  One stream, plain launches (no half
+ * batches, no captured graph); honours mvs_ctx_set_essential_confidence.  Followed by the usual mvs_batch_sync and
+ * mvs_batch_download, match list included. */
+mvs_status mvs_batch_run_essential(mvs_batch *b, const mvs_params *params, int n_active);
+/* n_run[count] of pairs [first, first + count) in the batch's LAST mvs_batch_run_points_essential or mvs_batch_run_essential:
+ * num_hypotheses, or the checkpoint the pair stopped at under a confidence level (the call then waits for the ctx stream, as
+ * it does after mvs_batch_run_essential, whose match counts only the device knows); 0 for a pair with fewer than eight
+ * matches and for a pair at or beyond that call's n_active, whatever an earlier call did with it.
  * MVS_ERR_INVALID_ARG before the first such call. */
 mvs_status mvs_batch_download_hypotheses_run(mvs_batch *b, int first, int count, int32_t *n_run);
+/* The per-hypothesis tables of pairs [first, first + count) in the batch's last five-point run of either kind, as
+ * mvs_ransac_essential exports them: n_roots [count][num_hypotheses], count_tbl [count][num_hypotheses][10] with -1 past
+ * n_roots; from the pair's n_run on (see above; 0 with fewer than eight matches) n_roots = 0 and count = -1.  Either pointer
+ * may be NULL.  Waits for the ctx stream.  MVS_ERR_INVALID_ARG before the first such run or when num_hypotheses is not that
+ * run's. */
+mvs_status mvs_batch_download_essential_tables(mvs_batch *b, int first, int count, int num_hypotheses, int32_t *n_roots,
+                                               int32_t *count_tbl);
 
 /* Timed replay: `warmup` untimed + `steps` timed passes over the resident inputs, bracketed by HIP events
  * on the ctx stream.  ms_total: wall ms of the `steps` passes.  ms_kernel[5]: summed ms per kernel over the
@@ -417,6 +441,11 @@ mvs_status mvs_seq_upload(mvs_seq *s, int first, int count, const uint8_t *desc,
                           const double K[9]);
 /* all pairs (batched two-view pipeline) + all tracks (join + batched PnP), asynchronous on the ctx stream */
 mvs_status mvs_seq_run(mvs_seq *s, const mvs_params *two_view, const mvs_pnp_params *pnp);
+/* mvs_seq_run with the five-point RANSAC (mvs_batch_run_essential) for the n_frames - 1 pairs; the join, PnP, optional refit
+ * and scale chain are mvs_seq_run's, and every mvs_seq_download_* / mvs_seq_refine_* call works behind it unchanged */
+mvs_status mvs_seq_run_essential(mvs_seq *s, const mvs_params *two_view, const mvs_pnp_params *pnp);
+/* mvs_batch_download_hypotheses_run for pairs [first, first + count) of the sequence's last mvs_seq_run_essential */
+mvs_status mvs_seq_download_hypotheses_run(mvs_seq *s, int first, int count, int32_t *n_run);
 mvs_status mvs_seq_sync(mvs_seq *s);
 /* `steps` timed passes after `warmup`; ms_total = wall ms of the timed passes (HIP events on the ctx stream) */
 mvs_status mvs_seq_time(mvs_seq *s, const mvs_params *two_view, const mvs_pnp_params *pnp, int warmup, int steps,

@@ -157,7 +157,8 @@ EXPORTS = [
     "mvs_ba_refine_window", "mvs_ba_refine_windows", "mvs_seq_refine_windows", "mvs_seq_window_count",
     "mvs_seq_download_windows", "mvs_five_point", "mvs_ransac_essential", "mvs_two_view_essential",
     "mvs_batch_run_points_essential", "mvs_ctx_set_essential_confidence", "mvs_ctx_essential_hypotheses_run",
-    "mvs_batch_download_hypotheses_run",
+    "mvs_batch_download_hypotheses_run", "mvs_image_pair_essential", "mvs_batch_run_essential",
+    "mvs_batch_download_essential_tables", "mvs_seq_run_essential", "mvs_seq_download_hypotheses_run",
 ]
 
 
@@ -211,6 +212,9 @@ def lib():
         _lib.mvs_ctx_set_essential_confidence.argtypes = [C.c_void_p, C.c_double]
         _lib.mvs_ctx_essential_hypotheses_run.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         _lib.mvs_batch_download_hypotheses_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        _lib.mvs_seq_download_hypotheses_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        _lib.mvs_batch_download_essential_tables.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                                             C.POINTER(C.c_int32)]
         _lib.mvs_ctx_destroy.argtypes = [C.c_void_p]
         _lib.mvs_batch_destroy.argtypes = [C.c_void_p]
         _lib.mvs_seq_destroy.argtypes = [C.c_void_p]
@@ -380,6 +384,16 @@ class Context:
 
     # ImagePair::ImagePair + reconstruct of one pair in one device pass
     def image_pair(self, base_desc, base_kp, pair_desc, pair_kp, K, params):
+        return self._image_pair("mvs_image_pair", base_desc, base_kp, pair_desc, pair_kp, K, params)[0]
+
+    def image_pair_essential(self, base_desc, base_kp, pair_desc, pair_kp, K, params):
+        """image_pair() with the five-point essential-matrix RANSAC in place of the 8-point one (mvs_image_pair_essential)"""
+        out, res = self._image_pair("mvs_image_pair_essential", base_desc, base_kp, pair_desc, pair_kp, K, params)
+        out["raw"] = bytes(res)
+        out["hypotheses_run"] = self.essential_hypotheses_run()
+        return out
+
+    def _image_pair(self, name, base_desc, base_kp, pair_desc, pair_kp, K, params):
         base_desc = np.ascontiguousarray(base_desc, dtype=np.uint8)
         pair_desc = np.ascontiguousarray(pair_desc, dtype=np.uint8)
         base_kp = np.ascontiguousarray(base_kp, dtype=np.float32).reshape(-1, 2)
@@ -390,17 +404,17 @@ class Context:
         mask = np.zeros(max(n2, 1), dtype=np.uint8)
         pts = np.zeros((max(n2, 1), 3))
         idx = np.zeros(max(n2, 1), dtype=np.int64)
-        st = lib().mvs_image_pair(self._h, _ptr(base_desc, C.c_uint8), _ptr(base_kp, C.c_float), C.c_int(n1),
+        st = getattr(lib(), name)(self._h, _ptr(base_desc, C.c_uint8), _ptr(base_kp, C.c_float), C.c_int(n1),
                                   _ptr(pair_desc, C.c_uint8), _ptr(pair_kp, C.c_float), C.c_int(n2),
                                   C.c_int(int(base_desc.shape[1])), _ptr(_f64(K, (9,)), C.c_double), C.byref(params),
                                   C.byref(res), mt.ctypes.data_as(C.c_void_p), _ptr(mask, C.c_uint8),
                                   _ptr(pts, C.c_double), _ptr(idx, C.c_int64))
-        self._check(st, "mvs_image_pair", allow_no_model=True)
+        self._check(st, name, allow_no_model=True)
         r = np.frombuffer(bytes(res), dtype=RESULT_DTYPE)[0]
         out = self._unpack(res, mask, pts, idx, int(r["n_matches"]))
         out["matches"] = mt[:int(r["n_matches"])].copy()
         out["ok"] = st == MVS_OK
-        return out
+        return out, res
 
     @staticmethod
     def _unpack(res, mask, pts, idx, m):
@@ -808,8 +822,25 @@ class Batch:
         """run_points() with the five-point essential-matrix RANSAC in place of the 8-point one (mvs_batch_run_points_essential)"""
         self._run_points("mvs_batch_run_points_essential", params, uv1, uv2, m)
 
+    def run_essential(self, params, n_active=None):
+        """run() with the five-point essential-matrix RANSAC in place of the 8-point one (mvs_batch_run_essential)"""
+        st = lib().mvs_batch_run_essential(self._h, C.byref(params), C.c_int(n_active or self.n_pairs))
+        self.ctx._check(st, "mvs_batch_run_essential")
+
+    def download_essential_tables(self, num_hypotheses, first=0, count=None):
+        """(n_roots [count][H], count [count][H][10]) of the last five-point run of either kind, in ransac_essential()'s
+        convention: count -1 past n_roots, nothing from the pair's n_run on (mvs_batch_download_essential_tables)"""
+        count = count or (self.n_pairs - first)
+        nr = np.zeros((count, num_hypotheses), dtype=np.int32)
+        ct = np.zeros((count, num_hypotheses, 10), dtype=np.int32)
+        st = lib().mvs_batch_download_essential_tables(self._h, C.c_int(first), C.c_int(count), C.c_int(num_hypotheses),
+                                                       _ptr(nr, C.c_int32), _ptr(ct, C.c_int32))
+        self.ctx._check(st, "mvs_batch_download_essential_tables")
+        return nr, ct
+
     def hypotheses_run(self):
-        """per pair, the hypotheses that took part in the last run_points_essential (mvs_batch_download_hypotheses_run)"""
+        """per pair, the hypotheses that took part in the last run_points_essential or run_essential
+        (mvs_batch_download_hypotheses_run)"""
         out = np.zeros(self.n_pairs, dtype=np.int32)
         self.ctx._check(lib().mvs_batch_download_hypotheses_run(self._h, C.c_int(0), C.c_int(self.n_pairs), _ptr(out, C.c_int32)),
                         "mvs_batch_download_hypotheses_run")
@@ -945,6 +976,18 @@ class Sequence:
     def run(self, params, pnp_params):
         self.ctx._check(lib().mvs_seq_run(self._h, C.byref(params), C.byref(pnp_params)), "mvs_seq_run")
         self.ctx._check(lib().mvs_seq_sync(self._h), "mvs_seq_sync")
+
+    def run_essential(self, params, pnp_params):
+        """run() with the five-point essential-matrix RANSAC for the pairs (mvs_seq_run_essential)"""
+        self.ctx._check(lib().mvs_seq_run_essential(self._h, C.byref(params), C.byref(pnp_params)), "mvs_seq_run_essential")
+        self.ctx._check(lib().mvs_seq_sync(self._h), "mvs_seq_sync")
+
+    def download_hypotheses_run(self):
+        """per pair, the hypotheses that took part in the last run_essential (mvs_seq_download_hypotheses_run)"""
+        out = np.zeros(self.n_frames - 1, dtype=np.int32)
+        st = lib().mvs_seq_download_hypotheses_run(self._h, C.c_int(0), C.c_int(self.n_frames - 1), _ptr(out, C.c_int32))
+        self.ctx._check(st, "mvs_seq_download_hypotheses_run")
+        return out
 
     def time(self, params, pnp_params, steps, warmup):
         ms = C.c_float(0)

@@ -945,7 +945,16 @@ public:
         std::vector<double> pts(3 * (size_t)nq);
         std::vector<int64_t> idx(nq);
         mvs_pair_result res;
-#ifdef MVSLAM_USE_ESSENTIAL_5POINT
+#if defined(MVSLAM_USE_ESSENTIAL_5POINT) && defined(MVSLAM_ESSENTIAL_ONE_PASS)
+        // reconstruct() with sfm_solve's five-point branch as ONE device pass (mvs_image_pair_essential): the results of the two
+        // calls below, one upload / synchronisation / download instead of two
+        const mvs_status st = (int)vb.size() >= 2 && nq >= 1
+                                  ? mvs_image_pair_essential(hip::context(), vb.get_descriptors().data.data(), kb.data(),
+                                                             (int)vb.size(), vp.get_descriptors().data.data(), kq.data(), nq,
+                                                             vb.get_descriptors().cols, K.data(), &prm, &res, matches.data(),
+                                                             nullptr, pts.data(), idx.data())
+                                  : MVS_NO_MODEL;
+#elif defined(MVSLAM_USE_ESSENTIAL_5POINT)
         // reconstruct() with sfm_solve's five-point branch: the reference's own two calls (image-pair.cpp:57-65,116-174),
         // match -> gather on the host -> mvs_two_view_essential (the one-pass mvs_image_pair is the 8-point path)
         int nm = 0;

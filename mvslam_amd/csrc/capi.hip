@@ -95,9 +95,10 @@ struct mvs_batch {
     int32_t *e5_cmax = nullptr;     // [n_pairs] largest count so far, between the rounds of such a call
     // the last five-point call on this batch (mvs_batch_download_hypotheses_run): its pairs, hypotheses and confidence level
     bool e5_ran = false;
-    int e5_last_n = 0;
+    int e5_last_n = 0, e5_last_H = 0;
     double e5_last_conf = 0.0;
     std::vector<int32_t> e5_host_run;   // n_run of that call where it had no confidence level: known without the device
+    bool e5_from_desc = false;          // ... unless that call matched descriptors: its match counts are in d.M only
     hipEvent_t ev[8]{};
     RefineDev refine{};     // allocated by the first mvs_batch_refine
     bool refine_ran = false;
@@ -392,8 +393,10 @@ static mvs_status ensure_tables(mvs_batch *b, Estimator est, int num_hypotheses)
     return MVS_ERR_INVALID_ARG;
 }
 
-// model stage + its finalize mode for pairs [0, n) on the ctx stream, plain launches (the tables are grown: ensure_tables)
-static void enqueue_model(mvs_batch *b, Estimator est, const RunParams &rp, int n)
+// model stage + its finalize mode for pairs [0, n) on the ctx stream, plain launches (the tables are grown: ensure_tables).
+// from_desc: the points are those of match_compact, launched in front on the same stream (enqueue_essential) -- the five-point
+// stage then solves and counts with its four-wavefront kernel; the point-fed entry points keep the launches they had
+static void enqueue_model(mvs_batch *b, Estimator est, const RunParams &rp, int n, bool from_desc)
 {
     hipStream_t s = b->ctx->stream;
     switch (est) {
@@ -403,9 +406,11 @@ static void enqueue_model(mvs_batch *b, Estimator est, const RunParams &rp, int 
         break;
     case Estimator::kFivePoint:
         launch_essential5(b->d, rp, n, b->e5_nroots, b->e5_count, b->e5_cap, b->e5_root, b->e5_nrun, b->e5_cmax,
-                          b->ctx->e5_confidence, s);
+                          b->ctx->e5_confidence, from_desc, s);
         b->e5_ran = true;
+        b->e5_from_desc = from_desc;
         b->e5_last_n = n;
+        b->e5_last_H = rp.num_hypotheses;
         b->e5_last_conf = b->ctx->e5_confidence;
         if (b == b->ctx->scratch) {   // (a single-shot call gets here with eight matches or more)
             b->ctx->e5_single = b->e5_last_conf > 0.0 ? 1 : 0;
@@ -1382,7 +1387,7 @@ mvs_status mvs_batch_run_points_essential(mvs_batch *b, const mvs_params *params
     const mvs_status st = stage_batch_points(b, Estimator::kFivePoint, params, n_active, uv1, uv2, m);
     if (st != MVS_OK)
         return st;
-    enqueue_model(b, Estimator::kFivePoint, to_run(*params), n_active);
+    enqueue_model(b, Estimator::kFivePoint, to_run(*params), n_active, false);
     if (!(b->e5_last_conf > 0.0)) {   // every hypothesis of every pair with eight matches or more (sfm-solve.cpp:37)
         b->e5_host_run.resize(n_active);
         for (int p = 0; p < n_active; ++p)
@@ -1390,6 +1395,33 @@ mvs_status mvs_batch_run_points_essential(mvs_batch *b, const mvs_params *params
     }
     HIP_TRY(b->ctx, hipGetLastError());
     return MVS_OK;
+}
+
+// The descriptor-fed five-point pipeline for pairs [0, n): matcher -> match_compact (which leaves the normalised points of the
+// match list in d.pts, where the stage reads them) -> five-point RANSAC -> decomposition and triangulation.  One stream, plain
+// launches.
+static mvs_status enqueue_essential(mvs_batch *b, const RunParams &rp, int n)
+{
+    hipStream_t s = b->ctx->stream;
+    launch_match_topk(b->d, rp, n, s);
+    launch_match_compact(b->d, rp, n, s);
+    enqueue_model(b, Estimator::kFivePoint, rp, n, true);
+    HIP_TRY(b->ctx, hipGetLastError());
+    return MVS_OK;
+}
+
+// mvs_batch_run with find_essential_matrix's five-point branch (sfm-solve.cpp:42-63) in place of the 8-point RANSAC
+mvs_status mvs_batch_run_essential(mvs_batch *b, const mvs_params *params, int n_active)
+{
+    if (!b || n_active < 1 || n_active > b->d.n_pairs)
+        return MVS_ERR_INVALID_ARG;
+    mvs_status st = check_params(params);
+    if (st != MVS_OK)
+        return st;
+    HIP_TRY(b->ctx, hipSetDevice(b->ctx->device));
+    if ((st = ensure_tables(b, Estimator::kFivePoint, params->num_hypotheses)) != MVS_OK)
+        return st;
+    return enqueue_essential(b, to_run(*params), n_active);
 }
 
 mvs_status mvs_batch_download_hypotheses_run(mvs_batch *b, int first, int count, int32_t *n_run)
@@ -1404,11 +1436,49 @@ mvs_status mvs_batch_download_hypotheses_run(mvs_batch *b, int first, int count,
     const int reached = std::min(count, b->e5_last_n - first);
     if (reached < 1)
         return MVS_OK;
-    if (!(b->e5_last_conf > 0.0)) {
+    if (!(b->e5_last_conf > 0.0) && !b->e5_from_desc) {
         std::copy(b->e5_host_run.begin() + first, b->e5_host_run.begin() + first + reached, n_run);
         return MVS_OK;
     }
-    HIP_TRY(ctx, hipMemcpyAsync(n_run, b->e5_nrun + first, (size_t)reached * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    // (without a confidence level behind the matcher: the match counts, which only the device knows)
+    const int32_t *src = b->e5_last_conf > 0.0 ? b->e5_nrun : b->d.M;
+    HIP_TRY(ctx, hipMemcpyAsync(n_run, src + first, (size_t)reached * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, sync_stream(ctx));
+    if (!(b->e5_last_conf > 0.0))
+        for (int p = 0; p < reached; ++p)
+            n_run[p] = n_run[p] >= 8 ? b->e5_last_H : 0;   // sfm-solve.cpp:37
+    return MVS_OK;
+}
+
+// The per-hypothesis tables of the batch's last five-point run, in mvs_ransac_essential's convention: rows below the pair's
+// n_run as counted, the rows from there on (not defined on the device) n_roots = 0, count = -1.
+mvs_status mvs_batch_download_essential_tables(mvs_batch *b, int first, int count, int num_hypotheses, int32_t *n_roots,
+                                               int32_t *count_tbl)
+{
+    if (!b || first < 0 || count < 1 || first + count > b->d.n_pairs || !b->e5_ran || num_hypotheses != b->e5_last_H)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = b->ctx;
+    std::vector<int32_t> run(count);
+    const mvs_status st = mvs_batch_download_hypotheses_run(b, first, count, run.data());
+    if (st != MVS_OK)
+        return st;
+    const size_t H = (size_t)num_hypotheses, cap = (size_t)b->e5_cap;
+    for (int p = 0; p < count; ++p) {
+        const size_t T = std::min(H, (size_t)std::max(run[p], 0)), row = (size_t)(first + p) * cap;
+        if (n_roots) {
+            int32_t *dst = n_roots + (size_t)p * H;
+            if (T)
+                HIP_TRY(ctx, hipMemcpyAsync(dst, b->e5_nroots + row, T * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+            std::fill(dst + T, dst + H, 0);
+        }
+        if (count_tbl) {
+            int32_t *dst = count_tbl + (size_t)p * H * kE5MaxRoots;
+            if (T)
+                HIP_TRY(ctx, hipMemcpyAsync(dst, b->e5_count + row * kE5MaxRoots, T * kE5MaxRoots * sizeof(int32_t),
+                                            hipMemcpyDeviceToHost, ctx->stream));
+            std::fill(dst + T * kE5MaxRoots, dst + H * kE5MaxRoots, -1);
+        }
+    }
     HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }
@@ -1957,7 +2027,7 @@ static mvs_status two_view_impl(mvs_ctx *ctx, Estimator est, const double *p1_uv
         return st;
     if ((st = ensure_tables(ctx->scratch, est, params->num_hypotheses)) != MVS_OK)
         return st;
-    enqueue_model(ctx->scratch, est, to_run(*params), 1);
+    enqueue_model(ctx->scratch, est, to_run(*params), 1, false);
     st = fetch_single(ctx, m, &res, points_xyz, point_idx, inlier_mask);
     if (st != MVS_OK)
         return st;
@@ -1985,13 +2055,15 @@ mvs_status mvs_two_view_essential(mvs_ctx *ctx, const double *p1_uv, const doubl
 // ImagePair::ImagePair + reconstruct (front-end/image-pair.cpp:30-71,116-174) of ONE pair in one device pass: the
 // descriptors and keypoints go up once, the four stages run back to back on the stream, everything comes back through the
 // pinned arena after a single synchronisation (match -> host gather -> sfm_solve as separate calls costs two round trips).
-mvs_status mvs_image_pair(mvs_ctx *ctx, const uint8_t *base_desc, const float *base_kp, int n_base,
-                          const uint8_t *pair_desc, const float *pair_kp, int n_pair, int desc_bytes, const double K[9],
-                          const mvs_params *params, mvs_pair_result *result, mvs_match *matches, uint8_t *inlier_mask,
-                          double *points_xyz, int64_t *point_idx)
+static mvs_status image_pair_impl(mvs_ctx *ctx, Estimator est, const uint8_t *base_desc, const float *base_kp, int n_base,
+                                  const uint8_t *pair_desc, const float *pair_kp, int n_pair, int desc_bytes, const double K[9],
+                                  const mvs_params *params, mvs_pair_result *result, mvs_match *matches, uint8_t *inlier_mask,
+                                  double *points_xyz, int64_t *point_idx)
 {
     if (!ctx || !base_desc || !base_kp || !pair_desc || !pair_kp || !K || !result)
         return MVS_ERR_INVALID_ARG;
+    if (est == Estimator::kFivePoint)
+        ctx->e5_single = -1;   // a call that fails before its RANSAC is enqueued leaves no n_run behind
     mvs_status st = check_params(params);
     if (st != MVS_OK)
         return st;
@@ -2005,7 +2077,7 @@ mvs_status mvs_image_pair(mvs_ctx *ctx, const uint8_t *base_desc, const float *b
     if ((st = ensure_scratch(ctx, std::max(n_base, n_pair), desc_bytes)) != MVS_OK)
         return st;
     mvs_batch *b = ctx->scratch;
-    if ((st = ensure_groups(b, params->num_hypotheses)) != MVS_OK)
+    if ((st = ensure_tables(b, est, params->num_hypotheses)) != MVS_OK)
         return st;
     const size_t db1 = (size_t)n_base * desc_bytes, db2 = (size_t)n_pair * desc_bytes;
     const size_t kb1 = (size_t)n_base * 2 * sizeof(float), kb2 = (size_t)n_pair * 2 * sizeof(float);
@@ -2043,11 +2115,35 @@ mvs_status mvs_image_pair(mvs_ctx *ctx, const uint8_t *base_desc, const float *b
         sp.part_bytes[2] = (uint32_t)kb1; sp.part_bytes[3] = (uint32_t)kb2;
         launch_single_params(b->d, sp, ctx->single_in.ptr(), ctx->stream);
     }
-    if ((st = enqueue_pipeline(b, to_run(*params), 1, false, nullptr)) != MVS_OK)
+    st = est == Estimator::kEightPoint ? enqueue_pipeline(b, to_run(*params), 1, false, nullptr)
+                                       : enqueue_essential(b, to_run(*params), 1);
+    if (st != MVS_OK)
         return st;
     if ((st = fetch_single(ctx, n_pair, result, points_xyz, point_idx, inlier_mask, matches)) != MVS_OK)
         return st;
+    if (est == Estimator::kFivePoint && ctx->e5_single == 0 && result->n_matches < 8)
+        ctx->e5_single_run = 0;   // no hypothesis ran (sfm-solve.cpp:37); with a confidence level the device's n_run says so
     return result->valid ? MVS_OK : MVS_NO_MODEL;
+}
+
+mvs_status mvs_image_pair(mvs_ctx *ctx, const uint8_t *base_desc, const float *base_kp, int n_base,
+                          const uint8_t *pair_desc, const float *pair_kp, int n_pair, int desc_bytes, const double K[9],
+                          const mvs_params *params, mvs_pair_result *result, mvs_match *matches, uint8_t *inlier_mask,
+                          double *points_xyz, int64_t *point_idx)
+{
+    return image_pair_impl(ctx, Estimator::kEightPoint, base_desc, base_kp, n_base, pair_desc, pair_kp, n_pair, desc_bytes, K,
+                           params, result, matches, inlier_mask, points_xyz, point_idx);
+}
+
+// mvs_image_pair with find_essential_matrix's five-point branch (sfm-solve.cpp:42-63): what mvs_match_hamming, a host gather
+// and mvs_two_view_essential compute in two round trips, in one pass.
+mvs_status mvs_image_pair_essential(mvs_ctx *ctx, const uint8_t *base_desc, const float *base_kp, int n_base,
+                                    const uint8_t *pair_desc, const float *pair_kp, int n_pair, int desc_bytes,
+                                    const double K[9], const mvs_params *params, mvs_pair_result *result, mvs_match *matches,
+                                    uint8_t *inlier_mask, double *points_xyz, int64_t *point_idx)
+{
+    return image_pair_impl(ctx, Estimator::kFivePoint, base_desc, base_kp, n_base, pair_desc, pair_kp, n_pair, desc_bytes, K,
+                           params, result, matches, inlier_mask, points_xyz, point_idx);
 }
 
 static mvs_status upload_mask(mvs_ctx *ctx, const uint8_t *mask, int m)
@@ -2218,7 +2314,7 @@ mvs_status mvs_ransac_fundamental(mvs_ctx *ctx, const double *p1_xy, const doubl
         b->d.hyp_count = b->hyp_table_count;
         b->d.hyp_residual = b->hyp_table_residual;
     }
-    enqueue_model(b, Estimator::kEightPoint, rp, 1);
+    enqueue_model(b, Estimator::kEightPoint, rp, 1, false);
     mvs_pair_result res;
     if ((st = fetch_single(ctx, m, &res, nullptr, nullptr, inlier_mask)) != MVS_OK)
         return st;
@@ -2279,7 +2375,7 @@ mvs_status mvs_ransac_essential(mvs_ctx *ctx, const double *p1_xy, const double 
     if (st != MVS_OK)
         return st;
     mvs_batch *b = ctx->scratch;
-    enqueue_model(b, Estimator::kFivePoint, rp, 1);
+    enqueue_model(b, Estimator::kFivePoint, rp, 1, false);
     mvs_pair_result res;
     if ((st = fetch_single(ctx, m, &res, nullptr, nullptr, inlier_mask)) != MVS_OK)
         return st;
@@ -2464,7 +2560,7 @@ mvs_status mvs_seq_upload(mvs_seq *q, int first, int count, const uint8_t *desc,
     return MVS_OK;
 }
 
-static mvs_status seq_prepare(mvs_seq *q, const mvs_params *tv, const mvs_pnp_params *pp)
+static mvs_status seq_prepare(mvs_seq *q, Estimator est, const mvs_params *tv, const mvs_pnp_params *pp)
 {
     if (!q || !pp || pp->num_hypotheses < 1 || !(pp->reproj_error > 0.0))
         return MVS_ERR_INVALID_ARG;
@@ -2474,7 +2570,7 @@ static mvs_status seq_prepare(mvs_seq *q, const mvs_params *tv, const mvs_pnp_pa
     if (st != MVS_OK)
         return st;
     HIP_TRY(q->ctx, hipSetDevice(q->ctx->device));
-    if ((st = ensure_groups(q->batch, tv->num_hypotheses)) != MVS_OK)
+    if ((st = ensure_tables(q->batch, est, tv->num_hypotheses)) != MVS_OK)
         return st;
     const int G = (pp->num_hypotheses + 255) / 256;
     if (G > q->pnp.max_groups) {
@@ -2501,9 +2597,10 @@ static mvs_status seq_prepare(mvs_seq *q, const mvs_params *tv, const mvs_pnp_pa
     return MVS_OK;
 }
 
-static mvs_status seq_enqueue(mvs_seq *q, const RunParams &rp)
+static mvs_status seq_enqueue(mvs_seq *q, Estimator est, const RunParams &rp)
 {
-    mvs_status st = enqueue_pipeline(q->batch, rp, q->n_frames - 1, false, nullptr);
+    mvs_status st = est == Estimator::kEightPoint ? enqueue_pipeline(q->batch, rp, q->n_frames - 1, false, nullptr)
+                                                  : enqueue_essential(q->batch, rp, q->n_frames - 1);
     if (st != MVS_OK)
         return st;
     launch_seq_join(q->join, q->ctx->stream);
@@ -2520,10 +2617,27 @@ static mvs_status seq_enqueue(mvs_seq *q, const RunParams &rp)
 
 mvs_status mvs_seq_run(mvs_seq *q, const mvs_params *two_view, const mvs_pnp_params *pnp)
 {
-    mvs_status st = seq_prepare(q, two_view, pnp);
+    mvs_status st = seq_prepare(q, Estimator::kEightPoint, two_view, pnp);
     if (st != MVS_OK)
         return st;
-    return seq_enqueue(q, to_run(*two_view));
+    return seq_enqueue(q, Estimator::kEightPoint, to_run(*two_view));
+}
+
+// mvs_seq_run with the five-point RANSAC for the n_frames - 1 pairs; the join, PnP, optional refit and chain read the pairs'
+// results, masks and points, which do not depend on the estimator
+mvs_status mvs_seq_run_essential(mvs_seq *q, const mvs_params *two_view, const mvs_pnp_params *pnp)
+{
+    mvs_status st = seq_prepare(q, Estimator::kFivePoint, two_view, pnp);
+    if (st != MVS_OK)
+        return st;
+    return seq_enqueue(q, Estimator::kFivePoint, to_run(*two_view));
+}
+
+mvs_status mvs_seq_download_hypotheses_run(mvs_seq *q, int first, int count, int32_t *n_run)
+{
+    if (!q)
+        return MVS_ERR_INVALID_ARG;
+    return mvs_batch_download_hypotheses_run(q->batch, first, count, n_run);
 }
 
 mvs_status mvs_seq_sync(mvs_seq *q)
@@ -2539,18 +2653,18 @@ mvs_status mvs_seq_time(mvs_seq *q, const mvs_params *two_view, const mvs_pnp_pa
 {
     if (steps < 1 || warmup < 0 || !ms_total)
         return MVS_ERR_INVALID_ARG;
-    mvs_status st = seq_prepare(q, two_view, pnp);
+    mvs_status st = seq_prepare(q, Estimator::kEightPoint, two_view, pnp);
     if (st != MVS_OK)
         return st;
     const RunParams rp = to_run(*two_view);
     hipStream_t s = q->ctx->stream;
     for (int i = 0; i < warmup; ++i)
-        if ((st = seq_enqueue(q, rp)) != MVS_OK)
+        if ((st = seq_enqueue(q, Estimator::kEightPoint, rp)) != MVS_OK)
             return st;
     HIP_TRY(q->ctx, sync_stream(q->ctx));
     HIP_TRY(q->ctx, hipEventRecord(q->batch->ev[5], s));
     for (int i = 0; i < steps; ++i)
-        if ((st = seq_enqueue(q, rp)) != MVS_OK)
+        if ((st = seq_enqueue(q, Estimator::kEightPoint, rp)) != MVS_OK)
             return st;
     HIP_TRY(q->ctx, hipEventRecord(q->batch->ev[6], s));
     HIP_TRY(q->ctx, hipEventSynchronize(q->batch->ev[6]));
@@ -2564,7 +2678,7 @@ mvs_status mvs_seq_time_stages(mvs_seq *q, const mvs_params *two_view, const mvs
 {
     if (steps < 1 || !ms_stage)
         return MVS_ERR_INVALID_ARG;
-    mvs_status st = seq_prepare(q, two_view, pnp);
+    mvs_status st = seq_prepare(q, Estimator::kEightPoint, two_view, pnp);
     if (st != MVS_OK)
         return st;
     const RunParams rp = to_run(*two_view);

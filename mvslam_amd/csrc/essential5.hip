@@ -31,6 +31,12 @@
 // running maximum, applies the rule and writes n_run = T_j for a pair that stops (-1: still running).  e5_select_rounds_kernel
 // is the selection with its hypothesis bound read from n_run.  No atomics, no flag is waited for: the order of the launches on
 // the stream is the only synchronisation.
+//
+// The descriptor-fed entry points (mvs_image_pair_essential, mvs_batch_run_essential, mvs_seq_run_essential) solve and count
+// with e5wide_solve_count_kernel instead: the same 64 hypotheses per workgroup, solved by wavefront 0 into the same LDS columns,
+// then counted by FOUR wavefronts -- wavefront v takes matches v, v + 4, ... -- whose integer partial counts wavefront 0 adds.
+// The inlier decision per (model, match) is the same code and the sum is over integers: its tables are those of the kernels
+// above, bit for bit.  One kernel serves the plain run, round 0 (n_run null) and the later rounds.
 #include "kernels.hpp"
 #include "sampler.hpp"
 #include "five_point.hpp"
@@ -39,6 +45,10 @@ namespace mvs {
 
 constexpr int kE5Lanes = kE5HypPerBlock;
 constexpr size_t kE5LdsBytes = (size_t)kE5Ws * kE5Lanes * sizeof(double);   // 141 312
+constexpr int kE5WideWaves = 4;   // wavefronts of e5wide_solve_count_kernel: one per SIMD of the CU its LDS block fills
+constexpr int kE5WideThreads = kE5Lanes * kE5WideWaves;
+// the workspace + [wavefront][root][lane] int32 partial counts: 151 552 of the CU's 163 840 bytes
+constexpr size_t kE5WideLdsBytes = kE5LdsBytes + (size_t)kE5WideWaves * kE5MaxRoots * kE5Lanes * sizeof(int32_t);
 
 __device__ __forceinline__ double e5_max_error_sq(const BatchDev &b, const RunParams &rp, int pair)
 {
@@ -119,6 +129,73 @@ __device__ __forceinline__ bool e5_better(const E5Best &a, const E5Best &b)   //
 #include "essential5_kernels.inc"
 #undef E5_ROUNDS
 
+// The solve + count kernel of the descriptor-fed entry points: grid (hypothesis blocks of [h_first, ...), pairs), four
+// wavefronts.  Wavefront 0 solves hypothesis h_first + 64 blockIdx.x + lane into the lane's LDS column, as the kernels above do;
+// then thread (wavefront v, lane l) scores the models of hypothesis l against matches v, v + 4, ... (each match read at a
+// wavefront-uniform address; every wavefront reads its own lanes' columns, so the stride-64 layout stays free of bank
+// conflicts) and wavefront 0 adds the four integer partial counts per (lane, root) and writes the tables where those kernels
+// write them.  n_run: null (a plain run, or round 0) or the pairs' checkpoints, a pair with n_run >= 0 having stopped.  Both
+// early returns are block-uniform and in front of the first barrier.
+__global__ __launch_bounds__(kE5WideThreads) void e5wide_solve_count_kernel(BatchDev b, RunParams rp, int32_t *n_roots,
+                                                                            int32_t *count, int h_stride, int h_first,
+                                                                            const int32_t *n_run)
+{
+    extern __shared__ double s_w[];
+    __shared__ int s_n[kE5Lanes];
+    int32_t *s_part = reinterpret_cast<int32_t *>(s_w + (size_t)kE5Ws * kE5Lanes);
+    const int pair = blockIdx.y, lane = threadIdx.x % kE5Lanes;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kE5Lanes);
+    const int M = min(b.M[pair], b.max_kp);
+    if (M < 8)   // sfm-solve.cpp:37; the selection reports "no model" without reading the tables
+        return;
+    if (n_run && n_run[pair] >= 0)   // the pair has stopped at an earlier checkpoint
+        return;
+    const int h = h_first + blockIdx.x * kE5Lanes + lane;
+    const bool live = h < rp.num_hypotheses;
+    const double *P = b.pts + (size_t)pair * b.max_kp * 4;
+    const E5Ws w{s_w + lane, kE5Lanes};
+    const double thr = e5_max_error_sq(b, rp, pair);
+    if (wave == 0) {
+        int n = 0;
+        if (live)
+            n = e5_solve_hyp(P, M, rp.seed + (uint64_t)b.gidx[pair], (uint32_t)h, rp.sampler, w);
+        s_n[lane] = n;
+    }
+    __syncthreads();
+    const int n = s_n[lane];
+    for (int r = 0; r < kE5MaxRoots; ++r) {
+        int cnt = 0;
+        if (r < n) {
+            double E[9];
+#pragma unroll
+            for (int e = 0; e < 9; ++e)
+                E[e] = w(9 * r + e);
+            for (int i = wave; i < M; i += kE5WideWaves) {
+                const double4 q = *reinterpret_cast<const double4 *>(P + (size_t)i * 4);
+                double num, den;
+                e5_sampson(E, q.x, q.y, q.z, q.w, num, den);
+                cnt += e5_inlier(num, den, thr) ? 1 : 0;
+            }
+        }
+        s_part[(wave * kE5MaxRoots + r) * kE5Lanes + lane] = cnt;
+    }
+    __syncthreads();
+    if (wave != 0 || !live)
+        return;
+    int32_t *cout = count + ((size_t)pair * h_stride + h) * kE5MaxRoots;
+    for (int r = 0; r < kE5MaxRoots; ++r) {
+        int cnt = -1;
+        if (r < n) {
+            cnt = 0;
+#pragma unroll
+            for (int v = 0; v < kE5WideWaves; ++v)
+                cnt += s_part[(v * kE5MaxRoots + r) * kE5Lanes + lane];
+        }
+        cout[r] = cnt;
+    }
+    n_roots[(size_t)pair * h_stride + h] = n;
+}
+
 // mvs_five_point: one solve by lane 0 (workspace stride 1)
 __global__ __launch_bounds__(64) void five_point_kernel(const double *p1, const double *p2, double *Eout, int *nout)
 {
@@ -146,19 +223,27 @@ hipError_t essential5_prepare()
                           (const void *)e5_select_rounds_kernel})
         if (e == hipSuccess)
             e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kE5LdsBytes);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)e5wide_solve_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)kE5WideLdsBytes);
     return e;
 }
 
 static_assert(kE5Checkpoint0 == kE5HypPerBlock, "the first checkpoint is one workgroup of the solve + count kernel");
 
 void launch_essential5(const BatchDev &b, const RunParams &rp, int n_active, int32_t *n_roots, int32_t *count, int h_stride,
-                       int32_t *best_root, int32_t *n_run, int32_t *c_max, double confidence, hipStream_t stream)
+                       int32_t *best_root, int32_t *n_run, int32_t *c_max, double confidence, bool wide, hipStream_t stream)
 {
     const int H = rp.num_hypotheses;
+    const dim3 wide_block(kE5WideThreads);
     if (!(confidence > 0.0)) {   // every hypothesis runs: the two launches there were before the termination rule
         const int G = (H + kE5Lanes - 1) / kE5Lanes;
-        hipLaunchKernelGGL(essential5_solve_count_kernel, dim3(G, n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp, n_roots,
-                           count, h_stride);
+        if (wide)
+            hipLaunchKernelGGL(e5wide_solve_count_kernel, dim3(G, n_active), wide_block, kE5WideLdsBytes, stream, b, rp, n_roots,
+                               count, h_stride, 0, (const int32_t *)nullptr);
+        else
+            hipLaunchKernelGGL(essential5_solve_count_kernel, dim3(G, n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp,
+                               n_roots, count, h_stride);
         hipLaunchKernelGGL(essential5_select_kernel, dim3(n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp, n_roots, count,
                            h_stride, best_root);
         return;
@@ -167,7 +252,10 @@ void launch_essential5(const BatchDev &b, const RunParams &rp, int n_active, int
     int first = 0, last = e5_checkpoint_first(H);
     for (int j = 0;; ++j) {
         const int G = (last - first + kE5Lanes - 1) / kE5Lanes;
-        if (j == 0)
+        if (wide)
+            hipLaunchKernelGGL(e5wide_solve_count_kernel, dim3(G, n_active), wide_block, kE5WideLdsBytes, stream, b, rp, n_roots,
+                               count, h_stride, first, j == 0 ? (const int32_t *)nullptr : n_run);
+        else if (j == 0)
             hipLaunchKernelGGL(essential5_solve_count_kernel, dim3(G, n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp,
                                n_roots, count, h_stride);
         else

@@ -472,9 +472,11 @@ hipError_t essential5_prepare();
 // five_point.hpp, applied per pair at the checkpoints 64, 128, ... by one round of launches each (no host synchronisation).
 // n_run: [P], written only with a confidence level: the checkpoint each pair stopped at (0: fewer than eight matches); rows
 // >= n_run of the tables are not defined.  c_max: [P] scratch of the rounds.  With confidence 0 neither is touched and the two
-// launches are those of before the rule existed
+// launches are those of before the rule existed.  wide: the solve + count launches are e5wide_solve_count_kernel (four
+// wavefronts count each workgroup's 64 hypotheses; the same tables, bit for bit) -- the descriptor-fed entry points; false:
+// the launches of the point-fed ones, as they were
 void launch_essential5(const BatchDev &b, const RunParams &rp, int n_active, int32_t *n_roots, int32_t *count, int h_stride,
-                       int32_t *best_root, int32_t *n_run, int32_t *c_max, double confidence, hipStream_t stream);
+                       int32_t *best_root, int32_t *n_run, int32_t *c_max, double confidence, bool wide, hipStream_t stream);
 // the minimal solver alone: p1 / p2 5 x (x, y), E [10][9], n
 void launch_five_point(const double *p1, const double *p2, double *E, int *n, hipStream_t stream);
 
