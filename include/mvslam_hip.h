@@ -302,9 +302,9 @@ mvs_status mvs_batch_run_points_essential(mvs_batch *b, const mvs_params *params
  * mvs_batch_download, match list included. */
 mvs_status mvs_batch_run_essential(mvs_batch *b, const mvs_params *params, int n_active);
 /* n_run[count] of pairs [first, first + count) in the batch's LAST mvs_batch_run_points_essential or mvs_batch_run_essential:
- * num_hypotheses, or the checkpoint the pair stopped at under a confidence level (the call then waits for the ctx stream, as
- * it does after mvs_batch_run_essential, whose match counts only the device knows); 0 for a pair with fewer than eight
- * matches and for a pair at or beyond that call's n_active, whatever an earlier call did with it.
+ * num_hypotheses, or the checkpoint the pair stopped at under a confidence level; 0 for a pair with fewer than eight
+ * matches and for a pair at or beyond that call's n_active, whatever an earlier call did with it.  The words are the
+ * device's: the call waits for the ctx stream.
  * MVS_ERR_INVALID_ARG before the first such call. */
 mvs_status mvs_batch_download_hypotheses_run(mvs_batch *b, int first, int count, int32_t *n_run);
 /* The per-hypothesis tables of pairs [first, first + count) in the batch's last five-point run of either kind, as

@@ -45,8 +45,8 @@ struct mvs_ctx {
     bool half_batches = true;
     double e5_confidence = 0.0;   // mvs_ctx_set_essential_confidence: 0 = every hypothesis of the five-point RANSAC runs
     // n_run of the last single-shot five-point call: none yet, or that call failed before its RANSAC was enqueued (-1); in
-    // e5_single_run (0: known on the host -- fewer than eight matches, or no confidence level so every hypothesis ran -- or saved
-    // from a scratch batch that has been replaced since); in scratch->e5_nrun[0] (1: a confidence level was set)
+    // e5_single_run (0: the host returned before the RANSAC -- fewer than eight matches, so 0 -- or the word was saved from a
+    // scratch batch that has been replaced since); in scratch->e5_nrun[0] (1: the call enqueued its RANSAC)
     int e5_single = -1;
     int32_t e5_single_run = 0;
     int cu_count = 256;   // hipDeviceAttributeMultiprocessorCount of `device` (mvs_ctx_create); MI355X: 256
@@ -91,14 +91,11 @@ struct mvs_batch {
     int32_t *e5_nroots = nullptr;   // [n_pairs][e5_cap]
     int32_t *e5_count = nullptr;    // [n_pairs][e5_cap][10]
     int32_t *e5_root = nullptr;     // [n_pairs] root index of the winner
-    int32_t *e5_nrun = nullptr;     // [n_pairs] checkpoint each pair stopped at, written by a call with a confidence level
-    int32_t *e5_cmax = nullptr;     // [n_pairs] largest count so far, between the rounds of such a call
-    // the last five-point call on this batch (mvs_batch_download_hypotheses_run): its pairs, hypotheses and confidence level
+    int32_t *e5_nrun = nullptr;     // [n_pairs] hypotheses each pair ran: the checkpoint it stopped at, or all / none of them
+    int32_t *e5_cmax = nullptr;     // [n_pairs] largest count so far, between the rounds of a call with a confidence level
+    // the last five-point call on this batch (mvs_batch_download_hypotheses_run): its pairs and hypotheses
     bool e5_ran = false;
     int e5_last_n = 0, e5_last_H = 0;
-    double e5_last_conf = 0.0;
-    std::vector<int32_t> e5_host_run;   // n_run of that call where it had no confidence level: known without the device
-    bool e5_from_desc = false;          // ... unless that call matched descriptors: its match counts are in d.M only
     hipEvent_t ev[8]{};
     RefineDev refine{};     // allocated by the first mvs_batch_refine
     bool refine_ran = false;
@@ -393,10 +390,8 @@ static mvs_status ensure_tables(mvs_batch *b, Estimator est, int num_hypotheses)
     return MVS_ERR_INVALID_ARG;
 }
 
-// model stage + its finalize mode for pairs [0, n) on the ctx stream, plain launches (the tables are grown: ensure_tables).
-// from_desc: the points are those of match_compact, launched in front on the same stream (enqueue_essential) -- the five-point
-// stage then solves and counts with its four-wavefront kernel; the point-fed entry points keep the launches they had
-static void enqueue_model(mvs_batch *b, Estimator est, const RunParams &rp, int n, bool from_desc)
+// model stage + its finalize mode for pairs [0, n) on the ctx stream, plain launches (the tables are grown: ensure_tables)
+static void enqueue_model(mvs_batch *b, Estimator est, const RunParams &rp, int n)
 {
     hipStream_t s = b->ctx->stream;
     switch (est) {
@@ -406,16 +401,12 @@ static void enqueue_model(mvs_batch *b, Estimator est, const RunParams &rp, int 
         break;
     case Estimator::kFivePoint:
         launch_essential5(b->d, rp, n, b->e5_nroots, b->e5_count, b->e5_cap, b->e5_root, b->e5_nrun, b->e5_cmax,
-                          b->ctx->e5_confidence, from_desc, s);
+                          b->ctx->e5_confidence, s);
         b->e5_ran = true;
-        b->e5_from_desc = from_desc;
         b->e5_last_n = n;
         b->e5_last_H = rp.num_hypotheses;
-        b->e5_last_conf = b->ctx->e5_confidence;
-        if (b == b->ctx->scratch) {   // (a single-shot call gets here with eight matches or more)
-            b->ctx->e5_single = b->e5_last_conf > 0.0 ? 1 : 0;
-            b->ctx->e5_single_run = rp.num_hypotheses;
-        }
+        if (b == b->ctx->scratch)
+            b->ctx->e5_single = 1;
         launch_finalize(b->d, rp, n, kFinalizeEssential, s);
         break;
     }
@@ -1387,12 +1378,7 @@ mvs_status mvs_batch_run_points_essential(mvs_batch *b, const mvs_params *params
     const mvs_status st = stage_batch_points(b, Estimator::kFivePoint, params, n_active, uv1, uv2, m);
     if (st != MVS_OK)
         return st;
-    enqueue_model(b, Estimator::kFivePoint, to_run(*params), n_active, false);
-    if (!(b->e5_last_conf > 0.0)) {   // every hypothesis of every pair with eight matches or more (sfm-solve.cpp:37)
-        b->e5_host_run.resize(n_active);
-        for (int p = 0; p < n_active; ++p)
-            b->e5_host_run[p] = m[p] >= 8 ? params->num_hypotheses : 0;
-    }
+    enqueue_model(b, Estimator::kFivePoint, to_run(*params), n_active);
     HIP_TRY(b->ctx, hipGetLastError());
     return MVS_OK;
 }
@@ -1405,7 +1391,7 @@ static mvs_status enqueue_essential(mvs_batch *b, const RunParams &rp, int n)
     hipStream_t s = b->ctx->stream;
     launch_match_topk(b->d, rp, n, s);
     launch_match_compact(b->d, rp, n, s);
-    enqueue_model(b, Estimator::kFivePoint, rp, n, true);
+    enqueue_model(b, Estimator::kFivePoint, rp, n);
     HIP_TRY(b->ctx, hipGetLastError());
     return MVS_OK;
 }
@@ -1430,23 +1416,14 @@ mvs_status mvs_batch_download_hypotheses_run(mvs_batch *b, int first, int count,
         return MVS_ERR_INVALID_ARG;
     mvs_ctx *ctx = b->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // pairs the last call did not reach: 0.  The others: the checkpoint its rounds left on the device, or, where every
-    // hypothesis ran, what the call worked out from its match counts
+    // pairs the last call did not reach: 0.  The others: the word its selection left on the device
     std::fill(n_run, n_run + count, 0);
     const int reached = std::min(count, b->e5_last_n - first);
     if (reached < 1)
         return MVS_OK;
-    if (!(b->e5_last_conf > 0.0) && !b->e5_from_desc) {
-        std::copy(b->e5_host_run.begin() + first, b->e5_host_run.begin() + first + reached, n_run);
-        return MVS_OK;
-    }
-    // (without a confidence level behind the matcher: the match counts, which only the device knows)
-    const int32_t *src = b->e5_last_conf > 0.0 ? b->e5_nrun : b->d.M;
-    HIP_TRY(ctx, hipMemcpyAsync(n_run, src + first, (size_t)reached * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(n_run, b->e5_nrun + first, (size_t)reached * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                ctx->stream));
     HIP_TRY(ctx, sync_stream(ctx));
-    if (!(b->e5_last_conf > 0.0))
-        for (int p = 0; p < reached; ++p)
-            n_run[p] = n_run[p] >= 8 ? b->e5_last_H : 0;   // sfm-solve.cpp:37
     return MVS_OK;
 }
 
@@ -2027,7 +2004,7 @@ static mvs_status two_view_impl(mvs_ctx *ctx, Estimator est, const double *p1_uv
         return st;
     if ((st = ensure_tables(ctx->scratch, est, params->num_hypotheses)) != MVS_OK)
         return st;
-    enqueue_model(ctx->scratch, est, to_run(*params), 1, false);
+    enqueue_model(ctx->scratch, est, to_run(*params), 1);
     st = fetch_single(ctx, m, &res, points_xyz, point_idx, inlier_mask);
     if (st != MVS_OK)
         return st;
@@ -2121,8 +2098,6 @@ static mvs_status image_pair_impl(mvs_ctx *ctx, Estimator est, const uint8_t *ba
         return st;
     if ((st = fetch_single(ctx, n_pair, result, points_xyz, point_idx, inlier_mask, matches)) != MVS_OK)
         return st;
-    if (est == Estimator::kFivePoint && ctx->e5_single == 0 && result->n_matches < 8)
-        ctx->e5_single_run = 0;   // no hypothesis ran (sfm-solve.cpp:37); with a confidence level the device's n_run says so
     return result->valid ? MVS_OK : MVS_NO_MODEL;
 }
 
@@ -2314,7 +2289,7 @@ mvs_status mvs_ransac_fundamental(mvs_ctx *ctx, const double *p1_xy, const doubl
         b->d.hyp_count = b->hyp_table_count;
         b->d.hyp_residual = b->hyp_table_residual;
     }
-    enqueue_model(b, Estimator::kEightPoint, rp, 1, false);
+    enqueue_model(b, Estimator::kEightPoint, rp, 1);
     mvs_pair_result res;
     if ((st = fetch_single(ctx, m, &res, nullptr, nullptr, inlier_mask)) != MVS_OK)
         return st;
@@ -2375,7 +2350,7 @@ mvs_status mvs_ransac_essential(mvs_ctx *ctx, const double *p1_xy, const double 
     if (st != MVS_OK)
         return st;
     mvs_batch *b = ctx->scratch;
-    enqueue_model(b, Estimator::kFivePoint, rp, 1, false);
+    enqueue_model(b, Estimator::kFivePoint, rp, 1);
     mvs_pair_result res;
     if ((st = fetch_single(ctx, m, &res, nullptr, nullptr, inlier_mask)) != MVS_OK)
         return st;

@@ -14,29 +14,23 @@
 //            the same call gives with num_hypotheses = T -- hypotheses >= T take no part, counted or not;
 //   no refit, no projection (sfm-solve.cpp:62-63).
 //
-// Layout.  essential5_solve_count_kernel: grid (hypothesis blocks, pairs), one wavefront per workgroup,
-// one hypothesis per lane.  The solver's arrays (10 x 20 elimination matrix, basis, polynomials: kE5Ws = 276 doubles) are the
-// lane's column of a 138 KB LDS block -- run-time indices (pivot rows, root slots) stay out of scratch memory -- and the
-// hypothesis' models stay in that block: the points of the pair are read once per model at a wavefront-uniform address and only
-// n_roots and ten int32 counts per hypothesis go to device memory.  essential5_select_kernel: one wavefront per pair reduces the
-// count table, RE-SOLVES the hypotheses tied at the largest count with the same device function (the same bits) for their
-// residuals, re-solves the winner once more for E and writes the mask.
+// Layout.  essential5_solve_count_kernel: grid (hypothesis blocks, pairs), four wavefronts per
+// workgroup, one hypothesis per lane.  Wavefront 0 solves: the solver's arrays (10 x 20 elimination matrix, basis, polynomials:
+// kE5Ws = 276 doubles) are the lane's column of a 138 KB LDS block -- run-time indices (pivot rows, root slots) stay out of
+// scratch memory -- and the hypothesis' models stay in that block.  All four wavefronts count -- wavefront v takes matches
+// v, v + 4, ..., each read once per model at a wavefront-uniform address -- and wavefront 0 adds the four integer partial counts,
+// so only n_roots and ten int32 counts per hypothesis go to device memory.  essential5_select_kernel: one wavefront per pair
+// reduces the count table, RE-SOLVES the hypotheses tied at the largest count with the same device function (the same bits) for
+// their residuals, re-solves the winner once more for E, writes the mask and leaves the pair's n_run on the device.
 //
-// Without a confidence level these two kernels are the stage, the code and the launches of before the rule existed.  With one
-// the stage is a fixed sequence of rounds, one per checkpoint (their number depends on H alone), plain launches on the one
-// stream and no host synchronisation: round 0 is essential5_solve_count_kernel on the first 64 hypotheses; round j > 0 is
-// e5_solve_count_rounds_kernel -- the same text (essential5_kernels.inc) with a first-hypothesis argument, in which a workgroup
-// of a pair that has stopped returns after reading the pair's n_run word: block-uniform, before any work -- over
-// [T_{j-1}, T_j); each round ends with e5_horizon_kernel, one wavefront per pair, which folds the new counts into the pair's
-// running maximum, applies the rule and writes n_run = T_j for a pair that stops (-1: still running).  e5_select_rounds_kernel
-// is the selection with its hypothesis bound read from n_run.  No atomics, no flag is waited for: the order of the launches on
-// the stream is the only synchronisation.
-//
-// The descriptor-fed entry points (mvs_image_pair_essential, mvs_batch_run_essential, mvs_seq_run_essential) solve and count
-// with e5wide_solve_count_kernel instead: the same 64 hypotheses per workgroup, solved by wavefront 0 into the same LDS columns,
-// then counted by FOUR wavefronts -- wavefront v takes matches v, v + 4, ... -- whose integer partial counts wavefront 0 adds.
-// The inlier decision per (model, match) is the same code and the sum is over integers: its tables are those of the kernels
-// above, bit for bit.  One kernel serves the plain run, round 0 (n_run null) and the later rounds.
+// Without a confidence level these two launches are the stage.  With one the stage is a fixed sequence of rounds, one per
+// checkpoint (their number depends on H alone), plain launches on the one stream and no host synchronisation: round j is
+// essential5_solve_count_kernel over [T_{j-1}, T_j) (round 0: the first 64 hypotheses, n_run null), in which a workgroup of a
+// pair that has stopped returns after reading the pair's n_run word: block-uniform, before any work; each round ends with
+// essential5_horizon_kernel, one wavefront per pair, which folds the new counts into the pair's running maximum, applies the
+// rule and writes n_run = T_j for a pair that stops (-1: still running).  The selection then takes its hypothesis bound from
+// n_run.  No atomics, no flag is waited for: the order of the launches on the stream is the only synchronisation.  Every entry
+// point, point-fed or descriptor-fed, runs this one sequence.
 #include "kernels.hpp"
 #include "sampler.hpp"
 #include "five_point.hpp"
@@ -45,10 +39,10 @@ namespace mvs {
 
 constexpr int kE5Lanes = kE5HypPerBlock;
 constexpr size_t kE5LdsBytes = (size_t)kE5Ws * kE5Lanes * sizeof(double);   // 141 312
-constexpr int kE5WideWaves = 4;   // wavefronts of e5wide_solve_count_kernel: one per SIMD of the CU its LDS block fills
-constexpr int kE5WideThreads = kE5Lanes * kE5WideWaves;
+constexpr int kE5Waves = 4;   // wavefronts of essential5_solve_count_kernel: one per SIMD of the CU its LDS block fills
+constexpr int kE5CountThreads = kE5Lanes * kE5Waves;
 // the workspace + [wavefront][root][lane] int32 partial counts: 151 552 of the CU's 163 840 bytes
-constexpr size_t kE5WideLdsBytes = kE5LdsBytes + (size_t)kE5WideWaves * kE5MaxRoots * kE5Lanes * sizeof(int32_t);
+constexpr size_t kE5CountLdsBytes = kE5LdsBytes + (size_t)kE5Waves * kE5MaxRoots * kE5Lanes * sizeof(int32_t);
 
 __device__ __forceinline__ double e5_max_error_sq(const BatchDev &b, const RunParams &rp, int pair)
 {
@@ -77,9 +71,9 @@ __device__ __forceinline__ int e5_solve_hyp(const double *P, int M, uint64_t see
 // maximum c_max, and the pair stops here -- n_run = h_last -- if this is the last checkpoint or e5_confident() says so; a pair
 // that goes on keeps n_run = -1.  The first checkpoint (h_first = 0) reads neither word: it initialises both, and gives the
 // pairs with fewer than eight matches n_run = 0.
-__global__ __launch_bounds__(kE5Lanes) void e5_horizon_kernel(BatchDev b, const int32_t *count, int h_stride, int h_first,
-                                                              int h_last, int is_last, int j, double confidence, int32_t *n_run,
-                                                              int32_t *c_max)
+__global__ __launch_bounds__(kE5Lanes) void essential5_horizon_kernel(BatchDev b, const int32_t *count, int h_stride,
+                                                                      int h_first, int h_last, int is_last, int j,
+                                                                      double confidence, int32_t *n_run, int32_t *c_max)
 {
     const int pair = blockIdx.x, lane = threadIdx.x;
     const int M = min(b.M[pair], b.max_kp);
@@ -119,26 +113,15 @@ __device__ __forceinline__ bool e5_better(const E5Best &a, const E5Best &b)   //
     return a.root < b.root;
 }
 
-// The solve + count kernel and the selection kernel, once as they were before the termination rule and once for its rounds
-// (essential5_kernels.inc).  The kernels of the rule are named e5_*: tests/test_five_point_host.py expects exactly three
-// kernels whose name holds "essential5" or "five_point_kernel", the ones a call without a confidence level uses.
-#define E5_ROUNDS 0
-#include "essential5_kernels.inc"
-#undef E5_ROUNDS
-#define E5_ROUNDS 1
-#include "essential5_kernels.inc"
-#undef E5_ROUNDS
-
-// The solve + count kernel of the descriptor-fed entry points: grid (hypothesis blocks of [h_first, ...), pairs), four
-// wavefronts.  Wavefront 0 solves hypothesis h_first + 64 blockIdx.x + lane into the lane's LDS column, as the kernels above do;
-// then thread (wavefront v, lane l) scores the models of hypothesis l against matches v, v + 4, ... (each match read at a
-// wavefront-uniform address; every wavefront reads its own lanes' columns, so the stride-64 layout stays free of bank
-// conflicts) and wavefront 0 adds the four integer partial counts per (lane, root) and writes the tables where those kernels
-// write them.  n_run: null (a plain run, or round 0) or the pairs' checkpoints, a pair with n_run >= 0 having stopped.  Both
+// The solve + count kernel: grid (hypothesis blocks of [h_first, ...), pairs), four wavefronts.  Wavefront 0 solves hypothesis
+// h_first + 64 blockIdx.x + lane into the lane's LDS column; then thread (wavefront v, lane l) scores the models of hypothesis
+// l against matches v, v + 4, ... (each match read at a wavefront-uniform address; every wavefront reads its own lanes'
+// columns, so the stride-64 layout stays free of bank conflicts) and wavefront 0 adds the four integer partial counts per
+// (lane, root) and writes the tables: count -1 past the hypothesis' n_roots.  n_run: null (a plain run, or round 0) or the pairs' checkpoints, a pair with n_run >= 0 having stopped.  Both
 // early returns are block-uniform and in front of the first barrier.
-__global__ __launch_bounds__(kE5WideThreads) void e5wide_solve_count_kernel(BatchDev b, RunParams rp, int32_t *n_roots,
-                                                                            int32_t *count, int h_stride, int h_first,
-                                                                            const int32_t *n_run)
+__global__ __launch_bounds__(kE5CountThreads) void essential5_solve_count_kernel(BatchDev b, RunParams rp, int32_t *n_roots,
+                                                                                 int32_t *count, int h_stride, int h_first,
+                                                                                 const int32_t *n_run)
 {
     extern __shared__ double s_w[];
     __shared__ int s_n[kE5Lanes];
@@ -170,7 +153,7 @@ __global__ __launch_bounds__(kE5WideThreads) void e5wide_solve_count_kernel(Batc
 #pragma unroll
             for (int e = 0; e < 9; ++e)
                 E[e] = w(9 * r + e);
-            for (int i = wave; i < M; i += kE5WideWaves) {
+            for (int i = wave; i < M; i += kE5Waves) {
                 const double4 q = *reinterpret_cast<const double4 *>(P + (size_t)i * 4);
                 double num, den;
                 e5_sampson(E, q.x, q.y, q.z, q.w, num, den);
@@ -188,12 +171,134 @@ __global__ __launch_bounds__(kE5WideThreads) void e5wide_solve_count_kernel(Batc
         if (r < n) {
             cnt = 0;
 #pragma unroll
-            for (int v = 0; v < kE5WideWaves; ++v)
+            for (int v = 0; v < kE5Waves; ++v)
                 cnt += s_part[(v * kE5MaxRoots + r) * kE5Lanes + lane];
         }
         cout[r] = cnt;
     }
     n_roots[(size_t)pair * h_stride + h] = n;
+}
+
+// The selection, one wavefront per pair.  confident: the pair's hypothesis bound is the n_run its rounds left; otherwise every
+// hypothesis ran (none for a pair with fewer than eight matches, sfm-solve.cpp:37) and the kernel writes that n_run itself, so
+// the host reads one array whatever the call was.
+__global__ __launch_bounds__(kE5Lanes) void essential5_select_kernel(BatchDev b, RunParams rp, const int32_t *n_roots,
+                                                                     const int32_t *count, int h_stride, int32_t *best_root,
+                                                                     int32_t *n_run, int confident)
+{
+    extern __shared__ double s_w[];
+    __shared__ double s_E[9];
+    const int pair = blockIdx.x, lane = threadIdx.x;
+    const int M = min(b.M[pair], b.max_kp);
+    const int H = confident ? n_run[pair] : (M >= 8 ? rp.num_hypotheses : 0);
+    if (!confident && lane == 0)
+        n_run[pair] = H;
+    mvs_pair_result *res = b.results + pair;
+    uint8_t *mask = b.mask + (size_t)pair * b.max_kp;
+    const double *P = b.pts + (size_t)pair * b.max_kp * 4;
+    const int32_t *C = count + (size_t)pair * h_stride * kE5MaxRoots;
+    const E5Ws w{s_w + lane, kE5Lanes};
+
+    for (int i = M + lane; i < b.max_kp; i += kE5Lanes)   // rows past the match list: cleared (deterministic downloads)
+        mask[i] = 0;
+    if (lane < 9) {   // the pose of a pair that ends without one is zero, whatever ran on the batch before
+        res->R1to2[lane] = 0.0;
+        res->R[lane] = 0.0;
+        if (lane < 3) {
+            res->t1to2[lane] = 0.0;
+            res->t[lane] = 0.0;
+        }
+    }
+    int best = -1;
+    if (M >= 8)
+        for (int k = lane; k < H * kE5MaxRoots; k += kE5Lanes)
+            best = max(best, C[k]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+        best = max(best, __shfl_xor(best, o));
+    if (best < 0) {
+        for (int i = lane; i < M; i += kE5Lanes)
+            mask[i] = 0;
+        if (lane < 9) {
+            res->F[lane] = 0.0;
+            res->E[lane] = 0.0;
+        }
+        if (lane == 0) {
+            res->best_hyp = -1;
+            res->best_count = 0;
+            res->best_residual = 0.0;
+            best_root[pair] = -1;
+        }
+        return;
+    }
+    const double thr = e5_max_error_sq(b, rp, pair);
+    const uint64_t seed = rp.seed + (uint64_t)b.gidx[pair];
+    // ---- residuals of the models tied at the largest count (lane l visits hypotheses l, l + 64, ... ascending) ----
+    E5Best me{0.0, -1, 0};
+    for (int h = lane; h < H; h += kE5Lanes) {
+        unsigned tied = 0;
+        for (int r = 0; r < kE5MaxRoots; ++r)
+            tied |= C[(size_t)h * kE5MaxRoots + r] == best ? 1u << r : 0u;
+        if (!tied)
+            continue;
+        const int n = e5_solve_hyp(P, M, seed, (uint32_t)h, rp.sampler, w);
+        for (int r = 0; r < n; ++r) {
+            if (!((tied >> r) & 1u))
+                continue;
+            double E[9];
+#pragma unroll
+            for (int e = 0; e < 9; ++e)
+                E[e] = w(9 * r + e);
+            double sum = 0.0;
+            for (int i = 0; i < M; ++i) {
+                const double4 q = *reinterpret_cast<const double4 *>(P + (size_t)i * 4);
+                double num, den;
+                e5_sampson(E, q.x, q.y, q.z, q.w, num, den);
+                if (e5_inlier(num, den, thr))
+                    sum += num / den;
+            }
+            const E5Best c{e5_residual_key(sum), h, r};
+            if (e5_better(c, me))
+                me = c;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        E5Best other;
+        other.res = __shfl_xor(me.res, o);
+        other.hyp = __shfl_xor(me.hyp, o);
+        other.root = __shfl_xor(me.root, o);
+        if (e5_better(other, me))
+            me = other;
+    }
+    // ---- the winner's E (solved once more: the same function, the same bits) and its mask ----
+    if (lane == 0) {
+        int n = 0;
+        if (me.hyp >= 0)
+            n = e5_solve_hyp(P, M, seed, (uint32_t)me.hyp, rp.sampler, w);
+        const bool ok = me.hyp >= 0 && me.root < n;
+        for (int e = 0; e < 9; ++e) {
+            const double v = ok ? w(9 * me.root + e) : 0.0;
+            s_E[e] = v;
+            res->F[e] = v;
+            res->E[e] = v;
+        }
+        res->best_hyp = ok ? me.hyp : -1;
+        res->best_count = ok ? best : 0;
+        res->best_residual = ok ? me.res : 0.0;
+        best_root[pair] = ok ? me.root : -1;
+    }
+    __syncthreads();
+    double E[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e)
+        E[e] = s_E[e];
+    for (int i = lane; i < M; i += kE5Lanes) {
+        const double4 q = *reinterpret_cast<const double4 *>(P + (size_t)i * 4);
+        double num, den;
+        e5_sampson(E, q.x, q.y, q.z, q.w, num, den);
+        mask[i] = e5_inlier(num, den, thr) ? 1 : 0;
+    }
 }
 
 // mvs_five_point: one solve by lane 0 (workspace stride 1)
@@ -217,59 +322,38 @@ __global__ __launch_bounds__(64) void five_point_kernel(const double *p1, const 
 
 hipError_t essential5_prepare()
 {
-    hipError_t e = hipFuncSetAttribute((const void *)essential5_solve_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)kE5LdsBytes);
-    for (const void *k : {(const void *)essential5_select_kernel, (const void *)e5_solve_count_rounds_kernel,
-                          (const void *)e5_select_rounds_kernel})
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kE5LdsBytes);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void *)e5wide_solve_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kE5WideLdsBytes);
-    return e;
+    const hipError_t e = hipFuncSetAttribute((const void *)essential5_solve_count_kernel,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kE5CountLdsBytes);
+    if (e != hipSuccess)
+        return e;
+    return hipFuncSetAttribute((const void *)essential5_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)kE5LdsBytes);
 }
 
 static_assert(kE5Checkpoint0 == kE5HypPerBlock, "the first checkpoint is one workgroup of the solve + count kernel");
 
 void launch_essential5(const BatchDev &b, const RunParams &rp, int n_active, int32_t *n_roots, int32_t *count, int h_stride,
-                       int32_t *best_root, int32_t *n_run, int32_t *c_max, double confidence, bool wide, hipStream_t stream)
+                       int32_t *best_root, int32_t *n_run, int32_t *c_max, double confidence, hipStream_t stream)
 {
     const int H = rp.num_hypotheses;
-    const dim3 wide_block(kE5WideThreads);
-    if (!(confidence > 0.0)) {   // every hypothesis runs: the two launches there were before the termination rule
-        const int G = (H + kE5Lanes - 1) / kE5Lanes;
-        if (wide)
-            hipLaunchKernelGGL(e5wide_solve_count_kernel, dim3(G, n_active), wide_block, kE5WideLdsBytes, stream, b, rp, n_roots,
-                               count, h_stride, 0, (const int32_t *)nullptr);
-        else
-            hipLaunchKernelGGL(essential5_solve_count_kernel, dim3(G, n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp,
-                               n_roots, count, h_stride);
-        hipLaunchKernelGGL(essential5_select_kernel, dim3(n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp, n_roots, count,
-                           h_stride, best_root);
-        return;
-    }
-    // round j counts [first, last) and tests at last; the first round is the plain kernel on a grid of one block per pair
-    int first = 0, last = e5_checkpoint_first(H);
+    const bool confident = confidence > 0.0;
+    // round j counts [first, last) and tests at last; without a confidence level the one round is every hypothesis, untested
+    int first = 0, last = confident ? e5_checkpoint_first(H) : H;
     for (int j = 0;; ++j) {
         const int G = (last - first + kE5Lanes - 1) / kE5Lanes;
-        if (wide)
-            hipLaunchKernelGGL(e5wide_solve_count_kernel, dim3(G, n_active), wide_block, kE5WideLdsBytes, stream, b, rp, n_roots,
-                               count, h_stride, first, j == 0 ? (const int32_t *)nullptr : n_run);
-        else if (j == 0)
-            hipLaunchKernelGGL(essential5_solve_count_kernel, dim3(G, n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp,
-                               n_roots, count, h_stride);
-        else
-            hipLaunchKernelGGL(e5_solve_count_rounds_kernel, dim3(G, n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp,
-                               n_roots, count, h_stride, first, n_run);
-        hipLaunchKernelGGL(e5_horizon_kernel, dim3(n_active), dim3(kE5Lanes), 0, stream, b, count, h_stride, first, last,
+        hipLaunchKernelGGL(essential5_solve_count_kernel, dim3(G, n_active), dim3(kE5CountThreads), kE5CountLdsBytes, stream, b,
+                           rp, n_roots, count, h_stride, first, j == 0 ? (const int32_t *)nullptr : n_run);
+        if (!confident)
+            break;
+        hipLaunchKernelGGL(essential5_horizon_kernel, dim3(n_active), dim3(kE5Lanes), 0, stream, b, count, h_stride, first, last,
                            last == H ? 1 : 0, j, confidence, n_run, c_max);
         if (last == H)
             break;
         first = last;
         last = e5_checkpoint_next(last, H);
     }
-    hipLaunchKernelGGL(e5_select_rounds_kernel, dim3(n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp, n_roots, count, h_stride,
-                       best_root, n_run);
+    hipLaunchKernelGGL(essential5_select_kernel, dim3(n_active), dim3(kE5Lanes), kE5LdsBytes, stream, b, rp, n_roots, count,
+                       h_stride, best_root, n_run, confident ? 1 : 0);
 }
 
 void launch_five_point(const double *p1, const double *p2, double *E, int *n, hipStream_t stream)

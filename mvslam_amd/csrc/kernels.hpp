@@ -462,7 +462,7 @@ void launch_fundamental(const double *p1, const double *p2, double *F, int *ok, 
 
 // ---- five-point essential-matrix RANSAC (essential5.hip) ----------------------------------------
 constexpr int kE5MaxRoots = 10;      // models of one hypothesis (five_point.hpp)
-constexpr int kE5HypPerBlock = 64;   // hypotheses per workgroup of the solve + count kernel: one per lane of its one wavefront
+constexpr int kE5HypPerBlock = 64;   // hypotheses per workgroup of the solve + count kernel: one per lane of a wavefront
 // opt-in to the kernels' LDS workspaces (> 64 KB), once per device
 hipError_t essential5_prepare();
 // pairs [0, n_active): every hypothesis solved and counted on the pair's resident normalised points, then the selection, which
@@ -470,13 +470,12 @@ hipError_t essential5_prepare();
 // kFinalizeEssential completes the record.  n_roots: [P][h_stride], count: [P][h_stride][10] (-1 past n_roots);
 // best_root: [P] root index of the winner (-1: none).  confidence: 0 = every hypothesis runs; in (0, 1) = the termination rule of
 // five_point.hpp, applied per pair at the checkpoints 64, 128, ... by one round of launches each (no host synchronisation).
-// n_run: [P], written only with a confidence level: the checkpoint each pair stopped at (0: fewer than eight matches); rows
-// >= n_run of the tables are not defined.  c_max: [P] scratch of the rounds.  With confidence 0 neither is touched and the two
-// launches are those of before the rule existed.  wide: the solve + count launches are e5wide_solve_count_kernel (four
-// wavefronts count each workgroup's 64 hypotheses; the same tables, bit for bit) -- the descriptor-fed entry points; false:
-// the launches of the point-fed ones, as they were
+// n_run: [P], always written: the hypotheses each pair ran -- the checkpoint it stopped at, or with confidence 0 all of them
+// (0: fewer than eight matches); rows >= n_run of the tables are not defined.  c_max: [P] scratch of the rounds, untouched with
+// confidence 0, when the stage is two launches: solve + count (four wavefronts count each workgroup's 64 hypotheses) and the
+// selection
 void launch_essential5(const BatchDev &b, const RunParams &rp, int n_active, int32_t *n_roots, int32_t *count, int h_stride,
-                       int32_t *best_root, int32_t *n_run, int32_t *c_max, double confidence, bool wide, hipStream_t stream);
+                       int32_t *best_root, int32_t *n_run, int32_t *c_max, double confidence, hipStream_t stream);
 // the minimal solver alone: p1 / p2 5 x (x, y), E [10][9], n
 void launch_five_point(const double *p1, const double *p2, double *E, int *n, hipStream_t stream);
 

@@ -115,26 +115,6 @@ def test_checkpoint_sequence():
     assert list(buf[:n]) == checkpoints(2 ** 31 - 1) and n == 26
 
 
-def test_new_kernels_need_no_scratch_and_the_horizon_kernel_no_lds():
-    import json
-    path = os.path.join(LIBDIR, "kernel_resources.json")
-    assert os.path.exists(path), "kernel_resources.json is missing: build the library first"
-    digest = json.load(open(path))
-    mine = {k: v for k, v in digest.items() if "e5_" in k}
-    assert sorted(k[k.index("e5_"):].split("ENS_")[0] for k in mine) == ["e5_horizon_kernel", "e5_select_rounds_kernel",
-                                                                         "e5_solve_count_rounds_kernel"], list(mine)
-    for k, v in mine.items():
-        assert v["scratch_bytes_per_lane"] == 0 and v["vgpr_spills"] == 0, (k, v)
-        if "e5_horizon_kernel" in k:
-            assert v["sgpr_spills"] == 0 and v["static_lds_bytes"] == 0, v
-    # the rounds' kernels are the plain ones' text: the same registers, but for the two arguments more
-    for plain, rounds in (("essential5_solve_count_kernel", "e5_solve_count_rounds_kernel"),
-                          ("essential5_select_kernel", "e5_select_rounds_kernel")):
-        a = next(v for k, v in digest.items() if plain in k)
-        b = next(v for k, v in digest.items() if rounds in k)
-        assert a["vgprs"] == b["vgprs"] and abs(a["sgprs"] - b["sgprs"]) <= 4, (plain, a, b)
-
-
 # ---- CPU: the C++ surface --------------------------------------------------------------------------------------------------
 def _build_shim():
     assert os.path.exists(os.path.join(LIBDIR, "libmvslam_hip.so")), "build the HIP library first (__graft_entry__.build)"
@@ -430,6 +410,47 @@ def test_batch_stops_each_pair_on_its_own(ctx, conf):
         got = b.hypotheses_run()
         assert np.array_equal(got[:10], want[:10] if p_level else np.where(m[:10] >= 8, H, 0)) and not got[10:].any()
     b.close()
+
+
+@pytest.mark.gpu
+def test_n_run_is_the_word_the_selection_leaves_on_the_device(ctx, conf):
+    """With or without a confidence level hypotheses_run() reads what the last call's selection wrote: a call without one, on
+    fewer pairs, after a call with one -- every hypothesis for eight matches or more, 0 below, and 0 (not the earlier call's
+    checkpoint) for the pairs it did not reach.  H = 65 is two checkpoints, 64 and 65."""
+    P, N, H, seed = 6, 16, 65, 500
+    m = np.array([0, 7, 8, 9, 11, 16], dtype=np.int32)
+    fams = list(helpers.CAMERAS)
+    Ks = np.stack([helpers.CAMERAS[fams[p % len(fams)]][0] for p in range(P)])
+    uv1, uv2 = np.zeros((P, N, 2)), np.zeros((P, N, 2))
+    for p in range(P):
+        a, b2 = scene(5000 + p, N, 0.2)
+        h = lambda q: np.hstack([q, np.ones((N, 1))]) @ Ks[p].T   # noqa: E731
+        uv1[p], uv2[p] = h(a)[:, :2], h(b2)[:, :2]
+        uv1[p, m[p]:], uv2[p, m[p]:] = 0.0, 0.0
+    prm = capi.default_params(num_hypotheses=H, sampler=capi.SAMPLER_PHILOX, seed=seed, max_error_sq=THR)
+    b = capi.Batch(ctx, P, N, 32)
+    try:
+        b.upload_intrinsics(0, Ks, global_index=np.arange(P) * 3)
+        conf(0.99)
+        b.run_points_essential(prm, uv1, uv2, m)
+        first = b.hypotheses_run()
+        conf(0.0)
+        b.run_points_essential(prm, uv1[:4], uv2[:4], m[:4])
+        b.sync()
+        run, (n_roots, count), out = b.hypotheses_run(), b.download_essential_tables(H), b.download()
+    finally:
+        b.close()
+    assert not first[:2].any() and (first[2:] >= BLOCK).all(), first      # (words the second call must not hand back)
+    assert run.tolist() == [0, 0, 65, 65, 0, 0]
+    for p in (2, 3):
+        n1, n2 = o.normalize_points(Ks[p], uv1[p, :m[p]]), o.normalize_points(Ks[p], uv2[p, :m[p]])
+        ref = em.host_ransac(n1, n2, THR, H, capi.SAMPLER_PHILOX, seed + 3 * p)
+        assert np.array_equal(n_roots[p], ref["n_roots"]) and np.array_equal(count[p], ref["count"]), p
+        r = out["results"][p]
+        assert (r["best_hyp"], r["best_count"]) == (ref["best_hyp"], ref["best_count"]), p
+        assert np.float64(r["best_residual"]).tobytes() == np.float64(ref["best_residual"]).tobytes(), p
+        assert r["E"].tobytes() == ref["E"].tobytes() and r["F"].tobytes() == ref["E"].tobytes(), p
+        assert np.array_equal(out["mask"][p][:m[p]], ref["mask"]) and not out["mask"][p][m[p]:].any(), p
 
 
 @pytest.mark.gpu

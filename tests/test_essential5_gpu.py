@@ -90,7 +90,7 @@ def _check_ransac(ctx, p1, p2, thr, H, sampler, seed):
     return got
 
 
-@pytest.mark.parametrize("m", [8, 9, 63, 64, 65, 4096])
+@pytest.mark.parametrize("m", [8, 9, 10, 11, 63, 64, 65, 4096])
 def test_ransac_essential_point_counts(ctx, m):
     p1, p2 = _get_scene(("mixed", m))[:2]
     for sampler, thr in ((capi.SAMPLER_PHILOX, 1e-6), (capi.SAMPLER_IDENTITY, 1e-3)):

@@ -1,8 +1,6 @@
 """The five-point RANSAC behind the matcher on the GPU: mvs_image_pair_essential, mvs_batch_run_essential and
 mvs_seq_run_essential against the point-fed calls they replace (mvs_match_hamming + mvs_two_view_essential,
-mvs_batch_run_points_essential) and the host model (tests/e5_model.py), byte for byte.  The descriptor-fed calls solve and count
-with e5wide_solve_count_kernel (four wavefronts share the matches of a workgroup's 64 hypotheses), the point-fed ones with the
-one-wavefront kernels: equal tables are the kernel's check.
+mvs_batch_run_points_essential) and the host model (tests/e5_model.py), byte for byte.
 
 Match counts are crafted: independent random 256-bit descriptors are at least ~85 bits apart, so copying k descriptors of the
 base frame into the pair frame gives exactly k matches under max_dist = 10."""
@@ -154,7 +152,7 @@ def test_image_pair_essential_argument_errors(ctx):
     assert not got["ok"] and got["n_matches"] <= 5 and got["hypotheses_run"] == 0
 
 
-# ---- 2. the wide kernel against the one-wavefront kernels --------------------------------------------------------------------------
+# ---- 2. the descriptor-fed batch against the point-fed one and the host model ------------------------------------------------------
 _BATCH_N = 128
 _HEAVY, _FEW, _EIGHT, _FULL = 2, 3, 4, 1     # pairs with special match lists (all below P = 5)
 
@@ -203,7 +201,7 @@ def _matched_points(data, out):
 
 @pytest.mark.parametrize("confidence", [0.0, 0.99])
 @pytest.mark.parametrize("P", [5, 64])
-def test_wide_kernel_tables_equal_the_one_wavefront_kernels(ctx, P, confidence):
+def test_descriptor_fed_and_point_fed_tables_are_equal_and_the_host_models(ctx, P, confidence):
     N, H = _BATCH_N, 1000
     data = _family_batch(P)
     prm = capi.default_params(num_hypotheses=H, sampler=capi.SAMPLER_PHILOX, seed=900, max_error_sq=_THR, ratio=0.7, max_dist=10.0)

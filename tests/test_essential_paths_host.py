@@ -1,12 +1,7 @@
 """CPU side of the descriptor-fed five-point entry points (mvs_image_pair_essential, mvs_batch_run_essential,
-mvs_seq_run_essential and their accessors): the exported surface, the resources of the four-wavefront solve + count kernel, and
-the shim's MVSLAM_ESSENTIAL_ONE_PASS.  The GPU side is tests/test_essential_paths_gpu.py.
-
-The kernel is named e5wide_solve_count_kernel: a name holding "e5_" would be counted by
-tests/test_essential5_confidence.py::test_new_kernels_need_no_scratch_and_the_horizon_kernel_no_lds, which expects exactly three
-such kernels, as a name holding "essential5" would be by tests/test_five_point_host.py."""
+mvs_seq_run_essential and their accessors): the exported surface and the shim's MVSLAM_ESSENTIAL_ONE_PASS.  The GPU side is
+tests/test_essential_paths_gpu.py; the kernels' resources are checked in tests/test_five_point_host.py."""
 import ctypes as C
-import json
 import os
 import re
 import subprocess
@@ -18,12 +13,9 @@ LIBDIR = os.path.join(ROOT, "mvslam_amd", "lib")
 HEADER = os.path.join(ROOT, "include", "mvslam_hip.h")
 SHIM = os.path.join(ROOT, "mvslam_amd", "compat", "mvslam_compat.hpp")
 SRC = os.path.join(ROOT, "tests", "cpp", "image_pair_one_pass.cpp")
-CSRC = os.path.join(ROOT, "mvslam_amd", "csrc")
 
 NEW_SYMBOLS = ["mvs_image_pair_essential", "mvs_batch_run_essential", "mvs_batch_download_essential_tables",
                "mvs_seq_run_essential", "mvs_seq_download_hypotheses_run", "mvs_batch_download_hypotheses_run"]
-WIDE = "e5wide_solve_count_kernel"
-CU_LDS_BYTES = 163840
 
 ONE_PASS_FLAGS = {"one_pass": ["-DMVSLAM_USE_ESSENTIAL_5POINT", "-DMVSLAM_ESSENTIAL_ONE_PASS"],
                   "two_calls": ["-DMVSLAM_USE_ESSENTIAL_5POINT"], "eight_point": []}
@@ -72,33 +64,6 @@ def test_the_new_calls_refuse_null_handles_without_a_device():
     assert lib.mvs_batch_download_essential_tables(None, 0, 1, 8, n, n) == capi.MVS_ERR_INVALID_ARG
     assert lib.mvs_image_pair_essential(None, None, None, 0, None, None, 0, 32, None, C.byref(prm), None, None, None, None,
                                         None) == capi.MVS_ERR_INVALID_ARG
-
-
-def _constant(text, name):
-    m = re.search(r"constexpr\s+\w+\s+%s\s*=\s*(\d+)\s*;" % name, text)
-    assert m, name
-    return int(m.group(1))
-
-
-def test_the_wide_kernel_spills_nothing_and_fits_the_lds_of_a_cu():
-    path = os.path.join(LIBDIR, "kernel_resources.json")
-    assert os.path.exists(path), "kernel_resources.json is missing: build the library first"
-    digest = json.load(open(path))
-    mine = {k: v for k, v in digest.items() if WIDE in k}
-    assert len(mine) == 1, list(mine)
-    v = next(iter(mine.values()))
-    assert v["scratch_bytes_per_lane"] == 0 and v["vgpr_spills"] == 0 and v["sgpr_spills"] == 0, v
-    # dynamic LDS as essential5.hip sizes it: the solver's workspace of 64 lanes + [4 wavefronts][10 roots][64 lanes] int32
-    hdr = open(os.path.join(CSRC, "five_point.hpp")).read() + open(os.path.join(CSRC, "kernels.hpp")).read()
-    src = open(os.path.join(CSRC, "essential5.hip")).read()
-    ws, roots, lanes = _constant(hdr, "kE5Ws"), _constant(hdr, "kE5MaxRoots"), _constant(hdr, "kE5HypPerBlock")
-    waves = _constant(src, "kE5WideWaves")
-    dynamic = ws * lanes * 8 + waves * roots * lanes * 4
-    assert dynamic == 141312 + 10240
-    assert v["static_lds_bytes"] + dynamic <= CU_LDS_BYTES, (v, dynamic)
-    # the kernels of a call without a confidence level are still the three they were
-    plain = [k for k in digest if "essential5" in k or "five_point_kernel" in k]
-    assert len(plain) == 3, plain
 
 
 def _preprocessed(flags):

@@ -7,6 +7,7 @@ the same model in 50-digit mpmath differs by at most D_MODEL in a matched matrix
 its matrices miss the constraints by at most R_MODEL (epipolar, det, trace).  The header is allowed ten times each."""
 import json
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -150,12 +151,39 @@ def test_cube_default_threshold_the_true_model_wins():
     assert np.abs(pts - rig["X"]).max() < 1e-3
 
 
+def _constant(text, name):
+    m = re.search(r"constexpr\s+\w+\s+%s\s*=\s*(\d+)\s*;" % name, text)
+    assert m, name
+    return int(m.group(1))
+
+
 def test_new_kernels_use_no_scratch_and_spill_nothing():
+    """the stage's kernels are exactly these four (no second text of one of them under another name), and what each may use"""
     path = os.path.join(ROOT, "mvslam_amd", "lib", "kernel_resources.json")
     if not os.path.exists(path):
         pytest.fail("kernel_resources.json is missing: build the library first")
     digest = json.load(open(path))
-    mine = {k: v for k, v in digest.items() if "essential5" in k or "five_point_kernel" in k}
-    assert len(mine) == 3, list(mine)
+    assert not [k for k in digest if re.search(r"e5(_|wide)", k)]
+    mine = {}
+    for k, v in digest.items():
+        if "essential5" in k or "five_point_kernel" in k:
+            m = re.match(r"_ZN3mvs(\d+)", k)                  # mvs::<name>(...), Itanium mangling
+            assert m, k
+            mine[k[m.end():m.end() + int(m.group(1))]] = v
+    assert sorted(mine) == ["essential5_horizon_kernel", "essential5_select_kernel", "essential5_solve_count_kernel",
+                            "five_point_kernel"], list(mine)
     for k, v in mine.items():
         assert v["scratch_bytes_per_lane"] == 0 and v["vgpr_spills"] == 0, (k, v)
+    v = mine["essential5_horizon_kernel"]
+    assert v["sgpr_spills"] == 0 and v["static_lds_bytes"] == 0, v
+    # solve + count: dynamic LDS as essential5.hip sizes it -- the solver's workspace of 64 lanes + [4 wavefronts][10 roots]
+    # [64 lanes] int32 -- beside its static LDS in the 160 KB of a CU
+    v = mine["essential5_solve_count_kernel"]
+    assert v["sgpr_spills"] == 0, v
+    csrc = os.path.join(ROOT, "mvslam_amd", "csrc")
+    hdr = open(os.path.join(csrc, "five_point.hpp")).read() + open(os.path.join(csrc, "kernels.hpp")).read()
+    src = open(os.path.join(csrc, "essential5.hip")).read()
+    ws, roots, lanes = _constant(hdr, "kE5Ws"), _constant(hdr, "kE5MaxRoots"), _constant(hdr, "kE5HypPerBlock")
+    dynamic = ws * lanes * 8 + _constant(src, "kE5Waves") * roots * lanes * 4
+    assert dynamic == 141312 + 10240
+    assert v["static_lds_bytes"] + dynamic <= 163840, (v, dynamic)

@@ -8,9 +8,8 @@ five-point call, so KERNEL time is read from a kernel trace of this script, one 
 
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o e5 -- python tools/essential5_latency.py --confidence 0.99
 
-(rows essential5_solve_count_kernel and essential5_select_kernel -- with a confidence level also e5_solve_count_rounds_kernel,
-e5_horizon_kernel and e5_select_rounds_kernel -- against the ransac_* rows of
-OUT/**/e5_kernel_stats.csv: calls, total and average ns; both paths share prep_points_kernel, finalize_model_kernel,
+(rows essential5_solve_count_kernel and essential5_select_kernel -- with a confidence level also essential5_horizon_kernel, and
+one solve + count call per round -- against the ransac_* rows of OUT/**/e5_kernel_stats.csv: calls, total and average ns; both paths share prep_points_kernel, finalize_model_kernel,
 triangulate_kernel and finalize_select_kernel).  What the script itself prints is host wall time around upload + launch + sync
 -- not kernel time."""
 import os
