@@ -44,6 +44,9 @@ extern "C" {
 /* still 4: mvs_image_pair_essential, mvs_batch_run_essential, mvs_seq_run_essential, mvs_seq_download_hypotheses_run and
  * mvs_batch_download_essential_tables are additions (new symbols only): the five-point RANSAC behind the matcher, for one pair,
  * a batch and a sequence; no existing entry point or struct changed */
+/* still 4: mvs_vo_params, mvs_track_frame, mvs_vo_params_default, mvs_seq_track, mvs_seq_download_track_frames,
+ * mvs_seq_download_track_map and mvs_seq_download_track_step are additions (new symbols only): VisualOdometer::track on a
+ * resident sequence */
 #define MVS_ABI_VERSION 4
 
 typedef enum mvs_status {
@@ -423,7 +426,10 @@ mvs_status mvs_batch_gather_results(mvs_batch *b, int n_active, void *rccl_comm,
  * k-1 and `base` of pair k).  Track q (q = 0 .. n_frames-3) joins, on the device, the points of pair q (expressed in
  * frame q's camera) to their observations in frame q + 2 through pair q + 1's matches (the vf-index join of
  * visual-odometer.cpp:528-556) and runs pnp_solve on them: pose of frame q + 2 in frame q's camera frame.
- * The VO state machine itself (initialisation gates, scale propagation, BA) stays on the host / out of scope. */
+ * Of the VO state machine, scale propagation (mvs_seq_download_trajectory), BA (mvs_seq_refine_pairs,
+ * mvs_seq_refine_windows) and the tracking loop VisualOdometer::track with its persistent map (mvs_seq_track, below) run on
+ * the device behind mvs_seq_run; the initialisation gates (check_image_pair), ImagePair::update and reset() stay with the
+ * caller. */
 typedef struct mvs_seq mvs_seq;
 typedef struct mvs_track_result {
     int32_t ok;        /* pnp_solve returned true */
@@ -621,6 +627,101 @@ mvs_status mvs_seq_refine_windows(mvs_seq *s, const mvs_seq_window_params *wp, c
  * window without points has (frames[w * F].ok tells which): the convention of mvs_ba_refine_windows. */
 mvs_status mvs_seq_download_windows(mvs_seq *s, mvs_seq_window_info *info, mvs_refine_result *frames, double *points,
                                     double *point_cov, int32_t *track_kp, double *point_guess);
+
+/* The tracking loop of a sequence that has been run: VisualOdometer::track (front-end/visual-odometer.cpp:384-500) with
+ * track_pnp (:502-615) and track_refine (:618-800), every frame on the device, no host synchronisation between frames
+ * (DESIGN.md section 4.7.2).  Unlike the tracks of mvs_seq_run, which only see their own pair's two-view points, the loop
+ * keeps a PERSISTENT MAP of points in the init frame's coordinates and carries every refined point forward.
+ *
+ * Pair k = (frames k, k + 1).  Point j of a valid pair k (ImagePair::matched_points, image-pair.cpp:159-164) has the match
+ * row r_j = point_idx[k][j], the base keypoint a_j = trainIdx (frame k), the new keypoint b_j = queryIdx (frame k + 1) and
+ * the position x_j in frame k's camera.  Point j is KEPT iff no j' < j has the same a (the rule of the sliding windows'
+ * links, in place of the reference's unordered_map order and its assert at :443).
+ *   init    (:326-339) frames < init_pair = k0 are not reached (state 0); frame k0 is INIT at the identity, frame k0 + 1 INIT
+ *           at pair k0's pose; map[k0 + 1][b_j] = (id = rank of j among the kept points, x_j).  With use_refined_init pose
+ *           and points are those of mvs_seq_refine_pairs.  An invalid pair k0 (with use_refined_init also: one whose
+ *           refinement has ok = 0) leaves frame k0 + 1 LOST_PNP and nothing else reached.
+ *   step f = k0 + 2 .. n_frames - 1, pair k = f - 1, T_last = (R_l, t_l) the pose of frame f - 1, map[f - 1]:
+ *     1 candidates  the kept j with map[f - 1][a_j].id >= 0, ascending j: world point = the map's X, image point =
+ *                   (double)kp[f][b_j]                                                                    (:519-555)
+ *     2 PnP         mvs_pnp_solve on the candidates, refit included, sampler key pnp->seed + f.  False -- also fewer than 7
+ *                   candidates or an invalid pair -- is LOST_PNP
+ *     3 scale       sqrt((e0 e0 + e1 e1) + e2 e2), e = t_pnp - t_l: the norm of :584-587 (a rotation does not change it)
+ *     4 gate        n_pnp_inliers < min_pnp_point_count is LOST_FEW                                     (:409-415)
+ *     5 points      tracked = the PnP inliers in candidate order, positions from the map; new = the kept j without a map entry
+ *                   at a_j, ascending j, ids continuing one counter for the whole call, position y = scale x_j,
+ *                   X_i = ((R_l[i][0] y0 + R_l[i][1] y1) + R_l[i][2] y2) + t_l[i] (:422-445).  PnP outliers leave the map
+ *     6 BA          mvs_ba_refine's two-frame problem, points = tracked then new; frame 0 = frame f - 1 at T_last with
+ *                   anchor_var, frame 1 = frame f at the PnP pose with regulator_var; tracked points carry the prior
+ *                   point_sigma^2 I at their map position, new points none; frame 0 observes only the new points (at
+ *                   kp[f - 1][a_j]: last_frame_vf_idx_to_point_id is filled at :438 only), frame 1 all points (at
+ *                   kp[f][b_j]); observation covariance (sigma_px 2^octave)^2 I.  ok = 0 is LOST_BA, error > max_error
+ *                   LOST_ERROR (:479-483)
+ *     7 commit      T_last = the refined pose of frame 1; map[f][b] = (id, refined point) of every point of the problem,
+ *                   every other entry empty (:485-498)
+ *     8 a LOST frame ends the run: its record says why, later frames keep state 0 and empty maps, and every later kernel reads
+ *       one device word and leaves (the solvers see problems of 0 points).
+ * Out of scope: ImagePair::update re-pairing (image-pair.cpp:77-114), check_image_pair (:348-382), reset() and the
+ * re-initialisation after a loss (the caller picks init_pair and calls again), a C++ VisualOdometer shim. */
+typedef struct mvs_vo_params {
+    int32_t init_pair;           /* k0: the pair the map is initialised from (frames k0, k0 + 1) */
+    int32_t use_refined_init;    /* 1: take pose / points of pair k0 from mvs_seq_refine_pairs' resident results */
+    int32_t min_pnp_point_count; /* 7  (visual-odometer.cpp:86-87, used at :409) */
+    int32_t reserved;
+    double max_error;            /* 0.5 (:77-78, used at :479) */
+    double anchor_var[2];        /* last frame's prior, DIAGONAL covariance {rotation, translation}: {1e-3, 1e-3}.  The reference
+                                    multiplies the identity by the stddev itself (:684-699), so these are the values, unsquared */
+    double regulator_var[2];     /* new frame's prior {1e-2, 1e-2} (same lines) */
+    double point_sigma;          /* tracked points' prior point_sigma^2 I, 1e-2 (:728-730); new points have none (:719-725) */
+    double sigma_px;             /* observation covariance (sigma_px 2^octave)^2 I, 0.5, as mvs_batch_refine */
+} mvs_vo_params;
+void mvs_vo_params_default(mvs_vo_params *p);
+enum {
+    MVS_TRACK_NOT_REACHED = 0, MVS_TRACK_INIT = 1, MVS_TRACK_TRACKED = 2, MVS_TRACK_LOST_PNP = 3, MVS_TRACK_LOST_FEW = 4,
+    MVS_TRACK_LOST_BA = 5, MVS_TRACK_LOST_ERROR = 6
+};
+typedef struct mvs_track_frame {
+    int32_t state;          /* MVS_TRACK_* */
+    int32_t n_cand;         /* candidates of the join with the map */
+    int32_t n_pnp_inliers;
+    int32_t n_tracked;      /* points of the BA problem with a prior (= n_pnp_inliers when the step got that far) */
+    int32_t n_new;          /* points without one; for frame k0 + 1: the points the map starts with */
+    int32_t pnp_best_hyp;   /* -1: fewer than 7 candidates */
+    int32_t iterations;     /* of the BA */
+    int32_t reserved;
+    double scale;
+    double error;           /* of the BA */
+    double R_pnp[9], t_pnp[3];   /* the PnP pose, camera in init frame */
+    double R[9], t[3];           /* the accepted pose (INIT and TRACKED frames), camera in init frame; zero otherwise */
+} mvs_track_frame;
+/* Asynchronous on the ctx stream, after mvs_seq_run or mvs_seq_run_essential; the results stay resident until the next
+ * mvs_seq_track or mvs_seq_run.  Of `refine` only the Levenberg-Marquardt fields are used (the whole struct must be valid).
+ * Changes nothing mvs_seq_download_pairs / _tracks / _trajectory / _refined / _windows return.
+ * MVS_ERR_INVALID_ARG: a sequence that has not been run, init_pair outside [0, n_frames - 2], sigma_px <= 0,
+ * point_sigma <= 0, a variance <= 0, use_refined_init without resident refined pairs -- mvs_seq_refine_pairs must have run
+ * since the last mvs_seq_run / mvs_seq_run_essential --, PnP parameters mvs_seq_run refuses.
+ * Memory: every per-frame buffer lives in one block owned by the SEQUENCE, which only grows and is freed by mvs_seq_destroy.
+ * Frame f owns (14 max_kp + 24) doubles, (7 max_kp + 2) int32, max_kp bytes and about 1.5 KB of records of it -- 141 bytes per
+ * keypoint slot --, and the block ends with one step's solver scratch of 61 max_kp doubles and the PnP records: 0.29 GB for
+ * 1000 frames of 2048 keypoints. */
+mvs_status mvs_seq_track(mvs_seq *s, const mvs_vo_params *vo, const mvs_pnp_params *pnp, const mvs_refine_params *refine);
+/* frames[n_frames]; waits for the ctx stream.  MVS_ERR_INVALID_ARG before mvs_seq_track (all three downloads) */
+mvs_status mvs_seq_download_track_frames(mvs_seq *s, mvs_track_frame *frames);
+/* the map as it stands after `frame`, keyed by that frame's keypoint index: point_id[max_kp] (-1 = none), X[max_kp][3] (zero
+ * where there is none).  Either pointer may be NULL */
+mvs_status mvs_seq_download_track_map(mvs_seq *s, int frame, int32_t *point_id, double *X);
+/* What step `frame` fed its solvers and got back, so that a caller can replay them through mvs_pnp_solve / mvs_ba_refine.
+ * Any pointer may be NULL; every array has max_kp rows, rows past the count the frame's record gives are zero; a frame that
+ * is no step (or that the run did not reach) gives zeros.
+ *   candidates [n_cand]: cand_base_kp (a, frame - 1), cand_new_kp (b, frame), cand_xyz [3], cand_uv [2];
+ *   pnp_inlier_idx [n_pnp_inliers]: indices into the candidates, ascending;
+ *   BA problem [n_tracked + n_new]: point_id, point_kp [2] = (a, b), point_is_new (also: frame 0 observes the point),
+ *   point_guess [3], guess_pose [2][12] = R (9), t (3) of frame - 1 and frame; ba_frames [2]: the solver's records of both
+ *   frames, points_refined [3]. */
+mvs_status mvs_seq_download_track_step(mvs_seq *s, int frame, int32_t *cand_base_kp, int32_t *cand_new_kp, double *cand_xyz,
+                                       double *cand_uv, int32_t *pnp_inlier_idx, int32_t *point_id, int32_t *point_kp,
+                                       uint8_t *point_is_new, double *point_guess, double *guess_pose,
+                                       mvs_refine_result *ba_frames, double *points_refined);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Row f3: keypoint + descriptor extraction.  Replaces VisualFeature::extract

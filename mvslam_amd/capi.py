@@ -114,6 +114,20 @@ class SeqWindowInfo(C.Structure):
 WINDOW_INFO_DTYPE = np.dtype([("first_frame", "<i4"), ("n_frames", "<i4"), ("n_points", "<i4"), ("n_tracks_found", "<i4")])
 
 
+class VoParams(C.Structure):
+    """mvs_vo_params: the tracking loop of Sequence.track"""
+    _fields_ = [("init_pair", C.c_int32), ("use_refined_init", C.c_int32), ("min_pnp_point_count", C.c_int32),
+                ("reserved", C.c_int32), ("max_error", C.c_double), ("anchor_var", C.c_double * 2),
+                ("regulator_var", C.c_double * 2), ("point_sigma", C.c_double), ("sigma_px", C.c_double)]
+
+
+TRACK_NOT_REACHED, TRACK_INIT, TRACK_TRACKED, TRACK_LOST_PNP, TRACK_LOST_FEW, TRACK_LOST_BA, TRACK_LOST_ERROR = range(7)
+TRACK_FRAME_DTYPE = np.dtype([("state", "<i4"), ("n_cand", "<i4"), ("n_pnp_inliers", "<i4"), ("n_tracked", "<i4"),
+                              ("n_new", "<i4"), ("pnp_best_hyp", "<i4"), ("iterations", "<i4"), ("reserved", "<i4"),
+                              ("scale", "<f8"), ("error", "<f8"), ("R_pnp", "<f8", (3, 3)), ("t_pnp", "<f8", (3,)),
+                              ("R", "<f8", (3, 3)), ("t", "<f8", (3,))])   # mvs_track_frame
+
+
 class OrbParams(C.Structure):
     _fields_ = [("nfeatures", C.c_int32), ("nlevels", C.c_int32), ("edge_threshold", C.c_int32),
                 ("fast_threshold", C.c_int32)]
@@ -159,6 +173,8 @@ EXPORTS = [
     "mvs_batch_run_points_essential", "mvs_ctx_set_essential_confidence", "mvs_ctx_essential_hypotheses_run",
     "mvs_batch_download_hypotheses_run", "mvs_image_pair_essential", "mvs_batch_run_essential",
     "mvs_batch_download_essential_tables", "mvs_seq_run_essential", "mvs_seq_download_hypotheses_run",
+    "mvs_vo_params_default", "mvs_seq_track", "mvs_seq_download_track_frames", "mvs_seq_download_track_map",
+    "mvs_seq_download_track_step",
 ]
 
 
@@ -219,6 +235,7 @@ def lib():
         _lib.mvs_batch_destroy.argtypes = [C.c_void_p]
         _lib.mvs_seq_destroy.argtypes = [C.c_void_p]
         _lib.mvs_seq_window_count.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.mvs_vo_params_default.restype = None
     return _lib
 
 
@@ -239,6 +256,17 @@ def default_pnp_params(**kw):
     lib().mvs_pnp_params_default(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
+    return p
+
+
+def default_vo_params(**kw):
+    p = VoParams()
+    lib().mvs_vo_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k in ("anchor_var", "regulator_var"):
+            getattr(p, k)[0], getattr(p, k)[1] = float(v[0]), float(v[1])
+        else:
+            setattr(p, k, v)
     return p
 
 
@@ -1072,6 +1100,53 @@ class Sequence:
                             first_frame=int(info[w]["first_frame"]), n_frames=int(info[w]["n_frames"]), n_points=m,
                             n_tracks_found=int(info[w]["n_tracks_found"]), track_kp=tkp[w, :m].copy(),
                             point_guess=guess[w, :m].copy()))
+        return out
+
+    def track(self, vo_params=None, pnp_params=None, refine_params=None):
+        """VisualOdometer::track over the resident sequence (mvs_seq_track): persistent map, PnP, two-frame BA and the
+        gates of every frame behind init_pair, on the device (asynchronous; the download_track_* calls fetch the results)"""
+        vo_params = vo_params or default_vo_params()
+        pnp_params = pnp_params or default_pnp_params()
+        refine_params = refine_params or default_refine_params()
+        st = lib().mvs_seq_track(self._h, C.byref(vo_params), C.byref(pnp_params), C.byref(refine_params))
+        self.ctx._check(st, "mvs_seq_track")
+
+    def download_track_frames(self):
+        """one TRACK_FRAME_DTYPE record per frame"""
+        fr = np.zeros(self.n_frames, dtype=TRACK_FRAME_DTYPE)
+        self.ctx._check(lib().mvs_seq_download_track_frames(self._h, fr.ctypes.data_as(C.c_void_p)),
+                        "mvs_seq_download_track_frames")
+        return fr
+
+    def download_track_map(self, frame):
+        """the map as it stands after `frame`, keyed by the frame's keypoint index: point_id (-1 = none), X"""
+        pid, X = np.zeros(self.max_kp, dtype=np.int32), np.zeros((self.max_kp, 3))
+        st = lib().mvs_seq_download_track_map(self._h, C.c_int(frame), _ptr(pid, C.c_int32), _ptr(X, C.c_double))
+        self.ctx._check(st, "mvs_seq_download_track_map")
+        return dict(point_id=pid, X=X)
+
+    def download_track_step(self, frame, record=None):
+        """what step `frame` fed its solvers and got back, cut to the counts of the frame's record (download_track_frames()
+        [frame] when not given): candidates (cand_base_kp, cand_new_kp, cand_xyz, cand_uv), pnp_inliers, the BA problem
+        (point_id, point_kp [m, 2], point_is_new, point_guess, guess_pose [2, 12]), ba_frames [2] and points_refined"""
+        N = self.max_kp
+        rec = self.download_track_frames()[frame] if record is None else record
+        ca, cb, inl, pid = (np.zeros(N, dtype=np.int32) for _ in range(4))
+        cX, cuv, pkp, pnew = np.zeros((N, 3)), np.zeros((N, 2)), np.zeros((N, 2), dtype=np.int32), np.zeros(N, dtype=np.uint8)
+        guess, pose, pts = np.zeros((N, 3)), np.zeros((2, 12)), np.zeros((N, 3))
+        ba = np.zeros(2, dtype=REFINE_DTYPE)
+        st = lib().mvs_seq_download_track_step(self._h, C.c_int(frame), _ptr(ca, C.c_int32), _ptr(cb, C.c_int32),
+                                               _ptr(cX, C.c_double), _ptr(cuv, C.c_double), _ptr(inl, C.c_int32),
+                                               _ptr(pid, C.c_int32), _ptr(pkp, C.c_int32), _ptr(pnew, C.c_uint8),
+                                               _ptr(guess, C.c_double), _ptr(pose, C.c_double), ba.ctypes.data_as(C.c_void_p),
+                                               _ptr(pts, C.c_double))
+        self.ctx._check(st, "mvs_seq_download_track_step")
+        nc, ni, m = int(rec["n_cand"]), int(rec["n_pnp_inliers"]), int(rec["n_tracked"]) + int(rec["n_new"])
+        full = dict(cand_base_kp=ca, cand_new_kp=cb, cand_xyz=cX, cand_uv=cuv, pnp_inliers=inl, point_id=pid, point_kp=pkp,
+                    point_is_new=pnew, point_guess=guess, points_refined=pts)
+        cut = dict(cand_base_kp=nc, cand_new_kp=nc, cand_xyz=nc, cand_uv=nc, pnp_inliers=ni)
+        out = {k: v[:cut.get(k, m)].copy() for k, v in full.items()}
+        out.update(guess_pose=pose, ba_frames=ba, raw=b"".join(v.tobytes() for v in full.values()) + pose.tobytes() + ba.tobytes())
         return out
 
     def download_pairs(self):

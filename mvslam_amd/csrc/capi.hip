@@ -123,6 +123,11 @@ struct mvs_seq {
     DevWorkspace win;
     SeqWinDev wd{};             // n_windows = 0 until the first call
     WinDev ws{};
+    // mvs_seq_track: every per-frame buffer of the tracking loop and one step's solver scratch, resident until the next call
+    DevWorkspace trk;
+    VoDev vo{};
+    bool track_ran = false;
+    bool refined_ran = false;   // mvs_seq_refine_pairs has refined the pairs of the LAST run (use_refined_init reads them)
 };
 
 #define HIP_TRY(ctx_, expr)                                                                    \
@@ -2587,6 +2592,8 @@ static mvs_status seq_enqueue(mvs_seq *q, Estimator est, const RunParams &rp)
     HIP_TRY(q->ctx, hipGetLastError());
     q->ran = true;
     q->wd.n_windows = 0;   // windows of an earlier run are not this run's
+    q->track_ran = false;  // nor is its tracking loop
+    q->refined_ran = false;  // nor are refined pairs (the batch keeps them downloadable; mvs_seq_track does not start from them)
     return MVS_OK;
 }
 
@@ -3338,7 +3345,12 @@ mvs_status mvs_seq_download_trajectory(mvs_seq *q, double *R, double *t, double 
 
 mvs_status mvs_seq_refine_pairs(mvs_seq *q, const mvs_refine_params *params, double sigma_px)
 {
-    return q ? mvs_batch_refine(q->batch, params, sigma_px) : MVS_ERR_INVALID_ARG;
+    if (!q)
+        return MVS_ERR_INVALID_ARG;
+    const mvs_status st = mvs_batch_refine(q->batch, params, sigma_px);
+    if (st == MVS_OK)
+        q->refined_ran = q->ran;
+    return st;
 }
 
 // ---- sliding windows of a sequence that has been run ------------------------------------------------------------------
@@ -3480,6 +3492,260 @@ mvs_status mvs_seq_download_windows(mvs_seq *q, mvs_seq_window_info *info, mvs_r
     for (size_t w = 0; w < W; ++w)
         if (!frames[w * F].ok)
             return MVS_NO_MODEL;
+    return MVS_OK;
+}
+
+// ---- the tracking loop of a sequence that has been run ---------------------------------------
+void mvs_vo_params_default(mvs_vo_params *p)
+{
+    if (!p)
+        return;
+    p->init_pair = 0;
+    p->use_refined_init = 0;
+    p->min_pnp_point_count = 7;   // visual-odometer.cpp:86-87
+    p->reserved = 0;
+    p->max_error = 0.5;           // :77-78
+    p->anchor_var[0] = p->anchor_var[1] = 1e-3;         // :684-699: the identity times the stddev itself
+    p->regulator_var[0] = p->regulator_var[1] = 1e-2;
+    p->point_sigma = 1e-2;        // :728-730
+    p->sigma_px = 0.5;            // visual-feature.cpp:203
+}
+
+mvs_status mvs_seq_track(mvs_seq *q, const mvs_vo_params *vp, const mvs_pnp_params *pp, const mvs_refine_params *rp)
+{
+    if (!q || !vp || !pp || !refine_params_ok(rp) || !q->ran || vp->init_pair < 0 || vp->init_pair > q->n_frames - 2 ||
+        !(vp->sigma_px > 0.0) || !(vp->point_sigma > 0.0) || !(vp->anchor_var[0] > 0.0) || !(vp->anchor_var[1] > 0.0) ||
+        !(vp->regulator_var[0] > 0.0) || !(vp->regulator_var[1] > 0.0))
+        return MVS_ERR_INVALID_ARG;
+    if (pp->num_hypotheses < 1 || !(pp->reproj_error > 0.0) ||
+        (pp->sampler != MVS_SAMPLER_IDENTITY && pp->sampler != MVS_SAMPLER_PHILOX))
+        return MVS_ERR_INVALID_ARG;
+    if (vp->use_refined_init && !q->refined_ran)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const BatchDev &bd = q->batch->d;
+    const size_t F = (size_t)q->n_frames, N = (size_t)bd.max_kp, G = (size_t)(pp->num_hypotheses + 255) / 256;
+    const size_t D = sizeof(double), I = sizeof(int32_t);
+    // what the downloads read first (cleared before every run), then the maps' ids (set to -1), then one step's scratch
+    Carve L{64};
+    const size_t off_frames = L.take(F * sizeof(mvs_track_frame));
+    const size_t off_ncand = L.take(F * I), off_m = L.take(F * I);
+    const size_t off_pnp = L.take(F * sizeof(PnpOut));
+    const size_t off_ba = L.take(F * 2 * sizeof(mvs_refine_result));
+    const size_t off_pose = L.take(F * 24 * D);
+    const size_t off_ca = L.take(F * N * I), off_cb = L.take(F * N * I), off_inl = L.take(F * N * I);
+    const size_t off_pid = L.take(F * N * I), off_pkp = L.take(F * N * 2 * I), off_pnew = L.take(F * N);
+    const size_t off_cX = L.take(F * N * 3 * D), off_cuv = L.take(F * N * 2 * D), off_guess = L.take(F * N * 3 * D);
+    const size_t off_pts = L.take(F * N * 3 * D), off_mX = L.take(F * N * 3 * D);
+    const size_t off_state = L.take(2 * I), off_T = L.take(12 * D), off_gidx = L.take(F * sizeof(int64_t));
+    const size_t off_mid = L.take(F * N * I);
+    const size_t off_scratch = L.take(0);
+    const size_t off_xy = L.take(N * 2 * D), off_fb = L.take(N * 3 * D), off_rec = L.take(G * sizeof(PnpRec));
+    const size_t off_obs0 = L.take(N * 2 * D), off_obs1 = L.take(N * 2 * D), off_cov0 = L.take(N * 4 * D);
+    const size_t off_cov1 = L.take(N * 4 * D), off_cov3 = L.take(N * 9 * D), off_oi0 = L.take(N * 3 * D);
+    const size_t off_oi1 = L.take(N * 3 * D), off_pinfo = L.take(N * 6 * D), off_tmp = L.take(N * 3 * D);
+    // pnp_solve's refit: a one-frame problem over the step's inliers
+    const size_t off_robs = L.take(N * 2 * D), off_roi = L.take(N * 3 * D), off_rp0 = L.take(N * 3 * D);
+    const size_t off_rpinfo = L.take(N * 6 * D), off_rpts = L.take(N * 3 * D), off_rtmp = L.take(N * 3 * D);
+    const size_t off_rpose = L.take(12 * D), off_rm = L.take(I), off_rout = L.take(sizeof(mvs_refine_result));
+    q->track_ran = false;   // growing frees the block an earlier call's results live in
+    const mvs_status st = ws_grow(ctx, q->trk, L.total());
+    if (st != MVS_OK)
+        return st;
+    char *base = q->trk.ptr();
+    auto dbl = [&](size_t off) { return reinterpret_cast<double *>(base + off); };
+    auto i32 = [&](size_t off) { return reinterpret_cast<int32_t *>(base + off); };
+    VoDev d{};
+    d.n_frames = q->n_frames;
+    d.max_kp = bd.max_kp;
+    d.k0 = vp->init_pair;
+    d.use_refined = vp->use_refined_init != 0;
+    d.min_pnp_points = vp->min_pnp_point_count;
+    d.max_error = vp->max_error;
+    d.sigma_px = vp->sigma_px;
+    d.point_var = vp->point_sigma * vp->point_sigma;
+    d.results = bd.results;
+    d.matches = bd.matches;
+    d.points = bd.points;
+    d.point_idx = bd.point_idx;
+    d.kp = bd.kp1;
+    d.oct = bd.oct1;
+    d.refined = d.use_refined ? q->batch->refine.out : nullptr;
+    d.refined_pts = d.use_refined ? q->batch->refine.pts : nullptr;
+    d.state = i32(off_state);
+    d.T_last = dbl(off_T);
+    d.gidx = reinterpret_cast<int64_t *>(base + off_gidx);
+    d.frames = reinterpret_cast<mvs_track_frame *>(base + off_frames);
+    d.map_id = i32(off_mid);
+    d.map_X = dbl(off_mX);
+    d.n_cand = i32(off_ncand);
+    d.cand_a = i32(off_ca);
+    d.cand_b = i32(off_cb);
+    d.cand_X = dbl(off_cX);
+    d.cand_uv = dbl(off_cuv);
+    d.pnp_out = reinterpret_cast<PnpOut *>(base + off_pnp);
+    d.inliers = i32(off_inl);
+    d.m = i32(off_m);
+    d.pt_id = i32(off_pid);
+    d.pt_kp = i32(off_pkp);
+    d.pt_new = reinterpret_cast<uint8_t *>(base + off_pnew);
+    d.guess = dbl(off_guess);
+    d.pose0 = dbl(off_pose);
+    d.ba_out = reinterpret_cast<mvs_refine_result *>(base + off_ba);
+    d.pts = dbl(off_pts);
+    d.obs0 = dbl(off_obs0);
+    d.obs1 = dbl(off_obs1);
+    d.cov0 = dbl(off_cov0);
+    d.cov1 = dbl(off_cov1);
+    d.cov3 = dbl(off_cov3);
+    // the step's PnP: mvs_pnp_solve's problem, one slice per frame
+    PnpDev p{};
+    p.n_problems = 1;
+    p.stride = (int)N;
+    p.num_hypotheses = pp->num_hypotheses;
+    p.sampler = pp->sampler;
+    p.min_inliers = pp->min_inliers;
+    p.max_groups = (int)G;
+    p.seed = pp->seed;
+    p.thr2 = pp->reproj_error * pp->reproj_error;
+    p.K = q->pnp.K;
+    p.Kinv = q->pnp.Kinv;
+    p.xy = dbl(off_xy);
+    p.fb = dbl(off_fb);
+    p.rec = reinterpret_cast<PnpRec *>(base + off_rec);
+    RefineDev rf{};   // its refit, as seq_prepare sets it up for the tracks
+    rf.n_problems = 1;
+    rf.stride = (int)N;
+    rf.n_frames = 1;
+    {
+        mvs_refine_params dp;
+        mvs_refine_params_default(&dp);
+        dp.pose_sigma[0] = dp.pose_sigma[1] = kRefitPoseSigma;
+        rf.cfg = to_cfg(dp, 1);
+    }
+    rf.m = i32(off_rm);
+    rf.K = q->pnp.K;
+    rf.pose0 = dbl(off_rpose);
+    rf.obs[0] = dbl(off_robs);
+    rf.oinfo[0] = dbl(off_roi);
+    rf.pts0 = dbl(off_rp0);
+    rf.pinfo = dbl(off_rpinfo);
+    rf.pts = dbl(off_rpts);
+    rf.pts_tmp = dbl(off_rtmp);
+    rf.out = reinterpret_cast<mvs_refine_result *>(base + off_rout);
+    // the step's BA: mvs_ba_refine's problem (refine_single with RefineExtra), prior weights from the variances
+    RefineDev ba{};
+    ba.n_problems = 1;
+    ba.stride = (int)N;
+    ba.n_frames = 2;
+    ba.cfg = to_cfg(*rp, 2);
+    for (int k = 0; k < 6; ++k) {
+        ba.cfg.w[0][k] = 1.0 / vp->anchor_var[k / 3];
+        ba.cfg.w[1][k] = 1.0 / vp->regulator_var[k / 3];
+    }
+    ba.K = bd.K;
+    ba.obs[0] = d.obs0;
+    ba.obs[1] = d.obs1;
+    ba.oinfo[0] = dbl(off_oi0);
+    ba.oinfo[1] = dbl(off_oi1);
+    ba.pinfo = dbl(off_pinfo);
+    ba.pts_tmp = dbl(off_tmp);
+    hipStream_t s = ctx->stream;
+    HIP_TRY(ctx, hipMemsetAsync(base, 0, off_mid, s));
+    HIP_TRY(ctx, hipMemsetAsync(base + off_mid, 0xff, off_scratch - off_mid, s));
+    launch_vo_init(d, s);
+    for (int f = d.k0 + 2; f < q->n_frames; ++f) {
+        const size_t of = (size_t)f * N;
+        launch_vo_join(d, f, s);
+        p.n = d.n_cand + f;
+        p.gidx = d.gidx + f;
+        p.X = d.cand_X + 3 * of;
+        p.uv = d.cand_uv + 2 * of;
+        p.inliers = const_cast<int32_t *>(d.inliers) + of;
+        p.out = const_cast<PnpOut *>(d.pnp_out) + f;
+        launch_pnp(p, s);
+        if (pp->refit)
+            launch_pnp_refit(p, rf, kRefitPointSigma, s);
+        launch_vo_assemble(d, f, s);
+        ba.m = d.m + f;
+        ba.pose0_all = d.pose0 + 24 * (size_t)f;
+        ba.pose0 = ba.pose0_all + 12;
+        ba.pts0 = d.guess + 3 * of;
+        ba.pts = const_cast<double *>(d.pts) + 3 * of;
+        ba.out_all = const_cast<mvs_refine_result *>(d.ba_out) + 2 * (size_t)f;
+        ba.out = ba.out_all + 1;
+        launch_refine_prep(ba, d.cov0, d.cov1, d.cov3, 1.0 / d.point_var, const_cast<double *>(ba.oinfo[0]),
+                           const_cast<double *>(ba.oinfo[1]), const_cast<double *>(ba.pinfo), d.pt_new + of, nullptr, s);
+        launch_refine(ba, s);
+        launch_vo_commit(d, f, s);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    q->vo = d;
+    q->track_ran = true;
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_download_track_frames(mvs_seq *q, mvs_track_frame *frames)
+{
+    if (!q || !frames || !q->track_ran)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(frames, q->vo.frames, (size_t)q->n_frames * sizeof(mvs_track_frame), hipMemcpyDeviceToHost,
+                                ctx->stream));
+    HIP_TRY(ctx, sync_stream(ctx));
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_download_track_map(mvs_seq *q, int frame, int32_t *point_id, double *X)
+{
+    if (!q || !q->track_ran || frame < 0 || frame >= q->n_frames)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t N = (size_t)q->vo.max_kp, of = (size_t)frame * N;
+    hipStream_t s = ctx->stream;
+    if (point_id)
+        HIP_TRY(ctx, hipMemcpyAsync(point_id, q->vo.map_id + of, N * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (X)
+        HIP_TRY(ctx, hipMemcpyAsync(X, q->vo.map_X + 3 * of, N * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_download_track_step(mvs_seq *q, int frame, int32_t *cand_base_kp, int32_t *cand_new_kp, double *cand_xyz,
+                                       double *cand_uv, int32_t *pnp_inlier_idx, int32_t *point_id, int32_t *point_kp,
+                                       uint8_t *point_is_new, double *point_guess, double *guess_pose,
+                                       mvs_refine_result *ba_frames, double *points_refined)
+{
+    if (!q || !q->track_ran || frame < 0 || frame >= q->n_frames)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const VoDev &d = q->vo;
+    const size_t N = (size_t)d.max_kp, of = (size_t)frame * N;
+    hipStream_t s = ctx->stream;
+    const struct {
+        void *dst;
+        const void *src;
+        size_t bytes;
+    } parts[] = {{cand_base_kp, d.cand_a + of, N * sizeof(int32_t)},
+                 {cand_new_kp, d.cand_b + of, N * sizeof(int32_t)},
+                 {cand_xyz, d.cand_X + 3 * of, N * 3 * sizeof(double)},
+                 {cand_uv, d.cand_uv + 2 * of, N * 2 * sizeof(double)},
+                 {pnp_inlier_idx, d.inliers + of, N * sizeof(int32_t)},
+                 {point_id, d.pt_id + of, N * sizeof(int32_t)},
+                 {point_kp, d.pt_kp + 2 * of, N * 2 * sizeof(int32_t)},
+                 {point_is_new, d.pt_new + of, N},
+                 {point_guess, d.guess + 3 * of, N * 3 * sizeof(double)},
+                 {guess_pose, d.pose0 + 24 * (size_t)frame, 24 * sizeof(double)},
+                 {ba_frames, d.ba_out + 2 * (size_t)frame, 2 * sizeof(mvs_refine_result)},
+                 {points_refined, d.pts + 3 * of, N * 3 * sizeof(double)}};
+    for (const auto &pt : parts)
+        if (pt.dst)
+            HIP_TRY(ctx, hipMemcpyAsync(pt.dst, pt.src, pt.bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }
 

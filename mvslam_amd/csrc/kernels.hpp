@@ -302,6 +302,54 @@ struct SeqWinDev {
 };
 void launch_seq_windows(const SeqWinDev &d, hipStream_t stream);
 
+// ---- the tracking loop of a resident sequence (mvs_seq_track) -------------------------------------
+// Glue between the solvers of one step f (pair k = f - 1), one workgroup each: vo_join_kernel joins pair k's kept points with
+// map[f - 1] into frame f's slice of a PnpDev; vo_assemble_kernel reads the PnP result, applies the gates and writes the
+// two-frame problem refine_prep_kernel + refine_kernel<2> read; vo_commit_kernel reads the BA result, applies the error gate
+// and writes T_last and map[f].  state[0] = 0 once a frame is lost: every later kernel leaves at once.
+struct VoDev {
+    int n_frames, max_kp;              // the sequence: frames, keypoint capacity N of a frame
+    int k0, use_refined, min_pnp_points;
+    double max_error, sigma_px, point_var;   // point_var = point_sigma^2
+    // resident state of the sequence (mvs_seq_run, mvs_seq_refine_pairs)
+    const mvs_pair_result *results;    // [n_frames - 1]
+    const mvs_match *matches;          // [n_frames - 1][N]
+    const double *points;              // [n_frames - 1][N][3]
+    const int32_t *point_idx;          // [n_frames - 1][N]
+    const float *kp;                   // [n_frames][N][2]
+    const uint8_t *oct;                // [n_frames][N]
+    const mvs_refine_result *refined;  // [n_frames - 1], use_refined only
+    const double *refined_pts;         // [n_frames - 1][N][3], use_refined only
+    // the loop's state
+    int32_t *state;                    // {1 while the run goes on, next point id}
+    double *T_last;                    // R (9), t (3)
+    int64_t *gidx;                     // [n_frames] = f: the sampler key offset of step f's PnP
+    // per frame
+    mvs_track_frame *frames;           // [n_frames]
+    int32_t *map_id;                   // [n_frames][N] -1 = none
+    double *map_X;                     // [n_frames][N][3]
+    int32_t *n_cand;                   // [n_frames]
+    int32_t *cand_a, *cand_b;          // [n_frames][N] keypoints of the candidates in frame f - 1 / f
+    double *cand_X, *cand_uv;          // [n_frames][N][3 / 2]: the step's PnP problem
+    const PnpOut *pnp_out;             // [n_frames]
+    const int32_t *inliers;            // [n_frames][N]
+    int32_t *m;                        // [n_frames] points of the step's BA problem
+    int32_t *pt_id, *pt_kp;            // [n_frames][N], [n_frames][N][2] = (a, b)
+    uint8_t *pt_new;                   // [n_frames][N]: the point has no prior and frame 0 observes it
+    double *guess;                     // [n_frames][N][3]
+    double *pose0;                     // [n_frames][2][12]
+    const mvs_refine_result *ba_out;   // [n_frames][2]
+    const double *pts;                 // [n_frames][N][3] refined points
+    // one step's inputs of refine_prep_kernel
+    double *obs0, *obs1;               // [N][2]
+    double *cov0, *cov1;               // [N][4]
+    double *cov3;                      // [N][9]
+};
+void launch_vo_init(const VoDev &d, hipStream_t stream);
+void launch_vo_join(const VoDev &d, int f, hipStream_t stream);
+void launch_vo_assemble(const VoDev &d, int f, hipStream_t stream);
+void launch_vo_commit(const VoDev &d, int f, hipStream_t stream);
+
 // ---- VisualFeature::extract (row f3): ORB-style extraction for a batch of equally sized images ----------------
 constexpr int kOrbMaxLevels = 16;
 constexpr int kOrbSelCap = 16384;    // keys of one (image, level) the selection can hold in LDS (128 KB): 2 n_l <= this, or the

@@ -541,6 +541,323 @@ void launch_seq_join(const SeqJoinDev &j, hipStream_t stream)
     hipLaunchKernelGGL(seq_join_kernel, dim3(j.n_tracks), dim3(256), 0, stream, j);
 }
 
+// ---- the tracking loop of a resident sequence (mvs_seq_track) -------------------------------------
+// Glue kernels of one step, one workgroup of 256 each.  The arithmetic they do themselves (scale, a new point's position) is
+// written in the order the header states, + * sqrt only, no fma.
+namespace {
+
+// point j of pair k: base keypoint a (frame k), new keypoint b (frame k + 1); false for indices outside the frame arrays
+__device__ __forceinline__ bool vo_point(const VoDev &d, int k, int j, int &a, int &b)
+{
+    const int N = d.max_kp;
+    const size_t o = (size_t)k * N;
+    const int r = d.point_idx[o + j];
+    if ((unsigned)r >= (unsigned)N)
+        return false;
+    const mvs_match mt = d.matches[o + r];
+    a = mt.trainIdx;
+    b = mt.queryIdx;
+    return (unsigned)a < (unsigned)N && (unsigned)b < (unsigned)N;
+}
+
+// s_first[a] = the smallest point j of pair k with base keypoint a (INT_MAX: none): point j is kept iff s_first[a_j] == j.
+// A minimum does not depend on the order the points arrive in.  Returns the pair's point count; ends with a barrier.
+__device__ __forceinline__ int vo_first_table(const VoDev &d, int k, bool valid, int *s_first)
+{
+    const int N = d.max_kp, tid = threadIdx.x;
+    const int npts = valid ? min(max(d.results[k].n_points, 0), N) : 0;
+    for (int i = tid; i < N; i += 256)
+        s_first[i] = INT_MAX;
+    __syncthreads();
+    for (int j = tid; j < npts; j += 256) {
+        int a, b;
+        if (vo_point(d, k, j, a, b))
+            atomicMin(&s_first[a], j);
+    }
+    __syncthreads();
+    return npts;
+}
+
+// position of a flagged thread among the flagged threads of the workgroup, in thread order, behind `basepos` (which moves on
+// by their number): the ballot compaction of seq_join_kernel.  Every thread of the workgroup calls it.
+__device__ __forceinline__ int vo_compact(bool flag, int *s_tot, int &basepos)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const unsigned long long bal = __ballot(flag);
+    const int pre = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0)
+        s_tot[w] = __popcll(bal);
+    __syncthreads();
+    int off = basepos, tot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int v = s_tot[k];
+        off += (k < w) ? v : 0;
+        tot += v;
+    }
+    basepos += tot;
+    __syncthreads();
+    return off + pre;
+}
+
+// grid 1.  Frames k0 and k0 + 1, the map the run starts with, the loop's state words.
+__global__ __launch_bounds__(256) void vo_init_kernel(VoDev d)
+{
+    __shared__ int s_first[kMaxKp];
+    __shared__ int s_tot[4];
+    const int tid = threadIdx.x, N = d.max_kp, k = d.k0;
+    const mvs_pair_result &res = d.results[k];
+    const bool valid = res.valid != 0 && (!d.use_refined || d.refined[k].ok != 0);
+    const int npts = vo_first_table(d, k, valid, s_first);
+    for (int f = tid; f < d.n_frames; f += 256)
+        d.gidx[f] = f;
+    int32_t *mid = d.map_id + (size_t)(k + 1) * N;
+    double *mX = d.map_X + (size_t)(k + 1) * N * 3;
+    const double *x = (d.use_refined ? d.refined_pts : d.points) + (size_t)k * N * 3;
+    int basepos = 0;
+    for (int start = 0; start < npts; start += 256) {
+        const int j = start + tid;
+        int a = 0, b = 0;
+        const bool flag = j < npts && vo_point(d, k, j, a, b) && s_first[a] == j;
+        const int pos = vo_compact(flag, s_tot, basepos);
+        if (flag) {   // queryIdx values are unique within one match list
+            mid[b] = pos;
+            mX[3 * b] = x[3 * j];
+            mX[3 * b + 1] = x[3 * j + 1];
+            mX[3 * b + 2] = x[3 * j + 2];
+        }
+    }
+    if (tid == 0) {
+        const double *R = d.use_refined ? d.refined[k].R : res.R, *t = d.use_refined ? d.refined[k].t : res.t;
+        mvs_track_frame a{}, b{};
+        a.state = MVS_TRACK_INIT;
+        a.pnp_best_hyp = b.pnp_best_hyp = -1;
+        a.R[0] = a.R[4] = a.R[8] = 1.0;
+        b.state = valid ? MVS_TRACK_INIT : MVS_TRACK_LOST_PNP;
+        if (valid) {
+            b.n_new = basepos;
+            for (int i = 0; i < 9; ++i)
+                b.R[i] = d.T_last[i] = R[i];
+            for (int i = 0; i < 3; ++i)
+                b.t[i] = d.T_last[9 + i] = t[i];
+        }
+        d.frames[k] = a;
+        d.frames[k + 1] = b;
+        d.state[0] = valid ? 1 : 0;
+        d.state[1] = basepos;
+    }
+}
+
+// grid 1.  Step f, pair k = f - 1: the kept points whose base keypoint has a map entry, in point order, become frame f's PnP
+// problem (visual-odometer.cpp:519-555).
+__global__ __launch_bounds__(256) void vo_join_kernel(VoDev d, int f)
+{
+    __shared__ int s_first[kMaxKp];
+    __shared__ int s_tot[4];
+    const int tid = threadIdx.x, N = d.max_kp, k = f - 1;
+    if (d.state[0] == 0) {   // written by earlier kernels only: uniform
+        if (tid == 0)
+            d.n_cand[f] = 0;
+        return;
+    }
+    const int npts = vo_first_table(d, k, d.results[k].valid != 0, s_first);
+    const size_t of = (size_t)f * N, ol = (size_t)(f - 1) * N;
+    const int32_t *mid = d.map_id + ol;
+    const double *mX = d.map_X + 3 * ol;
+    const float *kpf = d.kp + 2 * of;
+    int32_t *ca = d.cand_a + of, *cb = d.cand_b + of;
+    double *X = d.cand_X + 3 * of, *uv = d.cand_uv + 2 * of;
+    int basepos = 0;
+    for (int start = 0; start < npts; start += 256) {
+        const int j = start + tid;
+        int a = 0, b = 0;
+        const bool flag = j < npts && vo_point(d, k, j, a, b) && s_first[a] == j && mid[a] >= 0;
+        const int pos = vo_compact(flag, s_tot, basepos);
+        if (flag) {   // pos < npts <= N
+            ca[pos] = a;
+            cb[pos] = b;
+            X[3 * pos] = mX[3 * a];
+            X[3 * pos + 1] = mX[3 * a + 1];
+            X[3 * pos + 2] = mX[3 * a + 2];
+            uv[2 * pos] = (double)kpf[2 * b];       // visual-feature.cpp:179-190 float -> double
+            uv[2 * pos + 1] = (double)kpf[2 * b + 1];
+        }
+    }
+    if (tid == 0)
+        d.n_cand[f] = basepos;
+}
+
+// grid 1.  Step f behind its PnP: the gates, the scale, and the two-frame problem of visual-odometer.cpp:618-800 as
+// mvs_ba_refine takes it -- covariances and flags for refine_prep_kernel, so that the informations are that entry's.
+__global__ __launch_bounds__(256) void vo_assemble_kernel(VoDev d, int f)
+{
+    __shared__ int s_first[kMaxKp];
+    __shared__ int s_tot[4];
+    const int tid = threadIdx.x, N = d.max_kp, k = f - 1;
+    const int alive = d.state[0], id0 = d.state[1];
+    double Tl[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i)
+        Tl[i] = d.T_last[i];
+    __syncthreads();   // thread 0 writes the state words below
+    if (alive == 0) {
+        if (tid == 0)
+            d.m[f] = 0;
+        return;
+    }
+    const PnpOut &po = d.pnp_out[f];
+    const int nc = d.n_cand[f];
+    const bool pnp_ok = nc >= 7 && po.ok != 0;   // pnp-solve.cpp:13,22
+    const int n_inl = pnp_ok ? min(max(po.n_inliers, 0), nc) : 0;
+    double scale = 0.0;
+    if (pnp_ok) {
+        const double e0 = po.t[0] - Tl[9], e1 = po.t[1] - Tl[10], e2 = po.t[2] - Tl[11];
+        scale = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
+    }
+    mvs_track_frame fr{};
+    fr.n_cand = nc;
+    fr.n_pnp_inliers = n_inl;
+    fr.pnp_best_hyp = nc >= 7 ? po.best_hyp : -1;
+    fr.scale = scale;
+    if (pnp_ok) {
+        for (int i = 0; i < 9; ++i)
+            fr.R_pnp[i] = po.R[i];
+        for (int i = 0; i < 3; ++i)
+            fr.t_pnp[i] = po.t[i];
+    }
+    if (!pnp_ok || n_inl < d.min_pnp_points) {
+        if (tid == 0) {
+            fr.state = pnp_ok ? MVS_TRACK_LOST_FEW : MVS_TRACK_LOST_PNP;
+            d.frames[f] = fr;
+            d.m[f] = 0;
+            d.state[0] = 0;
+        }
+        return;
+    }
+    const size_t of = (size_t)f * N, ol = (size_t)(f - 1) * N;
+    const int32_t *mid = d.map_id + ol, *ca = d.cand_a + of, *cb = d.cand_b + of, *inl = d.inliers + of;
+    const double *cX = d.cand_X + 3 * of;
+    const float *kpl = d.kp + 2 * ol, *kpf = d.kp + 2 * of;
+    const uint8_t *ocl = d.oct + ol, *ocf = d.oct + of;
+    int32_t *pid = d.pt_id + of, *pkp = d.pt_kp + 2 * of;
+    uint8_t *pnew = d.pt_new + of;
+    double *guess = d.guess + 3 * of;
+    auto put = [&](int p, int id, int a, int b, bool is_new, double X0, double X1, double X2) {
+        pid[p] = id;
+        pkp[2 * p] = a;
+        pkp[2 * p + 1] = b;
+        pnew[p] = is_new ? 1 : 0;
+        guess[3 * p] = X0, guess[3 * p + 1] = X1, guess[3 * p + 2] = X2;
+        d.obs0[2 * p] = (double)kpl[2 * a], d.obs0[2 * p + 1] = (double)kpl[2 * a + 1];
+        d.obs1[2 * p] = (double)kpf[2 * b], d.obs1[2 * p + 1] = (double)kpf[2 * b + 1];
+        // VisualFeature::get_point_estimates: stddev = 2^octave * sigma_px (a power of two scales exactly)
+        const double s0 = ldexp(d.sigma_px, min((int)ocl[a], kSeqWinMaxOctave));
+        const double s1 = ldexp(d.sigma_px, min((int)ocf[b], kSeqWinMaxOctave));
+        const double v0 = s0 * s0, v1 = s1 * s1, pv = is_new ? 0.0 : d.point_var;   // no prior on a new point
+        d.cov0[4 * p] = v0, d.cov0[4 * p + 1] = 0.0, d.cov0[4 * p + 2] = 0.0, d.cov0[4 * p + 3] = v0;
+        d.cov1[4 * p] = v1, d.cov1[4 * p + 1] = 0.0, d.cov1[4 * p + 2] = 0.0, d.cov1[4 * p + 3] = v1;
+#pragma unroll
+        for (int e = 0; e < 9; ++e)
+            d.cov3[9 * p + e] = (e % 4 == 0) ? pv : 0.0;
+    };
+    // tracked points: the PnP inliers in candidate order, where the map has them
+    for (int i = tid; i < n_inl; i += 256) {
+        const int c = min(max(inl[i], 0), nc - 1);
+        const int a = ca[c], b = cb[c];
+        put(i, mid[a], a, b, false, cX[3 * c], cX[3 * c + 1], cX[3 * c + 2]);
+    }
+    // new points: the kept points of the pair whose base keypoint the map does not hold, scaled and moved into the init frame
+    const int npts = vo_first_table(d, k, d.results[k].valid != 0, s_first);
+    const double *x = d.points + 3 * ol;   // pair k's points: [k][N][3]
+    int basepos = 0;
+    for (int start = 0; start < npts; start += 256) {
+        const int j = start + tid;
+        int a = 0, b = 0;
+        const bool flag = j < npts && vo_point(d, k, j, a, b) && s_first[a] == j && mid[a] < 0;
+        const int pos = vo_compact(flag, s_tot, basepos);
+        if (flag && n_inl + pos < N) {   // tracked + new <= kept points <= N: the bound never cuts
+            const double y0 = scale * x[3 * j], y1 = scale * x[3 * j + 1], y2 = scale * x[3 * j + 2];
+            put(n_inl + pos, id0 + pos, a, b, true, ((Tl[0] * y0 + Tl[1] * y1) + Tl[2] * y2) + Tl[9],
+                ((Tl[3] * y0 + Tl[4] * y1) + Tl[5] * y2) + Tl[10], ((Tl[6] * y0 + Tl[7] * y1) + Tl[8] * y2) + Tl[11]);
+        }
+    }
+    if (tid == 0) {
+        const int n_new = min(basepos, N - n_inl);
+        double *pose = d.pose0 + 24 * (size_t)f;
+        for (int i = 0; i < 12; ++i)
+            pose[i] = Tl[i];
+        for (int i = 0; i < 9; ++i)
+            pose[12 + i] = po.R[i];
+        for (int i = 0; i < 3; ++i)
+            pose[21 + i] = po.t[i];
+        fr.n_tracked = n_inl;
+        fr.n_new = n_new;
+        d.frames[f] = fr;   // the state stays 0 until vo_commit_kernel has seen the BA
+        d.m[f] = n_inl + n_new;
+        d.state[1] = id0 + n_new;
+    }
+}
+
+// grid 1.  Step f behind its BA: the error gate (visual-odometer.cpp:479-483), T_last and map[f] (:485-498).
+__global__ __launch_bounds__(256) void vo_commit_kernel(VoDev d, int f)
+{
+    const int tid = threadIdx.x, N = d.max_kp;
+    const int alive = d.state[0];
+    __syncthreads();   // thread 0 may clear the word below
+    if (alive == 0)
+        return;
+    const mvs_refine_result &r = d.ba_out[2 * (size_t)f + 1];   // the new frame
+    const int m = min(max(d.m[f], 0), N);
+    const int st = r.ok == 0 ? MVS_TRACK_LOST_BA : (r.error > d.max_error ? MVS_TRACK_LOST_ERROR : MVS_TRACK_TRACKED);
+    if (tid == 0) {
+        mvs_track_frame &fr = d.frames[f];
+        fr.state = st;
+        fr.iterations = r.iterations;
+        fr.error = r.error;
+        if (st == MVS_TRACK_TRACKED) {
+            for (int i = 0; i < 9; ++i)
+                fr.R[i] = d.T_last[i] = r.R[i];
+            for (int i = 0; i < 3; ++i)
+                fr.t[i] = d.T_last[9 + i] = r.t[i];
+        } else {
+            d.state[0] = 0;
+        }
+    }
+    if (st != MVS_TRACK_TRACKED)
+        return;
+    const size_t of = (size_t)f * N;
+    const int32_t *pid = d.pt_id + of, *pkp = d.pt_kp + 2 * of;
+    const double *P = d.pts + 3 * of;
+    int32_t *mid = d.map_id + of;
+    double *mX = d.map_X + 3 * of;
+    for (int p = tid; p < m; p += 256) {
+        const int b = pkp[2 * p + 1];   // < N (vo_point); unique within the problem
+        mid[b] = pid[p];
+        mX[3 * b] = P[3 * p];
+        mX[3 * b + 1] = P[3 * p + 1];
+        mX[3 * b + 2] = P[3 * p + 2];
+    }
+}
+
+}  // namespace
+
+void launch_vo_init(const VoDev &d, hipStream_t stream)
+{
+    hipLaunchKernelGGL(vo_init_kernel, dim3(1), dim3(256), 0, stream, d);
+}
+void launch_vo_join(const VoDev &d, int f, hipStream_t stream)
+{
+    hipLaunchKernelGGL(vo_join_kernel, dim3(1), dim3(256), 0, stream, d, f);
+}
+void launch_vo_assemble(const VoDev &d, int f, hipStream_t stream)
+{
+    hipLaunchKernelGGL(vo_assemble_kernel, dim3(1), dim3(256), 0, stream, d, f);
+}
+void launch_vo_commit(const VoDev &d, int f, hipStream_t stream)
+{
+    hipLaunchKernelGGL(vo_commit_kernel, dim3(1), dim3(256), 0, stream, d, f);
+}
+
 // ---- sliding windows of a sequence: links between consecutive frames, then the windows' problems 
 // grid n_frames - 1, block 256.  Pair k: a link is an inlier row r < n_matches of a valid pair; it joins keypoint trainIdx of
 // frame k to keypoint queryIdx of frame k + 1.  Rows that share a trainIdx: the smallest row wins (a minimum does not depend
