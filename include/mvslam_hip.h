@@ -44,6 +44,9 @@ extern "C" {
 /* still 4: mvs_image_pair_essential, mvs_batch_run_essential, mvs_seq_run_essential, mvs_seq_download_hypotheses_run and
  * mvs_batch_download_essential_tables are additions (new symbols only): the five-point RANSAC behind the matcher, for one pair,
  * a batch and a sequence; no existing entry point or struct changed */
+/* still 4: mvs_seq_run_lags, mvs_seq_download_lag_pairs, mvs_seq_download_lag_refined, mvs_vo_init_params, mvs_odo_frame,
+ * mvs_vo_init_params_default, mvs_seq_odometry, mvs_seq_download_odometry_frames and MVS_TRACK_INITIALIZING are additions
+ * (new symbols only): VisualOdometer::add_frame on the device */
 /* still 4: mvs_vo_params, mvs_track_frame, mvs_vo_params_default, mvs_seq_track, mvs_seq_download_track_frames,
  * mvs_seq_download_track_map and mvs_seq_download_track_step are additions (new symbols only): VisualOdometer::track on a
  * resident sequence */
@@ -428,8 +431,8 @@ mvs_status mvs_batch_gather_results(mvs_batch *b, int n_active, void *rccl_comm,
  * visual-odometer.cpp:528-556) and runs pnp_solve on them: pose of frame q + 2 in frame q's camera frame.
  * Of the VO state machine, scale propagation (mvs_seq_download_trajectory), BA (mvs_seq_refine_pairs,
  * mvs_seq_refine_windows) and the tracking loop VisualOdometer::track with its persistent map (mvs_seq_track, below) run on
- * the device behind mvs_seq_run; the initialisation gates (check_image_pair), ImagePair::update and reset() stay with the
- * caller. */
+ * the device behind mvs_seq_run; the initialisation gates (check_image_pair), ImagePair::update and reset() -- the whole of
+ * add_frame -- run on the device in mvs_seq_odometry (below), over the lagged pairs of mvs_seq_run_lags. */
 typedef struct mvs_seq mvs_seq;
 typedef struct mvs_track_result {
     int32_t ok;        /* pnp_solve returned true */
@@ -661,8 +664,9 @@ mvs_status mvs_seq_download_windows(mvs_seq *s, mvs_seq_window_info *info, mvs_r
  *                   every other entry empty (:485-498)
  *     8 a LOST frame ends the run: its record says why, later frames keep state 0 and empty maps, and every later kernel reads
  *       one device word and leaves (the solvers see problems of 0 points).
- * Out of scope: ImagePair::update re-pairing (image-pair.cpp:77-114), check_image_pair (:348-382), reset() and the
- * re-initialisation after a loss (the caller picks init_pair and calls again), a C++ VisualOdometer shim. */
+ * Out of scope HERE: ImagePair::update re-pairing (image-pair.cpp:77-114), check_image_pair (:348-382), reset() and the
+ * re-initialisation after a loss (the caller picks init_pair and calls again) -- mvs_seq_odometry below has them.  Out of
+ * scope altogether: a C++ VisualOdometer shim. */
 typedef struct mvs_vo_params {
     int32_t init_pair;           /* k0: the pair the map is initialised from (frames k0, k0 + 1) */
     int32_t use_refined_init;    /* 1: take pose / points of pair k0 from mvs_seq_refine_pairs' resident results */
@@ -678,7 +682,8 @@ typedef struct mvs_vo_params {
 void mvs_vo_params_default(mvs_vo_params *p);
 enum {
     MVS_TRACK_NOT_REACHED = 0, MVS_TRACK_INIT = 1, MVS_TRACK_TRACKED = 2, MVS_TRACK_LOST_PNP = 3, MVS_TRACK_LOST_FEW = 4,
-    MVS_TRACK_LOST_BA = 5, MVS_TRACK_LOST_ERROR = 6
+    MVS_TRACK_LOST_BA = 5, MVS_TRACK_LOST_ERROR = 6,
+    MVS_TRACK_INITIALIZING = 7   /* mvs_seq_odometry only: processed while initialising, and did not initialise */
 };
 typedef struct mvs_track_frame {
     int32_t state;          /* MVS_TRACK_* */
@@ -722,6 +727,99 @@ mvs_status mvs_seq_download_track_step(mvs_seq *s, int frame, int32_t *cand_base
                                        double *cand_uv, int32_t *pnp_inlier_idx, int32_t *point_id, int32_t *point_kp,
                                        uint8_t *point_is_new, double *point_guess, double *guess_pose,
                                        mvs_refine_result *ba_frames, double *points_refined);
+
+/* ---- lagged pairs of a resident sequence ---------------------------------------------------------
+ * Pair k of lag d = (base = frame k, pair = frame k + d), k < n_frames - d: the view of the frame arrays that the sequence's own
+ * pairs (lag 1) are, with the second image's pointers moved d frames on.  What VisualOdometer::initialize matches a new frame
+ * against (ImagePair::update, image-pair.cpp:77-114), and what keyframe selection or loop-closure candidates would need.
+ * Asynchronous on the ctx stream, after mvs_seq_run or mvs_seq_run_essential.  For every lag d = 2 .. max_lag all n_frames - d
+ * pairs go through the pipeline of mvs_batch_run (essential = 0) or mvs_batch_run_essential (essential != 0) and then through
+ * mvs_batch_refine with the frames' uploaded octaves and sigma_px; lag 1 is the existing run, for which mvs_seq_refine_pairs is
+ * (re)run.  Pair k of every lag uses sampler key offset k (the sequence's global indices), as pair k of an uploaded batch with
+ * global_index[k] = k does: the results are those of mvs_batch_run on a batch holding the same frame pairs in order k.
+ * match_ssd[k] (per pair, int32, 0 for an invalid pair) = the sum over the pair's triangulated points j of the squared
+ * integer Hamming distance of match row point_idx[k][j] (ImagePair::match_inlier_ssd, image-pair.cpp:166), for lag 1 too.
+ * After the call every lag 1 .. max_lag has resident results and refined results, until the next mvs_seq_run /
+ * mvs_seq_run_essential (a later mvs_seq_refine_pairs replaces lag 1's refined results only).
+ * MVS_ERR_INVALID_ARG: a sequence that has not been run, max_lag < 1 or >= n_frames, sigma_px <= 0, invalid refine
+ * parameters, two-view parameters mvs_seq_run refuses.
+ * Memory: ONE BATCH PER LAG, owned by the sequence, created at the first call that needs the lag and freed by
+ * mvs_seq_destroy; only the frame arrays, the intrinsics and the key offsets are shared with the sequence.  Per frame and lag
+ * that is 187 bytes per keypoint slot of pipeline state (matches, mask, points, point indices and the triangulation scratch)
+ * and 272 of refinement state -- 459 max_kp bytes and about 0.7 KB of records -- plus the RANSAC stage's hypothesis tables,
+ * 77 bytes x hypotheses for the 8-point path: 0.94 GB + 0.08 GB per 1000 hypotheses for one lag of 1000 frames of 2048 keypoints. */
+mvs_status mvs_seq_run_lags(mvs_seq *s, const mvs_params *two_view, int max_lag, int essential,
+                            const mvs_refine_params *refine, double sigma_px);
+/* The n_frames - lag pairs of a resident lag (1 .. max_lag of the last mvs_seq_run_lags; MVS_ERR_INVALID_ARG otherwise).  The
+ * argument lists follow mvs_seq_download_pairs / mvs_seq_download_refined: all pairs of the lag, n_matches is
+ * results[k].n_matches, point_idx is int64; match_ssd[n_frames - lag].  Any pointer but `refined` may be NULL.  Lag 1 returns
+ * what mvs_seq_download_pairs / mvs_seq_download_refined return. */
+mvs_status mvs_seq_download_lag_pairs(mvs_seq *s, int lag, mvs_pair_result *results, mvs_match *matches, uint8_t *inlier_mask,
+                                      double *points_xyz, int64_t *point_idx, int32_t *match_ssd);
+mvs_status mvs_seq_download_lag_refined(mvs_seq *s, int lag, mvs_refine_result *refined, double *points_xyz, double *point_cov);
+
+/* ---- VisualOdometer::add_frame over a resident sequence (front-end/visual-odometer.cpp:129-382) ----
+ * The state machine around the tracking loop above: initialisation from the frame queue with ImagePair::update re-pairing,
+ * check_image_pair, and reset() + re-initialisation after a loss, every frame on the device, no host synchronisation between
+ * frames.  vo->init_pair and vo->use_refined_init are ignored (initialize() always refines, :282-286); vo->max_error is also
+ * the initialisation's error gate (the reference uses one value at :363 and :479).  Q = frame_queue_size.
+ *
+ * Device state: mode; q0, the oldest frame still queued; held[b] for every queued base frame b = (pair frame, lag, valid,
+ * count = n_points, ssd = match_ssd, error, refined).  At the start mode = INITIALIZING, q0 = 0, segment = -1; frame 0 stays
+ * NOT_REACHED until a pair with base 0 initialises.
+ * Frame f = 1 .. n_frames - 1.  The frame is pushed before it is processed (:138) and the oldest is popped afterwards if the
+ * queue then holds more than Q (:181-190): while f is processed the queue holds frames max(q0, f - Q) .. f, so the largest lag
+ * is Q, and afterwards q0 = max(q0, f - Q + 1).
+ *   TRACKING      steps 1-7 of mvs_seq_track on pair k = f - 1, PnP sampler key seed + f.  A LOST_* verdict does not end the
+ *                 run: it is reset() (:203-217): mode = INITIALIZING, q0 = f (the lost frame is kept), the held pairs are
+ *                 dropped.  The lost frame's record keeps its LOST_* state and carries no pose.
+ *   INITIALIZING  held[f - 1] = (f, lag 1, validity / count / ssd of pair f - 1, error = +inf, not refined); count and ssd of
+ *                 an invalid pair are 0.
+ *     1 refine    a valid newest pair takes validity and error from its resident refined result (ok = 0: invalid, error +inf)
+ *     2 update    every queued b < f - 1, oldest first: ImagePair::update (mvslam_compat.hpp:1034-1051) with the lagged pair
+ *                 (b, f).  The candidate must be valid, must not have count < held[b].count nor ssd < held[b].ssd, and
+ *                 replaces held[b] only if its refined error is < held[b].error (a failed refinement counts as +inf).  As in
+ *                 the shim an INVALID held pair (count 0, ssd 0, error +inf) can be replaced; the reference starts ssd at
+ *                 (uint32)-1 and adds a float into it, which is out of range for the conversion back, so its behaviour there
+ *                 is undefined and the shim's is kept.
+ *     3 choice    the queue is scanned oldest first (:315-345); the first held[b] that passes check_image_pair AND whose pair
+ *                 frame is f (the reference asserts that at :327) initialises.  Gates in the order of :353-379: valid;
+ *                 count >= min_match_inlier_count; error <= max_error; rot_sq <= max_rotation_magnitude^2 with rot_sq =
+ *                 (w0 w0 + w1 w1) + w2 w2, w = SO3::ln of the refined rotation in the shim's operation order
+ *                 (mvslam_compat.hpp:176-184); abs_tz = |t[2]| <= max_translation_z.
+ *                 Initialising is mvs_seq_track's init with the refined pose and points of that lagged pair: frame b INIT at
+ *                 the identity (a base frame that is the lost frame of the segment before keeps its LOST_* record; its pose
+ *                 in the new segment is the identity), frame f INIT at the refined pose, map[f][b_j] = (id, refined x_j) over
+ *                 the kept points, ids continuing the call's one counter; segment += 1, mode = TRACKING.  Frames between b
+ *                 and f keep MVS_TRACK_INITIALIZING.
+ *     4 otherwise frame f is MVS_TRACK_INITIALIZING.
+ * The per-frame records, maps and steps are mvs_seq_track's: mvs_seq_download_track_frames / _track_map / _track_step serve
+ * an odometry run as they serve a tracking run, and the run lives in the same block of the sequence (plus 72 bytes per frame).
+ * Asynchronous on the ctx stream.  MVS_ERR_INVALID_ARG: what mvs_seq_track refuses except the init_pair and use_refined_init
+ * conditions; frame_queue_size < 2; min_match_inlier_count < 0; a negative (or NaN) gate; lags 1 .. min(Q, n_frames - 1) not
+ * all resident from one mvs_seq_run_lags since the last mvs_seq_run / mvs_seq_run_essential. */
+typedef struct mvs_vo_init_params {
+    int32_t frame_queue_size;        /* 10  (visual-odometer.cpp:71-72)  */
+    int32_t min_match_inlier_count;  /* 20  (:74-75, used at :358)       */
+    double  max_rotation_magnitude;  /* 0.1 (:80-81, used at :368-369)   */
+    double  max_translation_z;       /* 0.1 (:83-84, used at :374-375)   */
+} mvs_vo_init_params;                /* max_error is mvs_vo_params.max_error */
+void mvs_vo_init_params_default(mvs_vo_init_params *p);
+typedef struct mvs_odo_frame {
+    int32_t mode_after;     /* 0 INITIALIZING, 1 TRACKING: the state add_frame leaves behind */
+    int32_t segment;        /* -1 before the first initialisation; counts initialisations from 0 */
+    int32_t init_base;      /* for a frame that initialised: the base frame b of the chosen pair (b, f); -1 otherwise */
+    int32_t queue_first;    /* oldest frame in the queue when this frame was processed */
+    int32_t n_updated;      /* queue entries this frame's ImagePair::update replaced */
+    int32_t gate_fail;      /* for the NEWEST pair (f-1, f) when nothing initialised: 0 passed / not looked at, 1 invalid,
+                               2 inliers, 3 error, 4 rotation, 5 translation z  (the order of :353-379) */
+    double  rot_sq, abs_tz; /* of the chosen pair, or of the newest pair when none was chosen (0 for an invalid pair and for a
+                               frame processed while tracking) */
+} mvs_odo_frame;
+mvs_status mvs_seq_odometry(mvs_seq *s, const mvs_vo_params *vo, const mvs_vo_init_params *init,
+                            const mvs_pnp_params *pnp, const mvs_refine_params *refine);
+/* odo[n_frames]; waits for the ctx stream.  MVS_ERR_INVALID_ARG unless the sequence's last tracking call was mvs_seq_odometry */
+mvs_status mvs_seq_download_odometry_frames(mvs_seq *s, mvs_odo_frame *odo);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Row f3: keypoint + descriptor extraction.  Replaces VisualFeature::extract

@@ -122,6 +122,17 @@ class VoParams(C.Structure):
 
 
 TRACK_NOT_REACHED, TRACK_INIT, TRACK_TRACKED, TRACK_LOST_PNP, TRACK_LOST_FEW, TRACK_LOST_BA, TRACK_LOST_ERROR = range(7)
+TRACK_INITIALIZING = 7   # Sequence.odometry only: processed while initialising, and did not initialise
+
+
+class VoInitParams(C.Structure):
+    """mvs_vo_init_params: the frame queue and the initialisation gates of Sequence.odometry"""
+    _fields_ = [("frame_queue_size", C.c_int32), ("min_match_inlier_count", C.c_int32),
+                ("max_rotation_magnitude", C.c_double), ("max_translation_z", C.c_double)]
+
+
+ODO_FRAME_DTYPE = np.dtype([("mode_after", "<i4"), ("segment", "<i4"), ("init_base", "<i4"), ("queue_first", "<i4"),
+                            ("n_updated", "<i4"), ("gate_fail", "<i4"), ("rot_sq", "<f8"), ("abs_tz", "<f8")])   # mvs_odo_frame
 TRACK_FRAME_DTYPE = np.dtype([("state", "<i4"), ("n_cand", "<i4"), ("n_pnp_inliers", "<i4"), ("n_tracked", "<i4"),
                               ("n_new", "<i4"), ("pnp_best_hyp", "<i4"), ("iterations", "<i4"), ("reserved", "<i4"),
                               ("scale", "<f8"), ("error", "<f8"), ("R_pnp", "<f8", (3, 3)), ("t_pnp", "<f8", (3,)),
@@ -174,7 +185,8 @@ EXPORTS = [
     "mvs_batch_download_hypotheses_run", "mvs_image_pair_essential", "mvs_batch_run_essential",
     "mvs_batch_download_essential_tables", "mvs_seq_run_essential", "mvs_seq_download_hypotheses_run",
     "mvs_vo_params_default", "mvs_seq_track", "mvs_seq_download_track_frames", "mvs_seq_download_track_map",
-    "mvs_seq_download_track_step",
+    "mvs_seq_download_track_step", "mvs_seq_run_lags", "mvs_seq_download_lag_pairs", "mvs_seq_download_lag_refined",
+    "mvs_vo_init_params_default", "mvs_seq_odometry", "mvs_seq_download_odometry_frames",
 ]
 
 
@@ -236,6 +248,7 @@ def lib():
         _lib.mvs_seq_destroy.argtypes = [C.c_void_p]
         _lib.mvs_seq_window_count.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mvs_vo_params_default.restype = None
+        _lib.mvs_vo_init_params_default.restype = None
     return _lib
 
 
@@ -267,6 +280,14 @@ def default_vo_params(**kw):
             getattr(p, k)[0], getattr(p, k)[1] = float(v[0]), float(v[1])
         else:
             setattr(p, k, v)
+    return p
+
+
+def default_vo_init_params(**kw):
+    p = VoInitParams()
+    lib().mvs_vo_init_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
     return p
 
 
@@ -1148,6 +1169,59 @@ class Sequence:
         out = {k: v[:cut.get(k, m)].copy() for k, v in full.items()}
         out.update(guess_pose=pose, ba_frames=ba, raw=b"".join(v.tobytes() for v in full.values()) + pose.tobytes() + ba.tobytes())
         return out
+
+    def run_lags(self, params, max_lag, essential=False, refine_params=None, sigma_px=0.5):
+        """the pairs (k, k + d) of every lag d = 2 .. max_lag through the pipeline of run() (run_essential() if `essential`)
+        and ImagePair::refine, and refine_pairs() for lag 1 (mvs_seq_run_lags; asynchronous)"""
+        refine_params = refine_params or default_refine_params()
+        st = lib().mvs_seq_run_lags(self._h, C.byref(params), C.c_int(max_lag), C.c_int(1 if essential else 0),
+                                    C.byref(refine_params), C.c_double(sigma_px))
+        self.ctx._check(st, "mvs_seq_run_lags")
+
+    def download_lag_pairs(self, lag):
+        """download_pairs() for the n_frames - lag pairs of a resident lag, plus match_ssd"""
+        P, N = max(self.n_frames - lag, 1), self.max_kp
+        res = np.zeros(P, dtype=RESULT_DTYPE)
+        mt = np.zeros((P, N), dtype=MATCH_DTYPE)
+        mk = np.zeros((P, N), dtype=np.uint8)
+        pts = np.zeros((P, N, 3))
+        idx = np.zeros((P, N), dtype=np.int64)
+        ssd = np.zeros(P, dtype=np.int32)
+        st = lib().mvs_seq_download_lag_pairs(self._h, C.c_int(lag), res.ctypes.data_as(C.c_void_p),
+                                              mt.ctypes.data_as(C.c_void_p), _ptr(mk, C.c_uint8), _ptr(pts, C.c_double),
+                                              _ptr(idx, C.c_int64), _ptr(ssd, C.c_int32))
+        self.ctx._check(st, "mvs_seq_download_lag_pairs")
+        return dict(results=res, matches=mt, mask=mk, points=pts, point_idx=idx, match_ssd=ssd)
+
+    def download_lag_refined(self, lag, points=True, point_cov=False):
+        """download_refined() for a resident lag"""
+        P, N = max(self.n_frames - lag, 1), self.max_kp
+        res = np.zeros(P, dtype=REFINE_DTYPE)
+        pts = np.zeros((P, N, 3)) if points else None
+        pc = np.zeros((P, N, 3, 3)) if point_cov else None
+        st = lib().mvs_seq_download_lag_refined(self._h, C.c_int(lag), res.ctypes.data_as(C.c_void_p), _ptr(pts, C.c_double),
+                                                _ptr(pc, C.c_double))
+        self.ctx._check(st, "mvs_seq_download_lag_refined")
+        return dict(refined=res, points=pts, point_cov=pc)
+
+    def odometry(self, vo_params=None, init_params=None, pnp_params=None, refine_params=None):
+        """VisualOdometer::add_frame over the resident sequence (mvs_seq_odometry): initialisation from the frame queue with
+        re-pairing over the lags of run_lags(), the tracking loop of track(), reset and re-initialisation after a loss, on
+        the device (asynchronous; download_odometry_frames() and the download_track_* calls fetch the results)"""
+        vo_params = vo_params or default_vo_params()
+        init_params = init_params or default_vo_init_params()
+        pnp_params = pnp_params or default_pnp_params()
+        refine_params = refine_params or default_refine_params()
+        st = lib().mvs_seq_odometry(self._h, C.byref(vo_params), C.byref(init_params), C.byref(pnp_params),
+                                    C.byref(refine_params))
+        self.ctx._check(st, "mvs_seq_odometry")
+
+    def download_odometry_frames(self):
+        """one ODO_FRAME_DTYPE record per frame"""
+        od = np.zeros(self.n_frames, dtype=ODO_FRAME_DTYPE)
+        self.ctx._check(lib().mvs_seq_download_odometry_frames(self._h, od.ctypes.data_as(C.c_void_p)),
+                        "mvs_seq_download_odometry_frames")
+        return od
 
     def download_pairs(self):
         P, N = self.n_frames - 1, self.max_kp

@@ -128,6 +128,15 @@ struct mvs_seq {
     VoDev vo{};
     bool track_ran = false;
     bool refined_ran = false;   // mvs_seq_refine_pairs has refined the pairs of the LAST run (use_refined_init reads them)
+    // mvs_seq_run_lags: one batch per lag d >= 2 viewing the frame arrays (lag_batch[d], entries 0 and 1 stay null), the
+    // device table of what the state machine reads of every lag and the per-pair descriptor SSDs, resident until the next run
+    std::vector<mvs_batch *> lag_batch;
+    DevWorkspace lagws;         // LagDev[lag_cap + 1], then int32 ssd[lag_cap + 1][n_frames]
+    int lag_cap = 0;
+    std::vector<LagDev> lag_host;   // the table's host copy (the downloads read the ssd pointers from it)
+    int lags_ran = 0;           // lags 1 .. lags_ran are resident from one mvs_seq_run_lags since the last run
+    bool odo_ran = false;       // the resident tracking results are mvs_seq_odometry's
+    OdoDev odo{};
 };
 
 #define HIP_TRY(ctx_, expr)                                                                    \
@@ -443,9 +452,14 @@ static mvs_status alloc_refine(mvs_ctx *ctx, DevBlocks &owner, RefineDev &d, int
     g.add(r.m, T);
     g.add(r.out, T);
     const mvs_status st = g.commit();
-    if (st == MVS_OK)
-        d = r;
-    return st;
+    if (st != MVS_OK)
+        return st;
+    // rows [m, stride) of a problem are never written: zero, so that a download is the same bytes wherever the block came from
+    HIP_TRY(ctx, hipMemsetAsync(r.pts, 0, T * S * 3 * sizeof(double), ctx->stream));
+    if (r.point_cov)
+        HIP_TRY(ctx, hipMemsetAsync(r.point_cov, 0, T * S * 9 * sizeof(double), ctx->stream));
+    d = r;
+    return MVS_OK;
 }
 
 #ifdef MVS_DEBUG_HOOKS
@@ -993,14 +1007,18 @@ mvs_status mvs_ctx_essential_hypotheses_run(mvs_ctx *ctx, int32_t *n_run)
 // ---------------------------------------------------------------------------------------------
 // n_frames == 0: every pair owns its two images.  n_frames == n_pairs + 1: the images are the frames of a sequence,
 // stored once; pair k = (frame k, frame k + 1) is a view into the frame arrays (row f2).
-static mvs_status batch_create_impl(mvs_ctx *ctx, int n_pairs, int max_kp, int desc_bytes, int n_frames, mvs_batch **out);
+static mvs_status batch_create_impl(mvs_ctx *ctx, int n_pairs, int max_kp, int desc_bytes, int n_frames, mvs_batch **out,
+                                    const BatchDev *frames_of = nullptr, int lag = 1);
 
 mvs_status mvs_batch_create(mvs_ctx *ctx, int n_pairs, int max_kp, int desc_bytes, mvs_batch **out)
 {
     return batch_create_impl(ctx, n_pairs, max_kp, desc_bytes, 0, out);
 }
 
-static mvs_status batch_create_impl(mvs_ctx *ctx, int n_pairs, int max_kp, int desc_bytes, int n_frames, mvs_batch **out)
+// n_frames != 0: the batch of a sequence, pair k = (frame k, frame k + lag) viewing ONE set of frame arrays -- its own, or
+// with frames_of those (and the intrinsics and key offsets) of the sequence's lag-1 batch
+static mvs_status batch_create_impl(mvs_ctx *ctx, int n_pairs, int max_kp, int desc_bytes, int n_frames, mvs_batch **out,
+                                    const BatchDev *frames_of, int lag)
 {
     if (!ctx || !out || n_pairs < 1 || max_kp < 1)
         return MVS_ERR_INVALID_ARG;
@@ -1026,19 +1044,23 @@ static mvs_status batch_create_impl(mvs_ctx *ctx, int n_pairs, int max_kp, int d
     int64_t *gidx = nullptr;
     const size_t NI = n_frames ? (size_t)n_frames : P;  // images held by desc1 / kp1 / n1
     DevGroup g(ctx, b->blocks);
-    g.add(desc1, NI * N * d.desc_words);
-    g.add(kp1, NI * N * 2);
-    g.add(oct1, NI * N);
-    g.add(n1, NI);
+    if (!frames_of) {
+        g.add(desc1, NI * N * d.desc_words);
+        g.add(kp1, NI * N * 2);
+        g.add(oct1, NI * N);
+        g.add(n1, NI);
+    }
     if (!n_frames) {
         g.add(desc2, P * N * d.desc_words);
         g.add(kp2, P * N * 2);
         g.add(oct2, P * N);
         g.add(n2, P);
     }
-    g.add(Kinv, P * 9);
-    g.add(K, P * 9);
-    g.add(gidx, P);
+    if (!frames_of) {
+        g.add(Kinv, P * 9);
+        g.add(K, P * 9);
+        g.add(gidx, P);
+    }
     g.add(d.knn_train, P * N);
     g.add(d.knn_dist, P * N);
     g.add(d.M, P);
@@ -1058,28 +1080,41 @@ static mvs_status batch_create_impl(mvs_ctx *ctx, int n_pairs, int max_kp, int d
         mvs_batch_destroy(b);
         return st;
     }
-    if (n_frames) {  // pair k's second image is frame k + 1
-        desc2 = desc1 + N * d.desc_words;
-        kp2 = kp1 + N * 2;
-        oct2 = oct1 + N;
-        n2 = n1 + 1;
+    if (frames_of) {   // shared, never written through this batch; pair k of the view is pair k of the owner
+        desc1 = const_cast<uint32_t *>(frames_of->desc1);
+        kp1 = const_cast<float *>(frames_of->kp1);
+        oct1 = const_cast<uint8_t *>(frames_of->oct1);
+        n1 = const_cast<int32_t *>(frames_of->n1);
+        Kinv = const_cast<double *>(frames_of->Kinv);
+        K = const_cast<double *>(frames_of->K);
+        gidx = const_cast<int64_t *>(frames_of->gidx);
+    }
+    if (n_frames) {  // pair k's second image is frame k + lag
+        const size_t L = (size_t)lag;
+        desc2 = desc1 + L * N * d.desc_words;
+        kp2 = kp1 + L * N * 2;
+        oct2 = oct1 + L * N;
+        n2 = n1 + L;
     }
     d.desc1 = desc1; d.desc2 = desc2; d.kp1 = kp1; d.kp2 = kp2; d.n1 = n1; d.n2 = n2;
     d.oct1 = oct1; d.oct2 = oct2;
     d.Kinv = Kinv; d.K = K; d.gidx = gidx;   // the RANSAC stage's blocks stay null until ensure_groups
     hipStream_t s = ctx->stream;
     // deterministic contents for rows the caller never uploads
-    (void)hipMemsetAsync(desc1, 0, NI * N * d.desc_words * 4, s);
-    (void)hipMemsetAsync(kp1, 0, NI * N * 2 * sizeof(float), s);
-    (void)hipMemsetAsync(n1, 0, NI * sizeof(int32_t), s);
-    (void)hipMemsetAsync(oct1, 0, NI * N, s);   // octave 0 (stddev = sigma_px) unless the extractor / caller says otherwise
+    if (!frames_of) {
+        (void)hipMemsetAsync(desc1, 0, NI * N * d.desc_words * 4, s);
+        (void)hipMemsetAsync(kp1, 0, NI * N * 2 * sizeof(float), s);
+        (void)hipMemsetAsync(n1, 0, NI * sizeof(int32_t), s);
+        (void)hipMemsetAsync(oct1, 0, NI * N, s);   // octave 0 (stddev = sigma_px) unless the extractor / caller says otherwise
+    }
     if (!n_frames) {
         (void)hipMemsetAsync(oct2, 0, P * N, s);
         (void)hipMemsetAsync(desc2, 0, P * N * d.desc_words * 4, s);
         (void)hipMemsetAsync(kp2, 0, P * N * 2 * sizeof(float), s);
         (void)hipMemsetAsync(n2, 0, P * sizeof(int32_t), s);
     }
-    (void)hipMemsetAsync(gidx, 0, P * sizeof(int64_t), s);
+    if (!frames_of)
+        (void)hipMemsetAsync(gidx, 0, P * sizeof(int64_t), s);
     (void)hipMemsetAsync(d.M, 0, P * sizeof(int32_t), s);
     (void)hipMemsetAsync(d.results, 0, P * sizeof(mvs_pair_result), s);
     (void)hipMemsetAsync(d.mask, 0, P * N, s);
@@ -2486,6 +2521,9 @@ void mvs_seq_destroy(mvs_seq *q)
         return;
     (void)hipSetDevice(q->ctx->device);
     (void)sync_stream(q->ctx);
+    for (mvs_batch *lb : q->lag_batch)
+        if (lb)
+            mvs_batch_destroy(lb);
     if (q->batch)
         mvs_batch_destroy(q->batch);
     delete q;
@@ -2594,6 +2632,8 @@ static mvs_status seq_enqueue(mvs_seq *q, Estimator est, const RunParams &rp)
     q->wd.n_windows = 0;   // windows of an earlier run are not this run's
     q->track_ran = false;  // nor is its tracking loop
     q->refined_ran = false;  // nor are refined pairs (the batch keeps them downloadable; mvs_seq_track does not start from them)
+    q->lags_ran = 0;         // nor are lagged pairs
+    q->odo_ran = false;
     return MVS_OK;
 }
 
@@ -3511,17 +3551,21 @@ void mvs_vo_params_default(mvs_vo_params *p)
     p->sigma_px = 0.5;            // visual-feature.cpp:203
 }
 
-mvs_status mvs_seq_track(mvs_seq *q, const mvs_vo_params *vp, const mvs_pnp_params *pp, const mvs_refine_params *rp)
+// what mvs_seq_track and mvs_seq_odometry both refuse: everything but the choice of the initial pair
+static bool track_args_ok(const mvs_seq *q, const mvs_vo_params *vp, const mvs_pnp_params *pp, const mvs_refine_params *rp)
 {
-    if (!q || !vp || !pp || !refine_params_ok(rp) || !q->ran || vp->init_pair < 0 || vp->init_pair > q->n_frames - 2 ||
-        !(vp->sigma_px > 0.0) || !(vp->point_sigma > 0.0) || !(vp->anchor_var[0] > 0.0) || !(vp->anchor_var[1] > 0.0) ||
-        !(vp->regulator_var[0] > 0.0) || !(vp->regulator_var[1] > 0.0))
-        return MVS_ERR_INVALID_ARG;
-    if (pp->num_hypotheses < 1 || !(pp->reproj_error > 0.0) ||
-        (pp->sampler != MVS_SAMPLER_IDENTITY && pp->sampler != MVS_SAMPLER_PHILOX))
-        return MVS_ERR_INVALID_ARG;
-    if (vp->use_refined_init && !q->refined_ran)
-        return MVS_ERR_INVALID_ARG;
+    return q && vp && pp && refine_params_ok(rp) && q->ran && vp->sigma_px > 0.0 && vp->point_sigma > 0.0 &&
+           vp->anchor_var[0] > 0.0 && vp->anchor_var[1] > 0.0 && vp->regulator_var[0] > 0.0 && vp->regulator_var[1] > 0.0 &&
+           pp->num_hypotheses >= 1 && pp->reproj_error > 0.0 &&
+           (pp->sampler == MVS_SAMPLER_IDENTITY || pp->sampler == MVS_SAMPLER_PHILOX);
+}
+
+// The block's layout and the launches of a run whose arguments have been checked.  mvs_seq_track: ip = nullptr, the map
+// starts from pair k0 (vo_init_kernel).  mvs_seq_odometry: ip = the queue's parameters, k0 = 0, and the queue's two kernels
+// follow every step.
+static mvs_status seq_track_enqueue(mvs_seq *q, const mvs_vo_params *vp, int k0, bool use_refined, const mvs_vo_init_params *ip,
+                                    const mvs_pnp_params *pp, const mvs_refine_params *rp)
+{
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const BatchDev &bd = q->batch->d;
@@ -3549,7 +3593,11 @@ mvs_status mvs_seq_track(mvs_seq *q, const mvs_vo_params *vp, const mvs_pnp_para
     const size_t off_robs = L.take(N * 2 * D), off_roi = L.take(N * 3 * D), off_rp0 = L.take(N * 3 * D);
     const size_t off_rpinfo = L.take(N * 6 * D), off_rpts = L.take(N * 3 * D), off_rtmp = L.take(N * 3 * D);
     const size_t off_rpose = L.take(12 * D), off_rm = L.take(I), off_rout = L.take(sizeof(mvs_refine_result));
+    // the queue of mvs_seq_odometry, behind everything mvs_seq_track lays out
+    const size_t off_odo = L.take(ip ? F * sizeof(mvs_odo_frame) : 0), off_held = L.take(ip ? F * sizeof(OdoHeld) : 0);
+    const size_t off_q = L.take(ip ? kOdoWords * I : 0), off_odo_end = L.take(0);
     q->track_ran = false;   // growing frees the block an earlier call's results live in
+    q->odo_ran = false;
     const mvs_status st = ws_grow(ctx, q->trk, L.total());
     if (st != MVS_OK)
         return st;
@@ -3559,8 +3607,8 @@ mvs_status mvs_seq_track(mvs_seq *q, const mvs_vo_params *vp, const mvs_pnp_para
     VoDev d{};
     d.n_frames = q->n_frames;
     d.max_kp = bd.max_kp;
-    d.k0 = vp->init_pair;
-    d.use_refined = vp->use_refined_init != 0;
+    d.k0 = k0;
+    d.use_refined = use_refined;
     d.min_pnp_points = vp->min_pnp_point_count;
     d.max_error = vp->max_error;
     d.sigma_px = vp->sigma_px;
@@ -3654,7 +3702,24 @@ mvs_status mvs_seq_track(mvs_seq *q, const mvs_vo_params *vp, const mvs_pnp_para
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx, hipMemsetAsync(base, 0, off_mid, s));
     HIP_TRY(ctx, hipMemsetAsync(base + off_mid, 0xff, off_scratch - off_mid, s));
-    launch_vo_init(d, s);
+    OdoDev o{};
+    if (ip) {
+        o.queue_size = ip->frame_queue_size;
+        o.min_inliers = ip->min_match_inlier_count;
+        o.max_error = vp->max_error;
+        o.max_rot_sq = ip->max_rotation_magnitude * ip->max_rotation_magnitude;
+        o.max_tz = ip->max_translation_z;
+        o.lags = q->lagws.ptr<LagDev>();
+        o.odo = reinterpret_cast<mvs_odo_frame *>(base + off_odo);
+        o.held = reinterpret_cast<OdoHeld *>(base + off_held);
+        o.q = i32(off_q);
+        HIP_TRY(ctx, hipMemsetAsync(base + off_odo, 0, off_odo_end - off_odo, s));
+        launch_vo_odo_begin(d, o, s);
+        launch_vo_queue(d, o, 1, s);   // frame 1 cannot be a tracking step: its step's kernels are not enqueued
+        launch_vo_map_init(d, o, 1, s);
+    } else {
+        launch_vo_init(d, s);
+    }
     for (int f = d.k0 + 2; f < q->n_frames; ++f) {
         const size_t of = (size_t)f * N;
         launch_vo_join(d, f, s);
@@ -3679,10 +3744,140 @@ mvs_status mvs_seq_track(mvs_seq *q, const mvs_vo_params *vp, const mvs_pnp_para
                            const_cast<double *>(ba.oinfo[1]), const_cast<double *>(ba.pinfo), d.pt_new + of, nullptr, s);
         launch_refine(ba, s);
         launch_vo_commit(d, f, s);
+        if (ip) {
+            launch_vo_queue(d, o, f, s);
+            launch_vo_map_init(d, o, f, s);
+        }
     }
     HIP_TRY(ctx, hipGetLastError());
     q->vo = d;
     q->track_ran = true;
+    if (ip) {
+        q->odo = o;
+        q->odo_ran = true;
+    }
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_track(mvs_seq *q, const mvs_vo_params *vp, const mvs_pnp_params *pp, const mvs_refine_params *rp)
+{
+    if (!track_args_ok(q, vp, pp, rp) || vp->init_pair < 0 || vp->init_pair > q->n_frames - 2 ||
+        (vp->use_refined_init && !q->refined_ran))
+        return MVS_ERR_INVALID_ARG;
+    return seq_track_enqueue(q, vp, vp->init_pair, vp->use_refined_init != 0, nullptr, pp, rp);
+}
+
+// ---- lagged pairs and VisualOdometer::add_frame over them ------------------------------------------
+mvs_status mvs_seq_run_lags(mvs_seq *q, const mvs_params *two_view, int max_lag, int essential, const mvs_refine_params *rp,
+                            double sigma_px)
+{
+    if (!q || !q->ran || max_lag < 1 || max_lag >= q->n_frames || !refine_params_ok(rp) || !(sigma_px > 0.0))
+        return MVS_ERR_INVALID_ARG;
+    mvs_status st = check_params(two_view);
+    if (st != MVS_OK)
+        return st;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    q->lags_ran = 0;
+    const BatchDev &bd = q->batch->d;
+    const size_t F = (size_t)q->n_frames;
+    const Estimator est = essential ? Estimator::kFivePoint : Estimator::kEightPoint;
+    if ((int)q->lag_batch.size() < max_lag + 1)
+        q->lag_batch.resize((size_t)max_lag + 1, nullptr);
+    for (int lag = 2; lag <= max_lag; ++lag) {
+        if (!q->lag_batch[lag] && (st = batch_create_impl(ctx, q->n_frames - lag, bd.max_kp, bd.desc_words * 4, q->n_frames,
+                                                          &q->lag_batch[lag], &bd, lag)) != MVS_OK)
+            return st;
+        if ((st = ensure_tables(q->lag_batch[lag], est, two_view->num_hypotheses)) != MVS_OK)
+            return st;
+    }
+    if (max_lag > q->lag_cap) {
+        Carve L{64};
+        L.take(((size_t)max_lag + 1) * sizeof(LagDev));
+        L.take(((size_t)max_lag + 1) * F * sizeof(int32_t));
+        if ((st = ws_grow(ctx, q->lagws, L.total())) != MVS_OK)
+            return st;
+        q->lag_cap = max_lag;
+    }
+    const size_t off_ssd = Carve{64}.up(((size_t)q->lag_cap + 1) * sizeof(LagDev));
+    int32_t *ssd = reinterpret_cast<int32_t *>(q->lagws.ptr() + off_ssd);
+    hipStream_t s = ctx->stream;
+    const RunParams run = to_run(*two_view);
+    // a failure on the way leaves lags_ran = 0: nothing reads a half-run set of lags
+    for (int lag = 1; lag <= max_lag; ++lag) {
+        mvs_batch *b = lag == 1 ? q->batch : q->lag_batch[lag];
+        const int n = q->n_frames - lag;
+        if (lag > 1 && (st = est == Estimator::kEightPoint ? enqueue_pipeline(b, run, n, false, nullptr)
+                                                           : enqueue_essential(b, run, n)) != MVS_OK)
+            return st;
+        if ((st = mvs_batch_refine(b, rp, sigma_px)) != MVS_OK)
+            return st;
+        launch_pair_ssd(b->d.results, b->d.matches, b->d.point_idx, n, bd.max_kp, ssd + (size_t)lag * F, s);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    q->lag_host.assign((size_t)q->lag_cap + 1, LagDev{});
+    for (int lag = 1; lag <= max_lag; ++lag) {
+        const mvs_batch *b = lag == 1 ? q->batch : q->lag_batch[lag];
+        q->lag_host[lag] = LagDev{b->d.results, b->d.matches, b->d.point_idx, ssd + (size_t)lag * F, b->refine.out, b->refine.pts};
+    }
+    for (int lag = 1; lag <= max_lag; ++lag)   // the entry travels as a kernel argument: no host buffer has to outlive the call
+        launch_lag_table_set(q->lagws.ptr<LagDev>(), lag, q->lag_host[lag], s);
+    HIP_TRY(ctx, hipGetLastError());
+    q->refined_ran = true;   // lag 1's refinement is mvs_seq_refine_pairs
+    q->lags_ran = max_lag;
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_download_lag_pairs(mvs_seq *q, int lag, mvs_pair_result *results, mvs_match *matches, uint8_t *inlier_mask,
+                                      double *points_xyz, int64_t *point_idx, int32_t *match_ssd)
+{
+    if (!q || lag < 1 || lag > q->lags_ran)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    const int n = q->n_frames - lag;
+    if (match_ssd) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipMemcpyAsync(match_ssd, q->lag_host[lag].ssd, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return mvs_batch_download(lag == 1 ? q->batch : q->lag_batch[lag], 0, n, results, matches, inlier_mask, points_xyz, point_idx);
+}
+
+mvs_status mvs_seq_download_lag_refined(mvs_seq *q, int lag, mvs_refine_result *refined, double *points_xyz, double *point_cov)
+{
+    if (!q || lag < 1 || lag > q->lags_ran)
+        return MVS_ERR_INVALID_ARG;
+    return mvs_batch_download_refined(lag == 1 ? q->batch : q->lag_batch[lag], refined, points_xyz, point_cov);
+}
+
+void mvs_vo_init_params_default(mvs_vo_init_params *p)
+{
+    if (!p)
+        return;
+    p->frame_queue_size = 10;          // visual-odometer.cpp:71-72
+    p->min_match_inlier_count = 20;    // :74-75
+    p->max_rotation_magnitude = 0.1;   // :80-81
+    p->max_translation_z = 0.1;        // :83-84
+}
+
+mvs_status mvs_seq_odometry(mvs_seq *q, const mvs_vo_params *vp, const mvs_vo_init_params *ip, const mvs_pnp_params *pp,
+                            const mvs_refine_params *rp)
+{
+    // init_pair and use_refined_init are not looked at: the queue chooses the pair, and it is always a refined one
+    if (!track_args_ok(q, vp, pp, rp) || !ip || ip->frame_queue_size < 2 || ip->min_match_inlier_count < 0 ||
+        !(ip->max_rotation_magnitude >= 0.0) || !(ip->max_translation_z >= 0.0) || !(vp->max_error >= 0.0) ||
+        q->lags_ran < std::min(ip->frame_queue_size, q->n_frames - 1))
+        return MVS_ERR_INVALID_ARG;
+    return seq_track_enqueue(q, vp, 0, false, ip, pp, rp);
+}
+
+mvs_status mvs_seq_download_odometry_frames(mvs_seq *q, mvs_odo_frame *odo)
+{
+    if (!q || !odo || !q->track_ran || !q->odo_ran)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(odo, q->odo.odo, (size_t)q->n_frames * sizeof(mvs_odo_frame), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }
 

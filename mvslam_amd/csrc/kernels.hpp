@@ -350,6 +350,45 @@ void launch_vo_join(const VoDev &d, int f, hipStream_t stream);
 void launch_vo_assemble(const VoDev &d, int f, hipStream_t stream);
 void launch_vo_commit(const VoDev &d, int f, hipStream_t stream);
 
+// ---- lagged pairs and VisualOdometer::add_frame on a resident sequence (mvs_seq_run_lags, mvs_seq_odometry; DESIGN.md
+// section 4.7.3) ------------------------------------------------------------------------------------------------------------
+// ssd[k] = sum over the triangulated points j of pair k of the squared Hamming distance of match row point_idx[k][j]
+// (image-pair.cpp:166), 0 for an invalid pair.  Grid n_pairs, one workgroup per pair.
+void launch_pair_ssd(const mvs_pair_result *results, const mvs_match *matches, const int32_t *point_idx, int n_pairs, int max_kp,
+                     int32_t *ssd, hipStream_t stream);
+// what the state machine reads of lag d: pair k = (frame k, frame k + d), n_frames - d pairs
+struct LagDev {
+    const mvs_pair_result *results;    // [n_frames - d]
+    const mvs_match *matches;          // [n_frames - d][N]
+    const int32_t *point_idx;          // [n_frames - d][N]
+    const int32_t *ssd;                // [n_frames - d]
+    const mvs_refine_result *refined;  // [n_frames - d]
+    const double *refined_pts;         // [n_frames - d][N][3]
+};
+// the image pair the queue holds for base frame b (ImagePair of m_image_pair_queue)
+struct OdoHeld {
+    int32_t pair, lag, valid, count, ssd, refined;
+    double error;
+};
+// q = {q0: the oldest frame still queued, segment, lag / base of the pair that initialises this frame, 1: it does}
+constexpr int kOdoWords = 8;
+struct OdoDev {
+    int queue_size, min_inliers;             // Q, min_match_inlier_count
+    double max_error, max_rot_sq, max_tz;    // max_rot_sq = max_rotation_magnitude^2
+    const LagDev *lags;                      // [Q + 1] device table, entry 0 unused
+    int32_t *q;                              // [kOdoWords]
+    OdoHeld *held;                           // [n_frames]
+    mvs_odo_frame *odo;                      // [n_frames]
+};
+// The loop of mvs_seq_odometry enqueues, per frame f: the step's kernels of mvs_seq_track (they run while VoDev::state[0] = 1 =
+// TRACKING and leave at once otherwise), then vo_queue_kernel (reset() after a lost step, or -- INITIALIZING -- the new pair,
+// the update scan, the gates and the choice), then vo_map_init_kernel (the map of the chosen pair; sets state[0] = 1).
+// table[lag] = entry, by one thread: the device table of mvs_seq_run_lags is written entry by entry from kernel arguments
+void launch_lag_table_set(LagDev *table, int lag, const LagDev &entry, hipStream_t stream);
+void launch_vo_odo_begin(const VoDev &d, const OdoDev &o, hipStream_t stream);
+void launch_vo_queue(const VoDev &d, const OdoDev &o, int f, hipStream_t stream);
+void launch_vo_map_init(const VoDev &d, const OdoDev &o, int f, hipStream_t stream);
+
 // ---- VisualFeature::extract (row f3): ORB-style extraction for a batch of equally sized images ----------------
 constexpr int kOrbMaxLevels = 16;
 constexpr int kOrbSelCap = 16384;    // keys of one (image, level) the selection can hold in LDS (128 KB): 2 n_l <= this, or the

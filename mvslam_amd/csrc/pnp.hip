@@ -839,7 +839,282 @@ __global__ __launch_bounds__(256) void vo_commit_kernel(VoDev d, int f)
     }
 }
 
+// ---- lagged pairs and VisualOdometer::add_frame (mvs_seq_run_lags, mvs_seq_odometry) ---------------
+// grid n_pairs, block 256.  Integer sum: the order of the additions does not matter.
+__global__ __launch_bounds__(256) void pair_ssd_kernel(const mvs_pair_result *results, const mvs_match *matches,
+                                                       const int32_t *point_idx, int N, int32_t *ssd)
+{
+    __shared__ int s_sum[256];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const mvs_pair_result &res = results[k];
+    const int npts = res.valid != 0 ? min(max(res.n_points, 0), N) : 0;
+    const size_t o = (size_t)k * N;
+    int sum = 0;
+    for (int j = tid; j < npts; j += 256) {
+        const int r = point_idx[o + j];
+        if ((unsigned)r < (unsigned)N) {
+            const int dist = (int)matches[o + r].distance;   // an integer Hamming distance held in a float
+            sum += dist * dist;
+        }
+    }
+    s_sum[tid] = sum;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w)
+            s_sum[tid] += s_sum[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0)
+        ssd[k] = s_sum[0];
+}
+
+// grid 1, block 1.
+__global__ void lag_table_set_kernel(LagDev *table, int lag, LagDev entry)
+{
+    table[lag] = entry;
+}
+
+// grid 1, block 64.  The words a run starts from: INITIALIZING (state[0] = 0 by the host's memset), an empty queue that starts
+// at frame 0, no segment yet, the PnP's sampler key offsets.
+__global__ __launch_bounds__(64) void vo_odo_begin_kernel(VoDev d, OdoDev o)
+{
+    const int tid = threadIdx.x;
+    for (int f = tid; f < d.n_frames; f += 64)
+        d.gidx[f] = f;
+    if (tid == 0) {
+        o.q[0] = 0;
+        o.q[1] = -1;
+        o.q[2] = o.q[3] = o.q[4] = 0;
+        mvs_odo_frame r{};
+        r.segment = -1;
+        r.init_base = -1;
+        o.odo[0] = r;
+    }
+}
+
+// check_image_pair (visual-odometer.cpp:353-379) of a held pair with base frame b: 0 passed, else the first gate that fails in
+// the reference's order.  rot_sq / abs_tz are those of the refined pose whenever the pair is valid (a valid held pair has
+// been refined), 0 otherwise.  SO3::ln in the operation order of the shim (mvslam_compat.hpp:176-184).
+__device__ __forceinline__ int vo_check_pair(const OdoDev &o, const OdoHeld &h, int b, double &rot_sq, double &abs_tz)
+{
+    rot_sq = 0.0;
+    abs_tz = 0.0;
+    if (!h.valid)
+        return 1;
+    const mvs_refine_result &r = o.lags[h.lag].refined[b];
+    double c = 0.5 * (((r.R[0] + r.R[4]) + r.R[8]) - 1.0);
+    c = c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c);
+    const double theta = acos(c);
+    const double v0 = r.R[7] - r.R[5], v1 = r.R[2] - r.R[6], v2 = r.R[3] - r.R[1];
+    const double A = theta < 1e-5 ? (1.0 + theta * theta / 6.0) * 0.5 : 0.5 * theta / sin(theta);
+    const double w0 = v0 * A, w1 = v1 * A, w2 = v2 * A;
+    rot_sq = (w0 * w0 + w1 * w1) + w2 * w2;
+    abs_tz = fabs(r.t[2]);
+    if (h.count < o.min_inliers)
+        return 2;
+    if (h.error > o.max_error)
+        return 3;
+    if (rot_sq > o.max_rot_sq)
+        return 4;
+    if (abs_tz > o.max_tz)
+        return 5;
+    return 0;
+}
+
+// grid 1, block 64.  Frame f behind its step's kernels: what add_frame does around track() / initialize().
+//   queue   the frame is pushed before it is processed (visual-odometer.cpp:138) and the oldest frame is popped afterwards
+//           if the queue then holds more than Q frames (:181-190), so the queue holds at most Q after every frame and at most
+//           Q + 1 while frame f is processed: frames max(q0, f - Q) .. f, largest lag Q; afterwards q0 = max(q0, f - Q + 1).
+//           reset() (:203-217) keeps the last frame only: q0 = f, and no pop follows.
+//   TRACKING at entry: the step's kernels have written frames[f].state (2 .. 6).  A LOST_* state is reset(): state[0] is 0
+//           already (vo_assemble_kernel / vo_commit_kernel), q0 = f; the held pairs before f are never read again.
+//   INITIALIZING at entry (frames[f].state is still 0): held[f - 1] = the new adjacent pair, refined when valid (:283-286);
+//           ImagePair::update of every older queued base frame against the lagged pair (b, f) (:288-296), one lane per base
+//           frame; then the scan, oldest first (:315-345), by thread 0.
+__global__ __launch_bounds__(64) void vo_queue_kernel(VoDev d, OdoDev o, int f)
+{
+    __shared__ int s_upd;
+    const int tid = threadIdx.x, Q = o.queue_size;
+    const int st_f = d.frames[f].state, q0 = o.q[0], seg = o.q[1];
+    const int qf = max(q0, f - Q);
+    if (tid == 0)
+        s_upd = 0;
+    __syncthreads();   // thread 0 writes the words read above
+    mvs_odo_frame rec{};
+    rec.segment = seg;
+    rec.init_base = -1;
+    rec.queue_first = qf;
+    if (st_f != MVS_TRACK_NOT_REACHED) {
+        if (tid == 0) {
+            const bool tracked = st_f == MVS_TRACK_TRACKED;
+            rec.mode_after = tracked ? 1 : 0;
+            o.odo[f] = rec;
+            o.q[0] = tracked ? max(q0, f - Q + 1) : f;
+            o.q[4] = 0;
+        }
+        return;
+    }
+    const double inf = __longlong_as_double(0x7ff0000000000000ll);
+    if (tid == 0) {
+        const LagDev &L = o.lags[1];
+        const mvs_pair_result &res = L.results[f - 1];
+        OdoHeld h{};
+        h.pair = f;
+        h.lag = 1;
+        h.valid = res.valid != 0;
+        h.count = h.valid ? res.n_points : 0;
+        h.ssd = h.valid ? L.ssd[f - 1] : 0;
+        h.error = inf;
+        if (h.valid) {
+            const mvs_refine_result &rr = L.refined[f - 1];
+            h.valid = h.refined = rr.ok != 0;
+            if (rr.ok != 0)
+                h.error = rr.error;
+        }
+        o.held[f - 1] = h;
+    }
+    for (int b = qf + tid; b < f - 1; b += 64) {   // lag f - b <= Q: b >= f - Q
+        const int lag = f - b;
+        const LagDev &L = o.lags[lag];
+        const mvs_pair_result &res = L.results[b];
+        const OdoHeld h = o.held[b];
+        if (res.valid == 0)
+            continue;
+        const int cnt = res.n_points, ssd = L.ssd[b];
+        if (cnt < h.count || ssd < h.ssd)
+            continue;
+        const mvs_refine_result &rr = L.refined[b];
+        const double err = rr.ok != 0 ? rr.error : inf;
+        if (err < h.error) {   // so the refinement succeeded
+            OdoHeld n{};
+            n.pair = f;
+            n.lag = lag;
+            n.valid = n.refined = 1;
+            n.count = cnt;
+            n.ssd = ssd;
+            n.error = err;
+            o.held[b] = n;
+            atomicAdd(&s_upd, 1);
+        }
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (tid != 0)
+        return;
+    int chosen = -1;
+    double rot = 0.0, tz = 0.0;
+    for (int b = qf; b < f; ++b) {
+        const OdoHeld h = o.held[b];
+        double r2, az;
+        const int code = vo_check_pair(o, h, b, r2, az);
+        if (b == f - 1) {
+            rec.gate_fail = code;
+            rot = r2;
+            tz = az;
+        }
+        if (code == 0 && h.pair == f) {   // the reference asserts the latter (:327)
+            chosen = b;
+            rot = r2;
+            tz = az;
+            break;
+        }
+    }
+    rec.n_updated = s_upd;
+    rec.rot_sq = rot;
+    rec.abs_tz = tz;
+    if (chosen >= 0) {
+        rec.mode_after = 1;
+        rec.segment = seg + 1;
+        rec.init_base = chosen;
+        rec.gate_fail = 0;
+        o.q[1] = seg + 1;
+        o.q[2] = o.held[chosen].lag;
+        o.q[3] = chosen;
+    } else {
+        mvs_track_frame fr{};
+        fr.state = MVS_TRACK_INITIALIZING;
+        d.frames[f] = fr;
+    }
+    o.q[4] = chosen >= 0 ? 1 : 0;
+    o.q[0] = max(q0, f - Q + 1);
+    o.odo[f] = rec;
+}
+
+// grid 1.  vo_init_kernel for the pair vo_queue_kernel chose: base frame b, lag f - b, refined pose and points; ids go on from
+// the call's counter.  A base frame that is the lost frame of the segment before keeps its LOST_* record.
+__global__ __launch_bounds__(256) void vo_map_init_kernel(VoDev d, OdoDev o, int f)
+{
+    __shared__ int s_first[kMaxKp];
+    __shared__ int s_tot[4];
+    const int tid = threadIdx.x, N = d.max_kp;
+    if (o.q[4] == 0)   // written by vo_queue_kernel only: uniform
+        return;
+    const int lag = o.q[2], k = o.q[3], id0 = d.state[1];
+    const LagDev L = o.lags[lag];
+    VoDev e = d;   // vo_point / vo_first_table on the lag's tables
+    e.results = L.results;
+    e.matches = L.matches;
+    e.point_idx = L.point_idx;
+    const int npts = vo_first_table(e, k, true, s_first);
+    int32_t *mid = d.map_id + (size_t)f * N;
+    double *mX = d.map_X + (size_t)f * N * 3;
+    const double *x = L.refined_pts + (size_t)k * N * 3;
+    int basepos = 0;
+    for (int start = 0; start < npts; start += 256) {
+        const int j = start + tid;
+        int a = 0, b = 0;
+        const bool flag = j < npts && vo_point(e, k, j, a, b) && s_first[a] == j;
+        const int pos = vo_compact(flag, s_tot, basepos);
+        if (flag) {
+            mid[b] = id0 + pos;
+            mX[3 * b] = x[3 * j];
+            mX[3 * b + 1] = x[3 * j + 1];
+            mX[3 * b + 2] = x[3 * j + 2];
+        }
+    }
+    if (tid == 0) {
+        const mvs_refine_result &r = L.refined[k];
+        mvs_track_frame a{}, b{};
+        a.state = b.state = MVS_TRACK_INIT;
+        a.pnp_best_hyp = b.pnp_best_hyp = -1;
+        a.R[0] = a.R[4] = a.R[8] = 1.0;
+        b.n_new = basepos;
+        for (int i = 0; i < 9; ++i)
+            b.R[i] = d.T_last[i] = r.R[i];
+        for (int i = 0; i < 3; ++i)
+            b.t[i] = d.T_last[9 + i] = r.t[i];
+        const int sk = d.frames[k].state;
+        if (sk < MVS_TRACK_LOST_PNP || sk > MVS_TRACK_LOST_ERROR)
+            d.frames[k] = a;
+        d.frames[f] = b;
+        d.state[0] = 1;
+        d.state[1] = id0 + basepos;
+    }
+}
+
 }  // namespace
+
+void launch_pair_ssd(const mvs_pair_result *results, const mvs_match *matches, const int32_t *point_idx, int n_pairs, int max_kp,
+                     int32_t *ssd, hipStream_t stream)
+{
+    hipLaunchKernelGGL(pair_ssd_kernel, dim3(n_pairs), dim3(256), 0, stream, results, matches, point_idx, max_kp, ssd);
+}
+void launch_lag_table_set(LagDev *table, int lag, const LagDev &entry, hipStream_t stream)
+{
+    hipLaunchKernelGGL(lag_table_set_kernel, dim3(1), dim3(1), 0, stream, table, lag, entry);
+}
+void launch_vo_odo_begin(const VoDev &d, const OdoDev &o, hipStream_t stream)
+{
+    hipLaunchKernelGGL(vo_odo_begin_kernel, dim3(1), dim3(64), 0, stream, d, o);
+}
+void launch_vo_queue(const VoDev &d, const OdoDev &o, int f, hipStream_t stream)
+{
+    hipLaunchKernelGGL(vo_queue_kernel, dim3(1), dim3(64), 0, stream, d, o, f);
+}
+void launch_vo_map_init(const VoDev &d, const OdoDev &o, int f, hipStream_t stream)
+{
+    hipLaunchKernelGGL(vo_map_init_kernel, dim3(1), dim3(256), 0, stream, d, o, f);
+}
 
 void launch_vo_init(const VoDev &d, hipStream_t stream)
 {
