@@ -864,6 +864,53 @@ mvs_status mvs_seq_upload_images(mvs_seq *s, int first, int count, const uint8_t
  * (a failed track keeps the scale and falls back to the two-view pose of pair q+1).  Any pointer may be NULL. */
 mvs_status mvs_seq_download_trajectory(mvs_seq *s, double *R, double *t, double *pair_scale, double *track_scale);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The back end: pose graphs.  Replaces Graph / GraphOptimizer of back-end/graph.{hpp,cpp}, i.e. GTSAM's
+ * LevenbergMarquardtOptimizer over Pose3 values, BetweenFactor<Pose3> edges with full 6 x 6 covariances and one prior that
+ * anchors a node at its initial value.  The library minimises
+ *   1/2 [ |e_anchor|^2_Sa + sum_k |e_k|^2_Sk ],   Sa = diag(sigma_rot^2 I3, sigma_trans^2 I3),
+ *   e_k = ( Log(Rz^T Rs^T Rd),  Rz^T (Rs^T (td - ts) - tz) )     for edge k = (s, d, Z = (Rz, tz)): Z measures Xs^-1 Xd,
+ * tangent order (rotation, translation), right perturbation R <- R Exp(dw), t <- t + R dv, with the Levenberg-Marquardt
+ * rule of the refinement (the LM fields of mvs_refine_params).  Graphs of up to 16 nodes are solved by one workgroup with
+ * a dense Cholesky in LDS (a batch of them is one launch); up to 4096 nodes and 65536 edges by a block-Jacobi
+ * preconditioned conjugate gradient, one host synchronisation per LM iteration.  Binary64, fixed reduction orders: the
+ * same input gives the same bytes.  DESIGN.md section 4.10. */
+typedef struct mvs_pose_graph {            /* all host pointers */
+    int32_t n_nodes, n_edges;
+    const double *node_pose;               /* n_nodes x 12: initial values, R row-major (9) then t (3) */
+    const int32_t *edge_src, *edge_dst;    /* n_edges */
+    const double *edge_pose;               /* n_edges x 12: Z */
+    const double *edge_cov;                /* n_edges x 36: row-major 6 x 6, order (rotation, translation) */
+    int32_t anchor_node;                   /* the reference: the origin */
+} mvs_pose_graph;
+typedef struct mvs_pose_graph_params {
+    mvs_refine_params lm;                  /* only the LM fields: max_iterations, lambda_*, rel_tol, abs_tol */
+    double anchor_sigma[2];                /* rotation, translation: 1e-4, 1e-4 (graph.cpp GRAPH_ANCHOR_STDDEV) */
+    double cg_rel_tol;                     /* 1e-10: the linear solve of the large path stops at |r| <= cg_rel_tol |g| ... */
+    int32_t cg_max_iterations;             /* ... or after this many iterations; 0 = 6 n_nodes */
+    int32_t reserved;
+} mvs_pose_graph_params;
+typedef struct mvs_pose_graph_result {
+    int32_t ok;              /* 1: converged or stopped by the iteration / lambda limits with a finite error */
+    int32_t iterations;      /* linear solves attempted (LM iterations) */
+    int32_t cg_iterations;   /* conjugate-gradient iterations over all of them (0 on the dense path) */
+    int32_t rejected_steps;  /* LM iterations whose candidate was not accepted */
+    double error_initial;    /* 1/2 sum of squared Mahalanobis residuals at the initial values ... */
+    double error;            /* ... and at the estimate */
+} mvs_pose_graph_result;
+void mvs_pose_graph_params_default(mvs_pose_graph_params *p);
+/* poses_out: n_nodes x 12.  MVS_ERR_INVALID_ARG (null pointers, indices out of range, src == dst, non-finite input) and
+ * MVS_ERR_CAPACITY (more than 4096 nodes or 65536 edges) are returned before anything runs.  MVS_NO_MODEL with ok = 0 and
+ * poses_out untouched: a covariance that is not positive definite, or a node no path of edges joins to the anchor. */
+mvs_status mvs_pose_graph_optimize(mvs_ctx *ctx, const mvs_pose_graph *graph, const mvs_pose_graph_params *params,
+                                   mvs_pose_graph_result *result, double *poses_out);
+/* n_graphs graphs; graph i's poses at poses_out + i * 12 * (largest n_nodes of the batch), rows beyond its own node count
+ * are not written.  Graphs of up to 16 nodes share one launch, larger ones run one after another; every graph gets the
+ * bytes the single call returns for it.  MVS_NO_MODEL if some graph failed (results[i].ok tells which). */
+mvs_status mvs_pose_graph_optimize_batch(mvs_ctx *ctx, const mvs_pose_graph *graphs, int n_graphs,
+                                         const mvs_pose_graph_params *params, mvs_pose_graph_result *results,
+                                         double *poses_out);
+
 #ifdef __cplusplus
 }
 #endif

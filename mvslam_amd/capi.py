@@ -139,6 +139,29 @@ TRACK_FRAME_DTYPE = np.dtype([("state", "<i4"), ("n_cand", "<i4"), ("n_pnp_inlie
                               ("R", "<f8", (3, 3)), ("t", "<f8", (3,))])   # mvs_track_frame
 
 
+class PoseGraph(C.Structure):
+    """mvs_pose_graph: one pose graph, every pointer a host pointer"""
+    _fields_ = [("n_nodes", C.c_int32), ("n_edges", C.c_int32), ("node_pose", C.POINTER(C.c_double)),
+                ("edge_src", C.POINTER(C.c_int32)), ("edge_dst", C.POINTER(C.c_int32)),
+                ("edge_pose", C.POINTER(C.c_double)), ("edge_cov", C.POINTER(C.c_double)), ("anchor_node", C.c_int32)]
+
+
+class PoseGraphParams(C.Structure):
+    _fields_ = [("lm", RefineParams), ("anchor_sigma", C.c_double * 2), ("cg_rel_tol", C.c_double),
+                ("cg_max_iterations", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PoseGraphResult(C.Structure):
+    _fields_ = [("ok", C.c_int32), ("iterations", C.c_int32), ("cg_iterations", C.c_int32),
+                ("rejected_steps", C.c_int32), ("error_initial", C.c_double), ("error", C.c_double)]
+
+
+POSE_GRAPH_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("iterations", "<i4"), ("cg_iterations", "<i4"),
+                                    ("rejected_steps", "<i4"), ("error_initial", "<f8"), ("error", "<f8")])
+assert POSE_GRAPH_RESULT_DTYPE.itemsize == C.sizeof(PoseGraphResult)
+POSE_GRAPH_DENSE_MAX_NODES, POSE_GRAPH_MAX_NODES, POSE_GRAPH_MAX_EDGES = 16, 4096, 65536
+
+
 class OrbParams(C.Structure):
     _fields_ = [("nfeatures", C.c_int32), ("nlevels", C.c_int32), ("edge_threshold", C.c_int32),
                 ("fast_threshold", C.c_int32)]
@@ -187,6 +210,7 @@ EXPORTS = [
     "mvs_vo_params_default", "mvs_seq_track", "mvs_seq_download_track_frames", "mvs_seq_download_track_map",
     "mvs_seq_download_track_step", "mvs_seq_run_lags", "mvs_seq_download_lag_pairs", "mvs_seq_download_lag_refined",
     "mvs_vo_init_params_default", "mvs_seq_odometry", "mvs_seq_download_odometry_frames",
+    "mvs_pose_graph_params_default", "mvs_pose_graph_optimize", "mvs_pose_graph_optimize_batch",
 ]
 
 
@@ -310,6 +334,20 @@ def default_refine_params(**kw):
     return p
 
 
+def default_pose_graph_params(**kw):
+    """mvs_pose_graph_params_default; keywords name a field of the struct or an LM field of its `lm` member"""
+    p = PoseGraphParams()
+    lib().mvs_pose_graph_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k == "anchor_sigma":
+            p.anchor_sigma[0], p.anchor_sigma[1] = float(v[0]), float(v[1])
+        elif k in ("cg_rel_tol", "cg_max_iterations"):
+            setattr(p, k, v)
+        else:
+            setattr(p.lm, k, v)
+    return p
+
+
 def _ptr(a, t):
     return None if a is None else a.ctypes.data_as(C.POINTER(t))
 
@@ -416,6 +454,56 @@ class Context:
             out[ki.name.decode()] = d
             i += 1
         return out
+
+    def _pose_graph_call(self, graphs, params, poses_out, single):
+        """one graph through mvs_pose_graph_optimize (`single`) or a list through mvs_pose_graph_optimize_batch"""
+        params = params or default_pose_graph_params()
+        G = len(graphs)
+        arr = (PoseGraph * max(G, 1))()
+        keep = []
+        nmax = 0
+        for i, g in enumerate(graphs):
+            npose = _f64(g["node_pose"]).reshape(-1, 12)
+            src = np.ascontiguousarray(g["edge_src"], dtype=np.int32).reshape(-1)
+            dst = np.ascontiguousarray(g["edge_dst"], dtype=np.int32).reshape(-1)
+            ep = _f64(g["edge_pose"]).reshape(-1, 12)
+            ec = _f64(g["edge_cov"]).reshape(-1, 36)
+            if not (len(src) == len(dst) == len(ep) == len(ec)):
+                raise ValueError("pose graph %d: the per-edge arrays differ in length" % i)
+            keep.append((npose, src, dst, ep, ec))
+            arr[i].n_nodes, arr[i].n_edges = npose.shape[0], len(src)
+            arr[i].node_pose = _ptr(npose, C.c_double)
+            arr[i].edge_src, arr[i].edge_dst = _ptr(src, C.c_int32), _ptr(dst, C.c_int32)
+            arr[i].edge_pose, arr[i].edge_cov = _ptr(ep, C.c_double), _ptr(ec, C.c_double)
+            arr[i].anchor_node = int(g.get("anchor", 0))
+            nmax = max(nmax, npose.shape[0])
+        if poses_out is None:
+            poses_out = np.zeros((G, nmax, 12))
+        assert poses_out.dtype == np.float64 and poses_out.flags.c_contiguous and poses_out.shape == (G, nmax, 12)
+        res = np.zeros(G, dtype=POSE_GRAPH_RESULT_DTYPE)
+        if single:
+            st = lib().mvs_pose_graph_optimize(self._h, arr, C.byref(params), res.ctypes.data_as(C.c_void_p),
+                                               _ptr(poses_out, C.c_double))
+        else:
+            st = lib().mvs_pose_graph_optimize_batch(self._h, arr, C.c_int(G), C.byref(params),
+                                                     res.ctypes.data_as(C.c_void_p), _ptr(poses_out, C.c_double))
+        self._check(st, "mvs_pose_graph_optimize", allow_no_model=True)
+        return st, res, poses_out
+
+    def pose_graph_optimize_batch(self, graphs, params=None, poses_out=None):
+        """mvs_pose_graph_optimize_batch.  graphs: dicts with node_pose (N x 12: R row-major, then t), edge_src, edge_dst,
+        edge_pose (E x 12), edge_cov (E x 6 x 6) and anchor (default 0).  Returns
+        (status, results[POSE_GRAPH_RESULT_DTYPE], poses n_graphs x Nmax x 12); `poses_out` (that shape, float64,
+        contiguous) is written in place when given, rows the library does not write keep their bytes.  Argument and
+        capacity errors raise MvsError; MVS_NO_MODEL is returned."""
+        return self._pose_graph_call(graphs, params, poses_out, False)
+
+    def pose_graph_optimize(self, graph, params=None, poses_out=None):
+        """mvs_pose_graph_optimize: (status, result record, poses N x 12)"""
+        if poses_out is not None:
+            poses_out = poses_out.reshape(1, -1, 12)
+        st, res, poses = self._pose_graph_call([graph], params, poses_out, True)
+        return st, res[0], poses[0]
 
     # VisualFeature::match_visual_features(vf1 = train, vf2 = query, max_dist)
     def match_hamming(self, train_desc, query_desc, ratio=0.7, max_dist=-1.0):

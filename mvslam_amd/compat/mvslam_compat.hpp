@@ -1068,4 +1068,145 @@ private:
     Params m_params;
 };
 
+// ---- back-end/data-type.hpp:8-22, back-end/graph.hpp:15-113: the pose graph and its optimiser ------------------------
+// Graph keeps pose nodes and BetweenFactor edges (mean = what the edge measures, X_src^-1 X_dst; covariance 6 x 6 in GTSAM's
+// tangent order, rotation then translation, handed over unchanged as graph.cpp:153-155 does) with the origin anchored at
+// sigma = 1e-4 (graph.cpp GRAPH_ANCHOR_STDDEV); GraphOptimizer is mvs_pose_graph_optimize instead
+// of GTSAM's LevenbergMarquardtOptimizer.  print() is omitted.
+class BackEndTypes
+{
+public:
+    using NodeId = Id::Type;
+    using EdgeId = Id::Type;
+    using GraphId = Id::Type;
+    // monotonically increasing per process, never Id::INVALID
+    static NodeId generate_node_id() { static NodeId next = 0; return next++; }
+    static EdgeId generate_edge_id() { static EdgeId next = 0; return next++; }
+    static GraphId generate_graph_id() { static GraphId next = 0; return next++; }
+    using TransformationEdgeValue = TransformationEstimate;
+    using PoseNodeValue = Transformation;
+};
+
+class GraphOptimizer;
+class Graph
+{
+public:
+    explicit Graph(const BackEndTypes::PoseNodeValue &origin) : m_id(BackEndTypes::generate_graph_id())
+    {
+        m_origin = add_pose_node(origin);
+    }
+    BackEndTypes::NodeId add_pose_node(const BackEndTypes::PoseNodeValue &P)
+    {
+        const BackEndTypes::NodeId id = BackEndTypes::generate_node_id();
+        m_index[id] = m_nodes.size();
+        m_nodes.push_back(Node{id, P});
+        return id;
+    }
+    BackEndTypes::EdgeId add_transformation_edge(BackEndTypes::NodeId src, BackEndTypes::NodeId dst,
+                                                 const BackEndTypes::TransformationEdgeValue &T)
+    {
+        assert(has_node(src) && has_node(dst));
+        const BackEndTypes::EdgeId id = BackEndTypes::generate_edge_id();
+        m_edge_ids.insert(id);
+        m_edges.push_back(Edge{id, src, dst, T});
+        return id;
+    }
+    bool has_node(BackEndTypes::NodeId node_id) const { return node_id != Id::INVALID && m_index.count(node_id) == 1; }
+    bool has_edge(BackEndTypes::EdgeId edge_id) const { return edge_id != Id::INVALID && m_edge_ids.count(edge_id) == 1; }
+    BackEndTypes::PoseNodeValue get_pose_node_value(BackEndTypes::NodeId node_id) const
+    {
+        assert(has_node(node_id));
+        return m_nodes[m_index.at(node_id)].value;
+    }
+    std::unordered_map<BackEndTypes::NodeId, BackEndTypes::PoseNodeValue> get_all_pose_node_value() const
+    {
+        std::unordered_map<BackEndTypes::NodeId, BackEndTypes::PoseNodeValue> out;
+        for (const Node &n : m_nodes)
+            out[n.id] = n.value;
+        return out;
+    }
+    bool reconcile_with(Graph &) { return false; }   // the reference asserts "NOT implemented yet" (graph.cpp:196-208)
+    BackEndTypes::GraphId get_id() const { return m_id; }
+    BackEndTypes::NodeId get_origin_node_id() const { return m_origin; }
+
+private:
+    friend class GraphOptimizer;
+    struct Node { BackEndTypes::NodeId id; BackEndTypes::PoseNodeValue value; };
+    struct Edge { BackEndTypes::EdgeId id; BackEndTypes::NodeId src, dst; BackEndTypes::TransformationEdgeValue value; };
+    BackEndTypes::GraphId m_id;
+    BackEndTypes::NodeId m_origin;
+    std::vector<Node> m_nodes;                                   // in insertion order: the node index of the C ABI
+    std::vector<Edge> m_edges;
+    std::unordered_map<BackEndTypes::NodeId, size_t> m_index;
+    std::unordered_set<BackEndTypes::EdgeId> m_edge_ids;
+};
+
+namespace hip
+{
+inline mvs_pose_graph_params &pose_graph_config()
+{
+    static mvs_pose_graph_params p = [] { mvs_pose_graph_params q; mvs_pose_graph_params_default(&q); return q; }();
+    return p;
+}
+}  // namespace hip
+
+class GraphOptimizer
+{
+public:
+    explicit GraphOptimizer(const Graph &g) : m_graph(g), m_optimized(false) {}   // a deep copy (graph.hpp:84-89)
+    // blocks until convergence or the iteration limit (graph.hpp:94-97); a graph the library cannot solve keeps its values
+    void optimize()
+    {
+        const size_t N = m_graph.m_nodes.size(), E = m_graph.m_edges.size();
+        std::vector<double> np(12 * N), ep(12 * E), ec(36 * E), out(12 * N);
+        std::vector<int32_t> src(E), dst(E);
+        auto put = [](const Transformation &T, double *p) {
+            std::memcpy(p, T.rotation().get_matrix().data(), 9 * sizeof(double));
+            for (int k = 0; k < 3; ++k)
+                p[9 + k] = T.translation()[k];
+        };
+        for (size_t i = 0; i < N; ++i)
+            put(m_graph.m_nodes[i].value, &np[12 * i]);
+        for (size_t k = 0; k < E; ++k) {
+            const Graph::Edge &e = m_graph.m_edges[k];
+            src[k] = (int32_t)m_graph.m_index.at(e.src);
+            dst[k] = (int32_t)m_graph.m_index.at(e.dst);
+            put(e.value.mean(), &ep[12 * k]);
+            std::memcpy(&ec[36 * k], e.value.covar().data(), 36 * sizeof(double));
+        }
+        mvs_pose_graph pg{};
+        pg.n_nodes = (int32_t)N, pg.n_edges = (int32_t)E;
+        pg.node_pose = np.data(), pg.edge_src = src.data(), pg.edge_dst = dst.data();
+        pg.edge_pose = ep.data(), pg.edge_cov = ec.data();
+        pg.anchor_node = (int32_t)m_graph.m_index.at(m_graph.m_origin);
+        mvs_pose_graph_result res{};
+        const mvs_status st = mvs_pose_graph_optimize(hip::context(), &pg, &hip::pose_graph_config(), &res, out.data());
+        if (st == MVS_NO_MODEL)
+            return;
+        hip::check(st, "mvs_pose_graph_optimize");
+        for (size_t i = 0; i < N; ++i)
+            m_graph.m_nodes[i].value = se3_from_arrays_(&out[12 * i], &out[12 * i + 9]);
+        m_optimized = true;
+        m_result = res;
+    }
+    // only values of nodes known to both are written; nothing is added (graph.hpp:99-108)
+    bool update_graph(Graph &g)
+    {
+        if (!m_optimized)
+            return false;
+        for (const Graph::Node &n : m_graph.m_nodes) {
+            auto it = g.m_index.find(n.id);
+            if (it != g.m_index.end())
+                g.m_nodes[it->second].value = n.value;
+        }
+        return true;
+    }
+    const mvs_pose_graph_result &result() const { return m_result; }   // not in the reference: what the solver reported
+
+private:
+    Graph m_graph;
+    bool m_optimized;
+    mvs_pose_graph_result m_result{};
+};
+
 }  // namespace mvSLAM

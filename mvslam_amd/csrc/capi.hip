@@ -60,6 +60,7 @@ struct mvs_ctx {
     DevWorkspace pnp;         // pnp_solve workspace
     DevWorkspace ref;         // sfm_refine / pnp_refine workspace
     DevWorkspace win;         // mvs_ba_refine_windows workspace
+    DevWorkspace pg;          // mvs_pose_graph_optimize workspace
     DevWorkspace orb;         // extraction workspace: orb_graph points into it
     int32_t *h_orb_ovf = nullptr;   // pinned: the extraction's overflow flag travels with the outputs (one stream wait per call)
     bool orb_ready = false;
@@ -4290,4 +4291,328 @@ mvs_status mvs_seq_upload_images(mvs_seq *q, int first, int count, const uint8_t
     return K ? mvs_seq_upload(q, first, count, nullptr, nullptr, nullptr, K) : MVS_OK;
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// pose graphs (the back end; posegraph.hip)
+void mvs_pose_graph_params_default(mvs_pose_graph_params *p)
+{
+    if (!p)
+        return;
+    mvs_refine_params_default(&p->lm);
+    p->anchor_sigma[0] = p->anchor_sigma[1] = 1e-4;   // graph.cpp GRAPH_ANCHOR_STDDEV
+    p->cg_rel_tol = 1e-10;
+    p->cg_max_iterations = 0;                         // 6 n_nodes
+    p->reserved = 0;
+}
+
+static PgCfg to_pg_cfg(const mvs_pose_graph_params &p)
+{
+    PgCfg c{};
+    c.max_iterations = p.lm.max_iterations;
+    c.lambda_initial = p.lm.lambda_initial;
+    c.lambda_factor = p.lm.lambda_factor;
+    c.lambda_upper = p.lm.lambda_upper;
+    c.rel_tol = p.lm.rel_tol;
+    c.abs_tol = p.lm.abs_tol;
+    c.w_anchor[0] = 1.0 / (p.anchor_sigma[0] * p.anchor_sigma[0]);
+    c.w_anchor[1] = 1.0 / (p.anchor_sigma[1] * p.anchor_sigma[1]);
+    c.cg_rel_tol = p.cg_rel_tol;
+    c.cg_max_iterations = p.cg_max_iterations;
+    return c;
+}
+
+static bool all_finite(const double *v, size_t n)
+{
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(v[i]))
+            return false;
+    return true;
+}
+
+// arguments of one graph: MVS_ERR_INVALID_ARG / MVS_ERR_CAPACITY before anything runs
+static mvs_status pose_graph_check(const mvs_pose_graph &g)
+{
+    if (g.n_nodes < 1 || g.n_edges < 0 || !g.node_pose)
+        return MVS_ERR_INVALID_ARG;
+    if (g.n_edges > 0 && (!g.edge_src || !g.edge_dst || !g.edge_pose || !g.edge_cov))
+        return MVS_ERR_INVALID_ARG;
+    if (g.n_nodes > kPgMaxNodes || g.n_edges > kPgMaxEdges)
+        return MVS_ERR_CAPACITY;
+    if (g.anchor_node < 0 || g.anchor_node >= g.n_nodes)
+        return MVS_ERR_INVALID_ARG;
+    for (int k = 0; k < g.n_edges; ++k) {
+        const int s = g.edge_src[k], d = g.edge_dst[k];
+        if (s < 0 || s >= g.n_nodes || d < 0 || d >= g.n_nodes || s == d)
+            return MVS_ERR_INVALID_ARG;
+    }
+    if (!all_finite(g.node_pose, 12 * (size_t)g.n_nodes) || !all_finite(g.edge_pose, 12 * (size_t)g.n_edges) ||
+        !all_finite(g.edge_cov, 36 * (size_t)g.n_edges))
+        return MVS_ERR_INVALID_ARG;
+    return MVS_OK;
+}
+
+// does a path of edges join every node to the anchor?  (With lambda on the diagonal a floating component would not break
+// the linear solve: its gauge freedom only leaves the values where they are.  So the topology is checked, exactly.)
+static bool pose_graph_connected(const mvs_pose_graph &g)
+{
+    std::vector<int> parent((size_t)g.n_nodes);
+    for (int i = 0; i < g.n_nodes; ++i)
+        parent[i] = i;
+    auto find = [&](int a) {
+        while (parent[a] != a)
+            a = parent[a] = parent[parent[a]];
+        return a;
+    };
+    for (int k = 0; k < g.n_edges; ++k)
+        parent[find(g.edge_src[k])] = find(g.edge_dst[k]);
+    const int root = find(g.anchor_node);
+    for (int i = 0; i < g.n_nodes; ++i)
+        if (find(i) != root)
+            return false;
+    return true;
+}
+
+// one graph of 17 .. 4096 nodes: LM on the host, one synchronisation per iteration
+static mvs_status pose_graph_large(mvs_ctx *ctx, const mvs_pose_graph &g, const mvs_pose_graph_params &params,
+                                   mvs_pose_graph_result *res, double *poses_out)
+{
+    const size_t N = (size_t)g.n_nodes, E = (size_t)g.n_edges;
+    // CSR list of the incident edges of every node, in edge order
+    std::vector<int32_t> off(N + 1, 0), inc(2 * E);
+    for (size_t k = 0; k < E; ++k) {
+        ++off[(size_t)g.edge_src[k] + 1];
+        ++off[(size_t)g.edge_dst[k] + 1];
+    }
+    for (size_t i = 0; i < N; ++i)
+        off[i + 1] += off[i];
+    {
+        std::vector<int32_t> fill(off.begin(), off.end() - 1);
+        for (size_t k = 0; k < E; ++k) {
+            inc[(size_t)fill[(size_t)g.edge_src[k]]++] = (int32_t)(2 * k);
+            inc[(size_t)fill[(size_t)g.edge_dst[k]]++] = (int32_t)(2 * k + 1);
+        }
+    }
+    Carve L{64};
+    const size_t o_state = L.take(sizeof(PgState));
+    const size_t o_src = L.take(E * 4), o_dst = L.take(E * 4), o_off = L.take((N + 1) * 4), o_inc = L.take(2 * E * 4);
+    const size_t o_z = L.take(E * 12 * 8), o_cov = L.take(E * 36 * 8), o_p0 = L.take(N * 12 * 8);
+    const size_t o_pa = L.take(N * 12 * 8), o_pb = L.take(N * 12 * 8);
+    const size_t o_W = L.take(E * 21 * 8), o_lin = L.take(E * kPgLin * 8), o_u = L.take(E * 6 * 8), o_ec = L.take(E * 8);
+    const size_t o_D = L.take(N * 21 * 8), o_Mf = L.take(N * 21 * 8);
+    size_t o_vec[6];
+    for (size_t &o : o_vec)
+        o = L.take(N * 6 * 8);
+    const size_t o_pq = L.take(N * 8), o_Ha = L.take(36 * 8);
+    mvs_status st = ws_grow(ctx, ctx->pg, L.total());
+    if (st != MVS_OK)
+        return st;
+    char *base = ctx->pg.ptr();
+    hipStream_t s = ctx->stream;
+    HIP_TRY(ctx, hipMemsetAsync(base + o_state, 0, sizeof(PgState), s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_src, g.edge_src, E * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_dst, g.edge_dst, E * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_off, off.data(), (N + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_inc, inc.data(), 2 * E * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_z, g.edge_pose, E * 12 * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_cov, g.edge_cov, E * 36 * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_p0, g.node_pose, N * 12 * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_pa, g.node_pose, N * 12 * 8, hipMemcpyHostToDevice, s));
+    auto dp = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
+    auto ip = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o); };
+    PgLargeDev d{};
+    d.n_nodes = g.n_nodes, d.n_edges = g.n_edges, d.anchor = g.anchor_node;
+    d.cfg = to_pg_cfg(params);
+    d.edge_src = ip(o_src), d.edge_dst = ip(o_dst), d.csr_off = ip(o_off), d.csr_inc = ip(o_inc);
+    d.edge_pose = dp(o_z), d.edge_cov = dp(o_cov), d.pose0 = dp(o_p0);
+    d.pose[0] = dp(o_pa), d.pose[1] = dp(o_pb);
+    d.W = dp(o_W), d.lin = dp(o_lin), d.u = dp(o_u), d.ecost = dp(o_ec), d.D = dp(o_D), d.Mf = dp(o_Mf);
+    d.g = dp(o_vec[0]), d.x = dp(o_vec[1]), d.r = dp(o_vec[2]), d.z = dp(o_vec[3]), d.p = dp(o_vec[4]), d.q = dp(o_vec[5]);
+    d.pq = dp(o_pq), d.Ha = dp(o_Ha);
+    d.state = reinterpret_cast<PgState *>(base + o_state);
+    const int cg_max = params.cg_max_iterations > 0 ? params.cg_max_iterations : 6 * g.n_nodes;
+    launch_pg_prep(d, s);
+    HIP_TRY(ctx, hipGetLastError());
+    PgState h{};
+    // a covariance that is not positive definite ends the call here, before anything is linearised on its whitening factor
+    HIP_TRY(ctx, hipMemcpyAsync(&h, d.state, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    if (h.bad_cov) {
+        *res = mvs_pose_graph_result{};
+        return MVS_OK;
+    }
+
+    // the LM rule of refine_kernel, on the host: the device computes, the host decides
+    const PgCfg &cfg = d.cfg;
+    int cb = 0, it = 0, rejected = 0, cg_total = 0;
+    double cur = 0.0, cost0 = 0.0, lam = cfg.lambda_initial;
+    bool ok0 = true, have0 = false;
+    while (ok0 && it < cfg.max_iterations) {
+        launch_pg_iteration(d, cb, lam, cg_max, !have0, s);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(&h, d.state, sizeof(h), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, sync_stream(ctx));
+        if (!have0) {
+            have0 = true;
+            cost0 = cur = h.cost0;
+            ok0 = std::isfinite(cur);
+            if (!ok0)
+                break;
+        }
+        cg_total += h.cg_iters;
+        // the linear solve counts as done when the CG converged, or ran out of iterations with a smaller residual
+        const bool solved = h.done == 1 || (h.done == 0 && h.rr < h.gnorm2);
+        const double cand = h.cand;
+        const bool accepted = solved && cand <= cur;
+        ++it;
+        if (accepted) {
+            cb ^= 1;
+            const double dec = 0.5 * (cur - cand);
+            const bool done = dec <= cfg.abs_tol || dec <= cfg.rel_tol * (0.5 * cur);
+            cur = cand;
+            lam = lam / cfg.lambda_factor;
+            if (done)
+                break;
+        } else {
+            ++rejected;
+            const double inc_e = 0.5 * (cand - cur);
+            if (solved && (inc_e <= cfg.abs_tol || inc_e <= cfg.rel_tol * (0.5 * cur)))
+                break;
+            lam = lam * cfg.lambda_factor;
+            if (lam > cfg.lambda_upper)
+                break;
+        }
+    }
+    if (!have0) {   // max_iterations = 0: the cost at the initial values alone (an iteration with no CG steps leaves x = 0)
+        launch_pg_iteration(d, cb, lam, 0, true, s);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(&h, d.state, sizeof(h), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, sync_stream(ctx));
+        cost0 = cur = h.cost0;
+        ok0 = std::isfinite(cur);
+    }
+    res->ok = ok0 ? 1 : 0;
+    res->iterations = it;
+    res->cg_iterations = cg_total;
+    res->rejected_steps = rejected;
+    res->error_initial = ok0 ? 0.5 * cost0 : 0.0;
+    res->error = ok0 ? 0.5 * cur : 0.0;
+    if (ok0) {
+        HIP_TRY(ctx, hipMemcpyAsync(poses_out, d.pose[cb], N * 12 * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, sync_stream(ctx));
+    }
+    return MVS_OK;
+}
+
+mvs_status mvs_pose_graph_optimize_batch(mvs_ctx *ctx, const mvs_pose_graph *graphs, int n_graphs,
+                                         const mvs_pose_graph_params *params, mvs_pose_graph_result *results,
+                                         double *poses_out)
+{
+    if (!ctx || !graphs || n_graphs < 1 || !params || !results || !poses_out)
+        return MVS_ERR_INVALID_ARG;
+    if (params->lm.max_iterations < 0 || !(params->lm.lambda_initial >= 0.0) || !(params->lm.lambda_factor > 1.0) ||
+        !(params->lm.lambda_upper > 0.0) || !(params->anchor_sigma[0] > 0.0) || !(params->anchor_sigma[1] > 0.0) ||
+        !(params->cg_rel_tol >= 0.0) || params->cg_max_iterations < 0)
+        return MVS_ERR_INVALID_ARG;
+    int Nmax = 0;
+    for (int i = 0; i < n_graphs; ++i) {
+        const mvs_status st = pose_graph_check(graphs[i]);
+        if (st != MVS_OK)
+            return st;
+        Nmax = std::max(Nmax, graphs[i].n_nodes);
+    }
+    std::memset(results, 0, (size_t)n_graphs * sizeof(mvs_pose_graph_result));
+    std::vector<char> joined((size_t)n_graphs);
+    for (int i = 0; i < n_graphs; ++i)
+        joined[(size_t)i] = pose_graph_connected(graphs[i]) ? 1 : 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the batch's graphs of up to 16 nodes: one upload, one launch, one download
+    std::vector<PgProblem> desc;
+    std::vector<int> which;
+    size_t sumN = 0, sumE = 0;
+    for (int i = 0; i < n_graphs; ++i) {
+        const mvs_pose_graph &g = graphs[i];
+        if (!joined[(size_t)i] || g.n_nodes > kPgDenseMaxNodes)
+            continue;
+        PgProblem p{};
+        p.n_nodes = g.n_nodes, p.n_edges = g.n_edges, p.anchor = g.anchor_node;
+        p.node_off = (int64_t)sumN, p.edge_off = (int64_t)sumE;
+        sumN += (size_t)g.n_nodes;
+        sumE += (size_t)g.n_edges;
+        desc.push_back(p);
+        which.push_back(i);
+    }
+    if (!desc.empty()) {
+        const size_t G = desc.size();
+        Carve L{64};   // outputs first and contiguous (results, poses): the download is their prefix
+        const size_t o_out = L.take(G * sizeof(mvs_pose_graph_result)), o_po = L.take(sumN * 12 * 8);
+        const size_t down = L.total();
+        const size_t o_W = L.take(sumE * 21 * 8), o_lin = L.take(sumE * kPgLin * 8);
+        const size_t o_up = L.total();   // the uploaded block: descriptors, node poses, edge poses, covariances, src, dst
+        Carve U{64};
+        const size_t u_desc = U.take(G * sizeof(PgProblem)), u_np = U.take(sumN * 12 * 8), u_z = U.take(sumE * 12 * 8);
+        const size_t u_cov = U.take(sumE * 36 * 8), u_src = U.take(sumE * 4), u_dst = U.take(sumE * 4);
+        const mvs_status st = ws_grow(ctx, ctx->pg, o_up + U.total());
+        if (st != MVS_OK)
+            return st;
+        std::vector<char> up(U.total());
+        std::memcpy(up.data() + u_desc, desc.data(), G * sizeof(PgProblem));
+        for (size_t k = 0; k < G; ++k) {
+            const mvs_pose_graph &g = graphs[which[k]];
+            const size_t n = (size_t)g.n_nodes, e = (size_t)g.n_edges, no = (size_t)desc[k].node_off, eo = (size_t)desc[k].edge_off;
+            std::memcpy(up.data() + u_np + no * 96, g.node_pose, n * 96);
+            if (e) {
+                std::memcpy(up.data() + u_z + eo * 96, g.edge_pose, e * 96);
+                std::memcpy(up.data() + u_cov + eo * 288, g.edge_cov, e * 288);
+                std::memcpy(up.data() + u_src + eo * 4, g.edge_src, e * 4);
+                std::memcpy(up.data() + u_dst + eo * 4, g.edge_dst, e * 4);
+            }
+        }
+        char *base = ctx->pg.ptr();
+        hipStream_t s = ctx->stream;
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_up, up.data(), up.size(), hipMemcpyHostToDevice, s));
+        PgDenseDev d{};
+        d.n_problems = (int)G;
+        d.cfg = to_pg_cfg(*params);
+        d.prob = reinterpret_cast<const PgProblem *>(base + o_up + u_desc);
+        d.node_pose = reinterpret_cast<const double *>(base + o_up + u_np);
+        d.edge_pose = reinterpret_cast<const double *>(base + o_up + u_z);
+        d.edge_cov = reinterpret_cast<const double *>(base + o_up + u_cov);
+        d.edge_src = reinterpret_cast<const int32_t *>(base + o_up + u_src);
+        d.edge_dst = reinterpret_cast<const int32_t *>(base + o_up + u_dst);
+        d.W = reinterpret_cast<double *>(base + o_W);
+        d.lin = reinterpret_cast<double *>(base + o_lin);
+        d.poses_out = reinterpret_cast<double *>(base + o_po);
+        d.out = reinterpret_cast<mvs_pose_graph_result *>(base + o_out);
+        launch_pg_dense(d, s);
+        HIP_TRY(ctx, hipGetLastError());
+        std::vector<char> host(down);
+        HIP_TRY(ctx, hipMemcpyAsync(host.data(), base, down, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, sync_stream(ctx));
+        for (size_t k = 0; k < G; ++k) {
+            const int i = which[k];
+            std::memcpy(&results[i], host.data() + o_out + k * sizeof(mvs_pose_graph_result), sizeof(mvs_pose_graph_result));
+            if (results[i].ok)
+                std::memcpy(poses_out + (size_t)i * Nmax * 12, host.data() + o_po + (size_t)desc[k].node_off * 96,
+                            (size_t)graphs[i].n_nodes * 96);
+        }
+    }
+    // larger graphs, one after another
+    for (int i = 0; i < n_graphs; ++i) {
+        if (!joined[(size_t)i] || graphs[i].n_nodes <= kPgDenseMaxNodes)
+            continue;
+        const mvs_status st = pose_graph_large(ctx, graphs[i], *params, &results[i], poses_out + (size_t)i * Nmax * 12);
+        if (st != MVS_OK)
+            return st;
+    }
+    bool all_ok = true;
+    for (int i = 0; i < n_graphs; ++i)
+        all_ok = all_ok && results[i].ok;
+    return all_ok ? MVS_OK : MVS_NO_MODEL;
+}
+
+mvs_status mvs_pose_graph_optimize(mvs_ctx *ctx, const mvs_pose_graph *graph, const mvs_pose_graph_params *params,
+                                   mvs_pose_graph_result *result, double *poses_out)
+{
+    return mvs_pose_graph_optimize_batch(ctx, graph, 1, params, result, poses_out);
+}
 }  // extern "C"

@@ -267,6 +267,67 @@ struct WinDev {
 };
 void launch_refine_window(const WinDev &d, hipStream_t stream);
 
+// ---- pose graphs: the back end (posegraph.hip) ---------------------------------------------
+constexpr int kPgDenseMaxNodes = 16;     // up to here one workgroup solves the dense 6N x 6N system in LDS
+constexpr int kPgMaxNodes = 4096, kPgMaxEdges = 65536;
+constexpr int kPgLin = 78;               // doubles of one linearised edge: whitened residual 6, A_src 36, A_dst 36 (row-major)
+struct PgCfg {
+    int max_iterations;
+    double lambda_initial, lambda_factor, lambda_upper, rel_tol, abs_tol;
+    double w_anchor[2];                  // 1 / sigma^2 of the anchor prior: rotation, translation
+    double cg_rel_tol;
+    int cg_max_iterations;
+};
+struct PgProblem {       // one graph of a dense-path batch
+    int32_t n_nodes, n_edges, anchor, reserved;
+    int64_t node_off;    // first node of the graph in node_pose / poses_out
+    int64_t edge_off;    // first edge of the graph in every per-edge array
+};
+static_assert(sizeof(PgProblem) == 32, "PgProblem layout");
+struct PgDenseDev {
+    int n_problems;
+    PgCfg cfg;
+    const PgProblem *prob;
+    const double *node_pose;     // [sum N][12] initial values; the anchor's is its prior mean
+    const int32_t *edge_src, *edge_dst;
+    const double *edge_pose;     // [sum E][12] Z
+    const double *edge_cov;      // [sum E][36]
+    double *W;                   // [sum E][21] whitening factor L^-1 of every edge (packed lower)
+    double *lin;                 // [sum E][kPgLin]
+    double *poses_out;           // [sum N][12]
+    mvs_pose_graph_result *out;  // [G]
+};
+void launch_pg_dense(const PgDenseDev &d, hipStream_t stream);
+
+struct PgState {         // what the host reads once per LM iteration of the large path
+    double cost0, cand;  // sum of squared whitened residuals at the initial / candidate values
+    double rz, gnorm2, rr;
+    int32_t done;        // CG status word: 0 running, 1 converged, 2 broke down (p.Hp <= 0 or a block not positive definite)
+    int32_t cg_iters;
+    int32_t bad_cov;     // some edge covariance is not positive definite
+    int32_t reserved;
+};
+struct PgLargeDev {
+    int n_nodes, n_edges, anchor;
+    PgCfg cfg;
+    const int32_t *edge_src, *edge_dst;
+    const double *edge_pose, *edge_cov;
+    const int32_t *csr_off;      // [N + 1]
+    const int32_t *csr_inc;      // [2 E] incident edges of every node in edge order: 2 * edge + (0: node is src, 1: dst)
+    const double *pose0;         // [N][12] initial values
+    double *pose[2];             // [N][12] current / candidate (which is which: the host's)
+    double *W, *lin, *u, *ecost; // [E][21], [E][kPgLin], [E][6], [E]
+    double *D, *Mf;              // [N][21] diagonal blocks of H; Cholesky factors of the damped blocks
+    double *g, *x, *r, *z, *p, *q;   // [N][6]
+    double *pq;                  // [N]
+    double *Ha;                  // [36] the anchor prior's block of H
+    PgState *state;
+};
+void launch_pg_prep(const PgLargeDev &d, hipStream_t stream);
+// one LM iteration at pose[cur] with damping lam: linearise, gather, PCG (every iteration enqueued, the status word ends
+// them), candidate = pose[cur ^ 1], its cost -> state->cand.  `first`: the cost at pose[cur] -> state->cost0 before it.
+void launch_pg_iteration(const PgLargeDev &d, int cur, double lam, int cg_max, bool first, hipStream_t stream);
+
 // ---- sliding windows of a resident sequence (mvs_seq_refine_windows) -------------------------
 // seq_link_kernel chains the inlier matches of consecutive pairs into tracks (every keypoint gets at most one successor and
 // one predecessor); seq_window_assemble_kernel turns the tracks of window w = frames [w * stride, w * stride + F) into the

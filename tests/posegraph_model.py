@@ -1,0 +1,386 @@
+"""numpy model of the pose-graph contract (include/mvslam_hip.h mvs_pose_graph_optimize):
+
+    cost = 1/2 [ |e_anchor|^2_Sa + sum_k |e_k|^2_Sk ],   e_k = ( Log(Rz^T Rs^T Rd),  Rz^T (Rs^T (td - ts) - tz) ),
+
+right perturbation R <- R Exp(dw), t <- t + R dv, the Levenberg-Marquardt rule of refine_kernel (lambda ADDED to the
+diagonal; accept when the candidate's cost is not above the current one; lambda /= factor on acceptance, *= factor on
+rejection; stop on a decrease -- or, for a rejected candidate that solved, an increase -- of the error within abs_tol or
+rel_tol * error, on lambda > lambda_upper, or after max_iterations linear solves).
+
+The model builds the dense normal equations and solves them with numpy.linalg.cholesky; `solver="pcg"` replaces that exact
+solve with the block-Jacobi preconditioned conjugate gradient the device's large path runs (stop at |r| <= cg_rel_tol |g|
+or after cg_max_iterations), so a disagreement between the device and the model can be attributed to the path.
+
+It also holds the fixtures the host and the GPU tests share."""
+import numpy as np
+
+LM_DEFAULT = dict(max_iterations=100, lambda_initial=1e-5, lambda_factor=10.0, lambda_upper=1e5, rel_tol=1e-12,
+                  abs_tol=1e-12)
+ANCHOR_SIGMA = (1e-4, 1e-4)
+CG_REL_TOL = 1e-10
+
+
+def hat(w):
+    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+
+
+def so3_exp(w):
+    w = np.asarray(w, dtype=np.float64)
+    th2 = float(w @ w)
+    th = np.sqrt(th2)
+    if th < 1e-4:
+        A, B = 1.0 - th2 / 6.0, 0.5 - th2 / 24.0
+    else:
+        A, B = np.sin(th) / th, (1.0 - np.cos(th)) / th2
+    K = hat(w)
+    return np.eye(3) + A * K + B * (K @ K)
+
+
+def so3_log(R):
+    v = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s = np.sqrt(float(v @ v))
+    c = 0.5 * (np.trace(R) - 1.0)
+    th = np.arctan2(s, c)
+    k = 1.0 + s * s / 6.0 if (s < 1e-4 and c > 0.0) else th / s
+    return k * v
+
+
+def so3_jrinv(w):
+    th2 = float(w @ w)
+    th = np.sqrt(th2)
+    if th < 1e-4:
+        g = 1.0 / 12.0 + th2 / 720.0
+    else:
+        g = 1.0 / th2 - (1.0 + np.cos(th)) / (2.0 * th * np.sin(th))
+    K = hat(w)
+    return np.eye(3) + 0.5 * K + g * (K @ K)
+
+
+def split(p):
+    p = np.asarray(p, dtype=np.float64).reshape(12)
+    return p[:9].reshape(3, 3), p[9:]
+
+
+def join(R, t):
+    return np.concatenate([np.asarray(R).reshape(9), np.asarray(t).reshape(3)])
+
+
+def retract(p, dx):
+    R, t = split(p)
+    return join(R @ so3_exp(dx[:3]), t + R @ dx[3:])
+
+
+def compose(a, b):
+    Ra, ta = split(a)
+    Rb, tb = split(b)
+    return join(Ra @ Rb, ta + Ra @ tb)
+
+
+def between(a, b):
+    """a^-1 b: what an edge (a -> b) measures"""
+    Ra, ta = split(a)
+    Rb, tb = split(b)
+    return join(Ra.T @ Rb, Ra.T @ (tb - ta))
+
+
+def edge_error(Z, Ps, Pd, jac=False):
+    """unwhitened error of one edge and, when asked, d e / d src and d e / d dst (6 x 6 each)"""
+    Rz, tz = split(Z)
+    Rs, ts = split(Ps)
+    Rd, td = split(Pd)
+    Rsd = Rs.T @ Rd
+    E = Rz.T @ Rsd
+    ew = so3_log(E)
+    q = Rs.T @ (td - ts)
+    e = np.concatenate([ew, Rz.T @ (q - tz)])
+    if not jac:
+        return e
+    Jri = so3_jrinv(ew)
+    Js, Jd = np.zeros((6, 6)), np.zeros((6, 6))
+    Js[:3, :3] = -Jri @ Rsd.T
+    Js[3:, :3] = Rz.T @ hat(q)
+    Js[3:, 3:] = -Rz.T
+    Jd[:3, :3] = Jri
+    Jd[3:, 3:] = E
+    return e, Js, Jd
+
+
+def prior_error(P0, P, jac=False):
+    R0, t0 = split(P0)
+    R, t = split(P)
+    Re = R0.T @ R
+    ew = so3_log(Re)
+    e = np.concatenate([ew, R0.T @ (t - t0)])
+    if not jac:
+        return e
+    J = np.zeros((6, 6))
+    J[:3, :3] = so3_jrinv(ew)
+    J[3:, 3:] = Re
+    return e, J
+
+
+def whitening(cov):
+    """W = L^-1 of cov = L L^T per edge; raises numpy.linalg.LinAlgError if a covariance is not positive definite"""
+    cov = np.asarray(cov, dtype=np.float64).reshape(-1, 6, 6)
+    return np.array([np.linalg.inv(np.linalg.cholesky(c)) for c in cov]).reshape(-1, 6, 6)
+
+
+def connected(g):
+    n = g["node_pose"].shape[0]
+    seen = {int(g.get("anchor", 0))}
+    grew = True
+    while grew:
+        grew = False
+        for s, d in zip(g["edge_src"], g["edge_dst"]):
+            if (int(s) in seen) != (int(d) in seen):
+                seen |= {int(s), int(d)}
+                grew = True
+    return len(seen) == n
+
+
+def _residuals(g, W, wa, poses, jac):
+    N, E, a = poses.shape[0], len(g["edge_src"]), int(g.get("anchor", 0))
+    r = np.zeros(6 * (E + 1))
+    J = np.zeros((6 * (E + 1), 6 * N)) if jac else None
+    for k in range(E):
+        s, d = int(g["edge_src"][k]), int(g["edge_dst"][k])
+        if jac:
+            e, Js, Jd = edge_error(g["edge_pose"][k], poses[s], poses[d], True)
+            J[6 * k:6 * k + 6, 6 * s:6 * s + 6] = W[k] @ Js
+            J[6 * k:6 * k + 6, 6 * d:6 * d + 6] = W[k] @ Jd
+        else:
+            e = edge_error(g["edge_pose"][k], poses[s], poses[d])
+        r[6 * k:6 * k + 6] = W[k] @ e
+    if jac:
+        e, Ja = prior_error(g["node_pose"][a], poses[a], True)
+        J[6 * E:, 6 * a:6 * a + 6] = wa[:, None] * Ja
+    else:
+        e = prior_error(g["node_pose"][a], poses[a])
+    r[6 * E:] = wa * e
+    return (r, J) if jac else r
+
+
+def pcg(H, b, rel_tol, max_iterations):
+    """block-Jacobi (6 x 6 diagonal blocks) preconditioned CG of H x = b from x = 0.
+    Returns (x, iterations, status): 1 converged, 0 out of iterations, 2 broke down."""
+    n = H.shape[0]
+    try:
+        Mi = np.array([np.linalg.inv(H[i:i + 6, i:i + 6]) for i in range(0, n, 6)])
+        for i in range(0, n, 6):
+            np.linalg.cholesky(H[i:i + 6, i:i + 6])
+    except np.linalg.LinAlgError:
+        return np.zeros(n), 0, 2
+    prec = lambda v: np.einsum("nij,nj->ni", Mi, v.reshape(-1, 6)).reshape(-1)
+    x, r = np.zeros(n), b.copy()
+    z = prec(r)
+    p = z.copy()
+    rz, gn = float(r @ z), np.sqrt(float(b @ b))
+    if gn == 0.0:
+        return x, 0, 1
+    for it in range(1, max_iterations + 1):
+        q = H @ p
+        pq = float(p @ q)
+        if not (pq > 0.0 and np.isfinite(pq)):
+            return x, it - 1, 2
+        alpha = rz / pq
+        x = x + alpha * p
+        r = r - alpha * q
+        z = prec(r)
+        rzn, rn = float(r @ z), np.sqrt(float(r @ r))
+        if rn <= rel_tol * gn:
+            return x, it, 1
+        if not rzn > 0.0:
+            return x, it, 2
+        p = z + (rzn / rz) * p
+        rz = rzn
+    return x, max_iterations, 0 if np.sqrt(float(r @ r)) < gn else 2
+
+
+def optimize(g, lm=None, anchor_sigma=ANCHOR_SIGMA, solver="exact", cg_rel_tol=CG_REL_TOL, cg_max_iterations=0):
+    """the contract, in numpy.  Returns dict(ok, iterations, cg_iterations, rejected_steps, error_initial, error, poses)."""
+    lm = dict(LM_DEFAULT, **(lm or {}))
+    poses = np.array(g["node_pose"], dtype=np.float64).reshape(-1, 12)
+    N = poses.shape[0]
+    fail = dict(ok=0, iterations=0, cg_iterations=0, rejected_steps=0, error_initial=0.0, error=0.0, poses=None)
+    if not connected(g):
+        return fail
+    try:
+        W = whitening(g["edge_cov"])
+    except np.linalg.LinAlgError:
+        return fail
+    wa = np.repeat(1.0 / np.asarray(anchor_sigma, dtype=np.float64), 3)
+    cg_max = cg_max_iterations or 6 * N
+    cost = lambda P: float(np.sum(_residuals(g, W, wa, P, False) ** 2))
+    cur = cost0 = cost(poses)
+    lam, it, rejected, cg_total = lm["lambda_initial"], 0, 0, 0
+    if not np.isfinite(cur):
+        return fail
+    while it < lm["max_iterations"]:
+        r, J = _residuals(g, W, wa, poses, True)
+        H = J.T @ J + lam * np.eye(6 * N)
+        b = -(J.T @ r)
+        solved, cand = True, 0.0
+        if solver == "exact":
+            try:
+                L = np.linalg.cholesky(H)
+                dx = np.linalg.solve(L.T, np.linalg.solve(L, b))
+            except np.linalg.LinAlgError:
+                solved = False
+        else:
+            dx, n_cg, status = pcg(H, b, cg_rel_tol, cg_max)
+            cg_total += n_cg
+            solved = status != 2
+        accepted = False
+        if solved:
+            new = np.array([retract(poses[i], dx[6 * i:6 * i + 6]) for i in range(N)])
+            cand = cost(new)
+            accepted = cand <= cur
+        it += 1
+        if accepted:
+            poses = new
+            dec = 0.5 * (cur - cand)
+            done = dec <= lm["abs_tol"] or dec <= lm["rel_tol"] * (0.5 * cur)
+            cur = cand
+            lam = lam / lm["lambda_factor"]
+            if done:
+                break
+        else:
+            rejected += 1
+            inc = 0.5 * (cand - cur)
+            if solved and (inc <= lm["abs_tol"] or inc <= lm["rel_tol"] * (0.5 * cur)):
+                break
+            lam = lam * lm["lambda_factor"]
+            if lam > lm["lambda_upper"]:
+                break
+    return dict(ok=1, iterations=it, cg_iterations=cg_total, rejected_steps=rejected, error_initial=0.5 * cost0,
+                error=0.5 * cur, poses=poses)
+
+
+def pose_distance(A, B):
+    """largest rotation angle of R1^T R2 and largest |t1 - t2| over the nodes of two pose tables"""
+    A, B = np.asarray(A).reshape(-1, 12), np.asarray(B).reshape(-1, 12)
+    rot = trans = 0.0
+    for a, b in zip(A, B):
+        Ra, ta = split(a)
+        Rb, tb = split(b)
+        rot = max(rot, float(np.linalg.norm(so3_log(Ra.T @ Rb))))
+        trans = max(trans, float(np.linalg.norm(ta - tb)))
+    return rot, trans
+
+
+# ---- fixtures ---------------------------------------------------------------------------------------------------------
+def se3(w, v):
+    """(Exp(w), v): rotation from the axis-angle vector, translation as given"""
+    return join(so3_exp(w), np.asarray(v, dtype=np.float64))
+
+
+def iso_cov(sigma2, n):
+    return np.tile((np.eye(6) * sigma2).reshape(36), (n, 1))
+
+
+def full_cov(rng, n, scale=1e-2):
+    """A A^T + 1e-4 I with a seeded random A"""
+    out = np.zeros((n, 36))
+    for k in range(n):
+        A = rng.normal(size=(6, 6)) * scale
+        out[k] = (A @ A.T + 1e-4 * np.eye(6)).reshape(36)
+    return out
+
+
+def graph(node_pose, edges, edge_pose, edge_cov, anchor=0):
+    e = np.asarray(edges, dtype=np.int32).reshape(-1, 2)
+    return dict(node_pose=np.ascontiguousarray(node_pose, dtype=np.float64).reshape(-1, 12),
+                edge_src=np.ascontiguousarray(e[:, 0]), edge_dst=np.ascontiguousarray(e[:, 1]),
+                edge_pose=np.ascontiguousarray(edge_pose, dtype=np.float64).reshape(-1, 12),
+                edge_cov=np.ascontiguousarray(edge_cov, dtype=np.float64).reshape(-1, 36), anchor=anchor)
+
+
+def trivial():
+    """test-graph.cpp `trivial`: the origin, one node guessed 1.2 x too far along x, one edge measuring the truth with
+    the isotropic covariance 0.01 I.  Returns (graph, true poses)."""
+    truth = np.array([se3([0, 0, 0], [0, 0, 0]), se3([0, 0, 0], [1, 0, 0])])
+    guess = np.array([truth[0], se3([0, 0, 0], [1.2, 0, 0])])
+    return graph(guess, [(0, 1)], [between(truth[0], truth[1])], iso_cov(0.01, 1)), truth
+
+
+def triangle(seed, sigma=0.01):
+    """test-graph.cpp `planar_triangle` with GTSAM's meaning of an edge: three steps of (120 degrees about z, 1 along x)
+    composed on the RIGHT (X_{i+1} = X_i M), measured with sigma noise, values by dead reckoning, and the loop closed by
+    an identity edge from the last node to the origin.  4 nodes, 4 edges.  Returns (graph, true poses)."""
+    rng = np.random.default_rng(1000 + seed)
+    M = se3([0, 0, 2.0 * np.pi / 3.0], [1, 0, 0])
+    truth, guess, edges, Z = [se3([0, 0, 0], [0, 0, 0])], [se3([0, 0, 0], [0, 0, 0])], [], []
+    for i in range(3):
+        meas = compose(M, se3(rng.normal(size=3) * sigma, rng.normal(size=3) * sigma))
+        truth.append(compose(truth[-1], M))
+        guess.append(compose(guess[-1], meas))
+        edges.append((i, i + 1))
+        Z.append(meas)
+    edges.append((3, 0))
+    Z.append(se3([0, 0, 0], [0, 0, 0]))
+    return graph(guess, edges, Z, iso_cov(sigma * sigma, 4)), np.array(truth)
+
+
+def ring(n, chords=(2,), seed=0, noise=0.01, guess_noise=0.05, full=True, extra_edges=()):
+    """n poses on a circle of radius 3 (heading along the tangent, a little roll and climb so that nothing is planar), edges
+    (i, i + 1) around the ring and (i, i + c) for every chord length c, measurements with `noise`, initial values off by
+    `guess_noise`, full covariances A A^T + 1e-4 I when `full`."""
+    rng = np.random.default_rng(2000 + 31 * n + seed)
+    truth = []
+    for i in range(n):
+        a = 2.0 * np.pi * i / n
+        R = so3_exp([0, 0, a + np.pi / 2]) @ so3_exp([0.2 * np.sin(3 * a), 0.1 * np.cos(2 * a), 0.0])
+        truth.append(join(R, [3.0 * np.cos(a), 3.0 * np.sin(a), 0.3 * np.sin(2 * a)]))
+    truth = np.array(truth)
+    edges = [(i, (i + 1) % n) for i in range(n)]
+    for c in chords:
+        edges += [(i, (i + c) % n) for i in range(n) if (i + c) % n != i]
+    edges += list(extra_edges)
+    Z = [compose(between(truth[s], truth[d]), se3(rng.normal(size=3) * noise, rng.normal(size=3) * noise)) for s, d in edges]
+    guess = np.array([truth[0]] + [retract(truth[i], rng.normal(size=6) * guess_noise) for i in range(1, n)])
+    cov = full_cov(rng, len(edges)) if full else iso_cov(noise * noise, len(edges))
+    return graph(guess, edges, Z, cov)
+
+
+def full_cov_graph():
+    """6 nodes, 9 edges (ring + three chords), every covariance full"""
+    g = ring(6, chords=(), seed=5, extra_edges=[(0, 2), (1, 4), (3, 5)])
+    assert len(g["edge_src"]) == 9
+    return g
+
+
+def star(spokes=70):
+    """one hub (node 0, the anchor) with `spokes` spokes: the hub's degree exceeds a wavefront"""
+    rng = np.random.default_rng(77)
+    truth = [se3([0, 0, 0], [0, 0, 0])]
+    for i in range(spokes):
+        a = 2.0 * np.pi * i / spokes
+        truth.append(se3([0.1 * np.sin(a), 0.2 * np.cos(a), a], [2.0 * np.cos(a), 2.0 * np.sin(a), 0.1 * i / spokes]))
+    truth = np.array(truth)
+    edges = [(0, i + 1) if i % 2 == 0 else (i + 1, 0) for i in range(spokes)]
+    Z = [compose(between(truth[s], truth[d]), se3(rng.normal(size=3) * 0.01, rng.normal(size=3) * 0.01)) for s, d in edges]
+    guess = np.array([truth[0]] + [retract(truth[i], rng.normal(size=6) * 0.05) for i in range(1, spokes + 1)])
+    return graph(guess, edges, Z, full_cov(rng, spokes))
+
+
+FAR_OFF = {8: (2, 1.5), 20: (3, 1.2)}   # nodes -> (seed, size of the error of the initial values)
+
+
+def far_off(n):
+    """ring of n nodes with chords whose initial values are more than a radian off: the first Gauss-Newton-sized steps
+    overshoot and Levenberg-Marquardt rejects them (16 of 31 steps at n = 8, 13 of 26 at n = 20, in this model).  The seeds
+    are ones at which no decision of the run is close: the last accepted step lowers an error of 25 by 9e-13, far above
+    the rounding of the cost and far below rel_tol * error."""
+    seed, off = FAR_OFF[n]
+    return ring(n, chords=(2,), seed=seed, guess_noise=off, full=False)
+
+
+def disconnected():
+    """4 nodes; node 3 hangs on nothing"""
+    g, _ = triangle(0)
+    keep = [0, 1]
+    return graph(g["node_pose"], [(0, 1), (1, 2)], g["edge_pose"][keep], g["edge_cov"][keep])
+
+
+PCG_FIXTURES = {"ring17": lambda: ring(17), "star70": star, "ring200": lambda: ring(200, chords=(5,)),
+                "far_off20": lambda: far_off(20), "ring40": lambda: ring(40)}
