@@ -901,7 +901,8 @@ typedef struct mvs_pose_graph_result {
 void mvs_pose_graph_params_default(mvs_pose_graph_params *p);
 /* poses_out: n_nodes x 12.  MVS_ERR_INVALID_ARG (null pointers, indices out of range, src == dst, non-finite input) and
  * MVS_ERR_CAPACITY (more than 4096 nodes or 65536 edges) are returned before anything runs.  MVS_NO_MODEL with ok = 0 and
- * poses_out untouched: a covariance that is not positive definite, or a node no path of edges joins to the anchor. */
+ * poses_out untouched: a covariance that is not positive definite, a node no path of edges joins to the anchor, or finite
+ * input whose cost at the initial values is not finite; every other field of the result is then zero. */
 mvs_status mvs_pose_graph_optimize(mvs_ctx *ctx, const mvs_pose_graph *graph, const mvs_pose_graph_params *params,
                                    mvs_pose_graph_result *result, double *poses_out);
 /* n_graphs graphs; graph i's poses at poses_out + i * 12 * (largest n_nodes of the batch), rows beyond its own node count

@@ -578,8 +578,8 @@ __global__ __launch_bounds__(kPgThreads) void pg_dense_kernel(PgDenseDev d)
         out->iterations = it;
         out->cg_iterations = 0;
         out->rejected_steps = rejected;
-        out->error_initial = 0.5 * cost0;
-        out->error = 0.5 * cur;
+        out->error_initial = ok0 ? 0.5 * cost0 : 0.0;   // a cost that is not finite: the zero record of every other failure
+        out->error = ok0 ? 0.5 * cur : 0.0;
     }
 }
 
