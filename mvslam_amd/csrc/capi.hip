@@ -602,6 +602,17 @@ int mvs_debug_set_prescreen_force(int m)
     return MVS_OK;
 }
 
+// wavefronts of pair_prepare / ransac_prescreen that left the relaxed normalisation for the guarded one (its range test
+// fired) since the last reset; the caller has synchronised the launches it asks about.  reset != 0: zero afterwards
+int mvs_debug_prescreen_fallback_waves(mvs_ctx *ctx, int reset, unsigned int *out)
+{
+    if (!ctx || !out)
+        return MVS_ERR_INVALID_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, prescreen_fallback_waves(out, reset != 0));
+    return MVS_OK;
+}
+
 // records of the RANSAC stage as the last run left them: rec_out n_hyp x 10 (F, counting threshold), state bytes, counts;
 // info[0..3] = {mode of the pair, bound of the pair, work-list entries 0, work-list entries 1}
 int mvs_debug_read_hyp_rec(mvs_batch *b, int pair, int n_hyp, double *rec_out, unsigned char *state_out, int32_t *cnt_out,

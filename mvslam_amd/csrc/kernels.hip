@@ -3205,6 +3205,14 @@ void set_count_dense(int v)
 }
 static int g_force_mode = -1;   // diagnostics: -1 = the probe decides, 0 / 1 = every pair exact / pre-screened
 void set_prescreen_force(int m) { g_force_mode = m; }
+hipError_t prescreen_fallback_waves(unsigned int *out, bool reset)
+{
+    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ps_fallback_waves), sizeof(*out));
+    const unsigned int zero = 0;
+    if (e == hipSuccess && reset)
+        e = hipMemcpyToSymbol(HIP_SYMBOL(g_ps_fallback_waves), &zero, sizeof(zero));
+    return e;
+}
 
 void launch_prescreen_only(const BatchDev &b, const RunParams &rp, int n_active, int mode, hipStream_t stream)
 {

@@ -594,6 +594,7 @@ void set_count_dense(int v);      // 1 = single-precision counting as pilot + de
                                   // ransac_count32 launch, 2 = ransac_count32 as the finish; 1000 + margin, 100000 + pilot size
 void set_match_mfma(int v);       // 1 (default) 256-bit descriptors on the matrix cores by batch size, 0 the VALU kernel
 void set_prescreen_force(int m);   // -1 probe decides (default), 0 every pair exact, 1 every pair pre-screened
+hipError_t prescreen_fallback_waves(unsigned int *out, bool reset);   // wavefronts that took the guarded normalisation
 void set_split_min_pairs(int v);  // launches with fewer pairs stay on the fused hypothesis-per-lane kernel (default 3)
 void launch_fastmath_check(const double *x, const double *y, int n, unsigned long long *out, hipStream_t stream);
 void launch_pairstep_check(const double *rows, int n, unsigned long long *out, hipStream_t stream);

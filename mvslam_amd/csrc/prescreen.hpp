@@ -38,7 +38,9 @@ constexpr double kPsU = 0x1p-53;          // unit roundoff
 constexpr double kPsTauC = 2.0e-12;       // >= 2.001 (8000 u + 8.01 u): <= 1080 Jacobi rotations + forming A^T A
 constexpr double kPsEtaQ = 4.0e-12;       // loss of orthogonality of the accumulated V^T over <= 1080 rotations
 constexpr double kPsSvd3 = 2.0e-11;       // backward error of the exact path's 3x3 Jacobi SVD + recomposition (generous)
-constexpr double kPsTrip = 1.0e-12;       // roundings of the verified singular triplet below (~150 operations on |x| <= 1.01)
+constexpr double kPsTrip = 1.01e-12;      // roundings of the verified singular triplet below (~150 operations on |x| <= 1.01):
+                                          // 1e-12, + 1e-14 >= 2.01 * 22 u * 1.01 for de-normalising with scales that are within
+                                          // 22 u of the exact path's (round 8)
 constexpr double kPsBandFrac = 4.0;       // a hypothesis is certified only if band <= kPsBandFrac * thr.  A certificate can only
                                           // help (a certified hypothesis is counted and then dropped or solved exactly, an
                                           // uncertified one is solved exactly in any case), and the UPPER count bound prunes
@@ -64,8 +66,8 @@ MVS_DEV double recip_guarded(double x) { return div_fast(1.0, x); }
 
 // Square root and reciprocal for BOUND arithmetic (round 4): results within 2^-49 of the true value instead of correctly
 // rounded -- 7 and 5 instructions where the IEEE sequences of hipcc take ~20 and ~13.  They are used only where the
-// derivation multiplies by an explicit slack factor (1 +- 1e-14 or more) or adds an absolute term in the safe direction, and
-// never on the path that has to reproduce the exact solve's bits (the Hartley scales) or that feeds F~ itself.
+// derivation multiplies by an explicit slack factor (1 +- 1e-14 or more) or adds an absolute term in the safe direction.
+// (The values F~ is made of have their own relaxed sequences since round 8: sqrt_relaxed_h / rcp_relaxed below.)
 MVS_DEV double sqrt_bound(double x)   // x finite and >= 2^-700 (callers' arguments are >= 1e-13 by construction)
 {
     const double y = __builtin_amdgcn_rsq(x);
@@ -88,6 +90,33 @@ MVS_DEV double rcp_bound(double x)    // 1 / x for normal x, two Newton steps on
     r = dfma(r, e, r);
     e = dfma(-x, r, 1.0);
     return dfma(r, e, r);
+}
+
+// Square root, reciprocal root and reciprocal for the values F~ is MADE of (round 8).  F~ is an
+// approximation whose distance from the exact path's F_J is what the band certifies, so a root or quotient on its way only
+// has to be within a STATED multiple of u of the true value; the multiples below enter rho, sigma8's subtrahend and kappa.
+// (A3): v_rsq_f64 / v_rcp_f64 return their value within 2^-26 -- what sqrt_fast, div_fast and the two functions above assume.
+//   sqrt_relaxed_h  g within 1.01 u of sqrt(x) for normal x in [2^-767, 2^767]: one coupled step takes the seed's e0 to
+//                   e1 <= 1.5 e0^2 + 2 u < 5.1 u, the residual step g + (x - g^2) h0 with the UNREFINED h0 = y / 2 leaves
+//                   |e1| (|e0| + |e1| / 2) + the last rounding: < u (1 + 2^-23).  Seven instructions (sqrt_fast_nz_h: ten).
+//                   h_out = h0, within 2^-26 of 1 / (2 sqrt(x))
+//   rcp_relaxed     within 3.01 u of 1 / x for normal x, 1 / x normal: ONE Newton step, e0^2 = 2 u, the step's two roundings
+//                   (2^-26 u and u).  Three instructions (rcp_bound: five, div_fast: eight)
+MVS_DEV double sqrt_relaxed_h(double x, double &h_out)
+{
+    const double y = __builtin_amdgcn_rsq(x);
+    double g = x * y;
+    const double h = y * 0.5;
+    const double r = dfma(-h, g, 0.5);
+    g = dfma(g, r, g);
+    const double d = dfma(-g, g, x);
+    h_out = h;
+    return dfma(d, h, g);
+}
+MVS_DEV double rcp_relaxed(double x)
+{
+    const double r = __builtin_amdgcn_rcp(x);
+    return dfma(r, dfma(-x, r, 1.0), r);
 }
 
 // Hartley normalisation of a sample from its gathered points: means and scales only (the normalised coordinates are
@@ -117,10 +146,27 @@ MVS_DEV bool sample_norm(const double (&px)[8], const double (&py)[8], double &s
     return ok;
 }
 
-// The same normalisation for a sample whose sixteen q = dx^2 + dy^2 are all normal numbers >= 2^-767 -- every sample of
-// distinct matches: the roots are sqrt_fast's sequence without its 0 / inf select (sqrt_fast_nz_h, by-product dropped: the
-// same bits for such q), and instead of a range test per root the caller gets the running minimum of q.  The caller decides
-// from qmin and the returned sum of roots (NaN here as soon as a q is inf or NaN) whether sample_norm has to be run instead.
+// The normalisation for a sample whose sixteen q = dx^2 + dy^2 are all normal numbers >= kPsQMin -- every sample of
+// distinct matches.  Round 7 took the roots with sqrt_fast's sequence without its 0 / inf select (the same bits for such q);
+// round 8 takes them within 1.01 u (sqrt_relaxed_h) and the scale quotient within 3.01 u (rcp_relaxed): the means are the
+// exact path's bits, the scale is within kPsScaleU = 22 u of the exact path's (1.01 + 1 of a root against
+// the correctly rounded one, the 7 additions of either sum, the quotients), which makes the pre-screen's design matrix and
+// transforms a relative perturbation of the exact path's -- paid for in rho, sigma8's subtrahend and kappa.  Instead of a range
+// test per root the caller gets the running minimum of q and decides from it and from the returned sum of roots (NaN here as
+// soon as a q is inf or NaN) whether sample_norm has to be run instead; q >= kPsQMin also makes the sum of roots >= 2^-50 > kEps
+// in BOTH paths, so the rejected-sample decision is not taken here at all (a sample near it is sample_norm's, unchanged).
+constexpr double kPsScaleU = 22.0;     // | relaxed scale / exact path's scale - 1 | <= kPsScaleU u: what kPsTrip's 1e-14 and rho's
+                                       // 50.2 u are derived from (tests/test_prescreen_unscaled.py measures it on the model)
+constexpr double kPsRhoC = 1.85e-13;   // || A n~ || <= kPsRhoC sqrt(S): (1548 + 4.1 + 50.2) u = 1603 u = 1.78e-13, derived where it is used
+static_assert(kPsRhoC >= 1603.0 * kPsU, "rho no longer covers the relaxed scales and column norms");
+static_assert(kPsTrip >= 1e-12 +2.01 * kPsScaleU * kPsU * 1.01, "kappa no longer covers the relaxed scales");
+constexpr double kPsQMin = 0x1p-100;
+constexpr double kPsScMax = 0x1p60;    // sum of both means of roots below this: 1 / sc is a normal number (rcp_relaxed); far
+                                       // above any ideal-camera coordinate and inside binary32's range, where mode 1 still counts
+#ifdef MVS_DEBUG_HOOKS
+// diagnostics library only: wavefronts whose range test fired and which took sample_norm (mvs_debug_prescreen_fallback_waves)
+__device__ unsigned int g_ps_fallback_waves;
+#endif
 MVS_DEV double sample_norm_nz(const double (&px)[8], const double (&py)[8], double &scale, double &mx, double &my, double &qmin)
 {
     mx = 0.0;
@@ -139,10 +185,10 @@ MVS_DEV double sample_norm_nz(const double (&px)[8], const double (&py)[8], doub
         const double q = dx * dx + dy * dy;
         qmin = fmin(qmin, q);
         double h;
-        sc += sqrt_fast_nz_h(q, h);
+        sc += sqrt_relaxed_h(q, h);
     }
     sc *= 0.125;
-    scale = kSqrt2 / sc;
+    scale = kSqrt2 * rcp_relaxed(sc);
     return sc;
 }
 
@@ -208,9 +254,16 @@ MVS_DEV void prescreen_rank2(const double (&g)[9], double (&X)[9], double &e_out
     X[3] = dfma(-w1, vx, g[3]); X[4] = dfma(-w1, vy, g[4]); X[5] = dfma(-w1, vz, g[5]);
     X[6] = dfma(-w2, vx, g[6]); X[7] = dfma(-w2, vy, g[7]); X[8] = dfma(-w2, vz, g[8]);
     const double sg2 = dfma(w2, w2, dfma(w1, w1, w0 * w0));
-    const double sig = dsqrt(sg2);
+    // round 8: sig within 1.01 u of || w || (0 below 2^-190: kPsTrip covers it), 1 / sig from the root's own half reciprocal
+    // root and one Newton step against sig (< 3.1 u, no v_rcp_f64): u is unit to 5.2 u, r1 = G v - sig u is 4.2 u sig.
+    // sg2 = +inf gives sig = NaN here (inf * rsq(inf) = inf * 0; the correctly rounded root gave inf): e_out and with it eta are
+    // NaN, and `eta < 1e-3` in the caller's last line is false for a NaN -- kPsNeedExact, as for inf
+    double hs;
+    const double sgc = sqrt_relaxed_h(fmax(sg2, 0x1p-380), hs);
+    const double sig = sg2 < 0x1p-380 ? 0.0 : sgc;
     // u = w / sig, eps2 = || G^T u - sig v ||  (garbage when sig is tiny: then the other branch is taken)
-    const double rs = div_fast(1.0, fmax(sig, 0x1p-190));
+    double rs = hs + hs;
+    rs = dfma(rs, dfma(-sgc, rs, 1.0), rs);
     const double u0 = w0 * rs, u1 = w1 * rs, u2 = w2 * rs;
     const double e0 = dfma(g[6], u2, dfma(g[3], u1, dfma(g[0], u0, -(sig * vx))));
     const double e1 = dfma(g[7], u2, dfma(g[4], u1, dfma(g[1], u0, -(sig * vy))));
@@ -220,7 +273,7 @@ MVS_DEV void prescreen_rank2(const double (&g)[9], double (&X)[9], double &e_out
     e_out = (useA ? eps2 : sig) + kPsTrip;
     sige_out = useA ? sig : 0.0;
     extra_out = useA ? eps2 + kPsTrip : kPsTrip;
-    ok = ok && (sig == sig);
+    ok = ok && (sg2 == sg2);
     // second singular value of X from q1 = s1^2 + s2^2 and q2 = s1^4 + s2^4:  P = s1^2 s2^2 = (q1^2 - q2) / 2,
     // s2^2 = 2 P / (q1 + sqrt(q1^2 - 4 P)); every rounding is pushed towards a smaller result
     const double q1 = dfma(X[8], X[8], dfma(X[7], X[7], dfma(X[6], X[6], dfma(X[5], X[5], dfma(X[4], X[4],
@@ -298,9 +351,21 @@ MVS_DEV int prescreen_hypothesis(const double *P, int (&idx)[8], double *park, c
         double qmin = __builtin_inf();
         const double sc1 = sample_norm_nz(x1, y1, nm.s1, nm.m1x, nm.m1y, qmin);
         const double sc2 = sample_norm_nz(x2, y2, nm.s2, nm.m2x, nm.m2y, qmin);
-        ok = (sc1 > kEps) && (sc2 > kEps);
-        const bool redo = !(qmin >= 0x1p-767) || !(sc1 + sc2 < __builtin_inf());
+        ok = true;   // (qmin >= kPsQMin: both sums of roots are above 2^-50 in this and in the exact path's arithmetic)
+        const bool redo = !(qmin >= kPsQMin) || !(sc1 + sc2 < kPsScMax);
         if (__builtin_expect(__any(redo), 0)) {   // wave-uniform; never taken for samples of distinct matches
+#ifdef MVS_DEBUG_HOOKS
+            if ((threadIdx.x & 63) == 0)          // (every lane of the wavefront is here, lane 0 among them)
+                atomicAdd(&g_ps_fallback_waves, 1u);
+#endif
+            // gathered again behind opaque offsets: the first gather's 32 values do not stay alive for this block's sake
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                uint32_t o = off[k];
+                asm volatile("" : "+v"(o));
+                const double4 p = *reinterpret_cast<const double4 *>(Pb + o);
+                x1[k] = p.x; y1[k] = p.y; x2[k] = p.z; y2[k] = p.w;
+            }
             ok = sample_norm(x1, y1, nm.s1, nm.m1x, nm.m1y, tiny);
             ok = sample_norm(x2, y2, nm.s2, nm.m2x, nm.m2y, tiny) && ok;
         }
@@ -365,17 +430,20 @@ MVS_DEV int prescreen_hypothesis(const double *P, int (&idx)[8], double *park, c
             ss = dfma(col[i], col[i], ss);
         piv_ok = piv_ok && (ss >= 0x1p-190);    // a (nearly) dependent row: no certificate; also keeps every divisor inside
         double hn;                              // the range of the unscaled sequences
-        const double nrm = sqrt_fast_nz_h(ss, hn);   // hn ~ 1 / (2 nrm), a by-product of the square root's own sequence
+        // round 8: nrm within 1.01 u of sqrt(ss) instead of correctly rounded (three instructions less); R_jj IS -+nrm, and
+        // the reflector's scale follows nrm (below), so the 1.01 u shows as a column residual 4.04 u ||x|| in E, (viii)
+        const double nrm = sqrt_relaxed_h(ss, hn);   // hn ~ 1 / (2 nrm) to 2^-26, the UNREFINED by-product
         const double x0 = col[j];
         const double alpha = x0 >= 0.0 ? -nrm : nrm;
-        const double vv = nrm * (nrm + dabs(x0));    // = v.v / 2
-        // 1 / R_jj for the triangular inverse below: 2 hn and one Newton step against nrm itself (relative error < 3 u
-        // whatever the seed's last bits were) -- the pivots used to be divided out again there, eight reciprocal
-        // sequences of eleven instructions each
+        const double vv = nrm * (nrm + dabs(x0));    // = v.v / 2 (1 + theta), |theta| <= 1.01 u + roundings
+        // 1 / R_jj for the triangular inverse below: 2 hn and one Newton step against nrm itself: (2^-26 + 2 u)^2 + the
+        // step's roundings, < 3.1 u ((iii) budgets 3 u + gamma_10 in z = 16 u: 13.1 u) -- the pivots used to be divided out
+        // again there, eight reciprocal sequences of eleven instructions each
         double iv = hn + hn;
         iv = dfma(iv, dfma(-nrm, iv, 1.0), iv);
         rd[j] = x0 >= 0.0 ? -iv : iv;                // = 1 / alpha
-        beta[j] = rcp_bound(vv);                     // within 2^-49 of 1 / vv: (iii)'s eps_beta <= 28 u
+        beta[j] = rcp_relaxed(vv);                   // within 3.01 u of 1 / vv (round 4: two steps, budgeted 16 u): (iii)'s
+                                                     // eps_beta = 12 u + 3.01 u + 1.01 u of nrm <= 28 u stays
         v[j][j] = x0 - alpha;                        // v0: same sign as x0, no cancellation
 #pragma unroll
         for (int i = j + 1; i < 9; ++i)
@@ -436,11 +504,13 @@ MVS_DEV int prescreen_hypothesis(const double *P, int (&idx)[8], double *park, c
     // residual of n~ against the rows of A -- a priori: with A^T + E = Q~ [R^; 0] (||E||_F <= 176 u ||A||_F, Q~ within 510 u of
     // orthogonal: DESIGN.md 4.3e (iii)) and n~ = the computed Q~ e_9 (eight reflector applications, <= 176 u of rounding),
     // A n~ = [R^T 0] Q~^T n~ - E^T n~ and Q~^T n~ = e_9 up to 1020 u + 176 u, so || A n~ || <= 1372 u ||A||_F + 176 u ||A||_F
-    // = 1548 u ||A||_F = 1.72e-13 ||A||_F <= 1.8e-13 sqrtS.
+    // = 1548 u ||A||_F = 1.72e-13 ||A||_F <= 1.8e-13 sqrtS.  Round 8: A~, the matrix factored here, is built with scales within
+    // 22 u of the exact path's, ||A - A~||_F <= 50.1 u ||A||_F, and a column norm within 1.01 u adds 4.1 u to E:
+    // || A n~ || <= (1548 + 4.1 + 50.2) u ||A||_F = 1603 u = 1.78e-13 ||A||_F <= 1.85e-13 sqrtS.
     // (The first version measured it from a second gather of the sample: 208 flop and eight loads per hypothesis for a term
     // that is five orders of magnitude below eta_J.)
-    const double rho = 1.8e-13 * sqrtS;
-    // sigma_8(A) >= (1 - z) / ||R^-1||_F (1 - 510 u) - 176 u ||A||_F
+    const double rho = kPsRhoC * sqrtS;
+    // sigma_8(A) >= (1 - z) / ||R^-1||_F (1 - 510 u) - 176 u ||A||_F  (round 8: - 231 u ||A||_F, E and Weyl for A - A~; 4e-14 is 360 u)
     const double z = 16.0 * kPsU * sqrtS * yf;
     const double sig8 = (1.0 - z) * rcp_bound(yf) * (1.0 - 1e-13) - 4e-14 * sqrtS;   // (510 u + the reciprocal's 2^-49 < 1e-13)
     const double rg = rcp_bound(sig8);   // (NaN / inf for sig8 <= 0: the certificate is refused below)
