@@ -873,7 +873,7 @@ mvs_status mvs_seq_download_trajectory(mvs_seq *s, double *R, double *t, double 
  * tangent order (rotation, translation), right perturbation R <- R Exp(dw), t <- t + R dv, with the Levenberg-Marquardt
  * rule of the refinement (the LM fields of mvs_refine_params).  Graphs of up to 16 nodes are solved by one workgroup with
  * a dense Cholesky in LDS (a batch of them is one launch); up to 4096 nodes and 65536 edges by a block-Jacobi
- * preconditioned conjugate gradient, one host synchronisation per LM iteration.  Binary64, fixed reduction orders: the
+ * preconditioned conjugate gradient, one host synchronisation per LM iteration (more with cg_chunk_iterations).  Binary64, fixed reduction orders: the
  * same input gives the same bytes.  DESIGN.md section 4.10. */
 typedef struct mvs_pose_graph {            /* all host pointers */
     int32_t n_nodes, n_edges;
@@ -888,7 +888,12 @@ typedef struct mvs_pose_graph_params {
     double anchor_sigma[2];                /* rotation, translation: 1e-4, 1e-4 (graph.cpp GRAPH_ANCHOR_STDDEV) */
     double cg_rel_tol;                     /* 1e-10: the linear solve of the large path stops at |r| <= cg_rel_tol |g| ... */
     int32_t cg_max_iterations;             /* ... or after this many iterations; 0 = 6 n_nodes */
-    int32_t reserved;
+    int32_t cg_chunk_iterations;           /* large path: 0 (the default; anything <= 0) enqueues the whole CG budget of an LM
+                                              iteration at once; c > 0 enqueues c iterations, reads the 64-byte status and goes
+                                              on only while the solve is neither converged nor broken.  The same kernels with
+                                              the same arguments: every output byte and result field equals those at 0.
+                                              Recommended: 64 (1000 nodes, 2030 edges: 1.08 s instead of 2.34 s; 16 and 256
+                                              are within 3 % of it; profiles/seq_pose_graph_latency.json) */
 } mvs_pose_graph_params;
 typedef struct mvs_pose_graph_result {
     int32_t ok;              /* 1: converged or stopped by the iteration / lambda limits with a finite error */
@@ -911,6 +916,56 @@ mvs_status mvs_pose_graph_optimize(mvs_ctx *ctx, const mvs_pose_graph *graph, co
 mvs_status mvs_pose_graph_optimize_batch(mvs_ctx *ctx, const mvs_pose_graph *graphs, int n_graphs,
                                          const mvs_pose_graph_params *params, mvs_pose_graph_result *results,
                                          double *poses_out);
+
+/* ---- The pose graph of a resident sequence: what feeds the back end ---------------------------
+ * Built on the device from what the sequence calls left resident, optimised there, no pose or covariance on the host in
+ * between.
+ *   Nodes       node k = frame k, k = 0 .. n_frames - 1, initial value G_k = (R_k, t_k) of mvs_seq_download_trajectory.  The
+ *               anchor is node 0.
+ *   Candidates  one per lag d = 1 .. max_lag and base k < n_frames - d: source k, destination k + d, measured by r =
+ *               refined[d][k] of mvs_seq_run_lags (pose2in1 of frame k + d in frame k = Xs^-1 Xd of an edge).
+ *   Acceptance  the pair is valid and r.ok; n_points >= min_points; r.error <= max_error; the scale s is finite and > 0; the
+ *               scaled covariance is positive definite by the solver's own 6 x 6 Cholesky test (on its lower triangle).  A
+ *               candidate that fails is dropped; it does not fail the graph.
+ *   Scale       a monocular pair has no metric scale, the trajectory supplies it.  D = t_{k+d} - t_k,
+ *               q_i = (R_k[0][i] D0 + R_k[1][i] D1) + R_k[2][i] D2,  s = sqrt((q0 q0 + q1 q1) + q2 q2) / sqrt((u0 u0 + u1 u1) +
+ *               u2 u2) with u = r.t;  Z = (r.R, (s u0, s u1, s u2)).
+ *   Covariance  S' = D S D, D = diag(1, 1, 1, s, s, s), every entry (f_i S_ij) f_j: under the right perturbation t + R dv a
+ *               translation scaled by s scales dv by s.
+ *   Fallback    where slot (1, k) yields no edge and both chain_sigma > 0: the edge (k, k + 1) with
+ *               Z = G_k^-1 G_{k+1} = (R_k^T R_{k+1}, q) -- R_Z[i][j] = (R_k[0][i] R_{k+1}[0][j] + R_k[1][i] R_{k+1}[1][j]) +
+ *               R_k[2][i] R_{k+1}[2][j], q as above at d = 1 -- and S = diag(chain_sigma[0]^2 I, chain_sigma[1]^2 I); kind 1,
+ *               scale 1.  Without it a node no path joins to node 0 makes the optimisation MVS_NO_MODEL.
+ *   Order       ascending (d, k); a fallback sits in slot (1, k).  Part of the contract: the solver sums in edge order.
+ * Plain binary64 multiplies and adds in exactly the order written, no fused operation: tests/seq_graph_model.py reproduces
+ * every byte. */
+typedef struct mvs_seq_graph_params {
+    int32_t max_lag;        /* 1 .. the lags resident from the last mvs_seq_run_lags */
+    int32_t min_points;     /* 0 = no gate */
+    double  max_error;      /* gate on the refined error; 1e30 = open */
+    double  chain_sigma[2]; /* rotation, translation of the fallback edge; <= 0: none */
+} mvs_seq_graph_params;
+/* Asynchronous on the ctx stream.  MVS_ERR_INVALID_ARG: max_lag < 1 or >= n_frames, min_points < 0, a negative or NaN
+ * max_error, a NaN chain_sigma; a sequence not run, or lags 1 .. max_lag not all resident from one mvs_seq_run_lags since the
+ * last run.  MVS_ERR_CAPACITY (a matter of n_frames and max_lag alone, reported before the sequence's state is looked at):
+ * more than 4096 frames or more than 65536 candidate slots.  The graph lives in a block of the sequence that only grows and
+ * stays until the next mvs_seq_run / _run_essential / _run_lags. */
+mvs_status mvs_seq_build_pose_graph(mvs_seq *s, const mvs_seq_graph_params *p);
+/* mvs_pose_graph_optimize on the resident graph: up to 16 frames through the dense path, more through the large path; result
+ * and optimised nodes are, byte for byte, those of mvs_pose_graph_optimize on the downloaded graph with anchor_node 0.  Only
+ * the edges' endpoints and their count come to the host (connectivity, the incidence list).  Waits for the ctx stream.
+ * MVS_NO_MODEL as there (the result is then zero and the resident optimised nodes are not written);
+ * MVS_ERR_INVALID_ARG before mvs_seq_build_pose_graph or for parameters mvs_pose_graph_optimize refuses. */
+mvs_status mvs_seq_optimize_pose_graph(mvs_seq *s, const mvs_pose_graph_params *p, mvs_pose_graph_result *result);
+/* The resident graph: *n_edges = E, node_pose n_frames x 12, and the first E rows of edge_src / edge_dst / edge_lag /
+ * edge_kind (0 measured, 1 fallback) / edge_scale (E), edge_pose (E x 12), edge_cov (E x 36).  Every array must hold the
+ * candidate slot count max_lag n_frames - max_lag (max_lag + 1) / 2 of the build; any pointer but n_edges may be NULL.
+ * MVS_ERR_INVALID_ARG before mvs_seq_build_pose_graph. */
+mvs_status mvs_seq_download_pose_graph(mvs_seq *s, int32_t *n_edges, double *node_pose, int32_t *edge_src, int32_t *edge_dst,
+                                       double *edge_pose, double *edge_cov, int32_t *edge_lag, int32_t *edge_kind, double *edge_scale);
+/* poses: n_frames x 12, the optimised nodes.  MVS_ERR_INVALID_ARG unless the last mvs_seq_optimize_pose_graph on the current
+ * graph succeeded. */
+mvs_status mvs_seq_download_pose_graph_poses(mvs_seq *s, double *poses);
 
 #ifdef __cplusplus
 }

@@ -148,7 +148,7 @@ class PoseGraph(C.Structure):
 
 class PoseGraphParams(C.Structure):
     _fields_ = [("lm", RefineParams), ("anchor_sigma", C.c_double * 2), ("cg_rel_tol", C.c_double),
-                ("cg_max_iterations", C.c_int32), ("reserved", C.c_int32)]
+                ("cg_max_iterations", C.c_int32), ("cg_chunk_iterations", C.c_int32)]
 
 
 class PoseGraphResult(C.Structure):
@@ -160,6 +160,14 @@ POSE_GRAPH_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("iterations", "<i4"), ("cg_i
                                     ("rejected_steps", "<i4"), ("error_initial", "<f8"), ("error", "<f8")])
 assert POSE_GRAPH_RESULT_DTYPE.itemsize == C.sizeof(PoseGraphResult)
 POSE_GRAPH_DENSE_MAX_NODES, POSE_GRAPH_MAX_NODES, POSE_GRAPH_MAX_EDGES = 16, 4096, 65536
+
+
+class SeqGraphParams(C.Structure):
+    """mvs_seq_graph_params: which resident lagged pairs become edges of the sequence's pose graph"""
+    _fields_ = [("max_lag", C.c_int32), ("min_points", C.c_int32), ("max_error", C.c_double), ("chain_sigma", C.c_double * 2)]
+
+
+SEQ_GRAPH_EDGE_MEASURED, SEQ_GRAPH_EDGE_CHAIN = 0, 1
 
 
 class OrbParams(C.Structure):
@@ -211,6 +219,8 @@ EXPORTS = [
     "mvs_seq_download_track_step", "mvs_seq_run_lags", "mvs_seq_download_lag_pairs", "mvs_seq_download_lag_refined",
     "mvs_vo_init_params_default", "mvs_seq_odometry", "mvs_seq_download_odometry_frames",
     "mvs_pose_graph_params_default", "mvs_pose_graph_optimize", "mvs_pose_graph_optimize_batch",
+    "mvs_seq_build_pose_graph", "mvs_seq_optimize_pose_graph", "mvs_seq_download_pose_graph",
+    "mvs_seq_download_pose_graph_poses",
 ]
 
 
@@ -341,7 +351,7 @@ def default_pose_graph_params(**kw):
     for k, v in kw.items():
         if k == "anchor_sigma":
             p.anchor_sigma[0], p.anchor_sigma[1] = float(v[0]), float(v[1])
-        elif k in ("cg_rel_tol", "cg_max_iterations"):
+        elif k in ("cg_rel_tol", "cg_max_iterations", "cg_chunk_iterations"):
             setattr(p, k, v)
         else:
             setattr(p.lm, k, v)
@@ -1310,6 +1320,46 @@ class Sequence:
         self.ctx._check(lib().mvs_seq_download_odometry_frames(self._h, od.ctypes.data_as(C.c_void_p)),
                         "mvs_seq_download_odometry_frames")
         return od
+
+    def build_pose_graph(self, max_lag, min_points=0, max_error=1e30, chain_sigma=(0.0, 0.0)):
+        """the pose graph of the sequence on the device (mvs_seq_build_pose_graph; asynchronous): nodes = the trajectory,
+        edges = the refined pairs of lags 1 .. max_lag from run_lags() that pass the gates, scaled by the trajectory"""
+        gp = SeqGraphParams(int(max_lag), int(min_points), float(max_error), (C.c_double * 2)(float(chain_sigma[0]),
+                                                                                              float(chain_sigma[1])))
+        self.ctx._check(lib().mvs_seq_build_pose_graph(self._h, C.byref(gp)), "mvs_seq_build_pose_graph")
+        self._graph_slots = max_lag * self.n_frames - max_lag * (max_lag + 1) // 2
+
+    def optimize_pose_graph(self, params=None):
+        """mvs_seq_optimize_pose_graph: (status, result record); download_pose_graph_poses() fetches the nodes"""
+        params = params or default_pose_graph_params()
+        res = np.zeros(1, dtype=POSE_GRAPH_RESULT_DTYPE)
+        st = lib().mvs_seq_optimize_pose_graph(self._h, C.byref(params), res.ctypes.data_as(C.c_void_p))
+        self.ctx._check(st, "mvs_seq_optimize_pose_graph", allow_no_model=True)
+        return st, res[0]
+
+    def download_pose_graph(self):
+        """the resident graph, cut to its edge count: node_pose [n_frames, 12], edge_src, edge_dst, edge_pose [E, 12],
+        edge_cov [E, 36], edge_lag, edge_kind, edge_scale, anchor (0) -- the keys Context.pose_graph_optimize reads, and more"""
+        S = max(getattr(self, "_graph_slots", 0), 1)
+        n = np.zeros(1, dtype=np.int32)
+        node = np.zeros((self.n_frames, 12))
+        src, dst, lag, kind = (np.zeros(S, dtype=np.int32) for _ in range(4))
+        Z, cov, scale = np.zeros((S, 12)), np.zeros((S, 36)), np.zeros(S)
+        st = lib().mvs_seq_download_pose_graph(self._h, _ptr(n, C.c_int32), _ptr(node, C.c_double), _ptr(src, C.c_int32),
+                                               _ptr(dst, C.c_int32), _ptr(Z, C.c_double), _ptr(cov, C.c_double),
+                                               _ptr(lag, C.c_int32), _ptr(kind, C.c_int32), _ptr(scale, C.c_double))
+        self.ctx._check(st, "mvs_seq_download_pose_graph")
+        E = int(n[0])
+        return dict(n_edges=E, node_pose=node, edge_src=src[:E].copy(), edge_dst=dst[:E].copy(), edge_pose=Z[:E].copy(),
+                    edge_cov=cov[:E].copy(), edge_lag=lag[:E].copy(), edge_kind=kind[:E].copy(), edge_scale=scale[:E].copy(),
+                    anchor=0)
+
+    def download_pose_graph_poses(self):
+        """the optimised nodes [n_frames, 12] of the last successful optimize_pose_graph()"""
+        poses = np.zeros((self.n_frames, 12))
+        st = lib().mvs_seq_download_pose_graph_poses(self._h, _ptr(poses, C.c_double))
+        self.ctx._check(st, "mvs_seq_download_pose_graph_poses")
+        return poses
 
     def download_pairs(self):
         P, N = self.n_frames - 1, self.max_kp

@@ -138,6 +138,12 @@ struct mvs_seq {
     int lags_ran = 0;           // lags 1 .. lags_ran are resident from one mvs_seq_run_lags since the last run
     bool odo_ran = false;       // the resident tracking results are mvs_seq_odometry's
     OdoDev odo{};
+    // mvs_seq_build_pose_graph: the candidate slots, the graph and the optimised nodes, resident until the next run
+    DevWorkspace graph;
+    SeqGraphDev gd{};
+    double *graph_opt_pose = nullptr;   // [n_frames][12] in `graph`
+    bool graph_built = false;   // the graph is that of the last run and its lags
+    bool graph_opt = false;     // mvs_seq_optimize_pose_graph has succeeded on it
 };
 
 #define HIP_TRY(ctx_, expr)                                                                    \
@@ -2646,6 +2652,7 @@ static mvs_status seq_enqueue(mvs_seq *q, Estimator est, const RunParams &rp)
     q->refined_ran = false;  // nor are refined pairs (the batch keeps them downloadable; mvs_seq_track does not start from them)
     q->lags_ran = 0;         // nor are lagged pairs
     q->odo_ran = false;
+    q->graph_built = q->graph_opt = false;   // nor is a pose graph
     return MVS_OK;
 }
 
@@ -3791,6 +3798,7 @@ mvs_status mvs_seq_run_lags(mvs_seq *q, const mvs_params *two_view, int max_lag,
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     q->lags_ran = 0;
+    q->graph_built = q->graph_opt = false;   // a graph of the lags this call overwrites
     const BatchDev &bd = q->batch->d;
     const size_t F = (size_t)q->n_frames;
     const Estimator est = essential ? Estimator::kFivePoint : Estimator::kEightPoint;
@@ -4313,7 +4321,7 @@ void mvs_pose_graph_params_default(mvs_pose_graph_params *p)
     p->anchor_sigma[0] = p->anchor_sigma[1] = 1e-4;   // graph.cpp GRAPH_ANCHOR_STDDEV
     p->cg_rel_tol = 1e-10;
     p->cg_max_iterations = 0;                         // 6 n_nodes
-    p->reserved = 0;
+    p->cg_chunk_iterations = 0;                       // the whole budget at once
 }
 
 static PgCfg to_pg_cfg(const mvs_pose_graph_params &p)
@@ -4383,70 +4391,79 @@ static bool pose_graph_connected(const mvs_pose_graph &g)
     return true;
 }
 
-// one graph of 17 .. 4096 nodes: LM on the host, one synchronisation per iteration
-static mvs_status pose_graph_large(mvs_ctx *ctx, const mvs_pose_graph &g, const mvs_pose_graph_params &params,
-                                   mvs_pose_graph_result *res, double *poses_out)
+// ---- the solver's entries over device-resident graphs ------------------------------------------------------------------
+// The host-pointer calls upload and come here; mvs_seq_optimize_pose_graph comes here with the graph of its sequence.  Only
+// edge_src / edge_dst are also needed on the host (connectivity, the CSR list).
+
+// scratch of the large path for N nodes and E edges, as offsets from one base in ctx->pg
+struct PgLargeLayout {
+    size_t o_state, o_off, o_inc, o_pa, o_pb, o_W, o_lin, o_u, o_ec, o_D, o_Mf, o_vec[6], o_pq, o_Ha, total;
+    PgLargeLayout(size_t N, size_t E)
+    {
+        Carve L{64};
+        o_state = L.take(sizeof(PgState));
+        o_off = L.take((N + 1) * 4), o_inc = L.take(2 * E * 4);
+        o_pa = L.take(N * 12 * 8), o_pb = L.take(N * 12 * 8);
+        o_W = L.take(E * 21 * 8), o_lin = L.take(E * kPgLin * 8), o_u = L.take(E * 6 * 8), o_ec = L.take(E * 8);
+        o_D = L.take(N * 21 * 8), o_Mf = L.take(N * 21 * 8);
+        for (size_t &o : o_vec)
+            o = L.take(N * 6 * 8);
+        o_pq = L.take(N * 8), o_Ha = L.take(36 * 8);
+        total = L.total();
+    }
+};
+
+// one graph of 17 .. 4096 nodes: LM on the host, one synchronisation per iteration (and, with cg_chunk_iterations > 0, one
+// per chunk of CG iterations that did not converge).  h_src / h_dst: the edges on the host; every d_* pointer is device
+// memory that stays valid through the call; `base` is scratch of PgLargeLayout(N, E).total bytes.  The optimised nodes go
+// to poses_out with a copy of kind `out_kind` (device to host, or device to device), only when the result is ok.
+static mvs_status pose_graph_large_dev(mvs_ctx *ctx, char *base, int n_nodes, int n_edges, int anchor, const int32_t *h_src,
+                                       const int32_t *h_dst, const int32_t *d_src, const int32_t *d_dst, const double *d_node,
+                                       const double *d_z, const double *d_cov, const mvs_pose_graph_params &params,
+                                       mvs_pose_graph_result *res, double *poses_out, hipMemcpyKind out_kind)
 {
-    const size_t N = (size_t)g.n_nodes, E = (size_t)g.n_edges;
+    const size_t N = (size_t)n_nodes, E = (size_t)n_edges;
     // CSR list of the incident edges of every node, in edge order
     std::vector<int32_t> off(N + 1, 0), inc(2 * E);
     for (size_t k = 0; k < E; ++k) {
-        ++off[(size_t)g.edge_src[k] + 1];
-        ++off[(size_t)g.edge_dst[k] + 1];
+        ++off[(size_t)h_src[k] + 1];
+        ++off[(size_t)h_dst[k] + 1];
     }
     for (size_t i = 0; i < N; ++i)
         off[i + 1] += off[i];
     {
         std::vector<int32_t> fill(off.begin(), off.end() - 1);
         for (size_t k = 0; k < E; ++k) {
-            inc[(size_t)fill[(size_t)g.edge_src[k]]++] = (int32_t)(2 * k);
-            inc[(size_t)fill[(size_t)g.edge_dst[k]]++] = (int32_t)(2 * k + 1);
+            inc[(size_t)fill[(size_t)h_src[k]]++] = (int32_t)(2 * k);
+            inc[(size_t)fill[(size_t)h_dst[k]]++] = (int32_t)(2 * k + 1);
         }
     }
-    Carve L{64};
-    const size_t o_state = L.take(sizeof(PgState));
-    const size_t o_src = L.take(E * 4), o_dst = L.take(E * 4), o_off = L.take((N + 1) * 4), o_inc = L.take(2 * E * 4);
-    const size_t o_z = L.take(E * 12 * 8), o_cov = L.take(E * 36 * 8), o_p0 = L.take(N * 12 * 8);
-    const size_t o_pa = L.take(N * 12 * 8), o_pb = L.take(N * 12 * 8);
-    const size_t o_W = L.take(E * 21 * 8), o_lin = L.take(E * kPgLin * 8), o_u = L.take(E * 6 * 8), o_ec = L.take(E * 8);
-    const size_t o_D = L.take(N * 21 * 8), o_Mf = L.take(N * 21 * 8);
-    size_t o_vec[6];
-    for (size_t &o : o_vec)
-        o = L.take(N * 6 * 8);
-    const size_t o_pq = L.take(N * 8), o_Ha = L.take(36 * 8);
-    mvs_status st = ws_grow(ctx, ctx->pg, L.total());
-    if (st != MVS_OK)
-        return st;
-    char *base = ctx->pg.ptr();
+    const PgLargeLayout L(N, E);
     hipStream_t s = ctx->stream;
-    HIP_TRY(ctx, hipMemsetAsync(base + o_state, 0, sizeof(PgState), s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_src, g.edge_src, E * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_dst, g.edge_dst, E * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_off, off.data(), (N + 1) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_inc, inc.data(), 2 * E * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_z, g.edge_pose, E * 12 * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_cov, g.edge_cov, E * 36 * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_p0, g.node_pose, N * 12 * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_pa, g.node_pose, N * 12 * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(base + L.o_state, 0, sizeof(PgState), s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + L.o_off, off.data(), (N + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + L.o_inc, inc.data(), 2 * E * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + L.o_pa, d_node, N * 12 * 8, hipMemcpyDeviceToDevice, s));
     auto dp = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
     auto ip = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o); };
     PgLargeDev d{};
-    d.n_nodes = g.n_nodes, d.n_edges = g.n_edges, d.anchor = g.anchor_node;
+    d.n_nodes = n_nodes, d.n_edges = n_edges, d.anchor = anchor;
     d.cfg = to_pg_cfg(params);
-    d.edge_src = ip(o_src), d.edge_dst = ip(o_dst), d.csr_off = ip(o_off), d.csr_inc = ip(o_inc);
-    d.edge_pose = dp(o_z), d.edge_cov = dp(o_cov), d.pose0 = dp(o_p0);
-    d.pose[0] = dp(o_pa), d.pose[1] = dp(o_pb);
-    d.W = dp(o_W), d.lin = dp(o_lin), d.u = dp(o_u), d.ecost = dp(o_ec), d.D = dp(o_D), d.Mf = dp(o_Mf);
-    d.g = dp(o_vec[0]), d.x = dp(o_vec[1]), d.r = dp(o_vec[2]), d.z = dp(o_vec[3]), d.p = dp(o_vec[4]), d.q = dp(o_vec[5]);
-    d.pq = dp(o_pq), d.Ha = dp(o_Ha);
-    d.state = reinterpret_cast<PgState *>(base + o_state);
-    const int cg_max = params.cg_max_iterations > 0 ? params.cg_max_iterations : 6 * g.n_nodes;
+    d.edge_src = d_src, d.edge_dst = d_dst, d.csr_off = ip(L.o_off), d.csr_inc = ip(L.o_inc);
+    d.edge_pose = d_z, d.edge_cov = d_cov, d.pose0 = d_node;
+    d.pose[0] = dp(L.o_pa), d.pose[1] = dp(L.o_pb);
+    d.W = dp(L.o_W), d.lin = dp(L.o_lin), d.u = dp(L.o_u), d.ecost = dp(L.o_ec), d.D = dp(L.o_D), d.Mf = dp(L.o_Mf);
+    d.g = dp(L.o_vec[0]), d.x = dp(L.o_vec[1]), d.r = dp(L.o_vec[2]), d.z = dp(L.o_vec[3]), d.p = dp(L.o_vec[4]), d.q = dp(L.o_vec[5]);
+    d.pq = dp(L.o_pq), d.Ha = dp(L.o_Ha);
+    d.state = reinterpret_cast<PgState *>(base + L.o_state);
+    const int cg_max = params.cg_max_iterations > 0 ? params.cg_max_iterations : 6 * n_nodes;
+    const int chunk = params.cg_chunk_iterations;
     launch_pg_prep(d, s);
     HIP_TRY(ctx, hipGetLastError());
     PgState h{};
     // a covariance that is not positive definite ends the call here, before anything is linearised on its whitening factor
     HIP_TRY(ctx, hipMemcpyAsync(&h, d.state, sizeof(h), hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, sync_stream(ctx));
+    HIP_TRY(ctx, sync_stream(ctx));   // `off` and `inc` have been read by here, too
     if (h.bad_cov) {
         *res = mvs_pose_graph_result{};
         return MVS_OK;
@@ -4458,7 +4475,25 @@ static mvs_status pose_graph_large(mvs_ctx *ctx, const mvs_pose_graph &g, const 
     double cur = 0.0, cost0 = 0.0, lam = cfg.lambda_initial;
     bool ok0 = true, have0 = false;
     while (ok0 && it < cfg.max_iterations) {
-        launch_pg_iteration(d, cb, lam, cg_max, !have0, s);
+        launch_pg_begin(d, cb, lam, !have0, s);
+        if (chunk <= 0) {
+            launch_pg_cg(d, lam, cg_max, s);
+        } else {
+            // chunk by chunk: the iterations not enqueued are the ones the status word would have sent away at once
+            for (int left = cg_max; left > 0;) {
+                const int n = std::min(chunk, left);
+                launch_pg_cg(d, lam, n, s);
+                left -= n;
+                if (left > 0) {
+                    HIP_TRY(ctx, hipGetLastError());
+                    HIP_TRY(ctx, hipMemcpyAsync(&h, d.state, sizeof(h), hipMemcpyDeviceToHost, s));
+                    HIP_TRY(ctx, sync_stream(ctx));
+                    if (h.done)
+                        break;
+                }
+            }
+        }
+        launch_pg_end(d, cb, s);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(&h, d.state, sizeof(h), hipMemcpyDeviceToHost, s));
         HIP_TRY(ctx, sync_stream(ctx));
@@ -4494,7 +4529,8 @@ static mvs_status pose_graph_large(mvs_ctx *ctx, const mvs_pose_graph &g, const 
         }
     }
     if (!have0) {   // max_iterations = 0: the cost at the initial values alone (an iteration with no CG steps leaves x = 0)
-        launch_pg_iteration(d, cb, lam, 0, true, s);
+        launch_pg_begin(d, cb, lam, true, s);
+        launch_pg_end(d, cb, s);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(&h, d.state, sizeof(h), hipMemcpyDeviceToHost, s));
         HIP_TRY(ctx, sync_stream(ctx));
@@ -4508,10 +4544,78 @@ static mvs_status pose_graph_large(mvs_ctx *ctx, const mvs_pose_graph &g, const 
     res->error_initial = ok0 ? 0.5 * cost0 : 0.0;
     res->error = ok0 ? 0.5 * cur : 0.0;
     if (ok0) {
-        HIP_TRY(ctx, hipMemcpyAsync(poses_out, d.pose[cb], N * 12 * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipMemcpyAsync(poses_out, d.pose[cb], N * 12 * 8, out_kind, s));
         HIP_TRY(ctx, sync_stream(ctx));
     }
     return MVS_OK;
+}
+
+// the host-pointer entry of the large path: upload, then the entry above
+static mvs_status pose_graph_large(mvs_ctx *ctx, const mvs_pose_graph &g, const mvs_pose_graph_params &params,
+                                   mvs_pose_graph_result *res, double *poses_out)
+{
+    const size_t N = (size_t)g.n_nodes, E = (size_t)g.n_edges;
+    Carve U{64};
+    const size_t o_src = U.take(E * 4), o_dst = U.take(E * 4), o_z = U.take(E * 12 * 8), o_cov = U.take(E * 36 * 8);
+    const size_t o_p0 = U.take(N * 12 * 8), o_solver = U.total();
+    mvs_status st = ws_grow(ctx, ctx->pg, o_solver + PgLargeLayout(N, E).total);
+    if (st != MVS_OK)
+        return st;
+    char *base = ctx->pg.ptr();
+    hipStream_t s = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_src, g.edge_src, E * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_dst, g.edge_dst, E * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_z, g.edge_pose, E * 12 * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_cov, g.edge_cov, E * 36 * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_p0, g.node_pose, N * 12 * 8, hipMemcpyHostToDevice, s));
+    auto dp = [&](size_t o) { return reinterpret_cast<const double *>(base + o); };
+    auto ip = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o); };
+    return pose_graph_large_dev(ctx, base + o_solver, g.n_nodes, g.n_edges, g.anchor_node, g.edge_src, g.edge_dst, ip(o_src),
+                                ip(o_dst), dp(o_p0), dp(o_z), dp(o_cov), params, res, poses_out, hipMemcpyDeviceToHost);
+}
+
+// scratch of a dense-path batch of G graphs with sumN nodes and sumE edges.  Outputs first and contiguous (results,
+// poses): a download is their prefix.
+struct PgDenseLayout {
+    size_t o_out, o_po, down, o_W, o_lin, total;
+    PgDenseLayout(size_t G, size_t sumN, size_t sumE)
+    {
+        Carve L{64};
+        o_out = L.take(G * sizeof(mvs_pose_graph_result)), o_po = L.take(sumN * 12 * 8);
+        down = L.total();
+        o_W = L.take(sumE * 21 * 8), o_lin = L.take(sumE * kPgLin * 8);
+        total = L.total();
+    }
+};
+
+// graphs of up to 16 nodes over device-resident inputs: one launch.  `base`: scratch of PgDenseLayout::total bytes.
+static mvs_status pose_graph_dense_dev(mvs_ctx *ctx, char *base, const PgDenseLayout &L, int n_graphs,
+                                       const mvs_pose_graph_params &params, const PgProblem *d_prob, const double *d_node,
+                                       const int32_t *d_src, const int32_t *d_dst, const double *d_z, const double *d_cov)
+{
+    PgDenseDev d{};
+    d.n_problems = n_graphs;
+    d.cfg = to_pg_cfg(params);
+    d.prob = d_prob;
+    d.node_pose = d_node;
+    d.edge_pose = d_z;
+    d.edge_cov = d_cov;
+    d.edge_src = d_src;
+    d.edge_dst = d_dst;
+    d.W = reinterpret_cast<double *>(base + L.o_W);
+    d.lin = reinterpret_cast<double *>(base + L.o_lin);
+    d.poses_out = reinterpret_cast<double *>(base + L.o_po);
+    d.out = reinterpret_cast<mvs_pose_graph_result *>(base + L.o_out);
+    launch_pg_dense(d, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return MVS_OK;
+}
+
+static bool pose_graph_params_ok(const mvs_pose_graph_params *params)
+{
+    return params && params->lm.max_iterations >= 0 && params->lm.lambda_initial >= 0.0 && params->lm.lambda_factor > 1.0 &&
+           params->lm.lambda_upper > 0.0 && params->anchor_sigma[0] > 0.0 && params->anchor_sigma[1] > 0.0 &&
+           params->cg_rel_tol >= 0.0 && params->cg_max_iterations >= 0;
 }
 
 mvs_status mvs_pose_graph_optimize_batch(mvs_ctx *ctx, const mvs_pose_graph *graphs, int n_graphs,
@@ -4520,9 +4624,7 @@ mvs_status mvs_pose_graph_optimize_batch(mvs_ctx *ctx, const mvs_pose_graph *gra
 {
     if (!ctx || !graphs || n_graphs < 1 || !params || !results || !poses_out)
         return MVS_ERR_INVALID_ARG;
-    if (params->lm.max_iterations < 0 || !(params->lm.lambda_initial >= 0.0) || !(params->lm.lambda_factor > 1.0) ||
-        !(params->lm.lambda_upper > 0.0) || !(params->anchor_sigma[0] > 0.0) || !(params->anchor_sigma[1] > 0.0) ||
-        !(params->cg_rel_tol >= 0.0) || params->cg_max_iterations < 0)
+    if (!pose_graph_params_ok(params))
         return MVS_ERR_INVALID_ARG;
     int Nmax = 0;
     for (int i = 0; i < n_graphs; ++i) {
@@ -4554,15 +4656,12 @@ mvs_status mvs_pose_graph_optimize_batch(mvs_ctx *ctx, const mvs_pose_graph *gra
     }
     if (!desc.empty()) {
         const size_t G = desc.size();
-        Carve L{64};   // outputs first and contiguous (results, poses): the download is their prefix
-        const size_t o_out = L.take(G * sizeof(mvs_pose_graph_result)), o_po = L.take(sumN * 12 * 8);
-        const size_t down = L.total();
-        const size_t o_W = L.take(sumE * 21 * 8), o_lin = L.take(sumE * kPgLin * 8);
-        const size_t o_up = L.total();   // the uploaded block: descriptors, node poses, edge poses, covariances, src, dst
+        const PgDenseLayout L(G, sumN, sumE);
+        const size_t o_up = L.total;   // the uploaded block: descriptors, node poses, edge poses, covariances, src, dst
         Carve U{64};
         const size_t u_desc = U.take(G * sizeof(PgProblem)), u_np = U.take(sumN * 12 * 8), u_z = U.take(sumE * 12 * 8);
         const size_t u_cov = U.take(sumE * 36 * 8), u_src = U.take(sumE * 4), u_dst = U.take(sumE * 4);
-        const mvs_status st = ws_grow(ctx, ctx->pg, o_up + U.total());
+        mvs_status st = ws_grow(ctx, ctx->pg, o_up + U.total());
         if (st != MVS_OK)
             return st;
         std::vector<char> up(U.total());
@@ -4581,29 +4680,20 @@ mvs_status mvs_pose_graph_optimize_batch(mvs_ctx *ctx, const mvs_pose_graph *gra
         char *base = ctx->pg.ptr();
         hipStream_t s = ctx->stream;
         HIP_TRY(ctx, hipMemcpyAsync(base + o_up, up.data(), up.size(), hipMemcpyHostToDevice, s));
-        PgDenseDev d{};
-        d.n_problems = (int)G;
-        d.cfg = to_pg_cfg(*params);
-        d.prob = reinterpret_cast<const PgProblem *>(base + o_up + u_desc);
-        d.node_pose = reinterpret_cast<const double *>(base + o_up + u_np);
-        d.edge_pose = reinterpret_cast<const double *>(base + o_up + u_z);
-        d.edge_cov = reinterpret_cast<const double *>(base + o_up + u_cov);
-        d.edge_src = reinterpret_cast<const int32_t *>(base + o_up + u_src);
-        d.edge_dst = reinterpret_cast<const int32_t *>(base + o_up + u_dst);
-        d.W = reinterpret_cast<double *>(base + o_W);
-        d.lin = reinterpret_cast<double *>(base + o_lin);
-        d.poses_out = reinterpret_cast<double *>(base + o_po);
-        d.out = reinterpret_cast<mvs_pose_graph_result *>(base + o_out);
-        launch_pg_dense(d, s);
-        HIP_TRY(ctx, hipGetLastError());
-        std::vector<char> host(down);
-        HIP_TRY(ctx, hipMemcpyAsync(host.data(), base, down, hipMemcpyDeviceToHost, s));
+        auto dp = [&](size_t o) { return reinterpret_cast<const double *>(base + o_up + o); };
+        auto ip = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o_up + o); };
+        st = pose_graph_dense_dev(ctx, base, L, (int)G, *params, reinterpret_cast<const PgProblem *>(base + o_up + u_desc),
+                                  dp(u_np), ip(u_src), ip(u_dst), dp(u_z), dp(u_cov));
+        if (st != MVS_OK)
+            return st;
+        std::vector<char> host(L.down);
+        HIP_TRY(ctx, hipMemcpyAsync(host.data(), base, L.down, hipMemcpyDeviceToHost, s));
         HIP_TRY(ctx, sync_stream(ctx));
         for (size_t k = 0; k < G; ++k) {
             const int i = which[k];
-            std::memcpy(&results[i], host.data() + o_out + k * sizeof(mvs_pose_graph_result), sizeof(mvs_pose_graph_result));
+            std::memcpy(&results[i], host.data() + L.o_out + k * sizeof(mvs_pose_graph_result), sizeof(mvs_pose_graph_result));
             if (results[i].ok)
-                std::memcpy(poses_out + (size_t)i * Nmax * 12, host.data() + o_po + (size_t)desc[k].node_off * 96,
+                std::memcpy(poses_out + (size_t)i * Nmax * 12, host.data() + L.o_po + (size_t)desc[k].node_off * 96,
                             (size_t)graphs[i].n_nodes * 96);
         }
     }
@@ -4625,5 +4715,149 @@ mvs_status mvs_pose_graph_optimize(mvs_ctx *ctx, const mvs_pose_graph *graph, co
                                    mvs_pose_graph_result *result, double *poses_out)
 {
     return mvs_pose_graph_optimize_batch(ctx, graph, 1, params, result, poses_out);
+}
+
+// ---- the pose graph of a resident sequence (seq_graph.hip) -------------------------------------
+mvs_status mvs_seq_build_pose_graph(mvs_seq *q, const mvs_seq_graph_params *p)
+{
+    if (!q || !p || p->max_lag < 1 || p->max_lag >= q->n_frames || p->min_points < 0 || !(p->max_error >= 0.0) ||
+        p->chain_sigma[0] != p->chain_sigma[0] || p->chain_sigma[1] != p->chain_sigma[1])
+        return MVS_ERR_INVALID_ARG;
+    const int64_t slots64 = (int64_t)p->max_lag * q->n_frames - (int64_t)p->max_lag * (p->max_lag + 1) / 2;
+    if (q->n_frames > kPgMaxNodes || slots64 > kPgMaxEdges)
+        return MVS_ERR_CAPACITY;
+    if (!q->ran || p->max_lag > q->lags_ran)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    q->graph_built = q->graph_opt = false;
+    const size_t S = (size_t)slots64, F = (size_t)q->n_frames;
+    Carve L{64};   // the count, src and dst first and in this order: mvs_seq_optimize_pose_graph downloads that prefix
+    const size_t o_n = L.take(4), o_src = L.take(S * 4), o_dst = L.take(S * 4), o_lag = L.take(S * 4), o_kind = L.take(S * 4);
+    const size_t o_scale = L.take(S * 8), o_z = L.take(S * 12 * 8), o_cov = L.take(S * 36 * 8), o_node = L.take(F * 12 * 8);
+    const size_t o_opt = L.take(F * 12 * 8), o_keep = L.take(S * 4), o_skind = L.take(S * 4), o_sscale = L.take(S * 8);
+    const size_t o_sz = L.take(S * 12 * 8), o_scov = L.take(S * 36 * 8);
+    const mvs_status st = ws_grow(ctx, q->graph, L.total());
+    if (st != MVS_OK)
+        return st;
+    char *base = q->graph.ptr();
+    auto dp = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
+    auto ip = [&](size_t o) { return reinterpret_cast<int32_t *>(base + o); };
+    SeqGraphDev g{};
+    g.n_frames = q->n_frames, g.max_lag = p->max_lag, g.n_slots = (int)S;
+    g.min_points = p->min_points;
+    g.max_error = p->max_error;
+    g.chain_on = p->chain_sigma[0] > 0.0 && p->chain_sigma[1] > 0.0;
+    g.chain_var[0] = p->chain_sigma[0] * p->chain_sigma[0];
+    g.chain_var[1] = p->chain_sigma[1] * p->chain_sigma[1];
+    g.lags = q->lagws.ptr<LagDev>();
+    g.traj_R = q->chain.traj_R, g.traj_t = q->chain.traj_t;
+    g.slot_keep = ip(o_keep), g.slot_kind = ip(o_skind), g.slot_scale = dp(o_sscale), g.slot_pose = dp(o_sz), g.slot_cov = dp(o_scov);
+    g.n_edges = ip(o_n), g.edge_src = ip(o_src), g.edge_dst = ip(o_dst), g.edge_lag = ip(o_lag), g.edge_kind = ip(o_kind);
+    g.edge_scale = dp(o_scale), g.edge_pose = dp(o_z), g.edge_cov = dp(o_cov), g.node_pose = dp(o_node);
+    launch_seq_graph(g, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    q->gd = g;
+    q->graph_opt_pose = dp(o_opt);
+    q->graph_built = true;
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_optimize_pose_graph(mvs_seq *q, const mvs_pose_graph_params *params, mvs_pose_graph_result *result)
+{
+    if (!q || !q->graph_built || !result || !pose_graph_params_ok(params))
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const SeqGraphDev &g = q->gd;
+    hipStream_t s = ctx->stream;
+    q->graph_opt = false;
+    *result = mvs_pose_graph_result{};
+    // the count and the edges' endpoints: all the host needs of the graph
+    const char *gbase = q->graph.ptr();
+    const size_t o_src = (const char *)g.edge_src - gbase, o_dst = (const char *)g.edge_dst - gbase;
+    std::vector<char> head(o_dst + (size_t)g.n_slots * 4);
+    HIP_TRY(ctx, hipMemcpyAsync(head.data(), gbase, head.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    int32_t E = 0;
+    std::memcpy(&E, head.data(), 4);
+    const int32_t *h_src = reinterpret_cast<const int32_t *>(head.data() + o_src);
+    const int32_t *h_dst = reinterpret_cast<const int32_t *>(head.data() + o_dst);
+    const int N = g.n_frames;
+    if (E < 0 || E > g.n_slots) {
+        ctx->err = "mvs_seq_optimize_pose_graph: edge count out of range";
+        return MVS_ERR_HIP;
+    }
+    mvs_pose_graph hg{};
+    hg.n_nodes = N, hg.n_edges = E, hg.edge_src = h_src, hg.edge_dst = h_dst, hg.anchor_node = 0;
+    if (!pose_graph_connected(hg))
+        return MVS_NO_MODEL;
+    if (N <= kPgDenseMaxNodes) {
+        PgProblem pr{};
+        pr.n_nodes = N, pr.n_edges = E, pr.anchor = 0;
+        const PgDenseLayout L(1, (size_t)N, (size_t)E);
+        const size_t o_desc = L.total;
+        mvs_status st = ws_grow(ctx, ctx->pg, o_desc + sizeof(PgProblem));
+        if (st != MVS_OK)
+            return st;
+        char *base = ctx->pg.ptr();
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_desc, &pr, sizeof(pr), hipMemcpyHostToDevice, s));
+        st = pose_graph_dense_dev(ctx, base, L, 1, *params, reinterpret_cast<const PgProblem *>(base + o_desc), g.node_pose,
+                                  g.edge_src, g.edge_dst, g.edge_pose, g.edge_cov);
+        if (st != MVS_OK)
+            return st;
+        HIP_TRY(ctx, hipMemcpyAsync(result, base + L.o_out, sizeof(*result), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, sync_stream(ctx));   // `pr` lives on this frame
+        if (result->ok)
+            HIP_TRY(ctx, hipMemcpyAsync(q->graph_opt_pose, base + L.o_po, (size_t)N * 96, hipMemcpyDeviceToDevice, s));
+    } else {
+        mvs_status st = ws_grow(ctx, ctx->pg, PgLargeLayout((size_t)N, (size_t)E).total);
+        if (st != MVS_OK)
+            return st;
+        st = pose_graph_large_dev(ctx, ctx->pg.ptr(), N, E, 0, h_src, h_dst, g.edge_src, g.edge_dst, g.node_pose, g.edge_pose,
+                                  g.edge_cov, *params, result, q->graph_opt_pose, hipMemcpyDeviceToDevice);
+        if (st != MVS_OK)
+            return st;
+    }
+    q->graph_opt = result->ok != 0;
+    return result->ok ? MVS_OK : MVS_NO_MODEL;
+}
+
+mvs_status mvs_seq_download_pose_graph(mvs_seq *q, int32_t *n_edges, double *node_pose, int32_t *edge_src, int32_t *edge_dst,
+                                       double *edge_pose, double *edge_cov, int32_t *edge_lag, int32_t *edge_kind,
+                                       double *edge_scale)
+{
+    if (!q || !q->graph_built || !n_edges)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const SeqGraphDev &g = q->gd;
+    hipStream_t s = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(n_edges, g.n_edges, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    const size_t E = (size_t)std::min(std::max(*n_edges, 0), g.n_slots);
+    const struct {
+        void *dst;
+        const void *src;
+        size_t bytes;
+    } parts[] = {{node_pose, g.node_pose, (size_t)g.n_frames * 96}, {edge_src, g.edge_src, E * 4}, {edge_dst, g.edge_dst, E * 4},
+                 {edge_pose, g.edge_pose, E * 96}, {edge_cov, g.edge_cov, E * 288}, {edge_lag, g.edge_lag, E * 4},
+                 {edge_kind, g.edge_kind, E * 4}, {edge_scale, g.edge_scale, E * 8}};
+    for (const auto &pt : parts)
+        if (pt.dst && pt.bytes)
+            HIP_TRY(ctx, hipMemcpyAsync(pt.dst, pt.src, pt.bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_download_pose_graph_poses(mvs_seq *q, double *poses)
+{
+    if (!q || !poses || !q->graph_built || !q->graph_opt)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(poses, q->graph_opt_pose, (size_t)q->n_frames * 96, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, sync_stream(ctx));
+    return MVS_OK;
 }
 }  // extern "C"

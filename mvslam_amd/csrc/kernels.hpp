@@ -324,9 +324,15 @@ struct PgLargeDev {
     PgState *state;
 };
 void launch_pg_prep(const PgLargeDev &d, hipStream_t stream);
-// one LM iteration at pose[cur] with damping lam: linearise, gather, PCG (every iteration enqueued, the status word ends
-// them), candidate = pose[cur ^ 1], its cost -> state->cand.  `first`: the cost at pose[cur] -> state->cost0 before it.
-void launch_pg_iteration(const PgLargeDev &d, int cur, double lam, int cg_max, bool first, hipStream_t stream);
+// one LM iteration at pose[cur] with damping lam, in three parts the host enqueues in this order:
+//   begin  linearise, gather, PCG start.  `first`: the cost at pose[cur] -> state->cost0 before it.
+//   cg     n PCG iterations; the status word makes the ones behind convergence leave at once.  The whole budget in one call
+//          or in chunks with a status read between them (mvs_pose_graph_params.cg_chunk_iterations): the same kernels with
+//          the same arguments either way.
+//   end    candidate = pose[cur ^ 1], its cost -> state->cand.
+void launch_pg_begin(const PgLargeDev &d, int cur, double lam, bool first, hipStream_t stream);
+void launch_pg_cg(const PgLargeDev &d, double lam, int n, hipStream_t stream);
+void launch_pg_end(const PgLargeDev &d, int cur, hipStream_t stream);
 
 // ---- sliding windows of a resident sequence (mvs_seq_refine_windows) -------------------------
 // seq_link_kernel chains the inlier matches of consecutive pairs into tracks (every keypoint gets at most one successor and
@@ -449,6 +455,33 @@ void launch_lag_table_set(LagDev *table, int lag, const LagDev &entry, hipStream
 void launch_vo_odo_begin(const VoDev &d, const OdoDev &o, hipStream_t stream);
 void launch_vo_queue(const VoDev &d, const OdoDev &o, int f, hipStream_t stream);
 void launch_vo_map_init(const VoDev &d, const OdoDev &o, int f, hipStream_t stream);
+
+// ---- the pose graph of a resident sequence (seq_graph.hip) -------------------------------------
+// Candidate slot (d, k), d = 1 .. max_lag, k < n_frames - d, sits at seq_graph_slot_off(n_frames, d) + k: ascending (d, k).
+__host__ __device__ constexpr int seq_graph_slot_off(int n_frames, int d) { return (d - 1) * n_frames - d * (d - 1) / 2; }
+struct SeqGraphDev {
+    int n_frames, max_lag, n_slots;
+    int min_points;
+    double max_error;
+    int chain_on;                      // both chain sigmas > 0
+    double chain_var[2];               // sigma^2: rotation, translation
+    // resident state of the sequence
+    const LagDev *lags;                // [max_lag + 1] device table of mvs_seq_run_lags, entry 0 unused
+    const double *traj_R, *traj_t;     // SeqChainDev's outputs
+    // per slot (seq_graph_edges_kernel); pose and cov are written for kept slots only
+    int32_t *slot_keep, *slot_kind;    // [n_slots]
+    double *slot_scale;                // [n_slots]
+    double *slot_pose;                 // [n_slots][12]
+    double *slot_cov;                  // [n_slots][36]
+    // the graph (seq_graph_compact_kernel): E = *n_edges dense entries in slot order
+    int32_t *n_edges;                  // [1]
+    int32_t *edge_src, *edge_dst, *edge_lag, *edge_kind;   // [n_slots]
+    double *edge_scale;                // [n_slots]
+    double *edge_pose;                 // [n_slots][12]
+    double *edge_cov;                  // [n_slots][36]
+    double *node_pose;                 // [n_frames][12]
+};
+void launch_seq_graph(const SeqGraphDev &g, hipStream_t stream);
 
 // ---- VisualFeature::extract (row f3): ORB-style extraction for a batch of equally sized images ----------------
 constexpr int kOrbMaxLevels = 16;

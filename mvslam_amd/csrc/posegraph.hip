@@ -10,11 +10,12 @@
 //   every entry of the dense lower triangle of H in LDS (at most 96 * 97 / 2 doubles = 37 KB) is summed by ONE thread over
 //   the edges in edge order -- no atomics, no partial-sum tree whose shape depends on the launch.  Cholesky and the two
 //   triangular solves run on that triangle in LDS.
-//   17 <= N <= 4096 (the pg_* kernels behind launch_pg_iteration): LM driven from the host, one synchronisation per LM
+//   17 <= N <= 4096 (the pg_* kernels behind launch_pg_begin / _cg / _end): LM driven from the host, one synchronisation per LM
 //   iteration; H is never formed.  One thread per edge linearises, one thread per node gathers its incident edges (a CSR
 //   list in edge order) into the diagonal block and the gradient, and a block-Jacobi preconditioned conjugate gradient
-//   solves (H + lambda I) x = -g with H p = edge kernel + the same gather.  Every CG iteration of the budget is enqueued
-//   up front; a status word on the device makes the ones behind convergence leave at once (DESIGN.md 4.7.3's pattern).
+//   solves (H + lambda I) x = -g with H p = edge kernel + the same gather.  The CG iterations of the budget are enqueued
+//   up front (all of them, or chunk by chunk with a status read in between: launch_pg_begin / _cg / _end); a status word on
+//   the device makes the ones behind convergence leave at once (DESIGN.md 4.7.3's pattern).
 // The LM rule is refine_kernel's, restated: lambda is ADDED to the diagonal, a candidate is accepted when its cost is not
 // above the current one, lambda /= factor on acceptance and *= factor on rejection, stop when the decrease (or, for a
 // rejected candidate that did solve, the increase) of the error is within abs_tol or rel_tol * error, or lambda passes
@@ -866,12 +867,19 @@ void launch_pg_prep(const PgLargeDev &d, hipStream_t stream)
     hipLaunchKernelGGL(pg_prep_kernel, dim3(eb > 0 ? eb : 1), dim3(kPgThreads), 0, stream, d);
 }
 
-void launch_pg_iteration(const PgLargeDev &d, int cur, double lam, int cg_max, bool first, hipStream_t stream)
+namespace {
+dim3 pg_edge_blocks(const PgLargeDev &d)
 {
-    const dim3 eb((d.n_edges + kPgThreads - 1) / kPgThreads > 0 ? (d.n_edges + kPgThreads - 1) / kPgThreads : 1);
+    const int eb = (d.n_edges + kPgThreads - 1) / kPgThreads;
+    return dim3(eb > 0 ? eb : 1);
+}
+}  // namespace
+
+void launch_pg_begin(const PgLargeDev &d, int cur, double lam, bool first, hipStream_t stream)
+{
+    const dim3 eb = pg_edge_blocks(d);
     const dim3 nb((d.n_nodes + 63) / 64);
     const double *ps = d.pose[cur];
-    double *pn = d.pose[cur ^ 1];
     if (first) {
         hipLaunchKernelGGL(pg_edge_kernel<false>, eb, dim3(kPgThreads), 0, stream, d, ps);
         hipLaunchKernelGGL(pg_cost_reduce_kernel, dim3(1), dim3(kPgThreads), 0, stream, d, ps, &d.state->cost0);
@@ -879,11 +887,25 @@ void launch_pg_iteration(const PgLargeDev &d, int cur, double lam, int cg_max, b
     hipLaunchKernelGGL(pg_edge_kernel<true>, eb, dim3(kPgThreads), 0, stream, d, ps);
     hipLaunchKernelGGL(pg_gather_kernel, nb, dim3(64), 0, stream, d, ps);
     hipLaunchKernelGGL(pg_cg_init_kernel, dim3(1), dim3(kPgThreads), 0, stream, d, lam);
-    for (int c = 0; c < cg_max; ++c) {
+}
+
+void launch_pg_cg(const PgLargeDev &d, double lam, int n, hipStream_t stream)
+{
+    const dim3 eb = pg_edge_blocks(d);
+    const dim3 nb((d.n_nodes + 63) / 64);
+    for (int c = 0; c < n; ++c) {
         hipLaunchKernelGGL(pg_edge_mv_kernel, eb, dim3(kPgThreads), 0, stream, d);
         hipLaunchKernelGGL(pg_node_mv_kernel, nb, dim3(64), 0, stream, d, lam);
         hipLaunchKernelGGL(pg_cg_step_kernel, dim3(1), dim3(kPgThreads), 0, stream, d);
     }
+}
+
+void launch_pg_end(const PgLargeDev &d, int cur, hipStream_t stream)
+{
+    const dim3 eb = pg_edge_blocks(d);
+    const dim3 nb((d.n_nodes + 63) / 64);
+    const double *ps = d.pose[cur];
+    double *pn = d.pose[cur ^ 1];
     hipLaunchKernelGGL(pg_update_kernel, nb, dim3(64), 0, stream, d, ps, pn);
     hipLaunchKernelGGL(pg_edge_kernel<false>, eb, dim3(kPgThreads), 0, stream, d, pn);
     hipLaunchKernelGGL(pg_cost_reduce_kernel, dim3(1), dim3(kPgThreads), 0, stream, d, pn, &d.state->cand);
