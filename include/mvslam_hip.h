@@ -460,7 +460,10 @@ mvs_status mvs_seq_sync(mvs_seq *s);
 mvs_status mvs_seq_time(mvs_seq *s, const mvs_params *two_view, const mvs_pnp_params *pnp, int warmup, int steps,
                         float *ms_total);
 /* per-stage HIP-event timing of the sequence step (the kernels' own stream): ms_stage[4] = summed ms over `steps`
- * instrumented passes of {pair pipeline, join, pnp_solve, scale propagation} */
+ * instrumented passes of {pair pipeline, join, pnp_solve, scale propagation}.  Every pass is an mvs_seq_run with these
+ * parameters: afterwards the pairs, tracks and trajectory are the last pass's and the sequence counts as run, and whatever
+ * was derived from an earlier run (windows, tracking, refined pairs as a tracking start, lags, odometry, pose graph) is
+ * stale, exactly as after mvs_seq_run */
 mvs_status mvs_seq_time_stages(mvs_seq *s, const mvs_params *two_view, const mvs_pnp_params *pnp, int steps, float *ms_stage);
 /* pairs [first, first + count) of the n_frames - 1 pairs: same layout as mvs_batch_download */
 mvs_status mvs_seq_download_pairs(mvs_seq *s, int first, int count, mvs_pair_result *results, mvs_match *matches,

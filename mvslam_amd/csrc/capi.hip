@@ -1,163 +1,22 @@
-// capi.hip -- host side of libmvslam_hip.so: contexts, resident batches, the C ABI of include/mvslam_hip.h.
-// No CPU fallback exists anywhere in this file: every entry point ends in a HIP kernel launch.
+// capi.hip -- host side of libmvslam_hip.so: contexts, resident batches, the C ABI of include/mvslam_hip.h.  Extraction is
+// in capi_orb.hip, the mvs_debug_* hooks of the diagnostics library in capi_debug.hip; capi_internal.hpp holds what they share.
+// No CPU fallback exists anywhere in these files: every entry point ends in a HIP kernel launch.
 #include <dlfcn.h>
-#include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <memory>
 #include <string>
 #include <type_traits>
 #include <vector>
 
-#include "kernels.hpp"
+#include "capi_internal.hpp"
 
-using namespace mvs;
-
-// ---- device memory: every block has one owner, whose destructor frees it ---------------------------------------------
-struct HipFree {
-    void operator()(void *p) const { (void)hipFree(p); }
-};
-using DevPtr = std::unique_ptr<void, HipFree>;
-// the blocks of a batch, a sequence or a probe's temporaries, allocated group by group (DevGroup)
-using DevBlocks = std::vector<DevPtr>;
-// one grow-only workspace of a context (ws_grow)
-struct DevWorkspace {
-    DevPtr p;
-    size_t bytes = 0;
-    template <typename T = char>
-    T *ptr() const { return static_cast<T *>(p.get()); }
-};
-
-struct mvs_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    // second queue of a large batch: its pairs go down the pipeline as two independent halves, one per stream, so that the
-    // latency-bound kernels of one half (list sort, exact solve of the few survivors, selection, ...) run under the
-    // throughput-bound kernels of the other (enqueue_pipeline).  Forked from / joined into `stream` with the two events.
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool half_batches = true;
-    double e5_confidence = 0.0;   // mvs_ctx_set_essential_confidence: 0 = every hypothesis of the five-point RANSAC runs
-    // n_run of the last single-shot five-point call: none yet, or that call failed before its RANSAC was enqueued (-1); in
-    // e5_single_run (0: the host returned before the RANSAC -- fewer than eight matches, so 0 -- or the word was saved from a
-    // scratch batch that has been replaced since); in scratch->e5_nrun[0] (1: the call enqueued its RANSAC)
-    int e5_single = -1;
-    int32_t e5_single_run = 0;
-    int cu_count = 256;   // hipDeviceAttributeMultiprocessorCount of `device` (mvs_ctx_create); MI355X: 256
-    std::string err;
-    mvs_batch *scratch = nullptr;  // batch of one pair backing the single-shot entry points
-    // workspaces, freed by their destructors
-    DevWorkspace uv;          // image points of a single-shot call: [max_kp][2] of camera 1, then the same of camera 2
-    DevWorkspace small;       // 128 doubles of staging (fundamental_kernel, five_point_kernel)
-    DevWorkspace single;      // gathered outputs of a single-shot call (one device-to-host copy)
-    DevWorkspace single_in;   // packed inputs of mvs_image_pair (one host-to-device copy)
-    DevWorkspace pnp;         // pnp_solve workspace
-    DevWorkspace ref;         // sfm_refine / pnp_refine workspace
-    DevWorkspace win;         // mvs_ba_refine_windows workspace
-    DevWorkspace pg;          // mvs_pose_graph_optimize workspace
-    DevWorkspace orb;         // extraction workspace: orb_graph points into it
-    int32_t *h_orb_ovf = nullptr;   // pinned: the extraction's overflow flag travels with the outputs (one stream wait per call)
-    bool orb_ready = false;
-    // the ~50 launches of one extraction, captured once per (batch shape, parameters, buffers) and replayed
-    hipGraphExec_t orb_graph = nullptr;
-    OrbDev orb_graph_key{};
-    bool orb_graph_valid = false;
-    // pinned staging arena of the single-shot entry points: small parameters and results travel through it with
-    // hipMemcpyAsync on the ctx stream (no synchronous pageable copies, no sync "so that a stack temporary may die")
-    char *h_pin = nullptr;
-    size_t h_pin_cap = 0, h_pin_off = 0;
-    bool pin_in_flight = false;   // an asynchronous copy may still be reading / writing the arena (set by pin_get, cleared
-                                  // by whoever synchronises the stream at the end of the call)
-};
-
-struct mvs_seq;
-
-struct mvs_batch {
-    mvs_ctx *ctx = nullptr;
-    BatchDev d{};
-    DevBlocks blocks;
-    double *uv1 = nullptr, *uv2 = nullptr;   // [n_pairs][max_kp][2] staging of mvs_batch_run_points (first use)
-    // the optional per-hypothesis tables of mvs_ransac_fundamental (d.hyp_count / d.hyp_residual during that call only)
-    int hyp_table_cap = 0;
-    int32_t *hyp_table_count = nullptr;
-    double *hyp_table_residual = nullptr;
-    // tables of the five-point RANSAC (essential5.hip), sized for the largest hypothesis count seen so far (first use)
-    int e5_cap = 0;
-    int32_t *e5_nroots = nullptr;   // [n_pairs][e5_cap]
-    int32_t *e5_count = nullptr;    // [n_pairs][e5_cap][10]
-    int32_t *e5_root = nullptr;     // [n_pairs] root index of the winner
-    int32_t *e5_nrun = nullptr;     // [n_pairs] hypotheses each pair ran: the checkpoint it stopped at, or all / none of them
-    int32_t *e5_cmax = nullptr;     // [n_pairs] largest count so far, between the rounds of a call with a confidence level
-    // the last five-point call on this batch (mvs_batch_download_hypotheses_run): its pairs and hypotheses
-    bool e5_ran = false;
-    int e5_last_n = 0, e5_last_H = 0;
-    hipEvent_t ev[8]{};
-    RefineDev refine{};     // allocated by the first mvs_batch_refine
-    bool refine_ran = false;
-    // pinned staging of the per-pair parameters derived on the host (K^-1, default indices): two slot sets used in turn,
-    // each guarded by an event recorded behind its copies, so an asynchronous upload waits for the copies of the upload
-    // before last at most -- never for the kernels or downloads queued on the stream in between
-    char *h_pin = nullptr;
-    hipEvent_t pin_ev[2]{};
-    bool pin_ev_live[2] = {false, false};
-    int pin_turn = 0;
-};
-
-struct mvs_seq {
-    mvs_ctx *ctx = nullptr;
-    mvs_batch *batch = nullptr;  // n_frames - 1 pairs viewing the frame arrays
-    int n_frames = 0, n_tracks = 0, stride = 0;
-    SeqJoinDev join{};
-    PnpDev pnp{};
-    SeqChainDev chain{};
-    RefineDev refit{};          // pnp_solve's refit over the inliers of every track (mvs_pnp_params.refit), allocated on demand
-    bool refit_on = false;
-    DevBlocks blocks;
-    bool ran = false;           // mvs_seq_run has filled the pairs, the tracks and the trajectory
-    // mvs_seq_refine_windows: link tables, the windows' problems and their results, resident until the next call
-    DevWorkspace win;
-    SeqWinDev wd{};             // n_windows = 0 until the first call
-    WinDev ws{};
-    // mvs_seq_track: every per-frame buffer of the tracking loop and one step's solver scratch, resident until the next call
-    DevWorkspace trk;
-    VoDev vo{};
-    bool track_ran = false;
-    bool refined_ran = false;   // mvs_seq_refine_pairs has refined the pairs of the LAST run (use_refined_init reads them)
-    // mvs_seq_run_lags: one batch per lag d >= 2 viewing the frame arrays (lag_batch[d], entries 0 and 1 stay null), the
-    // device table of what the state machine reads of every lag and the per-pair descriptor SSDs, resident until the next run
-    std::vector<mvs_batch *> lag_batch;
-    DevWorkspace lagws;         // LagDev[lag_cap + 1], then int32 ssd[lag_cap + 1][n_frames]
-    int lag_cap = 0;
-    std::vector<LagDev> lag_host;   // the table's host copy (the downloads read the ssd pointers from it)
-    int lags_ran = 0;           // lags 1 .. lags_ran are resident from one mvs_seq_run_lags since the last run
-    bool odo_ran = false;       // the resident tracking results are mvs_seq_odometry's
-    OdoDev odo{};
-    // mvs_seq_build_pose_graph: the candidate slots, the graph and the optimised nodes, resident until the next run
-    DevWorkspace graph;
-    SeqGraphDev gd{};
-    double *graph_opt_pose = nullptr;   // [n_frames][12] in `graph`
-    bool graph_built = false;   // the graph is that of the last run and its lags
-    bool graph_opt = false;     // mvs_seq_optimize_pose_graph has succeeded on it
-};
-
-#define HIP_TRY(ctx_, expr)                                                                    \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            if (ctx_)                                                                          \
-                (ctx_)->err = std::string(#expr) + ": " + hipGetErrorString(e_);               \
-            return MVS_ERR_HIP;                                                                \
-        }                                                                                      \
-    } while (0)
+using namespace mvs_host;
 
 // every wait for the ctx stream goes through here: once it has drained nothing reads or writes the arena any more
-static hipError_t sync_stream(mvs_ctx *ctx)
+hipError_t mvs_host::sync_stream(mvs_ctx *ctx)
 {
     const hipError_t e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess)
@@ -226,7 +85,36 @@ static mvs_status up_async(mvs_ctx *ctx, void *dst, const void *src, size_t byte
 constexpr double kRefitPointSigma = 1e-9, kRefitPoseSigma = 1e6;
 static RefineCfg to_cfg(const mvs_refine_params &p, int n_frames);
 
-static RunParams to_run(const mvs_params &p)
+// the refit's parameters: the defaults with no prior on the pose; its configuration as a one-frame problem
+static mvs_refine_params refit_params()
+{
+    mvs_refine_params rp;
+    mvs_refine_params_default(&rp);
+    rp.pose_sigma[0] = rp.pose_sigma[1] = kRefitPoseSigma;
+    return rp;
+}
+static RefineCfg refit_cfg() { return to_cfg(refit_params(), 1); }
+
+static bool pnp_params_ok(const mvs_pnp_params *p)
+{
+    return p && p->num_hypotheses >= 1 && p->reproj_error > 0.0 &&   // pnp-solve.cpp:13,22-23 (assert)
+           (p->sampler == MVS_SAMPLER_IDENTITY || p->sampler == MVS_SAMPLER_PHILOX);
+}
+
+// record groups of a PnP RANSAC: one per 256 hypotheses (pnp.hip)
+static int pnp_groups(const mvs_pnp_params &p) { return (p.num_hypotheses + 255) / 256; }
+
+// the parameters' share of a PnP problem; max_groups is the size of the caller's records and is set where they are laid out
+static void set_pnp_params(PnpDev &d, const mvs_pnp_params &p)
+{
+    d.num_hypotheses = p.num_hypotheses;
+    d.sampler = p.sampler;
+    d.min_inliers = p.min_inliers;
+    d.seed = p.seed;
+    d.thr2 = p.reproj_error * p.reproj_error;
+}
+
+RunParams mvs_host::to_run(const mvs_params &p)
 {
     RunParams r;
     r.ratio = p.ratio;
@@ -239,71 +127,9 @@ static RunParams to_run(const mvs_params &p)
     return r;
 }
 
-// PinholeCamera caches K.inverse() (vision/camera.cpp:16): fixed-size 3x3 cofactor inverse,
-// inv(r, c) = cofactor(c, r) * (1 / det), det expanded along the first column.
-static void mat3_inverse(const double *K, double *inv)
-{
-    auto m = [&](int r, int c) { return K[(r % 3) * 3 + (c % 3)]; };
-    auto cof = [&](int i, int j) { return m(i + 1, j + 1) * m(i + 2, j + 2) - m(i + 1, j + 2) * m(i + 2, j + 1); };
-    const double c00 = cof(0, 0), c10 = cof(1, 0), c20 = cof(2, 0);
-    const double det = (c00 * K[0] + c10 * K[3]) + c20 * K[6];
-    const double invdet = 1.0 / det;
-    inv[0] = c00 * invdet;       inv[1] = c10 * invdet;       inv[2] = c20 * invdet;
-    inv[3] = cof(0, 1) * invdet; inv[4] = cof(1, 1) * invdet; inv[5] = cof(2, 1) * invdet;
-    inv[6] = cof(0, 2) * invdet; inv[7] = cof(1, 2) * invdet; inv[8] = cof(2, 2) * invdet;
-}
-
-static bool affine_K(const double *K) { return K[6] == 0.0 && K[7] == 0.0 && K[8] == 1.0 && K[0] != 0.0 && K[4] != 0.0; }
-
-// One all-or-nothing group of device blocks for an owner.  add() allocates max(count, 1) elements for a destination
-// pointer (nothing more after a failure); commit() then either reports the failure -- the partial blocks are freed, no
-// pointer has changed -- or points every destination at its new block, hands the blocks to the owner and only then frees
-// the owner's blocks they supersede (the stream must be idle for that).
-class DevGroup {
-public:
-    DevGroup(mvs_ctx *ctx, DevBlocks &owner) : ctx_(ctx), owner_(owner) {}
-    template <typename T>
-    DevGroup &add(T *&dst, size_t count)
-    {
-        void *p = nullptr;
-        if (e_ == hipSuccess && (e_ = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T))) == hipSuccess)
-            parts_.emplace_back(DevPtr(p), [&dst](void *q) -> const void * {
-                const void *old = dst;
-                dst = static_cast<T *>(q);
-                return old;
-            });
-        return *this;
-    }
-    mvs_status commit()
-    {
-        if (e_ != hipSuccess) {
-            ctx_->err = std::string("hipMalloc: ") + hipGetErrorString(e_);
-            return MVS_ERR_HIP;
-        }
-        std::vector<const void *> old;
-        for (auto &part : parts_) {
-            old.push_back(part.second(part.first.get()));
-            owner_.push_back(std::move(part.first));
-        }
-        for (const void *o : old)
-            for (auto it = owner_.begin(); o && it != owner_.end(); ++it)
-                if (it->get() == o) {
-                    owner_.erase(it);
-                    break;
-                }
-        return MVS_OK;
-    }
-
-private:
-    mvs_ctx *ctx_;
-    DevBlocks &owner_;
-    hipError_t e_ = hipSuccess;
-    std::vector<std::pair<DevPtr, std::function<const void *(void *)>>> parts_;
-};
-
 // Grows a context workspace to at least `bytes` (first size: max(bytes, floor)).  Growing waits for the ctx stream, frees
 // the old block and marks the workspace empty before it allocates: a failed growth leaves no block behind.
-static mvs_status ws_grow(mvs_ctx *ctx, DevWorkspace &w, size_t bytes, size_t floor = 0)
+mvs_status mvs_host::ws_grow(mvs_ctx *ctx, DevWorkspace &w, size_t bytes, size_t floor)
 {
     if (w.bytes >= bytes)
         return MVS_OK;
@@ -318,7 +144,7 @@ static mvs_status ws_grow(mvs_ctx *ctx, DevWorkspace &w, size_t bytes, size_t fl
 }
 
 // the captured extraction graph points into the extraction workspace: dropped before that block is freed or replaced
-static void drop_orb_graph(mvs_ctx *ctx)
+void mvs_host::drop_orb_graph(mvs_ctx *ctx)
 {
     if (ctx->orb_graph)
         (void)hipGraphExecDestroy(ctx->orb_graph);
@@ -326,24 +152,10 @@ static void drop_orb_graph(mvs_ctx *ctx)
     ctx->orb_graph_valid = false;
 }
 
-// Layout of a workspace as consecutive parts: take() returns the offset of the next part, rounded up to `align` (a power of
-// two); end is where the last part ends, total() the same rounded up.
-struct Carve {
-    size_t align, end = 0;
-    size_t up(size_t x) const { return (x + align - 1) & ~(align - 1); }
-    size_t take(size_t bytes)
-    {
-        const size_t o = up(end);
-        end = o + bytes;
-        return o;
-    }
-    size_t total() const { return up(end); }
-};
-
 // per-hypothesis buffers of the RANSAC stage, sized for the largest hypothesis count seen so far: one group, so a failed
 // allocation leaves the batch as it was; the superseded blocks are freed at once: 77 B x hypotheses x pairs is 2 GB at the
 // bench size.
-static mvs_status ensure_groups(mvs_batch *b, int num_hypotheses)
+mvs_status mvs_host::ensure_groups(mvs_batch *b, int num_hypotheses)
 {
     const int G = (num_hypotheses + kHypPerBlock - 1) / kHypPerBlock;
     if (G <= b->d.max_groups)
@@ -469,416 +281,9 @@ static mvs_status alloc_refine(mvs_ctx *ctx, DevBlocks &owner, RefineDev &d, int
     return MVS_OK;
 }
 
-#ifdef MVS_DEBUG_HOOKS
-// generic "n inputs -> m outputs" staging for the two probes below
-template <typename Launch>
-static int probe_io(mvs_ctx *ctx, const void *const *in, const size_t *in_bytes, int n_in, void *const *outp, const size_t *out_bytes,
-                    int n_out, Launch launch)
-{
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    unsigned char *d[8] = {};
-    DevBlocks tmp;
-    DevGroup g(ctx, tmp);
-    for (int k = 0; k < n_in + n_out; ++k)
-        g.add(d[k], k < n_in ? in_bytes[k] : out_bytes[k - n_in]);
-    const mvs_status st = g.commit();
-    if (st != MVS_OK)
-        return st;
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < n_in && e == hipSuccess; ++k)
-        e = hipMemcpy(d[k], in[k], in_bytes[k], hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        launch(d);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-        e = sync_stream(ctx);
-    for (int k = 0; k < n_out && e == hipSuccess; ++k)
-        e = hipMemcpy(outp[k], d[n_in + k], out_bytes[k], hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        ctx->err = std::string("probe: ") + hipGetErrorString(e);
-        return MVS_ERR_HIP;
-    }
-    return MVS_OK;
-}
-
-#endif
-
 extern "C" {
 
 int mvs_abi_version(void) { return MVS_ABI_VERSION; }
-
-#ifdef MVS_DEBUG_HOOKS
-// Diagnostics, compiled ONLY into libmvslam_hip_dbg.so (make dbg; tests/ and tools/ load that library explicitly).  The
-// product library has neither symbol: a process-global kernel-variant switch is not something a caller of the
-// reference's interface should be able to reach.
-// diagnostics only (not in the public header): bitwise comparison of the unscaled sqrt / div device sequences with
-// the compiler's IEEE ones on host-supplied operands.  counts[4] = {sqrt mismatches, div mismatches, sqrt checked,
-// div checked}
-int mvs_debug_fastmath_check(mvs_ctx *ctx, const double *x, const double *y, int n, unsigned long long counts[4])
-{
-    if (!ctx || n < 1)
-        return MVS_ERR_INVALID_ARG;
-    double *dx = nullptr, *dy = nullptr;
-    unsigned long long *dc = nullptr;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    DevBlocks tmp;
-    const mvs_status st = DevGroup(ctx, tmp).add(dx, n).add(dy, n).add(dc, 4).commit();
-    if (st != MVS_OK)
-        return st;
-    HIP_TRY(ctx, hipMemcpyAsync(dx, x, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(dy, y, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(dc, 0, 32, ctx->stream));
-    launch_fastmath_check(dx, dy, n, dc, ctx->stream);
-    HIP_TRY(ctx, hipMemcpyAsync(counts, dc, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, sync_stream(ctx));
-    return MVS_OK;
-}
-
-// diagnostics only: one guarded Jacobi pair step per row pair against the IEEE one (pairstep_check_kernel).
-// rows: n x 6 doubles.  counts[4] = {steps that differ, steps compared, decisions that differ, bits of the largest
-// |1 - gamma * 2 h| seen (accuracy of the reciprocal estimate the seeded divisions start from)}
-int mvs_debug_pairstep_check(mvs_ctx *ctx, const double *rows, int n, unsigned long long counts[4])
-{
-    if (!ctx || n < 1)
-        return MVS_ERR_INVALID_ARG;
-    double *dr = nullptr;
-    unsigned long long *dc = nullptr;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    DevBlocks tmp;
-    const mvs_status st = DevGroup(ctx, tmp).add(dr, (size_t)n * 6).add(dc, 4).commit();
-    if (st != MVS_OK)
-        return st;
-    hipError_t e = hipMemcpyAsync(dr, rows, (size_t)n * 48, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(dc, 0, 32, ctx->stream);
-    if (e == hipSuccess) {
-        launch_pairstep_check(dr, n, dc, ctx->stream);
-        e = hipMemcpyAsync(counts, dc, 32, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    if (e == hipSuccess)
-        e = sync_stream(ctx);
-    return e == hipSuccess ? MVS_OK : MVS_ERR_HIP;
-}
-
-// diagnostics only (not in the public header): the counting variant of the pre-screened stage (kernels.hpp: set_count_dense)
-int mvs_debug_set_count_dense(int v)
-{
-    set_count_dense(v);
-    return MVS_OK;
-}
-
-// one 32 x 32 x 32 bf16 tile through the counting kernels' two MFMAs: a, b = [32][32] bf16 bit patterns on the host,
-// out = [32][32] binary32 (point x hypothesis)
-int mvs_debug_mfma_probe(mvs_ctx *ctx, const uint16_t *a, const uint16_t *b, float *out)
-{
-    if (!ctx || !a || !b || !out)
-        return MVS_ERR_INVALID_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint16_t *da = nullptr, *db = nullptr;
-    float *dout = nullptr;
-    DevBlocks tmp;
-    const mvs_status st = DevGroup(ctx, tmp).add(da, 1024).add(db, 1024).add(dout, 1024).commit();
-    if (st != MVS_OK)
-        return st;
-    HIP_TRY(ctx, hipMemcpy(da, a, 1024 * sizeof(uint16_t), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(db, b, 1024 * sizeof(uint16_t), hipMemcpyHostToDevice));
-    launch_mfma_probe(da, db, dout, ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, sync_stream(ctx));
-    HIP_TRY(ctx, hipMemcpy(out, dout, 1024 * sizeof(float), hipMemcpyDeviceToHost));
-    return MVS_OK;
-}
-
-int mvs_debug_set_split_min_pairs(int v)
-{
-    set_split_min_pairs(v);
-    return MVS_OK;
-}
-
-int mvs_debug_set_match_mfma(int v)
-{
-    set_match_mfma(v);
-    return MVS_OK;
-}
-
-int mvs_debug_set_prescreen_force(int m)
-{
-    set_prescreen_force(m);
-    return MVS_OK;
-}
-
-// wavefronts of pair_prepare / ransac_prescreen that left the relaxed normalisation for the guarded one (its range test
-// fired) since the last reset; the caller has synchronised the launches it asks about.  reset != 0: zero afterwards
-int mvs_debug_prescreen_fallback_waves(mvs_ctx *ctx, int reset, unsigned int *out)
-{
-    if (!ctx || !out)
-        return MVS_ERR_INVALID_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, prescreen_fallback_waves(out, reset != 0));
-    return MVS_OK;
-}
-
-// records of the RANSAC stage as the last run left them: rec_out n_hyp x 10 (F, counting threshold), state bytes, counts;
-// info[0..3] = {mode of the pair, bound of the pair, work-list entries 0, work-list entries 1}
-int mvs_debug_read_hyp_rec(mvs_batch *b, int pair, int n_hyp, double *rec_out, unsigned char *state_out, int32_t *cnt_out,
-                           int32_t *info)
-{
-    if (!b || !b->d.hyp_F || pair < 0 || pair >= b->d.n_pairs || n_hyp < 1 || n_hyp > b->d.max_groups * kHypPerBlock)
-        return MVS_ERR_INVALID_ARG;
-    const size_t Hp = (size_t)b->d.max_groups * kHypPerBlock;
-    HIP_TRY(b->ctx, sync_stream(b->ctx));
-    std::vector<unsigned char> stv(n_hyp);
-    HIP_TRY(b->ctx, hipMemcpy(stv.data(), b->d.hyp_okf + (size_t)pair * Hp, (size_t)n_hyp, hipMemcpyDeviceToHost));
-    if (rec_out) {
-        HIP_TRY(b->ctx, hipMemcpy(rec_out, b->d.hyp_F + (size_t)pair * Hp * kHypRec, (size_t)n_hyp * kHypRec * sizeof(double),
-                                  hipMemcpyDeviceToHost));
-        // a pair in mode 1 keeps its APPROXIMATE records in the 48-byte single-precision array: they are returned in the
-        // first 48 bytes of the hypothesis' 80-byte slot (the layout the records had when they shared one array)
-        int32_t pmode = 0;
-        HIP_TRY(b->ctx, hipMemcpy(&pmode, b->d.mode + pair, sizeof(int32_t), hipMemcpyDeviceToHost));
-        if (pmode == 1) {
-            std::vector<float> r32((size_t)n_hyp * kHypRec32);
-            HIP_TRY(b->ctx, hipMemcpy(r32.data(), b->d.hyp_r32 + (size_t)pair * Hp * kHypRec32, r32.size() * sizeof(float),
-                                      hipMemcpyDeviceToHost));
-            for (int h = 0; h < n_hyp; ++h)
-                if (stv[h] == 1)
-                    std::memcpy(rec_out + (size_t)h * kHypRec, r32.data() + (size_t)h * kHypRec32, kHypRec32 * sizeof(float));
-        }
-    }
-    if (state_out)
-        std::memcpy(state_out, stv.data(), (size_t)n_hyp);
-    if (cnt_out)
-        HIP_TRY(b->ctx, hipMemcpy(cnt_out, b->d.hyp_cnt + (size_t)pair * Hp, (size_t)n_hyp * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (info) {
-        uint32_t xc[2] = {0, 0};
-        HIP_TRY(b->ctx, hipMemcpy(&info[0], b->d.mode + pair, sizeof(int32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(b->ctx, hipMemcpy(&info[1], b->d.bound + pair, sizeof(int32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(b->ctx, hipMemcpy(xc, b->d.xcount, sizeof(xc), hipMemcpyDeviceToHost));
-        info[2] = (int32_t)xc[0];
-        info[3] = (int32_t)xc[1];
-    }
-    return MVS_OK;
-}
-
-// the pre-screen alone over pairs [0, n_active) of a batch that has been run (matches and points resident): pair_prepare +
-// ransac_prescreen, every pair forced into pre-screened mode `mode` (1: single-precision records, 2: double precision),
-// nothing solved exactly afterwards -- the records then hold F~ and the widened thresholds (state 1), or wait for the exact
-// solve (state 2): tests compare them with the oracle's exact F
-int mvs_debug_prescreen_only(mvs_batch *b, const mvs_params *params, int n_active, int mode)
-{
-    if (!b || !params || n_active < 1 || n_active > b->d.n_pairs || (mode != 1 && mode != 2))
-        return MVS_ERR_INVALID_ARG;
-    mvs_status st = ensure_groups(b, params->num_hypotheses);
-    if (st != MVS_OK)
-        return st;
-    launch_prescreen_only(b->d, to_run(*params), n_active, mode, b->ctx->stream);
-    HIP_TRY(b->ctx, hipGetLastError());
-    HIP_TRY(b->ctx, sync_stream(b->ctx));
-    return MVS_OK;
-}
-
-// full-population audit (kernels.hip: audit_kernel).  phase 0: pair_prepare + ransac_prescreen run here (the probe decides every
-// pair's mode), then every record is checked against the exact solve of its sample; phase 1: the caller has just run the
-// batch with the same parameters, the stage's decisions are checked.  counters[16] as documented at audit_kernel; maxc /
-// bound / mode: [n_active] (largest exact count, the stage's bound, the pair's mode), each may be null.
-int mvs_debug_audit(mvs_batch *b, const mvs_params *params, int n_active, int phase, unsigned long long counters[16],
-                    int32_t *maxc, int32_t *bound, int32_t *mode)
-{
-    if (!b || !params || !counters || n_active < 1 || n_active > b->d.n_pairs || (phase != 0 && phase != 1))
-        return MVS_ERR_INVALID_ARG;
-    mvs_ctx *ctx = b->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    mvs_status st = ensure_groups(b, params->num_hypotheses);
-    if (st != MVS_OK)
-        return st;
-    const RunParams rp = to_run(*params);
-    unsigned long long *dc = nullptr;
-    int32_t *dm = nullptr;
-    DevBlocks tmp;
-    if ((st = DevGroup(ctx, tmp).add(dc, 16).add(dm, n_active).commit()) != MVS_OK)
-        return st;
-    hipError_t e = hipMemsetAsync(dc, 0, 16 * sizeof(unsigned long long), ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(dm, 0xff, (size_t)n_active * sizeof(int32_t), ctx->stream);
-    if (e == hipSuccess && phase == 0)
-        launch_prescreen_only(b->d, rp, n_active, -1, ctx->stream);
-    if (e == hipSuccess)
-        e = launch_audit(b->d, rp, n_active, phase, dc, dm, ctx->stream);
-    if (e == hipSuccess)
-        e = sync_stream(ctx);
-    if (e == hipSuccess)
-        e = hipMemcpy(counters, dc, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && maxc)
-        e = hipMemcpy(maxc, dm, (size_t)n_active * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && bound)
-        e = hipMemcpy(bound, b->d.bound, (size_t)n_active * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && mode)
-        e = hipMemcpy(mode, b->d.mode, (size_t)n_active * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        ctx->err = std::string("mvs_debug_audit: ") + hipGetErrorString(e);
-        return MVS_ERR_HIP;
-    }
-    return MVS_OK;
-}
-
-// The same audit over the device state of ANOTHER library instance's batch (mvs_batch_device_state of libmvslam_hip.so, loaded
-// in the same process): the product binary ran the stage, this library only replays every hypothesis exactly and compares.
-// phase 1: the stage's decisions; phase 2: the records as the product's pre-screen wrote them and the stage left them (every
-// record still in state kPsApprox: (B) on every match, U >= c_J >= L) -- phase 0's checks WITHOUT re-running the pre-screen.
-int mvs_debug_audit_state(mvs_ctx *ctx, const void *state, size_t state_bytes, const mvs_params *params, int n_active, int phase,
-                          unsigned long long counters[16], int32_t *maxc, int32_t *bound, int32_t *mode)
-{
-    struct Blob {
-        uint64_t bytes, abi;
-        BatchDev d;
-    };
-    if (!ctx || !state || !params || !counters || (phase != 1 && phase != 2))
-        return MVS_ERR_INVALID_ARG;
-    Blob blob;
-    if (state_bytes != sizeof(Blob))
-        return MVS_ERR_INVALID_ARG;
-    std::memcpy(&blob, state, sizeof(Blob));
-    if (blob.bytes != sizeof(Blob) || blob.abi != (uint64_t)MVS_ABI_VERSION)
-        return MVS_ERR_INVALID_ARG;   // not the same build
-    const BatchDev &d = blob.d;
-    if (n_active < 1 || n_active > d.n_pairs || (params->num_hypotheses + kHypPerBlock - 1) / kHypPerBlock > d.max_groups)
-        return MVS_ERR_INVALID_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const RunParams rp = to_run(*params);
-    unsigned long long *dc = nullptr;
-    int32_t *dm = nullptr;
-    DevBlocks tmp;
-    const mvs_status st = DevGroup(ctx, tmp).add(dc, 16).add(dm, n_active).commit();
-    if (st != MVS_OK)
-        return st;
-    hipError_t e = hipMemsetAsync(dc, 0, 16 * sizeof(unsigned long long), ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(dm, 0xff, (size_t)n_active * sizeof(int32_t), ctx->stream);
-    if (e == hipSuccess)
-        e = launch_audit(d, rp, n_active, phase == 2 ? 0 : 1, dc, dm, ctx->stream);
-    if (e == hipSuccess)
-        e = sync_stream(ctx);
-    if (e == hipSuccess)
-        e = hipMemcpy(counters, dc, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && maxc)
-        e = hipMemcpy(maxc, dm, (size_t)n_active * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && bound)
-        e = hipMemcpy(bound, d.bound, (size_t)n_active * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && mode)
-        e = hipMemcpy(mode, d.mode, (size_t)n_active * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        ctx->err = std::string("mvs_debug_audit_state: ") + hipGetErrorString(e);
-        return MVS_ERR_HIP;
-    }
-    return MVS_OK;
-}
-
-// overwrite the ideal-camera points of one pair: pts4 = m x (x1, y1, x2, y2) doubles (the matcher's output is bypassed)
-int mvs_debug_set_points(mvs_batch *b, int pair, int m, const double *pts4)
-{
-    if (!b || !pts4 || pair < 0 || pair >= b->d.n_pairs || m < 0 || m > b->d.max_kp)
-        return MVS_ERR_INVALID_ARG;
-    mvs_ctx *ctx = b->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, sync_stream(ctx));
-    HIP_TRY(ctx, hipMemcpy(b->d.pts + (size_t)pair * b->d.max_kp * 4, pts4, (size_t)m * 4 * sizeof(double), hipMemcpyHostToDevice));
-    const int32_t mm = m;
-    HIP_TRY(ctx, hipMemcpy(b->d.M + pair, &mm, sizeof(mm), hipMemcpyHostToDevice));
-    return MVS_OK;
-}
-
-// read the ideal-camera points of one pair as the kernels see them: pts4 = capacity x 4 doubles, *m = the pair's match count
-int mvs_debug_get_points(mvs_batch *b, int pair, int *m, double *pts4)
-{
-    if (!b || !pts4 || !m || pair < 0 || pair >= b->d.n_pairs)
-        return MVS_ERR_INVALID_ARG;
-    mvs_ctx *ctx = b->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, sync_stream(ctx));
-    int32_t mm = 0;
-    HIP_TRY(ctx, hipMemcpy(&mm, b->d.M + pair, sizeof(mm), hipMemcpyDeviceToHost));
-    mm = std::min(mm, b->d.max_kp);
-    HIP_TRY(ctx, hipMemcpy(pts4, b->d.pts + (size_t)pair * b->d.max_kp * 4, (size_t)mm * 4 * sizeof(double), hipMemcpyDeviceToHost));
-    *m = mm;
-    return MVS_OK;
-}
-
-// pre-screen (every pair forced into mode pmode: 1 single-, 2 double-precision records) + the counting launches alone, with
-// only hypothesis keep[p] of pair p left valid (keep may be null).  dense: 0 = ransac_count32 in one launch, 1 = the product's
-// pilot + matrix-core dense phase + finish.  Out, each [n_active] and optional: the kept hypothesis' recorded count (U), the
-// pair's bound (best lower bound), the points the dense phase covered.
-int mvs_debug_count_only(mvs_batch *b, const mvs_params *params, int n_active, int pmode, int dense, const int32_t *keep,
-                         int32_t *cnt_out, int32_t *bound_out, int32_t *n1_out)
-{
-    if (!b || !params || n_active < 1 || n_active > b->d.n_pairs || (pmode != 1 && pmode != 2) || dense < 0 || dense > 2)
-        return MVS_ERR_INVALID_ARG;
-    mvs_ctx *ctx = b->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    mvs_status st = ensure_groups(b, params->num_hypotheses);
-    if (st != MVS_OK)
-        return st;
-    const size_t Hp = (size_t)b->d.max_groups * kHypPerBlock;
-    int32_t *dk = nullptr;
-    DevBlocks tmp;
-    if (keep) {
-        for (int p = 0; p < n_active; ++p)
-            if (keep[p] >= (int32_t)Hp)
-                return MVS_ERR_INVALID_ARG;
-        if ((st = DevGroup(ctx, tmp).add(dk, n_active).commit()) != MVS_OK)
-            return st;
-        HIP_TRY(ctx, hipMemcpy(dk, keep, (size_t)n_active * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(ctx, hipMemsetAsync(b->d.dense_n1, 0, (size_t)n_active * sizeof(int32_t), ctx->stream));
-    launch_count_only(b->d, to_run(*params), n_active, pmode, dense, dk, ctx->stream);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess)
-        e = sync_stream(ctx);
-    for (int p = 0; p < n_active && e == hipSuccess; ++p) {
-        if (cnt_out && keep && keep[p] >= 0)
-            e = hipMemcpy(cnt_out + p, b->d.hyp_cnt + (size_t)p * Hp + keep[p], sizeof(int32_t), hipMemcpyDeviceToHost);
-    }
-    if (e == hipSuccess && bound_out)
-        e = hipMemcpy(bound_out, b->d.bound, (size_t)n_active * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && n1_out)
-        e = hipMemcpy(n1_out, b->d.dense_n1, (size_t)n_active * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        ctx->err = std::string("mvs_debug_count_only: ") + hipGetErrorString(e);
-        return MVS_ERR_HIP;
-    }
-    return MVS_OK;
-}
-
-// the matrix-core counting's compare-free indicator on caller-supplied accumulator values (kernels.hip: indicator_probe_kernel)
-int mvs_debug_indicator_probe(mvs_ctx *ctx, const float *a, const float *tu, const float *tl, const float *T, int n, float *ind_u,
-                              float *ind_l, float *scale)
-{
-    if (!ctx || !a || !tu || !tl || !T || !ind_u || !ind_l || !scale || n < 1)
-        return MVS_ERR_INVALID_ARG;
-    const size_t nb = (size_t)n * sizeof(float);
-    const void *in[4] = {a, tu, tl, T};
-    const size_t ib[4] = {nb, nb, nb, nb};
-    void *out[3] = {ind_u, ind_l, scale};
-    const size_t ob[3] = {nb, nb, nb};
-    return probe_io(ctx, in, ib, 4, out, ob, 3, [&](unsigned char **d) {
-        launch_indicator_probe((const float *)d[0], (const float *)d[1], (const float *)d[2], (const float *)d[3], n, (float *)d[4],
-                               (float *)d[5], (float *)d[6], ctx->stream);
-    });
-}
-
-// de-normalisation + fused residual of both paths on caller-supplied (Fn, transforms, point) tuples: in n x 19, out n x 2
-int mvs_debug_rounding_probe(mvs_ctx *ctx, const double *in19, int n, double *out2)
-{
-    if (!ctx || !in19 || !out2 || n < 1)
-        return MVS_ERR_INVALID_ARG;
-    const void *in[1] = {in19};
-    const size_t ib[1] = {(size_t)n * 19 * sizeof(double)};
-    void *out[1] = {out2};
-    const size_t ob[1] = {(size_t)n * 2 * sizeof(double)};
-    return probe_io(ctx, in, ib, 1, out, ob, 1,
-                    [&](unsigned char **d) { launch_rounding_probe((const double *)d[0], n, (double *)d[1], ctx->stream); });
-}
-#endif  // MVS_DEBUG_HOOKS
 
 const char *mvs_status_str(mvs_status s)
 {
@@ -2598,9 +2003,7 @@ mvs_status mvs_seq_upload(mvs_seq *q, int first, int count, const uint8_t *desc,
 
 static mvs_status seq_prepare(mvs_seq *q, Estimator est, const mvs_params *tv, const mvs_pnp_params *pp)
 {
-    if (!q || !pp || pp->num_hypotheses < 1 || !(pp->reproj_error > 0.0))
-        return MVS_ERR_INVALID_ARG;
-    if (pp->sampler != MVS_SAMPLER_IDENTITY && pp->sampler != MVS_SAMPLER_PHILOX)
+    if (!q || !pnp_params_ok(pp))
         return MVS_ERR_INVALID_ARG;
     mvs_status st = check_params(tv);
     if (st != MVS_OK)
@@ -2608,43 +2011,43 @@ static mvs_status seq_prepare(mvs_seq *q, Estimator est, const mvs_params *tv, c
     HIP_TRY(q->ctx, hipSetDevice(q->ctx->device));
     if ((st = ensure_tables(q->batch, est, tv->num_hypotheses)) != MVS_OK)
         return st;
-    const int G = (pp->num_hypotheses + 255) / 256;
+    const int G = pnp_groups(*pp);
     if (G > q->pnp.max_groups) {
         HIP_TRY(q->ctx, sync_stream(q->ctx));   // the records it replaces are freed
         if ((st = DevGroup(q->ctx, q->blocks).add(q->pnp.rec, (size_t)q->n_tracks * G).commit()) != MVS_OK)
             return st;
         q->pnp.max_groups = G;
     }
-    q->pnp.num_hypotheses = pp->num_hypotheses;
-    q->pnp.sampler = pp->sampler;
-    q->pnp.min_inliers = pp->min_inliers;
-    q->pnp.seed = pp->seed;
-    q->pnp.thr2 = pp->reproj_error * pp->reproj_error;
+    set_pnp_params(q->pnp, *pp);
     q->refit_on = pp->refit != 0;
     if (q->refit_on && !q->refit.out &&
         (st = alloc_refine(q->ctx, q->blocks, q->refit, q->n_tracks, q->stride, 1, q->pnp.K)) != MVS_OK)
         return st;
-    if (q->refit_on) {
-        mvs_refine_params rp;
-        mvs_refine_params_default(&rp);
-        rp.pose_sigma[0] = rp.pose_sigma[1] = kRefitPoseSigma;
-        q->refit.cfg = to_cfg(rp, 1);
-    }
+    if (q->refit_on)
+        q->refit.cfg = refit_cfg();
     return MVS_OK;
 }
 
-static mvs_status seq_enqueue(mvs_seq *q, Estimator est, const RunParams &rp)
+// One step of a prepared sequence: pair pipeline, join, PnP (and its optional refit), chain.  ev (mvs_seq_time_stages): five
+// events recorded around those four stages; the pair pipeline itself is not instrumented (it keeps its two halves).
+static mvs_status seq_enqueue(mvs_seq *q, Estimator est, const RunParams &rp, hipEvent_t *ev = nullptr)
 {
+    hipStream_t s = q->ctx->stream;
+    if (ev) HIP_TRY(q->ctx, hipEventRecord(ev[0], s));
     mvs_status st = est == Estimator::kEightPoint ? enqueue_pipeline(q->batch, rp, q->n_frames - 1, false, nullptr)
                                                   : enqueue_essential(q->batch, rp, q->n_frames - 1);
     if (st != MVS_OK)
         return st;
-    launch_seq_join(q->join, q->ctx->stream);
-    launch_pnp(q->pnp, q->ctx->stream);
+    if (ev) HIP_TRY(q->ctx, hipEventRecord(ev[1], s));
+    launch_seq_join(q->join, s);
+    if (ev) HIP_TRY(q->ctx, hipEventRecord(ev[2], s));
+    launch_pnp(q->pnp, s);
     if (q->refit_on)
-        launch_pnp_refit(q->pnp, q->refit, kRefitPointSigma, q->ctx->stream);
+        launch_pnp_refit(q->pnp, q->refit, kRefitPointSigma, s);
+    if (ev) HIP_TRY(q->ctx, hipEventRecord(ev[3], s));
     q->chain.n_corr = q->pnp.n;
-    launch_seq_chain(q->chain, q->ctx->stream);
+    launch_seq_chain(q->chain, s);
+    if (ev) HIP_TRY(q->ctx, hipEventRecord(ev[4], s));
     HIP_TRY(q->ctx, hipGetLastError());
     q->ran = true;
     q->wd.n_windows = 0;   // windows of an earlier run are not this run's
@@ -2714,7 +2117,8 @@ mvs_status mvs_seq_time(mvs_seq *q, const mvs_params *two_view, const mvs_pnp_pa
 }
 
 // per-stage HIP-event timing of the sequence step on the kernels' own stream: ms_stage[4] = summed ms over `steps`
-// instrumented passes of {pair pipeline, join, pnp_solve (prep + ransac + finalize), chain}
+// instrumented passes of {pair pipeline, join, pnp_solve (prep + ransac + finalize), chain}.  Every pass is a run
+// (seq_enqueue): it leaves the sequence as mvs_seq_run does, what was derived from an earlier run stale
 mvs_status mvs_seq_time_stages(mvs_seq *q, const mvs_params *two_view, const mvs_pnp_params *pnp, int steps, float *ms_stage)
 {
     if (steps < 1 || !ms_stage)
@@ -2723,24 +2127,12 @@ mvs_status mvs_seq_time_stages(mvs_seq *q, const mvs_params *two_view, const mvs
     if (st != MVS_OK)
         return st;
     const RunParams rp = to_run(*two_view);
-    hipStream_t s = q->ctx->stream;
     hipEvent_t *ev = q->batch->ev;
     for (int k = 0; k < 4; ++k)
         ms_stage[k] = 0.f;
     for (int i = 0; i < steps; ++i) {
-        HIP_TRY(q->ctx, hipEventRecord(ev[0], s));
-        if ((st = enqueue_pipeline(q->batch, rp, q->n_frames - 1, false, nullptr)) != MVS_OK)
+        if ((st = seq_enqueue(q, Estimator::kEightPoint, rp, ev)) != MVS_OK)
             return st;
-        HIP_TRY(q->ctx, hipEventRecord(ev[1], s));
-        launch_seq_join(q->join, s);
-        HIP_TRY(q->ctx, hipEventRecord(ev[2], s));
-        launch_pnp(q->pnp, s);
-        if (q->refit_on)
-            launch_pnp_refit(q->pnp, q->refit, kRefitPointSigma, s);
-        HIP_TRY(q->ctx, hipEventRecord(ev[3], s));
-        q->chain.n_corr = q->pnp.n;
-        launch_seq_chain(q->chain, s);
-        HIP_TRY(q->ctx, hipEventRecord(ev[4], s));
         HIP_TRY(q->ctx, hipEventSynchronize(ev[4]));
         for (int k = 0; k < 4; ++k) {
             float ms = 0.f;
@@ -2828,16 +2220,14 @@ mvs_status mvs_pnp_solve(mvs_ctx *ctx, const double *world_xyz, const double *im
     *n_inliers = 0;
     if (best_hyp)
         *best_hyp = -1;
-    if (n < 7 || params->num_hypotheses < 1 || !(params->reproj_error > 0.0))  // pnp-solve.cpp:13,22-23 (assert)
-        return MVS_ERR_INVALID_ARG;
-    if (params->sampler != MVS_SAMPLER_IDENTITY && params->sampler != MVS_SAMPLER_PHILOX)
+    if (n < 7 || !pnp_params_ok(params))
         return MVS_ERR_INVALID_ARG;
     if (n > kPnpMaxPoints)
         return MVS_ERR_CAPACITY;
     if (!affine_K(K))
         return MVS_ERR_BAD_INTRINSICS;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int G = (params->num_hypotheses + 255) / 256;
+    const int G = pnp_groups(*params);
     // workspace layout: X[3n] uv[2n] xy[2n] fb[3n] | K[9] Kinv[9] | rec[G] | out | inliers[n] n
     Carve L{64};
     const size_t off_x = L.take((size_t)n * 10 * sizeof(double));
@@ -2865,12 +2255,8 @@ mvs_status mvs_pnp_solve(mvs_ctx *ctx, const double *world_xyz, const double *im
     PnpDev p{};
     p.n_problems = 1;
     p.stride = n;
-    p.num_hypotheses = params->num_hypotheses;
-    p.sampler = params->sampler;
-    p.min_inliers = params->min_inliers;
+    set_pnp_params(p, *params);
     p.max_groups = G;
-    p.seed = params->seed;
-    p.thr2 = params->reproj_error * params->reproj_error;
     p.n = dinl + n;
     p.gidx = nullptr;
     p.K = dK;
@@ -2911,9 +2297,7 @@ mvs_status mvs_pnp_solve(mvs_ctx *ctx, const double *world_xyz, const double *im
             std::memcpy(&uv[2 * i], image_uv + 2 * (size_t)tmp[i], 2 * sizeof(double));
             XC[9 * i] = XC[9 * i + 4] = XC[9 * i + 8] = kRefitPointSigma * kRefitPointSigma;
         }
-        mvs_refine_params rp;
-        mvs_refine_params_default(&rp);
-        rp.pose_sigma[0] = rp.pose_sigma[1] = kRefitPoseSigma;
+        const mvs_refine_params rp = refit_params();
         mvs_refine_result rr;
         if (mvs_pnp_refine(ctx, X.data(), XC.data(), uv.data(), nullptr, (int)m, K, out.R, out.t, &rp, &rr) == MVS_OK && rr.ok) {
             std::memcpy(out.R, rr.R, sizeof(out.R));
@@ -3573,10 +2957,8 @@ void mvs_vo_params_default(mvs_vo_params *p)
 // what mvs_seq_track and mvs_seq_odometry both refuse: everything but the choice of the initial pair
 static bool track_args_ok(const mvs_seq *q, const mvs_vo_params *vp, const mvs_pnp_params *pp, const mvs_refine_params *rp)
 {
-    return q && vp && pp && refine_params_ok(rp) && q->ran && vp->sigma_px > 0.0 && vp->point_sigma > 0.0 &&
-           vp->anchor_var[0] > 0.0 && vp->anchor_var[1] > 0.0 && vp->regulator_var[0] > 0.0 && vp->regulator_var[1] > 0.0 &&
-           pp->num_hypotheses >= 1 && pp->reproj_error > 0.0 &&
-           (pp->sampler == MVS_SAMPLER_IDENTITY || pp->sampler == MVS_SAMPLER_PHILOX);
+    return q && vp && pnp_params_ok(pp) && refine_params_ok(rp) && q->ran && vp->sigma_px > 0.0 && vp->point_sigma > 0.0 &&
+           vp->anchor_var[0] > 0.0 && vp->anchor_var[1] > 0.0 && vp->regulator_var[0] > 0.0 && vp->regulator_var[1] > 0.0;
 }
 
 // The block's layout and the launches of a run whose arguments have been checked.  mvs_seq_track: ip = nullptr, the map
@@ -3588,7 +2970,7 @@ static mvs_status seq_track_enqueue(mvs_seq *q, const mvs_vo_params *vp, int k0,
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const BatchDev &bd = q->batch->d;
-    const size_t F = (size_t)q->n_frames, N = (size_t)bd.max_kp, G = (size_t)(pp->num_hypotheses + 255) / 256;
+    const size_t F = (size_t)q->n_frames, N = (size_t)bd.max_kp, G = (size_t)pnp_groups(*pp);
     const size_t D = sizeof(double), I = sizeof(int32_t);
     // what the downloads read first (cleared before every run), then the maps' ids (set to -1), then one step's scratch
     Carve L{64};
@@ -3670,12 +3052,8 @@ static mvs_status seq_track_enqueue(mvs_seq *q, const mvs_vo_params *vp, int k0,
     PnpDev p{};
     p.n_problems = 1;
     p.stride = (int)N;
-    p.num_hypotheses = pp->num_hypotheses;
-    p.sampler = pp->sampler;
-    p.min_inliers = pp->min_inliers;
+    set_pnp_params(p, *pp);
     p.max_groups = (int)G;
-    p.seed = pp->seed;
-    p.thr2 = pp->reproj_error * pp->reproj_error;
     p.K = q->pnp.K;
     p.Kinv = q->pnp.Kinv;
     p.xy = dbl(off_xy);
@@ -3685,12 +3063,7 @@ static mvs_status seq_track_enqueue(mvs_seq *q, const mvs_vo_params *vp, int k0,
     rf.n_problems = 1;
     rf.stride = (int)N;
     rf.n_frames = 1;
-    {
-        mvs_refine_params dp;
-        mvs_refine_params_default(&dp);
-        dp.pose_sigma[0] = dp.pose_sigma[1] = kRefitPoseSigma;
-        rf.cfg = to_cfg(dp, 1);
-    }
+    rf.cfg = refit_cfg();
     rf.m = i32(off_rm);
     rf.K = q->pnp.K;
     rf.pose0 = dbl(off_rpose);
@@ -4006,287 +3379,6 @@ mvs_status mvs_seq_upload_octaves(mvs_seq *q, int first, int count, const uint8_
 mvs_status mvs_seq_download_refined(mvs_seq *q, mvs_refine_result *refined, double *points_xyz, double *point_cov)
 {
     return q ? mvs_batch_download_refined(q->batch, refined, points_xyz, point_cov) : MVS_ERR_INVALID_ARG;
-}
-
-// ---------------------------------------------------------------------------------------------
-// extraction (row f3)
-void mvs_orb_params_default(mvs_orb_params *p)
-{
-    if (!p)
-        return;
-    p->nfeatures = 500;
-    p->nlevels = 8;
-    p->edge_threshold = 31;
-    p->fast_threshold = 20;
-}
-
-static void philox_host(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, uint32_t out[4])
-{   // Philox4x32-10 (Random123), counter (c0, c1, 0, 0)
-    uint32_t c[4] = {c0, c1, 0, 0};
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1,
-                       n3 = (uint32_t)p0;
-        c[0] = n0, c[1] = n1, c[2] = n2, c[3] = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    std::memcpy(out, c, sizeof(c));
-}
-
-// the 256 point pairs of the steered-BRIEF tests
-static void orb_pattern_host(int8_t P[1024])
-{
-    for (int i = 0; i < 256; ++i) {
-        uint32_t w[8];
-        philox_host((uint32_t)i, 0, 0x0B5EED00u, 0x31u, w);
-        philox_host((uint32_t)i, 1, 0x0B5EED00u, 0x31u, w + 4);
-        int c[4];
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t a = w[2 * k], b = w[2 * k + 1];
-            const int u = (int)((a & 0xffffu) + (a >> 16) + (b & 0xffffu) + (b >> 16)) - 131072;
-            c[k] = std::max(-13, std::min(13, (u * 11) / 65536));
-        }
-        if (c[0] == c[2] && c[1] == c[3])
-            c[2] = c[0] + (c[0] < 0 ? 3 : -3);
-        for (int k = 0; k < 4; ++k)
-            P[4 * i + k] = (int8_t)c[k];
-    }
-}
-
-// pyramid layout and per-level quotas (cv::ORB: n_l proportional to 1.2^-l, the last level takes the remainder)
-static bool orb_layout_host(int w, int h, const mvs_orb_params &p, OrbDev &d, size_t &pixels)
-{
-    if (p.nlevels < 1 || p.nlevels > kOrbMaxLevels || p.nfeatures < 1)
-        return false;
-    double s = 1.0;
-    pixels = 0;
-    for (int l = 0; l < p.nlevels; ++l) {
-        OrbLevel &L = d.level[l];
-        L.w = (int)std::lrint((double)w / s);
-        L.h = (int)std::lrint((double)h / s);
-        L.scale = (float)s;
-        L.offset = pixels;
-        pixels += (size_t)std::max(L.w, 0) * std::max(L.h, 0);
-        s = s * 1.2;
-    }
-    const double factor = 1.0 / 1.2;
-    double fn = 1.0;
-    for (int l = 0; l < p.nlevels; ++l)
-        fn = fn * factor;
-    double nd = (double)p.nfeatures * (1.0 - factor) / (1.0 - fn);
-    int sum = 0;
-    for (int l = 0; l < p.nlevels - 1; ++l) {
-        // the rounded shares can add up to more than nfeatures when nfeatures is small (cv::ORB then returns more
-        // keypoints than asked for); the outputs have room for nfeatures: a level takes at most what is left
-        d.level[l].n_keep = std::min((int)std::lrint(nd), p.nfeatures - sum);
-        sum += d.level[l].n_keep;
-        nd = nd * factor;
-    }
-    d.level[p.nlevels - 1].n_keep = std::max(p.nfeatures - sum, 0);
-    return true;
-}
-
-// runs the extraction of n images (host pointer) through the ctx workspace; outputs go to the given DEVICE arrays
-// (desc / kp_xy / n_kp may belong to a sequence) and, when kp_rec_out is non-null, records are also left in the workspace
-// wait = false: the overflow flag's copy is queued but not waited for -- the caller queues its own downloads behind it, waits
-// once and then reads *ctx->h_orb_ovf
-static mvs_status orb_run(mvs_ctx *ctx, const uint8_t *images, int n, int w, int h, const mvs_orb_params &prm,
-                          uint8_t *d_desc_ext, float *d_kp_xy_ext, int32_t *d_n_ext, OrbDev &d,
-                          uint8_t *d_kp_oct_ext = nullptr, bool wait = true)
-{
-    if (w < 1 || h < 1 || w > 65535 || h > 65535)
-        return MVS_ERR_CAPACITY;
-    if (prm.fast_threshold < 1 || prm.fast_threshold > 254 || prm.edge_threshold < 19)
-        return MVS_ERR_INVALID_ARG;
-    d = OrbDev{};
-    size_t T = 0;
-    if (!orb_layout_host(w, h, prm, d, T))
-        return MVS_ERR_INVALID_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!ctx->orb_ready) {
-        HIP_TRY(ctx, orb_prepare());
-        ctx->orb_ready = true;
-    }
-    const size_t B = (size_t)n, NL = (size_t)prm.nlevels, NF = (size_t)prm.nfeatures;
-    Carve L{256};
-    const size_t o_pyr = L.take(T * B);
-    const size_t o_blur = L.take(T * B);
-    // resize tables: for every level >= 1, {source index, 11-bit weight} per destination column, then per row.  Their layout
-    // is part of the key, their contents are built only when the key is new (below)
-    size_t tab_entries = 0;
-    for (int l = 1; l < prm.nlevels; ++l) {
-        d.level[l].tab_offset = tab_entries;
-        tab_entries += (size_t)std::max(d.level[l].w, 0) + (size_t)std::max(d.level[l].h, 0);
-    }
-    auto build_tab = [&](std::vector<int2> &tab) {
-        tab.reserve(tab_entries);
-        for (int l = 1; l < prm.nlevels; ++l) {
-            const OrbLevel &Lv = d.level[l], &Pv = d.level[l - 1];
-            for (int pass = 0; pass < 2; ++pass) {
-                const long long sn = pass ? Pv.h : Pv.w, dn = pass ? Lv.h : Lv.w;
-                for (long long dd = 0; dd < dn; ++dd) {
-                    const long long num = (2 * dd + 1) * sn - dn, den = 2 * dn;   // source coordinate = num / den (>= 0 here)
-                    long long si = num >= 0 ? num / den : -1;
-                    const long long fr = num - si * den;
-                    int wgt = (int)((fr * 4096 + den) / (2 * den));               // round(frac * 2048)
-                    if (si < 0) si = 0, wgt = 0;
-                    if (si >= sn - 1) si = sn - 1;
-                    tab.push_back(make_int2((int)si, wgt));
-                }
-            }
-        }
-    };
-    const size_t o_tab = L.take(std::max<size_t>(tab_entries, 1) * sizeof(int2));
-    // candidate lists: a level's list holds the non-maximum suppression's own bound -- strict 3x3 maxima of the detection
-    // area, at most one per 2x2 block -- so it cannot overflow; only when 2 n_l exceeds what the selection holds in LDS the
-    // list is capped there (and a fuller level is reported as MVS_ERR_CAPACITY, as every level was in rounds 2-4)
-    int max_keep = 0;
-    for (int l = 0; l < prm.nlevels; ++l)
-        max_keep = std::max(max_keep, d.level[l].n_keep);
-    size_t cand_total = 0;
-    for (int l = 0; l < prm.nlevels; ++l) {
-        OrbLevel &Lv = d.level[l];
-        const long long dw = (long long)Lv.w - 2 * prm.edge_threshold, dh = (long long)Lv.h - 2 * prm.edge_threshold;
-        long long cap = dw > 0 && dh > 0 ? ((dw + 1) / 2) * ((dh + 1) / 2) + 64 : 64;
-        if (2LL * max_keep > kOrbSelCap)
-            cap = std::min<long long>(cap, kOrbSelCap);
-        if (cap > 0x7fffffff)
-            return MVS_ERR_CAPACITY;
-        Lv.cand_cap = (int)cap;
-        Lv.cand_off = cand_total;
-        cand_total += (size_t)cap;
-    }
-    d.cand_stride = cand_total;
-    const size_t o_keys = L.take(B * cand_total * 8);
-    const size_t o_cc = L.take(B * NL * 4);
-    const size_t o_sel = L.take(B * NL * NF * sizeof(OrbSel));
-    const size_t o_sc = L.take(B * NL * 4);
-    const size_t o_ovf = L.take(4);
-    const size_t o_pat = L.take(1024);
-    const size_t o_kp = L.take(B * NF * sizeof(mvs_keypoint));
-    const size_t o_desc = L.take(B * NF * 32);
-    const size_t o_n = L.take(B * 4);
-    if (ctx->orb.bytes < L.total())
-        drop_orb_graph(ctx);   // before its workspace is freed: a failed growth must not leave it behind
-    const mvs_status st = ws_grow(ctx, ctx->orb, L.total());
-    if (st != MVS_OK)
-        return st;
-    char *base = ctx->orb.ptr();
-    d.n_images = n;
-    d.n_levels = prm.nlevels;
-    d.nfeatures = prm.nfeatures;
-    d.edge = prm.edge_threshold;
-    d.fast_threshold = prm.fast_threshold;
-#ifdef MVS_DEBUG_HOOKS
-    d.flat_order = std::getenv("MVS_ORB_FLAT_ORDER") != nullptr;   // A/B of the describe kernel's block order (tools/profile_extract.sh)
-#endif
-    d.pyr = reinterpret_cast<uint8_t *>(base + o_pyr);
-    d.blur = reinterpret_cast<uint8_t *>(base + o_blur);
-    d.resize_tab = reinterpret_cast<const int2 *>(base + o_tab);
-    d.cand_keys = reinterpret_cast<uint64_t *>(base + o_keys);
-    d.cand_count = reinterpret_cast<int32_t *>(base + o_cc);
-    d.sel = reinterpret_cast<OrbSel *>(base + o_sel);
-    d.sel_count = reinterpret_cast<int32_t *>(base + o_sc);
-    d.overflow = reinterpret_cast<int32_t *>(base + o_ovf);
-    d.pattern = reinterpret_cast<int8_t *>(base + o_pat);
-    d.kp = reinterpret_cast<mvs_keypoint *>(base + o_kp);
-    d.desc = d_desc_ext ? d_desc_ext : reinterpret_cast<uint8_t *>(base + o_desc);
-    d.n_kp = d_n_ext ? d_n_ext : reinterpret_cast<int32_t *>(base + o_n);
-    d.kp_xy = d_kp_xy_ext;
-    d.kp_oct = d_kp_oct_ext;
-    hipStream_t s = ctx->stream;
-    // the test pattern and the resize tables depend on (size, parameters, workspace) only: a call with the key of the captured
-    // graph finds them in the workspace (round 5: they were uploaded, and the stream synchronised for them, on every call)
-    const bool same_key = ctx->orb_graph_valid && std::memcmp(&ctx->orb_graph_key, &d, sizeof(d)) == 0;
-    int8_t pat[1024];
-    std::vector<int2> tab;
-    if (!same_key) {
-        orb_pattern_host(pat);
-        build_tab(tab);
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_pat, pat, sizeof(pat), hipMemcpyHostToDevice, s));
-        if (!tab.empty())
-            HIP_TRY(ctx, hipMemcpyAsync(base + o_tab, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(d.pyr, images, (size_t)w * h * B, hipMemcpyHostToDevice, s));  // level 0 = the input
-    if (!same_key)
-        HIP_TRY(ctx, sync_stream(ctx));   // `pat` and `tab` live on this frame
-#ifdef MVS_DEBUG_HOOKS
-    static const bool no_graph = std::getenv("MVS_NO_GRAPH") != nullptr;   // A/B switch for tools/extract_bench.py (diagnostics build only)
-#else
-    constexpr bool no_graph = false;
-#endif
-    if (no_graph) {
-        launch_orb(d, s);
-    } else {
-        if (!same_key) {
-            drop_orb_graph(ctx);
-            hipGraph_t graph = nullptr;
-            HIP_TRY(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            launch_orb(d, s);
-            HIP_TRY(ctx, hipStreamEndCapture(s, &graph));
-            const hipError_t ie = hipGraphInstantiate(&ctx->orb_graph, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            HIP_TRY(ctx, ie);
-            std::memcpy(&ctx->orb_graph_key, &d, sizeof(d));
-            ctx->orb_graph_valid = true;
-        }
-        HIP_TRY(ctx, hipGraphLaunch(ctx->orb_graph, s));
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    if (!ctx->h_orb_ovf)
-        HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_orb_ovf), 64, hipHostMallocDefault));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_orb_ovf, d.overflow, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (!wait)
-        return MVS_OK;
-    HIP_TRY(ctx, sync_stream(ctx));
-    return *ctx->h_orb_ovf ? MVS_ERR_CAPACITY : MVS_OK;
-}
-
-mvs_status mvs_extract_time(mvs_ctx *ctx, int steps, float *ms_total)
-{
-    if (!ctx || !ms_total || steps < 1)
-        return MVS_ERR_INVALID_ARG;
-    if (!ctx->orb_graph_valid || !ctx->orb_graph)
-        return MVS_ERR_INVALID_ARG;   // nothing has been extracted on this context yet
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_TRY(ctx, hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) {
-        (void)hipEventDestroy(e0);
-        ctx->err = "mvs_extract_time: hipEventCreate failed";
-        return MVS_ERR_HIP;
-    }
-    hipStream_t s = ctx->stream;
-    hipError_t e = hipEventRecord(e0, s);
-    for (int i = 0; i < steps && e == hipSuccess; ++i)
-        e = hipGraphLaunch(ctx->orb_graph, s);
-    if (e == hipSuccess) e = hipEventRecord(e1, s);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
-    if (e == hipSuccess) e = hipEventElapsedTime(ms_total, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    HIP_TRY(ctx, e);
-    return MVS_OK;
-}
-
-mvs_status mvs_extract(mvs_ctx *ctx, const uint8_t *images, int n_images, int width, int height,
-                       const mvs_orb_params *params, mvs_keypoint *keypoints, uint8_t *descriptors, int32_t *n_keypoints)
-{
-    if (!ctx || !images || !params || !keypoints || !descriptors || !n_keypoints || n_images < 1)
-        return MVS_ERR_INVALID_ARG;
-    OrbDev d;
-    // one wait per call: the outputs are queued behind the launches and the overflow flag (round 5: the flag had its own wait)
-    const mvs_status st = orb_run(ctx, images, n_images, width, height, *params, nullptr, nullptr, nullptr, d, nullptr, false);
-    if (st != MVS_OK)
-        return st;
-    const size_t B = n_images, NF = params->nfeatures;
-    hipStream_t s = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(keypoints, d.kp, B * NF * sizeof(mvs_keypoint), hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipMemcpyAsync(descriptors, d.desc, B * NF * 32, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipMemcpyAsync(n_keypoints, d.n_kp, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, sync_stream(ctx));
-    return *ctx->h_orb_ovf ? MVS_ERR_CAPACITY : MVS_OK;
 }
 
 mvs_status mvs_seq_upload_images(mvs_seq *q, int first, int count, const uint8_t *images, int width, int height,

@@ -146,6 +146,20 @@ def test_product_library_has_one_path_and_no_experiment_ladder():
         assert k in prod, k
 
 
+def test_host_helpers_stay_out_of_the_dynamic_symbol_table():
+    """The helpers the host files (capi_*.hip) share live in one hidden namespace, mvs_host (capi_internal.hpp): the library
+    links them, nobody outside it can.  A helper defined outside that namespace, or the namespace losing its visibility
+    attribute, shows up here.  (Unless the library has been stripped, its static table must have them: the check is then
+    not vacuous.)"""
+    from mvslam_amd import capi
+
+    dynamic = subprocess.check_output(["nm", "-DC", capi.LIB_PATH]).decode()
+    assert "mvs_abi_version" in dynamic
+    assert "mvs_host::" not in dynamic, [ln for ln in dynamic.splitlines() if "mvs_host::" in ln]
+    static = subprocess.run(["nm", "-C", capi.LIB_PATH], capture_output=True, text=True).stdout
+    assert not static.strip() or "mvs_host::ws_grow" in static
+
+
 def test_hot_kernels_do_not_spill():
     """The build's -Rpass-analysis=kernel-resource-usage digest (lib/kernel_resources.json): the hot kernels of the pre-screened
     stage keep their state in registers.  ransac_prescreen_kernel sits a few registers below the 168 that three wavefronts

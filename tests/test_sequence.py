@@ -259,3 +259,67 @@ def test_gpu_sequence_refit_is_the_single_shot_refit_and_tightens_the_scale(ctx)
         assert tr1[k].tobytes() == want[k].tobytes(), k
     e0, e1 = np.abs(tr0["track_scale"] - 1.0), np.abs(tr1["track_scale"] - 1.0)
     assert np.median(e1) < np.median(e0), (e0, e1)    # what remains is the two-view triangulation noise of the map points
+
+
+@pytest.mark.gpu
+def test_gpu_sequence_time_stages_is_a_run(ctx):
+    """mvs_seq_time_stages enqueues mvs_seq_run's step (one body, events around its four stages).  (a) What it leaves on the
+    device is what a run with the same parameters leaves, byte for byte.  (b) It overwrites the pairs, tracks and trajectory,
+    so whatever was derived from an earlier run is stale afterwards exactly as after a second run: mvs_seq_track with
+    use_refined_init and mvs_seq_download_windows answer MVS_ERR_INVALID_ARG."""
+    from mvslam_amd import capi
+
+    F, N = 4, 128
+    seq = synth.make_sequence(F, n_kp=N, n_map=1500, noise_px=0.2)
+    prm = capi.default_params(num_hypotheses=64, sampler=capi.SAMPLER_PHILOX, seed=7, max_error_sq=1e-2)
+    pprm = capi.default_pnp_params(num_hypotheses=32, sampler=capi.SAMPLER_PHILOX, seed=11, reproj_error=2.0)
+
+    def new_sequence():
+        s = capi.Sequence(ctx, F, N, 32)
+        s.upload(0, seq["desc"], seq["kp"], seq["n_kp"], seq["K"])
+        return s
+
+    def state(s):
+        return s.download_pairs(), s.download_tracks(), s.download_trajectory()
+
+    # one sequence, so that rows no kernel writes (beyond a pair's matches, a track's correspondences) hold the same bytes
+    # both times; a run with another seed in front of each, so that neither reads back what the other left
+    other = capi.default_params(num_hypotheses=64, sampler=capi.SAMPLER_PHILOX, seed=8, max_error_sq=1e-2)
+    s = new_sequence()
+    s.run(other, pprm)
+    s.run(prm, pprm)
+    want = state(s)
+    s.run(other, pprm)
+    assert state(s)[0]["results"].tobytes() != want[0]["results"].tobytes()
+    ms = s.time_stages(prm, pprm, 1)
+    got = state(s)
+    s.close()
+    assert sorted(ms) == ["chain", "join", "pairs", "pnp"] and all(v >= 0.0 for v in ms.values())
+    assert want[1]["tracks"]["ok"].any(), "the shape has no track: the comparison would be of empty records"
+    for w, g in zip(want, got):
+        assert sorted(w) == sorted(g)
+        for k in w:
+            assert w[k].tobytes() == g[k].tobytes(), k
+
+    def stale_after(again):
+        s = new_sequence()
+        s.run(prm, pprm)
+        s.refine_pairs()
+        s.refine_windows(3, 1, max_points=N)
+        s.track(capi.default_vo_params(use_refined_init=1), pprm)     # fresh: both answer
+        s.download_windows()
+        again(s)
+        status = []
+        for call in (lambda: s.track(capi.default_vo_params(use_refined_init=1), pprm), s.download_windows):
+            with pytest.raises(capi.MvsError) as e:
+                call()
+            status.append(e.value.status)
+        s.track(capi.default_vo_params(), pprm)                       # and the sequence counts as run
+        s.download_track_frames()
+        s.close()
+        return status
+
+    after_run = stale_after(lambda s: s.run(prm, pprm))
+    after_timing = stale_after(lambda s: s.time_stages(prm, pprm, 1))
+    assert after_run == [capi.MVS_ERR_INVALID_ARG] * 2
+    assert after_timing == after_run
