@@ -50,6 +50,9 @@ extern "C" {
 /* still 4: mvs_vo_params, mvs_track_frame, mvs_vo_params_default, mvs_seq_track, mvs_seq_download_track_frames,
  * mvs_seq_download_track_map and mvs_seq_download_track_step are additions (new symbols only): VisualOdometer::track on a
  * resident sequence */
+/* still 4: mvs_seq_loop_scores, mvs_seq_download_loop_scores, mvs_loop_select_params, mvs_loop_candidate, mvs_seq_select_loops,
+ * mvs_seq_verify_loops, mvs_loop_edge_params, mvs_seq_add_loop_edges and mvs_seq_download_loop_candidates are additions (new
+ * symbols only): loop closures of a resident sequence */
 #define MVS_ABI_VERSION 4
 
 typedef enum mvs_status {
@@ -961,14 +964,91 @@ mvs_status mvs_seq_build_pose_graph(mvs_seq *s, const mvs_seq_graph_params *p);
  * MVS_ERR_INVALID_ARG before mvs_seq_build_pose_graph or for parameters mvs_pose_graph_optimize refuses. */
 mvs_status mvs_seq_optimize_pose_graph(mvs_seq *s, const mvs_pose_graph_params *p, mvs_pose_graph_result *result);
 /* The resident graph: *n_edges = E, node_pose n_frames x 12, and the first E rows of edge_src / edge_dst / edge_lag /
- * edge_kind (0 measured, 1 fallback) / edge_scale (E), edge_pose (E x 12), edge_cov (E x 36).  Every array must hold the
- * candidate slot count max_lag n_frames - max_lag (max_lag + 1) / 2 of the build; any pointer but n_edges may be NULL.
+ * edge_kind (0 measured, 1 fallback, 2 loop closure) / edge_scale (E), edge_pose (E x 12), edge_cov (E x 36).  Every array
+ * must hold the candidate slot count max_lag n_frames - max_lag (max_lag + 1) / 2 of the build -- after a successful
+ * mvs_seq_add_loop_edges that slot count PLUS the max_candidates of the selection whose edges that call added (a later
+ * mvs_seq_select_loops does not change the graph, nor what its download needs) --; any pointer but n_edges may be NULL.
  * MVS_ERR_INVALID_ARG before mvs_seq_build_pose_graph. */
 mvs_status mvs_seq_download_pose_graph(mvs_seq *s, int32_t *n_edges, double *node_pose, int32_t *edge_src, int32_t *edge_dst,
                                        double *edge_pose, double *edge_cov, int32_t *edge_lag, int32_t *edge_kind, double *edge_scale);
 /* poses: n_frames x 12, the optimised nodes.  MVS_ERR_INVALID_ARG unless the last mvs_seq_optimize_pose_graph on the current
  * graph succeeded. */
 mvs_status mvs_seq_download_pose_graph_poses(mvs_seq *s, double *poses);
+
+/* ---- Loop closures of a resident sequence -------------------------------------------------------
+ * Every edge of the graph above joins frames at most max_lag apart: it smooths a trajectory and cannot remove its drift.  These
+ * calls find frames that see the same place again, verify the pairs with the two-view pipeline and the refinement, and append
+ * them to the resident graph.  The reference has no loop closure; this is the library's own, specified here and restated in
+ * numpy by tests/seq_loop_model.py.  Asynchronous on the ctx stream unless stated otherwise.
+ *
+ * 1 Scores.  For frames i < j with j - i >= min_gap, score[i][j] = the number of keypoints of frame j (queries) that pass the
+ *   matcher's test against frame i (trains): n_i >= 2, (double)(float)D0 < ratio (double)(float)D1, and max_dist < 0 or
+ *   (double)(float)D0 <= max_dist, with D0 <= D1 the two smallest Hamming distances counted with multiplicity (two trains at
+ *   one distance: D1 = D0).  It is the n_matches the pair pipeline reports for base i, pair j.  Every other entry of the
+ *   n_frames x n_frames table (row i, column j) is zero.  Needs the frames uploaded, not a run.  A later mvs_seq_upload or
+ *   mvs_seq_upload_images discards the table, the list and the verification (their calls and downloads return
+ *   MVS_ERR_INVALID_ARG until mvs_seq_loop_scores runs again); mvs_seq_upload_octaves discards the verification.  Edges
+ *   already in the graph stay.
+ *   MVS_ERR_INVALID_ARG: min_gap < 1 or >= n_frames, a NaN ratio or max_dist.  MVS_ERR_CAPACITY: more than 4096 frames
+ *   (reported first).  The table (4 n_frames^2 bytes) is owned by the sequence. */
+mvs_status mvs_seq_loop_scores(mvs_seq *s, double ratio, double max_dist, int min_gap);
+/* scores: n_frames x n_frames int32.  Waits for the ctx stream.  MVS_ERR_INVALID_ARG before mvs_seq_loop_scores. */
+mvs_status mvs_seq_download_loop_scores(mvs_seq *s, int32_t *scores);
+
+/* 2 Selection.  (i, j) is eligible iff score[i][j] >= min_score.  Every j keeps its top_k eligible i by score, the smaller i
+ *   on a tie.  The list is ordered by ascending j, then descending score, then ascending i, and cut after max_candidates
+ *   entries; both the kept and the uncut count are recorded.  On the device; the list stays resident.
+ *   MVS_ERR_INVALID_ARG: before mvs_seq_loop_scores, min_score < 1, top_k < 1, max_candidates < 1. */
+typedef struct mvs_loop_select_params {
+    int32_t min_score;       /* >= 1 */
+    int32_t top_k;           /* >= 1 */
+    int32_t max_candidates;  /* >= 1 */
+    int32_t reserved;
+} mvs_loop_select_params;
+typedef struct mvs_loop_candidate {
+    int32_t i, j;            /* base (train) and query frame, i < j */
+    int32_t score;
+    int32_t accepted;        /* 1: mvs_seq_add_loop_edges made it an edge; 0 before that call */
+} mvs_loop_candidate;
+mvs_status mvs_seq_select_loops(mvs_seq *s, const mvs_loop_select_params *p);
+
+/* 3 Verification.  Candidate c = (i, j) becomes pair c of one batch owned by the sequence (max_candidates pairs that own their
+ *   images, created at the first call): a device gather of descriptors, keypoints, octaves and counts of frames i and j, the
+ *   intrinsics of the sequence's pair i, sampler key offset c.  Then mvs_batch_run (essential = 0) or mvs_batch_run_essential
+ *   on the kept candidates, then mvs_batch_refine.  Results and refined results are, byte for byte, those of these calls on an
+ *   uploaded batch holding the same frame pairs in candidate order with global_index[c] = c.  The call reads the kept count
+ *   on the host once (it waits for the ctx stream there).
+ *   MVS_ERR_INVALID_ARG: before mvs_seq_select_loops, sigma_px <= 0, parameters mvs_batch_run / mvs_batch_refine refuse.
+ *   Memory: what mvs_seq_run_lags states per lag, for max_candidates pairs, plus their own two images each. */
+mvs_status mvs_seq_verify_loops(mvs_seq *s, const mvs_params *two_view, int essential, const mvs_refine_params *refine,
+                                double sigma_px);
+
+/* 4 Edges.  After mvs_seq_build_pose_graph and mvs_seq_verify_loops: one edge per accepted candidate is appended behind the
+ *   built edges, in candidate order: source i, destination j, edge_lag = j - i, edge_kind = 2.  Acceptance, the scale s and
+ *   S' = D S D are the rules of mvs_seq_build_pose_graph with (k, k + d) = (i, j) and r = the candidate's refined result.
+ *   Then loop_sigma[0]^2 is added to the three rotation diagonal entries of S' and loop_sigma[1]^2 to the three translation
+ *   ones (each only where its loop_sigma > 0): the scale of a loop edge comes from a drifted trajectory, and at a true revisit
+ *   s is small, so S' alone would be far too tight.  The positive-definite test runs on the final matrix.  Plain binary64 in
+ *   the order written, no fused operation.  A second call first cuts the graph back to its built edges; the call clears what
+ *   mvs_seq_optimize_pose_graph left.  mvs_seq_optimize_pose_graph works on the longer list unchanged.
+ *   MVS_ERR_CAPACITY (reported first, nothing changes): the build's candidate slots plus max_candidates exceed 65536.
+ *   MVS_ERR_INVALID_ARG: min_points < 0, a negative or NaN max_error, a NaN loop_sigma, no graph built, candidates not
+ *   verified since the last selection. */
+typedef struct mvs_loop_edge_params {
+    int32_t min_points;     /* 0 = no gate */
+    int32_t reserved;
+    double  max_error;      /* gate on the refined error; 1e30 = open */
+    double  loop_sigma[2];  /* rotation, translation; <= 0 adds nothing */
+} mvs_loop_edge_params;
+mvs_status mvs_seq_add_loop_edges(mvs_seq *s, const mvs_loop_edge_params *p);
+
+/* The resident list.  *n_kept entries of cand[max_candidates] are candidates (the rest zero), *n_found is the count before the
+ * cut.  results / matches / inlier_mask / points_xyz / point_idx: rows [0, n_kept) as mvs_batch_download lays them out, and
+ * refined[n_kept]: valid after mvs_seq_verify_loops (MVS_ERR_INVALID_ARG if one of them is asked for before).  Any pointer may
+ * be NULL.  Waits for the ctx stream.  MVS_ERR_INVALID_ARG before mvs_seq_select_loops. */
+mvs_status mvs_seq_download_loop_candidates(mvs_seq *s, int32_t *n_kept, int32_t *n_found, mvs_loop_candidate *cand,
+                                            mvs_pair_result *results, mvs_match *matches, uint8_t *inlier_mask,
+                                            double *points_xyz, int64_t *point_idx, mvs_refine_result *refined);
 
 #ifdef __cplusplus
 }

@@ -167,7 +167,21 @@ class SeqGraphParams(C.Structure):
     _fields_ = [("max_lag", C.c_int32), ("min_points", C.c_int32), ("max_error", C.c_double), ("chain_sigma", C.c_double * 2)]
 
 
-SEQ_GRAPH_EDGE_MEASURED, SEQ_GRAPH_EDGE_CHAIN = 0, 1
+SEQ_GRAPH_EDGE_MEASURED, SEQ_GRAPH_EDGE_CHAIN, SEQ_GRAPH_EDGE_LOOP = 0, 1, 2
+
+
+class LoopSelectParams(C.Structure):
+    """mvs_loop_select_params: which scored frame pairs become loop-closure candidates"""
+    _fields_ = [("min_score", C.c_int32), ("top_k", C.c_int32), ("max_candidates", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LoopEdgeParams(C.Structure):
+    """mvs_loop_edge_params: the gates and the extra covariance of the loop edges"""
+    _fields_ = [("min_points", C.c_int32), ("reserved", C.c_int32), ("max_error", C.c_double), ("loop_sigma", C.c_double * 2)]
+
+
+LOOP_CANDIDATE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("score", "<i4"), ("accepted", "<i4")])
+LOOP_MAX_FRAMES = 4096
 
 
 class OrbParams(C.Structure):
@@ -220,7 +234,8 @@ EXPORTS = [
     "mvs_vo_init_params_default", "mvs_seq_odometry", "mvs_seq_download_odometry_frames",
     "mvs_pose_graph_params_default", "mvs_pose_graph_optimize", "mvs_pose_graph_optimize_batch",
     "mvs_seq_build_pose_graph", "mvs_seq_optimize_pose_graph", "mvs_seq_download_pose_graph",
-    "mvs_seq_download_pose_graph_poses",
+    "mvs_seq_download_pose_graph_poses", "mvs_seq_loop_scores", "mvs_seq_download_loop_scores", "mvs_seq_select_loops",
+    "mvs_seq_verify_loops", "mvs_seq_add_loop_edges", "mvs_seq_download_loop_candidates",
 ]
 
 
@@ -1328,6 +1343,7 @@ class Sequence:
                                                                                               float(chain_sigma[1])))
         self.ctx._check(lib().mvs_seq_build_pose_graph(self._h, C.byref(gp)), "mvs_seq_build_pose_graph")
         self._graph_slots = max_lag * self.n_frames - max_lag * (max_lag + 1) // 2
+        self._graph_loop_rows = 0
 
     def optimize_pose_graph(self, params=None):
         """mvs_seq_optimize_pose_graph: (status, result record); download_pose_graph_poses() fetches the nodes"""
@@ -1340,7 +1356,8 @@ class Sequence:
     def download_pose_graph(self):
         """the resident graph, cut to its edge count: node_pose [n_frames, 12], edge_src, edge_dst, edge_pose [E, 12],
         edge_cov [E, 36], edge_lag, edge_kind, edge_scale, anchor (0) -- the keys Context.pose_graph_optimize reads, and more"""
-        S = max(getattr(self, "_graph_slots", 0), 1)
+        # rows: the build's slots, plus the max_candidates of the selection whose edges add_loop_edges() last added
+        S = max(getattr(self, "_graph_slots", 0) + getattr(self, "_graph_loop_rows", 0), 1)
         n = np.zeros(1, dtype=np.int32)
         node = np.zeros((self.n_frames, 12))
         src, dst, lag, kind = (np.zeros(S, dtype=np.int32) for _ in range(4))
@@ -1360,6 +1377,63 @@ class Sequence:
         st = lib().mvs_seq_download_pose_graph_poses(self._h, _ptr(poses, C.c_double))
         self.ctx._check(st, "mvs_seq_download_pose_graph_poses")
         return poses
+
+    def sync(self):
+        """wait for the context's stream (the loop-closure calls are asynchronous)"""
+        self.ctx._check(lib().mvs_seq_sync(self._h), "mvs_seq_sync")
+
+    def loop_scores(self, ratio=0.7, max_dist=10.0, min_gap=1):
+        """score[i][j], j - i >= min_gap: keypoints of frame j that match into frame i (mvs_seq_loop_scores; asynchronous)"""
+        st = lib().mvs_seq_loop_scores(self._h, C.c_double(ratio), C.c_double(max_dist), C.c_int(min_gap))
+        self.ctx._check(st, "mvs_seq_loop_scores")
+
+    def download_loop_scores(self):
+        """the [n_frames, n_frames] int32 score table, zero outside the eligible triangle"""
+        sc = np.zeros((self.n_frames, self.n_frames), dtype=np.int32)
+        self.ctx._check(lib().mvs_seq_download_loop_scores(self._h, _ptr(sc, C.c_int32)), "mvs_seq_download_loop_scores")
+        return sc
+
+    def select_loops(self, min_score, top_k, max_candidates):
+        """per query frame the top_k base frames with score >= min_score, cut at max_candidates (mvs_seq_select_loops)"""
+        sp = LoopSelectParams(int(min_score), int(top_k), int(max_candidates), 0)
+        self.ctx._check(lib().mvs_seq_select_loops(self._h, C.byref(sp)), "mvs_seq_select_loops")
+        self._loop_max_candidates = int(max_candidates)
+
+    def verify_loops(self, params, essential=False, refine_params=None, sigma_px=0.5):
+        """the candidates through the two-view pipeline and ImagePair::refine (mvs_seq_verify_loops)"""
+        refine_params = refine_params or default_refine_params()
+        st = lib().mvs_seq_verify_loops(self._h, C.byref(params), C.c_int(1 if essential else 0), C.byref(refine_params),
+                                        C.c_double(sigma_px))
+        self.ctx._check(st, "mvs_seq_verify_loops")
+
+    def add_loop_edges(self, min_points=0, max_error=1e30, loop_sigma=(0.0, 0.0)):
+        """one edge of kind 2 per accepted candidate behind the built edges of the pose graph (mvs_seq_add_loop_edges)"""
+        ep = LoopEdgeParams(int(min_points), 0, float(max_error), (C.c_double * 2)(float(loop_sigma[0]), float(loop_sigma[1])))
+        self.ctx._check(lib().mvs_seq_add_loop_edges(self._h, C.byref(ep)), "mvs_seq_add_loop_edges")
+        self._graph_loop_rows = getattr(self, "_loop_max_candidates", 0)
+
+    def download_loop_candidates(self, pairs=False):
+        """the resident list cut to its kept count: cand (LOOP_CANDIDATE_DTYPE), n_kept, n_found; with pairs=True also what
+        Batch.download / download_refined give for the verified candidates (results, matches, mask, points, point_idx, refined)"""
+        Cn, N = max(getattr(self, "_loop_max_candidates", 0), 1), self.max_kp
+        kept, found = C.c_int32(0), C.c_int32(0)
+        cand = np.zeros(Cn, dtype=LOOP_CANDIDATE_DTYPE)
+        none = C.c_void_p()
+        res = np.zeros(Cn, dtype=RESULT_DTYPE) if pairs else None
+        mt = np.zeros((Cn, N), dtype=MATCH_DTYPE) if pairs else None
+        mk = np.zeros((Cn, N), dtype=np.uint8) if pairs else None
+        pts = np.zeros((Cn, N, 3)) if pairs else None
+        idx = np.zeros((Cn, N), dtype=np.int64) if pairs else None
+        ref = np.zeros(Cn, dtype=REFINE_DTYPE) if pairs else None
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else none
+        st = lib().mvs_seq_download_loop_candidates(self._h, C.byref(kept), C.byref(found), vp(cand), vp(res), vp(mt), vp(mk),
+                                                    vp(pts), vp(idx), vp(ref))
+        self.ctx._check(st, "mvs_seq_download_loop_candidates")
+        k = kept.value
+        out = dict(n_kept=k, n_found=found.value, cand=cand[:k].copy(), cand_all=cand)
+        if pairs:
+            out.update(results=res[:k], matches=mt[:k], mask=mk[:k], points=pts[:k], point_idx=idx[:k], refined=ref[:k])
+        return out
 
     def download_pairs(self):
         P, N = self.n_frames - 1, self.max_kp

@@ -1947,6 +1947,8 @@ void mvs_seq_destroy(mvs_seq *q)
     for (mvs_batch *lb : q->lag_batch)
         if (lb)
             mvs_batch_destroy(lb);
+    if (q->loop_batch)
+        mvs_batch_destroy(q->loop_batch);
     if (q->batch)
         mvs_batch_destroy(q->batch);
     delete q;
@@ -1959,6 +1961,7 @@ mvs_status mvs_seq_upload(mvs_seq *q, int first, int count, const uint8_t *desc,
         return MVS_ERR_INVALID_ARG;
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    q->loop_scored = q->loop_selected = q->loop_verified = false;   // the table, the list and the batch describe other frames
     const BatchDev &d = q->batch->d;
     hipStream_t s = ctx->stream;
     const size_t N = d.max_kp, DW = d.desc_words, off = first;
@@ -3370,6 +3373,7 @@ mvs_status mvs_seq_upload_octaves(mvs_seq *q, int first, int count, const uint8_
     for (size_t i = 0; i < bytes; ++i)
         if (octave[i] > 30)
             return MVS_ERR_INVALID_ARG;
+    q->loop_verified = false;   // the verification's refinement weighed the observations by the octaves before
     HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint8_t *>(q->batch->d.oct1) + (size_t)first * N, octave, bytes,
                                 hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, sync_stream(ctx));
@@ -3392,6 +3396,7 @@ mvs_status mvs_seq_upload_images(mvs_seq *q, int first, int count, const uint8_t
     mvs_orb_params prm = *params;
     prm.nfeatures = bd.max_kp;
     const size_t N = bd.max_kp, off = first;
+    q->loop_scored = q->loop_selected = q->loop_verified = false;   // as mvs_seq_upload
     OrbDev d;
     mvs_status st = orb_run(q->ctx, images, count, width, height, prm,
                             reinterpret_cast<uint8_t *>(const_cast<uint32_t *>(bd.desc1)) + off * N * 32,
@@ -3810,6 +3815,32 @@ mvs_status mvs_pose_graph_optimize(mvs_ctx *ctx, const mvs_pose_graph *graph, co
 }
 
 // ---- the pose graph of a resident sequence (seq_graph.hip) -------------------------------------
+// The graph's block: S candidate slots, room for `cap` >= S edges (the loop edges of mvs_seq_add_loop_edges sit behind the
+// built ones), F nodes.  The count, src and dst first and in this order: mvs_seq_optimize_pose_graph downloads that prefix.
+struct SeqGraphLayout {
+    size_t S, cap, o_n, o_built, o_src, o_dst, o_lag, o_kind, o_scale, o_z, o_cov, o_node, o_opt, o_keep, o_skind, o_sscale, o_sz, o_scov, total;
+    SeqGraphLayout(size_t S_, size_t cap_, size_t F) : S(S_), cap(cap_)
+    {
+        Carve L{64};
+        o_n = L.take(4), o_src = L.take(cap * 4), o_dst = L.take(cap * 4), o_lag = L.take(cap * 4), o_kind = L.take(cap * 4);
+        o_scale = L.take(cap * 8), o_z = L.take(cap * 12 * 8), o_cov = L.take(cap * 36 * 8), o_node = L.take(F * 12 * 8);
+        o_opt = L.take(F * 12 * 8), o_keep = L.take(S * 4), o_skind = L.take(S * 4), o_sscale = L.take(S * 8);
+        o_sz = L.take(S * 12 * 8), o_scov = L.take(S * 36 * 8);
+        o_built = L.take(4);   // edges of the built graph, behind which the loop edges go (mvs_seq_add_loop_edges)
+        total = L.total();
+    }
+    // points g's arrays into the block at `base`; returns the optimised nodes' place
+    double *point(SeqGraphDev &g, char *base) const
+    {
+        auto dp = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
+        auto ip = [&](size_t o) { return reinterpret_cast<int32_t *>(base + o); };
+        g.slot_keep = ip(o_keep), g.slot_kind = ip(o_skind), g.slot_scale = dp(o_sscale), g.slot_pose = dp(o_sz), g.slot_cov = dp(o_scov);
+        g.n_edges = ip(o_n), g.edge_src = ip(o_src), g.edge_dst = ip(o_dst), g.edge_lag = ip(o_lag), g.edge_kind = ip(o_kind);
+        g.edge_scale = dp(o_scale), g.edge_pose = dp(o_z), g.edge_cov = dp(o_cov), g.node_pose = dp(o_node);
+        return dp(o_opt);
+    }
+};
+
 mvs_status mvs_seq_build_pose_graph(mvs_seq *q, const mvs_seq_graph_params *p)
 {
     if (!q || !p || p->max_lag < 1 || p->max_lag >= q->n_frames || p->min_points < 0 || !(p->max_error >= 0.0) ||
@@ -3823,18 +3854,13 @@ mvs_status mvs_seq_build_pose_graph(mvs_seq *q, const mvs_seq_graph_params *p)
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     q->graph_built = q->graph_opt = false;
-    const size_t S = (size_t)slots64, F = (size_t)q->n_frames;
-    Carve L{64};   // the count, src and dst first and in this order: mvs_seq_optimize_pose_graph downloads that prefix
-    const size_t o_n = L.take(4), o_src = L.take(S * 4), o_dst = L.take(S * 4), o_lag = L.take(S * 4), o_kind = L.take(S * 4);
-    const size_t o_scale = L.take(S * 8), o_z = L.take(S * 12 * 8), o_cov = L.take(S * 36 * 8), o_node = L.take(F * 12 * 8);
-    const size_t o_opt = L.take(F * 12 * 8), o_keep = L.take(S * 4), o_skind = L.take(S * 4), o_sscale = L.take(S * 8);
-    const size_t o_sz = L.take(S * 12 * 8), o_scov = L.take(S * 36 * 8);
-    const mvs_status st = ws_grow(ctx, q->graph, L.total());
+    const size_t S = (size_t)slots64;
+    // room behind the slots for the loop edges of the current selection (mvs_seq_add_loop_edges grows the block otherwise)
+    const size_t want = S + (q->loop_selected ? (size_t)q->ld.max_candidates : 0);
+    const SeqGraphLayout L(S, want > (size_t)kPgMaxEdges ? S : want, (size_t)q->n_frames);
+    const mvs_status st = ws_grow(ctx, q->graph, L.total);
     if (st != MVS_OK)
         return st;
-    char *base = q->graph.ptr();
-    auto dp = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
-    auto ip = [&](size_t o) { return reinterpret_cast<int32_t *>(base + o); };
     SeqGraphDev g{};
     g.n_frames = q->n_frames, g.max_lag = p->max_lag, g.n_slots = (int)S;
     g.min_points = p->min_points;
@@ -3844,13 +3870,13 @@ mvs_status mvs_seq_build_pose_graph(mvs_seq *q, const mvs_seq_graph_params *p)
     g.chain_var[1] = p->chain_sigma[1] * p->chain_sigma[1];
     g.lags = q->lagws.ptr<LagDev>();
     g.traj_R = q->chain.traj_R, g.traj_t = q->chain.traj_t;
-    g.slot_keep = ip(o_keep), g.slot_kind = ip(o_skind), g.slot_scale = dp(o_sscale), g.slot_pose = dp(o_sz), g.slot_cov = dp(o_scov);
-    g.n_edges = ip(o_n), g.edge_src = ip(o_src), g.edge_dst = ip(o_dst), g.edge_lag = ip(o_lag), g.edge_kind = ip(o_kind);
-    g.edge_scale = dp(o_scale), g.edge_pose = dp(o_z), g.edge_cov = dp(o_cov), g.node_pose = dp(o_node);
+    q->graph_opt_pose = L.point(g, q->graph.ptr());
+    q->graph_n_built = reinterpret_cast<int32_t *>(q->graph.ptr() + L.o_built);
+    q->graph_edge_cap = (int)L.cap;
+    q->loop_edges_added = false;
     launch_seq_graph(g, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     q->gd = g;
-    q->graph_opt_pose = dp(o_opt);
     q->graph_built = true;
     return MVS_OK;
 }
@@ -3868,7 +3894,7 @@ mvs_status mvs_seq_optimize_pose_graph(mvs_seq *q, const mvs_pose_graph_params *
     // the count and the edges' endpoints: all the host needs of the graph
     const char *gbase = q->graph.ptr();
     const size_t o_src = (const char *)g.edge_src - gbase, o_dst = (const char *)g.edge_dst - gbase;
-    std::vector<char> head(o_dst + (size_t)g.n_slots * 4);
+    std::vector<char> head(o_dst + (size_t)q->graph_edge_cap * 4);
     HIP_TRY(ctx, hipMemcpyAsync(head.data(), gbase, head.size(), hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, sync_stream(ctx));
     int32_t E = 0;
@@ -3876,7 +3902,7 @@ mvs_status mvs_seq_optimize_pose_graph(mvs_seq *q, const mvs_pose_graph_params *
     const int32_t *h_src = reinterpret_cast<const int32_t *>(head.data() + o_src);
     const int32_t *h_dst = reinterpret_cast<const int32_t *>(head.data() + o_dst);
     const int N = g.n_frames;
-    if (E < 0 || E > g.n_slots) {
+    if (E < 0 || E > q->graph_edge_cap) {
         ctx->err = "mvs_seq_optimize_pose_graph: edge count out of range";
         return MVS_ERR_HIP;
     }
@@ -3927,7 +3953,7 @@ mvs_status mvs_seq_download_pose_graph(mvs_seq *q, int32_t *n_edges, double *nod
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx, hipMemcpyAsync(n_edges, g.n_edges, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, sync_stream(ctx));
-    const size_t E = (size_t)std::min(std::max(*n_edges, 0), g.n_slots);
+    const size_t E = (size_t)std::min(std::max(*n_edges, 0), q->graph_edge_cap);
     const struct {
         void *dst;
         const void *src;
@@ -3950,6 +3976,212 @@ mvs_status mvs_seq_download_pose_graph_poses(mvs_seq *q, double *poses)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemcpyAsync(poses, q->graph_opt_pose, (size_t)q->n_frames * 96, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, sync_stream(ctx));
+    return MVS_OK;
+}
+
+// ---- loop closures of a resident sequence (loop.hip, seq_graph.hip) -----------------------------
+mvs_status mvs_seq_loop_scores(mvs_seq *q, double ratio, double max_dist, int min_gap)
+{
+    if (!q)
+        return MVS_ERR_INVALID_ARG;
+    if (q->n_frames > kLoopMaxFrames)
+        return MVS_ERR_CAPACITY;
+    if (min_gap < 1 || min_gap >= q->n_frames || ratio != ratio || max_dist != max_dist)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    q->loop_scored = q->loop_selected = q->loop_verified = false;
+    const size_t F = (size_t)q->n_frames;
+    const mvs_status st = ws_grow(ctx, q->loop_score, F * F * sizeof(int32_t));
+    if (st != MVS_OK)
+        return st;
+    const BatchDev &d = q->batch->d;
+    LoopDev &l = q->ld;
+    l.n_frames = q->n_frames, l.max_kp = d.max_kp, l.desc_words = d.desc_words;
+    l.desc = d.desc1, l.kp = d.kp1, l.oct = d.oct1, l.n_kp = d.n1, l.K = d.K, l.Kinv = d.Kinv;
+    l.score = q->loop_score.ptr<int32_t>();
+    HIP_TRY(ctx, launch_loop_scores(l, ratio, max_dist, min_gap, ctx->stream));
+    HIP_TRY(ctx, hipGetLastError());
+    q->loop_scored = true;
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_download_loop_scores(mvs_seq *q, int32_t *scores)
+{
+    if (!q || !scores || !q->loop_scored)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t F = (size_t)q->n_frames;
+    HIP_TRY(ctx, hipMemcpyAsync(scores, q->ld.score, F * F * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, sync_stream(ctx));
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_select_loops(mvs_seq *q, const mvs_loop_select_params *p)
+{
+    if (!q || !p || !q->loop_scored || p->min_score < 1 || p->top_k < 1 || p->max_candidates < 1)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    q->loop_selected = q->loop_verified = false;
+    const size_t F = (size_t)q->n_frames, C = (size_t)p->max_candidates;
+    const size_t top_k = (size_t)std::min(p->top_k, q->n_frames);   // a frame has fewer than n_frames base frames
+    Carve L{64};
+    const size_t o_counts = L.take(2 * 4), o_rown = L.take(F * 4), o_rowkey = L.take(F * top_k * 4);
+    const size_t o_cand = L.take(C * sizeof(mvs_loop_candidate));
+    const mvs_status st = ws_grow(ctx, q->loop_sel, L.total());
+    if (st != MVS_OK)
+        return st;
+    char *base = q->loop_sel.ptr();
+    LoopDev &l = q->ld;
+    l.min_score = p->min_score, l.top_k = (int)top_k, l.max_candidates = p->max_candidates;
+    l.counts = reinterpret_cast<int32_t *>(base + o_counts);
+    l.row_n = reinterpret_cast<int32_t *>(base + o_rown);
+    l.row_key = reinterpret_cast<int32_t *>(base + o_rowkey);
+    l.cand = reinterpret_cast<mvs_loop_candidate *>(base + o_cand);
+    launch_loop_select(l, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    q->loop_selected = true;
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_verify_loops(mvs_seq *q, const mvs_params *two_view, int essential, const mvs_refine_params *rp,
+                                double sigma_px)
+{
+    if (!q || !q->loop_selected || !refine_params_ok(rp) || !(sigma_px > 0.0))
+        return MVS_ERR_INVALID_ARG;
+    mvs_status st = check_params(two_view);
+    if (st != MVS_OK)
+        return st;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    q->loop_verified = false;
+    const LoopDev &l = q->ld;
+    if (q->loop_batch && q->loop_batch->d.n_pairs != l.max_candidates) {
+        mvs_batch_destroy(q->loop_batch);
+        q->loop_batch = nullptr;
+    }
+    if (!q->loop_batch &&
+        (st = batch_create_impl(ctx, l.max_candidates, l.max_kp, l.desc_words * 4, 0, &q->loop_batch)) != MVS_OK)
+        return st;
+    mvs_batch *b = q->loop_batch;
+    const Estimator est = essential ? Estimator::kFivePoint : Estimator::kEightPoint;
+    if ((st = ensure_tables(b, est, two_view->num_hypotheses)) != MVS_OK)
+        return st;
+    hipStream_t s = ctx->stream;
+    // the one host read between selection and verification: how many pairs the pipeline runs on
+    int32_t counts[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(counts, l.counts, sizeof(counts), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    const int kept = counts[0];
+    if (kept < 0 || kept > l.max_candidates) {
+        ctx->err = "mvs_seq_verify_loops: candidate count out of range";
+        return MVS_ERR_HIP;
+    }
+    // pairs past the kept ones are no candidates: their records read "invalid", so the refinement skips them
+    HIP_TRY(ctx, hipMemsetAsync(b->d.results + kept, 0, (size_t)(l.max_candidates - kept) * sizeof(mvs_pair_result), s));
+    if (kept > 0) {
+        launch_loop_gather(l, b->d, s);
+        HIP_TRY(ctx, hipGetLastError());
+        const RunParams run = to_run(*two_view);
+        if ((st = est == Estimator::kEightPoint ? enqueue_pipeline(b, run, kept, false, nullptr) : enqueue_essential(b, run, kept)) != MVS_OK)
+            return st;
+    }
+    if ((st = mvs_batch_refine(b, rp, sigma_px)) != MVS_OK)
+        return st;
+    q->loop_kept = kept;
+    q->loop_verified = true;
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_add_loop_edges(mvs_seq *q, const mvs_loop_edge_params *p)
+{
+    if (!q || !p)
+        return MVS_ERR_INVALID_ARG;
+    if (q->graph_built && q->loop_selected && (int64_t)q->gd.n_slots + q->ld.max_candidates > kPgMaxEdges)
+        return MVS_ERR_CAPACITY;
+    if (p->min_points < 0 || !(p->max_error >= 0.0) || p->loop_sigma[0] != p->loop_sigma[0] || p->loop_sigma[1] != p->loop_sigma[1] ||
+        !q->graph_built || !q->loop_verified)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const int need = q->gd.n_slots + q->ld.max_candidates;
+    if (q->graph_edge_cap < need) {
+        // the block was carved before this selection: a larger one, the graph's arrays copied over (the slots are scratch)
+        const size_t F = (size_t)q->n_frames, C = (size_t)q->graph_edge_cap;
+        const SeqGraphLayout Ln((size_t)q->gd.n_slots, (size_t)need, F);
+        void *np = nullptr;
+        HIP_TRY(ctx, hipMalloc(&np, Ln.total));
+        DevPtr fresh(np);
+        SeqGraphDev g = q->gd;
+        double *opt = Ln.point(g, static_cast<char *>(np));
+        int32_t *n_built = reinterpret_cast<int32_t *>(static_cast<char *>(np) + Ln.o_built);
+        const SeqGraphDev &o = q->gd;
+        const struct {
+            void *dst;
+            const void *src;
+            size_t bytes;
+        } parts[] = {{g.n_edges, o.n_edges, 4}, {g.edge_src, o.edge_src, C * 4}, {g.edge_dst, o.edge_dst, C * 4},
+                     {g.edge_lag, o.edge_lag, C * 4}, {g.edge_kind, o.edge_kind, C * 4}, {g.edge_scale, o.edge_scale, C * 8},
+                     {g.edge_pose, o.edge_pose, C * 96}, {g.edge_cov, o.edge_cov, C * 288}, {g.node_pose, o.node_pose, F * 96},
+                     {opt, q->graph_opt_pose, F * 96}, {n_built, q->graph_n_built, 4}};
+        for (const auto &pt : parts)
+            HIP_TRY(ctx, hipMemcpyAsync(pt.dst, pt.src, pt.bytes, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(ctx, sync_stream(ctx));   // the old block is freed
+        q->graph.p = std::move(fresh);
+        q->graph.bytes = Ln.total;
+        q->gd = g;
+        q->graph_opt_pose = opt;
+        q->graph_n_built = n_built;
+        q->graph_edge_cap = need;
+    }
+    if (!q->loop_edges_added)   // the first call behind a build: remember where the built edges end
+        HIP_TRY(ctx, hipMemcpyAsync(q->graph_n_built, q->gd.n_edges, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    LoopEdgeDev e{};
+    e.cand = q->ld.cand, e.counts = q->ld.counts;
+    e.results = q->loop_batch->d.results, e.refined = q->loop_batch->refine.out;
+    e.n_built = q->graph_n_built;
+    e.max_candidates = q->ld.max_candidates, e.min_points = p->min_points;
+    e.max_error = p->max_error;
+    for (int k = 0; k < 2; ++k) {
+        e.add[k] = p->loop_sigma[k] > 0.0;
+        e.var[k] = p->loop_sigma[k] * p->loop_sigma[k];
+    }
+    launch_loop_edges(q->gd, e, s);
+    HIP_TRY(ctx, hipGetLastError());
+    q->loop_edges_added = true;
+    q->graph_opt = false;
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_download_loop_candidates(mvs_seq *q, int32_t *n_kept, int32_t *n_found, mvs_loop_candidate *cand,
+                                            mvs_pair_result *results, mvs_match *matches, uint8_t *inlier_mask,
+                                            double *points_xyz, int64_t *point_idx, mvs_refine_result *refined)
+{
+    if (!q || !q->loop_selected)
+        return MVS_ERR_INVALID_ARG;
+    const bool pairs = results || matches || inlier_mask || points_xyz || point_idx;
+    if ((pairs || refined) && !q->loop_verified)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    int32_t counts[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(counts, q->ld.counts, sizeof(counts), hipMemcpyDeviceToHost, s));
+    if (cand)
+        HIP_TRY(ctx, hipMemcpyAsync(cand, q->ld.cand, (size_t)q->ld.max_candidates * sizeof(mvs_loop_candidate), hipMemcpyDeviceToHost, s));
+    if (refined && q->loop_kept > 0)
+        HIP_TRY(ctx, hipMemcpyAsync(refined, q->loop_batch->refine.out, (size_t)q->loop_kept * sizeof(mvs_refine_result),
+                                    hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    if (n_kept)
+        *n_kept = counts[0];
+    if (n_found)
+        *n_found = counts[1];
+    if (pairs && q->loop_kept > 0)
+        return mvs_batch_download(q->loop_batch, 0, q->loop_kept, results, matches, inlier_mask, points_xyz, point_idx);
     return MVS_OK;
 }
 }  // extern "C"

@@ -141,6 +141,18 @@ struct mvs_seq {
     double *graph_opt_pose = nullptr;   // [n_frames][12] in `graph`
     bool graph_built = false;   // the graph is that of the last run and its lags
     bool graph_opt = false;     // mvs_seq_optimize_pose_graph has succeeded on it
+    int graph_edge_cap = 0;     // rows of the graph's edge arrays: the build's slots, plus room for loop edges
+    int32_t *graph_n_built = nullptr;   // [1] in `graph`: edges of the built graph, behind which the loop edges go
+    // loop closures (mvs_seq_loop_scores .. mvs_seq_add_loop_edges): the score table, the selection's block (counts,
+    // per-frame rows, the list) and the batch that verifies the candidates, created at the first
+    // verification and replaced when max_candidates changes
+    DevWorkspace loop_score, loop_sel;
+    LoopDev ld{};
+    mvs_batch *loop_batch = nullptr;
+    int loop_kept = 0;                 // candidates the last verification ran on
+    bool loop_scored = false, loop_selected = false;
+    bool loop_verified = false;        // the batch holds the results of the current list
+    bool loop_edges_added = false;     // the graph's edges past *graph_n_built are loop edges
 };
 
 #define HIP_TRY(ctx_, expr)                                                                    \

@@ -483,6 +483,46 @@ struct SeqGraphDev {
 };
 void launch_seq_graph(const SeqGraphDev &g, hipStream_t stream);
 
+// ---- loop closures of a resident sequence (loop.hip, seq_graph.hip) ---------------------------
+constexpr int kLoopMaxFrames = 4096;
+struct LoopDev {
+    int n_frames, max_kp, desc_words;
+    // the sequence's frame arrays
+    const uint32_t *desc;              // [n_frames][N][desc_words]
+    const float *kp;                   // [n_frames][N][2]
+    const uint8_t *oct;                // [n_frames][N]
+    const int32_t *n_kp;               // [n_frames]
+    const double *K, *Kinv;            // [n_frames - 1][9] intrinsics of the sequence's pairs
+    int32_t *score;                    // [n_frames][n_frames], row i (base / train), column j (query); zero unless j - i >= min_gap
+    // selection (loop_select_rows_kernel, loop_select_compact_kernel)
+    int min_score, top_k, max_candidates;
+    int32_t *row_n;                    // [n_frames] candidates of query frame j (<= top_k)
+    int32_t *row_key;                  // [n_frames][top_k] score << 12 | (4095 - i), descending
+    mvs_loop_candidate *cand;          // [max_candidates], rows past the kept count zero
+    int32_t *counts;                   // {kept, found}: entries of the list, and of the list before the cut
+};
+// score[i][j] for every i <= j - min_gap, on a table cleared first (the status is that clear's: nothing is launched if it
+// fails).  desc_words 8: the FP4 matrix-core kernel; 4 and 16: popcount
+hipError_t launch_loop_scores(const LoopDev &d, double ratio, double max_dist, int min_gap, hipStream_t stream);
+void launch_loop_select(const LoopDev &d, hipStream_t stream);
+// pair c of `b` (a batch whose pairs own both images) = (frame cand[c].i, frame cand[c].j) for c < counts[0]: descriptors,
+// keypoints, octaves, counts, the intrinsics of the sequence's pair i and the sampler key offset c
+void launch_loop_gather(const LoopDev &d, const BatchDev &b, hipStream_t stream);
+// Appends one edge per accepted candidate behind the *n_built edges of the graph (seq_graph.hip): the rule of
+// seq_graph_edges_kernel with (k, k + d) = (i, j), plus var[0] / var[1] on the diagonal where add[0] / add[1]
+struct LoopEdgeDev {
+    mvs_loop_candidate *cand;          // the list; `accepted` is written
+    const int32_t *counts;             // {kept, found}
+    const mvs_pair_result *results;    // [max_candidates] of the verification batch
+    const mvs_refine_result *refined;  // [max_candidates]
+    const int32_t *n_built;            // [1] edges of the built graph
+    int max_candidates, min_points;
+    double max_error;
+    int add[2];
+    double var[2];
+};
+void launch_loop_edges(const SeqGraphDev &g, const LoopEdgeDev &e, hipStream_t stream);
+
 // ---- VisualFeature::extract (row f3): ORB-style extraction for a batch of equally sized images ----------------
 constexpr int kOrbMaxLevels = 16;
 constexpr int kOrbSelCap = 16384;    // keys of one (image, level) the selection can hold in LDS (128 KB): 2 n_l <= this, or the

@@ -10,6 +10,8 @@
 //   seq_graph_compact_kernel  one workgroup: exclusive prefix sum of the keep flags, tile of 256 slots by tile, and the
 //                             scatter of every kept slot to its place.  Integer scan, no atomics: the output order is the
 //                             slot order, ascending (d, k).
+//   loop_edges_kernel         one workgroup: the verified loop-closure candidates (loop.hip) through the same rule, appended
+//                             behind the built edges in candidate order.
 #include "kernels.hpp"
 
 namespace mvs {
@@ -179,7 +181,98 @@ __global__ __launch_bounds__(kSgThreads) void seq_graph_compact_kernel(SeqGraphD
         *g.n_edges = running;
 }
 
+// Loop-closure edges, one workgroup: candidate c = (i, j) of the verified list, tile of 256 by
+// tile.  The gates, the scale and S' = D S D are seq_graph_edges_kernel's with (k, k + d) = (i, j); then the loop variances go
+// on the diagonal and the Cholesky test runs on that final matrix.  The accepted candidates are appended behind the *n_built
+// edges of the graph in candidate order (the integer scan of seq_graph_compact_kernel) and *n_edges = *n_built + accepted.
+__global__ __launch_bounds__(kSgThreads) void loop_edges_kernel(SeqGraphDev g, LoopEdgeDev e)
+{
+    __shared__ int s_wave[kSgThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n_cand = min(e.counts[0], e.max_candidates);
+    int running = *e.n_built;
+    for (int base = 0; base < n_cand; base += kSgThreads) {
+        const int c = base + tid;
+        int keep = 0, ci = 0, cj = 0;
+        double s = 0.0, t0 = 0.0, t1 = 0.0, t2 = 0.0;
+        if (c < n_cand) {
+            ci = e.cand[c].i, cj = e.cand[c].j;
+            const mvs_pair_result &pr = e.results[c];
+            const mvs_refine_result &rr = e.refined[c];
+            if (pr.valid && rr.ok && pr.n_points >= e.min_points && rr.error <= e.max_error) {
+                const double *Ri = g.traj_R + 9 * (int64_t)ci, *ti = g.traj_t + 3 * (int64_t)ci, *tj = g.traj_t + 3 * (int64_t)cj;
+                const double d0 = tj[0] - ti[0], d1 = tj[1] - ti[1], d2 = tj[2] - ti[2];
+                double q[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    q[k] = (Ri[k] * d0 + Ri[3 + k] * d1) + Ri[6 + k] * d2;
+                t0 = rr.t[0], t1 = rr.t[1], t2 = rr.t[2];
+                s = sqrt((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) / sqrt((t0 * t0 + t1 * t1) + t2 * t2);
+                if (s > 0.0 && s < __builtin_inf()) {
+                    double S[21];
+#pragma unroll
+                    for (int r = 0; r < 6; ++r)
+#pragma unroll
+                        for (int cc = 0; cc <= r; ++cc) {
+                            double v = ((r < 3 ? 1.0 : s) * rr.pose_cov[6 * r + cc]) * (cc < 3 ? 1.0 : s);
+                            if (r == cc && e.add[r / 3])
+                                v = v + e.var[r / 3];
+                            S[lidx(r, cc)] = v;
+                        }
+                    keep = chol6_ok(S) ? 1 : 0;
+                }
+            }
+        }
+        const unsigned long long bal = __ballot(keep != 0);
+        const int before = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0)
+            s_wave[wave] = __popcll(bal);
+        __syncthreads();
+        int pos = running + before, total = 0;
+#pragma unroll
+        for (int w = 0; w < kSgThreads / 64; ++w) {
+            pos += w < wave ? s_wave[w] : 0;
+            total += s_wave[w];
+        }
+        if (c < n_cand)
+            e.cand[c].accepted = keep;
+        if (keep) {
+            const mvs_refine_result &rr = e.refined[c];
+            g.edge_src[pos] = ci;
+            g.edge_dst[pos] = cj;
+            g.edge_lag[pos] = cj - ci;
+            g.edge_kind[pos] = 2;
+            g.edge_scale[pos] = s;
+            double *Zo = g.edge_pose + 12 * (int64_t)pos, *Co = g.edge_cov + 36 * (int64_t)pos;
+#pragma unroll
+            for (int k = 0; k < 9; ++k)
+                Zo[k] = rr.R[k];
+            Zo[9] = s * t0;
+            Zo[10] = s * t1;
+            Zo[11] = s * t2;
+#pragma unroll
+            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                for (int cc = 0; cc < 6; ++cc) {
+                    double v = ((r < 3 ? 1.0 : s) * rr.pose_cov[6 * r + cc]) * (cc < 3 ? 1.0 : s);
+                    if (r == cc && e.add[r / 3])
+                        v = v + e.var[r / 3];
+                    Co[6 * r + cc] = v;
+                }
+        }
+        running += total;
+        __syncthreads();   // s_wave is rewritten by the next tile
+    }
+    if (tid == 0)
+        *g.n_edges = running;
+}
+
 }  // namespace
+
+void launch_loop_edges(const SeqGraphDev &g, const LoopEdgeDev &e, hipStream_t stream)
+{
+    hipLaunchKernelGGL(loop_edges_kernel, dim3(1), dim3(kSgThreads), 0, stream, g, e);
+}
 
 void launch_seq_graph(const SeqGraphDev &g, hipStream_t stream)
 {

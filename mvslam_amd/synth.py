@@ -102,10 +102,21 @@ def make_sequence(n_frames, n_kp=2000, n_map=20000, noise_px=0.5, flip_p=0.02, s
     `n_map` points; every frame keeps up to 0.8 * n_kp visible map points (noisy projections, the point's descriptor
     with per-frame bit flips) and pads to n_kp with clutter.  Returns desc [F, n_kp, B], kp [F, n_kp, 2] float32,
     n_kp [F], K, and the ground-truth camera poses (R_w2c, t_w2c) per frame."""
+    return _render_sequence(n_frames, step * n_frames, lambda f: (yaw_step * f, _path_centre(step, f)), n_kp, n_map, noise_px,
+                            flip_p, seed, width, height, desc_bytes, K)
+
+
+def _path_centre(step, f):
+    """camera centre at position f of make_sequence's path (f need not be an integer)"""
+    return np.array([0.5 * step * f, 0.0, step * f * 0.866])
+
+
+def _render_sequence(n_frames, L, pose_of, n_kp, n_map, noise_px, flip_p, seed, width, height, desc_bytes, K):
+    """the persistent map and noise model of make_sequence for any trajectory: pose_of(f) = (yaw, camera centre); L = the
+    length of the path, which sizes the corridor the map lies in.  One generator, drawn from in a fixed order."""
     rng = np.random.default_rng(seed)
     nbits = desc_bytes * 8
     # the map lies in a corridor in front of the trajectory
-    L = step * n_frames
     Xw = np.stack([rng.uniform(-6, 6 + 0.5 * L, n_map), rng.uniform(-3, 3, n_map), rng.uniform(2, 12 + L, n_map)], axis=1)
     map_bits = rng.integers(0, 2, size=(n_map, nbits), dtype=np.uint8)
     desc = np.empty((n_frames, n_kp, desc_bytes), dtype=np.uint8)
@@ -113,9 +124,8 @@ def make_sequence(n_frames, n_kp=2000, n_map=20000, noise_px=0.5, flip_p=0.02, s
     poses = []
     n_vis_max = int(0.8 * n_kp)
     for f in range(n_frames):
-        yaw = yaw_step * f
+        yaw, c = pose_of(f)
         R = np.array([[np.cos(yaw), 0, -np.sin(yaw)], [0, 1, 0], [np.sin(yaw), 0, np.cos(yaw)]])   # world -> camera
-        c = np.array([0.5 * step * f, 0.0, step * f * 0.866])                                      # camera centre
         t = -R @ c
         Xc = (R @ Xw.T).T + t
         z = Xc[:, 2]
@@ -138,3 +148,28 @@ def make_sequence(n_frames, n_kp=2000, n_map=20000, noise_px=0.5, flip_p=0.02, s
         desc[f] = np.packbits(fb[perm], axis=1, bitorder="little")
         poses.append((R, t))
     return dict(desc=desc, kp=kp, n_kp=np.full(n_frames, n_kp, dtype=np.int32), K=K.copy(), poses=poses)
+
+
+def make_loop_sequence(n_frames, shift=0.1, n_kp=2000, n_map=20000, noise_px=0.5, flip_p=0.02, seed=0x5E9, width=640,
+                       height=480, desc_bytes=32, K=K_DEFAULT, step=0.05, yaw_step=0.005):
+    """A sequence that comes back: frames 0 .. H - 1 (H = ceil(n_frames / 2)) run out along make_sequence's path, frames
+    H .. n_frames - 1 run back over positions H - 1, H - 2, ... on a track moved `shift` m sideways (at right angles to the
+    path, level), looking the way the outbound frame at that position looked.  Frame f >= H revisits frame 2 H - 1 - f with
+    a baseline of `shift`: a loop closure with a two-view geometry.  Same map,
+    noise model and outputs as make_sequence, plus `revisit` [n_frames]: the outbound frame a frame revisits (-1: none)."""
+    H = (n_frames + 1) // 2
+    side = np.array([0.866, 0.0, -0.5])
+    side *= shift / np.linalg.norm(side)
+    revisit = np.full(n_frames, -1, dtype=np.int32)
+    for f in range(H, n_frames):
+        revisit[f] = 2 * H - 1 - f
+
+    def pose_of(f):
+        if f < H:
+            return yaw_step * f, _path_centre(step, f)
+        g = int(revisit[f])
+        return yaw_step * g, _path_centre(step, g) + side
+
+    out = _render_sequence(n_frames, step * H, pose_of, n_kp, n_map, noise_px, flip_p, seed, width, height, desc_bytes, K)
+    out["revisit"] = revisit
+    return out
