@@ -118,9 +118,13 @@ mvs_status mvs_ctx_create_on_stream(int device_id, void *hip_stream, mvs_ctx **o
 void mvs_ctx_destroy(mvs_ctx *ctx);
 void *mvs_ctx_stream(mvs_ctx *ctx); /* hipStream_t the kernels are launched on */
 /* A batch of >= 64 pairs goes down the pipeline as two independent halves, the second on a context-owned side stream that is
- * forked from and joined back into the context's stream inside the call (the caller sees one stream; results are identical:
- * pairs are independent, estimator-RANSAC.cpp:76-84 runs per pair).  enable = 0 keeps every launch on the one stream.
- * Default: enabled. */
+ * forked from the context's stream (results are identical: pairs are independent, estimator-RANSAC.cpp:76-84 runs per pair).
+ * The side stream is joined back into the context's stream on demand: by the next call on this context that uses the stream
+ * for anything but the same run again -- upload, download, copy, refine, stats, timing, sync, destroy, any other entry point
+ * -- so back-to-back runs of a resident batch overlap one call's tail with the next call's kernels, and every result a call
+ * of this library hands out is complete.  A caller who can enqueue work of their own on the stream sees one stream, as
+ * before: if the stream was borrowed (mvs_ctx_create_on_stream) or mvs_ctx_stream() has ever been called on this context, the
+ * join happens inside every run, before it returns.  enable = 0 keeps every launch on the one stream.  Default: enabled. */
 mvs_status mvs_ctx_set_half_batches(mvs_ctx *ctx, int enable);
 /* Confidence level of the five-point essential-matrix RANSAC (the reference's VF_MATCH_CONFIDENCE_LEVEL = 0.99,
  * sfm-solve.cpp:22-23,58), honoured by mvs_ransac_essential, mvs_two_view_essential and mvs_batch_run_points_essential; the

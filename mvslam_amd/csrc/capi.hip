@@ -15,10 +15,28 @@
 
 using namespace mvs_host;
 
-// every wait for the ctx stream goes through here: once it has drained nothing reads or writes the arena any more
+// Joins the open side lane of a halves run into the context's stream (enqueue_pipeline leaves it open; ctx_stream is the one
+// caller outside it).  Whatever fails, nothing is left running unjoined: without an event edge the lane is waited for on the
+// host -- a later download or a release of the groups must never race with the second half.
+hipError_t mvs_host::close_lane(mvs_ctx *ctx)
+{
+    if (!ctx->lane_open)
+        return hipSuccess;
+    ctx->lane_open = false;
+    ctx->lane_batch = nullptr;
+    hipError_t e = hipEventRecord(ctx->ev_join, ctx->side);
+    if (e == hipSuccess)
+        e = hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0);
+    if (e != hipSuccess)
+        (void)hipStreamSynchronize(ctx->side);
+    return e;
+}
+
+// every wait for the ctx stream goes through here (an open side lane is joined first: ctx_stream): once it has drained nothing
+// reads or writes the arena any more
 hipError_t mvs_host::sync_stream(mvs_ctx *ctx)
 {
-    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    const hipError_t e = hipStreamSynchronize(ctx_stream(ctx));
     if (e == hipSuccess)
         ctx->pin_in_flight = false;
     return e;
@@ -77,7 +95,7 @@ static mvs_status up_async(mvs_ctx *ctx, void *dst, const void *src, size_t byte
 {
     void *p = pin_put(ctx, src, bytes);
     PIN_TRY(ctx, p);
-    HIP_TRY(ctx, hipMemcpyAsync(dst, p, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dst, p, bytes, hipMemcpyHostToDevice, ctx_stream(ctx)));
     return MVS_OK;
 }
 
@@ -226,7 +244,7 @@ static mvs_status ensure_tables(mvs_batch *b, Estimator est, int num_hypotheses)
 // model stage + its finalize mode for pairs [0, n) on the ctx stream, plain launches (the tables are grown: ensure_tables)
 static void enqueue_model(mvs_batch *b, Estimator est, const RunParams &rp, int n)
 {
-    hipStream_t s = b->ctx->stream;
+    hipStream_t s = ctx_stream(b->ctx);
     switch (est) {
     case Estimator::kEightPoint:
         launch_ransac(b->d, rp, n, false, s);
@@ -274,9 +292,9 @@ static mvs_status alloc_refine(mvs_ctx *ctx, DevBlocks &owner, RefineDev &d, int
     if (st != MVS_OK)
         return st;
     // rows [m, stride) of a problem are never written: zero, so that a download is the same bytes wherever the block came from
-    HIP_TRY(ctx, hipMemsetAsync(r.pts, 0, T * S * 3 * sizeof(double), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(r.pts, 0, T * S * 3 * sizeof(double), ctx_stream(ctx)));
     if (r.point_cov)
-        HIP_TRY(ctx, hipMemsetAsync(r.point_cov, 0, T * S * 9 * sizeof(double), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(r.point_cov, 0, T * S * 9 * sizeof(double), ctx_stream(ctx)));
     d = r;
     return MVS_OK;
 }
@@ -334,6 +352,7 @@ mvs_status mvs_ctx_create_on_stream(int device_id, void *hip_stream, mvs_ctx **o
     }
     if (hip_stream) {
         c->stream = static_cast<hipStream_t>(hip_stream);
+        c->caller_sees_stream = true;
     } else {
         if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
             delete c;
@@ -362,7 +381,9 @@ mvs_status mvs_ctx_create_on_stream(int device_id, void *hip_stream, mvs_ctx **o
     if (ws_grow(c, c->small, 128 * sizeof(double)) != MVS_OK ||
         hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_dense[0], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_dense[1], hipEventDisableTiming) != hipSuccess) {
         mvs_ctx_destroy(c);
         return MVS_ERR_HIP;
     }
@@ -389,12 +410,20 @@ void mvs_ctx_destroy(mvs_ctx *ctx)
     }
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
+    for (hipEvent_t e : ctx->ev_dense)
+        if (e) (void)hipEventDestroy(e);
     if (ctx->own_stream)
         (void)hipStreamDestroy(ctx->stream);
     delete ctx;   // the workspaces' destructors free them
 }
 
-void *mvs_ctx_stream(mvs_ctx *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
+void *mvs_ctx_stream(mvs_ctx *ctx)
+{
+    if (!ctx)
+        return nullptr;
+    ctx->caller_sees_stream = true;   // from now on every halves run joins before it returns
+    return (void *)ctx_stream(ctx);
+}
 
 mvs_status mvs_ctx_set_half_batches(mvs_ctx *ctx, int enable)
 {
@@ -420,7 +449,7 @@ mvs_status mvs_ctx_essential_hypotheses_run(mvs_ctx *ctx, int32_t *n_run)
     if (ctx->e5_single == 0)
         return MVS_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpyAsync(n_run, ctx->scratch->e5_nrun, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(n_run, ctx->scratch->e5_nrun, sizeof(int32_t), hipMemcpyDeviceToHost, ctx_stream(ctx)));
     HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }
@@ -522,7 +551,7 @@ static mvs_status batch_create_impl(mvs_ctx *ctx, int n_pairs, int max_kp, int d
     d.desc1 = desc1; d.desc2 = desc2; d.kp1 = kp1; d.kp2 = kp2; d.n1 = n1; d.n2 = n2;
     d.oct1 = oct1; d.oct2 = oct2;
     d.Kinv = Kinv; d.K = K; d.gidx = gidx;   // the RANSAC stage's blocks stay null until ensure_groups
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     // deterministic contents for rows the caller never uploads
     if (!frames_of) {
         (void)hipMemsetAsync(desc1, 0, NI * N * d.desc_words * 4, s);
@@ -581,7 +610,7 @@ static mvs_status batch_upload_impl(mvs_batch *b, int first, int count, const ui
     mvs_ctx *ctx = b->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const BatchDev &d = b->d;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     const size_t N = d.max_kp, DW = d.desc_words;
     if (n_base)
         for (int i = 0; i < count; ++i)
@@ -711,8 +740,9 @@ static BatchDev batch_view(const BatchDev &b, int first, int count, int half)
 constexpr int kHalvesMinPairs = 64;   // a batch of at least this many pairs runs as two halves on two streams
 
 static void enqueue_stages(const BatchDev &d, const RunParams &rp, int n_active, bool stats, hipStream_t s, hipEvent_t *ev,
-                           LaunchTimer *lt, bool with_match = true)
+                           LaunchTimer *lt, bool with_match = true, hipEvent_t wait_for = nullptr, hipEvent_t after_dense = nullptr)
 {
+    if (wait_for) (void)hipStreamWaitEvent(s, wait_for, 0);
     if (ev) (void)hipEventRecord(ev[0], s);
     if (with_match)
         launch_match_topk(d, rp, n_active, s, lt);
@@ -720,7 +750,7 @@ static void enqueue_stages(const BatchDev &d, const RunParams &rp, int n_active,
     if (with_match)
         launch_match_compact(d, rp, n_active, s, lt);
     if (ev) (void)hipEventRecord(ev[2], s);
-    launch_ransac(d, rp, n_active, stats, s, lt);
+    launch_ransac(d, rp, n_active, stats, s, lt, after_dense);
     if (ev) (void)hipEventRecord(ev[3], s);
     launch_finalize(d, rp, n_active, kFinalizeFull, s, lt);
     if (ev) (void)hipEventRecord(ev[4], s);
@@ -730,33 +760,54 @@ static mvs_status enqueue_pipeline(mvs_batch *b, const RunParams &rp, int n_acti
                                    LaunchTimer *lt = nullptr, bool with_match = true)
 {
     mvs_ctx *ctx = b->ctx;
-    hipStream_t s = ctx->stream;
     const bool halves = n_active >= kHalvesMinPairs && !stats && !ev && !lt && !b->d.hyp_count && ctx->half_batches;
     if (!halves) {
-        enqueue_stages(b->d, rp, n_active, stats, s, ev, lt, with_match);
+        enqueue_stages(b->d, rp, n_active, stats, ctx_stream(ctx), ev, lt, with_match);
     } else {
-        // two independent halves: the second on the side stream, after everything already queued on the main stream, and
-        // joined back into it (the caller's next operation on the main stream sees both).  Measured on the bench batch:
-        // 2 parts +2.2 % pairs/s, +10 % frames/s on the sequence; 3 and 4 parts, a 40:60 split and a lower or higher
-        // priority of the side stream are all within noise of or below two equal halves.  The kernel trace shows the heavy
-        // kernels of the two halves serialising or sharing the chip at the same total rate and the two latency-bound tails
-        // (list sort ... selection ... triangulation, ~0.8 ms per half whatever its size) largely coinciding; holding the
-        // second half's counting back with an event until the first half's dense phase has drained puts it under the first
-        // half's tail but leaves the second tail exposed: same step time within 1 % (measured, not kept).
+        // Two independent halves, one per lane: the first on the context's stream, the second on the side stream.  This is the
+        // one place that reads the two streams directly.  The side lane is NOT joined back here: it stays open, and whatever
+        // uses the context's stream next joins it first (ctx_stream) -- unless that is this very run again (same batch, same
+        // pairs, nothing in between), whose halves touch exactly what the same lane's previous half touched (batch_view: every
+        // per-pair array and both per-launch scalars belong to one half) and so need their own lane's order only.
+        // The lanes alternate: a half's throughput section (match ... dense count) waits for the event the other lane records
+        // behind its latest dense count, so the heavy sections run one after the other at full chip width and the latency-bound
+        // tail of a half (list sort ... selection ... triangulation, ~0.8 ms whatever its size) runs under the other lane's
+        // heavy section -- the last one under the NEXT call's.  Only a run that continues an open lane is chained (below).  Measured on the bench batch (ms per step, three runs each,
+        // parent and change alternating): joined inside every call 4.378-4.402, free-running open lanes 4.220-4.238 (they fall
+        // into lock-step, both tails coincide again), alternating open lanes 4.121-4.176 (kept).  A caller who sees the stream
+        // gets the parent's arrangement unchanged: two free halves, joined before the call returns.
+        // Inside one call (measured earlier): 2 parts +2.2 % pairs/s, +10 % frames/s on the sequence; 3 and 4 parts, a 40:60
+        // split and a lower or higher priority of the side stream are all within noise of or below two halves.
+        if (ctx->lane_open && (ctx->lane_batch != b || ctx->lane_pairs != n_active))
+            (void)close_lane(ctx);   // another batch shares the workspaces, another count moves the split
+        hipStream_t s = ctx->stream;
         const int na = (n_active + 1) / 2;
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, s));          // nothing is on the side stream yet: a plain return is safe
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-        enqueue_stages(batch_view(b->d, 0, na, 0), rp, na, false, s, nullptr, nullptr, with_match);
+        const bool repeat = ctx->lane_open;
+        if (!repeat) {
+            // the second half waits for whatever is on the main stream (uploads, ...); nothing of this call is on the side
+            // stream yet: a plain return is safe
+            HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, s));
+            HIP_TRY(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+        }
+        // The chain of dense-count events exists between calls only: the first run behind a join is two free halves, as it
+        // has always been -- that is the whole of a run that something joins at once (a sequence's pairs, a lag, an upload /
+        // run / download loop) -- and records the events the next run's halves wait for.
+        const bool chain = repeat && !ctx->caller_sees_stream;
+        const bool record = !ctx->caller_sees_stream;
+        enqueue_stages(batch_view(b->d, 0, na, 0), rp, na, false, s, nullptr, nullptr, with_match,
+                       chain ? ctx->ev_dense[1] : nullptr, record ? ctx->ev_dense[0] : nullptr);
         const hipError_t e_first = hipGetLastError();            // a launch failure of the first half, attributed to it
-        enqueue_stages(batch_view(b->d, na, n_active - na, 1), rp, n_active - na, false, ctx->side, nullptr, nullptr, with_match);
+        // from here on work may be queued on the side stream: the lane is open, and whatever fails it is joined before this
+        // call returns
+        ctx->lane_open = true;
+        ctx->lane_batch = b;
+        ctx->lane_pairs = n_active;
+        enqueue_stages(batch_view(b->d, na, n_active - na, 1), rp, n_active - na, false, ctx->side, nullptr, nullptr, with_match,
+                       chain ? ctx->ev_dense[0] : nullptr, record ? ctx->ev_dense[1] : nullptr);
         const hipError_t e_second = hipGetLastError();
-        // from here on work may be queued on the side stream: whatever fails, the caller's stream joins it before this call
-        // returns (a later download or a release of the groups must never race with the second half) -- ADVICE r4
-        hipError_t e_join = hipEventRecord(ctx->ev_join, ctx->side);
-        if (e_join == hipSuccess)
-            e_join = hipStreamWaitEvent(s, ctx->ev_join, 0);
-        if (e_join != hipSuccess)
-            (void)hipStreamSynchronize(ctx->side);               // no event edge: wait for the half on the host instead
+        hipError_t e_join = hipSuccess;
+        if (ctx->caller_sees_stream || e_first != hipSuccess || e_second != hipSuccess)
+            e_join = close_lane(ctx);
         HIP_TRY(ctx, e_first);
         HIP_TRY(ctx, e_second);
         HIP_TRY(ctx, e_join);
@@ -804,7 +855,7 @@ static mvs_status stage_batch_points(mvs_batch *b, Estimator est, const mvs_para
         if ((st = DevGroup(ctx, b->blocks).add(b->uv1, count).add(b->uv2, count).commit()) != MVS_OK)
             return st;
     }
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     const size_t pb = (size_t)n_active * N * 2 * sizeof(double);
     HIP_TRY(ctx, hipMemcpyAsync(b->uv1, uv1, pb, hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemcpyAsync(b->uv2, uv2, pb, hipMemcpyHostToDevice, s));
@@ -851,7 +902,7 @@ mvs_status mvs_batch_run_points_essential(mvs_batch *b, const mvs_params *params
 // launches.
 static mvs_status enqueue_essential(mvs_batch *b, const RunParams &rp, int n)
 {
-    hipStream_t s = b->ctx->stream;
+    hipStream_t s = ctx_stream(b->ctx);
     launch_match_topk(b->d, rp, n, s);
     launch_match_compact(b->d, rp, n, s);
     enqueue_model(b, Estimator::kFivePoint, rp, n);
@@ -885,7 +936,7 @@ mvs_status mvs_batch_download_hypotheses_run(mvs_batch *b, int first, int count,
     if (reached < 1)
         return MVS_OK;
     HIP_TRY(ctx, hipMemcpyAsync(n_run, b->e5_nrun + first, (size_t)reached * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                ctx->stream));
+                                ctx_stream(ctx)));
     HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }
@@ -908,14 +959,14 @@ mvs_status mvs_batch_download_essential_tables(mvs_batch *b, int first, int coun
         if (n_roots) {
             int32_t *dst = n_roots + (size_t)p * H;
             if (T)
-                HIP_TRY(ctx, hipMemcpyAsync(dst, b->e5_nroots + row, T * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(dst, b->e5_nroots + row, T * sizeof(int32_t), hipMemcpyDeviceToHost, ctx_stream(ctx)));
             std::fill(dst + T, dst + H, 0);
         }
         if (count_tbl) {
             int32_t *dst = count_tbl + (size_t)p * H * kE5MaxRoots;
             if (T)
                 HIP_TRY(ctx, hipMemcpyAsync(dst, b->e5_count + row * kE5MaxRoots, T * kE5MaxRoots * sizeof(int32_t),
-                                            hipMemcpyDeviceToHost, ctx->stream));
+                                            hipMemcpyDeviceToHost, ctx_stream(ctx)));
             std::fill(dst + T * kE5MaxRoots, dst + H * kE5MaxRoots, -1);
         }
     }
@@ -945,16 +996,16 @@ mvs_status mvs_batch_time(mvs_batch *b, const mvs_params *params, int n_active, 
     if (st != MVS_OK)
         return st;
     const RunParams rp = to_run(*params);
-    hipStream_t s = ctx->stream;
     for (int i = 0; i < warmup; ++i)
         if ((st = enqueue_pipeline(b, rp, n_active, false, nullptr)) != MVS_OK)
             return st;
     HIP_TRY(ctx, sync_stream(ctx));
-    HIP_TRY(ctx, hipEventRecord(b->ev[5], s));
+    // the two events bracket both lanes: the first run forks behind ev[5], ctx_stream joins the open lane in front of ev[6]
+    HIP_TRY(ctx, hipEventRecord(b->ev[5], ctx_stream(ctx)));
     for (int i = 0; i < steps; ++i)
         if ((st = enqueue_pipeline(b, rp, n_active, false, nullptr)) != MVS_OK)
             return st;
-    HIP_TRY(ctx, hipEventRecord(b->ev[6], s));
+    HIP_TRY(ctx, hipEventRecord(b->ev[6], ctx_stream(ctx)));
     HIP_TRY(ctx, hipEventSynchronize(b->ev[6]));
     if (ms_total)
         HIP_TRY(ctx, hipEventElapsedTime(ms_total, b->ev[5], b->ev[6]));
@@ -1005,7 +1056,7 @@ mvs_status mvs_batch_time_kernels(mvs_batch *b, const mvs_params *params, int n_
     for (int k = 0; k < cap; ++k)
         ms[k] = 0.f;
     for (int i = 0; i < steps && st == MVS_OK; ++i) {
-        LaunchTimer lt{ctx->stream, ev, kid, cap, 0};
+        LaunchTimer lt{ctx_stream(ctx), ev, kid, cap, 0};
         st = enqueue_pipeline(b, rp, n_active, false, nullptr, &lt);
         if (st != MVS_OK)
             break;
@@ -1046,7 +1097,7 @@ mvs_status mvs_kernel_info_get(mvs_ctx *ctx, int index, int max_kp, int desc_byt
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::memset(out, 0, sizeof(*out));
     std::snprintf(out->name, sizeof(out->name), "%s", kd.name);
-    const char *sym = hipKernelNameRefByPtr(kd.fn, ctx->stream);
+    const char *sym = hipKernelNameRefByPtr(kd.fn, ctx_stream(ctx));
     std::snprintf(out->symbol, sizeof(out->symbol), "%s", sym ? sym : "");
     hipFuncAttributes fa;
     HIP_TRY(ctx, hipFuncGetAttributes(&fa, kd.fn));
@@ -1071,7 +1122,7 @@ static mvs_status batch_download_enqueue(mvs_batch *b, int first, int count, mvs
                                          uint8_t *inlier_mask, double *points_xyz, int32_t *point_idx32)
 {
     mvs_ctx *ctx = b->ctx;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     const BatchDev &d = b->d;
     const size_t N = d.max_kp, off = first, cnt = count;
     if (results)
@@ -1146,7 +1197,7 @@ mvs_status mvs_batch_gather_results(mvs_batch *b, int n_active, void *rccl_comm,
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int rc = fn(b->d.results, dst_device, (size_t)n_active * sizeof(mvs_pair_result), /* ncclUint8 */ 1, rccl_comm,
-                      ctx->stream);
+                      ctx_stream(ctx));
     if (rc != 0) {
         ctx->err = std::string("ncclAllGather: ") + (es ? es(rc) : "error");
         return MVS_ERR_HIP;
@@ -1166,7 +1217,7 @@ mvs_status mvs_batch_stats(mvs_batch *b, const mvs_params *params, int n_active,
     st = ensure_groups(b, params->num_hypotheses);
     if (st != MVS_OK)
         return st;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     HIP_TRY(ctx, hipMemsetAsync(b->d.stats, 0, 16 * sizeof(unsigned long long), s));
     st = enqueue_pipeline(b, to_run(*params), n_active, true, nullptr);
     if (st != MVS_OK)
@@ -1262,7 +1313,7 @@ mvs_status mvs_batch_copy_results_device(mvs_batch *b, int first, int count, voi
         return MVS_ERR_INVALID_ARG;
     HIP_TRY(b->ctx, hipSetDevice(b->ctx->device));
     HIP_TRY(b->ctx, hipMemcpyAsync(dst_device, b->d.results + first, (size_t)count * sizeof(mvs_pair_result),
-                                   hipMemcpyDeviceToDevice, b->ctx->stream));
+                                   hipMemcpyDeviceToDevice, ctx_stream(b->ctx)));
     return MVS_OK;
 }
 
@@ -1279,7 +1330,7 @@ static mvs_status ensure_scratch(mvs_ctx *ctx, int max_kp, int desc_bytes)
         max_kp = std::max(max_kp, ctx->scratch->d.max_kp);
         if (ctx->e5_single == 1) {   // mvs_ctx_essential_hypotheses_run outlives the batch it would read
             HIP_TRY(ctx, hipMemcpyAsync(&ctx->e5_single_run, ctx->scratch->e5_nrun, sizeof(int32_t), hipMemcpyDeviceToHost,
-                                        ctx->stream));
+                                        ctx_stream(ctx)));
             HIP_TRY(ctx, sync_stream(ctx));
             ctx->e5_single = 0;
         }
@@ -1308,7 +1359,7 @@ static mvs_status stage_points(mvs_ctx *ctx, const double *p1_uv, const double *
     if ((st = ws_grow(ctx, ctx->uv, 2 * half * sizeof(double))) != MVS_OK)
         return st;
     double *d_uv1 = ctx->uv.ptr<double>(), *d_uv2 = d_uv1 + half;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     double kinv[9];
     mat3_inverse(K, kinv);
     const int64_t zero = 0;
@@ -1334,7 +1385,7 @@ static mvs_status fetch_single(mvs_ctx *ctx, int m, mvs_pair_result *res, double
                                uint8_t *mask, mvs_match *matches = nullptr)
 {
     mvs_batch *b = ctx->scratch;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     const size_t rows = (size_t)std::max(m, 0);
     // pair 0's outputs gathered on the device into one block, ONE copy to the pinned arena
     const int flags = ((mask && rows) ? 1 : 0) | ((points_xyz && rows) ? 2 : 0) | ((point_idx && rows) ? 4 : 0) |
@@ -1385,7 +1436,7 @@ mvs_status mvs_match_hamming(mvs_ctx *ctx, const uint8_t *train_desc, int n_trai
     if (st != MVS_OK)
         return st;
     mvs_batch *b = ctx->scratch;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     const int32_t n1 = n_train, n2 = n_query;
     const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     const size_t cap = (size_t)std::min(n_train, n_query);   // a query matches at most once
@@ -1542,7 +1593,7 @@ static mvs_status image_pair_impl(mvs_ctx *ctx, Estimator est, const uint8_t *ba
         std::memcpy(h_in + o_desc2, pair_desc, db2);
         std::memcpy(h_in + o_kp1, base_kp, kb1);
         std::memcpy(h_in + o_kp2, pair_kp, kb2);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->single_in.ptr(), h_in, total, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->single_in.ptr(), h_in, total, hipMemcpyHostToDevice, ctx_stream(ctx)));
         SingleParams sp;
         sp.n1 = n1;
         sp.n2 = n2;
@@ -1553,7 +1604,7 @@ static mvs_status image_pair_impl(mvs_ctx *ctx, Estimator est, const uint8_t *ba
         }
         sp.part_bytes[0] = (uint32_t)db1; sp.part_bytes[1] = (uint32_t)db2;
         sp.part_bytes[2] = (uint32_t)kb1; sp.part_bytes[3] = (uint32_t)kb2;
-        launch_single_params(b->d, sp, ctx->single_in.ptr(), ctx->stream);
+        launch_single_params(b->d, sp, ctx->single_in.ptr(), ctx_stream(ctx));
     }
     st = est == Estimator::kEightPoint ? enqueue_pipeline(b, to_run(*params), 1, false, nullptr)
                                        : enqueue_essential(b, to_run(*params), 1);
@@ -1588,9 +1639,9 @@ static mvs_status upload_mask(mvs_ctx *ctx, const uint8_t *mask, int m)
 {
     mvs_batch *b = ctx->scratch;
     if (mask) {   // the caller's buffer outlives the call: every entry point synchronises before it returns
-        HIP_TRY(ctx, hipMemcpyAsync(b->d.mask, mask, (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(b->d.mask, mask, (size_t)m, hipMemcpyHostToDevice, ctx_stream(ctx)));
     } else {
-        HIP_TRY(ctx, hipMemsetAsync(b->d.mask, 1, (size_t)m, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(b->d.mask, 1, (size_t)m, ctx_stream(ctx)));
     }
     return MVS_OK;
 }
@@ -1617,7 +1668,7 @@ mvs_status mvs_triangulate(mvs_ctx *ctx, const double *p1_uv, const double *p2_u
         return st;
     RunParams rp{};
     rp.num_hypotheses = 1;
-    launch_finalize(b->d, rp, 1, kFinalizeTriangulate, ctx->stream);
+    launch_finalize(b->d, rp, 1, kFinalizeTriangulate, ctx_stream(ctx));
     st = fetch_single(ctx, m, &res, points_xyz, point_idx, nullptr);
     if (st != MVS_OK)
         return st;
@@ -1647,7 +1698,7 @@ mvs_status mvs_recover_pose(mvs_ctx *ctx, const double E[9], const double *p1_uv
         return st;
     RunParams rp{};
     rp.num_hypotheses = 1;
-    launch_finalize(b->d, rp, 1, kFinalizeFromE, ctx->stream);
+    launch_finalize(b->d, rp, 1, kFinalizeFromE, ctx_stream(ctx));
     st = fetch_single(ctx, m, &res, points_xyz, point_idx, nullptr);
     if (st != MVS_OK)
         return st;
@@ -1659,7 +1710,7 @@ mvs_status mvs_find_fundamental_matrix(mvs_ctx *ctx, const double p1_xy[16], con
     if (!ctx || !p1_xy || !p2_xy || !F)
         return MVS_ERR_INVALID_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     double *d = ctx->small.ptr<double>();  // [0,16) p1, [16,32) p2, [32,41) F, [48] ok flag (as int)
     HIP_TRY(ctx, hipMemcpyAsync(d, p1_xy, 16 * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemcpyAsync(d + 16, p2_xy, 16 * sizeof(double), hipMemcpyHostToDevice, s));
@@ -1775,7 +1826,7 @@ mvs_status mvs_five_point(mvs_ctx *ctx, const double p1_xy[10], const double p2_
         return MVS_ERR_INVALID_ARG;
     *n = 0;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     double *d = ctx->small.ptr<double>();  // [0,10) p1, [10,20) p2, [20,110) E, [110] n (as int)
     HIP_TRY(ctx, hipMemcpyAsync(d, p1_xy, 10 * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemcpyAsync(d + 10, p2_xy, 10 * sizeof(double), hipMemcpyHostToDevice, s));
@@ -1890,9 +1941,9 @@ mvs_status mvs_seq_create(mvs_ctx *ctx, int n_frames, int max_kp, int desc_bytes
         g[i] = (int64_t)i;
     {   // on the ctx stream (it is non-blocking: NULL-stream copies would not be ordered against the kernels that write
         // these buffers later), and with the partly built object released on failure
-        hipError_t e = hipMemcpyAsync(gidx, g.data(), T * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(n_corr, 0, T * sizeof(int32_t), ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(po, 0, T * sizeof(PnpOut), ctx->stream);
+        hipError_t e = hipMemcpyAsync(gidx, g.data(), T * sizeof(int64_t), hipMemcpyHostToDevice, ctx_stream(ctx));
+        if (e == hipSuccess) e = hipMemsetAsync(n_corr, 0, T * sizeof(int32_t), ctx_stream(ctx));
+        if (e == hipSuccess) e = hipMemsetAsync(po, 0, T * sizeof(PnpOut), ctx_stream(ctx));
         if (e == hipSuccess) e = sync_stream(ctx);   // `g` lives on this frame
         if (e != hipSuccess) {
             ctx->err = std::string("mvs_seq_create: ") + hipGetErrorString(e);
@@ -1963,7 +2014,7 @@ mvs_status mvs_seq_upload(mvs_seq *q, int first, int count, const uint8_t *desc,
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     q->loop_scored = q->loop_selected = q->loop_verified = false;   // the table, the list and the batch describe other frames
     const BatchDev &d = q->batch->d;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     const size_t N = d.max_kp, DW = d.desc_words, off = first;
     if (n_kp)
         for (int i = 0; i < count; ++i)
@@ -2035,12 +2086,12 @@ static mvs_status seq_prepare(mvs_seq *q, Estimator est, const mvs_params *tv, c
 // events recorded around those four stages; the pair pipeline itself is not instrumented (it keeps its two halves).
 static mvs_status seq_enqueue(mvs_seq *q, Estimator est, const RunParams &rp, hipEvent_t *ev = nullptr)
 {
-    hipStream_t s = q->ctx->stream;
-    if (ev) HIP_TRY(q->ctx, hipEventRecord(ev[0], s));
+    if (ev) HIP_TRY(q->ctx, hipEventRecord(ev[0], ctx_stream(q->ctx)));
     mvs_status st = est == Estimator::kEightPoint ? enqueue_pipeline(q->batch, rp, q->n_frames - 1, false, nullptr)
                                                   : enqueue_essential(q->batch, rp, q->n_frames - 1);
     if (st != MVS_OK)
         return st;
+    hipStream_t s = ctx_stream(q->ctx);   // behind both halves of the pairs: the join reads every pair
     if (ev) HIP_TRY(q->ctx, hipEventRecord(ev[1], s));
     launch_seq_join(q->join, s);
     if (ev) HIP_TRY(q->ctx, hipEventRecord(ev[2], s));
@@ -2104,16 +2155,15 @@ mvs_status mvs_seq_time(mvs_seq *q, const mvs_params *two_view, const mvs_pnp_pa
     if (st != MVS_OK)
         return st;
     const RunParams rp = to_run(*two_view);
-    hipStream_t s = q->ctx->stream;
     for (int i = 0; i < warmup; ++i)
         if ((st = seq_enqueue(q, Estimator::kEightPoint, rp)) != MVS_OK)
             return st;
     HIP_TRY(q->ctx, sync_stream(q->ctx));
-    HIP_TRY(q->ctx, hipEventRecord(q->batch->ev[5], s));
+    HIP_TRY(q->ctx, hipEventRecord(q->batch->ev[5], ctx_stream(q->ctx)));
     for (int i = 0; i < steps; ++i)
         if ((st = seq_enqueue(q, Estimator::kEightPoint, rp)) != MVS_OK)
             return st;
-    HIP_TRY(q->ctx, hipEventRecord(q->batch->ev[6], s));
+    HIP_TRY(q->ctx, hipEventRecord(q->batch->ev[6], ctx_stream(q->ctx)));   // (the stream is fetched behind every pipeline)
     HIP_TRY(q->ctx, hipEventSynchronize(q->batch->ev[6]));
     HIP_TRY(q->ctx, hipEventElapsedTime(ms_total, q->batch->ev[5], q->batch->ev[6]));
     return MVS_OK;
@@ -2245,7 +2295,7 @@ mvs_status mvs_pnp_solve(mvs_ctx *ctx, const double *world_xyz, const double *im
     double *dX = reinterpret_cast<double *>(base + off_x), *duv = dX + 3 * (size_t)n, *dxy = duv + 2 * (size_t)n, *dfb = dxy + 2 * (size_t)n;
     double *dK = reinterpret_cast<double *>(base + off_k);
     int32_t *dinl = reinterpret_cast<int32_t *>(base + off_inl);
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     double kk[18];
     std::memcpy(kk, K, 9 * sizeof(double));
     mat3_inverse(K, kk + 9);
@@ -2395,7 +2445,7 @@ static mvs_status refine_single(mvs_ctx *ctx, int frames, const double *obs_a, c
     double *c2a = dpcov + 9 * M, *c2b = c2a + 4 * M, *c3 = c2b + 4 * M, *dK = c3 + 9 * M, *dpose = dK + 9, *dpose_all = dpose + 12;
     int32_t *dm = reinterpret_cast<int32_t *>(base + off_m);
     uint8_t *dv0 = reinterpret_cast<uint8_t *>(base + off_valid0), *dv1 = reinterpret_cast<uint8_t *>(base + off_valid1);
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     const int32_t m32 = m;
     double pose[12];
     std::memcpy(pose, R_guess, 9 * sizeof(double));
@@ -2660,7 +2710,7 @@ mvs_status mvs_ba_refine_windows(mvs_ctx *ctx, const mvs_ba_window *problems, in
         std::vector<char> up(head + in.size() * sizeof(double));
         std::memcpy(up.data(), desc.data(), G * sizeof(WinProblem));
         std::memcpy(up.data() + head, in.data(), in.size() * sizeof(double));
-        hipStream_t s = ctx->stream;
+        hipStream_t s = ctx_stream(ctx);
         HIP_TRY(ctx, hipMemcpyAsync(base + off_up, up.data(), up.size(), hipMemcpyHostToDevice, s));
         WinDev d{};
         d.n_problems = (int)G;
@@ -2740,7 +2790,7 @@ mvs_status mvs_batch_refine(mvs_batch *b, const mvs_refine_params *params, doubl
             return st;
     }
     d.cfg = to_cfg(*params, 2);
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     launch_refine_gather(bd, (int)P, sigma_px, params->point_sigma, d.stride, const_cast<int32_t *>(d.m),
                          const_cast<double *>(d.pose0), const_cast<double *>(d.obs[0]), const_cast<double *>(d.obs[1]),
                          const_cast<double *>(d.oinfo[0]), const_cast<double *>(d.oinfo[1]),
@@ -2759,7 +2809,7 @@ mvs_status mvs_batch_download_refined(mvs_batch *b, mvs_refine_result *refined, 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const RefineDev &d = b->refine;
     const size_t P = d.n_problems, N = d.stride;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     HIP_TRY(ctx, hipMemcpyAsync(refined, d.out, P * sizeof(mvs_refine_result), hipMemcpyDeviceToHost, s));
     if (points_xyz)
         HIP_TRY(ctx, hipMemcpyAsync(points_xyz, d.pts, P * N * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -2775,7 +2825,7 @@ mvs_status mvs_seq_download_trajectory(mvs_seq *q, double *R, double *t, double 
         return MVS_ERR_INVALID_ARG;
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     const size_t F = q->n_frames;
     if (R)
         HIP_TRY(ctx, hipMemcpyAsync(R, q->chain.traj_R, F * 9 * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -2897,7 +2947,7 @@ mvs_status mvs_seq_refine_windows(mvs_seq *q, const mvs_seq_window_params *wp, c
     s.pts_tmp = reinterpret_cast<double *>(base + off_tmp);
     s.point_cov = reinterpret_cast<double *>(base + off_cov);
     s.out = reinterpret_cast<mvs_refine_result *>(base + off_out);
-    hipStream_t stream = ctx->stream;
+    hipStream_t stream = ctx_stream(ctx);
     // a window without points is left alone by the window kernel: its records read ok = 0
     HIP_TRY(ctx, hipMemsetAsync(base + off_out, 0, off_zero_end - off_out, stream));
     launch_seq_windows(d, stream);
@@ -2917,7 +2967,7 @@ mvs_status mvs_seq_download_windows(mvs_seq *q, mvs_seq_window_info *info, mvs_r
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const SeqWinDev &d = q->wd;
     const size_t W = (size_t)d.n_windows, F = (size_t)d.F, cap = (size_t)d.max_points;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     std::vector<mvs_refine_result> own;
     if (!frames) {   // the status needs the records
         own.resize(W * F);
@@ -3094,7 +3144,7 @@ static mvs_status seq_track_enqueue(mvs_seq *q, const mvs_vo_params *vp, int k0,
     ba.oinfo[1] = dbl(off_oi1);
     ba.pinfo = dbl(off_pinfo);
     ba.pts_tmp = dbl(off_tmp);
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     HIP_TRY(ctx, hipMemsetAsync(base, 0, off_mid, s));
     HIP_TRY(ctx, hipMemsetAsync(base + off_mid, 0xff, off_scratch - off_mid, s));
     OdoDev o{};
@@ -3197,7 +3247,6 @@ mvs_status mvs_seq_run_lags(mvs_seq *q, const mvs_params *two_view, int max_lag,
     }
     const size_t off_ssd = Carve{64}.up(((size_t)q->lag_cap + 1) * sizeof(LagDev));
     int32_t *ssd = reinterpret_cast<int32_t *>(q->lagws.ptr() + off_ssd);
-    hipStream_t s = ctx->stream;
     const RunParams run = to_run(*two_view);
     // a failure on the way leaves lags_ran = 0: nothing reads a half-run set of lags
     for (int lag = 1; lag <= max_lag; ++lag) {
@@ -3208,9 +3257,11 @@ mvs_status mvs_seq_run_lags(mvs_seq *q, const mvs_params *two_view, int max_lag,
             return st;
         if ((st = mvs_batch_refine(b, rp, sigma_px)) != MVS_OK)
             return st;
-        launch_pair_ssd(b->d.results, b->d.matches, b->d.point_idx, n, bd.max_kp, ssd + (size_t)lag * F, s);
+        // the stream is fetched behind the pipeline: it may have left the side lane open, and this reads every pair
+        launch_pair_ssd(b->d.results, b->d.matches, b->d.point_idx, n, bd.max_kp, ssd + (size_t)lag * F, ctx_stream(ctx));
     }
     HIP_TRY(ctx, hipGetLastError());
+    hipStream_t s = ctx_stream(ctx);
     q->lag_host.assign((size_t)q->lag_cap + 1, LagDev{});
     for (int lag = 1; lag <= max_lag; ++lag) {
         const mvs_batch *b = lag == 1 ? q->batch : q->lag_batch[lag];
@@ -3233,7 +3284,7 @@ mvs_status mvs_seq_download_lag_pairs(mvs_seq *q, int lag, mvs_pair_result *resu
     const int n = q->n_frames - lag;
     if (match_ssd) {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipMemcpyAsync(match_ssd, q->lag_host[lag].ssd, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(match_ssd, q->lag_host[lag].ssd, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx_stream(ctx)));
     }
     return mvs_batch_download(lag == 1 ? q->batch : q->lag_batch[lag], 0, n, results, matches, inlier_mask, points_xyz, point_idx);
 }
@@ -3272,7 +3323,7 @@ mvs_status mvs_seq_download_odometry_frames(mvs_seq *q, mvs_odo_frame *odo)
         return MVS_ERR_INVALID_ARG;
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpyAsync(odo, q->odo.odo, (size_t)q->n_frames * sizeof(mvs_odo_frame), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(odo, q->odo.odo, (size_t)q->n_frames * sizeof(mvs_odo_frame), hipMemcpyDeviceToHost, ctx_stream(ctx)));
     HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }
@@ -3284,7 +3335,7 @@ mvs_status mvs_seq_download_track_frames(mvs_seq *q, mvs_track_frame *frames)
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemcpyAsync(frames, q->vo.frames, (size_t)q->n_frames * sizeof(mvs_track_frame), hipMemcpyDeviceToHost,
-                                ctx->stream));
+                                ctx_stream(ctx)));
     HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }
@@ -3296,7 +3347,7 @@ mvs_status mvs_seq_download_track_map(mvs_seq *q, int frame, int32_t *point_id, 
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t N = (size_t)q->vo.max_kp, of = (size_t)frame * N;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     if (point_id)
         HIP_TRY(ctx, hipMemcpyAsync(point_id, q->vo.map_id + of, N * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (X)
@@ -3316,7 +3367,7 @@ mvs_status mvs_seq_download_track_step(mvs_seq *q, int frame, int32_t *cand_base
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const VoDev &d = q->vo;
     const size_t N = (size_t)d.max_kp, of = (size_t)frame * N;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     const struct {
         void *dst;
         const void *src;
@@ -3355,10 +3406,10 @@ mvs_status mvs_batch_upload_octaves(mvs_batch *b, int first, int count, const ui
                     return MVS_ERR_INVALID_ARG;   // stddev = (1 << octave) * 0.5 (visual-feature.cpp:203)
     if (base_octave)
         HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint8_t *>(b->d.oct1) + off, base_octave, bytes, hipMemcpyHostToDevice,
-                                    ctx->stream));
+                                    ctx_stream(ctx)));
     if (pair_octave)
         HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint8_t *>(b->d.oct2) + off, pair_octave, bytes, hipMemcpyHostToDevice,
-                                    ctx->stream));
+                                    ctx_stream(ctx)));
     HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }
@@ -3375,7 +3426,7 @@ mvs_status mvs_seq_upload_octaves(mvs_seq *q, int first, int count, const uint8_
             return MVS_ERR_INVALID_ARG;
     q->loop_verified = false;   // the verification's refinement weighed the observations by the octaves before
     HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint8_t *>(q->batch->d.oct1) + (size_t)first * N, octave, bytes,
-                                hipMemcpyHostToDevice, ctx->stream));
+                                hipMemcpyHostToDevice, ctx_stream(ctx)));
     HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }
@@ -3536,7 +3587,7 @@ static mvs_status pose_graph_large_dev(mvs_ctx *ctx, char *base, int n_nodes, in
         }
     }
     const PgLargeLayout L(N, E);
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     HIP_TRY(ctx, hipMemsetAsync(base + L.o_state, 0, sizeof(PgState), s));
     HIP_TRY(ctx, hipMemcpyAsync(base + L.o_off, off.data(), (N + 1) * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemcpyAsync(base + L.o_inc, inc.data(), 2 * E * 4, hipMemcpyHostToDevice, s));
@@ -3659,7 +3710,7 @@ static mvs_status pose_graph_large(mvs_ctx *ctx, const mvs_pose_graph &g, const 
     if (st != MVS_OK)
         return st;
     char *base = ctx->pg.ptr();
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     HIP_TRY(ctx, hipMemcpyAsync(base + o_src, g.edge_src, E * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemcpyAsync(base + o_dst, g.edge_dst, E * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemcpyAsync(base + o_z, g.edge_pose, E * 12 * 8, hipMemcpyHostToDevice, s));
@@ -3703,7 +3754,7 @@ static mvs_status pose_graph_dense_dev(mvs_ctx *ctx, char *base, const PgDenseLa
     d.lin = reinterpret_cast<double *>(base + L.o_lin);
     d.poses_out = reinterpret_cast<double *>(base + L.o_po);
     d.out = reinterpret_cast<mvs_pose_graph_result *>(base + L.o_out);
-    launch_pg_dense(d, ctx->stream);
+    launch_pg_dense(d, ctx_stream(ctx));
     HIP_TRY(ctx, hipGetLastError());
     return MVS_OK;
 }
@@ -3775,7 +3826,7 @@ mvs_status mvs_pose_graph_optimize_batch(mvs_ctx *ctx, const mvs_pose_graph *gra
             }
         }
         char *base = ctx->pg.ptr();
-        hipStream_t s = ctx->stream;
+        hipStream_t s = ctx_stream(ctx);
         HIP_TRY(ctx, hipMemcpyAsync(base + o_up, up.data(), up.size(), hipMemcpyHostToDevice, s));
         auto dp = [&](size_t o) { return reinterpret_cast<const double *>(base + o_up + o); };
         auto ip = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o_up + o); };
@@ -3874,7 +3925,7 @@ mvs_status mvs_seq_build_pose_graph(mvs_seq *q, const mvs_seq_graph_params *p)
     q->graph_n_built = reinterpret_cast<int32_t *>(q->graph.ptr() + L.o_built);
     q->graph_edge_cap = (int)L.cap;
     q->loop_edges_added = false;
-    launch_seq_graph(g, ctx->stream);
+    launch_seq_graph(g, ctx_stream(ctx));
     HIP_TRY(ctx, hipGetLastError());
     q->gd = g;
     q->graph_built = true;
@@ -3888,7 +3939,7 @@ mvs_status mvs_seq_optimize_pose_graph(mvs_seq *q, const mvs_pose_graph_params *
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const SeqGraphDev &g = q->gd;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     q->graph_opt = false;
     *result = mvs_pose_graph_result{};
     // the count and the edges' endpoints: all the host needs of the graph
@@ -3950,7 +4001,7 @@ mvs_status mvs_seq_download_pose_graph(mvs_seq *q, int32_t *n_edges, double *nod
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const SeqGraphDev &g = q->gd;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     HIP_TRY(ctx, hipMemcpyAsync(n_edges, g.n_edges, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, sync_stream(ctx));
     const size_t E = (size_t)std::min(std::max(*n_edges, 0), q->graph_edge_cap);
@@ -3974,7 +4025,7 @@ mvs_status mvs_seq_download_pose_graph_poses(mvs_seq *q, double *poses)
         return MVS_ERR_INVALID_ARG;
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpyAsync(poses, q->graph_opt_pose, (size_t)q->n_frames * 96, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(poses, q->graph_opt_pose, (size_t)q->n_frames * 96, hipMemcpyDeviceToHost, ctx_stream(ctx)));
     HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }
@@ -4000,7 +4051,7 @@ mvs_status mvs_seq_loop_scores(mvs_seq *q, double ratio, double max_dist, int mi
     l.n_frames = q->n_frames, l.max_kp = d.max_kp, l.desc_words = d.desc_words;
     l.desc = d.desc1, l.kp = d.kp1, l.oct = d.oct1, l.n_kp = d.n1, l.K = d.K, l.Kinv = d.Kinv;
     l.score = q->loop_score.ptr<int32_t>();
-    HIP_TRY(ctx, launch_loop_scores(l, ratio, max_dist, min_gap, ctx->stream));
+    HIP_TRY(ctx, launch_loop_scores(l, ratio, max_dist, min_gap, ctx_stream(ctx)));
     HIP_TRY(ctx, hipGetLastError());
     q->loop_scored = true;
     return MVS_OK;
@@ -4013,7 +4064,7 @@ mvs_status mvs_seq_download_loop_scores(mvs_seq *q, int32_t *scores)
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t F = (size_t)q->n_frames;
-    HIP_TRY(ctx, hipMemcpyAsync(scores, q->ld.score, F * F * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(scores, q->ld.score, F * F * sizeof(int32_t), hipMemcpyDeviceToHost, ctx_stream(ctx)));
     HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }
@@ -4040,7 +4091,7 @@ mvs_status mvs_seq_select_loops(mvs_seq *q, const mvs_loop_select_params *p)
     l.row_n = reinterpret_cast<int32_t *>(base + o_rown);
     l.row_key = reinterpret_cast<int32_t *>(base + o_rowkey);
     l.cand = reinterpret_cast<mvs_loop_candidate *>(base + o_cand);
-    launch_loop_select(l, ctx->stream);
+    launch_loop_select(l, ctx_stream(ctx));
     HIP_TRY(ctx, hipGetLastError());
     q->loop_selected = true;
     return MVS_OK;
@@ -4069,7 +4120,7 @@ mvs_status mvs_seq_verify_loops(mvs_seq *q, const mvs_params *two_view, int esse
     const Estimator est = essential ? Estimator::kFivePoint : Estimator::kEightPoint;
     if ((st = ensure_tables(b, est, two_view->num_hypotheses)) != MVS_OK)
         return st;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     // the one host read between selection and verification: how many pairs the pipeline runs on
     int32_t counts[2] = {0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(counts, l.counts, sizeof(counts), hipMemcpyDeviceToHost, s));
@@ -4106,7 +4157,7 @@ mvs_status mvs_seq_add_loop_edges(mvs_seq *q, const mvs_loop_edge_params *p)
         return MVS_ERR_INVALID_ARG;
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     const int need = q->gd.n_slots + q->ld.max_candidates;
     if (q->graph_edge_cap < need) {
         // the block was carved before this selection: a larger one, the graph's arrays copied over (the slots are scratch)
@@ -4167,7 +4218,7 @@ mvs_status mvs_seq_download_loop_candidates(mvs_seq *q, int32_t *n_kept, int32_t
         return MVS_ERR_INVALID_ARG;
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     int32_t counts[2] = {0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(counts, q->ld.counts, sizeof(counts), hipMemcpyDeviceToHost, s));
     if (cand)

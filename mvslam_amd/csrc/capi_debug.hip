@@ -59,11 +59,11 @@ int mvs_debug_fastmath_check(mvs_ctx *ctx, const double *x, const double *y, int
     const mvs_status st = DevGroup(ctx, tmp).add(dx, n).add(dy, n).add(dc, 4).commit();
     if (st != MVS_OK)
         return st;
-    HIP_TRY(ctx, hipMemcpyAsync(dx, x, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(dy, y, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(dc, 0, 32, ctx->stream));
-    launch_fastmath_check(dx, dy, n, dc, ctx->stream);
-    HIP_TRY(ctx, hipMemcpyAsync(counts, dc, 32, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dx, x, (size_t)n * 8, hipMemcpyHostToDevice, ctx_stream(ctx)));
+    HIP_TRY(ctx, hipMemcpyAsync(dy, y, (size_t)n * 8, hipMemcpyHostToDevice, ctx_stream(ctx)));
+    HIP_TRY(ctx, hipMemsetAsync(dc, 0, 32, ctx_stream(ctx)));
+    launch_fastmath_check(dx, dy, n, dc, ctx_stream(ctx));
+    HIP_TRY(ctx, hipMemcpyAsync(counts, dc, 32, hipMemcpyDeviceToHost, ctx_stream(ctx)));
     HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }
@@ -82,12 +82,12 @@ int mvs_debug_pairstep_check(mvs_ctx *ctx, const double *rows, int n, unsigned l
     const mvs_status st = DevGroup(ctx, tmp).add(dr, (size_t)n * 6).add(dc, 4).commit();
     if (st != MVS_OK)
         return st;
-    hipError_t e = hipMemcpyAsync(dr, rows, (size_t)n * 48, hipMemcpyHostToDevice, ctx->stream);
+    hipError_t e = hipMemcpyAsync(dr, rows, (size_t)n * 48, hipMemcpyHostToDevice, ctx_stream(ctx));
     if (e == hipSuccess)
-        e = hipMemsetAsync(dc, 0, 32, ctx->stream);
+        e = hipMemsetAsync(dc, 0, 32, ctx_stream(ctx));
     if (e == hipSuccess) {
-        launch_pairstep_check(dr, n, dc, ctx->stream);
-        e = hipMemcpyAsync(counts, dc, 32, hipMemcpyDeviceToHost, ctx->stream);
+        launch_pairstep_check(dr, n, dc, ctx_stream(ctx));
+        e = hipMemcpyAsync(counts, dc, 32, hipMemcpyDeviceToHost, ctx_stream(ctx));
     }
     if (e == hipSuccess)
         e = sync_stream(ctx);
@@ -116,7 +116,7 @@ int mvs_debug_mfma_probe(mvs_ctx *ctx, const uint16_t *a, const uint16_t *b, flo
         return st;
     HIP_TRY(ctx, hipMemcpy(da, a, 1024 * sizeof(uint16_t), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(db, b, 1024 * sizeof(uint16_t), hipMemcpyHostToDevice));
-    launch_mfma_probe(da, db, dout, ctx->stream);
+    launch_mfma_probe(da, db, dout, ctx_stream(ctx));
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, sync_stream(ctx));
     HIP_TRY(ctx, hipMemcpy(out, dout, 1024 * sizeof(float), hipMemcpyDeviceToHost));
@@ -205,7 +205,7 @@ int mvs_debug_prescreen_only(mvs_batch *b, const mvs_params *params, int n_activ
     mvs_status st = ensure_groups(b, params->num_hypotheses);
     if (st != MVS_OK)
         return st;
-    launch_prescreen_only(b->d, to_run(*params), n_active, mode, b->ctx->stream);
+    launch_prescreen_only(b->d, to_run(*params), n_active, mode, ctx_stream(b->ctx));
     HIP_TRY(b->ctx, hipGetLastError());
     HIP_TRY(b->ctx, sync_stream(b->ctx));
     return MVS_OK;
@@ -231,13 +231,13 @@ int mvs_debug_audit(mvs_batch *b, const mvs_params *params, int n_active, int ph
     DevBlocks tmp;
     if ((st = DevGroup(ctx, tmp).add(dc, 16).add(dm, n_active).commit()) != MVS_OK)
         return st;
-    hipError_t e = hipMemsetAsync(dc, 0, 16 * sizeof(unsigned long long), ctx->stream);
+    hipError_t e = hipMemsetAsync(dc, 0, 16 * sizeof(unsigned long long), ctx_stream(ctx));
     if (e == hipSuccess)
-        e = hipMemsetAsync(dm, 0xff, (size_t)n_active * sizeof(int32_t), ctx->stream);
+        e = hipMemsetAsync(dm, 0xff, (size_t)n_active * sizeof(int32_t), ctx_stream(ctx));
     if (e == hipSuccess && phase == 0)
-        launch_prescreen_only(b->d, rp, n_active, -1, ctx->stream);
+        launch_prescreen_only(b->d, rp, n_active, -1, ctx_stream(ctx));
     if (e == hipSuccess)
-        e = launch_audit(b->d, rp, n_active, phase, dc, dm, ctx->stream);
+        e = launch_audit(b->d, rp, n_active, phase, dc, dm, ctx_stream(ctx));
     if (e == hipSuccess)
         e = sync_stream(ctx);
     if (e == hipSuccess)
@@ -285,11 +285,11 @@ int mvs_debug_audit_state(mvs_ctx *ctx, const void *state, size_t state_bytes, c
     const mvs_status st = DevGroup(ctx, tmp).add(dc, 16).add(dm, n_active).commit();
     if (st != MVS_OK)
         return st;
-    hipError_t e = hipMemsetAsync(dc, 0, 16 * sizeof(unsigned long long), ctx->stream);
+    hipError_t e = hipMemsetAsync(dc, 0, 16 * sizeof(unsigned long long), ctx_stream(ctx));
     if (e == hipSuccess)
-        e = hipMemsetAsync(dm, 0xff, (size_t)n_active * sizeof(int32_t), ctx->stream);
+        e = hipMemsetAsync(dm, 0xff, (size_t)n_active * sizeof(int32_t), ctx_stream(ctx));
     if (e == hipSuccess)
-        e = launch_audit(d, rp, n_active, phase == 2 ? 0 : 1, dc, dm, ctx->stream);
+        e = launch_audit(d, rp, n_active, phase == 2 ? 0 : 1, dc, dm, ctx_stream(ctx));
     if (e == hipSuccess)
         e = sync_stream(ctx);
     if (e == hipSuccess)
@@ -362,8 +362,8 @@ int mvs_debug_count_only(mvs_batch *b, const mvs_params *params, int n_active, i
             return st;
         HIP_TRY(ctx, hipMemcpy(dk, keep, (size_t)n_active * sizeof(int32_t), hipMemcpyHostToDevice));
     }
-    HIP_TRY(ctx, hipMemsetAsync(b->d.dense_n1, 0, (size_t)n_active * sizeof(int32_t), ctx->stream));
-    launch_count_only(b->d, to_run(*params), n_active, pmode, dense, dk, ctx->stream);
+    HIP_TRY(ctx, hipMemsetAsync(b->d.dense_n1, 0, (size_t)n_active * sizeof(int32_t), ctx_stream(ctx)));
+    launch_count_only(b->d, to_run(*params), n_active, pmode, dense, dk, ctx_stream(ctx));
     hipError_t e = hipGetLastError();
     if (e == hipSuccess)
         e = sync_stream(ctx);
@@ -395,7 +395,7 @@ int mvs_debug_indicator_probe(mvs_ctx *ctx, const float *a, const float *tu, con
     const size_t ob[3] = {nb, nb, nb};
     return probe_io(ctx, in, ib, 4, out, ob, 3, [&](unsigned char **d) {
         launch_indicator_probe((const float *)d[0], (const float *)d[1], (const float *)d[2], (const float *)d[3], n, (float *)d[4],
-                               (float *)d[5], (float *)d[6], ctx->stream);
+                               (float *)d[5], (float *)d[6], ctx_stream(ctx));
     });
 }
 
@@ -409,6 +409,6 @@ int mvs_debug_rounding_probe(mvs_ctx *ctx, const double *in19, int n, double *ou
     void *out[1] = {out2};
     const size_t ob[1] = {(size_t)n * 2 * sizeof(double)};
     return probe_io(ctx, in, ib, 1, out, ob, 1,
-                    [&](unsigned char **d) { launch_rounding_probe((const double *)d[0], n, (double *)d[1], ctx->stream); });
+                    [&](unsigned char **d) { launch_rounding_probe((const double *)d[0], n, (double *)d[1], ctx_stream(ctx)); });
 }
 }  // extern "C"

@@ -34,11 +34,20 @@ struct mvs_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    // second queue of a large batch: its pairs go down the pipeline as two independent halves, one per stream, so that the
-    // latency-bound kernels of one half (list sort, exact solve of the few survivors, selection, ...) run under the
-    // throughput-bound kernels of the other (enqueue_pipeline).  Forked from / joined into `stream` with the two events.
+    // second queue of a large batch: its pairs go down the pipeline as two independent halves, one per lane (`stream` and
+    // `side`), so that the latency-bound kernels of one half (list sort, exact solve of the few survivors, selection, ...) run
+    // under the throughput-bound kernels of the other -- and, while nothing else uses the context, under those of the NEXT
+    // call: a halves run leaves the side lane open (enqueue_pipeline) and whatever uses the context's stream next joins it
+    // (ctx_stream).  Nothing but ctx_stream, enqueue_pipeline, close_lane and create / destroy reads `stream` or `side`.
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipEvent_t ev_dense[2]{};   // recorded behind a lane's dense count: the other lane's next throughput section waits for it
+    bool lane_open = false;                 // work of a halves run is on `side` that `stream` has not joined yet
+    const mvs_batch *lane_batch = nullptr;  // the open lane's batch and pairs: only the same run again leaves it open
+    int lane_pairs = 0;
+    // the caller can enqueue work of their own on the stream (it is theirs, or mvs_ctx_stream has handed it out): every halves
+    // run joins before it returns, "the caller sees one stream"
+    bool caller_sees_stream = false;
     bool half_batches = true;
     double e5_confidence = 0.0;   // mvs_ctx_set_essential_confidence: 0 = every hypothesis of the five-point RANSAC runs
     // n_run of the last single-shot five-point call: none yet, or that call failed before its RANSAC was enqueued (-1); in
@@ -247,6 +256,15 @@ inline void mat3_inverse(const double *K, double *inv)
 inline bool affine_K(const double *K) { return K[6] == 0.0 && K[7] == 0.0 && K[8] == 1.0 && K[0] != 0.0 && K[4] != 0.0; }
 
 // capi.hip
+hipError_t close_lane(mvs_ctx *ctx);
+// The context's stream, for every use but the halves path of enqueue_pipeline: an open side lane is joined into it first, so
+// that whatever the caller enqueues, records or waits for on the returned stream is behind both halves.
+inline hipStream_t ctx_stream(mvs_ctx *ctx)
+{
+    if (ctx->lane_open)
+        (void)close_lane(ctx);   // without an event edge it has waited for the lane on the host: joined either way
+    return ctx->stream;
+}
 hipError_t sync_stream(mvs_ctx *ctx);
 mvs_status ws_grow(mvs_ctx *ctx, DevWorkspace &w, size_t bytes, size_t floor = 0);
 void drop_orb_graph(mvs_ctx *ctx);

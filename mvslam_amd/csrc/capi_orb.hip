@@ -185,7 +185,7 @@ mvs_status mvs_host::orb_run(mvs_ctx *ctx, const uint8_t *images, int n, int w, 
     d.n_kp = d_n_ext ? d_n_ext : reinterpret_cast<int32_t *>(base + o_n);
     d.kp_xy = d_kp_xy_ext;
     d.kp_oct = d_kp_oct_ext;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     // the test pattern and the resize tables depend on (size, parameters, workspace) only: a call with the key of the captured
     // graph finds them in the workspace (round 5: they were uploaded, and the stream synchronised for them, on every call)
     const bool same_key = ctx->orb_graph_valid && std::memcmp(&ctx->orb_graph_key, &d, sizeof(d)) == 0;
@@ -261,7 +261,7 @@ mvs_status mvs_extract_time(mvs_ctx *ctx, int steps, float *ms_total)
         ctx->err = "mvs_extract_time: hipEventCreate failed";
         return MVS_ERR_HIP;
     }
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     hipError_t e = hipEventRecord(e0, s);
     for (int i = 0; i < steps && e == hipSuccess; ++i)
         e = hipGraphLaunch(ctx->orb_graph, s);
@@ -285,7 +285,7 @@ mvs_status mvs_extract(mvs_ctx *ctx, const uint8_t *images, int n_images, int wi
     if (st != MVS_OK)
         return st;
     const size_t B = n_images, NF = params->nfeatures;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx_stream(ctx);
     HIP_TRY(ctx, hipMemcpyAsync(keypoints, d.kp, B * NF * sizeof(mvs_keypoint), hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipMemcpyAsync(descriptors, d.desc, B * NF * 32, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipMemcpyAsync(n_keypoints, d.n_kp, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));

@@ -3174,7 +3174,8 @@ constexpr int g_force_mode = -1;
 // bound, from there on).  The diagnostics library can put ransac_count32_kernel in the place of the whole sequence
 // (g_count_dense = 0) or of the finish (2) -- byte-identical results, 5.2 ms against 0.2 + 2.0 + 1.4 per 512 pairs
 // (profiles/r03_count32_experiments.md).
-static void launch_counting(const BatchDev &b, const RunParams &rp, int n_active, hipStream_t stream, LaunchTimer *lt, bool stats)
+static void launch_counting(const BatchDev &b, const RunParams &rp, int n_active, hipStream_t stream, LaunchTimer *lt, bool stats,
+                            hipEvent_t after_dense = nullptr)
 {
     const int H = rp.num_hypotheses;
     const int n_groups4 = (H + kCntSlots - 1) / kCntSlots;
@@ -3207,6 +3208,10 @@ static void launch_counting(const BatchDev &b, const RunParams &rp, int n_active
         else
             hipLaunchKernelGGL((ransac_count_mfma_kernel<false, kDenseThreads, kDenseBatches>), dense_grid, dim3(kDenseThreads),
                                lds_dense, stream, b, rp, g_dense_margin);
+        // the one place after_dense is recorded: a launch that takes another way (the fused kernel, the diagnostics' one-launch
+        // counting) leaves the event as it was, and whoever waits for it waits for an earlier record or not at all.  Intended:
+        // the event only paces independent half batches (enqueue_pipeline), no result depends on it
+        if (after_dense) (void)hipEventRecord(after_dense, stream);
         if (lt) lt->mark(kKRansacCountFinish);
 #ifdef MVS_DEBUG_HOOKS
         if (g_count_dense == 2) {   // the vector finish, on the dense phase's unsorted list
@@ -3249,7 +3254,7 @@ static void launch_counting(const BatchDev &b, const RunParams &rp, int n_active
 // the probe sends there) -> counting with per-hypothesis thresholds -> survivors -> exact solve of the hypotheses without a
 // certificate and of the survivors -> select
 static void launch_prescreened(const BatchDev &b, const RunParams &rp, int n_active, hipStream_t stream, LaunchTimer *lt,
-                               bool stats)
+                               bool stats, hipEvent_t after_dense = nullptr)
 {
     const int H = rp.num_hypotheses;
     const int G = (H + kHypPerBlock - 1) / kHypPerBlock;
@@ -3263,7 +3268,7 @@ static void launch_prescreened(const BatchDev &b, const RunParams &rp, int n_act
     static_assert(kSolveBlock == 64, "ransac_solve_list_kernel takes blocks of 64 hypotheses");
     hipLaunchKernelGGL(ransac_solve_list_kernel, dim3(2048), dim3(64), 0, stream, b, rp,
                        G * (kHypPerBlock / kSolveBlock));
-    launch_counting(b, rp, n_active, stream, lt, stats);
+    launch_counting(b, rp, n_active, stream, lt, stats, after_dense);
     if (lt) lt->mark(kKRansacSurvivors);
     hipLaunchKernelGGL(ransac_survivors_kernel, dim3(kSurvWg, n_active), dim3(256), 0, stream, b, rp, n_active);
     // one exact solve over the whole work list: what the pre-screen flagged + the survivors of the counting
@@ -3277,7 +3282,8 @@ static void launch_prescreened(const BatchDev &b, const RunParams &rp, int n_act
 // the pre-screened stage, or -- for one or two pairs, the per-hypothesis tables and the instrumented replay's rotation
 // counters -- the fused hypothesis-per-lane kernel.  The replay runs the fused kernel with the Guarded solve: the flop model of
 // the benchmark was derived with its rotation counters.
-void launch_ransac(const BatchDev &b, const RunParams &rp, int n_active, bool stats, hipStream_t stream, LaunchTimer *lt)
+void launch_ransac(const BatchDev &b, const RunParams &rp, int n_active, bool stats, hipStream_t stream, LaunchTimer *lt,
+                   hipEvent_t after_dense)
 {
     const int G = (rp.num_hypotheses + kHypPerBlock - 1) / kHypPerBlock;
     const dim3 grid(G, n_active), block(kHypPerBlock);
@@ -3291,7 +3297,7 @@ void launch_ransac(const BatchDev &b, const RunParams &rp, int n_active, bool st
         if (stats && b.hyp_F && !b.hyp_count && prescreened_launch(b, n_active, rp.num_hypotheses))
             launch_prescreened(b, rp, n_active, stream, nullptr, true);   // + the product path's own counters
     } else {
-        launch_prescreened(b, rp, n_active, stream, lt, false);
+        launch_prescreened(b, rp, n_active, stream, lt, false, after_dense);
     }
 }
 

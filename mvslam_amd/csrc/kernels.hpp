@@ -653,7 +653,9 @@ bool kernel_desc(int id, int max_kp, int desc_words, KernelDesc *out);
 void launch_match_topk(const BatchDev &b, const RunParams &rp, int n_active, hipStream_t stream, LaunchTimer *lt = nullptr);
 void launch_match_compact(const BatchDev &b, const RunParams &rp, int n_active, hipStream_t stream, LaunchTimer *lt = nullptr);
 void launch_prep_points(const BatchDev &b, const double *uv1, const double *uv2, int n_active, hipStream_t stream);
-void launch_ransac(const BatchDev &b, const RunParams &rp, int n_active, bool stats, hipStream_t stream, LaunchTimer *lt = nullptr);
+// after_dense: recorded on `stream` behind the dense count of the pre-screened stage (the end of its throughput-bound part)
+void launch_ransac(const BatchDev &b, const RunParams &rp, int n_active, bool stats, hipStream_t stream, LaunchTimer *lt = nullptr,
+                   hipEvent_t after_dense = nullptr);
 void launch_finalize(const BatchDev &b, const RunParams &rp, int n_active, int mode, hipStream_t stream, LaunchTimer *lt = nullptr);
 // opt-in to > 64 KB of dynamic LDS for the kernels that need it, once per device; hipSuccess or the first error
 hipError_t prepare_kernels();
