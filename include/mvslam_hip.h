@@ -979,6 +979,45 @@ mvs_status mvs_seq_download_pose_graph(mvs_seq *s, int32_t *n_edges, double *nod
  * graph succeeded. */
 mvs_status mvs_seq_download_pose_graph_poses(mvs_seq *s, double *poses);
 
+/* ---- Marginal covariances of a pose graph ---------------------------------------------------------
+ * Inputs: a graph g as above, poses X (n_nodes x 12, the linearisation point; NULL: g.node_pose) and anchor_sigma.
+ *   H = J_a^T W_a J_a + sum_k J_k^T W_k J_k,  no lambda.
+ * Residuals, Jacobians, tangent order (rotation, translation), right perturbation and whitening are exactly those of the
+ * optimiser.  The anchor's mean is g.node_pose[anchor_node], as there; J_a is evaluated at X[anchor_node].  Sigma = H^-1.
+ * The call returns the 6 x 6 blocks Sigma_ij, row-major, of a list of queries (i, j): i = j is the marginal covariance of node
+ * i, i != j the cross-covariance.
+ *   - A diagonal block is returned exactly symmetric.
+ *   - The bytes of Sigma_ji are the transpose of the bytes of Sigma_ij.
+ *   - A block's bytes do not depend on which other queries are in the call or on their order.
+ *   - The same input gives the same bytes: binary64, explicit FMAs, fixed summation orders, no floating-point atomics.
+ * How: H is assembled as a block lower triangle inside its envelope (nodes in their natural order; row i stores the blocks
+ * first[i] .. i, first[i] = the smallest of i and its neighbours), factorised there (H = L L^T, one workgroup, fill never leaves
+ * a row's envelope) and Sigma_ij = (L^-1 E_i)^T (L^-1 E_j) comes from forward solves alone, one workgroup per query.
+ * envelope_blocks = sum_i (i - first[i] + 1); more than 2^21 blocks (604 MB) is MVS_ERR_CAPACITY, reported before anything is
+ * launched.  One path for 1 .. 4096 nodes. */
+typedef struct mvs_pose_graph_marginals_info {
+    int32_t ok;               /* 1: factorised, every block written */
+    int32_t envelope_blocks;  /* 6 x 6 blocks stored for L */
+    int32_t bad_node;         /* node whose pivot failed, -1 otherwise */
+    int32_t reserved;
+    double  min_pivot;        /* smallest diagonal entry of L */
+} mvs_pose_graph_marginals_info;
+/* cov_out: n_query x 36.  n_query = 0 with both lists NULL: every diagonal block, cov_out n_nodes x 36.  Argument, capacity and
+ * topology errors are those of mvs_pose_graph_optimize with the same status codes; a query index out of range, a list that is
+ * missing, non-finite poses or an anchor_sigma that is not positive are MVS_ERR_INVALID_ARG.  MVS_NO_MODEL with ok = 0 and cov_out
+ * untouched: an edge covariance that is not positive definite, a node no path of edges joins to the anchor, or a pivot of the
+ * factorisation that is not finite and positive (bad_node tells where).  Waits for the ctx stream. */
+mvs_status mvs_pose_graph_marginals(mvs_ctx *ctx, const mvs_pose_graph *graph, const double *poses /* NULL: node_pose */,
+                                    const double anchor_sigma[2], int n_query, const int32_t *query_i,
+                                    const int32_t *query_j, double *cov_out /* n x 36 */,
+                                    mvs_pose_graph_marginals_info *info);
+/* The same on the resident graph of a sequence (loop edges included) at its resident OPTIMISED nodes, read through device
+ * pointers: only the edges' endpoints go to the host and only the blocks come back.  The bytes are those of
+ * mvs_pose_graph_marginals on mvs_seq_download_pose_graph plus mvs_seq_download_pose_graph_poses with anchor_node 0.
+ * MVS_ERR_INVALID_ARG unless the last mvs_seq_optimize_pose_graph on the current graph succeeded. */
+mvs_status mvs_seq_pose_graph_marginals(mvs_seq *s, const double anchor_sigma[2], int n_query, const int32_t *query_i,
+                                        const int32_t *query_j, double *cov_out, mvs_pose_graph_marginals_info *info);
+
 /* ---- Loop closures of a resident sequence -------------------------------------------------------
  * Every edge of the graph above joins frames at most max_lag apart: it smooths a trajectory and cannot remove its drift.  These
  * calls find frames that see the same place again, verify the pairs with the two-view pipeline and the refinement, and append

@@ -160,6 +160,29 @@ POSE_GRAPH_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("iterations", "<i4"), ("cg_i
                                     ("rejected_steps", "<i4"), ("error_initial", "<f8"), ("error", "<f8")])
 assert POSE_GRAPH_RESULT_DTYPE.itemsize == C.sizeof(PoseGraphResult)
 POSE_GRAPH_DENSE_MAX_NODES, POSE_GRAPH_MAX_NODES, POSE_GRAPH_MAX_EDGES = 16, 4096, 65536
+POSE_GRAPH_MARGINALS_INFO_DTYPE = np.dtype([("ok", "<i4"), ("envelope_blocks", "<i4"), ("bad_node", "<i4"), ("reserved", "<i4"),
+                                            ("min_pivot", "<f8")])
+POSE_GRAPH_MAX_ENVELOPE_BLOCKS = 1 << 21
+
+
+def _marginals_args(n_nodes, queries, anchor_sigma, cov_out):
+    """(sigma, n_query, query_i, query_j, cov_out, info) of the two marginals calls; queries None = every diagonal block"""
+    sig = anchor_sigma if anchor_sigma is not None else (1e-4, 1e-4)   # mvs_pose_graph_params_default's
+    sigma = (C.c_double * 2)(float(sig[0]), float(sig[1]))
+    if queries is None:
+        qi = qj = None
+        n = 0
+        rows = n_nodes
+    else:
+        q = np.asarray(queries, dtype=np.int32).reshape(-1, 2)
+        qi, qj = np.ascontiguousarray(q[:, 0]), np.ascontiguousarray(q[:, 1])
+        n = rows = len(qi)
+        if n == 0:
+            raise ValueError("an empty query list: pass None for every diagonal block")
+    if cov_out is None:
+        cov_out = np.zeros((rows, 6, 6))
+    assert cov_out.dtype == np.float64 and cov_out.flags.c_contiguous and cov_out.shape == (rows, 6, 6)
+    return sigma, n, qi, qj, cov_out, np.zeros(1, dtype=POSE_GRAPH_MARGINALS_INFO_DTYPE)
 
 
 class SeqGraphParams(C.Structure):
@@ -236,6 +259,7 @@ EXPORTS = [
     "mvs_seq_build_pose_graph", "mvs_seq_optimize_pose_graph", "mvs_seq_download_pose_graph",
     "mvs_seq_download_pose_graph_poses", "mvs_seq_loop_scores", "mvs_seq_download_loop_scores", "mvs_seq_select_loops",
     "mvs_seq_verify_loops", "mvs_seq_add_loop_edges", "mvs_seq_download_loop_candidates",
+    "mvs_pose_graph_marginals", "mvs_seq_pose_graph_marginals",
 ]
 
 
@@ -529,6 +553,30 @@ class Context:
             poses_out = poses_out.reshape(1, -1, 12)
         st, res, poses = self._pose_graph_call([graph], params, poses_out, True)
         return st, res[0], poses[0]
+
+    def pose_graph_marginals(self, graph, poses=None, queries=None, anchor_sigma=None, cov_out=None):
+        """mvs_pose_graph_marginals: blocks of Sigma = H^-1 at `poses` (None: the graph's node_pose).  queries: pairs (i, j),
+        None = every diagonal block.  Returns (status, info record, cov [n, 6, 6]); `cov_out` (that shape, float64, contiguous)
+        is written in place when given and keeps its bytes on MVS_NO_MODEL.  Argument and capacity errors raise MvsError."""
+        npose = _f64(graph["node_pose"]).reshape(-1, 12)
+        src = np.ascontiguousarray(graph["edge_src"], dtype=np.int32).reshape(-1)
+        dst = np.ascontiguousarray(graph["edge_dst"], dtype=np.int32).reshape(-1)
+        ep = _f64(graph["edge_pose"]).reshape(-1, 12)
+        ec = _f64(graph["edge_cov"]).reshape(-1, 36)
+        if not (len(src) == len(dst) == len(ep) == len(ec)):
+            raise ValueError("pose graph: the per-edge arrays differ in length")
+        g = PoseGraph(npose.shape[0], len(src), _ptr(npose, C.c_double), _ptr(src, C.c_int32), _ptr(dst, C.c_int32),
+                      _ptr(ep, C.c_double), _ptr(ec, C.c_double), int(graph.get("anchor", 0)))
+        X = None
+        if poses is not None:
+            X = _f64(poses).reshape(-1, 12)
+            if X.shape[0] != npose.shape[0]:
+                raise ValueError("pose graph: `poses` has another node count than the graph")
+        sigma, n, qi, qj, cov_out, info = _marginals_args(npose.shape[0], queries, anchor_sigma, cov_out)
+        st = lib().mvs_pose_graph_marginals(self._h, C.byref(g), _ptr(X, C.c_double), sigma, C.c_int(n), _ptr(qi, C.c_int32),
+                                            _ptr(qj, C.c_int32), _ptr(cov_out, C.c_double), info.ctypes.data_as(C.c_void_p))
+        self._check(st, "mvs_pose_graph_marginals", allow_no_model=True)
+        return st, info[0], cov_out
 
     # VisualFeature::match_visual_features(vf1 = train, vf2 = query, max_dist)
     def match_hamming(self, train_desc, query_desc, ratio=0.7, max_dist=-1.0):
@@ -1377,6 +1425,16 @@ class Sequence:
         st = lib().mvs_seq_download_pose_graph_poses(self._h, _ptr(poses, C.c_double))
         self.ctx._check(st, "mvs_seq_download_pose_graph_poses")
         return poses
+
+    def pose_graph_marginals(self, queries=None, anchor_sigma=None, cov_out=None):
+        """mvs_seq_pose_graph_marginals: blocks of Sigma = H^-1 of the resident graph at its optimised nodes; as
+        Context.pose_graph_marginals.  Raises MvsError (MVS_ERR_INVALID_ARG) unless the last optimize_pose_graph() on the
+        current graph succeeded."""
+        sigma, n, qi, qj, cov_out, info = _marginals_args(self.n_frames, queries, anchor_sigma, cov_out)
+        st = lib().mvs_seq_pose_graph_marginals(self._h, sigma, C.c_int(n), _ptr(qi, C.c_int32), _ptr(qj, C.c_int32),
+                                                _ptr(cov_out, C.c_double), info.ctypes.data_as(C.c_void_p))
+        self.ctx._check(st, "mvs_seq_pose_graph_marginals", allow_no_model=True)
+        return st, info[0], cov_out
 
     def sync(self):
         """wait for the context's stream (the loop-closure calls are asynchronous)"""

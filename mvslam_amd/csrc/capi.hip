@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "pg_envelope.hpp"
 
 using namespace mvs_host;
 
@@ -4028,6 +4029,194 @@ mvs_status mvs_seq_download_pose_graph_poses(mvs_seq *q, double *poses)
     HIP_TRY(ctx, hipMemcpyAsync(poses, q->graph_opt_pose, (size_t)q->n_frames * 96, hipMemcpyDeviceToHost, ctx_stream(ctx)));
     HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
+}
+
+// ---- marginal covariances of a pose graph (pg_marginals.hip, pg_envelope.hpp) -------------------
+// what the host decides before anything is launched: the query list, the envelope, the per-block term lists, the chunk
+struct PgmPlan {
+    std::vector<int32_t> first, row_off, qi, qj;
+    mvs_pgm::BlockLists lists;
+    int64_t blocks = 0;
+    int chunk = 1;
+};
+
+static mvs_status pgm_plan(int N, int E, int anchor, const int32_t *src, const int32_t *dst, int n_query, const int32_t *qi,
+                           const int32_t *qj, PgmPlan &P)
+{
+    if (!mvs_pgm::expand_queries(N, n_query, qi, qj, P.qi, P.qj))
+        return MVS_ERR_INVALID_ARG;
+    P.blocks = mvs_pgm::envelope(N, E, src, dst, P.first, P.row_off);
+    if (P.blocks > mvs_pgm::kMaxEnvelopeBlocks)
+        return MVS_ERR_CAPACITY;
+    P.lists = mvs_pgm::block_lists(E, anchor, src, dst, P.first, P.row_off);
+    P.chunk = std::min(mvs_pgm::query_chunk(N), (int)P.qi.size());
+    return MVS_OK;
+}
+
+// the solver's scratch, as offsets from one base in ctx->pgm
+struct PgmLayout {
+    size_t o_state, o_first, o_row, o_sblk, o_soff, o_codes, o_qi, o_qj, o_Ha, o_out, o_lin, o_sky, o_y, total;
+    PgmLayout(size_t N, size_t E, const PgmPlan &P)
+    {
+        Carve L{64};
+        o_state = L.take(sizeof(PgmState));
+        o_first = L.take(N * 4), o_row = L.take((N + 1) * 4);
+        o_sblk = L.take(P.lists.slot_blk.size() * 4), o_soff = L.take(P.lists.slot_off.size() * 4);
+        o_codes = L.take(P.lists.codes.size() * 4);
+        o_qi = L.take(P.qi.size() * 4), o_qj = L.take(P.qj.size() * 4);
+        o_Ha = L.take(36 * 8), o_out = L.take((size_t)P.chunk * 36 * 8);
+        o_lin = L.take(E * kPgLin * 8), o_sky = L.take((size_t)P.blocks * 36 * 8);
+        o_y = L.take((size_t)P.chunk * N * 6 * mvs_pgm::kYCols * 8);
+        total = L.total();
+    }
+};
+
+// assembly, factorisation and the solves over a device-resident graph; `base`: scratch of PgmLayout::total bytes.  d_node
+// holds the anchor's mean, d_X the linearisation point.  cov_out is written only behind a factorisation that succeeded.
+static mvs_status pgm_run(mvs_ctx *ctx, char *base, const PgmLayout &L, const PgmPlan &P, int N, int E, int anchor,
+                          const int32_t *d_src, const int32_t *d_dst, const double *d_node, const double *d_X, const double *d_z,
+                          const double *d_cov, const double anchor_sigma[2], double *cov_out, mvs_pose_graph_marginals_info *info)
+{
+    hipStream_t s = ctx_stream(ctx);
+    const PgmState st0{0, -1, HUGE_VAL};
+    auto up = [&](size_t o, const void *src, size_t bytes) {
+        return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    };
+    HIP_TRY(ctx, up(L.o_state, &st0, sizeof(st0)));
+    HIP_TRY(ctx, up(L.o_first, P.first.data(), P.first.size() * 4));
+    HIP_TRY(ctx, up(L.o_row, P.row_off.data(), P.row_off.size() * 4));
+    HIP_TRY(ctx, up(L.o_sblk, P.lists.slot_blk.data(), P.lists.slot_blk.size() * 4));
+    HIP_TRY(ctx, up(L.o_soff, P.lists.slot_off.data(), P.lists.slot_off.size() * 4));
+    HIP_TRY(ctx, up(L.o_codes, P.lists.codes.data(), P.lists.codes.size() * 4));
+    HIP_TRY(ctx, up(L.o_qi, P.qi.data(), P.qi.size() * 4));
+    HIP_TRY(ctx, up(L.o_qj, P.qj.data(), P.qj.size() * 4));
+    HIP_TRY(ctx, hipMemsetAsync(base + L.o_sky, 0, (size_t)P.blocks * 36 * 8, s));
+    auto dp = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
+    auto ip = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o); };
+    PgmDev d{};
+    d.n_nodes = N, d.n_edges = E, d.anchor = anchor, d.n_slots = (int)P.lists.slot_blk.size();
+    d.w_anchor[0] = 1.0 / (anchor_sigma[0] * anchor_sigma[0]);
+    d.w_anchor[1] = 1.0 / (anchor_sigma[1] * anchor_sigma[1]);
+    d.edge_src = d_src, d.edge_dst = d_dst, d.edge_pose = d_z, d.edge_cov = d_cov, d.pose0 = d_node, d.X = d_X;
+    d.first = ip(L.o_first), d.row_off = ip(L.o_row), d.slot_blk = ip(L.o_sblk), d.slot_off = ip(L.o_soff), d.codes = ip(L.o_codes);
+    d.lin = dp(L.o_lin), d.Ha = dp(L.o_Ha), d.sky = dp(L.o_sky), d.y = dp(L.o_y), d.out = dp(L.o_out);
+    d.state = reinterpret_cast<PgmState *>(base + L.o_state);
+    launch_pgm_assemble(d, s);
+    launch_pgm_factor(d, s);
+    HIP_TRY(ctx, hipGetLastError());
+    PgmState h{};
+    HIP_TRY(ctx, hipMemcpyAsync(&h, d.state, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));   // the plan's vectors and st0 have been read by here, too
+    info->bad_node = h.bad_node;
+    info->min_pivot = h.status == 1 ? 0.0 : std::sqrt(h.min_d);
+    if (h.status)
+        return MVS_NO_MODEL;
+    const int nq = (int)P.qi.size();
+    for (int off = 0; off < nq; off += P.chunk) {
+        const int n = std::min(P.chunk, nq - off);
+        d.qi = ip(L.o_qi) + off, d.qj = ip(L.o_qj) + off;
+        launch_pgm_solve(d, n, s);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(cov_out + (size_t)off * 36, d.out, (size_t)n * 36 * 8, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(ctx, sync_stream(ctx));
+    info->ok = 1;
+    return MVS_OK;
+}
+
+static bool pgm_args_ok(const double anchor_sigma[2], int n_query, const double *cov_out, const mvs_pose_graph_marginals_info *info)
+{
+    return anchor_sigma && anchor_sigma[0] > 0.0 && anchor_sigma[1] > 0.0 && n_query >= 0 && cov_out && info;
+}
+
+mvs_status mvs_pose_graph_marginals(mvs_ctx *ctx, const mvs_pose_graph *graph, const double *poses, const double anchor_sigma[2],
+                                    int n_query, const int32_t *query_i, const int32_t *query_j, double *cov_out,
+                                    mvs_pose_graph_marginals_info *info)
+{
+    if (!ctx || !graph || !pgm_args_ok(anchor_sigma, n_query, cov_out, info))
+        return MVS_ERR_INVALID_ARG;
+    const mvs_pose_graph &g = *graph;
+    mvs_status st = pose_graph_check(g);
+    if (st != MVS_OK)
+        return st;
+    const size_t N = (size_t)g.n_nodes, E = (size_t)g.n_edges;
+    if (poses && !all_finite(poses, 12 * N))
+        return MVS_ERR_INVALID_ARG;
+    *info = mvs_pose_graph_marginals_info{0, 0, -1, 0, 0.0};
+    PgmPlan P;
+    st = pgm_plan(g.n_nodes, g.n_edges, g.anchor_node, g.edge_src, g.edge_dst, n_query, query_i, query_j, P);
+    if (st != MVS_OK)
+        return st;
+    info->envelope_blocks = (int32_t)P.blocks;
+    if (!pose_graph_connected(g))
+        return MVS_NO_MODEL;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Carve U{64};
+    const size_t o_src = U.take(E * 4), o_dst = U.take(E * 4), o_z = U.take(E * 12 * 8), o_cov = U.take(E * 36 * 8);
+    const size_t o_p0 = U.take(N * 12 * 8), o_x = U.take(N * 12 * 8), o_solver = U.total();
+    const PgmLayout L(N, E, P);
+    st = ws_grow(ctx, ctx->pgm, o_solver + L.total);
+    if (st != MVS_OK)
+        return st;
+    char *base = ctx->pgm.ptr();
+    hipStream_t s = ctx_stream(ctx);
+    if (E) {
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_src, g.edge_src, E * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_dst, g.edge_dst, E * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_z, g.edge_pose, E * 12 * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_cov, g.edge_cov, E * 36 * 8, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_p0, g.node_pose, N * 12 * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_x, poses ? poses : g.node_pose, N * 12 * 8, hipMemcpyHostToDevice, s));
+    auto dp = [&](size_t o) { return reinterpret_cast<const double *>(base + o); };
+    auto ip = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o); };
+    return pgm_run(ctx, base + o_solver, L, P, g.n_nodes, g.n_edges, g.anchor_node, ip(o_src), ip(o_dst), dp(o_p0), dp(o_x),
+                   dp(o_z), dp(o_cov), anchor_sigma, cov_out, info);
+}
+
+mvs_status mvs_seq_pose_graph_marginals(mvs_seq *q, const double anchor_sigma[2], int n_query, const int32_t *query_i,
+                                        const int32_t *query_j, double *cov_out, mvs_pose_graph_marginals_info *info)
+{
+    if (!q || !q->graph_built || !q->graph_opt || !pgm_args_ok(anchor_sigma, n_query, cov_out, info))
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const SeqGraphDev &g = q->gd;
+    hipStream_t s = ctx_stream(ctx);
+    // the count and the edges' endpoints: all the host needs of the graph
+    const char *gbase = q->graph.ptr();
+    const size_t o_src = (const char *)g.edge_src - gbase, o_dst = (const char *)g.edge_dst - gbase;
+    std::vector<char> head(o_dst + (size_t)q->graph_edge_cap * 4);
+    HIP_TRY(ctx, hipMemcpyAsync(head.data(), gbase, head.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    int32_t E = 0;
+    std::memcpy(&E, head.data(), 4);
+    const int32_t *h_src = reinterpret_cast<const int32_t *>(head.data() + o_src);
+    const int32_t *h_dst = reinterpret_cast<const int32_t *>(head.data() + o_dst);
+    const int N = g.n_frames;
+    bool edges_ok = E >= 0 && E <= q->graph_edge_cap;
+    for (int k = 0; edges_ok && k < E; ++k)
+        edges_ok = h_src[k] >= 0 && h_src[k] < N && h_dst[k] >= 0 && h_dst[k] < N && h_src[k] != h_dst[k];
+    if (!edges_ok) {
+        ctx->err = "mvs_seq_pose_graph_marginals: the resident graph's edges are out of range";
+        return MVS_ERR_HIP;
+    }
+    *info = mvs_pose_graph_marginals_info{0, 0, -1, 0, 0.0};
+    PgmPlan P;
+    mvs_status st = pgm_plan(N, E, 0, h_src, h_dst, n_query, query_i, query_j, P);
+    if (st != MVS_OK)
+        return st;
+    info->envelope_blocks = (int32_t)P.blocks;
+    mvs_pose_graph hg{};
+    hg.n_nodes = N, hg.n_edges = E, hg.edge_src = h_src, hg.edge_dst = h_dst, hg.anchor_node = 0;
+    if (!pose_graph_connected(hg))
+        return MVS_NO_MODEL;
+    const PgmLayout L((size_t)N, (size_t)E, P);
+    st = ws_grow(ctx, ctx->pgm, L.total);
+    if (st != MVS_OK)
+        return st;
+    return pgm_run(ctx, ctx->pgm.ptr(), L, P, N, E, 0, g.edge_src, g.edge_dst, g.node_pose, q->graph_opt_pose, g.edge_pose,
+                   g.edge_cov, anchor_sigma, cov_out, info);
 }
 
 // ---- loop closures of a resident sequence (loop.hip, seq_graph.hip) -----------------------------

@@ -67,6 +67,7 @@ struct mvs_ctx {
     DevWorkspace ref;         // sfm_refine / pnp_refine workspace
     DevWorkspace win;         // mvs_ba_refine_windows workspace
     DevWorkspace pg;          // mvs_pose_graph_optimize workspace
+    DevWorkspace pgm;         // mvs_pose_graph_marginals workspace: uploads, lists, the skyline, the solves' y
     DevWorkspace orb;         // extraction workspace: orb_graph points into it
     int32_t *h_orb_ovf = nullptr;   // pinned: the extraction's overflow flag travels with the outputs (one stream wait per call)
     bool orb_ready = false;

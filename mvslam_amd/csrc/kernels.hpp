@@ -334,6 +334,39 @@ void launch_pg_begin(const PgLargeDev &d, int cur, double lam, bool first, hipSt
 void launch_pg_cg(const PgLargeDev &d, double lam, int n, hipStream_t stream);
 void launch_pg_end(const PgLargeDev &d, int cur, hipStream_t stream);
 
+// ---- marginal covariances of a pose graph (pg_marginals.hip) ---------------------------------
+// H = J_a^T W_a J_a + sum_k J_k^T W_k J_k at the poses X, no lambda, as the block lower triangle inside its envelope (row i
+// holds the blocks first[i] .. i, 36 doubles each, row-major); factorised in place, H = L L^T.
+struct PgmState {
+    int32_t status;      // 0 running / done, 1 an edge covariance is not positive definite, 2 a pivot failed
+    int32_t bad_node;    // the node of that pivot, -1 otherwise
+    double min_d;        // the smallest pivot before its square root (the smallest diagonal entry of L, squared)
+};
+struct PgmDev {
+    int n_nodes, n_edges, anchor, n_slots;
+    double w_anchor[2];
+    const int32_t *edge_src, *edge_dst;
+    const double *edge_pose, *edge_cov;
+    const double *pose0;         // [N][12] the anchor's mean is pose0[anchor]
+    const double *X;             // [N][12] the linearisation point
+    const int32_t *first;        // [N]
+    const int32_t *row_off;      // [N + 1] first block of every row in sky
+    const int32_t *slot_blk;     // [n_slots] block of H that slot s owns
+    const int32_t *slot_off;     // [n_slots + 1]
+    const int32_t *codes;        // terms of every slot in edge order (pg_envelope.hpp block_lists)
+    double *lin;                 // [E][kPgLin]
+    double *Ha;                  // [36] the anchor prior's block
+    double *sky;                 // [envelope blocks][36]
+    PgmState *state;
+    // the solves: query q = (qi[q], qj[q]) owns y[q] and writes out[q]
+    const int32_t *qi, *qj;
+    double *y;                   // [chunk][N][6][12]
+    double *out;                 // [chunk][36]
+};
+void launch_pgm_assemble(const PgmDev &d, hipStream_t stream);
+void launch_pgm_factor(const PgmDev &d, hipStream_t stream);
+void launch_pgm_solve(const PgmDev &d, int n_query, hipStream_t stream);
+
 // ---- sliding windows of a resident sequence (mvs_seq_refine_windows) -------------------------
 // seq_link_kernel chains the inlier matches of consecutive pairs into tracks (every keypoint gets at most one successor and
 // one predecessor); seq_window_assemble_kernel turns the tracks of window w = frames [w * stride, w * stride + F) into the
