@@ -1,5 +1,6 @@
 // capi.hip -- host side of libmvslam_hip.so: contexts, resident batches, the C ABI of include/mvslam_hip.h.  Extraction is
-// in capi_orb.hip, the mvs_debug_* hooks of the diagnostics library in capi_debug.hip; capi_internal.hpp holds what they share.
+// in capi_orb.hip, the back end (pose graphs, marginals, loop closures) in capi_graph.hip, the mvs_debug_* hooks of the
+// diagnostics library in capi_debug.hip; capi_internal.hpp holds what they share.
 // No CPU fallback exists anywhere in these files: every entry point ends in a HIP kernel launch.
 #include <dlfcn.h>
 
@@ -12,7 +13,6 @@
 #include <vector>
 
 #include "capi_internal.hpp"
-#include "pg_envelope.hpp"
 
 using namespace mvs_host;
 
@@ -230,10 +230,9 @@ static mvs_status ensure_e5(mvs_batch *b, int num_hypotheses)
 }
 
 // The model stage in front of the shared tail (decomposition, triangulation): the 8-point RANSAC of kernels.hip or the
-// five-point one of essential5.hip.  Everything the two differ in on the host is in the two functions below.
-enum class Estimator { kEightPoint, kFivePoint };
-
-static mvs_status ensure_tables(mvs_batch *b, Estimator est, int num_hypotheses)
+// five-point one of essential5.hip (Estimator: capi_internal.hpp).  Everything the two differ in on the host is in the two
+// functions below and in run_pairs.
+mvs_status mvs_host::ensure_tables(mvs_batch *b, Estimator est, int num_hypotheses)
 {
     switch (est) {
     case Estimator::kEightPoint: return ensure_groups(b, num_hypotheses);
@@ -460,18 +459,16 @@ mvs_status mvs_ctx_essential_hypotheses_run(mvs_ctx *ctx, int32_t *n_run)
 // ---------------------------------------------------------------------------------------------
 // n_frames == 0: every pair owns its two images.  n_frames == n_pairs + 1: the images are the frames of a sequence,
 // stored once; pair k = (frame k, frame k + 1) is a view into the frame arrays (row f2).
-static mvs_status batch_create_impl(mvs_ctx *ctx, int n_pairs, int max_kp, int desc_bytes, int n_frames, mvs_batch **out,
-                                    const BatchDev *frames_of = nullptr, int lag = 1);
-
 mvs_status mvs_batch_create(mvs_ctx *ctx, int n_pairs, int max_kp, int desc_bytes, mvs_batch **out)
 {
     return batch_create_impl(ctx, n_pairs, max_kp, desc_bytes, 0, out);
 }
 
 // n_frames != 0: the batch of a sequence, pair k = (frame k, frame k + lag) viewing ONE set of frame arrays -- its own, or
-// with frames_of those (and the intrinsics and key offsets) of the sequence's lag-1 batch
-static mvs_status batch_create_impl(mvs_ctx *ctx, int n_pairs, int max_kp, int desc_bytes, int n_frames, mvs_batch **out,
-                                    const BatchDev *frames_of, int lag)
+// with frames_of those (and the intrinsics and key offsets) of the sequence's lag-1 batch.  (extern "C++": a member of
+// mvs_host defined inside the extern "C" block keeps the linkage of its declaration.)
+extern "C++" mvs_status mvs_host::batch_create_impl(mvs_ctx *ctx, int n_pairs, int max_kp, int desc_bytes, int n_frames,
+                                                    mvs_batch **out, const BatchDev *frames_of, int lag)
 {
     if (!ctx || !out || n_pairs < 1 || max_kp < 1)
         return MVS_ERR_INVALID_ARG;
@@ -702,7 +699,7 @@ void mvs_host_free(void *p)
         (void)hipHostFree(p);
 }
 
-static mvs_status check_params(const mvs_params *p)
+extern "C++" mvs_status mvs_host::check_params(const mvs_params *p)
 {
     if (!p || p->num_hypotheses < 1 || (p->sampler != MVS_SAMPLER_IDENTITY && p->sampler != MVS_SAMPLER_PHILOX))
         return MVS_ERR_INVALID_ARG;  // estimator-RANSAC.cpp:13 assert(max_iteration > 0)
@@ -909,6 +906,12 @@ static mvs_status enqueue_essential(mvs_batch *b, const RunParams &rp, int n)
     enqueue_model(b, Estimator::kFivePoint, rp, n);
     HIP_TRY(b->ctx, hipGetLastError());
     return MVS_OK;
+}
+
+// the descriptor-fed pipeline of either estimator for pairs [0, n) (the tables are grown: ensure_tables)
+extern "C++" mvs_status mvs_host::run_pairs(mvs_batch *b, Estimator est, const RunParams &rp, int n)
+{
+    return est == Estimator::kEightPoint ? enqueue_pipeline(b, rp, n, false, nullptr) : enqueue_essential(b, rp, n);
 }
 
 // mvs_batch_run with find_essential_matrix's five-point branch (sfm-solve.cpp:42-63) in place of the 8-point RANSAC
@@ -1607,9 +1610,7 @@ static mvs_status image_pair_impl(mvs_ctx *ctx, Estimator est, const uint8_t *ba
         sp.part_bytes[2] = (uint32_t)kb1; sp.part_bytes[3] = (uint32_t)kb2;
         launch_single_params(b->d, sp, ctx->single_in.ptr(), ctx_stream(ctx));
     }
-    st = est == Estimator::kEightPoint ? enqueue_pipeline(b, to_run(*params), 1, false, nullptr)
-                                       : enqueue_essential(b, to_run(*params), 1);
-    if (st != MVS_OK)
+    if ((st = run_pairs(b, est, to_run(*params), 1)) != MVS_OK)
         return st;
     if ((st = fetch_single(ctx, n_pair, result, points_xyz, point_idx, inlier_mask, matches)) != MVS_OK)
         return st;
@@ -2088,8 +2089,7 @@ static mvs_status seq_prepare(mvs_seq *q, Estimator est, const mvs_params *tv, c
 static mvs_status seq_enqueue(mvs_seq *q, Estimator est, const RunParams &rp, hipEvent_t *ev = nullptr)
 {
     if (ev) HIP_TRY(q->ctx, hipEventRecord(ev[0], ctx_stream(q->ctx)));
-    mvs_status st = est == Estimator::kEightPoint ? enqueue_pipeline(q->batch, rp, q->n_frames - 1, false, nullptr)
-                                                  : enqueue_essential(q->batch, rp, q->n_frames - 1);
+    mvs_status st = run_pairs(q->batch, est, rp, q->n_frames - 1);
     if (st != MVS_OK)
         return st;
     hipStream_t s = ctx_stream(q->ctx);   // behind both halves of the pairs: the join reads every pair
@@ -2381,7 +2381,7 @@ void mvs_refine_params_default(mvs_refine_params *p)
     p->point_sigma = 1e-2;
 }
 
-static bool refine_params_ok(const mvs_refine_params *p)
+extern "C++" bool mvs_host::refine_params_ok(const mvs_refine_params *p)
 {
     return p && p->max_iterations >= 0 && p->lambda_initial >= 0.0 && p->lambda_factor > 1.0 &&
            p->lambda_upper > 0.0 && p->anchor_sigma[0] > 0.0 && p->anchor_sigma[1] > 0.0 && p->pose_sigma[0] > 0.0 &&
@@ -3253,8 +3253,7 @@ mvs_status mvs_seq_run_lags(mvs_seq *q, const mvs_params *two_view, int max_lag,
     for (int lag = 1; lag <= max_lag; ++lag) {
         mvs_batch *b = lag == 1 ? q->batch : q->lag_batch[lag];
         const int n = q->n_frames - lag;
-        if (lag > 1 && (st = est == Estimator::kEightPoint ? enqueue_pipeline(b, run, n, false, nullptr)
-                                                           : enqueue_essential(b, run, n)) != MVS_OK)
+        if (lag > 1 && (st = run_pairs(b, est, run, n)) != MVS_OK)
             return st;
         if ((st = mvs_batch_refine(b, rp, sigma_px)) != MVS_OK)
             return st;
@@ -3457,971 +3456,5 @@ mvs_status mvs_seq_upload_images(mvs_seq *q, int first, int count, const uint8_t
     if (st != MVS_OK)
         return st;
     return K ? mvs_seq_upload(q, first, count, nullptr, nullptr, nullptr, K) : MVS_OK;
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// pose graphs (the back end; posegraph.hip)
-void mvs_pose_graph_params_default(mvs_pose_graph_params *p)
-{
-    if (!p)
-        return;
-    mvs_refine_params_default(&p->lm);
-    p->anchor_sigma[0] = p->anchor_sigma[1] = 1e-4;   // graph.cpp GRAPH_ANCHOR_STDDEV
-    p->cg_rel_tol = 1e-10;
-    p->cg_max_iterations = 0;                         // 6 n_nodes
-    p->cg_chunk_iterations = 0;                       // the whole budget at once
-}
-
-static PgCfg to_pg_cfg(const mvs_pose_graph_params &p)
-{
-    PgCfg c{};
-    c.max_iterations = p.lm.max_iterations;
-    c.lambda_initial = p.lm.lambda_initial;
-    c.lambda_factor = p.lm.lambda_factor;
-    c.lambda_upper = p.lm.lambda_upper;
-    c.rel_tol = p.lm.rel_tol;
-    c.abs_tol = p.lm.abs_tol;
-    c.w_anchor[0] = 1.0 / (p.anchor_sigma[0] * p.anchor_sigma[0]);
-    c.w_anchor[1] = 1.0 / (p.anchor_sigma[1] * p.anchor_sigma[1]);
-    c.cg_rel_tol = p.cg_rel_tol;
-    c.cg_max_iterations = p.cg_max_iterations;
-    return c;
-}
-
-static bool all_finite(const double *v, size_t n)
-{
-    for (size_t i = 0; i < n; ++i)
-        if (!std::isfinite(v[i]))
-            return false;
-    return true;
-}
-
-// arguments of one graph: MVS_ERR_INVALID_ARG / MVS_ERR_CAPACITY before anything runs
-static mvs_status pose_graph_check(const mvs_pose_graph &g)
-{
-    if (g.n_nodes < 1 || g.n_edges < 0 || !g.node_pose)
-        return MVS_ERR_INVALID_ARG;
-    if (g.n_edges > 0 && (!g.edge_src || !g.edge_dst || !g.edge_pose || !g.edge_cov))
-        return MVS_ERR_INVALID_ARG;
-    if (g.n_nodes > kPgMaxNodes || g.n_edges > kPgMaxEdges)
-        return MVS_ERR_CAPACITY;
-    if (g.anchor_node < 0 || g.anchor_node >= g.n_nodes)
-        return MVS_ERR_INVALID_ARG;
-    for (int k = 0; k < g.n_edges; ++k) {
-        const int s = g.edge_src[k], d = g.edge_dst[k];
-        if (s < 0 || s >= g.n_nodes || d < 0 || d >= g.n_nodes || s == d)
-            return MVS_ERR_INVALID_ARG;
-    }
-    if (!all_finite(g.node_pose, 12 * (size_t)g.n_nodes) || !all_finite(g.edge_pose, 12 * (size_t)g.n_edges) ||
-        !all_finite(g.edge_cov, 36 * (size_t)g.n_edges))
-        return MVS_ERR_INVALID_ARG;
-    return MVS_OK;
-}
-
-// does a path of edges join every node to the anchor?  (With lambda on the diagonal a floating component would not break
-// the linear solve: its gauge freedom only leaves the values where they are.  So the topology is checked, exactly.)
-static bool pose_graph_connected(const mvs_pose_graph &g)
-{
-    std::vector<int> parent((size_t)g.n_nodes);
-    for (int i = 0; i < g.n_nodes; ++i)
-        parent[i] = i;
-    auto find = [&](int a) {
-        while (parent[a] != a)
-            a = parent[a] = parent[parent[a]];
-        return a;
-    };
-    for (int k = 0; k < g.n_edges; ++k)
-        parent[find(g.edge_src[k])] = find(g.edge_dst[k]);
-    const int root = find(g.anchor_node);
-    for (int i = 0; i < g.n_nodes; ++i)
-        if (find(i) != root)
-            return false;
-    return true;
-}
-
-// ---- the solver's entries over device-resident graphs ------------------------------------------------------------------
-// The host-pointer calls upload and come here; mvs_seq_optimize_pose_graph comes here with the graph of its sequence.  Only
-// edge_src / edge_dst are also needed on the host (connectivity, the CSR list).
-
-// scratch of the large path for N nodes and E edges, as offsets from one base in ctx->pg
-struct PgLargeLayout {
-    size_t o_state, o_off, o_inc, o_pa, o_pb, o_W, o_lin, o_u, o_ec, o_D, o_Mf, o_vec[6], o_pq, o_Ha, total;
-    PgLargeLayout(size_t N, size_t E)
-    {
-        Carve L{64};
-        o_state = L.take(sizeof(PgState));
-        o_off = L.take((N + 1) * 4), o_inc = L.take(2 * E * 4);
-        o_pa = L.take(N * 12 * 8), o_pb = L.take(N * 12 * 8);
-        o_W = L.take(E * 21 * 8), o_lin = L.take(E * kPgLin * 8), o_u = L.take(E * 6 * 8), o_ec = L.take(E * 8);
-        o_D = L.take(N * 21 * 8), o_Mf = L.take(N * 21 * 8);
-        for (size_t &o : o_vec)
-            o = L.take(N * 6 * 8);
-        o_pq = L.take(N * 8), o_Ha = L.take(36 * 8);
-        total = L.total();
-    }
-};
-
-// one graph of 17 .. 4096 nodes: LM on the host, one synchronisation per iteration (and, with cg_chunk_iterations > 0, one
-// per chunk of CG iterations that did not converge).  h_src / h_dst: the edges on the host; every d_* pointer is device
-// memory that stays valid through the call; `base` is scratch of PgLargeLayout(N, E).total bytes.  The optimised nodes go
-// to poses_out with a copy of kind `out_kind` (device to host, or device to device), only when the result is ok.
-static mvs_status pose_graph_large_dev(mvs_ctx *ctx, char *base, int n_nodes, int n_edges, int anchor, const int32_t *h_src,
-                                       const int32_t *h_dst, const int32_t *d_src, const int32_t *d_dst, const double *d_node,
-                                       const double *d_z, const double *d_cov, const mvs_pose_graph_params &params,
-                                       mvs_pose_graph_result *res, double *poses_out, hipMemcpyKind out_kind)
-{
-    const size_t N = (size_t)n_nodes, E = (size_t)n_edges;
-    // CSR list of the incident edges of every node, in edge order
-    std::vector<int32_t> off(N + 1, 0), inc(2 * E);
-    for (size_t k = 0; k < E; ++k) {
-        ++off[(size_t)h_src[k] + 1];
-        ++off[(size_t)h_dst[k] + 1];
-    }
-    for (size_t i = 0; i < N; ++i)
-        off[i + 1] += off[i];
-    {
-        std::vector<int32_t> fill(off.begin(), off.end() - 1);
-        for (size_t k = 0; k < E; ++k) {
-            inc[(size_t)fill[(size_t)h_src[k]]++] = (int32_t)(2 * k);
-            inc[(size_t)fill[(size_t)h_dst[k]]++] = (int32_t)(2 * k + 1);
-        }
-    }
-    const PgLargeLayout L(N, E);
-    hipStream_t s = ctx_stream(ctx);
-    HIP_TRY(ctx, hipMemsetAsync(base + L.o_state, 0, sizeof(PgState), s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + L.o_off, off.data(), (N + 1) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + L.o_inc, inc.data(), 2 * E * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + L.o_pa, d_node, N * 12 * 8, hipMemcpyDeviceToDevice, s));
-    auto dp = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
-    auto ip = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o); };
-    PgLargeDev d{};
-    d.n_nodes = n_nodes, d.n_edges = n_edges, d.anchor = anchor;
-    d.cfg = to_pg_cfg(params);
-    d.edge_src = d_src, d.edge_dst = d_dst, d.csr_off = ip(L.o_off), d.csr_inc = ip(L.o_inc);
-    d.edge_pose = d_z, d.edge_cov = d_cov, d.pose0 = d_node;
-    d.pose[0] = dp(L.o_pa), d.pose[1] = dp(L.o_pb);
-    d.W = dp(L.o_W), d.lin = dp(L.o_lin), d.u = dp(L.o_u), d.ecost = dp(L.o_ec), d.D = dp(L.o_D), d.Mf = dp(L.o_Mf);
-    d.g = dp(L.o_vec[0]), d.x = dp(L.o_vec[1]), d.r = dp(L.o_vec[2]), d.z = dp(L.o_vec[3]), d.p = dp(L.o_vec[4]), d.q = dp(L.o_vec[5]);
-    d.pq = dp(L.o_pq), d.Ha = dp(L.o_Ha);
-    d.state = reinterpret_cast<PgState *>(base + L.o_state);
-    const int cg_max = params.cg_max_iterations > 0 ? params.cg_max_iterations : 6 * n_nodes;
-    const int chunk = params.cg_chunk_iterations;
-    launch_pg_prep(d, s);
-    HIP_TRY(ctx, hipGetLastError());
-    PgState h{};
-    // a covariance that is not positive definite ends the call here, before anything is linearised on its whitening factor
-    HIP_TRY(ctx, hipMemcpyAsync(&h, d.state, sizeof(h), hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, sync_stream(ctx));   // `off` and `inc` have been read by here, too
-    if (h.bad_cov) {
-        *res = mvs_pose_graph_result{};
-        return MVS_OK;
-    }
-
-    // the LM rule of refine_kernel, on the host: the device computes, the host decides
-    const PgCfg &cfg = d.cfg;
-    int cb = 0, it = 0, rejected = 0, cg_total = 0;
-    double cur = 0.0, cost0 = 0.0, lam = cfg.lambda_initial;
-    bool ok0 = true, have0 = false;
-    while (ok0 && it < cfg.max_iterations) {
-        launch_pg_begin(d, cb, lam, !have0, s);
-        if (chunk <= 0) {
-            launch_pg_cg(d, lam, cg_max, s);
-        } else {
-            // chunk by chunk: the iterations not enqueued are the ones the status word would have sent away at once
-            for (int left = cg_max; left > 0;) {
-                const int n = std::min(chunk, left);
-                launch_pg_cg(d, lam, n, s);
-                left -= n;
-                if (left > 0) {
-                    HIP_TRY(ctx, hipGetLastError());
-                    HIP_TRY(ctx, hipMemcpyAsync(&h, d.state, sizeof(h), hipMemcpyDeviceToHost, s));
-                    HIP_TRY(ctx, sync_stream(ctx));
-                    if (h.done)
-                        break;
-                }
-            }
-        }
-        launch_pg_end(d, cb, s);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(&h, d.state, sizeof(h), hipMemcpyDeviceToHost, s));
-        HIP_TRY(ctx, sync_stream(ctx));
-        if (!have0) {
-            have0 = true;
-            cost0 = cur = h.cost0;
-            ok0 = std::isfinite(cur);
-            if (!ok0)
-                break;
-        }
-        cg_total += h.cg_iters;
-        // the linear solve counts as done when the CG converged, or ran out of iterations with a smaller residual
-        const bool solved = h.done == 1 || (h.done == 0 && h.rr < h.gnorm2);
-        const double cand = h.cand;
-        const bool accepted = solved && cand <= cur;
-        ++it;
-        if (accepted) {
-            cb ^= 1;
-            const double dec = 0.5 * (cur - cand);
-            const bool done = dec <= cfg.abs_tol || dec <= cfg.rel_tol * (0.5 * cur);
-            cur = cand;
-            lam = lam / cfg.lambda_factor;
-            if (done)
-                break;
-        } else {
-            ++rejected;
-            const double inc_e = 0.5 * (cand - cur);
-            if (solved && (inc_e <= cfg.abs_tol || inc_e <= cfg.rel_tol * (0.5 * cur)))
-                break;
-            lam = lam * cfg.lambda_factor;
-            if (lam > cfg.lambda_upper)
-                break;
-        }
-    }
-    if (!have0) {   // max_iterations = 0: the cost at the initial values alone (an iteration with no CG steps leaves x = 0)
-        launch_pg_begin(d, cb, lam, true, s);
-        launch_pg_end(d, cb, s);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(&h, d.state, sizeof(h), hipMemcpyDeviceToHost, s));
-        HIP_TRY(ctx, sync_stream(ctx));
-        cost0 = cur = h.cost0;
-        ok0 = std::isfinite(cur);
-    }
-    res->ok = ok0 ? 1 : 0;
-    res->iterations = it;
-    res->cg_iterations = cg_total;
-    res->rejected_steps = rejected;
-    res->error_initial = ok0 ? 0.5 * cost0 : 0.0;
-    res->error = ok0 ? 0.5 * cur : 0.0;
-    if (ok0) {
-        HIP_TRY(ctx, hipMemcpyAsync(poses_out, d.pose[cb], N * 12 * 8, out_kind, s));
-        HIP_TRY(ctx, sync_stream(ctx));
-    }
-    return MVS_OK;
-}
-
-// the host-pointer entry of the large path: upload, then the entry above
-static mvs_status pose_graph_large(mvs_ctx *ctx, const mvs_pose_graph &g, const mvs_pose_graph_params &params,
-                                   mvs_pose_graph_result *res, double *poses_out)
-{
-    const size_t N = (size_t)g.n_nodes, E = (size_t)g.n_edges;
-    Carve U{64};
-    const size_t o_src = U.take(E * 4), o_dst = U.take(E * 4), o_z = U.take(E * 12 * 8), o_cov = U.take(E * 36 * 8);
-    const size_t o_p0 = U.take(N * 12 * 8), o_solver = U.total();
-    mvs_status st = ws_grow(ctx, ctx->pg, o_solver + PgLargeLayout(N, E).total);
-    if (st != MVS_OK)
-        return st;
-    char *base = ctx->pg.ptr();
-    hipStream_t s = ctx_stream(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_src, g.edge_src, E * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_dst, g.edge_dst, E * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_z, g.edge_pose, E * 12 * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_cov, g.edge_cov, E * 36 * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_p0, g.node_pose, N * 12 * 8, hipMemcpyHostToDevice, s));
-    auto dp = [&](size_t o) { return reinterpret_cast<const double *>(base + o); };
-    auto ip = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o); };
-    return pose_graph_large_dev(ctx, base + o_solver, g.n_nodes, g.n_edges, g.anchor_node, g.edge_src, g.edge_dst, ip(o_src),
-                                ip(o_dst), dp(o_p0), dp(o_z), dp(o_cov), params, res, poses_out, hipMemcpyDeviceToHost);
-}
-
-// scratch of a dense-path batch of G graphs with sumN nodes and sumE edges.  Outputs first and contiguous (results,
-// poses): a download is their prefix.
-struct PgDenseLayout {
-    size_t o_out, o_po, down, o_W, o_lin, total;
-    PgDenseLayout(size_t G, size_t sumN, size_t sumE)
-    {
-        Carve L{64};
-        o_out = L.take(G * sizeof(mvs_pose_graph_result)), o_po = L.take(sumN * 12 * 8);
-        down = L.total();
-        o_W = L.take(sumE * 21 * 8), o_lin = L.take(sumE * kPgLin * 8);
-        total = L.total();
-    }
-};
-
-// graphs of up to 16 nodes over device-resident inputs: one launch.  `base`: scratch of PgDenseLayout::total bytes.
-static mvs_status pose_graph_dense_dev(mvs_ctx *ctx, char *base, const PgDenseLayout &L, int n_graphs,
-                                       const mvs_pose_graph_params &params, const PgProblem *d_prob, const double *d_node,
-                                       const int32_t *d_src, const int32_t *d_dst, const double *d_z, const double *d_cov)
-{
-    PgDenseDev d{};
-    d.n_problems = n_graphs;
-    d.cfg = to_pg_cfg(params);
-    d.prob = d_prob;
-    d.node_pose = d_node;
-    d.edge_pose = d_z;
-    d.edge_cov = d_cov;
-    d.edge_src = d_src;
-    d.edge_dst = d_dst;
-    d.W = reinterpret_cast<double *>(base + L.o_W);
-    d.lin = reinterpret_cast<double *>(base + L.o_lin);
-    d.poses_out = reinterpret_cast<double *>(base + L.o_po);
-    d.out = reinterpret_cast<mvs_pose_graph_result *>(base + L.o_out);
-    launch_pg_dense(d, ctx_stream(ctx));
-    HIP_TRY(ctx, hipGetLastError());
-    return MVS_OK;
-}
-
-static bool pose_graph_params_ok(const mvs_pose_graph_params *params)
-{
-    return params && params->lm.max_iterations >= 0 && params->lm.lambda_initial >= 0.0 && params->lm.lambda_factor > 1.0 &&
-           params->lm.lambda_upper > 0.0 && params->anchor_sigma[0] > 0.0 && params->anchor_sigma[1] > 0.0 &&
-           params->cg_rel_tol >= 0.0 && params->cg_max_iterations >= 0;
-}
-
-mvs_status mvs_pose_graph_optimize_batch(mvs_ctx *ctx, const mvs_pose_graph *graphs, int n_graphs,
-                                         const mvs_pose_graph_params *params, mvs_pose_graph_result *results,
-                                         double *poses_out)
-{
-    if (!ctx || !graphs || n_graphs < 1 || !params || !results || !poses_out)
-        return MVS_ERR_INVALID_ARG;
-    if (!pose_graph_params_ok(params))
-        return MVS_ERR_INVALID_ARG;
-    int Nmax = 0;
-    for (int i = 0; i < n_graphs; ++i) {
-        const mvs_status st = pose_graph_check(graphs[i]);
-        if (st != MVS_OK)
-            return st;
-        Nmax = std::max(Nmax, graphs[i].n_nodes);
-    }
-    std::memset(results, 0, (size_t)n_graphs * sizeof(mvs_pose_graph_result));
-    std::vector<char> joined((size_t)n_graphs);
-    for (int i = 0; i < n_graphs; ++i)
-        joined[(size_t)i] = pose_graph_connected(graphs[i]) ? 1 : 0;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the batch's graphs of up to 16 nodes: one upload, one launch, one download
-    std::vector<PgProblem> desc;
-    std::vector<int> which;
-    size_t sumN = 0, sumE = 0;
-    for (int i = 0; i < n_graphs; ++i) {
-        const mvs_pose_graph &g = graphs[i];
-        if (!joined[(size_t)i] || g.n_nodes > kPgDenseMaxNodes)
-            continue;
-        PgProblem p{};
-        p.n_nodes = g.n_nodes, p.n_edges = g.n_edges, p.anchor = g.anchor_node;
-        p.node_off = (int64_t)sumN, p.edge_off = (int64_t)sumE;
-        sumN += (size_t)g.n_nodes;
-        sumE += (size_t)g.n_edges;
-        desc.push_back(p);
-        which.push_back(i);
-    }
-    if (!desc.empty()) {
-        const size_t G = desc.size();
-        const PgDenseLayout L(G, sumN, sumE);
-        const size_t o_up = L.total;   // the uploaded block: descriptors, node poses, edge poses, covariances, src, dst
-        Carve U{64};
-        const size_t u_desc = U.take(G * sizeof(PgProblem)), u_np = U.take(sumN * 12 * 8), u_z = U.take(sumE * 12 * 8);
-        const size_t u_cov = U.take(sumE * 36 * 8), u_src = U.take(sumE * 4), u_dst = U.take(sumE * 4);
-        mvs_status st = ws_grow(ctx, ctx->pg, o_up + U.total());
-        if (st != MVS_OK)
-            return st;
-        std::vector<char> up(U.total());
-        std::memcpy(up.data() + u_desc, desc.data(), G * sizeof(PgProblem));
-        for (size_t k = 0; k < G; ++k) {
-            const mvs_pose_graph &g = graphs[which[k]];
-            const size_t n = (size_t)g.n_nodes, e = (size_t)g.n_edges, no = (size_t)desc[k].node_off, eo = (size_t)desc[k].edge_off;
-            std::memcpy(up.data() + u_np + no * 96, g.node_pose, n * 96);
-            if (e) {
-                std::memcpy(up.data() + u_z + eo * 96, g.edge_pose, e * 96);
-                std::memcpy(up.data() + u_cov + eo * 288, g.edge_cov, e * 288);
-                std::memcpy(up.data() + u_src + eo * 4, g.edge_src, e * 4);
-                std::memcpy(up.data() + u_dst + eo * 4, g.edge_dst, e * 4);
-            }
-        }
-        char *base = ctx->pg.ptr();
-        hipStream_t s = ctx_stream(ctx);
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_up, up.data(), up.size(), hipMemcpyHostToDevice, s));
-        auto dp = [&](size_t o) { return reinterpret_cast<const double *>(base + o_up + o); };
-        auto ip = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o_up + o); };
-        st = pose_graph_dense_dev(ctx, base, L, (int)G, *params, reinterpret_cast<const PgProblem *>(base + o_up + u_desc),
-                                  dp(u_np), ip(u_src), ip(u_dst), dp(u_z), dp(u_cov));
-        if (st != MVS_OK)
-            return st;
-        std::vector<char> host(L.down);
-        HIP_TRY(ctx, hipMemcpyAsync(host.data(), base, L.down, hipMemcpyDeviceToHost, s));
-        HIP_TRY(ctx, sync_stream(ctx));
-        for (size_t k = 0; k < G; ++k) {
-            const int i = which[k];
-            std::memcpy(&results[i], host.data() + L.o_out + k * sizeof(mvs_pose_graph_result), sizeof(mvs_pose_graph_result));
-            if (results[i].ok)
-                std::memcpy(poses_out + (size_t)i * Nmax * 12, host.data() + L.o_po + (size_t)desc[k].node_off * 96,
-                            (size_t)graphs[i].n_nodes * 96);
-        }
-    }
-    // larger graphs, one after another
-    for (int i = 0; i < n_graphs; ++i) {
-        if (!joined[(size_t)i] || graphs[i].n_nodes <= kPgDenseMaxNodes)
-            continue;
-        const mvs_status st = pose_graph_large(ctx, graphs[i], *params, &results[i], poses_out + (size_t)i * Nmax * 12);
-        if (st != MVS_OK)
-            return st;
-    }
-    bool all_ok = true;
-    for (int i = 0; i < n_graphs; ++i)
-        all_ok = all_ok && results[i].ok;
-    return all_ok ? MVS_OK : MVS_NO_MODEL;
-}
-
-mvs_status mvs_pose_graph_optimize(mvs_ctx *ctx, const mvs_pose_graph *graph, const mvs_pose_graph_params *params,
-                                   mvs_pose_graph_result *result, double *poses_out)
-{
-    return mvs_pose_graph_optimize_batch(ctx, graph, 1, params, result, poses_out);
-}
-
-// ---- the pose graph of a resident sequence (seq_graph.hip) -------------------------------------
-// The graph's block: S candidate slots, room for `cap` >= S edges (the loop edges of mvs_seq_add_loop_edges sit behind the
-// built ones), F nodes.  The count, src and dst first and in this order: mvs_seq_optimize_pose_graph downloads that prefix.
-struct SeqGraphLayout {
-    size_t S, cap, o_n, o_built, o_src, o_dst, o_lag, o_kind, o_scale, o_z, o_cov, o_node, o_opt, o_keep, o_skind, o_sscale, o_sz, o_scov, total;
-    SeqGraphLayout(size_t S_, size_t cap_, size_t F) : S(S_), cap(cap_)
-    {
-        Carve L{64};
-        o_n = L.take(4), o_src = L.take(cap * 4), o_dst = L.take(cap * 4), o_lag = L.take(cap * 4), o_kind = L.take(cap * 4);
-        o_scale = L.take(cap * 8), o_z = L.take(cap * 12 * 8), o_cov = L.take(cap * 36 * 8), o_node = L.take(F * 12 * 8);
-        o_opt = L.take(F * 12 * 8), o_keep = L.take(S * 4), o_skind = L.take(S * 4), o_sscale = L.take(S * 8);
-        o_sz = L.take(S * 12 * 8), o_scov = L.take(S * 36 * 8);
-        o_built = L.take(4);   // edges of the built graph, behind which the loop edges go (mvs_seq_add_loop_edges)
-        total = L.total();
-    }
-    // points g's arrays into the block at `base`; returns the optimised nodes' place
-    double *point(SeqGraphDev &g, char *base) const
-    {
-        auto dp = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
-        auto ip = [&](size_t o) { return reinterpret_cast<int32_t *>(base + o); };
-        g.slot_keep = ip(o_keep), g.slot_kind = ip(o_skind), g.slot_scale = dp(o_sscale), g.slot_pose = dp(o_sz), g.slot_cov = dp(o_scov);
-        g.n_edges = ip(o_n), g.edge_src = ip(o_src), g.edge_dst = ip(o_dst), g.edge_lag = ip(o_lag), g.edge_kind = ip(o_kind);
-        g.edge_scale = dp(o_scale), g.edge_pose = dp(o_z), g.edge_cov = dp(o_cov), g.node_pose = dp(o_node);
-        return dp(o_opt);
-    }
-};
-
-mvs_status mvs_seq_build_pose_graph(mvs_seq *q, const mvs_seq_graph_params *p)
-{
-    if (!q || !p || p->max_lag < 1 || p->max_lag >= q->n_frames || p->min_points < 0 || !(p->max_error >= 0.0) ||
-        p->chain_sigma[0] != p->chain_sigma[0] || p->chain_sigma[1] != p->chain_sigma[1])
-        return MVS_ERR_INVALID_ARG;
-    const int64_t slots64 = (int64_t)p->max_lag * q->n_frames - (int64_t)p->max_lag * (p->max_lag + 1) / 2;
-    if (q->n_frames > kPgMaxNodes || slots64 > kPgMaxEdges)
-        return MVS_ERR_CAPACITY;
-    if (!q->ran || p->max_lag > q->lags_ran)
-        return MVS_ERR_INVALID_ARG;
-    mvs_ctx *ctx = q->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    q->graph_built = q->graph_opt = false;
-    const size_t S = (size_t)slots64;
-    // room behind the slots for the loop edges of the current selection (mvs_seq_add_loop_edges grows the block otherwise)
-    const size_t want = S + (q->loop_selected ? (size_t)q->ld.max_candidates : 0);
-    const SeqGraphLayout L(S, want > (size_t)kPgMaxEdges ? S : want, (size_t)q->n_frames);
-    const mvs_status st = ws_grow(ctx, q->graph, L.total);
-    if (st != MVS_OK)
-        return st;
-    SeqGraphDev g{};
-    g.n_frames = q->n_frames, g.max_lag = p->max_lag, g.n_slots = (int)S;
-    g.min_points = p->min_points;
-    g.max_error = p->max_error;
-    g.chain_on = p->chain_sigma[0] > 0.0 && p->chain_sigma[1] > 0.0;
-    g.chain_var[0] = p->chain_sigma[0] * p->chain_sigma[0];
-    g.chain_var[1] = p->chain_sigma[1] * p->chain_sigma[1];
-    g.lags = q->lagws.ptr<LagDev>();
-    g.traj_R = q->chain.traj_R, g.traj_t = q->chain.traj_t;
-    q->graph_opt_pose = L.point(g, q->graph.ptr());
-    q->graph_n_built = reinterpret_cast<int32_t *>(q->graph.ptr() + L.o_built);
-    q->graph_edge_cap = (int)L.cap;
-    q->loop_edges_added = false;
-    launch_seq_graph(g, ctx_stream(ctx));
-    HIP_TRY(ctx, hipGetLastError());
-    q->gd = g;
-    q->graph_built = true;
-    return MVS_OK;
-}
-
-mvs_status mvs_seq_optimize_pose_graph(mvs_seq *q, const mvs_pose_graph_params *params, mvs_pose_graph_result *result)
-{
-    if (!q || !q->graph_built || !result || !pose_graph_params_ok(params))
-        return MVS_ERR_INVALID_ARG;
-    mvs_ctx *ctx = q->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const SeqGraphDev &g = q->gd;
-    hipStream_t s = ctx_stream(ctx);
-    q->graph_opt = false;
-    *result = mvs_pose_graph_result{};
-    // the count and the edges' endpoints: all the host needs of the graph
-    const char *gbase = q->graph.ptr();
-    const size_t o_src = (const char *)g.edge_src - gbase, o_dst = (const char *)g.edge_dst - gbase;
-    std::vector<char> head(o_dst + (size_t)q->graph_edge_cap * 4);
-    HIP_TRY(ctx, hipMemcpyAsync(head.data(), gbase, head.size(), hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, sync_stream(ctx));
-    int32_t E = 0;
-    std::memcpy(&E, head.data(), 4);
-    const int32_t *h_src = reinterpret_cast<const int32_t *>(head.data() + o_src);
-    const int32_t *h_dst = reinterpret_cast<const int32_t *>(head.data() + o_dst);
-    const int N = g.n_frames;
-    if (E < 0 || E > q->graph_edge_cap) {
-        ctx->err = "mvs_seq_optimize_pose_graph: edge count out of range";
-        return MVS_ERR_HIP;
-    }
-    mvs_pose_graph hg{};
-    hg.n_nodes = N, hg.n_edges = E, hg.edge_src = h_src, hg.edge_dst = h_dst, hg.anchor_node = 0;
-    if (!pose_graph_connected(hg))
-        return MVS_NO_MODEL;
-    if (N <= kPgDenseMaxNodes) {
-        PgProblem pr{};
-        pr.n_nodes = N, pr.n_edges = E, pr.anchor = 0;
-        const PgDenseLayout L(1, (size_t)N, (size_t)E);
-        const size_t o_desc = L.total;
-        mvs_status st = ws_grow(ctx, ctx->pg, o_desc + sizeof(PgProblem));
-        if (st != MVS_OK)
-            return st;
-        char *base = ctx->pg.ptr();
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_desc, &pr, sizeof(pr), hipMemcpyHostToDevice, s));
-        st = pose_graph_dense_dev(ctx, base, L, 1, *params, reinterpret_cast<const PgProblem *>(base + o_desc), g.node_pose,
-                                  g.edge_src, g.edge_dst, g.edge_pose, g.edge_cov);
-        if (st != MVS_OK)
-            return st;
-        HIP_TRY(ctx, hipMemcpyAsync(result, base + L.o_out, sizeof(*result), hipMemcpyDeviceToHost, s));
-        HIP_TRY(ctx, sync_stream(ctx));   // `pr` lives on this frame
-        if (result->ok)
-            HIP_TRY(ctx, hipMemcpyAsync(q->graph_opt_pose, base + L.o_po, (size_t)N * 96, hipMemcpyDeviceToDevice, s));
-    } else {
-        mvs_status st = ws_grow(ctx, ctx->pg, PgLargeLayout((size_t)N, (size_t)E).total);
-        if (st != MVS_OK)
-            return st;
-        st = pose_graph_large_dev(ctx, ctx->pg.ptr(), N, E, 0, h_src, h_dst, g.edge_src, g.edge_dst, g.node_pose, g.edge_pose,
-                                  g.edge_cov, *params, result, q->graph_opt_pose, hipMemcpyDeviceToDevice);
-        if (st != MVS_OK)
-            return st;
-    }
-    q->graph_opt = result->ok != 0;
-    return result->ok ? MVS_OK : MVS_NO_MODEL;
-}
-
-mvs_status mvs_seq_download_pose_graph(mvs_seq *q, int32_t *n_edges, double *node_pose, int32_t *edge_src, int32_t *edge_dst,
-                                       double *edge_pose, double *edge_cov, int32_t *edge_lag, int32_t *edge_kind,
-                                       double *edge_scale)
-{
-    if (!q || !q->graph_built || !n_edges)
-        return MVS_ERR_INVALID_ARG;
-    mvs_ctx *ctx = q->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const SeqGraphDev &g = q->gd;
-    hipStream_t s = ctx_stream(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(n_edges, g.n_edges, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, sync_stream(ctx));
-    const size_t E = (size_t)std::min(std::max(*n_edges, 0), q->graph_edge_cap);
-    const struct {
-        void *dst;
-        const void *src;
-        size_t bytes;
-    } parts[] = {{node_pose, g.node_pose, (size_t)g.n_frames * 96}, {edge_src, g.edge_src, E * 4}, {edge_dst, g.edge_dst, E * 4},
-                 {edge_pose, g.edge_pose, E * 96}, {edge_cov, g.edge_cov, E * 288}, {edge_lag, g.edge_lag, E * 4},
-                 {edge_kind, g.edge_kind, E * 4}, {edge_scale, g.edge_scale, E * 8}};
-    for (const auto &pt : parts)
-        if (pt.dst && pt.bytes)
-            HIP_TRY(ctx, hipMemcpyAsync(pt.dst, pt.src, pt.bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, sync_stream(ctx));
-    return MVS_OK;
-}
-
-mvs_status mvs_seq_download_pose_graph_poses(mvs_seq *q, double *poses)
-{
-    if (!q || !poses || !q->graph_built || !q->graph_opt)
-        return MVS_ERR_INVALID_ARG;
-    mvs_ctx *ctx = q->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpyAsync(poses, q->graph_opt_pose, (size_t)q->n_frames * 96, hipMemcpyDeviceToHost, ctx_stream(ctx)));
-    HIP_TRY(ctx, sync_stream(ctx));
-    return MVS_OK;
-}
-
-// ---- marginal covariances of a pose graph (pg_marginals.hip, pg_envelope.hpp) -------------------
-// what the host decides before anything is launched: the query list, the envelope, the per-block term lists, the chunk
-struct PgmPlan {
-    std::vector<int32_t> first, row_off, qi, qj;
-    mvs_pgm::BlockLists lists;
-    int64_t blocks = 0;
-    int chunk = 1;
-};
-
-static mvs_status pgm_plan(int N, int E, int anchor, const int32_t *src, const int32_t *dst, int n_query, const int32_t *qi,
-                           const int32_t *qj, PgmPlan &P)
-{
-    if (!mvs_pgm::expand_queries(N, n_query, qi, qj, P.qi, P.qj))
-        return MVS_ERR_INVALID_ARG;
-    P.blocks = mvs_pgm::envelope(N, E, src, dst, P.first, P.row_off);
-    if (P.blocks > mvs_pgm::kMaxEnvelopeBlocks)
-        return MVS_ERR_CAPACITY;
-    P.lists = mvs_pgm::block_lists(E, anchor, src, dst, P.first, P.row_off);
-    P.chunk = std::min(mvs_pgm::query_chunk(N), (int)P.qi.size());
-    return MVS_OK;
-}
-
-// the solver's scratch, as offsets from one base in ctx->pgm
-struct PgmLayout {
-    size_t o_state, o_first, o_row, o_sblk, o_soff, o_codes, o_qi, o_qj, o_Ha, o_out, o_lin, o_sky, o_y, total;
-    PgmLayout(size_t N, size_t E, const PgmPlan &P)
-    {
-        Carve L{64};
-        o_state = L.take(sizeof(PgmState));
-        o_first = L.take(N * 4), o_row = L.take((N + 1) * 4);
-        o_sblk = L.take(P.lists.slot_blk.size() * 4), o_soff = L.take(P.lists.slot_off.size() * 4);
-        o_codes = L.take(P.lists.codes.size() * 4);
-        o_qi = L.take(P.qi.size() * 4), o_qj = L.take(P.qj.size() * 4);
-        o_Ha = L.take(36 * 8), o_out = L.take((size_t)P.chunk * 36 * 8);
-        o_lin = L.take(E * kPgLin * 8), o_sky = L.take((size_t)P.blocks * 36 * 8);
-        o_y = L.take((size_t)P.chunk * N * 6 * mvs_pgm::kYCols * 8);
-        total = L.total();
-    }
-};
-
-// assembly, factorisation and the solves over a device-resident graph; `base`: scratch of PgmLayout::total bytes.  d_node
-// holds the anchor's mean, d_X the linearisation point.  cov_out is written only behind a factorisation that succeeded.
-static mvs_status pgm_run(mvs_ctx *ctx, char *base, const PgmLayout &L, const PgmPlan &P, int N, int E, int anchor,
-                          const int32_t *d_src, const int32_t *d_dst, const double *d_node, const double *d_X, const double *d_z,
-                          const double *d_cov, const double anchor_sigma[2], double *cov_out, mvs_pose_graph_marginals_info *info)
-{
-    hipStream_t s = ctx_stream(ctx);
-    const PgmState st0{0, -1, HUGE_VAL};
-    auto up = [&](size_t o, const void *src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-    };
-    HIP_TRY(ctx, up(L.o_state, &st0, sizeof(st0)));
-    HIP_TRY(ctx, up(L.o_first, P.first.data(), P.first.size() * 4));
-    HIP_TRY(ctx, up(L.o_row, P.row_off.data(), P.row_off.size() * 4));
-    HIP_TRY(ctx, up(L.o_sblk, P.lists.slot_blk.data(), P.lists.slot_blk.size() * 4));
-    HIP_TRY(ctx, up(L.o_soff, P.lists.slot_off.data(), P.lists.slot_off.size() * 4));
-    HIP_TRY(ctx, up(L.o_codes, P.lists.codes.data(), P.lists.codes.size() * 4));
-    HIP_TRY(ctx, up(L.o_qi, P.qi.data(), P.qi.size() * 4));
-    HIP_TRY(ctx, up(L.o_qj, P.qj.data(), P.qj.size() * 4));
-    HIP_TRY(ctx, hipMemsetAsync(base + L.o_sky, 0, (size_t)P.blocks * 36 * 8, s));
-    auto dp = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
-    auto ip = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o); };
-    PgmDev d{};
-    d.n_nodes = N, d.n_edges = E, d.anchor = anchor, d.n_slots = (int)P.lists.slot_blk.size();
-    d.w_anchor[0] = 1.0 / (anchor_sigma[0] * anchor_sigma[0]);
-    d.w_anchor[1] = 1.0 / (anchor_sigma[1] * anchor_sigma[1]);
-    d.edge_src = d_src, d.edge_dst = d_dst, d.edge_pose = d_z, d.edge_cov = d_cov, d.pose0 = d_node, d.X = d_X;
-    d.first = ip(L.o_first), d.row_off = ip(L.o_row), d.slot_blk = ip(L.o_sblk), d.slot_off = ip(L.o_soff), d.codes = ip(L.o_codes);
-    d.lin = dp(L.o_lin), d.Ha = dp(L.o_Ha), d.sky = dp(L.o_sky), d.y = dp(L.o_y), d.out = dp(L.o_out);
-    d.state = reinterpret_cast<PgmState *>(base + L.o_state);
-    launch_pgm_assemble(d, s);
-    launch_pgm_factor(d, s);
-    HIP_TRY(ctx, hipGetLastError());
-    PgmState h{};
-    HIP_TRY(ctx, hipMemcpyAsync(&h, d.state, sizeof(h), hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, sync_stream(ctx));   // the plan's vectors and st0 have been read by here, too
-    info->bad_node = h.bad_node;
-    info->min_pivot = h.status == 1 ? 0.0 : std::sqrt(h.min_d);
-    if (h.status)
-        return MVS_NO_MODEL;
-    const int nq = (int)P.qi.size();
-    for (int off = 0; off < nq; off += P.chunk) {
-        const int n = std::min(P.chunk, nq - off);
-        d.qi = ip(L.o_qi) + off, d.qj = ip(L.o_qj) + off;
-        launch_pgm_solve(d, n, s);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(cov_out + (size_t)off * 36, d.out, (size_t)n * 36 * 8, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(ctx, sync_stream(ctx));
-    info->ok = 1;
-    return MVS_OK;
-}
-
-static bool pgm_args_ok(const double anchor_sigma[2], int n_query, const double *cov_out, const mvs_pose_graph_marginals_info *info)
-{
-    return anchor_sigma && anchor_sigma[0] > 0.0 && anchor_sigma[1] > 0.0 && n_query >= 0 && cov_out && info;
-}
-
-mvs_status mvs_pose_graph_marginals(mvs_ctx *ctx, const mvs_pose_graph *graph, const double *poses, const double anchor_sigma[2],
-                                    int n_query, const int32_t *query_i, const int32_t *query_j, double *cov_out,
-                                    mvs_pose_graph_marginals_info *info)
-{
-    if (!ctx || !graph || !pgm_args_ok(anchor_sigma, n_query, cov_out, info))
-        return MVS_ERR_INVALID_ARG;
-    const mvs_pose_graph &g = *graph;
-    mvs_status st = pose_graph_check(g);
-    if (st != MVS_OK)
-        return st;
-    const size_t N = (size_t)g.n_nodes, E = (size_t)g.n_edges;
-    if (poses && !all_finite(poses, 12 * N))
-        return MVS_ERR_INVALID_ARG;
-    *info = mvs_pose_graph_marginals_info{0, 0, -1, 0, 0.0};
-    PgmPlan P;
-    st = pgm_plan(g.n_nodes, g.n_edges, g.anchor_node, g.edge_src, g.edge_dst, n_query, query_i, query_j, P);
-    if (st != MVS_OK)
-        return st;
-    info->envelope_blocks = (int32_t)P.blocks;
-    if (!pose_graph_connected(g))
-        return MVS_NO_MODEL;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    Carve U{64};
-    const size_t o_src = U.take(E * 4), o_dst = U.take(E * 4), o_z = U.take(E * 12 * 8), o_cov = U.take(E * 36 * 8);
-    const size_t o_p0 = U.take(N * 12 * 8), o_x = U.take(N * 12 * 8), o_solver = U.total();
-    const PgmLayout L(N, E, P);
-    st = ws_grow(ctx, ctx->pgm, o_solver + L.total);
-    if (st != MVS_OK)
-        return st;
-    char *base = ctx->pgm.ptr();
-    hipStream_t s = ctx_stream(ctx);
-    if (E) {
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_src, g.edge_src, E * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_dst, g.edge_dst, E * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_z, g.edge_pose, E * 12 * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_cov, g.edge_cov, E * 36 * 8, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_p0, g.node_pose, N * 12 * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_x, poses ? poses : g.node_pose, N * 12 * 8, hipMemcpyHostToDevice, s));
-    auto dp = [&](size_t o) { return reinterpret_cast<const double *>(base + o); };
-    auto ip = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o); };
-    return pgm_run(ctx, base + o_solver, L, P, g.n_nodes, g.n_edges, g.anchor_node, ip(o_src), ip(o_dst), dp(o_p0), dp(o_x),
-                   dp(o_z), dp(o_cov), anchor_sigma, cov_out, info);
-}
-
-mvs_status mvs_seq_pose_graph_marginals(mvs_seq *q, const double anchor_sigma[2], int n_query, const int32_t *query_i,
-                                        const int32_t *query_j, double *cov_out, mvs_pose_graph_marginals_info *info)
-{
-    if (!q || !q->graph_built || !q->graph_opt || !pgm_args_ok(anchor_sigma, n_query, cov_out, info))
-        return MVS_ERR_INVALID_ARG;
-    mvs_ctx *ctx = q->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const SeqGraphDev &g = q->gd;
-    hipStream_t s = ctx_stream(ctx);
-    // the count and the edges' endpoints: all the host needs of the graph
-    const char *gbase = q->graph.ptr();
-    const size_t o_src = (const char *)g.edge_src - gbase, o_dst = (const char *)g.edge_dst - gbase;
-    std::vector<char> head(o_dst + (size_t)q->graph_edge_cap * 4);
-    HIP_TRY(ctx, hipMemcpyAsync(head.data(), gbase, head.size(), hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, sync_stream(ctx));
-    int32_t E = 0;
-    std::memcpy(&E, head.data(), 4);
-    const int32_t *h_src = reinterpret_cast<const int32_t *>(head.data() + o_src);
-    const int32_t *h_dst = reinterpret_cast<const int32_t *>(head.data() + o_dst);
-    const int N = g.n_frames;
-    bool edges_ok = E >= 0 && E <= q->graph_edge_cap;
-    for (int k = 0; edges_ok && k < E; ++k)
-        edges_ok = h_src[k] >= 0 && h_src[k] < N && h_dst[k] >= 0 && h_dst[k] < N && h_src[k] != h_dst[k];
-    if (!edges_ok) {
-        ctx->err = "mvs_seq_pose_graph_marginals: the resident graph's edges are out of range";
-        return MVS_ERR_HIP;
-    }
-    *info = mvs_pose_graph_marginals_info{0, 0, -1, 0, 0.0};
-    PgmPlan P;
-    mvs_status st = pgm_plan(N, E, 0, h_src, h_dst, n_query, query_i, query_j, P);
-    if (st != MVS_OK)
-        return st;
-    info->envelope_blocks = (int32_t)P.blocks;
-    mvs_pose_graph hg{};
-    hg.n_nodes = N, hg.n_edges = E, hg.edge_src = h_src, hg.edge_dst = h_dst, hg.anchor_node = 0;
-    if (!pose_graph_connected(hg))
-        return MVS_NO_MODEL;
-    const PgmLayout L((size_t)N, (size_t)E, P);
-    st = ws_grow(ctx, ctx->pgm, L.total);
-    if (st != MVS_OK)
-        return st;
-    return pgm_run(ctx, ctx->pgm.ptr(), L, P, N, E, 0, g.edge_src, g.edge_dst, g.node_pose, q->graph_opt_pose, g.edge_pose,
-                   g.edge_cov, anchor_sigma, cov_out, info);
-}
-
-// ---- loop closures of a resident sequence (loop.hip, seq_graph.hip) -----------------------------
-mvs_status mvs_seq_loop_scores(mvs_seq *q, double ratio, double max_dist, int min_gap)
-{
-    if (!q)
-        return MVS_ERR_INVALID_ARG;
-    if (q->n_frames > kLoopMaxFrames)
-        return MVS_ERR_CAPACITY;
-    if (min_gap < 1 || min_gap >= q->n_frames || ratio != ratio || max_dist != max_dist)
-        return MVS_ERR_INVALID_ARG;
-    mvs_ctx *ctx = q->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    q->loop_scored = q->loop_selected = q->loop_verified = false;
-    const size_t F = (size_t)q->n_frames;
-    const mvs_status st = ws_grow(ctx, q->loop_score, F * F * sizeof(int32_t));
-    if (st != MVS_OK)
-        return st;
-    const BatchDev &d = q->batch->d;
-    LoopDev &l = q->ld;
-    l.n_frames = q->n_frames, l.max_kp = d.max_kp, l.desc_words = d.desc_words;
-    l.desc = d.desc1, l.kp = d.kp1, l.oct = d.oct1, l.n_kp = d.n1, l.K = d.K, l.Kinv = d.Kinv;
-    l.score = q->loop_score.ptr<int32_t>();
-    HIP_TRY(ctx, launch_loop_scores(l, ratio, max_dist, min_gap, ctx_stream(ctx)));
-    HIP_TRY(ctx, hipGetLastError());
-    q->loop_scored = true;
-    return MVS_OK;
-}
-
-mvs_status mvs_seq_download_loop_scores(mvs_seq *q, int32_t *scores)
-{
-    if (!q || !scores || !q->loop_scored)
-        return MVS_ERR_INVALID_ARG;
-    mvs_ctx *ctx = q->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t F = (size_t)q->n_frames;
-    HIP_TRY(ctx, hipMemcpyAsync(scores, q->ld.score, F * F * sizeof(int32_t), hipMemcpyDeviceToHost, ctx_stream(ctx)));
-    HIP_TRY(ctx, sync_stream(ctx));
-    return MVS_OK;
-}
-
-mvs_status mvs_seq_select_loops(mvs_seq *q, const mvs_loop_select_params *p)
-{
-    if (!q || !p || !q->loop_scored || p->min_score < 1 || p->top_k < 1 || p->max_candidates < 1)
-        return MVS_ERR_INVALID_ARG;
-    mvs_ctx *ctx = q->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    q->loop_selected = q->loop_verified = false;
-    const size_t F = (size_t)q->n_frames, C = (size_t)p->max_candidates;
-    const size_t top_k = (size_t)std::min(p->top_k, q->n_frames);   // a frame has fewer than n_frames base frames
-    Carve L{64};
-    const size_t o_counts = L.take(2 * 4), o_rown = L.take(F * 4), o_rowkey = L.take(F * top_k * 4);
-    const size_t o_cand = L.take(C * sizeof(mvs_loop_candidate));
-    const mvs_status st = ws_grow(ctx, q->loop_sel, L.total());
-    if (st != MVS_OK)
-        return st;
-    char *base = q->loop_sel.ptr();
-    LoopDev &l = q->ld;
-    l.min_score = p->min_score, l.top_k = (int)top_k, l.max_candidates = p->max_candidates;
-    l.counts = reinterpret_cast<int32_t *>(base + o_counts);
-    l.row_n = reinterpret_cast<int32_t *>(base + o_rown);
-    l.row_key = reinterpret_cast<int32_t *>(base + o_rowkey);
-    l.cand = reinterpret_cast<mvs_loop_candidate *>(base + o_cand);
-    launch_loop_select(l, ctx_stream(ctx));
-    HIP_TRY(ctx, hipGetLastError());
-    q->loop_selected = true;
-    return MVS_OK;
-}
-
-mvs_status mvs_seq_verify_loops(mvs_seq *q, const mvs_params *two_view, int essential, const mvs_refine_params *rp,
-                                double sigma_px)
-{
-    if (!q || !q->loop_selected || !refine_params_ok(rp) || !(sigma_px > 0.0))
-        return MVS_ERR_INVALID_ARG;
-    mvs_status st = check_params(two_view);
-    if (st != MVS_OK)
-        return st;
-    mvs_ctx *ctx = q->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    q->loop_verified = false;
-    const LoopDev &l = q->ld;
-    if (q->loop_batch && q->loop_batch->d.n_pairs != l.max_candidates) {
-        mvs_batch_destroy(q->loop_batch);
-        q->loop_batch = nullptr;
-    }
-    if (!q->loop_batch &&
-        (st = batch_create_impl(ctx, l.max_candidates, l.max_kp, l.desc_words * 4, 0, &q->loop_batch)) != MVS_OK)
-        return st;
-    mvs_batch *b = q->loop_batch;
-    const Estimator est = essential ? Estimator::kFivePoint : Estimator::kEightPoint;
-    if ((st = ensure_tables(b, est, two_view->num_hypotheses)) != MVS_OK)
-        return st;
-    hipStream_t s = ctx_stream(ctx);
-    // the one host read between selection and verification: how many pairs the pipeline runs on
-    int32_t counts[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(counts, l.counts, sizeof(counts), hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, sync_stream(ctx));
-    const int kept = counts[0];
-    if (kept < 0 || kept > l.max_candidates) {
-        ctx->err = "mvs_seq_verify_loops: candidate count out of range";
-        return MVS_ERR_HIP;
-    }
-    // pairs past the kept ones are no candidates: their records read "invalid", so the refinement skips them
-    HIP_TRY(ctx, hipMemsetAsync(b->d.results + kept, 0, (size_t)(l.max_candidates - kept) * sizeof(mvs_pair_result), s));
-    if (kept > 0) {
-        launch_loop_gather(l, b->d, s);
-        HIP_TRY(ctx, hipGetLastError());
-        const RunParams run = to_run(*two_view);
-        if ((st = est == Estimator::kEightPoint ? enqueue_pipeline(b, run, kept, false, nullptr) : enqueue_essential(b, run, kept)) != MVS_OK)
-            return st;
-    }
-    if ((st = mvs_batch_refine(b, rp, sigma_px)) != MVS_OK)
-        return st;
-    q->loop_kept = kept;
-    q->loop_verified = true;
-    return MVS_OK;
-}
-
-mvs_status mvs_seq_add_loop_edges(mvs_seq *q, const mvs_loop_edge_params *p)
-{
-    if (!q || !p)
-        return MVS_ERR_INVALID_ARG;
-    if (q->graph_built && q->loop_selected && (int64_t)q->gd.n_slots + q->ld.max_candidates > kPgMaxEdges)
-        return MVS_ERR_CAPACITY;
-    if (p->min_points < 0 || !(p->max_error >= 0.0) || p->loop_sigma[0] != p->loop_sigma[0] || p->loop_sigma[1] != p->loop_sigma[1] ||
-        !q->graph_built || !q->loop_verified)
-        return MVS_ERR_INVALID_ARG;
-    mvs_ctx *ctx = q->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx_stream(ctx);
-    const int need = q->gd.n_slots + q->ld.max_candidates;
-    if (q->graph_edge_cap < need) {
-        // the block was carved before this selection: a larger one, the graph's arrays copied over (the slots are scratch)
-        const size_t F = (size_t)q->n_frames, C = (size_t)q->graph_edge_cap;
-        const SeqGraphLayout Ln((size_t)q->gd.n_slots, (size_t)need, F);
-        void *np = nullptr;
-        HIP_TRY(ctx, hipMalloc(&np, Ln.total));
-        DevPtr fresh(np);
-        SeqGraphDev g = q->gd;
-        double *opt = Ln.point(g, static_cast<char *>(np));
-        int32_t *n_built = reinterpret_cast<int32_t *>(static_cast<char *>(np) + Ln.o_built);
-        const SeqGraphDev &o = q->gd;
-        const struct {
-            void *dst;
-            const void *src;
-            size_t bytes;
-        } parts[] = {{g.n_edges, o.n_edges, 4}, {g.edge_src, o.edge_src, C * 4}, {g.edge_dst, o.edge_dst, C * 4},
-                     {g.edge_lag, o.edge_lag, C * 4}, {g.edge_kind, o.edge_kind, C * 4}, {g.edge_scale, o.edge_scale, C * 8},
-                     {g.edge_pose, o.edge_pose, C * 96}, {g.edge_cov, o.edge_cov, C * 288}, {g.node_pose, o.node_pose, F * 96},
-                     {opt, q->graph_opt_pose, F * 96}, {n_built, q->graph_n_built, 4}};
-        for (const auto &pt : parts)
-            HIP_TRY(ctx, hipMemcpyAsync(pt.dst, pt.src, pt.bytes, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(ctx, sync_stream(ctx));   // the old block is freed
-        q->graph.p = std::move(fresh);
-        q->graph.bytes = Ln.total;
-        q->gd = g;
-        q->graph_opt_pose = opt;
-        q->graph_n_built = n_built;
-        q->graph_edge_cap = need;
-    }
-    if (!q->loop_edges_added)   // the first call behind a build: remember where the built edges end
-        HIP_TRY(ctx, hipMemcpyAsync(q->graph_n_built, q->gd.n_edges, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    LoopEdgeDev e{};
-    e.cand = q->ld.cand, e.counts = q->ld.counts;
-    e.results = q->loop_batch->d.results, e.refined = q->loop_batch->refine.out;
-    e.n_built = q->graph_n_built;
-    e.max_candidates = q->ld.max_candidates, e.min_points = p->min_points;
-    e.max_error = p->max_error;
-    for (int k = 0; k < 2; ++k) {
-        e.add[k] = p->loop_sigma[k] > 0.0;
-        e.var[k] = p->loop_sigma[k] * p->loop_sigma[k];
-    }
-    launch_loop_edges(q->gd, e, s);
-    HIP_TRY(ctx, hipGetLastError());
-    q->loop_edges_added = true;
-    q->graph_opt = false;
-    return MVS_OK;
-}
-
-mvs_status mvs_seq_download_loop_candidates(mvs_seq *q, int32_t *n_kept, int32_t *n_found, mvs_loop_candidate *cand,
-                                            mvs_pair_result *results, mvs_match *matches, uint8_t *inlier_mask,
-                                            double *points_xyz, int64_t *point_idx, mvs_refine_result *refined)
-{
-    if (!q || !q->loop_selected)
-        return MVS_ERR_INVALID_ARG;
-    const bool pairs = results || matches || inlier_mask || points_xyz || point_idx;
-    if ((pairs || refined) && !q->loop_verified)
-        return MVS_ERR_INVALID_ARG;
-    mvs_ctx *ctx = q->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx_stream(ctx);
-    int32_t counts[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(counts, q->ld.counts, sizeof(counts), hipMemcpyDeviceToHost, s));
-    if (cand)
-        HIP_TRY(ctx, hipMemcpyAsync(cand, q->ld.cand, (size_t)q->ld.max_candidates * sizeof(mvs_loop_candidate), hipMemcpyDeviceToHost, s));
-    if (refined && q->loop_kept > 0)
-        HIP_TRY(ctx, hipMemcpyAsync(refined, q->loop_batch->refine.out, (size_t)q->loop_kept * sizeof(mvs_refine_result),
-                                    hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, sync_stream(ctx));
-    if (n_kept)
-        *n_kept = counts[0];
-    if (n_found)
-        *n_found = counts[1];
-    if (pairs && q->loop_kept > 0)
-        return mvs_batch_download(q->loop_batch, 0, q->loop_kept, results, matches, inlier_mask, points_xyz, point_idx);
-    return MVS_OK;
 }
 }  // extern "C"

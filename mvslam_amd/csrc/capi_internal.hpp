@@ -1,6 +1,6 @@
-// capi_internal.hpp -- what the host files of libmvslam_hip.so (capi.hip, capi_orb.hip, capi_debug.hip) share: the owners of
-// device memory, the three opaque objects of include/mvslam_hip.h, HIP_TRY and the helpers that cross a file boundary.  A
-// helper that one file uses is static in that file and is not declared here.
+// capi_internal.hpp -- what the host files of libmvslam_hip.so (capi.hip, capi_orb.hip, capi_graph.hip, capi_debug.hip) share:
+// the owners of device memory, the three opaque objects of include/mvslam_hip.h, HIP_TRY and the helpers that cross a file
+// boundary.  A helper that one file uses is static in that file and is not declared here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -271,6 +271,13 @@ mvs_status ws_grow(mvs_ctx *ctx, DevWorkspace &w, size_t bytes, size_t floor = 0
 void drop_orb_graph(mvs_ctx *ctx);
 RunParams to_run(const mvs_params &p);
 mvs_status ensure_groups(mvs_batch *b, int num_hypotheses);
+enum class Estimator { kEightPoint, kFivePoint };   // the model stage of a pair pipeline: kernels.hip or essential5.hip
+mvs_status ensure_tables(mvs_batch *b, Estimator est, int num_hypotheses);
+mvs_status batch_create_impl(mvs_ctx *ctx, int n_pairs, int max_kp, int desc_bytes, int n_frames, mvs_batch **out,
+                             const BatchDev *frames_of = nullptr, int lag = 1);
+mvs_status check_params(const mvs_params *p);
+mvs_status run_pairs(mvs_batch *b, Estimator est, const RunParams &rp, int n);
+bool refine_params_ok(const mvs_refine_params *p);
 
 // capi_orb.hip
 mvs_status orb_run(mvs_ctx *ctx, const uint8_t *images, int n, int w, int h, const mvs_orb_params &prm, uint8_t *d_desc_ext,

@@ -336,6 +336,19 @@ def test_case11_finite_input_whose_cost_overflows():
         assert m.optimize(g)["ok"] == 0
 
 
+def test_host_logic_under_the_sanitizers(tmp_path):
+    """tests/cpp/pg_host_check.cpp over mvslam_amd/csrc/pg_host.hpp: N = 1 with no edges, a chain, two components, duplicate
+    edges in both orientations, the 4096-node hub, endpoints out of range, the CSR list against a brute-force one and
+    all_finite, with -fsanitize=address,undefined.  A program of its own: nothing of it is loaded into python."""
+    exe = str(tmp_path / "pg_host_check")
+    subprocess.check_call(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(ROOT, "mvslam_amd", "csrc"), "-o", exe,
+                           os.path.join(ROOT, "tests", "cpp", "pg_host_check.cpp")])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0 and r.stdout.strip() == "ok"
+
+
 REF = "/root/reference/source"
 
 
