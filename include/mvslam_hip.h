@@ -927,6 +927,46 @@ mvs_status mvs_pose_graph_optimize_batch(mvs_ctx *ctx, const mvs_pose_graph *gra
                                          const mvs_pose_graph_params *params, mvs_pose_graph_result *results,
                                          double *poses_out);
 
+/* ---- The linear solver of the large path -------------------------------------------------------
+ * A switch of the context, MVS_PG_SOLVER_PCG by default: with it every call returns the bytes it returned before the switch
+ * existed.  Any other value than the two below: MVS_ERR_INVALID_ARG, the setting stays.  With MVS_PG_SOLVER_DIRECT graphs of
+ * more than 16 nodes in mvs_pose_graph_optimize, mvs_pose_graph_optimize_batch and mvs_seq_optimize_pose_graph solve every
+ * LM step exactly; graphs of up to 16 nodes take the dense path and return the same bytes under either setting.  One step at
+ * the current poses X and damping lambda, with the optimiser's own residuals, Jacobians, whitening and anchor term:
+ *   1. A = H + lambda I as a block lower triangle inside its envelope (row i holds the blocks first[i] .. i, first[i] the
+ *      smallest of i and its neighbours, nodes in their natural order) and the gradient g; every block's terms are summed in
+ *      edge order, the anchor's last.
+ *   2. A_ii = C_i C_i^T (a 6 x 6 Cholesky);  A~_ij = C_i^-1 A_ij C_j^-T off the diagonal, A~_ii = I exactly, b~_i = -C_i^-1 g_i.
+ *   3. A~ = L L^T in the skyline; fill stays inside a row's envelope.
+ *   4. L y = b~, then L^T z = y with the rows in descending order: row i finishes z_i, then subtracts L(i, c)^T z_i from y_c
+ *      for every c of its envelope.
+ *   5. delta_i = C_i^-T z_i; retraction and candidate cost as under PCG.
+ * A pivot that is not finite and positive, in step 2 or 3, is a failed solve: the step is rejected, lambda is multiplied by
+ * lambda_factor and no stall test is made; the rest of the LM rule is unchanged.  The block scaling is what the PCG's
+ * block-Jacobi preconditioner does implicitly; without it H of a long monocular sequence is not positive definite in binary64.
+ * Binary64, explicit FMAs, fixed summation orders, no floating-point atomics: the same input gives the same bytes.  One host
+ * synchronisation and a constant number of launches per LM iteration.
+ * cg_rel_tol, cg_max_iterations and cg_chunk_iterations are ignored and cg_iterations is 0.  Argument, topology and covariance
+ * errors are those of the PCG path, with the same status codes and the same "poses_out untouched, result zero".  One more
+ * refusal: an envelope of more than 2^21 blocks (the limit of mvs_pose_graph_marginals) is MVS_ERR_CAPACITY, reported for a
+ * graph of more than 16 nodes before anything is launched.  There is no fill-reducing ordering: a 4096-node hub (8.4 million
+ * blocks) optimises under PCG and is refused under DIRECT. */
+#define MVS_PG_SOLVER_PCG 0
+#define MVS_PG_SOLVER_DIRECT 1
+mvs_status mvs_ctx_set_pose_graph_solver(mvs_ctx *ctx, int solver);
+/* What the direct solver met in the context's last graph that went through it (MVS_ERR_INVALID_ARG before there is one). */
+typedef struct mvs_pose_graph_direct_info {
+    int32_t envelope_blocks;   /* sum_i (i - first[i] + 1) */
+    int32_t widest_row;        /* max_i (i - first[i] + 1) */
+    int32_t failed_solves;     /* LM iterations whose solve failed on a pivot */
+    int32_t bad_node;          /* the node of the first such pivot, -1 if there was none */
+    double min_pivot;          /* the smallest diagonal entry of L over the call's completed factorisations of the scaled
+                                  matrix (1 = a node nothing couples), 0 if none completed */
+    double failed_pivot;       /* the first failed pivot of the skyline, before its square root (<= 0 or not finite); 0 if
+                                  there was none or a diagonal block of H + lambda I failed */
+} mvs_pose_graph_direct_info;
+mvs_status mvs_ctx_pose_graph_direct_info(mvs_ctx *ctx, mvs_pose_graph_direct_info *info);
+
 /* ---- The pose graph of a resident sequence: what feeds the back end ---------------------------
  * Built on the device from what the sequence calls left resident, optimised there, no pose or covariance on the host in
  * between.

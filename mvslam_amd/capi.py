@@ -163,6 +163,9 @@ POSE_GRAPH_DENSE_MAX_NODES, POSE_GRAPH_MAX_NODES, POSE_GRAPH_MAX_EDGES = 16, 409
 POSE_GRAPH_MARGINALS_INFO_DTYPE = np.dtype([("ok", "<i4"), ("envelope_blocks", "<i4"), ("bad_node", "<i4"), ("reserved", "<i4"),
                                             ("min_pivot", "<f8")])
 POSE_GRAPH_MAX_ENVELOPE_BLOCKS = 1 << 21
+MVS_PG_SOLVER_PCG, MVS_PG_SOLVER_DIRECT = 0, 1
+POSE_GRAPH_DIRECT_INFO_DTYPE = np.dtype([("envelope_blocks", "<i4"), ("widest_row", "<i4"), ("failed_solves", "<i4"),
+                                         ("bad_node", "<i4"), ("min_pivot", "<f8"), ("failed_pivot", "<f8")])
 
 
 def _marginals_args(n_nodes, queries, anchor_sigma, cov_out):
@@ -260,6 +263,7 @@ EXPORTS = [
     "mvs_seq_download_pose_graph_poses", "mvs_seq_loop_scores", "mvs_seq_download_loop_scores", "mvs_seq_select_loops",
     "mvs_seq_verify_loops", "mvs_seq_add_loop_edges", "mvs_seq_download_loop_candidates",
     "mvs_pose_graph_marginals", "mvs_seq_pose_graph_marginals",
+    "mvs_ctx_set_pose_graph_solver", "mvs_ctx_pose_graph_direct_info",
 ]
 
 
@@ -312,6 +316,10 @@ def lib():
         _lib.mvs_ctx_set_essential_confidence.restype = C.c_int
         _lib.mvs_ctx_set_essential_confidence.argtypes = [C.c_void_p, C.c_double]
         _lib.mvs_ctx_essential_hypotheses_run.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        _lib.mvs_ctx_set_pose_graph_solver.restype = C.c_int
+        _lib.mvs_ctx_set_pose_graph_solver.argtypes = [C.c_void_p, C.c_int]
+        _lib.mvs_ctx_pose_graph_direct_info.restype = C.c_int
+        _lib.mvs_ctx_pose_graph_direct_info.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mvs_batch_download_hypotheses_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]
         _lib.mvs_seq_download_hypotheses_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]
         _lib.mvs_batch_download_essential_tables.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
@@ -465,6 +473,19 @@ class Context:
         """Confidence level of the five-point RANSAC: 0 (default) runs every hypothesis, 0 < p < 1 stops each pair at the first
         checkpoint (64, 128, ...) at which its best count reaches that confidence (mvs_ctx_set_essential_confidence)."""
         self._check(lib().mvs_ctx_set_essential_confidence(self._h, C.c_double(p)), "mvs_ctx_set_essential_confidence")
+
+    def set_pose_graph_solver(self, solver):
+        """The linear solver of pose graphs of more than 16 nodes: MVS_PG_SOLVER_PCG (default) or MVS_PG_SOLVER_DIRECT, the
+        block-scaled skyline Cholesky (mvs_ctx_set_pose_graph_solver).  Anything else raises MvsError (MVS_ERR_INVALID_ARG)."""
+        self._check(lib().mvs_ctx_set_pose_graph_solver(self._h, C.c_int(solver)), "mvs_ctx_set_pose_graph_solver")
+
+    def pose_graph_direct_info(self):
+        """what the direct solver met in the last graph that went through it (mvs_ctx_pose_graph_direct_info): a record of
+        POSE_GRAPH_DIRECT_INFO_DTYPE"""
+        info = np.zeros(1, dtype=POSE_GRAPH_DIRECT_INFO_DTYPE)
+        self._check(lib().mvs_ctx_pose_graph_direct_info(self._h, info.ctypes.data_as(C.c_void_p)),
+                    "mvs_ctx_pose_graph_direct_info")
+        return info[0]
 
     def essential_hypotheses_run(self):
         """hypotheses that took part in the last single-shot five-point call (mvs_ctx_essential_hypotheses_run)"""

@@ -366,6 +366,9 @@ inline RansacConfig &ransac_config()
     static thread_local RansacConfig cfg;
     return cfg;
 }
+#ifndef MVSLAM_POSE_GRAPH_SOLVER
+#define MVSLAM_POSE_GRAPH_SOLVER 0   // MVS_PG_SOLVER_PCG; -DMVSLAM_POSE_GRAPH_SOLVER=1 selects MVS_PG_SOLVER_DIRECT
+#endif
 // one mvs_ctx per host thread; throws if there is no HIP device (there is no CPU fallback)
 inline mvs_ctx *context()
 {
@@ -385,6 +388,9 @@ inline mvs_ctx *context()
         if (mvs_ctx_set_essential_confidence(h.ctx, MVSLAM_ESSENTIAL_CONFIDENCE) != MVS_OK)
             throw std::runtime_error("mvSLAM HIP backend: MVSLAM_ESSENTIAL_CONFIDENCE must be 0 or in (0, 1)");
 #endif
+        // the linear solver of GraphOptimizer's graphs of more than 16 nodes: 0 the conjugate gradient, 1 the direct solve
+        if (mvs_ctx_set_pose_graph_solver(h.ctx, MVSLAM_POSE_GRAPH_SOLVER) != MVS_OK)
+            throw std::runtime_error("mvSLAM HIP backend: MVSLAM_POSE_GRAPH_SOLVER must be 0 (PCG) or 1 (direct)");
     }
     return h.ctx;
 }

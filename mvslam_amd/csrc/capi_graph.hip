@@ -1,4 +1,5 @@
-// capi_graph.hip -- host side of libmvslam_hip.so: the back end.  Pose graphs (posegraph.hip), the
+// capi_graph.hip -- host side of libmvslam_hip.so: the back end.  Pose graphs (posegraph.hip; the direct
+// LM step of pg_direct.hip, section 4.10.4), the
 // graph of a resident sequence (seq_graph.hip), marginal covariances (pg_marginals.hip) and loop closures (loop.hip).  What it
 // decides about a graph without the device is in pg_host.hpp and pg_envelope.hpp.
 #include <algorithm>
@@ -25,6 +26,22 @@ void mvs_pose_graph_params_default(mvs_pose_graph_params *p)
     p->cg_rel_tol = 1e-10;
     p->cg_max_iterations = 0;                         // 6 n_nodes
     p->cg_chunk_iterations = 0;                       // the whole budget at once
+}
+
+mvs_status mvs_ctx_set_pose_graph_solver(mvs_ctx *ctx, int solver)
+{
+    if (!ctx || (solver != MVS_PG_SOLVER_PCG && solver != MVS_PG_SOLVER_DIRECT))
+        return MVS_ERR_INVALID_ARG;
+    ctx->pg_solver = solver;
+    return MVS_OK;
+}
+
+mvs_status mvs_ctx_pose_graph_direct_info(mvs_ctx *ctx, mvs_pose_graph_direct_info *info)
+{
+    if (!ctx || !info || !ctx->pgd_ran)
+        return MVS_ERR_INVALID_ARG;
+    *info = ctx->pgd_info;
+    return MVS_OK;
 }
 
 // weights of the anchor's prior (rotation, translation) from its standard deviations
@@ -90,14 +107,53 @@ struct PgLargeLayout {
     }
 };
 
+// what the direct solver (pg_direct.hip) has the host decide before anything is launched: the
+// envelope, the per-block term lists and the blocks' rows and slots
+struct PgdPlan {
+    std::vector<int32_t> first, row_off;
+    mvs_pgm::BlockLists lists;
+    mvs_pgm::DirectPlan blk;
+    int64_t blocks = 0;
+};
+static mvs_status pgd_plan(int N, int E, int anchor, const int32_t *src, const int32_t *dst, PgdPlan &P)
+{
+    P.blocks = mvs_pgm::envelope(N, E, src, dst, P.first, P.row_off);
+    if (P.blocks > mvs_pgm::kMaxEnvelopeBlocks)
+        return MVS_ERR_CAPACITY;
+    P.lists = mvs_pgm::block_lists(E, anchor, src, dst, P.first, P.row_off);
+    P.blk = mvs_pgm::direct_plan(N, P.first, P.row_off, P.lists);
+    return MVS_OK;
+}
+// the direct solver's scratch behind the large path's, as offsets from the end of PgLargeLayout
+struct PgdLayout {
+    size_t o_state, o_first, o_row, o_brow, o_bslot, o_soff, o_codes, o_sky, total;
+    PgdLayout(size_t N, const PgdPlan &P)
+    {
+        Carve L{64};
+        o_state = L.take(sizeof(PgdState));
+        o_first = L.take(N * 4), o_row = L.take((N + 1) * 4);
+        o_brow = L.take((size_t)P.blocks * 4), o_bslot = L.take((size_t)P.blocks * 4);
+        o_soff = L.take(P.lists.slot_off.size() * 4), o_codes = L.take(P.lists.codes.size() * 4);
+        o_sky = L.take((size_t)P.blocks * 36 * 8);
+        total = L.total();
+    }
+};
+// scratch of one large-path graph: PCG's, and with a plan the direct solver's behind it
+static size_t pg_large_scratch(size_t N, size_t E, const PgdPlan *plan)
+{
+    return PgLargeLayout(N, E).total + (plan ? PgdLayout(N, *plan).total : 0);
+}
+
 // one graph of 17 .. 4096 nodes: LM on the host, one synchronisation per iteration (and, with cg_chunk_iterations > 0, one
-// per chunk of CG iterations that did not converge).  h_src / h_dst: the edges on the host; every d_* pointer is device
+// per chunk of CG iterations that did not converge).  `plan`: null for the PCG, the direct solver's plan otherwise (then the
+// scratch is pg_large_scratch's).  h_src / h_dst: the edges on the host; every d_* pointer is device
 // memory that stays valid through the call; `base` is scratch of PgLargeLayout(N, E).total bytes.  The optimised nodes go
 // to poses_out with a copy of kind `out_kind` (device to host, or device to device), only when the result is ok.
 static mvs_status pose_graph_large_dev(mvs_ctx *ctx, char *base, int n_nodes, int n_edges, int anchor, const int32_t *h_src,
                                        const int32_t *h_dst, const int32_t *d_src, const int32_t *d_dst, const double *d_node,
                                        const double *d_z, const double *d_cov, const mvs_pose_graph_params &params,
-                                       mvs_pose_graph_result *res, double *poses_out, hipMemcpyKind out_kind)
+                                       mvs_pose_graph_result *res, double *poses_out, hipMemcpyKind out_kind,
+                                       const PgdPlan *plan = nullptr)
 {
     const size_t N = (size_t)n_nodes, E = (size_t)n_edges;
     std::vector<int32_t> off, inc;
@@ -120,6 +176,32 @@ static mvs_status pose_graph_large_dev(mvs_ctx *ctx, char *base, int n_nodes, in
     d.g = dp(L.o_vec[0]), d.x = dp(L.o_vec[1]), d.r = dp(L.o_vec[2]), d.z = dp(L.o_vec[3]), d.p = dp(L.o_vec[4]), d.q = dp(L.o_vec[5]);
     d.pq = dp(L.o_pq), d.Ha = dp(L.o_Ha);
     d.state = reinterpret_cast<PgState *>(base + L.o_state);
+    // the direct solver reads D and g of the gather, keeps C_i^-1 where the PCG keeps its block factors, the right-hand side in
+    // r, and leaves the step in x
+    PgdDev pd{};
+    PgdState hd{};
+    if (plan) {
+        const PgdLayout Ld(N, *plan);
+        char *db = base + L.total;
+        auto up = [&](size_t o, const std::vector<int32_t> &v) {
+            return v.empty() ? hipSuccess : hipMemcpyAsync(db + o, v.data(), v.size() * 4, hipMemcpyHostToDevice, s);
+        };
+        HIP_TRY(ctx, up(Ld.o_first, plan->first));
+        HIP_TRY(ctx, up(Ld.o_row, plan->row_off));
+        HIP_TRY(ctx, up(Ld.o_brow, plan->blk.blk_row));
+        HIP_TRY(ctx, up(Ld.o_bslot, plan->blk.blk_slot));
+        HIP_TRY(ctx, up(Ld.o_soff, plan->lists.slot_off));
+        HIP_TRY(ctx, up(Ld.o_codes, plan->lists.codes));
+        auto dip = [&](size_t o) { return reinterpret_cast<const int32_t *>(db + o); };
+        pd.n_nodes = n_nodes, pd.n_blocks = (int)plan->blocks;
+        pd.first = dip(Ld.o_first), pd.row_off = dip(Ld.o_row), pd.blk_row = dip(Ld.o_brow), pd.blk_slot = dip(Ld.o_bslot);
+        pd.slot_off = dip(Ld.o_soff), pd.codes = dip(Ld.o_codes);
+        pd.lin = d.lin, pd.D = d.D, pd.g = d.g, pd.Cinv = d.Mf, pd.y = d.r, pd.x = d.x;
+        pd.sky = reinterpret_cast<double *>(db + Ld.o_sky);
+        pd.state = reinterpret_cast<PgdState *>(db + Ld.o_state);
+        ctx->pgd_ran = true;
+        ctx->pgd_info = mvs_pose_graph_direct_info{(int32_t)plan->blocks, plan->blk.widest, 0, -1, 0.0, 0.0};
+    }
     const int cg_max = params.cg_max_iterations > 0 ? params.cg_max_iterations : 6 * n_nodes;
     const int chunk = params.cg_chunk_iterations;
     PgState h{};
@@ -128,12 +210,14 @@ static mvs_status pose_graph_large_dev(mvs_ctx *ctx, char *base, int n_nodes, in
     auto read_state = [&]() -> mvs_status {
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(&h, d.state, sizeof(h), hipMemcpyDeviceToHost, s));
+        if (plan)
+            HIP_TRY(ctx, hipMemcpyAsync(&hd, pd.state, sizeof(hd), hipMemcpyDeviceToHost, s));
         HIP_TRY(ctx, sync_stream(ctx));
         return MVS_OK;
     };
     launch_pg_prep(d, s);
     // a covariance that is not positive definite ends the call here, before anything is linearised on its whitening factor
-    if ((st = read_state()) != MVS_OK)   // `off` and `inc` have been read by here, too
+    if ((st = read_state()) != MVS_OK)   // `off`, `inc` and the plan's lists have been read by here, too
         return st;
     if (h.bad_cov) {
         *res = mvs_pose_graph_result{};
@@ -147,6 +231,24 @@ static mvs_status pose_graph_large_dev(mvs_ctx *ctx, char *base, int n_nodes, in
     bool ok0 = true, have0 = false;
     // one iteration on the device and its status; the first one also gives the cost at the initial values
     auto iterate = [&](bool with_cg) -> mvs_status {
+        if (plan) {
+            // a constant number of launches whatever the graph: linearise, gather, the four of the solve, update and cost
+            // (max_iterations = 0: the cost at the initial values alone)
+            launch_pg_linearise(d, cb, !have0, s);
+            if (with_cg) {
+                HIP_TRY(ctx, hipMemsetAsync(pd.state, 0, sizeof(PgdState), s));
+                launch_pgd_step(pd, lam, s);
+                launch_pg_end(d, cb, s);
+            }
+            if ((st = read_state()) != MVS_OK)
+                return st;
+            if (!have0) {
+                have0 = true;
+                cost0 = cur = h.cost0;
+                ok0 = std::isfinite(cur);
+            }
+            return MVS_OK;
+        }
         launch_pg_begin(d, cb, lam, !have0, s);
         if (with_cg && chunk <= 0) {
             launch_pg_cg(d, lam, cg_max, s);
@@ -180,8 +282,20 @@ static mvs_status pose_graph_large_dev(mvs_ctx *ctx, char *base, int n_nodes, in
         if (!ok0)
             break;
         cg_total += h.cg_iters;
-        // the linear solve counts as done when the CG converged, or ran out of iterations with a smaller residual
-        const bool solved = h.done == 1 || (h.done == 0 && h.rr < h.gnorm2);
+        if (plan) {
+            mvs_pose_graph_direct_info &info = ctx->pgd_info;
+            if (hd.status != 0 && info.failed_solves++ == 0) {
+                info.bad_node = n_nodes - hd.bad_code;
+                info.failed_pivot = hd.status == 3 ? hd.min_d : 0.0;
+            }
+            if (hd.status == 0) {   // a factorisation that completed
+                const double piv = std::sqrt(hd.min_d);
+                info.min_pivot = info.min_pivot > 0.0 ? std::min(info.min_pivot, piv) : piv;
+            }
+        }
+        // the linear solve counts as done when the CG converged, or ran out of iterations with a smaller residual; the direct
+        // solve when no pivot failed
+        const bool solved = plan ? hd.status == 0 : (h.done == 1 || (h.done == 0 && h.rr < h.gnorm2));
         const double cand = h.cand;
         const bool accepted = solved && cand <= cur;
         ++it;
@@ -253,14 +367,14 @@ static mvs_status pose_graph_upload(mvs_ctx *ctx, DevWorkspace &ws, const mvs_po
 
 // the host-pointer entry of the large path: upload, then the entry above
 static mvs_status pose_graph_large(mvs_ctx *ctx, const mvs_pose_graph &g, const mvs_pose_graph_params &params,
-                                   mvs_pose_graph_result *res, double *poses_out)
+                                   mvs_pose_graph_result *res, double *poses_out, const PgdPlan *plan)
 {
     PgUploaded u;
-    const mvs_status st = pose_graph_upload(ctx, ctx->pg, g, nullptr, PgLargeLayout((size_t)g.n_nodes, (size_t)g.n_edges).total, u);
+    const mvs_status st = pose_graph_upload(ctx, ctx->pg, g, nullptr, pg_large_scratch((size_t)g.n_nodes, (size_t)g.n_edges, plan), u);
     if (st != MVS_OK)
         return st;
     return pose_graph_large_dev(ctx, u.scratch, g.n_nodes, g.n_edges, g.anchor_node, g.edge_src, g.edge_dst, u.src, u.dst, u.node,
-                                u.z, u.cov, params, res, poses_out, hipMemcpyDeviceToHost);
+                                u.z, u.cov, params, res, poses_out, hipMemcpyDeviceToHost, plan);
 }
 
 // scratch of a dense-path batch of G graphs with sumN nodes and sumE edges.  Outputs first and contiguous (results,
@@ -321,6 +435,16 @@ mvs_status mvs_pose_graph_optimize_batch(mvs_ctx *ctx, const mvs_pose_graph *gra
         if (st != MVS_OK)
             return st;
         Nmax = std::max(Nmax, graphs[i].n_nodes);
+    }
+    // the direct solver's plans, and its one refusal, before anything is launched
+    std::vector<PgdPlan> plans(ctx->pg_solver == MVS_PG_SOLVER_DIRECT ? (size_t)n_graphs : 0);
+    for (size_t i = 0; i < plans.size(); ++i) {
+        const mvs_pose_graph &g = graphs[i];
+        if (g.n_nodes <= kPgDenseMaxNodes)
+            continue;
+        const mvs_status st = pgd_plan(g.n_nodes, g.n_edges, g.anchor_node, g.edge_src, g.edge_dst, plans[i]);
+        if (st != MVS_OK)
+            return st;
     }
     std::memset(results, 0, (size_t)n_graphs * sizeof(mvs_pose_graph_result));
     std::vector<char> joined((size_t)n_graphs);
@@ -392,7 +516,8 @@ mvs_status mvs_pose_graph_optimize_batch(mvs_ctx *ctx, const mvs_pose_graph *gra
     for (int i = 0; i < n_graphs; ++i) {
         if (!joined[(size_t)i] || graphs[i].n_nodes <= kPgDenseMaxNodes)
             continue;
-        const mvs_status st = pose_graph_large(ctx, graphs[i], *params, &results[i], poses_out + (size_t)i * Nmax * 12);
+        const mvs_status st = pose_graph_large(ctx, graphs[i], *params, &results[i], poses_out + (size_t)i * Nmax * 12,
+                                               plans.empty() ? nullptr : &plans[(size_t)i]);
         if (st != MVS_OK)
             return st;
     }
@@ -538,6 +663,10 @@ mvs_status mvs_seq_optimize_pose_graph(mvs_seq *q, const mvs_pose_graph_params *
     if (st != MVS_OK)
         return st;
     const int N = g.n_frames, E = head.n_edges;
+    PgdPlan plan;
+    const bool direct = ctx->pg_solver == MVS_PG_SOLVER_DIRECT && N > kPgDenseMaxNodes;
+    if (direct && (st = pgd_plan(N, E, 0, head.src, head.dst, plan)) != MVS_OK)
+        return st;
     if (!pose_graph_connected(N, E, head.src, head.dst, 0))
         return MVS_NO_MODEL;
     if (N <= kPgDenseMaxNodes) {
@@ -558,10 +687,10 @@ mvs_status mvs_seq_optimize_pose_graph(mvs_seq *q, const mvs_pose_graph_params *
         if (result->ok)
             HIP_TRY(ctx, hipMemcpyAsync(q->graph_opt_pose, base + L.o_po, (size_t)N * 96, hipMemcpyDeviceToDevice, s));
     } else {
-        if ((st = ws_grow(ctx, ctx->pg, PgLargeLayout((size_t)N, (size_t)E).total)) != MVS_OK)
+        if ((st = ws_grow(ctx, ctx->pg, pg_large_scratch((size_t)N, (size_t)E, direct ? &plan : nullptr))) != MVS_OK)
             return st;
         st = pose_graph_large_dev(ctx, ctx->pg.ptr(), N, E, 0, head.src, head.dst, g.edge_src, g.edge_dst, g.node_pose, g.edge_pose,
-                                  g.edge_cov, *params, result, q->graph_opt_pose, hipMemcpyDeviceToDevice);
+                                  g.edge_cov, *params, result, q->graph_opt_pose, hipMemcpyDeviceToDevice, direct ? &plan : nullptr);
         if (st != MVS_OK)
             return st;
     }

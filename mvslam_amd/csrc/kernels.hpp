@@ -333,6 +333,36 @@ void launch_pg_prep(const PgLargeDev &d, hipStream_t stream);
 void launch_pg_begin(const PgLargeDev &d, int cur, double lam, bool first, hipStream_t stream);
 void launch_pg_cg(const PgLargeDev &d, double lam, int n, hipStream_t stream);
 void launch_pg_end(const PgLargeDev &d, int cur, hipStream_t stream);
+// begin without the PCG start: what the direct step (below) has in front of it
+void launch_pg_linearise(const PgLargeDev &d, int cur, bool first, hipStream_t stream);
+
+// ---- the direct LM step of the large path (pg_direct.hip) ------------------------------------
+// (H + lambda I) x = -g by a block-scaled skyline Cholesky.  The diagonal blocks D and the gradient g are pg_gather_kernel's;
+// C_i C_i^T = D_i + lambda I, the scaled matrix C_i^-1 A_ij C_j^-T (unit diagonal blocks) is assembled into the envelope of
+// pg_envelope.hpp, factorised in place and solved; x_i = C_i^-T z_i.
+struct PgdState {
+    int32_t status;      // 0 solved; 2 a diagonal block of H + lambda I failed its Cholesky; 3 a pivot of the skyline failed
+    int32_t bad_code;    // n_nodes - (the first node at which that happened); 0: none
+    double min_d;        // the smallest pivot of the scaled factorisation before its square root (status 0 or 3)
+};
+struct PgdDev {
+    int n_nodes, n_blocks;
+    const int32_t *first;        // [N]
+    const int32_t *row_off;      // [N + 1]
+    const int32_t *blk_row;      // [n_blocks] the row of every block of the envelope
+    const int32_t *blk_slot;     // [n_blocks] its slot in the term lists, -1: no term touches it (fill only)
+    const int32_t *slot_off;     // [n_slots + 1]
+    const int32_t *codes;        // pg_envelope.hpp block_lists
+    const double *lin;           // [E][kPgLin]
+    const double *D, *g;         // [N][21], [N][6]: pg_gather_kernel's
+    double *Cinv;                // [N][21] C_i^-1, packed lower
+    double *sky;                 // [n_blocks][36]; a diagonal block of the factor holds L_ii^-1
+    double *y;                   // [N][6] right-hand side, then y, then z
+    double *x;                   // [N][6] the step
+    PgdState *state;
+};
+// scale, assemble, factorise (the forward substitution rides along), back-substitute and unscale: four launches
+void launch_pgd_step(const PgdDev &d, double lam, hipStream_t stream);
 
 // ---- marginal covariances of a pose graph (pg_marginals.hip) ---------------------------------
 // H = J_a^T W_a J_a + sum_k J_k^T W_k J_k at the poses X, no lambda, as the block lower triangle inside its envelope (row i

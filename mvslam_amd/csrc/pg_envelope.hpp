@@ -1,6 +1,7 @@
-// pg_envelope.hpp -- the host side of the pose-graph marginals (pg_marginals.hip): the block
-// skyline of H, the per-block edge lists of its assembly and the chunking of the queries.  Plain C++ with no HIP in it, so
-// that tests/cpp/pg_envelope_check.cpp can run it under the host sanitizers.
+// pg_envelope.hpp -- the host side of the pose-graph marginals (pg_marginals.hip) and of the direct
+// LM step (pg_direct.hip; section 4.10.4): the block skyline of H, the per-block edge lists of its assembly, the blocks' rows
+// and slots, and the chunking of the queries.  Plain C++ with no HIP in it, so that tests/cpp/pg_envelope_check.cpp and
+// tests/cpp/pg_direct_plan_check.cpp can run it under the host sanitizers.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -73,6 +74,29 @@ inline BlockLists block_lists(int n_edges, int anchor, const int32_t *src, const
         out.codes.push_back(terms[t].second);
     }
     out.slot_off.push_back((int32_t)terms.size());
+    return out;
+}
+
+// What the direct LM step (pg_direct.hip) needs of the envelope beyond the above: for every block
+// its row (its column is first[row] + its place in the row) and its slot in `lists`, -1 for a block no term touches (fill
+// only); the widest row in blocks.
+struct DirectPlan {
+    std::vector<int32_t> blk_row, blk_slot;
+    int widest = 0;
+};
+inline DirectPlan direct_plan(int n_nodes, const std::vector<int32_t> &first, const std::vector<int32_t> &row_off, const BlockLists &lists)
+{
+    DirectPlan out;
+    const size_t blocks = n_nodes > 0 ? (size_t)row_off[(size_t)n_nodes] : 0;
+    out.blk_row.resize(blocks);
+    out.blk_slot.assign(blocks, -1);
+    for (int i = 0; i < n_nodes; ++i) {
+        out.widest = std::max(out.widest, i - first[(size_t)i] + 1);
+        for (int32_t b = row_off[(size_t)i]; b < row_off[(size_t)i + 1]; ++b)
+            out.blk_row[(size_t)b] = i;
+    }
+    for (size_t s = 0; s < lists.slot_blk.size(); ++s)
+        out.blk_slot[(size_t)lists.slot_blk[s]] = (int32_t)s;
     return out;
 }
 

@@ -875,7 +875,7 @@ dim3 pg_edge_blocks(const PgLargeDev &d)
 }
 }  // namespace
 
-void launch_pg_begin(const PgLargeDev &d, int cur, double lam, bool first, hipStream_t stream)
+void launch_pg_linearise(const PgLargeDev &d, int cur, bool first, hipStream_t stream)
 {
     const dim3 eb = pg_edge_blocks(d);
     const dim3 nb((d.n_nodes + 63) / 64);
@@ -886,6 +886,11 @@ void launch_pg_begin(const PgLargeDev &d, int cur, double lam, bool first, hipSt
     }
     hipLaunchKernelGGL(pg_edge_kernel<true>, eb, dim3(kPgThreads), 0, stream, d, ps);
     hipLaunchKernelGGL(pg_gather_kernel, nb, dim3(64), 0, stream, d, ps);
+}
+
+void launch_pg_begin(const PgLargeDev &d, int cur, double lam, bool first, hipStream_t stream)
+{
+    launch_pg_linearise(d, cur, first, stream);
     hipLaunchKernelGGL(pg_cg_init_kernel, dim3(1), dim3(kPgThreads), 0, stream, d, lam);
 }
 
