@@ -34,16 +34,21 @@ def _flip(row, bits):
     return r
 
 
-def _run(ctx, d1, d2, n1, n2, settings):
+def _run(ctx, d1, d2, n1, n2, settings, desc_bytes=32, matrix_core=True, oracle=None):
+    """every pair of a batch against the oracle's match list, byte for byte, at every (ratio, max_dist) of `settings`.
+    matrix_core: the batch must have at least 512 matrix-core workgroups (True) or fewer (False: the vector kernel serves
+    256-bit descriptors too); oracle(p, ratio, max_dist): the oracle's list of pair p, if the caller keeps one"""
     P, N = d1.shape[:2]
-    assert -(-N // MM_QUERIES_PER_GROUP) * P >= 512
+    assert (-(-N // MM_QUERIES_PER_GROUP) * P >= 512) == matrix_core
+    if oracle is None:
+        oracle = lambda p, ratio, max_dist: o.match_visual_features(d1[p, :n1[p]], d2[p, :n2[p]], ratio, max_dist)
     assert np.all(n1 >= 2)                                # the oracle's ratio test needs two trains
     rng = np.random.default_rng(99)
     kp = np.zeros((P, N, 2), dtype=np.float32)
     kp[..., 0] = rng.uniform(0, 640, size=(P, N))
     kp[..., 1] = rng.uniform(0, 480, size=(P, N))
     K = np.tile(synth.K_DEFAULT.reshape(1, 9), (P, 1))
-    b = capi.Batch(ctx, P, N, 32)
+    b = capi.Batch(ctx, P, N, desc_bytes)
     try:
         b.upload(0, d1, kp, n1, d2, kp, n2, K, np.arange(P, dtype=np.int64))
         for ratio, max_dist in settings:
@@ -52,7 +57,7 @@ def _run(ctx, d1, d2, n1, n2, settings):
             b.run(prm)
             b.sync()
             out = b.download(mask=False, points=False)
-            refs = helpers.threads(lambda p: o.match_visual_features(d1[p, :n1[p]], d2[p, :n2[p]], ratio, max_dist), list(range(P)))
+            refs = helpers.threads(lambda p: oracle(p, ratio, max_dist), list(range(P)))
             total = 0
             for p in range(P):
                 ref = refs[p]

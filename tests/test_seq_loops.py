@@ -227,17 +227,23 @@ def test_gpu_loop_sequence_selects_its_revisits(loop_seq):
 @pytest.mark.gpu
 @pytest.mark.parametrize("essential", [False, True], ids=["eight_point", "five_point"])
 def test_gpu_verification_equals_an_uploaded_batch(ctx, loop_seq, essential):
+    s, data = loop_seq
+    check_verification_equals_an_uploaded_batch(ctx, s, data, essential)
+
+
+def check_verification_equals_an_uploaded_batch(ctx, s, data, essential, desc_bytes=32):
+    """the verification of the selected candidates of `s` (which holds `data` and st._octaves) against a batch of the same
+    (i, j) frames uploaded from the host: every byte of the pair results and of the refinement records"""
     from mvslam_amd import capi
 
-    s, data = loop_seq
     prm = _two_view()
     s.verify_loops(prm, essential=essential)
     got = s.download_loop_candidates(pairs=True)
     k = got["n_kept"]
     ci, cj = got["cand"]["i"], got["cand"]["j"]
-    b = capi.Batch(ctx, k, N_KP, 32)
+    b = capi.Batch(ctx, k, N_KP, desc_bytes)
     try:
-        oct_ = st._octaves(LOOP_FRAMES)
+        oct_ = st._octaves(s.n_frames)
         b.upload(0, data["desc"][ci], data["kp"][ci], data["n_kp"][ci], data["desc"][cj], data["kp"][cj], data["n_kp"][cj],
                  np.tile(data["K"].reshape(1, 9), (k, 1)), np.arange(k, dtype=np.int64))
         b.upload_octaves(0, oct_[ci], oct_[cj])

@@ -116,8 +116,6 @@ def _ssd(gp):
 @pytest.mark.gpu
 @pytest.mark.parametrize("essential", [False, True])
 def test_gpu_lagged_pairs_equal_the_batch_path(ctx, essential):
-    from mvslam_amd import capi
-
     seq = make_seq()
     s = _open(ctx, seq, essential=essential)
     try:
@@ -132,25 +130,34 @@ def test_gpu_lagged_pairs_equal_the_batch_path(ctx, essential):
             assert gp["match_ssd"].tolist() == _ssd(gp), d
             assert gp["results"]["valid"].any() and gp["match_ssd"].min() >= 0 and len(gp["results"]) == N_FRAMES - d
         assert any(raw[d][0]["match_ssd"].max() > 0 for d in raw)
-        for d in (2, 3):
-            P = N_FRAMES - d
-            b = capi.Batch(ctx, P, N_KP, 32)
-            try:
-                b.upload(0, seq["desc"][:P], seq["kp"][:P], seq["n_kp"][:P], seq["desc"][d:], seq["kp"][d:], seq["n_kp"][d:],
-                         seq["K"], np.arange(P))
-                b.upload_octaves(0, _octaves()[:P], _octaves()[d:])
-                (b.run_essential if essential else b.run)(_params())
-                b.refine(sigma_px=0.5)
-                want, wantr = b.download(), b.download_refined(point_cov=True)
-            finally:
-                b.close()
-            for k in ("results", "matches", "mask", "points", "point_idx"):
-                assert raw[d][0][k].tobytes() == want[k].tobytes(), (d, k)
-            for k in ("refined", "points", "point_cov"):   # every byte: rows past n_points are zero on both sides
-                assert raw[d][1][k].tobytes() == wantr[k].tobytes(), (d, k)
-            assert raw[d][0]["results"].tobytes() != one["results"][:P].tobytes()       # not the adjacent pairs again
+        check_lags_equal_a_batch(ctx, raw, one, seq, _octaves(), _params(), essential)
     finally:
         s.close()
+
+
+def check_lags_equal_a_batch(ctx, raw, one, seq, octaves, prm, essential, lags=(2, 3), desc_bytes=32):
+    """raw[d] = (download_lag_pairs(d), download_lag_refined(d, point_cov=True)) of a sequence holding `seq` and `octaves`,
+    run with `prm`: every byte equals an uploaded batch of the pairs (i, i + d); one = the sequence's download_pairs()"""
+    from mvslam_amd import capi
+
+    n_frames, n_kp = seq["desc"].shape[:2]
+    for d in lags:
+        P = n_frames - d
+        b = capi.Batch(ctx, P, n_kp, desc_bytes)
+        try:
+            b.upload(0, seq["desc"][:P], seq["kp"][:P], seq["n_kp"][:P], seq["desc"][d:], seq["kp"][d:], seq["n_kp"][d:],
+                     seq["K"], np.arange(P))
+            b.upload_octaves(0, octaves[:P], octaves[d:])
+            (b.run_essential if essential else b.run)(prm)
+            b.refine(sigma_px=0.5)
+            want, wantr = b.download(), b.download_refined(point_cov=True)
+        finally:
+            b.close()
+        for k in ("results", "matches", "mask", "points", "point_idx"):
+            assert raw[d][0][k].tobytes() == want[k].tobytes(), (d, k)
+        for k in ("refined", "points", "point_cov"):   # every byte: rows past n_points are zero on both sides
+            assert raw[d][1][k].tobytes() == wantr[k].tobytes(), (d, k)
+        assert raw[d][0]["results"].tobytes() != one["results"][:P].tobytes()       # not the adjacent pairs again
 
 
 # ---------------------------------------------------------------------------------------------------------------------

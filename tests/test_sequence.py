@@ -33,7 +33,9 @@ def _pool(fn, n_items, threads):
     return out
 
 
-def oracle_sequence(seq, prm, pprm, ratio=0.7, max_dist=10.0, threads=1):
+def oracle_sequence(seq, prm, pprm, ratio=0.7, max_dist=10.0, threads=1, pairs=None):
+    """(pairs, tracks) of the oracle; with `pairs` given (records with ok, matches, point_idx, points: a device's download,
+    say) only the join and the PnP on top of them"""
     F = len(seq["n_kp"])
     K = seq["K"]
 
@@ -43,7 +45,7 @@ def oracle_sequence(seq, prm, pprm, ratio=0.7, max_dist=10.0, threads=1):
         return o.image_pair(seq["desc"][k][:a], seq["kp"][k][:a], seq["desc"][k + 1][:b], seq["kp"][k + 1][:b], K,
                             op, ratio, max_dist)
 
-    pairs = _pool(pair, F - 1, threads)
+    pairs = _pool(pair, F - 1, threads) if pairs is None else pairs
 
     def track(q):
         pa, pb = pairs[q], pairs[q + 1]
@@ -65,6 +67,38 @@ def oracle_sequence(seq, prm, pprm, ratio=0.7, max_dist=10.0, threads=1):
 
     tracks = _pool(track, F - 2, threads)
     return pairs, tracks
+
+
+def check_pairs_against_oracle(gp, pairs):
+    """download_pairs() against the oracle's pairs: the zero-copy pair views behave like a batch"""
+    for k, ref in enumerate(pairs):
+        r = gp["results"][k]
+        M = ref["n_matches"]
+        assert r["n_matches"] == M and gp["matches"][k][:M].tobytes() == ref["matches"].tobytes()
+        assert bool(r["valid"]) == ref["ok"] and np.array_equal(gp["mask"][k][:M], ref["mask"])
+        if ref["ok"]:
+            n = ref["n_points"]
+            assert np.array_equal(gp["point_idx"][k][:n], ref["point_idx"])
+            assert gp["points"][k][:n].tobytes() == ref["points"].tobytes()
+
+
+def check_tracks_against_oracle(gt, tracks):
+    """download_tracks() against the oracle's join and PnP; returns the number of tracks that solve"""
+    n_ok = 0
+    for q, ref in enumerate(tracks):
+        t = gt["tracks"][q]
+        nc = len(ref["X"])
+        assert t["n_corr"] == nc                                       # the join: same correspondences, same order
+        assert gt["corr_xyz"][q][:nc].tobytes() == ref["X"].tobytes()
+        assert gt["corr_uv"][q][:nc].tobytes() == ref["uv"].tobytes()
+        assert bool(t["ok"]) == ref["ok"] and t["best_hyp"] == ref["best_hyp"]
+        if ref["ok"]:
+            n_ok += 1
+            ni = len(ref["inliers"])
+            assert t["n_inliers"] == ni and np.array_equal(gt["inlier_idx"][q][:ni], ref["inliers"])   # bit-exact
+            assert helpers.rel_err(t["R"], ref["R"]) <= 1e-4 and helpers.rel_err(t["t"], ref["t"]) <= 1e-4
+            assert t["R"].tobytes() == ref["R"].tobytes() and t["t"].tobytes() == ref["t"].tobytes()
+    return n_ok
 
 
 def test_sequence_generator_is_consistent():
@@ -92,29 +126,8 @@ def test_gpu_sequence_matches_oracle(ctx):
     gp, gt = s.download_pairs(), s.download_tracks()
     s.close()
     pairs, tracks = oracle_sequence(seq, prm, pprm)
-    for k, ref in enumerate(pairs):                                   # the zero-copy pair views behave like a batch
-        r = gp["results"][k]
-        M = ref["n_matches"]
-        assert r["n_matches"] == M and gp["matches"][k][:M].tobytes() == ref["matches"].tobytes()
-        assert bool(r["valid"]) == ref["ok"] and np.array_equal(gp["mask"][k][:M], ref["mask"])
-        if ref["ok"]:
-            n = ref["n_points"]
-            assert np.array_equal(gp["point_idx"][k][:n], ref["point_idx"])
-            assert gp["points"][k][:n].tobytes() == ref["points"].tobytes()
-    n_ok = 0
-    for q, ref in enumerate(tracks):
-        t = gt["tracks"][q]
-        nc = len(ref["X"])
-        assert t["n_corr"] == nc                                       # the join: same correspondences, same order
-        assert gt["corr_xyz"][q][:nc].tobytes() == ref["X"].tobytes()
-        assert gt["corr_uv"][q][:nc].tobytes() == ref["uv"].tobytes()
-        assert bool(t["ok"]) == ref["ok"] and t["best_hyp"] == ref["best_hyp"]
-        if ref["ok"]:
-            n_ok += 1
-            ni = len(ref["inliers"])
-            assert t["n_inliers"] == ni and np.array_equal(gt["inlier_idx"][q][:ni], ref["inliers"])   # bit-exact
-            assert helpers.rel_err(t["R"], ref["R"]) <= 1e-4 and helpers.rel_err(t["t"], ref["t"]) <= 1e-4
-            assert t["R"].tobytes() == ref["R"].tobytes() and t["t"].tobytes() == ref["t"].tobytes()
+    check_pairs_against_oracle(gp, pairs)
+    n_ok = check_tracks_against_oracle(gt, tracks)
     assert n_ok >= F - 3                                                # the tracks actually solve
 
 
