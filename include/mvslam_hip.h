@@ -1058,6 +1058,46 @@ mvs_status mvs_pose_graph_marginals(mvs_ctx *ctx, const mvs_pose_graph *graph, c
 mvs_status mvs_seq_pose_graph_marginals(mvs_seq *s, const double anchor_sigma[2], int n_query, const int32_t *query_i,
                                         const int32_t *query_j, double *cov_out, mvs_pose_graph_marginals_info *info);
 
+/* ---- Robust edge losses and per-edge residuals --------------------------------------------------
+ * A switch of the context, MVS_PG_LOSS_NONE by default: with it every call returns the bytes it returned before the switch
+ * existed.  With s_k = |r_k|^2, the squared norm of edge k's whitened residual, the optimiser's cost becomes
+ *   1/2 [ |e_anchor|^2 + sum_{k < first_edge} s_k + sum_{k >= first_edge} rho2(s_k) ],   x = sqrt(s):
+ *     MVS_PG_LOSS_NONE    rho2 = s                                    w = 1
+ *     MVS_PG_LOSS_HUBER   rho2 = s if x <= k, else (2 k) x - k k      w = 1 if x <= k, else k / x
+ *     MVS_PG_LOSS_CAUCHY  rho2 = (k k) log1p(s / (k k))               w = (k k) / (k k + s)
+ * (GTSAM's mEstimator::Huber and mEstimator::Cauchy, in this library's "twice the cost" convention).  The linearisation is
+ * iteratively reweighted least squares, as GTSAM's: a robustified edge enters H and g as sqrt(w) r, sqrt(w) A_src and
+ * sqrt(w) A_dst, nothing else changes.  The anchor is never robustified.  The LM rule, its exits, error and error_initial are
+ * those of mvs_pose_graph_optimize on the cost above: a candidate is accepted when its ROBUST cost is not above the current one.
+ * Order of operations, part of the contract: s by the optimiser's fused sum of squares; x = sqrt(s); one division for w (Cauchy's
+ * cost: log1p of one quotient); sqrt(w); each of the 78 doubles of the linearised edge multiplied once by sqrt(w).  Binary64, no
+ * further fused operation, no atomics: the same input gives the same bytes.
+ * first_edge: the edges with index >= first_edge inside their graph (of a batch: inside each graph) get the loss; 0 = all.
+ * MVS_PG_LOSS_LOOP_EDGES stands, in mvs_seq_optimize_pose_graph and mvs_seq_pose_graph_edge_stats, for the number of edges the
+ * resident graph had before mvs_seq_add_loop_edges: exactly its edges of kind 2 get the loss (none added: no edge does, and the
+ * bytes are those of MVS_PG_LOSS_NONE).  The calls on a host graph refuse it with MVS_ERR_INVALID_ARG before anything runs.
+ * MVS_ERR_INVALID_ARG, the setting stays: a loss that is none of the three; with a loss other than NONE a k that is not finite
+ * and > 0; first_edge < -1.  The setting holds for mvs_pose_graph_optimize, mvs_pose_graph_optimize_batch and
+ * mvs_seq_optimize_pose_graph on every path (dense, PCG, direct).  mvs_pose_graph_marginals and mvs_seq_pose_graph_marginals
+ * IGNORE it: their H is the Gaussian one, whatever loss the poses were optimised under. */
+#define MVS_PG_LOSS_NONE 0
+#define MVS_PG_LOSS_HUBER 1
+#define MVS_PG_LOSS_CAUCHY 2
+#define MVS_PG_LOSS_LOOP_EDGES (-1)
+mvs_status mvs_ctx_set_pose_graph_loss(mvs_ctx *ctx, int loss, double k, int32_t first_edge);
+/* chi2[k] = s_k at `poses` (n_nodes x 12; NULL: graph->node_pose) for every edge, and, with weight != NULL, weight[k] = w(s_k)
+ * under the context's current loss, 1 for the edges below first_edge: what tells a caller which edge the loss turned down.  Both
+ * arrays hold n_edges doubles.  Argument, capacity, topology and covariance errors are those of mvs_pose_graph_optimize with its
+ * status codes (MVS_NO_MODEL: a node no path joins to the anchor, a covariance that is not positive definite; nothing is
+ * written then); non-finite poses and MVS_PG_LOSS_LOOP_EDGES are MVS_ERR_INVALID_ARG.  Waits for the ctx stream. */
+mvs_status mvs_pose_graph_edge_stats(mvs_ctx *ctx, const mvs_pose_graph *graph, const double *poses /* NULL: node_pose */,
+                                     double *chi2 /* n_edges: s_k */, double *weight /* n_edges, may be NULL */);
+/* The same on the resident graph of a sequence at its resident OPTIMISED nodes, through device pointers; the arrays hold what
+ * mvs_seq_download_pose_graph's hold.  The bytes are those of mvs_pose_graph_edge_stats on the downloaded graph and poses (with
+ * first_edge resolved as above).  MVS_ERR_INVALID_ARG unless the last mvs_seq_optimize_pose_graph on the current graph
+ * succeeded. */
+mvs_status mvs_seq_pose_graph_edge_stats(mvs_seq *s, double *chi2, double *weight);
+
 /* ---- Loop closures of a resident sequence -------------------------------------------------------
  * Every edge of the graph above joins frames at most max_lag apart: it smooths a trajectory and cannot remove its drift.  These
  * calls find frames that see the same place again, verify the pairs with the two-view pipeline and the refinement, and append

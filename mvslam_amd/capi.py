@@ -164,6 +164,8 @@ POSE_GRAPH_MARGINALS_INFO_DTYPE = np.dtype([("ok", "<i4"), ("envelope_blocks", "
                                             ("min_pivot", "<f8")])
 POSE_GRAPH_MAX_ENVELOPE_BLOCKS = 1 << 21
 MVS_PG_SOLVER_PCG, MVS_PG_SOLVER_DIRECT = 0, 1
+MVS_PG_LOSS_NONE, MVS_PG_LOSS_HUBER, MVS_PG_LOSS_CAUCHY = 0, 1, 2
+MVS_PG_LOSS_LOOP_EDGES = -1
 POSE_GRAPH_DIRECT_INFO_DTYPE = np.dtype([("envelope_blocks", "<i4"), ("widest_row", "<i4"), ("failed_solves", "<i4"),
                                          ("bad_node", "<i4"), ("min_pivot", "<f8"), ("failed_pivot", "<f8")])
 
@@ -264,6 +266,7 @@ EXPORTS = [
     "mvs_seq_verify_loops", "mvs_seq_add_loop_edges", "mvs_seq_download_loop_candidates",
     "mvs_pose_graph_marginals", "mvs_seq_pose_graph_marginals",
     "mvs_ctx_set_pose_graph_solver", "mvs_ctx_pose_graph_direct_info",
+    "mvs_ctx_set_pose_graph_loss", "mvs_pose_graph_edge_stats", "mvs_seq_pose_graph_edge_stats",
 ]
 
 
@@ -318,6 +321,13 @@ def lib():
         _lib.mvs_ctx_essential_hypotheses_run.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         _lib.mvs_ctx_set_pose_graph_solver.restype = C.c_int
         _lib.mvs_ctx_set_pose_graph_solver.argtypes = [C.c_void_p, C.c_int]
+        _lib.mvs_ctx_set_pose_graph_loss.restype = C.c_int
+        _lib.mvs_ctx_set_pose_graph_loss.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int32]
+        _lib.mvs_pose_graph_edge_stats.restype = C.c_int
+        _lib.mvs_pose_graph_edge_stats.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                   C.POINTER(C.c_double)]
+        _lib.mvs_seq_pose_graph_edge_stats.restype = C.c_int
+        _lib.mvs_seq_pose_graph_edge_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib.mvs_ctx_pose_graph_direct_info.restype = C.c_int
         _lib.mvs_ctx_pose_graph_direct_info.argtypes = [C.c_void_p, C.c_void_p]
         _lib.mvs_batch_download_hypotheses_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]
@@ -478,6 +488,38 @@ class Context:
         """The linear solver of pose graphs of more than 16 nodes: MVS_PG_SOLVER_PCG (default) or MVS_PG_SOLVER_DIRECT, the
         block-scaled skyline Cholesky (mvs_ctx_set_pose_graph_solver).  Anything else raises MvsError (MVS_ERR_INVALID_ARG)."""
         self._check(lib().mvs_ctx_set_pose_graph_solver(self._h, C.c_int(solver)), "mvs_ctx_set_pose_graph_solver")
+
+    def set_pose_graph_loss(self, loss, k=1.0, first_edge=0):
+        """The robust loss of the pose graphs' edges (mvs_ctx_set_pose_graph_loss): MVS_PG_LOSS_NONE (default),
+        MVS_PG_LOSS_HUBER or MVS_PG_LOSS_CAUCHY with the constant k, on the edges with index >= first_edge inside their graph
+        (MVS_PG_LOSS_LOOP_EDGES: the loop edges of a resident graph).  A refused setting raises MvsError
+        (MVS_ERR_INVALID_ARG) and leaves the previous one in force."""
+        self._check(lib().mvs_ctx_set_pose_graph_loss(self._h, C.c_int(loss), C.c_double(k), C.c_int32(first_edge)),
+                    "mvs_ctx_set_pose_graph_loss")
+
+    def pose_graph_edge_stats(self, graph, poses=None):
+        """mvs_pose_graph_edge_stats: (status, chi2 [E], weight [E]) at `poses` (None: the graph's node_pose) -- the squared norm
+        of every edge's whitened residual and its weight under the context's loss.  MVS_NO_MODEL is returned (the arrays are
+        then zero); argument and capacity errors raise MvsError."""
+        npose = _f64(graph["node_pose"]).reshape(-1, 12)
+        src = np.ascontiguousarray(graph["edge_src"], dtype=np.int32).reshape(-1)
+        dst = np.ascontiguousarray(graph["edge_dst"], dtype=np.int32).reshape(-1)
+        ep = _f64(graph["edge_pose"]).reshape(-1, 12)
+        ec = _f64(graph["edge_cov"]).reshape(-1, 36)
+        if not (len(src) == len(dst) == len(ep) == len(ec)):
+            raise ValueError("pose graph: the per-edge arrays differ in length")
+        g = PoseGraph(npose.shape[0], len(src), _ptr(npose, C.c_double), _ptr(src, C.c_int32), _ptr(dst, C.c_int32),
+                      _ptr(ep, C.c_double), _ptr(ec, C.c_double), int(graph.get("anchor", 0)))
+        X = None
+        if poses is not None:
+            X = _f64(poses).reshape(-1, 12)
+            if X.shape[0] != npose.shape[0]:
+                raise ValueError("pose graph: `poses` has another node count than the graph")
+        chi2, weight = np.zeros(max(len(src), 1)), np.zeros(max(len(src), 1))
+        st = lib().mvs_pose_graph_edge_stats(self._h, C.byref(g), _ptr(X, C.c_double), _ptr(chi2, C.c_double),
+                                             _ptr(weight, C.c_double))
+        self._check(st, "mvs_pose_graph_edge_stats", allow_no_model=True)
+        return st, chi2[:len(src)], weight[:len(src)]
 
     def pose_graph_direct_info(self):
         """what the direct solver met in the last graph that went through it (mvs_ctx_pose_graph_direct_info): a record of
@@ -1446,6 +1488,18 @@ class Sequence:
         st = lib().mvs_seq_download_pose_graph_poses(self._h, _ptr(poses, C.c_double))
         self.ctx._check(st, "mvs_seq_download_pose_graph_poses")
         return poses
+
+    def pose_graph_edge_stats(self):
+        """mvs_seq_pose_graph_edge_stats: (status, chi2 [E], weight [E]) of the resident graph's edges at its optimised nodes,
+        under the context's loss.  Raises MvsError (MVS_ERR_INVALID_ARG) unless the last optimize_pose_graph() on the current
+        graph succeeded."""
+        cap = max(getattr(self, "_graph_slots", 0) + getattr(self, "_graph_loop_rows", 0), 1)   # download_pose_graph's rows
+        chi2, weight, n = np.zeros(cap), np.zeros(cap), np.zeros(1, dtype=np.int32)
+        st = lib().mvs_seq_pose_graph_edge_stats(self._h, _ptr(chi2, C.c_double), _ptr(weight, C.c_double))
+        self.ctx._check(st, "mvs_seq_pose_graph_edge_stats", allow_no_model=True)
+        self.ctx._check(lib().mvs_seq_download_pose_graph(self._h, _ptr(n, C.c_int32), None, None, None, None, None, None, None,
+                                                          None), "mvs_seq_download_pose_graph")
+        return st, chi2[:int(n[0])], weight[:int(n[0])]
 
     def pose_graph_marginals(self, queries=None, anchor_sigma=None, cov_out=None):
         """mvs_seq_pose_graph_marginals: blocks of Sigma = H^-1 of the resident graph at its optimised nodes; as

@@ -369,6 +369,17 @@ inline RansacConfig &ransac_config()
 #ifndef MVSLAM_POSE_GRAPH_SOLVER
 #define MVSLAM_POSE_GRAPH_SOLVER 0   // MVS_PG_SOLVER_PCG; -DMVSLAM_POSE_GRAPH_SOLVER=1 selects MVS_PG_SOLVER_DIRECT
 #endif
+// the robust loss of GraphOptimizer's edges (mvs_ctx_set_pose_graph_loss): 0 none, 1 Huber, 2 Cauchy, with its constant, on
+// the edges from MVSLAM_POSE_GRAPH_LOSS_FIRST_EDGE on (in the order they were added to the Graph)
+#ifndef MVSLAM_POSE_GRAPH_LOSS
+#define MVSLAM_POSE_GRAPH_LOSS 0
+#endif
+#ifndef MVSLAM_POSE_GRAPH_LOSS_K
+#define MVSLAM_POSE_GRAPH_LOSS_K 1.0
+#endif
+#ifndef MVSLAM_POSE_GRAPH_LOSS_FIRST_EDGE
+#define MVSLAM_POSE_GRAPH_LOSS_FIRST_EDGE 0
+#endif
 // one mvs_ctx per host thread; throws if there is no HIP device (there is no CPU fallback)
 inline mvs_ctx *context()
 {
@@ -391,6 +402,10 @@ inline mvs_ctx *context()
         // the linear solver of GraphOptimizer's graphs of more than 16 nodes: 0 the conjugate gradient, 1 the direct solve
         if (mvs_ctx_set_pose_graph_solver(h.ctx, MVSLAM_POSE_GRAPH_SOLVER) != MVS_OK)
             throw std::runtime_error("mvSLAM HIP backend: MVSLAM_POSE_GRAPH_SOLVER must be 0 (PCG) or 1 (direct)");
+        if (MVSLAM_POSE_GRAPH_LOSS_FIRST_EDGE < 0 ||
+            mvs_ctx_set_pose_graph_loss(h.ctx, MVSLAM_POSE_GRAPH_LOSS, MVSLAM_POSE_GRAPH_LOSS_K, MVSLAM_POSE_GRAPH_LOSS_FIRST_EDGE) != MVS_OK)
+            throw std::runtime_error("mvSLAM HIP backend: MVSLAM_POSE_GRAPH_LOSS must be 0 (none), 1 (Huber) or 2 (Cauchy), with "
+                                     "MVSLAM_POSE_GRAPH_LOSS_K > 0 and MVSLAM_POSE_GRAPH_LOSS_FIRST_EDGE >= 0");
     }
     return h.ctx;
 }

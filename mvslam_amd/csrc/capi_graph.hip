@@ -36,6 +36,16 @@ mvs_status mvs_ctx_set_pose_graph_solver(mvs_ctx *ctx, int solver)
     return MVS_OK;
 }
 
+mvs_status mvs_ctx_set_pose_graph_loss(mvs_ctx *ctx, int loss, double k, int32_t first_edge)
+{
+    if (!ctx || !loss_args_ok(loss, k, first_edge))
+        return MVS_ERR_INVALID_ARG;
+    ctx->pg_loss = loss;
+    ctx->pg_loss_k = k;
+    ctx->pg_loss_first = first_edge;
+    return MVS_OK;
+}
+
 mvs_status mvs_ctx_pose_graph_direct_info(mvs_ctx *ctx, mvs_pose_graph_direct_info *info)
 {
     if (!ctx || !info || !ctx->pgd_ran)
@@ -51,9 +61,26 @@ static void anchor_weights(const double sigma[2], double w[2])
     w[1] = 1.0 / (sigma[1] * sigma[1]);
 }
 
-static PgCfg to_pg_cfg(const mvs_pose_graph_params &p)
+// the robust loss of one call's edges: the context's setting with first_edge resolved
+struct PgLoss {
+    int loss = MVS_PG_LOSS_NONE;
+    double k = 0.0;
+    int32_t first = 0;
+};
+// the context's setting for a host graph, where first_edge stands for itself (the callers have refused
+// MVS_PG_LOSS_LOOP_EDGES)
+static PgLoss ctx_loss(const mvs_ctx *ctx)
+{
+    PgLoss l;
+    if (ctx->pg_loss != MVS_PG_LOSS_NONE)
+        l.loss = ctx->pg_loss, l.k = ctx->pg_loss_k, l.first = ctx->pg_loss_first;
+    return l;
+}
+
+static PgCfg to_pg_cfg(const mvs_pose_graph_params &p, const PgLoss &loss)
 {
     PgCfg c{};
+    c.loss = loss.loss, c.loss_first = loss.first, c.loss_k = loss.k;
     c.max_iterations = p.lm.max_iterations;
     c.lambda_initial = p.lm.lambda_initial;
     c.lambda_factor = p.lm.lambda_factor;
@@ -152,8 +179,8 @@ static size_t pg_large_scratch(size_t N, size_t E, const PgdPlan *plan)
 static mvs_status pose_graph_large_dev(mvs_ctx *ctx, char *base, int n_nodes, int n_edges, int anchor, const int32_t *h_src,
                                        const int32_t *h_dst, const int32_t *d_src, const int32_t *d_dst, const double *d_node,
                                        const double *d_z, const double *d_cov, const mvs_pose_graph_params &params,
-                                       mvs_pose_graph_result *res, double *poses_out, hipMemcpyKind out_kind,
-                                       const PgdPlan *plan = nullptr)
+                                       const PgLoss &loss, mvs_pose_graph_result *res, double *poses_out,
+                                       hipMemcpyKind out_kind, const PgdPlan *plan = nullptr)
 {
     const size_t N = (size_t)n_nodes, E = (size_t)n_edges;
     std::vector<int32_t> off, inc;
@@ -168,7 +195,7 @@ static mvs_status pose_graph_large_dev(mvs_ctx *ctx, char *base, int n_nodes, in
     auto ip = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o); };
     PgLargeDev d{};
     d.n_nodes = n_nodes, d.n_edges = n_edges, d.anchor = anchor;
-    d.cfg = to_pg_cfg(params);
+    d.cfg = to_pg_cfg(params, loss);
     d.edge_src = d_src, d.edge_dst = d_dst, d.csr_off = ip(L.o_off), d.csr_inc = ip(L.o_inc);
     d.edge_pose = d_z, d.edge_cov = d_cov, d.pose0 = d_node;
     d.pose[0] = dp(L.o_pa), d.pose[1] = dp(L.o_pb);
@@ -374,7 +401,7 @@ static mvs_status pose_graph_large(mvs_ctx *ctx, const mvs_pose_graph &g, const 
     if (st != MVS_OK)
         return st;
     return pose_graph_large_dev(ctx, u.scratch, g.n_nodes, g.n_edges, g.anchor_node, g.edge_src, g.edge_dst, u.src, u.dst, u.node,
-                                u.z, u.cov, params, res, poses_out, hipMemcpyDeviceToHost, plan);
+                                u.z, u.cov, params, ctx_loss(ctx), res, poses_out, hipMemcpyDeviceToHost, plan);
 }
 
 // scratch of a dense-path batch of G graphs with sumN nodes and sumE edges.  Outputs first and contiguous (results,
@@ -393,12 +420,13 @@ struct PgDenseLayout {
 
 // graphs of up to 16 nodes over device-resident inputs: one launch.  `base`: scratch of PgDenseLayout::total bytes.
 static mvs_status pose_graph_dense_dev(mvs_ctx *ctx, char *base, const PgDenseLayout &L, int n_graphs,
-                                       const mvs_pose_graph_params &params, const PgProblem *d_prob, const double *d_node,
-                                       const int32_t *d_src, const int32_t *d_dst, const double *d_z, const double *d_cov)
+                                       const mvs_pose_graph_params &params, const PgLoss &loss, const PgProblem *d_prob,
+                                       const double *d_node, const int32_t *d_src, const int32_t *d_dst, const double *d_z,
+                                       const double *d_cov)
 {
     PgDenseDev d{};
     d.n_problems = n_graphs;
-    d.cfg = to_pg_cfg(params);
+    d.cfg = to_pg_cfg(params, loss);
     d.prob = d_prob;
     d.node_pose = d_node;
     d.edge_pose = d_z;
@@ -427,7 +455,7 @@ mvs_status mvs_pose_graph_optimize_batch(mvs_ctx *ctx, const mvs_pose_graph *gra
 {
     if (!ctx || !graphs || n_graphs < 1 || !params || !results || !poses_out)
         return MVS_ERR_INVALID_ARG;
-    if (!pose_graph_params_ok(params))
+    if (!pose_graph_params_ok(params) || !loss_fits_host_graph(ctx->pg_loss, ctx->pg_loss_first))
         return MVS_ERR_INVALID_ARG;
     int Nmax = 0;
     for (int i = 0; i < n_graphs; ++i) {
@@ -497,8 +525,9 @@ mvs_status mvs_pose_graph_optimize_batch(mvs_ctx *ctx, const mvs_pose_graph *gra
         HIP_TRY(ctx, hipMemcpyAsync(base + o_up, up.data(), up.size(), hipMemcpyHostToDevice, s));
         auto dp = [&](size_t o) { return reinterpret_cast<const double *>(base + o_up + o); };
         auto ip = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o_up + o); };
-        st = pose_graph_dense_dev(ctx, base, L, (int)G, *params, reinterpret_cast<const PgProblem *>(base + o_up + u_desc),
-                                  dp(u_np), ip(u_src), ip(u_dst), dp(u_z), dp(u_cov));
+        st = pose_graph_dense_dev(ctx, base, L, (int)G, *params, ctx_loss(ctx),
+                                  reinterpret_cast<const PgProblem *>(base + o_up + u_desc), dp(u_np), ip(u_src), ip(u_dst), dp(u_z),
+                                  dp(u_cov));
         if (st != MVS_OK)
             return st;
         std::vector<char> host(L.down);
@@ -609,6 +638,26 @@ static mvs_status seq_graph_head(mvs_seq *q, const char *caller, SeqGraphHead &h
     return MVS_OK;
 }
 
+// The context's loss for q's resident graph of E edges: MVS_PG_LOSS_LOOP_EDGES becomes the number of edges the graph had
+// before mvs_seq_add_loop_edges, the word the block keeps for that call (none added: E, so that no edge has the loss).
+static mvs_status seq_graph_loss(mvs_seq *q, const char *caller, int32_t E, PgLoss &loss)
+{
+    mvs_ctx *ctx = q->ctx;
+    loss = ctx_loss(ctx);
+    if (loss.loss == MVS_PG_LOSS_NONE || loss.first != MVS_PG_LOSS_LOOP_EDGES)
+        return MVS_OK;
+    loss.first = E;
+    if (!q->loop_edges_added)
+        return MVS_OK;
+    HIP_TRY(ctx, hipMemcpyAsync(&loss.first, q->graph_n_built, sizeof(int32_t), hipMemcpyDeviceToHost, ctx_stream(ctx)));
+    HIP_TRY(ctx, sync_stream(ctx));
+    if (loss.first < 0 || loss.first > E) {
+        ctx->err = std::string(caller) + ": the resident graph's count of built edges is out of range";
+        return MVS_ERR_HIP;
+    }
+    return MVS_OK;
+}
+
 mvs_status mvs_seq_build_pose_graph(mvs_seq *q, const mvs_seq_graph_params *p)
 {
     if (!q || !p || p->max_lag < 1 || p->max_lag >= q->n_frames || p->min_points < 0 || !(p->max_error >= 0.0) ||
@@ -663,6 +712,9 @@ mvs_status mvs_seq_optimize_pose_graph(mvs_seq *q, const mvs_pose_graph_params *
     if (st != MVS_OK)
         return st;
     const int N = g.n_frames, E = head.n_edges;
+    PgLoss loss;
+    if ((st = seq_graph_loss(q, "mvs_seq_optimize_pose_graph", E, loss)) != MVS_OK)
+        return st;
     PgdPlan plan;
     const bool direct = ctx->pg_solver == MVS_PG_SOLVER_DIRECT && N > kPgDenseMaxNodes;
     if (direct && (st = pgd_plan(N, E, 0, head.src, head.dst, plan)) != MVS_OK)
@@ -678,7 +730,7 @@ mvs_status mvs_seq_optimize_pose_graph(mvs_seq *q, const mvs_pose_graph_params *
             return st;
         char *base = ctx->pg.ptr();
         HIP_TRY(ctx, hipMemcpyAsync(base + o_desc, &pr, sizeof(pr), hipMemcpyHostToDevice, s));
-        st = pose_graph_dense_dev(ctx, base, L, 1, *params, reinterpret_cast<const PgProblem *>(base + o_desc), g.node_pose,
+        st = pose_graph_dense_dev(ctx, base, L, 1, *params, loss, reinterpret_cast<const PgProblem *>(base + o_desc), g.node_pose,
                                   g.edge_src, g.edge_dst, g.edge_pose, g.edge_cov);
         if (st != MVS_OK)
             return st;
@@ -690,7 +742,8 @@ mvs_status mvs_seq_optimize_pose_graph(mvs_seq *q, const mvs_pose_graph_params *
         if ((st = ws_grow(ctx, ctx->pg, pg_large_scratch((size_t)N, (size_t)E, direct ? &plan : nullptr))) != MVS_OK)
             return st;
         st = pose_graph_large_dev(ctx, ctx->pg.ptr(), N, E, 0, head.src, head.dst, g.edge_src, g.edge_dst, g.node_pose, g.edge_pose,
-                                  g.edge_cov, *params, result, q->graph_opt_pose, hipMemcpyDeviceToDevice, direct ? &plan : nullptr);
+                                  g.edge_cov, *params, loss, result, q->graph_opt_pose, hipMemcpyDeviceToDevice,
+                                  direct ? &plan : nullptr);
         if (st != MVS_OK)
             return st;
     }
@@ -890,6 +943,94 @@ mvs_status mvs_seq_pose_graph_marginals(mvs_seq *q, const double anchor_sigma[2]
         return st;
     return pgm_run(ctx, ctx->pgm.ptr(), L, P, N, E, 0, g.edge_src, g.edge_dst, g.node_pose, q->graph_opt_pose, g.edge_pose,
                    g.edge_cov, anchor_sigma, cov_out, info);
+}
+
+// ---- per-edge residuals and weights (pg_edge_stats_kernel) ----------------------------------------
+// scratch of the stats launch for E edges, as offsets from one base: the outputs first and contiguous
+struct PgStatsLayout {
+    size_t o_chi2, o_weight, o_bad, o_W, total;
+    explicit PgStatsLayout(size_t E)
+    {
+        Carve L{64};
+        o_chi2 = L.take(E * 8), o_weight = L.take(E * 8), o_bad = L.take(4), o_W = L.take(E * 21 * 8);
+        total = L.total();
+    }
+};
+
+// the launch over a device-resident graph and poses d_X, and the download; `base`: scratch of PgStatsLayout(E).total bytes.
+// MVS_NO_MODEL, nothing written: an edge covariance that is not positive definite.
+static mvs_status pg_stats_run(mvs_ctx *ctx, char *base, int E, const PgLoss &loss, const int32_t *d_src, const int32_t *d_dst,
+                               const double *d_z, const double *d_cov, const double *d_X, double *chi2, double *weight)
+{
+    if (E == 0)
+        return MVS_OK;
+    const PgStatsLayout L((size_t)E);
+    hipStream_t s = ctx_stream(ctx);
+    HIP_TRY(ctx, hipMemsetAsync(base + L.o_bad, 0, 4, s));
+    PgStatsDev d{};
+    d.n_edges = E;
+    d.cfg.loss = loss.loss, d.cfg.loss_first = loss.first, d.cfg.loss_k = loss.k;
+    d.edge_src = d_src, d.edge_dst = d_dst, d.edge_pose = d_z, d.edge_cov = d_cov, d.X = d_X;
+    d.W = reinterpret_cast<double *>(base + L.o_W);
+    d.chi2 = reinterpret_cast<double *>(base + L.o_chi2);
+    d.weight = weight ? reinterpret_cast<double *>(base + L.o_weight) : nullptr;
+    d.bad_cov = reinterpret_cast<int32_t *>(base + L.o_bad);
+    launch_pg_edge_stats(d, s);
+    HIP_TRY(ctx, hipGetLastError());
+    int32_t bad = 0;
+    std::vector<double> host(2 * (size_t)E);
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, d.bad_cov, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(host.data(), d.chi2, (size_t)E * 8, hipMemcpyDeviceToHost, s));
+    if (weight)
+        HIP_TRY(ctx, hipMemcpyAsync(host.data() + E, d.weight, (size_t)E * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    if (bad)
+        return MVS_NO_MODEL;
+    std::memcpy(chi2, host.data(), (size_t)E * 8);
+    if (weight)
+        std::memcpy(weight, host.data() + E, (size_t)E * 8);
+    return MVS_OK;
+}
+
+mvs_status mvs_pose_graph_edge_stats(mvs_ctx *ctx, const mvs_pose_graph *graph, const double *poses, double *chi2, double *weight)
+{
+    if (!ctx || !graph || !chi2 || !loss_fits_host_graph(ctx->pg_loss, ctx->pg_loss_first))
+        return MVS_ERR_INVALID_ARG;
+    const mvs_pose_graph &g = *graph;
+    mvs_status st = pose_graph_check(g);
+    if (st != MVS_OK)
+        return st;
+    if (poses && !all_finite(poses, 12 * (size_t)g.n_nodes))
+        return MVS_ERR_INVALID_ARG;
+    if (!pose_graph_connected(g.n_nodes, g.n_edges, g.edge_src, g.edge_dst, g.anchor_node))
+        return MVS_NO_MODEL;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PgUploaded u;
+    if ((st = pose_graph_upload(ctx, ctx->pg, g, poses ? poses : g.node_pose, PgStatsLayout((size_t)g.n_edges).total, u)) != MVS_OK)
+        return st;
+    return pg_stats_run(ctx, u.scratch, g.n_edges, ctx_loss(ctx), u.src, u.dst, u.z, u.cov, u.x, chi2, weight);
+}
+
+mvs_status mvs_seq_pose_graph_edge_stats(mvs_seq *q, double *chi2, double *weight)
+{
+    if (!q || !q->graph_built || !q->graph_opt || !chi2)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const SeqGraphDev &g = q->gd;
+    SeqGraphHead head;
+    mvs_status st = seq_graph_head(q, "mvs_seq_pose_graph_edge_stats", head);
+    if (st != MVS_OK)
+        return st;
+    const int N = g.n_frames, E = head.n_edges;
+    PgLoss loss;
+    if ((st = seq_graph_loss(q, "mvs_seq_pose_graph_edge_stats", E, loss)) != MVS_OK)
+        return st;
+    if (!pose_graph_connected(N, E, head.src, head.dst, 0))
+        return MVS_NO_MODEL;
+    if ((st = ws_grow(ctx, ctx->pg, PgStatsLayout((size_t)E).total)) != MVS_OK)
+        return st;
+    return pg_stats_run(ctx, ctx->pg.ptr(), E, loss, g.edge_src, g.edge_dst, g.edge_pose, g.edge_cov, q->graph_opt_pose, chi2, weight);
 }
 
 // ---- loop closures of a resident sequence (loop.hip, seq_graph.hip) -----------------------------

@@ -51,7 +51,12 @@ struct mvs_ctx {
     bool half_batches = true;
     double e5_confidence = 0.0;   // mvs_ctx_set_essential_confidence: 0 = every hypothesis of the five-point RANSAC runs
     int pg_solver = MVS_PG_SOLVER_PCG;   // mvs_ctx_set_pose_graph_solver: the linear solver of the pose graphs' large path
-    bool pgd_ran = false;                // a graph has gone through the direct solver: pgd_info is that of the last one
+    // mvs_ctx_set_pose_graph_loss: the robust loss of the pose graphs' edges from pg_loss_first on (-1: the loop edges of a
+    // resident graph), its constant
+    int pg_loss = MVS_PG_LOSS_NONE;
+    double pg_loss_k = 1.0;
+    int32_t pg_loss_first = 0;
+    bool pgd_ran = false;               // a graph has gone through the direct solver: pgd_info is that of the last one
     mvs_pose_graph_direct_info pgd_info{};
     // n_run of the last single-shot five-point call: none yet, or that call failed before its RANSAC was enqueued (-1); in
     // e5_single_run (0: the host returned before the RANSAC -- fewer than eight matches, so 0 -- or the word was saved from a

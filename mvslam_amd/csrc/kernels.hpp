@@ -277,6 +277,10 @@ struct PgCfg {
     double w_anchor[2];                  // 1 / sigma^2 of the anchor prior: rotation, translation
     double cg_rel_tol;
     int cg_max_iterations;
+    // robust loss of the edges with index >= loss_first inside their graph (mvs_ctx_set_pose_graph_loss; DESIGN.md section
+    // 4.10.5): 0 none, 1 Huber, 2 Cauchy, with the constant loss_k.  0 runs the statements the kernels ran before there was one.
+    int loss, loss_first;
+    double loss_k;
 };
 struct PgProblem {       // one graph of a dense-path batch
     int32_t n_nodes, n_edges, anchor, reserved;
@@ -335,6 +339,20 @@ void launch_pg_cg(const PgLargeDev &d, double lam, int n, hipStream_t stream);
 void launch_pg_end(const PgLargeDev &d, int cur, hipStream_t stream);
 // begin without the PCG start: what the direct step (below) has in front of it
 void launch_pg_linearise(const PgLargeDev &d, int cur, bool first, hipStream_t stream);
+
+// per-edge residuals of one graph at the poses X (mvs_pose_graph_edge_stats): chi2[k] = |r_k|^2 of the whitened residual and,
+// with `weight`, w(chi2[k]) under cfg's loss (1 below cfg.loss_first).  Every pointer is device memory; W is scratch.
+struct PgStatsDev {
+    int n_edges;
+    PgCfg cfg;                   // loss, loss_first and loss_k are read
+    const int32_t *edge_src, *edge_dst;
+    const double *edge_pose, *edge_cov;
+    const double *X;             // [N][12]
+    double *W;                   // [E][21]
+    double *chi2, *weight;       // [E]; weight may be null
+    int32_t *bad_cov;            // set to 1 when an edge covariance is not positive definite (zeroed by the launch's caller)
+};
+void launch_pg_edge_stats(const PgStatsDev &d, hipStream_t stream);
 
 // ---- the direct LM step of the large path (pg_direct.hip) ------------------------------------
 // (H + lambda I) x = -g by a block-scaled skyline Cholesky.  The diagonal blocks D and the gradient g are pg_gather_kernel's;

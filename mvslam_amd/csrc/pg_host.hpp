@@ -1,6 +1,7 @@
 // pg_host.hpp -- what the host decides about a pose graph before anything is launched (capi_graph.hip; DESIGN.md section
-// 4.10): finite input, endpoints in range, connectivity, the incidence list of the large path.  Plain C++ with no HIP in it,
-// so that tests/cpp/pg_host_check.cpp can run it under the host sanitizers.
+// 4.10): finite input, endpoints in range, connectivity, the incidence list of the large path, the arguments of the robust
+// loss.  Plain C++ with no HIP in it, so that tests/cpp/pg_host_check.cpp and tests/cpp/pg_loss_args_check.cpp can run it under
+// the host sanitizers.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -15,6 +16,20 @@ inline bool all_finite(const double *v, size_t n)
         if (!std::isfinite(v[i]))
             return false;
     return true;
+}
+
+// mvs_ctx_set_pose_graph_loss's arguments: a loss of 0 (none), 1 (Huber) or 2 (Cauchy); with a loss, a constant k that is
+// finite and > 0; first_edge >= -1 (-1: the loop edges of a resident graph)
+inline bool loss_args_ok(int loss, double k, int32_t first_edge)
+{
+    if (loss < 0 || loss > 2 || first_edge < -1)
+        return false;
+    return loss == 0 || (std::isfinite(k) && k > 0.0);
+}
+// may a call on a host graph run under this setting?  It has no loop edges for first_edge = -1 to stand for.
+inline bool loss_fits_host_graph(int loss, int32_t first_edge)
+{
+    return loss == 0 || first_edge >= 0;
 }
 
 // every edge joins two different nodes of [0, n_nodes).  The two functions below index by the endpoints: they are called on

@@ -21,6 +21,10 @@
 // rejected candidate that did solve, the increase) of the error is within abs_tol or rel_tol * error, or lambda passes
 // lambda_upper, or after max_iterations linear solves.
 //
+// Robust edge losses (mvs_ctx_set_pose_graph_loss) enter through pg_loss alone: an edge's term of
+// the cost becomes rho2(|r|^2) and its linearisation is multiplied by sqrt(w), in pg_dense_kernel and pg_edge_kernel; every
+// other kernel, pg_direct.hip's included, reads what those two left.  Without a loss the kernels are the ones they were.
+//
 // so3_exp / so3_log / so3_jrinv / pose_prior / chol_packed / chol_solve are COPIES of the functions in refine.hip's
 // anonymous namespace (same statements, same order): moving them to device_math.hpp would recompile every refine kernel
 // from a different inclusion order, and keeping their resource figures identical to the parent build's could not be
@@ -286,6 +290,42 @@ __device__ __forceinline__ double sq6(const double (&r)[6])
     return fma(r[5], r[5], fma(r[4], r[4], fma(r[3], r[3], fma(r[2], r[2], fma(r[1], r[1], r[0] * r[0])))));
 }
 
+// ---- robust losses (mvs_ctx_set_pose_graph_loss) ----------------------------------------------
+// weight w(s) of a robustified edge from s = |r|^2 and x = sqrt(s): Huber 1 or k / x, Cauchy k^2 / (k^2 + s)
+__device__ __forceinline__ double pg_loss_weight(const PgCfg &cfg, double s, double x)
+{
+    const double k = cfg.loss_k;
+    if (cfg.loss == 1)
+        return x <= k ? 1.0 : k / x;
+    const double k2 = k * k;
+    return k2 / (k2 + s);
+}
+// edge k_index with s = |r|^2: rho2(s), its term of twice the cost, and sqrt(w(s)), the factor of its residual and Jacobians.
+// Below cfg.loss_first: s and 1.  The order is the contract's: one sqrt, one division (the Cauchy cost: log1p of one
+// quotient), one sqrt.
+__device__ __forceinline__ void pg_loss(const PgCfg &cfg, int k_index, double s, double &rho2, double &sqrt_w)
+{
+    rho2 = s;
+    sqrt_w = 1.0;
+    if (k_index < cfg.loss_first)
+        return;
+    const double k = cfg.loss_k, x = sqrt(s);
+    if (cfg.loss == 1) {
+        if (!(x <= k))
+            rho2 = (2.0 * k) * x - k * k;
+    } else {
+        const double k2 = k * k;
+        rho2 = k2 * log1p(s / k2);
+    }
+    sqrt_w = sqrt(pg_loss_weight(cfg, s, x));
+}
+// the linearised edge {r, A_src, A_dst} times sqrt(w): what makes the normal equations those of the reweighted problem
+__device__ __forceinline__ void pg_scale_lin(double *lin, double sqrt_w)
+{
+    for (int i = 0; i < kPgLin; ++i)
+        lin[i] = lin[i] * sqrt_w;
+}
+
 // column i of A . column j of B (A, B row-major 6 x 6)
 __device__ __forceinline__ double coldot(const double *A, int i, const double *B, int j)
 {
@@ -386,6 +426,8 @@ __device__ __forceinline__ double block_sum(double x, double *red)
 }
 
 // ---- dense path -------------------------------------------------------------------------------------------------------
+// LOSS: the context has a robust loss.  Without it the kernel holds the statements it held before there were losses.
+template <bool LOSS>
 __global__ __launch_bounds__(kPgThreads) void pg_dense_kernel(PgDenseDev d)
 {
     __shared__ double H[kPgDim * (kPgDim + 1) / 2];
@@ -426,13 +468,20 @@ __global__ __launch_bounds__(kPgThreads) void pg_dense_kernel(PgDenseDev d)
         return;
     }
 
-    // sum of the squared whitened residuals at ps (an LDS pose table), the same bits in every thread
+    // sum of the squared whitened residuals (under a loss: of rho2 of each) at ps (an LDS pose table), the same bits in
+    // every thread
     auto cost_at = [&](const double *ps) -> double {
         double c = 0.0;
         for (int k = tid; k < E; k += kPgThreads) {
             double r[6];
             edge_eval<false>(Z + 12 * (int64_t)k, W + 21 * (int64_t)k, ps + 12 * src[k], ps + 12 * dst[k], r, nullptr);
-            c = c + sq6(r);
+            if (LOSS) {
+                double rho2, sw;
+                pg_loss(cfg, k, sq6(r), rho2, sw);
+                c = c + rho2;
+            } else {
+                c = c + sq6(r);
+            }
         }
         return block_sum(c, red) + anchor_eval<false>(cfg, pose0 + 12 * P.anchor, ps + 12 * P.anchor, nullptr);
     };
@@ -451,6 +500,11 @@ __global__ __launch_bounds__(kPgThreads) void pg_dense_kernel(PgDenseDev d)
             double r[6];
             edge_eval<true>(Z + 12 * (int64_t)k, W + 21 * (int64_t)k, ps + 12 * src[k], ps + 12 * dst[k], r,
                             lin + (int64_t)kPgLin * k);
+            if (LOSS) {
+                double rho2, sw;
+                pg_loss(cfg, k, sq6(r), rho2, sw);
+                pg_scale_lin(lin + (int64_t)kPgLin * k, sw);
+            }
         }
         if (tid == 0)
             anchor_eval<true>(cfg, pose0 + 12 * P.anchor, ps + 12 * P.anchor, anc);
@@ -598,7 +652,9 @@ __global__ __launch_bounds__(kPgThreads) void pg_prep_kernel(PgLargeDev d)
         d.state->bad_cov = 1;   // every writer stores the same word (the host zeroes it before the launch)
 }
 
-template <bool JAC>
+// LOSS: as in pg_dense_kernel.  The PCG and the direct step read `lin` and `ecost` and nothing else of an edge, so the loss
+// reaches both through this kernel alone.
+template <bool JAC, bool LOSS>
 __global__ __launch_bounds__(kPgThreads) void pg_edge_kernel(PgLargeDev d, const double *ps)
 {
     const int k = blockIdx.x * kPgThreads + threadIdx.x;
@@ -607,8 +663,34 @@ __global__ __launch_bounds__(kPgThreads) void pg_edge_kernel(PgLargeDev d, const
     double r[6];
     edge_eval<JAC>(d.edge_pose + 12 * (int64_t)k, d.W + 21 * (int64_t)k, ps + 12 * (int64_t)d.edge_src[k],
                    ps + 12 * (int64_t)d.edge_dst[k], r, JAC ? d.lin + (int64_t)kPgLin * k : nullptr);
-    if (!JAC)
+    if (LOSS) {
+        double rho2, sw;
+        pg_loss(d.cfg, k, sq6(r), rho2, sw);
+        if (JAC)
+            pg_scale_lin(d.lin + (int64_t)kPgLin * k, sw);
+        else
+            d.ecost[k] = rho2;
+    } else if (!JAC) {
         d.ecost[k] = sq6(r);
+    }
+}
+
+// edge k at the poses d.X: chi2 = |r|^2 of its whitened residual and its weight under d.cfg's loss
+__global__ __launch_bounds__(kPgThreads) void pg_edge_stats_kernel(PgStatsDev d)
+{
+    const int k = blockIdx.x * kPgThreads + threadIdx.x;
+    if (k >= d.n_edges)
+        return;
+    double *W = d.W + 21 * (int64_t)k;
+    if (!edge_prep(d.edge_cov + 36 * (int64_t)k, W))
+        *d.bad_cov = 1;   // every writer stores the same word
+    double r[6];
+    edge_eval<false>(d.edge_pose + 12 * (int64_t)k, W, d.X + 12 * (int64_t)d.edge_src[k], d.X + 12 * (int64_t)d.edge_dst[k], r,
+                     nullptr);
+    const double s = sq6(r);
+    d.chi2[k] = s;
+    if (d.weight)
+        d.weight[k] = d.cfg.loss != 0 && k >= d.cfg.loss_first ? pg_loss_weight(d.cfg, s, sqrt(s)) : 1.0;
 }
 
 // sum of the edges' costs (thread t: edges t, t + 256, ... in order; then the workgroup tree) + the anchor -> *dst
@@ -858,7 +940,10 @@ void launch_pg_dense(const PgDenseDev &d, hipStream_t stream)
 {
     if (d.n_problems <= 0)
         return;
-    hipLaunchKernelGGL(pg_dense_kernel, dim3(d.n_problems), dim3(kPgThreads), 0, stream, d);
+    if (d.cfg.loss != 0)
+        hipLaunchKernelGGL(pg_dense_kernel<true>, dim3(d.n_problems), dim3(kPgThreads), 0, stream, d);
+    else
+        hipLaunchKernelGGL(pg_dense_kernel<false>, dim3(d.n_problems), dim3(kPgThreads), 0, stream, d);
 }
 
 void launch_pg_prep(const PgLargeDev &d, hipStream_t stream)
@@ -873,18 +958,26 @@ dim3 pg_edge_blocks(const PgLargeDev &d)
     const int eb = (d.n_edges + kPgThreads - 1) / kPgThreads;
     return dim3(eb > 0 ? eb : 1);
 }
+// pg_edge_kernel<JAC> at the poses ps, with or without the context's loss
+template <bool JAC>
+void launch_pg_edges(const PgLargeDev &d, const double *ps, hipStream_t stream)
+{
+    if (d.cfg.loss != 0)
+        hipLaunchKernelGGL((pg_edge_kernel<JAC, true>), pg_edge_blocks(d), dim3(kPgThreads), 0, stream, d, ps);
+    else
+        hipLaunchKernelGGL((pg_edge_kernel<JAC, false>), pg_edge_blocks(d), dim3(kPgThreads), 0, stream, d, ps);
+}
 }  // namespace
 
 void launch_pg_linearise(const PgLargeDev &d, int cur, bool first, hipStream_t stream)
 {
-    const dim3 eb = pg_edge_blocks(d);
     const dim3 nb((d.n_nodes + 63) / 64);
     const double *ps = d.pose[cur];
     if (first) {
-        hipLaunchKernelGGL(pg_edge_kernel<false>, eb, dim3(kPgThreads), 0, stream, d, ps);
+        launch_pg_edges<false>(d, ps, stream);
         hipLaunchKernelGGL(pg_cost_reduce_kernel, dim3(1), dim3(kPgThreads), 0, stream, d, ps, &d.state->cost0);
     }
-    hipLaunchKernelGGL(pg_edge_kernel<true>, eb, dim3(kPgThreads), 0, stream, d, ps);
+    launch_pg_edges<true>(d, ps, stream);
     hipLaunchKernelGGL(pg_gather_kernel, nb, dim3(64), 0, stream, d, ps);
 }
 
@@ -907,13 +1000,19 @@ void launch_pg_cg(const PgLargeDev &d, double lam, int n, hipStream_t stream)
 
 void launch_pg_end(const PgLargeDev &d, int cur, hipStream_t stream)
 {
-    const dim3 eb = pg_edge_blocks(d);
     const dim3 nb((d.n_nodes + 63) / 64);
     const double *ps = d.pose[cur];
     double *pn = d.pose[cur ^ 1];
     hipLaunchKernelGGL(pg_update_kernel, nb, dim3(64), 0, stream, d, ps, pn);
-    hipLaunchKernelGGL(pg_edge_kernel<false>, eb, dim3(kPgThreads), 0, stream, d, pn);
+    launch_pg_edges<false>(d, pn, stream);
     hipLaunchKernelGGL(pg_cost_reduce_kernel, dim3(1), dim3(kPgThreads), 0, stream, d, pn, &d.state->cand);
+}
+
+void launch_pg_edge_stats(const PgStatsDev &d, hipStream_t stream)
+{
+    if (d.n_edges <= 0)
+        return;
+    hipLaunchKernelGGL(pg_edge_stats_kernel, dim3((d.n_edges + kPgThreads - 1) / kPgThreads), dim3(kPgThreads), 0, stream, d);
 }
 
 }  // namespace mvs
