@@ -164,3 +164,16 @@ def check_batch_against_oracle(data, out, prm, n1=None, n2=None, n_threads=1):
             assert rel_err(out["points"][i][:n], ref["points"]) <= TIGHT
             assert rel_err(r["R"], ref["R"]) <= TIGHT and rel_err(r["t"], ref["t"]) <= TIGHT
     return refs
+
+
+def check_two_view(got, ref, m):
+    assert got["ok"] == ref["ok"]
+    assert got["best_hyp"] == ref["best_hyp"] and got["best_count"] == ref["best_count"]
+    assert np.array_equal(got["mask"], ref["mask"][:m])                  # inlier indices: bit-exact
+    if ref["ok"]:
+        assert np.array_equal(got["point_idx"], ref["point_idx"])         # surviving indices: bit-exact
+        for k in ("R", "t", "E", "F", "R1to2", "t1to2"):
+            assert rel_err(got[k], ref[k]) <= REL_TOL, k
+            assert rel_err(got[k], ref[k]) <= TIGHT, k
+        assert rel_err(got["points"], ref["points"]) <= REL_TOL
+        assert rel_err(got["points"], ref["points"]) <= TIGHT

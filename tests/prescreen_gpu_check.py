@@ -44,6 +44,107 @@ def adversarial(data, rng):
     return data
 
 
+def check_pair_records(lib, b, p, H, pmode, thr, p1, p2, seed, stats):
+    """pair p of a batch whose records mvs_debug_prescreen_only(pmode) has just written; p1, p2: the pair's normalised points
+    [M][2], seed: its sampler key.  Every hypothesis: state 0 exactly when the oracle rejects the sample; a certified record's
+    band covers | r_i(F_J) - r_i(F~) | and U >= count_J >= L (violations are counted in stats, not raised)."""
+    M = len(p1)
+    rec = np.zeros((H, 10))
+    state = np.zeros(H, dtype=np.uint8)
+    info = (C.c_int32 * 4)()
+    st = lib.mvs_debug_read_hyp_rec(b._h, C.c_int(p), C.c_int(H), rec.ctypes.data_as(C.POINTER(C.c_double)),
+                                    state.ctypes.data_as(C.POINTER(C.c_ubyte)), None, info)
+    assert st == 0 and info[0] == pmode
+    rec32 = rec.view(np.float32).reshape(H, 20)
+    # single precision: the device evaluates the fma chain in binary32 on the rounded points
+    q1, q2 = p1.astype(np.float32).astype(np.float64), p2.astype(np.float32).astype(np.float64)
+    a1 = np.c_[np.abs(q1), np.ones(M)]
+    a2 = np.c_[np.abs(q2), np.ones(M)]
+    for h in range(H):
+        idx = o.sample8(seed, h, M)
+        ok, FJ = o.find_fundamental_matrix(p1[idx], p2[idx])
+        stats["hyp"] += 1
+        assert (state[h] == 0) == (not ok), (p, h, state[h], ok)
+        if state[h] == 0:
+            stats["invalid"] += 1
+            continue
+        if state[h] == 2:
+            stats["need_exact"] += 1
+            continue
+        assert state[h] == 1
+        stats["certified"] += 1
+        rj = pm.residuals(FJ, p1, p2)
+        cj = int((rj < thr).sum())
+        if pmode == 2:
+            band = rec[h, 9] - thr
+            assert 0 < band <= pm.BAND_FRAC * thr * (1 + 1e-12), (p, h, band)
+            ra = pm.residuals(rec[h, :9].reshape(3, 3), p1, p2)
+            d = float(np.abs(rj - ra).max())
+            cu, cl = int((ra < thr + band).sum()), int((ra < thr - band).sum())
+        else:
+            F32 = rec32[h, :9].astype(np.float64).reshape(3, 3)
+            tu, tl = float(rec32[h, 9]), float(rec32[h, 10])
+            band = tu - thr if tl <= 0.0 else min(tu - thr, thr - tl)   # (tl is clamped at 0 for bands beyond thr)
+            assert 0 < band <= pm.BAND_FRAC * thr * (1 + 1e-5), (p, h, band)
+            ra = pm.residuals(F32, q1, q2)      # binary64 evaluation of the binary32 operands ...
+            T = np.einsum("ij,jk,ik->i", a2, np.abs(F32), a1)
+            # ... + the arithmetic roundings of binary32: four nested fma, or (matrix cores) the rounded
+            # monomial and an fmaf chain over ten k
+            d = float((np.abs(rj - ra) + 11.01 * 2.0 ** -24 * T).max())
+            slack = 11.01 * 2.0 ** -24 * T
+            cu, cl = int((ra - slack < tu).sum()), int((ra + slack < tl).sum())
+        stats["worst_ratio"] = max(stats["worst_ratio"], d / band)
+        if d > band:
+            stats["viol"] += 1
+        if not (cu >= cj >= cl):
+            stats["count_viol"] += 1
+
+
+def run_every_mode(lib, b, run, stats):
+    """the whole stage with every pair forced exact (0), forced pre-screened (1, 2), with the probe deciding (-1), and mode 1
+    with the two matrix-core counting variants (101, 102); run(): one run of the batch.  Returns the six downloads; the work
+    list lengths go into stats.  The switches are left at (forced 1, variant 102 - 100): callers reset them."""
+    outs = []
+    # 101: mode 1 with the counting as pilot + dense matrix-core phase + matrix-core finish (the default), 102: the same
+    # with the vector finish; the others count with one ransac_count32 / ransac_count2 launch
+    for mode in (0, 1, 2, -1, 101, 102):
+        lib.mvs_debug_set_count_dense(C.c_int(mode - 100 if mode > 100 else 0))
+        mode = 1 if mode > 100 else mode
+        lib.mvs_debug_set_prescreen_force(C.c_int(mode))
+        run()
+        b.sync()
+        outs.append(b.download())
+        info = (C.c_int32 * 4)()
+        lib.mvs_debug_read_hyp_rec(b._h, C.c_int(0), C.c_int(1), None, None, None, info)
+        stats["mode%d_list" % mode if mode >= 0 else "auto_list"] = [int(info[2]), int(info[3])]
+    return outs
+
+
+def assert_modes_equal(outs, thr):
+    for k in ("results", "mask", "points", "point_idx", "matches"):
+        assert all(outs[0][k].tobytes() == o_[k].tobytes() for o_ in outs[1:]), ("modes differ", thr, k)
+
+
+def check_dense_counts(lib, b, p, H, thr, p1, p2, result, stats):
+    """pair p after a run with the default counting variant and every pair pre-screened: the pair's bound is a maximum of
+    LOWER bounds L' <= count_J, so it cannot exceed the winner's exact count; and every approximate record that reached the
+    exact solve carries its UPPER bound U' >= count_J in hyp_cnt (the record now holds the exact F: count it)"""
+    rec = np.zeros((H, 10))
+    state = np.zeros(H, dtype=np.uint8)
+    cnt = np.zeros(H, dtype=np.int32)
+    info = (C.c_int32 * 4)()
+    st = lib.mvs_debug_read_hyp_rec(b._h, C.c_int(p), C.c_int(H), rec.ctypes.data_as(C.POINTER(C.c_double)),
+                                    state.ctypes.data_as(C.POINTER(C.c_ubyte)), cnt.ctypes.data_as(C.POINTER(C.c_int32)), info)
+    assert st == 0 and info[0] == 1
+    if result["valid"]:
+        assert info[1] <= result["best_count"], (p, thr, info[1], int(result["best_count"]))
+    for h in np.nonzero((state == 3) & (cnt >= 0) & (cnt < 2 ** 31 - 1))[0]:
+        cj_lo = int((pm.residuals(rec[h, :9].reshape(3, 3), p1, p2) < thr * (1 - 1e-9)).sum())
+        stats["mfma_checked"] = stats.get("mfma_checked", 0) + 1
+        if cnt[h] < cj_lo:
+            stats["count_viol"] += 1
+
+
 def main():
     P, N, H = 8, 600, 1536
     thr_list = [1e-2, 1e-3]
@@ -58,6 +159,14 @@ def main():
     b = capi.Batch(ctx, P, N, 32)
     b.upload(0, data["desc1"], data["kp1"], data["n1"], data["desc2"], data["kp2"], data["n2"], data["K"], data["global_index"])
     stats = dict(hyp=0, invalid=0, certified=0, need_exact=0, worst_ratio=0.0, viol=0, count_viol=0)
+
+    def points_of(out, p):
+        M = int(out["results"][p]["n_matches"])
+        mt = out["matches"][p][:M]
+        K = data["K"][p].reshape(3, 3)
+        return (o.normalize_points(K, data["kp1"][p][mt["trainIdx"]].astype(np.float64)),
+                o.normalize_points(K, data["kp2"][p][mt["queryIdx"]].astype(np.float64)))
+
     for thr in thr_list:
         prm = capi.default_params(num_hypotheses=H, sampler=capi.SAMPLER_PHILOX, seed=synth.SEED_BASE, max_error_sq=thr)
         b.run(prm)
@@ -67,111 +176,26 @@ def main():
             st = lib.mvs_debug_prescreen_only(b._h, C.byref(prm), C.c_int(P), C.c_int(pmode))
             assert st == 0, st
             for p in range(P):
-                M = int(base["results"][p]["n_matches"])
-                if M < 8:
+                if int(base["results"][p]["n_matches"]) < 8:
                     continue
-                mt = base["matches"][p][:M]
-                K = data["K"][p].reshape(3, 3)
-                p1 = o.normalize_points(K, data["kp1"][p][mt["trainIdx"]].astype(np.float64))
-                p2 = o.normalize_points(K, data["kp2"][p][mt["queryIdx"]].astype(np.float64))
-                rec = np.zeros((H, 10))
-                state = np.zeros(H, dtype=np.uint8)
-                info = (C.c_int32 * 4)()
-                st = lib.mvs_debug_read_hyp_rec(b._h, C.c_int(p), C.c_int(H), rec.ctypes.data_as(C.POINTER(C.c_double)),
-                                                state.ctypes.data_as(C.POINTER(C.c_ubyte)), None, info)
-                assert st == 0 and info[0] == pmode
-                rec32 = rec.view(np.float32).reshape(H, 20)
-                # single precision: the device evaluates the fma chain in binary32 on the rounded points
-                q1, q2 = p1.astype(np.float32).astype(np.float64), p2.astype(np.float32).astype(np.float64)
-                a1 = np.c_[np.abs(q1), np.ones(M)]
-                a2 = np.c_[np.abs(q2), np.ones(M)]
-                seed = synth.SEED_BASE + int(data["global_index"][p])
-                for h in range(H):
-                    idx = o.sample8(seed, h, M)
-                    ok, FJ = o.find_fundamental_matrix(p1[idx], p2[idx])
-                    stats["hyp"] += 1
-                    assert (state[h] == 0) == (not ok), (p, h, state[h], ok)
-                    if state[h] == 0:
-                        stats["invalid"] += 1
-                        continue
-                    if state[h] == 2:
-                        stats["need_exact"] += 1
-                        continue
-                    assert state[h] == 1
-                    stats["certified"] += 1
-                    rj = pm.residuals(FJ, p1, p2)
-                    cj = int((rj < thr).sum())
-                    if pmode == 2:
-                        band = rec[h, 9] - thr
-                        assert 0 < band <= pm.BAND_FRAC * thr * (1 + 1e-12), (p, h, band)
-                        ra = pm.residuals(rec[h, :9].reshape(3, 3), p1, p2)
-                        d = float(np.abs(rj - ra).max())
-                        cu, cl = int((ra < thr + band).sum()), int((ra < thr - band).sum())
-                    else:
-                        F32 = rec32[h, :9].astype(np.float64).reshape(3, 3)
-                        tu, tl = float(rec32[h, 9]), float(rec32[h, 10])
-                        band = tu - thr if tl <= 0.0 else min(tu - thr, thr - tl)   # (tl is clamped at 0 for bands beyond thr)
-                        assert 0 < band <= pm.BAND_FRAC * thr * (1 + 1e-5), (p, h, band)
-                        ra = pm.residuals(F32, q1, q2)      # binary64 evaluation of the binary32 operands ...
-                        T = np.einsum("ij,jk,ik->i", a2, np.abs(F32), a1)
-                        # ... + the arithmetic roundings of binary32: four nested fma, or (matrix cores) the rounded
-                        # monomial and an fmaf chain over ten k
-                        d = float((np.abs(rj - ra) + 11.01 * 2.0 ** -24 * T).max())
-                        slack = 11.01 * 2.0 ** -24 * T
-                        cu, cl = int((ra - slack < tu).sum()), int((ra + slack < tl).sum())
-                    stats["worst_ratio"] = max(stats["worst_ratio"], d / band)
-                    if d > band:
-                        stats["viol"] += 1
-                    if not (cu >= cj >= cl):
-                        stats["count_viol"] += 1
+                p1, p2 = points_of(base, p)
+                check_pair_records(lib, b, p, H, pmode, thr, p1, p2, synth.SEED_BASE + int(data["global_index"][p]), stats)
         # the whole stage: every pair exact / every pair pre-screened / the probe decides
-        outs = []
-        # 101: mode 1 with the counting as pilot + dense matrix-core phase + matrix-core finish (the default), 102: the same
-        # with the vector finish; the others count with one ransac_count32 / ransac_count2 launch
-        for mode in (0, 1, 2, -1, 101, 102):
-            lib.mvs_debug_set_count_dense(C.c_int(mode - 100 if mode > 100 else 0))
-            mode = 1 if mode > 100 else mode
-            lib.mvs_debug_set_prescreen_force(C.c_int(mode))
-            b.run(prm)
-            b.sync()
-            outs.append(b.download())
-            info = (C.c_int32 * 4)()
-            lib.mvs_debug_read_hyp_rec(b._h, C.c_int(0), C.c_int(1), None, None, None, info)
-            stats["mode%d_list" % mode if mode >= 0 else "auto_list"] = [int(info[2]), int(info[3])]
-        # the matrix-core counts themselves (default variant, every pair pre-screened): the pair's bound is a maximum of LOWER
-        # bounds L' <= count_J, so it cannot exceed the winner's exact count; and every approximate record that reached the
-        # exact solve carries its UPPER bound U' >= count_J in hyp_cnt (the record now holds the exact F: count it)
+        outs = run_every_mode(lib, b, lambda: b.run(prm), stats)
+        # the matrix-core counts themselves (default variant, every pair pre-screened)
         lib.mvs_debug_set_count_dense(C.c_int(1))
         lib.mvs_debug_set_prescreen_force(C.c_int(1))
         b.run(prm)
         b.sync()
         chk = b.download()
         for p in range(P):
-            M = int(chk["results"][p]["n_matches"])
-            if M < 8:
+            if int(chk["results"][p]["n_matches"]) < 8:
                 continue
-            mt = chk["matches"][p][:M]
-            K = data["K"][p].reshape(3, 3)
-            p1 = o.normalize_points(K, data["kp1"][p][mt["trainIdx"]].astype(np.float64))
-            p2 = o.normalize_points(K, data["kp2"][p][mt["queryIdx"]].astype(np.float64))
-            rec = np.zeros((H, 10))
-            state = np.zeros(H, dtype=np.uint8)
-            cnt = np.zeros(H, dtype=np.int32)
-            info = (C.c_int32 * 4)()
-            st = lib.mvs_debug_read_hyp_rec(b._h, C.c_int(p), C.c_int(H), rec.ctypes.data_as(C.POINTER(C.c_double)),
-                                            state.ctypes.data_as(C.POINTER(C.c_ubyte)), cnt.ctypes.data_as(C.POINTER(C.c_int32)), info)
-            assert st == 0 and info[0] == 1
-            if chk["results"][p]["valid"]:
-                assert info[1] <= chk["results"][p]["best_count"], (p, thr, info[1], int(chk["results"][p]["best_count"]))
-            for h in np.nonzero((state == 3) & (cnt >= 0) & (cnt < 2 ** 31 - 1))[0]:
-                cj_lo = int((pm.residuals(rec[h, :9].reshape(3, 3), p1, p2) < thr * (1 - 1e-9)).sum())
-                stats["mfma_checked"] = stats.get("mfma_checked", 0) + 1
-                if cnt[h] < cj_lo:
-                    stats["count_viol"] += 1
+            p1, p2 = points_of(chk, p)
+            check_dense_counts(lib, b, p, H, thr, p1, p2, chk["results"][p], stats)
         lib.mvs_debug_set_prescreen_force(C.c_int(-1))
         lib.mvs_debug_set_count_dense(C.c_int(1))
-        for k in ("results", "mask", "points", "point_idx", "matches"):
-            assert all(outs[0][k].tobytes() == o_[k].tobytes() for o_ in outs[1:]), ("modes differ", thr, k)
+        assert_modes_equal(outs, thr)
         for p in range(P):
             ref = o.image_pair(data["desc1"][p], data["kp1"][p], data["desc2"][p], data["kp2"][p], data["K"][p].reshape(3, 3),
                                o.make_params(H, o.SAMPLER_PHILOX, synth.SEED_BASE + int(data["global_index"][p]), thr), 0.7, 10.0)

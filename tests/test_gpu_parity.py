@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 
 REL_TOL, TIGHT = helpers.REL_TOL, helpers.TIGHT
 _run_batch, _check_batch_against_oracle = helpers.run_batch, helpers.check_batch_against_oracle
+_check_two_view = helpers.check_two_view
 
 
 def _rand_desc(rng, n, nbytes=32):
@@ -291,19 +292,6 @@ def test_ransac_too_few_points(ctx):
 
 
 # ----------------------------------------------------------------------------- sfm_solve / triangulate KATs
-def _check_two_view(got, ref, m):
-    assert got["ok"] == ref["ok"]
-    assert got["best_hyp"] == ref["best_hyp"] and got["best_count"] == ref["best_count"]
-    assert np.array_equal(got["mask"], ref["mask"][:m])                  # inlier indices: bit-exact
-    if ref["ok"]:
-        assert np.array_equal(got["point_idx"], ref["point_idx"])         # surviving indices: bit-exact
-        for k in ("R", "t", "E", "F", "R1to2", "t1to2"):
-            assert helpers.rel_err(got[k], ref[k]) <= REL_TOL, k
-            assert helpers.rel_err(got[k], ref[k]) <= TIGHT, k
-        assert helpers.rel_err(got["points"], ref["points"]) <= REL_TOL
-        assert helpers.rel_err(got["points"], ref["points"]) <= TIGHT
-
-
 def test_sfm_solve_L_shape_kat(ctx):
     """test/test-sfm.cpp geometry with the L-shaped rig (the cube is degenerate for the 8-point solver,
     SURVEY section 0.3): pose.ln() == (1,0,0,0,0,0), the 8 points recovered in input order, tol 1e-3."""
