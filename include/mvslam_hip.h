@@ -579,6 +579,48 @@ mvs_status mvs_ba_refine_window(mvs_ctx *ctx, const mvs_ba_window *problem, cons
  * ok = 0 (frames_out[p * Fmax].ok tells which). */
 mvs_status mvs_ba_refine_windows(mvs_ctx *ctx, const mvs_ba_window *problems, int n_problems, const mvs_refine_params *params,
                                  mvs_refine_result *frames_out, double *points_out, double *point_cov_out);
+/* ba_frame_pose_and_point for 1 .. 4096 frames, fed as a SPARSE problem: every point lists the
+ * frames that observe it, so an observation a frame lacks is simply absent.  Cost, tangent order (rotation, translation; right
+ * perturbation) and LM rule are the window kernel's; the points are eliminated on the device, the reduced camera system is
+ * assembled into its block skyline (row i reaches back to the smallest frame that shares a point with frame i) and the LM step
+ * is the block-scaled skyline Cholesky of mvs_ctx_set_pose_graph_solver's direct solver; the host drives the lambda schedule
+ * with one synchronisation per iteration.  Tracks over consecutive frames give a band whose width is the longest track. */
+typedef struct mvs_ba_sparse {        /* all host pointers */
+    int32_t n_frames;                 /* 1 .. 4096 */
+    int32_t n_points;                 /* 1 .. 1 << 20 */
+    int32_t n_obs;                    /* 1 .. 1 << 23 */
+    int32_t reserved;
+    const double *K;                  /* 9, affine */
+    const double *frame_pose;         /* n_frames x 12, as mvs_ba_window */
+    const double *frame_prior_var;    /* n_frames x 6, <= 0: no prior on that coordinate */
+    const double *points;             /* n_points x 3 */
+    const double *point_prior_cov;    /* n_points x 9 or NULL; first entry <= 0: no prior */
+    const int32_t *obs_off;           /* n_points + 1: observations of point p are rows obs_off[p] .. obs_off[p+1]-1 */
+    const int32_t *obs_frame;         /* n_obs, strictly ascending within a point */
+    const double *obs_uv;             /* n_obs x 2 */
+    const double *obs_cov;            /* n_obs x 4 or NULL = identity */
+} mvs_ba_sparse;
+typedef struct mvs_ba_sparse_result {
+    int32_t ok, iterations, rejected_steps, failed_solves;
+    double error_initial, error;
+    int32_t envelope_blocks, widest_row;   /* of the reduced camera system */
+    int32_t bad_frame, reserved;           /* first failed pivot's frame, -1 */
+} mvs_ba_sparse_result;
+/* Every argument error is returned before anything runs.  MVS_ERR_INVALID_ARG: a null pointer (the optional ones apart), a
+ * non-finite input, obs_off that is not monotone from 0 to n_obs, obs_frame out of range or not strictly ascending within a
+ * point, refine parameters mvs_ba_refine refuses.  MVS_ERR_CAPACITY: the limits above, an envelope of more than 2^21 blocks
+ * (the skyline's limit, as for the pose graphs), or more than 2^28 pairs of observations that share a point, counted over all points (sum of t (t - 1) / 2
+ * over the tracks' lengths t: the term lists of the assembly).  MVS_NO_MODEL with ok = 0 and every output array untouched: at the estimate (lambda = 0) a point's 3 x 3 block or
+ * a pivot of the skyline fails the window kernel's pivot rule -- a gauge no prior fixes, a point with neither observation nor
+ * prior; `result` is still filled.  During the iterations such a failure raises lambda (failed_solves counts them).
+ * Outputs: poses_out n_frames x 12; points_out n_points x 3, pose_cov_out n_frames x 36 and point_cov_out n_points x 9 may be
+ * NULL (the covariance sweep runs only when one of the two is asked for).  Only the LM fields of params are read.  The same
+ * input gives the same bytes. */
+mvs_status mvs_ba_refine_sparse(mvs_ctx *ctx, const mvs_ba_sparse *problem, const mvs_refine_params *params,
+                                mvs_ba_sparse_result *result, double *poses_out /* n_frames x 12 */,
+                                double *points_out /* n_points x 3, may be NULL */,
+                                double *pose_cov_out /* n_frames x 36, may be NULL */,
+                                double *point_cov_out /* n_points x 9, may be NULL */);
 /* Batched ImagePair::refine (front-end/image-pair.cpp:176-238) on a batch that has been run: every valid pair is refined
  * from its own results on the device.  Observations = the matched keypoints with the covariance
  * VisualFeature::get_point_estimates gives them (vision/visual-feature.cpp:192-207): stddev = (1 << kp.octave) * 0.5 px,

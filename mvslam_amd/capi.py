@@ -98,6 +98,21 @@ class BaWindow(C.Structure):
                 ("obs_valid", C.POINTER(C.POINTER(C.c_uint8)))]
 
 
+class BaSparse(C.Structure):
+    """mvs_ba_sparse: a bundle adjustment of up to 4096 frames with the observations as a CSR by point"""
+    _fields_ = [("n_frames", C.c_int32), ("n_points", C.c_int32), ("n_obs", C.c_int32), ("reserved", C.c_int32),
+                ("K", C.POINTER(C.c_double)), ("frame_pose", C.POINTER(C.c_double)),
+                ("frame_prior_var", C.POINTER(C.c_double)), ("points", C.POINTER(C.c_double)),
+                ("point_prior_cov", C.POINTER(C.c_double)), ("obs_off", C.POINTER(C.c_int32)),
+                ("obs_frame", C.POINTER(C.c_int32)), ("obs_uv", C.POINTER(C.c_double)), ("obs_cov", C.POINTER(C.c_double))]
+
+
+class BaSparseResult(C.Structure):
+    _fields_ = [("ok", C.c_int32), ("iterations", C.c_int32), ("rejected_steps", C.c_int32), ("failed_solves", C.c_int32),
+                ("error_initial", C.c_double), ("error", C.c_double), ("envelope_blocks", C.c_int32),
+                ("widest_row", C.c_int32), ("bad_frame", C.c_int32), ("reserved", C.c_int32)]
+
+
 REFINE_DTYPE = np.dtype([("ok", "<i4"), ("iterations", "<i4"), ("error", "<f8"), ("R", "<f8", (3, 3)),
                          ("t", "<f8", (3,)), ("pose_cov", "<f8", (6, 6))])
 
@@ -252,7 +267,7 @@ EXPORTS = [
     "mvs_batch_upload_async", "mvs_batch_download_async", "mvs_host_alloc", "mvs_host_free", "mvs_image_pair",
     "mvs_batch_gather_results", "mvs_seq_time_stages", "mvs_batch_time_kernels", "mvs_kernel_info_get",
     "mvs_extract_time", "mvs_ctx_set_half_batches", "mvs_batch_device_state", "mvs_batch_run_points",
-    "mvs_ba_refine_window", "mvs_ba_refine_windows", "mvs_seq_refine_windows", "mvs_seq_window_count",
+    "mvs_ba_refine_window", "mvs_ba_refine_windows", "mvs_ba_refine_sparse", "mvs_seq_refine_windows", "mvs_seq_window_count",
     "mvs_seq_download_windows", "mvs_five_point", "mvs_ransac_essential", "mvs_two_view_essential",
     "mvs_batch_run_points_essential", "mvs_ctx_set_essential_confidence", "mvs_ctx_essential_hypotheses_run",
     "mvs_batch_download_hypotheses_run", "mvs_image_pair_essential", "mvs_batch_run_essential",
@@ -963,6 +978,42 @@ class Context:
         self._check(st, "mvs_ba_refine_window", allow_no_model=True)
         return dict(ok=st == MVS_OK, R=res["R"].copy(), t=res["t"].copy(), pose_cov=res["pose_cov"].copy(), points=pts[:m],
                     point_cov=ptc[:m], error=float(res["error"][0]), iterations=int(res["iterations"][0]), raw=res[:F].tobytes())
+
+    # ba_frame_pose_and_point on 1 .. 4096 frames, fed as a sparse problem
+    def ba_refine_sparse(self, K, frame_pose, frame_prior_var, points, point_prior_cov, obs_off, obs_frame, obs_uv, obs_cov=None,
+                         params=None, pose_cov=True, point_cov=True, n_frames=None):
+        """mvs_ba_refine_sparse.  obs_off [n_points + 1], obs_frame [n_obs] (ascending within a point), obs_uv [n_obs, 2],
+        obs_cov [n_obs, 4] or None.  Returns a dict: status (MVS_OK / MVS_NO_MODEL), ok, the result record's fields, R
+        [F, 3, 3], t [F, 3], points, pose_cov / point_cov (None when not asked for) and `raw`, the bytes of every output.  On
+        MVS_NO_MODEL the output arrays are as they were allocated (zero).  n_frames overrides the count taken from
+        frame_pose (the refusal tests)."""
+        params = params or default_refine_params()
+        fp, fv = _f64(frame_pose).reshape(-1, 12), _f64(frame_prior_var).reshape(-1, 6)
+        pg, Kc = _f64(points).reshape(-1, 3), _f64(K, (9,))
+        off = np.ascontiguousarray(obs_off, dtype=np.int32)
+        ofr = np.ascontiguousarray(obs_frame, dtype=np.int32)
+        uv = _f64(obs_uv).reshape(-1, 2)
+        F, m, n_obs = len(fp) if n_frames is None else n_frames, len(pg), len(ofr)
+        pb = BaSparse()
+        pb.n_frames, pb.n_points, pb.n_obs = F, m, n_obs
+        pb.K, pb.frame_pose, pb.frame_prior_var, pb.points = (_ptr(Kc, C.c_double), _ptr(fp, C.c_double), _ptr(fv, C.c_double),
+                                                              _ptr(pg, C.c_double))
+        pc = None if point_prior_cov is None else _f64(point_prior_cov, (m, 9))
+        oc = None if obs_cov is None else _f64(obs_cov, (n_obs, 4))
+        pb.point_prior_cov, pb.obs_cov = _ptr(pc, C.c_double), _ptr(oc, C.c_double)
+        pb.obs_off, pb.obs_frame, pb.obs_uv = _ptr(off, C.c_int32), _ptr(ofr, C.c_int32), _ptr(uv, C.c_double)
+        res = BaSparseResult()
+        poses, pts = np.zeros((max(F, 1), 12)), np.zeros((max(m, 1), 3))
+        pcv = np.zeros((max(F, 1), 6, 6)) if pose_cov else None
+        ptc = np.zeros((max(m, 1), 3, 3)) if point_cov else None
+        st = lib().mvs_ba_refine_sparse(self._h, C.byref(pb), C.byref(params), C.byref(res), _ptr(poses, C.c_double),
+                                        _ptr(pts, C.c_double), _ptr(pcv, C.c_double), _ptr(ptc, C.c_double))
+        self._check(st, "mvs_ba_refine_sparse", allow_no_model=True)
+        out = {k: getattr(res, k) for k, _ in BaSparseResult._fields_}
+        out.update(status=st, ok=bool(res.ok), R=poses[:, :9].reshape(-1, 3, 3).copy(), t=poses[:, 9:].copy(), points=pts,
+                   pose_cov=pcv, point_cov=ptc,
+                   raw=b"".join(a.tobytes() for a in (poses, pts, pcv, ptc) if a is not None) + bytes(res))
+        return out
 
     def find_fundamental_matrix(self, p1, p2):
         p1, p2 = _f64(p1, (16,)), _f64(p2, (16,))

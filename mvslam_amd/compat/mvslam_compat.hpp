@@ -766,8 +766,92 @@ public:
 };
 using PointIdToPoint2Estimate = std::unordered_map<Id::Type, Point2Estimate>;
 
-// Same signature as the reference.  Supported: one to eight frames (the reference itself builds one or two: sfm_refine,
-// pnp_refine, VisualOdometer::track_refine; more is a sliding window, mvs_ba_refine_window); diagonal frame priors.  With this one function forwarded,
+namespace hip {
+// ba_frame_pose_and_point on nine and more frames: the maps packed as an mvs_ba_sparse (the observations of every point in
+// ascending frame order) for mvs_ba_refine_sparse
+inline void ba_sparse_(const CameraIntrinsics &ci, const std::vector<Id::Type> &fids, const std::vector<Id::Type> &pids,
+                       const std::unordered_map<Id::Type, int> &pidx,
+                       const std::unordered_map<Id::Type, Transformation> &frame_pose_guess,
+                       const std::unordered_map<Id::Type, TransformationUncertainty> &frame_pose_prior,
+                       const std::unordered_map<Id::Type, Point3> &point_guess,
+                       const std::unordered_map<Id::Type, Point3Uncertainty> &point_prior,
+                       const std::unordered_map<Id::Type, PointIdToPoint2Estimate> &frame_observation,
+                       std::unordered_map<Id::Type, TransformationEstimate> &frame_pose_estimate,
+                       std::unordered_map<Id::Type, Point3Estimate> &point_estimate, ScalarType &final_error)
+{
+    const int F = (int)fids.size(), m = (int)pids.size();
+    std::vector<double> pose(12 * (size_t)F), var(6 * (size_t)F, 0.0), pts(3 * (size_t)m), pcov(9 * (size_t)m, 0.0);
+    std::vector<int32_t> off((size_t)m + 1, 0);
+    for (int f = 0; f < F; ++f) {
+        const Transformation &T = frame_pose_guess.at(fids[f]);
+        std::memcpy(&pose[12 * (size_t)f], T.rotation().get_matrix().m, 9 * sizeof(double));
+        std::memcpy(&pose[12 * (size_t)f + 9], T.translation().v, 3 * sizeof(double));
+        auto pr = frame_pose_prior.find(fids[f]);
+        if (pr != frame_pose_prior.end())
+            for (int k = 0; k < 6; ++k)
+                var[6 * (size_t)f + k] = pr->second(k, k);
+        auto ob = frame_observation.find(fids[f]);
+        if (ob != frame_observation.end())
+            for (const auto &kv : ob->second)
+                ++off[(size_t)pidx.at(kv.first) + 1];
+    }
+    for (int i = 0; i < m; ++i)
+        off[(size_t)i + 1] += off[(size_t)i];
+    const size_t n = (size_t)off[(size_t)m];
+    std::vector<int32_t> fr(n), at(off.begin(), off.end() - 1);
+    std::vector<double> uv(2 * n), cv(4 * n);
+    for (int f = 0; f < F; ++f) {   // frames ascend, so every point's list does
+        auto ob = frame_observation.find(fids[f]);
+        if (ob == frame_observation.end())
+            continue;
+        for (const auto &kv : ob->second) {
+            const size_t o = (size_t)at[(size_t)pidx.at(kv.first)]++;
+            fr[o] = f;
+            std::memcpy(&uv[2 * o], kv.second.mean().v, 2 * sizeof(double));
+            std::memcpy(&cv[4 * o], kv.second.covar().m, 4 * sizeof(double));
+        }
+    }
+    for (int i = 0; i < m; ++i) {
+        std::memcpy(&pts[3 * (size_t)i], point_guess.at(pids[i]).v, 3 * sizeof(double));
+        auto pr = point_prior.find(pids[i]);
+        if (pr != point_prior.end())
+            std::memcpy(&pcov[9 * (size_t)i], pr->second.m, 9 * sizeof(double));
+    }
+    mvs_ba_sparse pb;
+    std::memset(&pb, 0, sizeof(pb));
+    pb.n_frames = F, pb.n_points = m, pb.n_obs = (int32_t)n;
+    pb.K = ci.data();
+    pb.frame_pose = pose.data(), pb.frame_prior_var = var.data(), pb.points = pts.data(), pb.point_prior_cov = pcov.data();
+    pb.obs_off = off.data(), pb.obs_frame = fr.data(), pb.obs_uv = uv.data(), pb.obs_cov = cv.data();
+    mvs_ba_sparse_result res;
+    std::vector<double> po(12 * (size_t)F), pp(3 * (size_t)m), fc(36 * (size_t)F), pc(9 * (size_t)m);
+    const mvs_status st = mvs_ba_refine_sparse(context(), &pb, &refine_config(), &res, po.data(), pp.data(), fc.data(), pc.data());
+    check(st, "ba_frame_pose_and_point");
+    if (st != MVS_OK)
+        throw std::runtime_error("ba_frame_pose_and_point: indeterminate system");   // GTSAM throws here as well
+    frame_pose_estimate.clear();
+    for (int f = 0; f < F; ++f) {
+        mvs_refine_result r;
+        std::memset(&r, 0, sizeof(r));
+        r.ok = 1, r.iterations = res.iterations, r.error = res.error;
+        std::memcpy(r.R, &po[12 * (size_t)f], 9 * sizeof(double));
+        std::memcpy(r.t, &po[12 * (size_t)f + 9], 3 * sizeof(double));
+        std::memcpy(r.pose_cov, &fc[36 * (size_t)f], 36 * sizeof(double));
+        frame_pose_estimate[fids[f]] = estimate_from_result_(r);
+    }
+    point_estimate.clear();
+    for (int i = 0; i < m; ++i) {
+        Point3Uncertainty C;
+        std::memcpy(C.m, &pc[9 * (size_t)i], sizeof(C.m));
+        point_estimate[pids[i]] = Point3Estimate(Point3(pp[3 * (size_t)i], pp[3 * (size_t)i + 1], pp[3 * (size_t)i + 2]), C);
+    }
+    final_error = res.error;
+}
+}  // namespace hip
+
+// Same signature as the reference.  Supported: 1 to 4096 frames (the reference itself builds one or two: sfm_refine,
+// pnp_refine, VisualOdometer::track_refine; up to eight go through mvs_ba_refine_window, nine and more through
+// mvs_ba_refine_sparse); diagonal frame priors.  With this one function forwarded,
 // sfm-refine.cpp, pnp-refine.cpp and visual-odometer.cpp stay untouched and GTSAM leaves the link line.
 inline void ba_frame_pose_and_point(const CameraIntrinsics &ci, const std::unordered_set<Id::Type> &frame_id,
                                     const std::unordered_set<Id::Type> &point_id,
@@ -779,7 +863,7 @@ inline void ba_frame_pose_and_point(const CameraIntrinsics &ci, const std::unord
                                     std::unordered_map<Id::Type, TransformationEstimate> &frame_pose_estimate,
                                     std::unordered_map<Id::Type, Point3Estimate> &point_estimate, ScalarType &final_error)
 {
-    assert(frame_id.size() > 0 && frame_id.size() <= 8);   // ba.cpp:39; the window kernel's capacity
+    assert(frame_id.size() > 0 && frame_id.size() <= 4096);   // ba.cpp:39; mvs_ba_refine_sparse's capacity
     assert(point_id.size() > 0);
     assert(frame_pose_guess.size() == frame_id.size() && point_guess.size() == point_id.size());
     assert(frame_pose_prior.size() + point_prior.size() >= 2);   // ba.cpp:43
@@ -790,6 +874,11 @@ inline void ba_frame_pose_and_point(const CameraIntrinsics &ci, const std::unord
     std::unordered_map<Id::Type, int> pidx;
     for (int i = 0; i < m; ++i)
         pidx[pids[i]] = i;
+    if (F > 8) {   // nine frames and more: the sparse entry, an observation a frame lacks is simply absent
+        hip::ba_sparse_(ci, fids, pids, pidx, frame_pose_guess, frame_pose_prior, point_guess, point_prior, frame_observation,
+                        frame_pose_estimate, point_estimate, final_error);
+        return;
+    }
     std::vector<double> pose(12 * (size_t)F), var(6 * (size_t)F, 0.0), pts(3 * (size_t)m), pcov(9 * (size_t)m, 0.0);
     std::vector<std::vector<double>> obs(F), ocov(F);
     std::vector<std::vector<uint8_t>> valid(F);

@@ -1,4 +1,4 @@
-// capi_internal.hpp -- what the host files of libmvslam_hip.so (capi.hip, capi_orb.hip, capi_graph.hip, capi_debug.hip) share:
+// capi_internal.hpp -- what the host files of libmvslam_hip.so (capi.hip, capi_orb.hip, capi_graph.hip, capi_ba.hip, capi_debug.hip) share:
 // the owners of device memory, the three opaque objects of include/mvslam_hip.h, HIP_TRY and the helpers that cross a file
 // boundary.  A helper that one file uses is static in that file and is not declared here.
 #pragma once
@@ -76,6 +76,7 @@ struct mvs_ctx {
     DevWorkspace win;         // mvs_ba_refine_windows workspace
     DevWorkspace pg;          // mvs_pose_graph_optimize workspace
     DevWorkspace pgm;         // mvs_pose_graph_marginals workspace: uploads, lists, the skyline, the solves' y
+    DevWorkspace bas;         // mvs_ba_refine_sparse workspace: uploads, lists, linearisation, the skyline (capi_ba.hip)
     DevWorkspace orb;         // extraction workspace: orb_graph points into it
     int32_t *h_orb_ovf = nullptr;   // pinned: the extraction's overflow flag travels with the outputs (one stream wait per call)
     bool orb_ready = false;

@@ -378,9 +378,56 @@ struct PgdDev {
     double *y;                   // [N][6] right-hand side, then y, then z
     double *x;                   // [N][6] the step
     PgdState *state;
+    // the second source (ba_sparse.hip), zero for the pose graphs: `pre` holds the off-diagonal blocks
+    // of the envelope already summed, unscaled ([n_blocks][36]; it may be `sky` itself) and the term lists are not read; D and g
+    // are then the caller's own.  A pivot of the skyline must exceed pivot_tol (the scaled matrix has a unit diagonal).
+    const double *pre;
+    double pivot_tol;
 };
 // scale, assemble, factorise (the forward substitution rides along), back-substitute and unscale: four launches
 void launch_pgd_step(const PgdDev &d, double lam, hipStream_t stream);
+
+// ---- sparse bundle adjustment of up to 4096 frames (ba_sparse.hip) ----------------------------
+// The points are eliminated per point, the reduced camera system goes into the skyline of ba_envelope.hpp and the step is
+// launch_pgd_step's with PgdDev::pre = sky, D and g the arrays below.  The host drives the LM loop.
+constexpr int kBasLin = 20;      // doubles of one linearised observation: Jc 12 (2 x 6), Jp 6 (2 x 3), r 2
+constexpr int kBasRedChunk = 4096;   // terms one workgroup of the cost's first reduction stage sums
+struct BasState {        // what the host reads once per LM iteration
+    double cost;         // sum of the squared Mahalanobis norms at the values of the last cost launch (no 1/2)
+    int32_t bad_point;   // some point's V failed the pivot rule in the last build
+    int32_t reserved;
+};
+struct BasDev {
+    int n_frames, n_points, n_obs, n_blocks;
+    double cam[5];               // fx sk cx fy cy
+    const double *pose0, *w;     // [F][12] guess = prior mean; [F][6] prior weights (0: none)
+    const double *pts0, *pinfo;  // [P][3] guess = prior mean; [P][6] prior information (xx xy xz yy yz zz)
+    const int32_t *obs_off, *obs_frame, *obs_point;   // [P + 1], [O], [O]
+    const double *obs_uv, *oinfo;                     // [O][2], [O][3] (xx xy yy)
+    const int32_t *fr_off, *fr_obs;                   // [F + 1], [O]
+    const int32_t *first, *row_off, *blk_row, *last;  // the envelope: [F], [F + 1], [n_blocks], [F]
+    const int32_t *pair_off, *pair_a, *pair_c;        // [n_blocks + 1], [pairs], [pairs]
+    double *pose[2], *pts[2];    // [F][12], [P][3]: current / candidate (which is which: the host's)
+    double *lin;                 // [O][kBasLin]; the covariance pass keeps Y_o (18) in it
+    double *Li, *gh;             // [P][6] L^-1 of V = L L^T (l00 l10 l11 l20 l21 l22), [P][3] L^-1 g_p
+    double *Z, *zd;              // [O][18] Z_o = Hcp_o L^-T (6 x 3), [O][3] Z_o^T delta_f
+    double *prior;               // [F][27] the pose priors' share of Hcc_f (21, packed lower) and g_f (6)
+    double *D, *g;               // [F][21], [F][6]: diagonal blocks and gradient of the reduced system (lambda not in it)
+    double *sky;                 // [n_blocks][36]
+    const double *Cinv, *x;      // [F][21], [F][6]: the step's scaling and the step (PgdDev's)
+    double *terms, *partial;     // [O + P + F] cost terms, [ceil(that / kBasRedChunk)]
+    double *inv, *colm;          // [n_blocks][36] blocks of the scaled S^-1, [F][36] (covariance pass)
+    double *pose_cov, *point_cov;   // [F][36], [P][9]; either may be null
+    BasState *state;
+};
+// cost at pose[which], pts[which] -> state->cost
+void launch_bas_cost(const BasDev &d, int which, hipStream_t stream);
+// linearise at [cur] with damping lam: Li, gh, Z, D, g and the off-diagonal blocks of sky; clears state->bad_point first
+void launch_bas_build(const BasDev &d, int cur, double lam, hipStream_t stream);
+// candidate = [cur ^ 1] from the step x
+void launch_bas_update(const BasDev &d, int cur, hipStream_t stream);
+// behind a build and a step at lambda = 0: blocks of S^-1 inside the envelope, pose_cov, point_cov
+void launch_bas_cov(const BasDev &d, hipStream_t stream);
 
 // ---- marginal covariances of a pose graph (pg_marginals.hip) ---------------------------------
 // H = J_a^T W_a J_a + sum_k J_k^T W_k J_k at the poses X, no lambda, as the block lower triangle inside its envelope (row i

@@ -16,6 +16,9 @@
 //   pgd_solve_kernel     ONE workgroup: rows in descending order, z_i = L_ii^-T y_i, then y_c -= L(i, c)^T z_i for every c of
 //                        the row's envelope (one owner per entry, one row at a time); at the end x_i = C_i^-T z_i.
 // Every kernel leaves at once when the status word is set.  Binary64, explicit FMAs, every sum in a fixed order.
+// The sparse bundle adjustment (ba_sparse.hip; section 4.7.4) runs the same four kernels on a second source: PgdDev::pre holds
+// the off-diagonal blocks already summed, D and g are its own, PgdDev::pivot_tol its pivot rule.  Both are zero for the pose
+// graphs, whose statements and bytes are what they were.
 //
 // chol_packed / coldot are COPIES of posegraph.hip's (same statements, same order), for the reason pg_marginals.hip gives.
 #include "kernels.hpp"
@@ -134,9 +137,11 @@ __global__ __launch_bounds__(kPgdThreads) void pgd_assemble_kernel(PgdDev d)
     if (on) {
         i = d.blk_row[b];
         j = d.first[i] + (int)(b - d.row_off[i]);
-        const int slot = d.blk_slot[b];
-        off = i != j && slot >= 0;
-        if (off) {
+        const int slot = d.pre ? -1 : d.blk_slot[b];
+        off = i != j && (d.pre || slot >= 0);
+        if (off && d.pre) {   // the second source: the block has been summed already
+            A[lb][e] = d.pre[36 * b + e];
+        } else if (off) {
             double acc = 0.0;
             for (int t = d.slot_off[slot]; t < d.slot_off[slot + 1]; ++t) {
                 const int code = d.codes[t];
@@ -239,7 +244,7 @@ __global__ __launch_bounds__(kPgdThreads) void pgd_factor_kernel(PgdDev d)
 #pragma unroll
                 for (int c = 0; c <= r; ++c)
                     S[lidx(r, c)] = Dg[6 * r + c];
-            const bool ok = chol_packed<6>(S, min_d);
+            const bool ok = chol_packed<6>(S, min_d) && min_d > d.pivot_tol;   // 0 for the pose graphs: chol_packed's own rule
             tri_inverse(S, W);
 #pragma unroll
             for (int r = 0; r < 6; ++r)
