@@ -683,6 +683,47 @@ mvs_status mvs_seq_refine_windows(mvs_seq *s, const mvs_seq_window_params *wp, c
 mvs_status mvs_seq_download_windows(mvs_seq *s, mvs_seq_window_info *info, mvs_refine_result *frames, double *points,
                                     double *point_cov, int32_t *track_kp, double *point_guess);
 
+/* ONE bundle adjustment over every frame of a sequence that has been run (mvs_seq_run, mvs_seq_run_essential, and whatever
+ * ran after them), assembled on the device from what is resident and solved by the sparse solver of mvs_ba_refine_sparse
+ * (DESIGN.md section 4.7.5).  New symbols only: mvs_abi_version stays 4.
+ *   links   those of mvs_seq_refine_windows: an inlier row of a valid pair k joins keypoint trainIdx of frame k to keypoint
+ *           queryIdx of frame k + 1, the smallest row wins per trainIdx, tracks are simple chains;
+ *   depth   of a keypoint: the links behind it (0 where no link arrives);
+ *   tracks  a head is a keypoint with a link out of it whose depth is 0 (max_track_frames = 0: uncut) or a multiple of
+ *           T = max_track_frames; its track is the chain from the head on, to the chain's end or, cut, over T frames at the most.
+ *           Every track has at least two frames and its frames are consecutive;
+ *   points  a track is a point if one of its OWN links was triangulated; the first such pair k gives the guess
+ *           X = traj_R[k] (pair_scale[k] x) + traj_t[k].  Points are numbered by (head frame, head keypoint); the observations
+ *           of a point are stored in frame order: obs_frame[obs_off[p] + s] = head_frame[p] + s;
+ *   problem the sequence's camera; poses = the trajectory; frame 0 carries params->anchor_sigma, the others pose_sigma
+ *           (variances sigma^2, an entry <= 0 would be no prior); every point the prior point_sigma^2 I at its guess; an
+ *           observation the covariance (sigma_px * 2^octave)^2 I.  A frame no point reaches is held by its prior alone. */
+typedef struct mvs_seq_global_params {
+    int32_t max_track_frames;   /* T: 0 = uncut, or 2 .. 4096 */
+    int32_t reserved;
+    double sigma_px;            /* as mvs_batch_refine */
+} mvs_seq_global_params;
+/* Synchronous: the host reads the device's counts once (points, observations, blocks of the envelope, pairs), sizes the
+ * workspace, and drives lambda with one synchronisation per iteration as mvs_ba_refine_sparse does; `result` is that call's
+ * record.  MVS_ERR_INVALID_ARG: a null pointer, a sequence that has not been run, sigma_px <= 0, max_track_frames outside
+ * {0, 2 .. 4096}, refine parameters mvs_ba_refine refuses.  MVS_ERR_CAPACITY, before any solve: more than 4096 frames, or
+ * counts beyond the limits of mvs_ba_refine_sparse (2^20 points, 2^23 observations, 2^21 blocks, 2^28 pairs).  MVS_NO_MODEL:
+ * no point at all (ok = 0), or the solver's own (ok = 0, as mvs_ba_refine_sparse).  The same input gives the same bytes.
+ * Memory: the link tables, the problem, the plan and the results live in two blocks owned by the SEQUENCE, which only grow and
+ * are freed by mvs_seq_destroy; they stay resident until the next call or the next run. */
+mvs_status mvs_seq_refine_global(mvs_seq *s, const mvs_seq_global_params *gp, const mvs_refine_params *params,
+                                 mvs_ba_sparse_result *result);
+/* points and observations of the last mvs_seq_refine_global (0 and 0 after a call that found no point) */
+mvs_status mvs_seq_global_counts(mvs_seq *s, int32_t *n_points, int32_t *n_obs);
+/* Any pointer may be NULL.  poses n_frames x 12, points n_points x 3, pose_cov n_frames x 36, point_cov n_points x 9; the
+ * covariance sweep runs at the first call that asks for either.  MVS_NO_MODEL with every output untouched when the last
+ * mvs_seq_refine_global ended with ok = 0. */
+mvs_status mvs_seq_download_global(mvs_seq *s, double *poses, double *points, double *pose_cov, double *point_cov);
+/* The assembled problem, any pointer may be NULL: obs_off[n_points + 1], obs_frame[n_obs], obs_kp[n_obs] (the keypoint of
+ * every observation in its frame), head_frame[n_points], head_kp[n_points], point_guess n_points x 3, obs_uv n_obs x 2. */
+mvs_status mvs_seq_download_global_problem(mvs_seq *s, int32_t *obs_off, int32_t *obs_frame, int32_t *obs_kp,
+                                           int32_t *head_frame, int32_t *head_kp, double *point_guess, double *obs_uv);
+
 /* The tracking loop of a sequence that has been run: VisualOdometer::track (front-end/visual-odometer.cpp:384-500) with
  * track_pnp (:502-615) and track_refine (:618-800), every frame on the device, no host synchronisation between frames
  * (DESIGN.md section 4.7.2).  Unlike the tracks of mvs_seq_run, which only see their own pair's two-view points, the loop

@@ -129,6 +129,11 @@ class SeqWindowInfo(C.Structure):
 WINDOW_INFO_DTYPE = np.dtype([("first_frame", "<i4"), ("n_frames", "<i4"), ("n_points", "<i4"), ("n_tracks_found", "<i4")])
 
 
+class SeqGlobalParams(C.Structure):
+    """mvs_seq_global_params: max_track_frames 0 = uncut tracks, or 2 .. 4096"""
+    _fields_ = [("max_track_frames", C.c_int32), ("reserved", C.c_int32), ("sigma_px", C.c_double)]
+
+
 class VoParams(C.Structure):
     """mvs_vo_params: the tracking loop of Sequence.track"""
     _fields_ = [("init_pair", C.c_int32), ("use_refined_init", C.c_int32), ("min_pnp_point_count", C.c_int32),
@@ -282,6 +287,7 @@ EXPORTS = [
     "mvs_pose_graph_marginals", "mvs_seq_pose_graph_marginals",
     "mvs_ctx_set_pose_graph_solver", "mvs_ctx_pose_graph_direct_info",
     "mvs_ctx_set_pose_graph_loss", "mvs_pose_graph_edge_stats", "mvs_seq_pose_graph_edge_stats",
+    "mvs_seq_refine_global", "mvs_seq_global_counts", "mvs_seq_download_global", "mvs_seq_download_global_problem",
 ]
 
 
@@ -303,6 +309,8 @@ def dbg_lib():
         _dbg.mvs_debug_audit_state.restype = C.c_int
         _dbg.mvs_debug_audit_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]
+        _dbg.mvs_debug_seq_global_plan.restype = C.c_int
+        _dbg.mvs_debug_seq_global_plan.argtypes = [C.c_void_p] * 12
     return _dbg
 
 
@@ -353,6 +361,10 @@ def lib():
         _lib.mvs_batch_destroy.argtypes = [C.c_void_p]
         _lib.mvs_seq_destroy.argtypes = [C.c_void_p]
         _lib.mvs_seq_window_count.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.mvs_seq_refine_global.argtypes = [C.c_void_p] * 4
+        _lib.mvs_seq_global_counts.argtypes = [C.c_void_p] * 3
+        _lib.mvs_seq_download_global.argtypes = [C.c_void_p] * 5
+        _lib.mvs_seq_download_global_problem.argtypes = [C.c_void_p] * 8
         _lib.mvs_vo_params_default.restype = None
         _lib.mvs_vo_init_params_default.restype = None
     return _lib
@@ -1396,6 +1408,56 @@ class Sequence:
                             first_frame=int(info[w]["first_frame"]), n_frames=int(info[w]["n_frames"]), n_points=m,
                             n_tracks_found=int(info[w]["n_tracks_found"]), track_kp=tkp[w, :m].copy(),
                             point_guess=guess[w, :m].copy()))
+        return out
+
+    def refine_global(self, max_track_frames=0, params=None, sigma_px=0.5):
+        """ONE bundle adjustment over every frame of a sequence that has been run, assembled on the device from the resident
+        matches, points and trajectory and solved by the sparse solver (mvs_seq_refine_global; synchronous).  Tracks are
+        whole (max_track_frames = 0) or cut into pieces of that many frames.  Returns the result record's fields as a dict
+        with status (MVS_OK / MVS_NO_MODEL), ok, n_points, n_obs and `raw`, the record's bytes."""
+        params = params or default_refine_params()
+        gp = SeqGlobalParams(int(max_track_frames), 0, float(sigma_px))
+        res = BaSparseResult()
+        st = lib().mvs_seq_refine_global(self._h, C.byref(gp), C.byref(params), C.byref(res))
+        self.ctx._check(st, "mvs_seq_refine_global", allow_no_model=True)
+        out = {k: getattr(res, k) for k, _ in BaSparseResult._fields_}
+        n_points, n_obs = self.global_counts()
+        out.update(status=st, ok=bool(res.ok), n_points=n_points, n_obs=n_obs, raw=bytes(res))
+        return out
+
+    def global_counts(self):
+        """(points, observations) of the last refine_global()"""
+        n_points, n_obs = C.c_int32(0), C.c_int32(0)
+        st = lib().mvs_seq_global_counts(self._h, C.byref(n_points), C.byref(n_obs))
+        self.ctx._check(st, "mvs_seq_global_counts")
+        return n_points.value, n_obs.value
+
+    def download_global(self, points=True, pose_cov=True, point_cov=True):
+        """the estimate of the last refine_global(): status, R [F, 3, 3], t [F, 3], points [P, 3], pose_cov [F, 6, 6] and
+        point_cov [P, 3, 3] (None when not asked for; the covariance sweep runs at the first request) and `raw`, the bytes of
+        every array.  On MVS_NO_MODEL the arrays are as they were allocated (zero)."""
+        F, (P, _) = self.n_frames, self.global_counts()
+        poses = np.zeros((F, 12))
+        pts = np.zeros((max(P, 1), 3)) if points else None
+        pcv = np.zeros((F, 6, 6)) if pose_cov else None
+        ptc = np.zeros((max(P, 1), 3, 3)) if point_cov else None
+        st = lib().mvs_seq_download_global(self._h, _ptr(poses, C.c_double), _ptr(pts, C.c_double), _ptr(pcv, C.c_double),
+                                           _ptr(ptc, C.c_double))
+        self.ctx._check(st, "mvs_seq_download_global", allow_no_model=True)
+        return dict(status=st, R=poses[:, :9].reshape(-1, 3, 3).copy(), t=poses[:, 9:].copy(), points=pts, pose_cov=pcv,
+                    point_cov=ptc, raw=b"".join(a.tobytes() for a in (poses, pts, pcv, ptc) if a is not None))
+
+    def download_global_problem(self):
+        """the problem the last refine_global() assembled: obs_off [P + 1], obs_frame / obs_kp [O], head_frame / head_kp [P],
+        point_guess [P, 3], obs_uv [O, 2]"""
+        P, O = self.global_counts()
+        i32 = lambda n: np.zeros(n, dtype=np.int32)
+        out = dict(obs_off=i32(P + 1), obs_frame=i32(O), obs_kp=i32(O), head_frame=i32(P), head_kp=i32(P),
+                   point_guess=np.zeros((P, 3)), obs_uv=np.zeros((O, 2)))
+        st = lib().mvs_seq_download_global_problem(
+            self._h, *[out[k].ctypes.data_as(C.c_void_p) for k in ("obs_off", "obs_frame", "obs_kp", "head_frame", "head_kp",
+                                                                  "point_guess", "obs_uv")])
+        self.ctx._check(st, "mvs_seq_download_global_problem")
         return out
 
     def track(self, vo_params=None, pnp_params=None, refine_params=None):

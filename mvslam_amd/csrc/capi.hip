@@ -2111,6 +2111,7 @@ static mvs_status seq_enqueue(mvs_seq *q, Estimator est, const RunParams &rp, hi
     q->lags_ran = 0;         // nor are lagged pairs
     q->odo_ran = false;
     q->graph_built = q->graph_opt = false;   // nor is a pose graph
+    q->glob_counted = q->glob_built = q->glob_solved = q->glob_cov = false;   // nor is a global problem
     return MVS_OK;
 }
 

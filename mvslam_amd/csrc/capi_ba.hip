@@ -1,6 +1,9 @@
-// capi_ba.hip -- the host side of mvs_ba_refine_sparse (include/mvslam_hip.h): argument checks, the
-// plan of ba_envelope.hpp, one workspace of the context, and the LM loop of refine_window_kernel driven from here -- the device
-// computes (ba_sparse.hip, pg_direct.hip), the host decides, one synchronisation per iteration.
+// capi_ba.hip -- the host side of the sparse bundle adjustment (include/mvslam_hip.h; DESIGN.md sections 4.7.4 and 4.7.5).
+// One solver, bas_solve: the LM loop of refine_window_kernel driven from here over a problem and a plan that lie in device
+// memory -- the device computes (ba_sparse.hip, pg_direct.hip), the host decides, one synchronisation per iteration.  Two
+// entries feed it: mvs_ba_refine_sparse (argument checks, the plan of ba_envelope.hpp, packing and upload into a workspace of
+// the context) and mvs_seq_refine_global (the problem and the plan built on the device from a resident sequence by
+// seq_global.hip, in two workspaces of the sequence).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -8,6 +11,7 @@
 
 #include "ba_envelope.hpp"
 #include "capi_internal.hpp"
+#include "seq_global_host.hpp"
 
 using namespace mvs_host;
 
@@ -38,125 +42,66 @@ void point_info(const double *C, double *L)
     L[0] = c00 * id, L[1] = c01 * id, L[2] = c02 * id;
     L[3] = (a[0] * a[5] - a[2] * a[2]) * id, L[4] = (a[1] * a[2] - a[0] * a[4]) * id, L[5] = (a[0] * a[3] - a[1] * a[1]) * id;
 }
+// a prior variance as the weight the kernels read: none where the variance is not positive
+double prior_weight(double var) { return var > 0.0 ? 1.0 / var : 0.0; }
 
-}  // namespace
-
-extern "C" {
-
-mvs_status mvs_ba_refine_sparse(mvs_ctx *ctx, const mvs_ba_sparse *pb, const mvs_refine_params *params,
-                                mvs_ba_sparse_result *result, double *poses_out, double *points_out, double *pose_cov_out,
-                                double *point_cov_out)
+// the solver's own arrays as offsets into a workspace, laid out behind whatever the entry has laid out for its inputs and lists
+struct BasWork {
+    size_t pose[2], pts[2], lin, Li, gh, Z, zd, prior, D, g, sky, Cinv, y, x, terms, part, pst, bst, inv, colm, pcov, ptcov;
+    bool want_cov, pose_cov, point_cov;
+};
+BasWork carve_work(Carve &L, size_t F, size_t P, size_t O, size_t B, bool pose_cov, bool point_cov)
 {
-    if (!ctx || !pb || !result || !poses_out || !refine_params_ok(params))
-        return MVS_ERR_INVALID_ARG;
-    if (pb->n_frames < 1 || pb->n_points < 1 || pb->n_obs < 1)
-        return MVS_ERR_INVALID_ARG;
-    if (pb->n_frames > mvs_bas::kMaxFrames || pb->n_points > mvs_bas::kMaxPoints || pb->n_obs > mvs_bas::kMaxObs)
-        return MVS_ERR_CAPACITY;
-    if (!pb->K || !pb->frame_pose || !pb->frame_prior_var || !pb->points || !pb->obs_off || !pb->obs_frame || !pb->obs_uv)
-        return MVS_ERR_INVALID_ARG;
-    const int F = pb->n_frames, P = pb->n_points, O = pb->n_obs;
-    if (!all_finite(pb->K, 9) || !affine_K(pb->K) || !all_finite(pb->frame_pose, 12 * (size_t)F) ||
-        !all_finite(pb->frame_prior_var, 6 * (size_t)F) || !all_finite(pb->points, 3 * (size_t)P) ||
-        (pb->point_prior_cov && !all_finite(pb->point_prior_cov, 9 * (size_t)P)) || !all_finite(pb->obs_uv, 2 * (size_t)O) ||
-        (pb->obs_cov && !all_finite(pb->obs_cov, 4 * (size_t)O)))
-        return MVS_ERR_INVALID_ARG;
-    if (mvs_bas::check_csr(F, P, O, pb->obs_off, pb->obs_frame) != 0)
-        return MVS_ERR_INVALID_ARG;
-    const mvs_bas::Plan plan = mvs_bas::plan(F, P, O, pb->obs_off, pb->obs_frame);
-    if (!plan.fits())
-        return MVS_ERR_CAPACITY;
-    const size_t B = (size_t)plan.blocks, NP = (size_t)plan.pairs;
-    const bool want_cov = pose_cov_out || point_cov_out;
-
-    // the uploaded doubles: weights and information matrices are derived here
-    std::vector<double> w(6 * (size_t)F), pinfo(6 * (size_t)P, 0.0), oinfo(3 * (size_t)O, 0.0);
-    for (size_t k = 0; k < w.size(); ++k)
-        w[k] = pb->frame_prior_var[k] > 0.0 ? 1.0 / pb->frame_prior_var[k] : 0.0;
-    for (size_t i = 0; i < (size_t)P && pb->point_prior_cov; ++i)
-        if (pb->point_prior_cov[9 * i] > 0.0)
-            point_info(pb->point_prior_cov + 9 * i, pinfo.data() + 6 * i);
-    for (size_t o = 0; o < (size_t)O; ++o) {
-        if (!pb->obs_cov)
-            oinfo[3 * o] = 1.0, oinfo[3 * o + 2] = 1.0;
-        else
-            obs_info(pb->obs_cov + 4 * o, oinfo.data() + 3 * o);
-    }
-
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int64_t n_terms = (int64_t)O + P + F;
+    BasWork k{};
+    const bool want_cov = pose_cov || point_cov;
+    const int64_t n_terms = (int64_t)O + (int64_t)P + (int64_t)F;
     const size_t chunks = (size_t)((n_terms + kBasRedChunk - 1) / kBasRedChunk);
-    Carve L{64};
-    const size_t o_pose0 = L.take(12 * (size_t)F * 8), o_w = L.take(6 * (size_t)F * 8), o_pts0 = L.take(3 * (size_t)P * 8);
-    const size_t o_pinfo = L.take(6 * (size_t)P * 8), o_uv = L.take(2 * (size_t)O * 8), o_oinfo = L.take(3 * (size_t)O * 8);
-    const size_t o_ooff = L.take(((size_t)P + 1) * 4), o_ofr = L.take((size_t)O * 4), o_opt = L.take((size_t)O * 4);
-    const size_t o_froff = L.take(((size_t)F + 1) * 4), o_frobs = L.take((size_t)O * 4);
-    const size_t o_first = L.take((size_t)F * 4), o_row = L.take(((size_t)F + 1) * 4), o_brow = L.take(B * 4);
-    const size_t o_last = L.take((size_t)F * 4), o_poff = L.take((B + 1) * 4), o_pa = L.take(NP * 4), o_pc = L.take(NP * 4);
-    const size_t o_pose[2] = {L.take(12 * (size_t)F * 8), L.take(12 * (size_t)F * 8)};
-    const size_t o_pts[2] = {L.take(3 * (size_t)P * 8), L.take(3 * (size_t)P * 8)};
-    const size_t o_lin = L.take((size_t)kBasLin * O * 8), o_Li = L.take(6 * (size_t)P * 8), o_gh = L.take(3 * (size_t)P * 8);
-    const size_t o_Z = L.take(18 * (size_t)O * 8), o_zd = L.take(3 * (size_t)O * 8);
-    const size_t o_prior = L.take(27 * (size_t)F * 8);
-    const size_t o_D = L.take(21 * (size_t)F * 8), o_g = L.take(6 * (size_t)F * 8), o_sky = L.take(36 * B * 8);
-    const size_t o_Cinv = L.take(21 * (size_t)F * 8), o_y = L.take(6 * (size_t)F * 8), o_x = L.take(6 * (size_t)F * 8);
-    const size_t o_terms = L.take((size_t)n_terms * 8), o_part = L.take(chunks * 8);
-    const size_t o_pst = L.take(sizeof(PgdState)), o_bst = L.take(sizeof(BasState));
-    const size_t o_inv = L.take(want_cov ? 36 * B * 8 : 0), o_colm = L.take(want_cov ? 36 * (size_t)F * 8 : 0);
-    const size_t o_pcov = L.take(pose_cov_out ? 36 * (size_t)F * 8 : 0), o_ptcov = L.take(point_cov_out ? 9 * (size_t)P * 8 : 0);
-    mvs_status st = ws_grow(ctx, ctx->bas, L.total());
-    if (st != MVS_OK)
-        return st;
-    char *base = ctx->bas.ptr();
-    hipStream_t s = ctx_stream(ctx);
+    k.pose[0] = L.take(12 * F * 8), k.pose[1] = L.take(12 * F * 8);
+    k.pts[0] = L.take(3 * P * 8), k.pts[1] = L.take(3 * P * 8);
+    k.lin = L.take((size_t)kBasLin * O * 8), k.Li = L.take(6 * P * 8), k.gh = L.take(3 * P * 8);
+    k.Z = L.take(18 * O * 8), k.zd = L.take(3 * O * 8);
+    k.prior = L.take(27 * F * 8);
+    k.D = L.take(21 * F * 8), k.g = L.take(6 * F * 8), k.sky = L.take(36 * B * 8);
+    k.Cinv = L.take(21 * F * 8), k.y = L.take(6 * F * 8), k.x = L.take(6 * F * 8);
+    k.terms = L.take((size_t)n_terms * 8), k.part = L.take(chunks * 8);
+    k.pst = L.take(sizeof(PgdState)), k.bst = L.take(sizeof(BasState));
+    k.inv = L.take(want_cov ? 36 * B * 8 : 0), k.colm = L.take(want_cov ? 36 * F * 8 : 0);
+    k.pcov = L.take(pose_cov ? 36 * F * 8 : 0), k.ptcov = L.take(point_cov ? 9 * P * 8 : 0);
+    k.want_cov = want_cov, k.pose_cov = pose_cov, k.point_cov = point_cov;
+    return k;
+}
+// d's counts, inputs and lists are set: this adds the solver's arrays, and pd, the step (pg_direct.hip's kernels on their
+// second source)
+void bind_work(char *base, const BasWork &k, BasDev &d, PgdDev &pd)
+{
     auto dp = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
-    auto ip = [&](size_t o) { return reinterpret_cast<int32_t *>(base + o); };
-    auto up = [&](size_t o, const void *src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-    };
-    HIP_TRY(ctx, up(o_pose0, pb->frame_pose, 12 * (size_t)F * 8));
-    HIP_TRY(ctx, up(o_w, w.data(), w.size() * 8));
-    HIP_TRY(ctx, up(o_pts0, pb->points, 3 * (size_t)P * 8));
-    HIP_TRY(ctx, up(o_pinfo, pinfo.data(), pinfo.size() * 8));
-    HIP_TRY(ctx, up(o_uv, pb->obs_uv, 2 * (size_t)O * 8));
-    HIP_TRY(ctx, up(o_oinfo, oinfo.data(), oinfo.size() * 8));
-    HIP_TRY(ctx, up(o_ooff, pb->obs_off, ((size_t)P + 1) * 4));
-    HIP_TRY(ctx, up(o_ofr, pb->obs_frame, (size_t)O * 4));
-    HIP_TRY(ctx, up(o_opt, plan.obs_point.data(), (size_t)O * 4));
-    HIP_TRY(ctx, up(o_froff, plan.fr_off.data(), ((size_t)F + 1) * 4));
-    HIP_TRY(ctx, up(o_frobs, plan.fr_obs.data(), (size_t)O * 4));
-    HIP_TRY(ctx, up(o_first, plan.first.data(), (size_t)F * 4));
-    HIP_TRY(ctx, up(o_row, plan.row_off.data(), ((size_t)F + 1) * 4));
-    HIP_TRY(ctx, up(o_brow, plan.blk_row.data(), B * 4));
-    HIP_TRY(ctx, up(o_last, plan.last.data(), (size_t)F * 4));
-    HIP_TRY(ctx, up(o_poff, plan.pair_off.data(), (B + 1) * 4));
-    HIP_TRY(ctx, up(o_pa, plan.pair_a.data(), NP * 4));
-    HIP_TRY(ctx, up(o_pc, plan.pair_c.data(), NP * 4));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_pose[0], base + o_pose0, 12 * (size_t)F * 8, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_pts[0], base + o_pts0, 3 * (size_t)P * 8, hipMemcpyDeviceToDevice, s));
-
-    BasDev d{};
-    d.n_frames = F, d.n_points = P, d.n_obs = O, d.n_blocks = (int)B;
-    d.cam[0] = pb->K[0], d.cam[1] = pb->K[1], d.cam[2] = pb->K[2], d.cam[3] = pb->K[4], d.cam[4] = pb->K[5];
-    d.pose0 = dp(o_pose0), d.w = dp(o_w), d.pts0 = dp(o_pts0), d.pinfo = dp(o_pinfo);
-    d.obs_off = ip(o_ooff), d.obs_frame = ip(o_ofr), d.obs_point = ip(o_opt), d.obs_uv = dp(o_uv), d.oinfo = dp(o_oinfo);
-    d.fr_off = ip(o_froff), d.fr_obs = ip(o_frobs);
-    d.first = ip(o_first), d.row_off = ip(o_row), d.blk_row = ip(o_brow), d.last = ip(o_last);
-    d.pair_off = ip(o_poff), d.pair_a = ip(o_pa), d.pair_c = ip(o_pc);
-    d.pose[0] = dp(o_pose[0]), d.pose[1] = dp(o_pose[1]), d.pts[0] = dp(o_pts[0]), d.pts[1] = dp(o_pts[1]);
-    d.lin = dp(o_lin), d.Li = dp(o_Li), d.gh = dp(o_gh), d.Z = dp(o_Z), d.zd = dp(o_zd), d.D = dp(o_D), d.g = dp(o_g);
-    d.prior = dp(o_prior);
-    d.sky = dp(o_sky), d.Cinv = dp(o_Cinv), d.x = dp(o_x), d.terms = dp(o_terms), d.partial = dp(o_part);
-    d.inv = want_cov ? dp(o_inv) : nullptr, d.colm = want_cov ? dp(o_colm) : nullptr;
-    d.pose_cov = pose_cov_out ? dp(o_pcov) : nullptr, d.point_cov = point_cov_out ? dp(o_ptcov) : nullptr;
-    d.state = reinterpret_cast<BasState *>(base + o_bst);
-    // the step: pg_direct.hip's kernels on their second source
-    PgdDev pd{};
-    pd.n_nodes = F, pd.n_blocks = (int)B;
+    d.pose[0] = dp(k.pose[0]), d.pose[1] = dp(k.pose[1]), d.pts[0] = dp(k.pts[0]), d.pts[1] = dp(k.pts[1]);
+    d.lin = dp(k.lin), d.Li = dp(k.Li), d.gh = dp(k.gh), d.Z = dp(k.Z), d.zd = dp(k.zd), d.D = dp(k.D), d.g = dp(k.g);
+    d.prior = dp(k.prior);
+    d.sky = dp(k.sky), d.Cinv = dp(k.Cinv), d.x = dp(k.x), d.terms = dp(k.terms), d.partial = dp(k.part);
+    d.inv = k.want_cov ? dp(k.inv) : nullptr, d.colm = k.want_cov ? dp(k.colm) : nullptr;
+    d.pose_cov = k.pose_cov ? dp(k.pcov) : nullptr, d.point_cov = k.point_cov ? dp(k.ptcov) : nullptr;
+    d.state = reinterpret_cast<BasState *>(base + k.bst);
+    pd = PgdDev{};
+    pd.n_nodes = d.n_frames, pd.n_blocks = d.n_blocks;
     pd.first = d.first, pd.row_off = d.row_off, pd.blk_row = d.blk_row;
-    pd.D = d.D, pd.g = d.g, pd.Cinv = dp(o_Cinv), pd.sky = d.sky, pd.y = dp(o_y), pd.x = dp(o_x);
-    pd.state = reinterpret_cast<PgdState *>(base + o_pst);
+    pd.D = d.D, pd.g = d.g, pd.Cinv = dp(k.Cinv), pd.sky = d.sky, pd.y = dp(k.y), pd.x = dp(k.x);
+    pd.state = reinterpret_cast<PgdState *>(base + k.pst);
     pd.pre = d.sky, pd.pivot_tol = kPivotTol;
+}
+
+// The solver over a problem whose inputs and lists lie in device memory (or are on their way there on the context's stream):
+// the LM loop from the guesses pose0 / pts0, then the factorisation at the estimate with lambda = 0, which decides ok and is
+// what launch_bas_cov continues from.  *result is filled whenever MVS_OK or MVS_NO_MODEL is returned; the estimate is then
+// d.pose[*cur_out] / d.pts[*cur_out].
+mvs_status bas_solve(mvs_ctx *ctx, const BasDev &d, const PgdDev &pd, const mvs_refine_params *params, int widest,
+                     mvs_ba_sparse_result *result, int *cur_out)
+{
+    const int F = d.n_frames;
+    hipStream_t s = ctx_stream(ctx);
+    mvs_status st = MVS_OK;
+    HIP_TRY(ctx, hipMemcpyAsync(d.pose[0], d.pose0, 12 * (size_t)F * 8, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d.pts[0], d.pts0, 3 * (size_t)d.n_points * 8, hipMemcpyDeviceToDevice, s));
 
     BasState hb{};
     PgdState hd{};
@@ -168,7 +113,7 @@ mvs_status mvs_ba_refine_sparse(mvs_ctx *ctx, const mvs_ba_sparse *pb, const mvs
         return MVS_OK;
     };
     mvs_ba_sparse_result res{};
-    res.envelope_blocks = (int32_t)plan.blocks, res.widest_row = plan.widest, res.bad_frame = -1;
+    res.envelope_blocks = (int32_t)d.n_blocks, res.widest_row = widest, res.bad_frame = -1;
     bool have_bad = false;
     auto note_failure = [&]() {
         if (!have_bad && hd.status != 0) {
@@ -179,7 +124,7 @@ mvs_status mvs_ba_refine_sparse(mvs_ctx *ctx, const mvs_ba_sparse *pb, const mvs
     HIP_TRY(ctx, hipMemsetAsync(pd.state, 0, sizeof(PgdState), s));
     HIP_TRY(ctx, hipMemsetAsync(d.state, 0, sizeof(BasState), s));
     launch_bas_cost(d, 0, s);
-    if ((st = read_state()) != MVS_OK)   // the plan's lists and the packed inputs have been read by here, too
+    if ((st = read_state()) != MVS_OK)   // whatever the caller has enqueued in front (uploads, the assembly) is done by here, too
         return st;
 
     // the LM rule of refine_window_kernel
@@ -241,8 +186,106 @@ mvs_status mvs_ba_refine_sparse(mvs_ctx *ctx, const mvs_ba_sparse *pb, const mvs
     res.error_initial = 0.5 * cost0;
     res.error = 0.5 * cur;
     *result = res;
-    if (!ok)
-        return MVS_NO_MODEL;
+    *cur_out = cb;
+    return ok ? MVS_OK : MVS_NO_MODEL;
+}
+
+}  // namespace
+
+extern "C" {
+
+mvs_status mvs_ba_refine_sparse(mvs_ctx *ctx, const mvs_ba_sparse *pb, const mvs_refine_params *params,
+                                mvs_ba_sparse_result *result, double *poses_out, double *points_out, double *pose_cov_out,
+                                double *point_cov_out)
+{
+    if (!ctx || !pb || !result || !poses_out || !refine_params_ok(params))
+        return MVS_ERR_INVALID_ARG;
+    if (pb->n_frames < 1 || pb->n_points < 1 || pb->n_obs < 1)
+        return MVS_ERR_INVALID_ARG;
+    if (pb->n_frames > mvs_bas::kMaxFrames || pb->n_points > mvs_bas::kMaxPoints || pb->n_obs > mvs_bas::kMaxObs)
+        return MVS_ERR_CAPACITY;
+    if (!pb->K || !pb->frame_pose || !pb->frame_prior_var || !pb->points || !pb->obs_off || !pb->obs_frame || !pb->obs_uv)
+        return MVS_ERR_INVALID_ARG;
+    const int F = pb->n_frames, P = pb->n_points, O = pb->n_obs;
+    if (!all_finite(pb->K, 9) || !affine_K(pb->K) || !all_finite(pb->frame_pose, 12 * (size_t)F) ||
+        !all_finite(pb->frame_prior_var, 6 * (size_t)F) || !all_finite(pb->points, 3 * (size_t)P) ||
+        (pb->point_prior_cov && !all_finite(pb->point_prior_cov, 9 * (size_t)P)) || !all_finite(pb->obs_uv, 2 * (size_t)O) ||
+        (pb->obs_cov && !all_finite(pb->obs_cov, 4 * (size_t)O)))
+        return MVS_ERR_INVALID_ARG;
+    if (mvs_bas::check_csr(F, P, O, pb->obs_off, pb->obs_frame) != 0)
+        return MVS_ERR_INVALID_ARG;
+    const mvs_bas::Plan plan = mvs_bas::plan(F, P, O, pb->obs_off, pb->obs_frame);
+    if (!plan.fits())
+        return MVS_ERR_CAPACITY;
+    const size_t B = (size_t)plan.blocks, NP = (size_t)plan.pairs;
+    const bool want_cov = pose_cov_out || point_cov_out;
+
+    // the uploaded doubles: weights and information matrices are derived here
+    std::vector<double> w(6 * (size_t)F), pinfo(6 * (size_t)P, 0.0), oinfo(3 * (size_t)O, 0.0);
+    for (size_t k = 0; k < w.size(); ++k)
+        w[k] = prior_weight(pb->frame_prior_var[k]);
+    for (size_t i = 0; i < (size_t)P && pb->point_prior_cov; ++i)
+        if (pb->point_prior_cov[9 * i] > 0.0)
+            point_info(pb->point_prior_cov + 9 * i, pinfo.data() + 6 * i);
+    for (size_t o = 0; o < (size_t)O; ++o) {
+        if (!pb->obs_cov)
+            oinfo[3 * o] = 1.0, oinfo[3 * o + 2] = 1.0;
+        else
+            obs_info(pb->obs_cov + 4 * o, oinfo.data() + 3 * o);
+    }
+
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Carve L{64};
+    const size_t o_pose0 = L.take(12 * (size_t)F * 8), o_w = L.take(6 * (size_t)F * 8), o_pts0 = L.take(3 * (size_t)P * 8);
+    const size_t o_pinfo = L.take(6 * (size_t)P * 8), o_uv = L.take(2 * (size_t)O * 8), o_oinfo = L.take(3 * (size_t)O * 8);
+    const size_t o_ooff = L.take(((size_t)P + 1) * 4), o_ofr = L.take((size_t)O * 4), o_opt = L.take((size_t)O * 4);
+    const size_t o_froff = L.take(((size_t)F + 1) * 4), o_frobs = L.take((size_t)O * 4);
+    const size_t o_first = L.take((size_t)F * 4), o_row = L.take(((size_t)F + 1) * 4), o_brow = L.take(B * 4);
+    const size_t o_last = L.take((size_t)F * 4), o_poff = L.take((B + 1) * 4), o_pa = L.take(NP * 4), o_pc = L.take(NP * 4);
+    const BasWork wk = carve_work(L, (size_t)F, (size_t)P, (size_t)O, B, pose_cov_out != nullptr, point_cov_out != nullptr);
+    mvs_status st = ws_grow(ctx, ctx->bas, L.total());
+    if (st != MVS_OK)
+        return st;
+    char *base = ctx->bas.ptr();
+    hipStream_t s = ctx_stream(ctx);
+    auto dp = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
+    auto ip = [&](size_t o) { return reinterpret_cast<int32_t *>(base + o); };
+    auto up = [&](size_t o, const void *src, size_t bytes) {
+        return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    };
+    HIP_TRY(ctx, up(o_pose0, pb->frame_pose, 12 * (size_t)F * 8));
+    HIP_TRY(ctx, up(o_w, w.data(), w.size() * 8));
+    HIP_TRY(ctx, up(o_pts0, pb->points, 3 * (size_t)P * 8));
+    HIP_TRY(ctx, up(o_pinfo, pinfo.data(), pinfo.size() * 8));
+    HIP_TRY(ctx, up(o_uv, pb->obs_uv, 2 * (size_t)O * 8));
+    HIP_TRY(ctx, up(o_oinfo, oinfo.data(), oinfo.size() * 8));
+    HIP_TRY(ctx, up(o_ooff, pb->obs_off, ((size_t)P + 1) * 4));
+    HIP_TRY(ctx, up(o_ofr, pb->obs_frame, (size_t)O * 4));
+    HIP_TRY(ctx, up(o_opt, plan.obs_point.data(), (size_t)O * 4));
+    HIP_TRY(ctx, up(o_froff, plan.fr_off.data(), ((size_t)F + 1) * 4));
+    HIP_TRY(ctx, up(o_frobs, plan.fr_obs.data(), (size_t)O * 4));
+    HIP_TRY(ctx, up(o_first, plan.first.data(), (size_t)F * 4));
+    HIP_TRY(ctx, up(o_row, plan.row_off.data(), ((size_t)F + 1) * 4));
+    HIP_TRY(ctx, up(o_brow, plan.blk_row.data(), B * 4));
+    HIP_TRY(ctx, up(o_last, plan.last.data(), (size_t)F * 4));
+    HIP_TRY(ctx, up(o_poff, plan.pair_off.data(), (B + 1) * 4));
+    HIP_TRY(ctx, up(o_pa, plan.pair_a.data(), NP * 4));
+    HIP_TRY(ctx, up(o_pc, plan.pair_c.data(), NP * 4));
+
+    BasDev d{};
+    d.n_frames = F, d.n_points = P, d.n_obs = O, d.n_blocks = (int)B;
+    d.cam[0] = pb->K[0], d.cam[1] = pb->K[1], d.cam[2] = pb->K[2], d.cam[3] = pb->K[4], d.cam[4] = pb->K[5];
+    d.pose0 = dp(o_pose0), d.w = dp(o_w), d.pts0 = dp(o_pts0), d.pinfo = dp(o_pinfo);
+    d.obs_off = ip(o_ooff), d.obs_frame = ip(o_ofr), d.obs_point = ip(o_opt), d.obs_uv = dp(o_uv), d.oinfo = dp(o_oinfo);
+    d.fr_off = ip(o_froff), d.fr_obs = ip(o_frobs);
+    d.first = ip(o_first), d.row_off = ip(o_row), d.blk_row = ip(o_brow), d.last = ip(o_last);
+    d.pair_off = ip(o_poff), d.pair_a = ip(o_pa), d.pair_c = ip(o_pc);
+    PgdDev pd{};
+    bind_work(base, wk, d, pd);
+    int cb = 0;
+    // the plan's lists and the packed inputs have been read once the solver has read its first cost
+    if ((st = bas_solve(ctx, d, pd, params, plan.widest, result, &cb)) != MVS_OK)
+        return st;
     if (want_cov)
         launch_bas_cov(d, s);
     HIP_TRY(ctx, hipGetLastError());
@@ -253,6 +296,208 @@ mvs_status mvs_ba_refine_sparse(mvs_ctx *ctx, const mvs_ba_sparse *pb, const mvs
         HIP_TRY(ctx, hipMemcpyAsync(pose_cov_out, d.pose_cov, 36 * (size_t)F * 8, hipMemcpyDeviceToHost, s));
     if (point_cov_out)
         HIP_TRY(ctx, hipMemcpyAsync(point_cov_out, d.point_cov, 9 * (size_t)P * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    return MVS_OK;
+}
+
+// ---- the global problem of a sequence that has been run -----------------------------------------
+mvs_status mvs_seq_refine_global(mvs_seq *q, const mvs_seq_global_params *gp, const mvs_refine_params *params,
+                                 mvs_ba_sparse_result *result)
+{
+    if (!q || !gp || !result || !refine_params_ok(params) || !q->ran || q->n_frames < 2 || !(gp->sigma_px > 0.0) ||
+        !mvs_seqg::track_frames_ok(gp->max_track_frames))
+        return MVS_ERR_INVALID_ARG;
+    if (q->n_frames > mvs_bas::kMaxFrames)
+        return MVS_ERR_CAPACITY;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const BatchDev &bd = q->batch->d;
+    const size_t F = (size_t)q->n_frames, N = (size_t)bd.max_kp, I = sizeof(int32_t);
+    q->glob_counted = q->glob_built = q->glob_solved = q->glob_cov = false;   // growing frees what an earlier call left
+
+    // stage 1, sized by the sequence alone: the link tables, one word per keypoint for the depth, the rank, the observation
+    // offset and the observation itself, and the per-frame counts and scans
+    Carve A{64};
+    const size_t a_succ = A.take((F - 1) * N * I), a_pred = A.take(F * N * I), a_rtp = A.take((F - 1) * N * I);
+    const size_t a_depth = A.take(F * N * I), a_rank = A.take(F * N * I), a_oofs = A.take(F * N * I), a_kpo = A.take(F * N * I);
+    const size_t a_frp = A.take(F * I), a_fro = A.take(F * I), a_reach = A.take(F * I), a_frq = A.take(F * 8);
+    const size_t a_ptb = A.take(F * I), a_obb = A.take(F * I);
+    const size_t a_first = A.take(F * I), a_row = A.take((F + 1) * I), a_last = A.take(F * I);
+    const size_t a_cnt = A.take(F * I), a_froff = A.take((F + 1) * I), a_rowp = A.take(F * I), a_rowb = A.take((F + 1) * I);
+    const size_t a_state = A.take(sizeof(SeqGlobState));
+    mvs_status st = ws_grow(ctx, q->glob_tab, A.total());
+    if (st != MVS_OK)
+        return st;
+    char *tab = q->glob_tab.ptr();
+    auto ti = [&](size_t o) { return reinterpret_cast<int32_t *>(tab + o); };
+    SeqGlobDev g{};
+    g.w.n_frames = q->n_frames;
+    g.w.max_kp = bd.max_kp;
+    g.w.results = bd.results;
+    g.w.matches = bd.matches;
+    g.w.mask = bd.mask;
+    g.w.points = bd.points;
+    g.w.point_idx = bd.point_idx;
+    g.w.kp = bd.kp1;
+    g.w.oct = bd.oct1;
+    g.w.K = bd.K;
+    g.w.traj_R = q->chain.traj_R;
+    g.w.traj_t = q->chain.traj_t;
+    g.w.traj_sigma = q->chain.traj_sigma;
+    g.w.succ = ti(a_succ), g.w.pred = ti(a_pred), g.w.row_to_point = ti(a_rtp);
+    // frame 0 carries anchor_sigma, the others pose_sigma: variances sigma * sigma, weights as the sparse entry derives them;
+    // every point the prior point_sigma^2 I, an observation the covariance (sigma_px * 2^octave)^2 I
+    for (int k = 0; k < 6; ++k) {
+        const double a = params->anchor_sigma[k / 3], m = params->pose_sigma[k / 3];
+        g.w.w_anchor[k] = prior_weight(a * a);
+        g.w.w_pose[k] = prior_weight(m * m);
+    }
+    const double pv = params->point_sigma * params->point_sigma;
+    const double pc[9] = {pv, 0.0, 0.0, 0.0, pv, 0.0, 0.0, 0.0, pv};
+    point_info(pc, g.w.pinfo);
+    for (int oc = 0; oc <= kSeqWinMaxOctave; ++oc) {
+        const double sd = std::ldexp(gp->sigma_px, oc);
+        const double cv[4] = {sd * sd, 0.0, 0.0, sd * sd};
+        obs_info(cv, g.w.oinfo[oc]);
+    }
+    g.T = gp->max_track_frames;
+    g.depth = ti(a_depth), g.rank = ti(a_rank), g.oofs = ti(a_oofs), g.kp_obs = ti(a_kpo);
+    g.fr_points = ti(a_frp), g.fr_nobs = ti(a_fro), g.fr_reach = ti(a_reach);
+    g.fr_pairs = reinterpret_cast<int64_t *>(tab + a_frq);
+    g.pt_base = ti(a_ptb), g.ob_base = ti(a_obb);
+    g.first = ti(a_first), g.row_off = ti(a_row), g.last = ti(a_last);
+    g.fr_cnt = ti(a_cnt), g.fr_off = ti(a_froff), g.row_pairs = ti(a_rowp), g.row_base = ti(a_rowb);
+    g.state = reinterpret_cast<SeqGlobState *>(tab + a_state);
+    hipStream_t s = ctx_stream(ctx);
+    launch_seq_glob_count(g, s);
+    HIP_TRY(ctx, hipGetLastError());
+    // the one read before the LM loop: the counts, and the camera the solver takes by value
+    SeqGlobState hs{};
+    double K[9];
+    HIP_TRY(ctx, hipMemcpyAsync(&hs, g.state, sizeof(hs), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(K, bd.K, sizeof(K), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    const mvs_seqg::Counts fit = mvs_seqg::counts_status((int64_t)F, hs.n_points, hs.n_obs, hs.blocks, hs.pairs);
+    if (fit == mvs_seqg::kTooLarge)
+        return MVS_ERR_CAPACITY;
+    g.n_points = hs.n_points, g.n_obs = hs.n_obs, g.n_blocks = (int)hs.blocks, g.n_pairs = hs.pairs;
+    q->gl = g;
+    q->glob_counted = true;
+    if (fit == mvs_seqg::kNoPoints) {
+        mvs_ba_sparse_result none{};
+        none.envelope_blocks = (int32_t)hs.blocks, none.widest_row = hs.widest, none.bad_frame = -1;
+        *result = none;
+        q->glob_res = none;
+        return MVS_NO_MODEL;
+    }
+
+    // stage 2, sized by the counts: the problem, the plan's lists, the solver's arrays (covariances included: the sweep runs
+    // when a download asks for them)
+    const size_t P = (size_t)hs.n_points, O = (size_t)hs.n_obs, B = (size_t)hs.blocks, NP = (size_t)hs.pairs;
+    Carve L{64};
+    const size_t o_pose0 = L.take(12 * F * 8), o_w = L.take(6 * F * 8), o_pts0 = L.take(3 * P * 8), o_pinfo = L.take(6 * P * 8);
+    const size_t o_uv = L.take(2 * O * 8), o_oinfo = L.take(3 * O * 8);
+    const size_t o_ooff = L.take((P + 1) * I), o_hf = L.take(P * I), o_hk = L.take(P * I);
+    const size_t o_ofr = L.take(O * I), o_opt = L.take(O * I), o_okp = L.take(O * I), o_frobs = L.take(O * I);
+    const size_t o_brow = L.take(B * I), o_prel = L.take(B * I), o_poff = L.take((B + 1) * I);
+    const size_t o_pa = L.take(NP * I), o_pc = L.take(NP * I);
+    const BasWork wk = carve_work(L, F, P, O, B, true, true);
+    if ((st = ws_grow(ctx, q->glob, L.total())) != MVS_OK)
+        return st;
+    char *base = q->glob.ptr();
+    auto dp = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
+    auto ip = [&](size_t o) { return reinterpret_cast<int32_t *>(base + o); };
+    g.pose0 = dp(o_pose0), g.wts = dp(o_w), g.pts0 = dp(o_pts0), g.pinfo = dp(o_pinfo);
+    g.obs_uv = dp(o_uv), g.oinfo = dp(o_oinfo);
+    g.obs_off = ip(o_ooff), g.head_frame = ip(o_hf), g.head_kp = ip(o_hk);
+    g.obs_frame = ip(o_ofr), g.obs_point = ip(o_opt), g.obs_kp = ip(o_okp), g.fr_obs = ip(o_frobs);
+    g.blk_row = ip(o_brow), g.pair_rel = ip(o_prel), g.pair_off = ip(o_poff), g.pair_a = ip(o_pa), g.pair_c = ip(o_pc);
+    HIP_TRY(ctx, hipMemsetAsync(g.kp_obs, 0xff, F * N * I, s));
+    launch_seq_glob_build(g, s);
+    HIP_TRY(ctx, hipGetLastError());
+    q->gl = g;
+    q->glob_built = true;
+
+    BasDev d{};
+    d.n_frames = (int)F, d.n_points = (int)P, d.n_obs = (int)O, d.n_blocks = (int)B;
+    d.cam[0] = K[0], d.cam[1] = K[1], d.cam[2] = K[2], d.cam[3] = K[4], d.cam[4] = K[5];
+    d.pose0 = g.pose0, d.w = g.wts, d.pts0 = g.pts0, d.pinfo = g.pinfo;
+    d.obs_off = g.obs_off, d.obs_frame = g.obs_frame, d.obs_point = g.obs_point, d.obs_uv = g.obs_uv, d.oinfo = g.oinfo;
+    d.fr_off = g.fr_off, d.fr_obs = g.fr_obs;
+    d.first = g.first, d.row_off = g.row_off, d.blk_row = g.blk_row, d.last = g.last;
+    d.pair_off = g.pair_off, d.pair_a = g.pair_a, d.pair_c = g.pair_c;
+    PgdDev pd{};
+    bind_work(base, wk, d, pd);
+    int cb = 0;
+    st = bas_solve(ctx, d, pd, params, hs.widest, result, &cb);
+    if (st != MVS_OK && st != MVS_NO_MODEL)
+        return st;
+    q->glob_bas = d;
+    q->glob_cur = cb;
+    q->glob_res = *result;
+    q->glob_solved = true;
+    return st;
+}
+
+mvs_status mvs_seq_global_counts(mvs_seq *q, int32_t *n_points, int32_t *n_obs)
+{
+    if (!q || !q->glob_counted)
+        return MVS_ERR_INVALID_ARG;
+    if (n_points)
+        *n_points = q->gl.n_points;
+    if (n_obs)
+        *n_obs = q->gl.n_obs;
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_download_global(mvs_seq *q, double *poses, double *points, double *pose_cov, double *point_cov)
+{
+    if (!q || !q->glob_counted)
+        return MVS_ERR_INVALID_ARG;
+    if (!q->glob_solved || !q->glob_res.ok)
+        return MVS_NO_MODEL;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const BasDev &d = q->glob_bas;
+    const size_t F = (size_t)d.n_frames, P = (size_t)d.n_points;
+    hipStream_t s = ctx_stream(ctx);
+    if ((pose_cov || point_cov) && !q->glob_cov) {   // the sweep continues from the factorisation the solver ended on
+        launch_bas_cov(d, s);
+        HIP_TRY(ctx, hipGetLastError());
+        q->glob_cov = true;
+    }
+    if (poses)
+        HIP_TRY(ctx, hipMemcpyAsync(poses, d.pose[q->glob_cur], 12 * F * 8, hipMemcpyDeviceToHost, s));
+    if (points)
+        HIP_TRY(ctx, hipMemcpyAsync(points, d.pts[q->glob_cur], 3 * P * 8, hipMemcpyDeviceToHost, s));
+    if (pose_cov)
+        HIP_TRY(ctx, hipMemcpyAsync(pose_cov, d.pose_cov, 36 * F * 8, hipMemcpyDeviceToHost, s));
+    if (point_cov)
+        HIP_TRY(ctx, hipMemcpyAsync(point_cov, d.point_cov, 9 * P * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_download_global_problem(mvs_seq *q, int32_t *obs_off, int32_t *obs_frame, int32_t *obs_kp, int32_t *head_frame,
+                                           int32_t *head_kp, double *point_guess, double *obs_uv)
+{
+    if (!q || !q->glob_built)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const SeqGlobDev &g = q->gl;
+    const size_t P = (size_t)g.n_points, O = (size_t)g.n_obs, I = sizeof(int32_t);
+    hipStream_t s = ctx_stream(ctx);
+    auto get = [&](void *dst, const void *src, size_t bytes) {
+        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    };
+    HIP_TRY(ctx, get(obs_off, g.obs_off, (P + 1) * I));
+    HIP_TRY(ctx, get(obs_frame, g.obs_frame, O * I));
+    HIP_TRY(ctx, get(obs_kp, g.obs_kp, O * I));
+    HIP_TRY(ctx, get(head_frame, g.head_frame, P * I));
+    HIP_TRY(ctx, get(head_kp, g.head_kp, P * I));
+    HIP_TRY(ctx, get(point_guess, g.pts0, 3 * P * 8));
+    HIP_TRY(ctx, get(obs_uv, g.obs_uv, 2 * O * 8));
     HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }

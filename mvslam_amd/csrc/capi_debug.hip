@@ -411,4 +411,40 @@ int mvs_debug_rounding_probe(mvs_ctx *ctx, const double *in19, int n, double *ou
     return probe_io(ctx, in, ib, 1, out, ob, 1,
                     [&](unsigned char **d) { launch_rounding_probe((const double *)d[0], n, (double *)d[1], ctx_stream(ctx)); });
 }
+
+// the plan lists the device built for the last mvs_seq_refine_global (seq_global.hip), to be compared with mvs_bas::plan on the
+// downloaded CSR.  counts[6] = {frames, points, observations, blocks, pairs, widest row}; every list may be NULL: first[F],
+// row_off[F + 1], blk_row[blocks], last[F], obs_point[O], fr_off[F + 1], fr_obs[O], pair_off[blocks + 1], pair_a / pair_c[pairs]
+int mvs_debug_seq_global_plan(mvs_seq *q, int64_t *counts, int32_t *first, int32_t *row_off, int32_t *blk_row, int32_t *last,
+                              int32_t *obs_point, int32_t *fr_off, int32_t *fr_obs, int32_t *pair_off, int32_t *pair_a,
+                              int32_t *pair_c)
+{
+    if (!q || !q->glob_built)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, sync_stream(ctx));
+    const SeqGlobDev &g = q->gl;
+    const size_t F = (size_t)g.w.n_frames, O = (size_t)g.n_obs, B = (size_t)g.n_blocks, NP = (size_t)g.n_pairs, I = sizeof(int32_t);
+    if (counts) {
+        SeqGlobState hs{};
+        HIP_TRY(ctx, hipMemcpy(&hs, g.state, sizeof(hs), hipMemcpyDeviceToHost));
+        counts[0] = (int64_t)F, counts[1] = hs.n_points, counts[2] = hs.n_obs, counts[3] = hs.blocks, counts[4] = hs.pairs;
+        counts[5] = hs.widest;
+    }
+    auto get = [&](void *dst, const void *src, size_t bytes) {
+        return dst && bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    HIP_TRY(ctx, get(first, g.first, F * I));
+    HIP_TRY(ctx, get(row_off, g.row_off, (F + 1) * I));
+    HIP_TRY(ctx, get(blk_row, g.blk_row, B * I));
+    HIP_TRY(ctx, get(last, g.last, F * I));
+    HIP_TRY(ctx, get(obs_point, g.obs_point, O * I));
+    HIP_TRY(ctx, get(fr_off, g.fr_off, (F + 1) * I));
+    HIP_TRY(ctx, get(fr_obs, g.fr_obs, O * I));
+    HIP_TRY(ctx, get(pair_off, g.pair_off, (B + 1) * I));
+    HIP_TRY(ctx, get(pair_a, g.pair_a, NP * I));
+    HIP_TRY(ctx, get(pair_c, g.pair_c, NP * I));
+    return MVS_OK;
+}
 }  // extern "C"

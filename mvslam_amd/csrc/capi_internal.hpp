@@ -172,6 +172,17 @@ struct mvs_seq {
     bool loop_scored = false, loop_selected = false;
     bool loop_verified = false;        // the batch holds the results of the current list
     bool loop_edges_added = false;     // the graph's edges past *graph_n_built are loop edges
+    // mvs_seq_refine_global (capi_ba.hip): the link tables and counts (glob_tab, sized by the sequence alone), then the problem,
+    // the plan and the solver's arrays (glob, sized by the counts), resident until the next call or run
+    DevWorkspace glob_tab, glob;
+    SeqGlobDev gl{};
+    BasDev glob_bas{};                 // the solver's view of `glob`
+    int glob_cur = 0;                  // which of glob_bas.pose / pts holds the estimate
+    bool glob_counted = false;         // gl holds the counts of the last call
+    bool glob_built = false;           // ... and the problem and the plan have been built from them
+    bool glob_solved = false;          // ... and the solver has run on them: glob_res is its record
+    bool glob_cov = false;             // the covariance sweep has run at the estimate
+    mvs_ba_sparse_result glob_res{};
 };
 
 #define HIP_TRY(ctx_, expr)                                                                    \

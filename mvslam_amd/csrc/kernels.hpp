@@ -496,6 +496,49 @@ struct SeqWinDev {
     double *point_guess;               // [n_windows][max_points][3]
 };
 void launch_seq_windows(const SeqWinDev &d, hipStream_t stream);
+// seq_link_kernel alone: succ, pred and row_to_point of d (n_frames, max_kp and the resident state are read)
+void launch_seq_link(const SeqWinDev &d, hipStream_t stream);
+
+// ---- the global problem of a resident sequence (mvs_seq_refine_global; seq_global.hip) ----------
+// The tracks of seq_link_kernel's tables, whole (T = 0) or cut into pieces of T frames, become the points of ONE sparse
+// problem in the layout BasDev reads, and every list of mvs_bas::plan (ba_envelope.hpp) is built on the device.  Two stages
+// with one host read of SeqGlobState between them: the first is sized by the sequence alone, the second by the counts.
+struct SeqGlobState {
+    int32_t n_points, n_obs;
+    int64_t pairs;               // sum of t (t - 1) / 2 over the tracks' lengths
+    int64_t blocks;              // of the envelope
+    int32_t widest, reserved;
+};
+struct SeqGlobDev {
+    SeqWinDev w;                 // the sequence's resident state, the link tables, w_anchor, w_pose, pinfo, oinfo
+    int T;                       // max_track_frames: 0 = uncut
+    // stage 1
+    int32_t *depth;              // [n_frames][N] links behind keypoint i
+    int32_t *rank;               // [n_frames][N] in-frame rank of the point whose head keypoint i is, -1: none
+    int32_t *oofs;               // [n_frames][N] in-frame offset of that point's observations
+    int32_t *fr_points, *fr_nobs, *fr_reach;   // [n_frames] points and observations that start in a frame, the last frame they reach
+    int64_t *fr_pairs;           // [n_frames]
+    int32_t *pt_base, *ob_base;  // [n_frames] exclusive scans of fr_points / fr_nobs
+    int32_t *first, *row_off, *last;   // [n_frames], [n_frames + 1], [n_frames]: the envelope
+    SeqGlobState *state;
+    // stage 2
+    int n_points, n_obs, n_blocks;
+    int64_t n_pairs;
+    int32_t *kp_obs;             // [n_frames][N] the observation keypoint i makes, -1: none; then every frame's sorted list
+    int32_t *obs_off, *head_frame, *head_kp;   // [P + 1], [P], [P]
+    int32_t *obs_frame, *obs_point, *obs_kp;   // [O]
+    double *obs_uv, *oinfo;      // [O][2], [O][3]
+    double *pts0, *pinfo;        // [P][3], [P][6]
+    double *pose0, *wts;         // [n_frames][12], [n_frames][6]
+    int32_t *fr_cnt, *fr_off, *fr_obs;         // [n_frames], [n_frames + 1], [O]
+    int32_t *blk_row, *pair_rel; // [n_blocks]: the row of a block, the offset of its pairs inside the row
+    int32_t *row_pairs, *row_base;   // [n_frames], [n_frames + 1]: pairs of a row, their exclusive scan
+    int32_t *pair_off, *pair_a, *pair_c;       // [n_blocks + 1], [pairs], [pairs]
+};
+// links, depths, counts, scans and the envelope: everything SeqGlobState holds
+void launch_seq_glob_count(const SeqGlobDev &d, hipStream_t stream);
+// the problem (emit) and the plan's lists; kp_obs has been set to -1 by the caller
+void launch_seq_glob_build(const SeqGlobDev &d, hipStream_t stream);
 
 // ---- the tracking loop of a resident sequence (mvs_seq_track) -------------------------------------
 // Glue between the solvers of one step f (pair k = f - 1), one workgroup each: vo_join_kernel joins pair k's kept points with

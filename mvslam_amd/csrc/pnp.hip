@@ -1338,6 +1338,13 @@ void launch_seq_windows(const SeqWinDev &d, hipStream_t stream)
     hipLaunchKernelGGL(seq_window_assemble_kernel, dim3(d.n_windows), dim3(256), 0, stream, d);
 }
 
+void launch_seq_link(const SeqWinDev &d, hipStream_t stream)
+{
+    if (d.n_frames < 2)
+        return;
+    hipLaunchKernelGGL(seq_link_kernel, dim3(d.n_frames - 1), dim3(256), 0, stream, d);
+}
+
 void launch_pnp(const PnpDev &p, hipStream_t stream)
 {
     const int Q = p.n_problems;
