@@ -621,6 +621,43 @@ mvs_status mvs_ba_refine_sparse(mvs_ctx *ctx, const mvs_ba_sparse *problem, cons
                                 double *points_out /* n_points x 3, may be NULL */,
                                 double *pose_cov_out /* n_frames x 36, may be NULL */,
                                 double *point_cov_out /* n_points x 9, may be NULL */);
+/* Robust losses on the reprojection terms of the sparse bundle adjustment, with per-observation statistics (DESIGN.md section
+ * 4.7.6; GTSAM: noiseModel::Robust on the projection factors).  New symbols only: mvs_abi_version stays 4.
+ * A switch of the context, MVS_BA_LOSS_NONE by default: with it every call launches what it launched before the switch
+ * existed and returns the bytes it returned.  mvs_ba_refine_sparse and mvs_seq_refine_global honour it; mvs_ba_refine,
+ * mvs_ba_refine_window(s), mvs_seq_refine_windows, mvs_seq_track and every *_refine of pairs IGNORE it.
+ *   cost   observation o has the residual r_o (2) and the information matrix W_o; s_o = r_o^T W_o r_o, x = sqrt(s_o).  The
+ *          cost becomes 1/2 [pose priors + point priors + sum_o rho2(s_o)], rho2 and the weight w as for the pose graphs:
+ *     MVS_BA_LOSS_NONE    rho2 = s                                    w = 1
+ *     MVS_BA_LOSS_HUBER   rho2 = s if x <= k, else (2 k) x - k k      w = 1 if x <= k, else k / x
+ *     MVS_BA_LOSS_CAUCHY  rho2 = (k k) log1p(s / (k k))               w = (k k) / (k k + s)
+ *          The priors are never robustified.  An observation behind its camera keeps its fixed residual (2 fx, 2 fx) and its
+ *          zero Jacobians and gets rho2 of that s like any other term.
+ *   step   IRLS: observation o enters every sum of the linearisation with the information matrix w(s_o) W_o, nothing else
+ *          changes.  s by the cost's own statements (wr0 = fma(W1, r1, W0 r0), wr1 = fma(W2, r1, W1 r0), s = fma(r1, wr1,
+ *          r0 wr0)), one sqrt for x, one division for w (the Cauchy cost: log1p of one quotient), three products w W0, w W1,
+ *          w W2.  Binary64, no atomics, the same input gives the same bytes; Huber with k = 1e30 has w = 1 and rho2 = s
+ *          exactly and returns the bytes of MVS_BA_LOSS_NONE.
+ *   LM     the rule, the exits, error, error_initial, rejected_steps and failed_solves are those of mvs_ba_refine_sparse, on
+ *          the robust cost: a candidate is accepted when its robust cost is not above the current one.
+ *   covariances  pose_cov_out and point_cov_out continue from the lambda = 0 factorisation the solver ends with, which under a
+ *          loss is the REWEIGHTED system: they are the covariances of the reweighted linearisation (what GTSAM's Marginals
+ *          gives over robust factors).  The pose graphs' marginals, in contrast, stay Gaussian under their loss: that sweep has
+ *          an edge evaluation of its own, this one reuses the solver's factor.
+ * MVS_ERR_INVALID_ARG, the setting stays: a loss that is none of the three; with a loss other than NONE, a k that is not finite
+ * and > 0. */
+#define MVS_BA_LOSS_NONE 0
+#define MVS_BA_LOSS_HUBER 1
+#define MVS_BA_LOSS_CAUCHY 2
+mvs_status mvs_ctx_set_ba_loss(mvs_ctx *ctx, int loss, double k);
+/* s_o = r_o^T W_o r_o of every observation of `problem` at the given poses and points, and its weight w(s_o) under the
+ * context's loss (1.0 under MVS_BA_LOSS_NONE).  The argument checks and status codes are mvs_ba_refine_sparse's (the limits of
+ * the plan apart: no plan and no envelope are built, only the observation arrays, the poses and the points are uploaded);
+ * non-finite poses or points are MVS_ERR_INVALID_ARG.  Nothing is written on an error.  Waits for the ctx stream. */
+mvs_status mvs_ba_sparse_obs_stats(mvs_ctx *ctx, const mvs_ba_sparse *problem,
+                                   const double *poses /* n_frames x 12, NULL: frame_pose */,
+                                   const double *points /* n_points x 3, NULL: points */,
+                                   double *chi2 /* n_obs */, double *weight /* n_obs, may be NULL */);
 /* Batched ImagePair::refine (front-end/image-pair.cpp:176-238) on a batch that has been run: every valid pair is refined
  * from its own results on the device.  Observations = the matched keypoints with the covariance
  * VisualFeature::get_point_estimates gives them (vision/visual-feature.cpp:192-207): stddev = (1 << kp.octave) * 0.5 px,
@@ -719,6 +756,11 @@ mvs_status mvs_seq_global_counts(mvs_seq *s, int32_t *n_points, int32_t *n_obs);
  * covariance sweep runs at the first call that asks for either.  MVS_NO_MODEL with every output untouched when the last
  * mvs_seq_refine_global ended with ok = 0. */
 mvs_status mvs_seq_download_global(mvs_seq *s, double *poses, double *points, double *pose_cov, double *point_cov);
+/* mvs_ba_sparse_obs_stats on the resident problem at the resident estimate of the last mvs_seq_refine_global, through device
+ * pointers, under the context's loss as it is set at this call: chi2 and weight (may be NULL) hold n_obs of
+ * mvs_seq_global_counts, and their bytes are those of mvs_ba_sparse_obs_stats on the downloaded problem and estimate.
+ * MVS_ERR_INVALID_ARG unless the last mvs_seq_refine_global on the current run ended with ok = 1.  Waits for the ctx stream. */
+mvs_status mvs_seq_global_obs_stats(mvs_seq *s, double *chi2, double *weight);
 /* The assembled problem, any pointer may be NULL: obs_off[n_points + 1], obs_frame[n_obs], obs_kp[n_obs] (the keypoint of
  * every observation in its frame), head_frame[n_points], head_kp[n_points], point_guess n_points x 3, obs_uv n_obs x 2. */
 mvs_status mvs_seq_download_global_problem(mvs_seq *s, int32_t *obs_off, int32_t *obs_frame, int32_t *obs_kp,

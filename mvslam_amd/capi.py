@@ -186,6 +186,7 @@ POSE_GRAPH_MAX_ENVELOPE_BLOCKS = 1 << 21
 MVS_PG_SOLVER_PCG, MVS_PG_SOLVER_DIRECT = 0, 1
 MVS_PG_LOSS_NONE, MVS_PG_LOSS_HUBER, MVS_PG_LOSS_CAUCHY = 0, 1, 2
 MVS_PG_LOSS_LOOP_EDGES = -1
+MVS_BA_LOSS_NONE, MVS_BA_LOSS_HUBER, MVS_BA_LOSS_CAUCHY = 0, 1, 2
 POSE_GRAPH_DIRECT_INFO_DTYPE = np.dtype([("envelope_blocks", "<i4"), ("widest_row", "<i4"), ("failed_solves", "<i4"),
                                          ("bad_node", "<i4"), ("min_pivot", "<f8"), ("failed_pivot", "<f8")])
 
@@ -287,6 +288,7 @@ EXPORTS = [
     "mvs_pose_graph_marginals", "mvs_seq_pose_graph_marginals",
     "mvs_ctx_set_pose_graph_solver", "mvs_ctx_pose_graph_direct_info",
     "mvs_ctx_set_pose_graph_loss", "mvs_pose_graph_edge_stats", "mvs_seq_pose_graph_edge_stats",
+    "mvs_ctx_set_ba_loss", "mvs_ba_sparse_obs_stats", "mvs_seq_global_obs_stats",
     "mvs_seq_refine_global", "mvs_seq_global_counts", "mvs_seq_download_global", "mvs_seq_download_global_problem",
 ]
 
@@ -365,6 +367,12 @@ def lib():
         _lib.mvs_seq_global_counts.argtypes = [C.c_void_p] * 3
         _lib.mvs_seq_download_global.argtypes = [C.c_void_p] * 5
         _lib.mvs_seq_download_global_problem.argtypes = [C.c_void_p] * 8
+        _lib.mvs_ctx_set_ba_loss.restype = C.c_int
+        _lib.mvs_ctx_set_ba_loss.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        _lib.mvs_ba_sparse_obs_stats.restype = C.c_int
+        _lib.mvs_ba_sparse_obs_stats.argtypes = [C.c_void_p, C.c_void_p] + [C.POINTER(C.c_double)] * 4
+        _lib.mvs_seq_global_obs_stats.restype = C.c_int
+        _lib.mvs_seq_global_obs_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib.mvs_vo_params_default.restype = None
         _lib.mvs_vo_init_params_default.restype = None
     return _lib
@@ -475,6 +483,25 @@ def pinned_free(a):
         lib().mvs_host_free(p)
 
 
+def _ba_sparse_problem(K, frame_pose, frame_prior_var, points, point_prior_cov, obs_off, obs_frame, obs_uv, obs_cov, n_frames):
+    """(mvs_ba_sparse, the arrays it points into, n_frames, n_points, n_obs) of ba_refine_sparse's keyword arguments"""
+    fp, fv = _f64(frame_pose).reshape(-1, 12), _f64(frame_prior_var).reshape(-1, 6)
+    pg, Kc = _f64(points).reshape(-1, 3), _f64(K, (9,))
+    off = np.ascontiguousarray(obs_off, dtype=np.int32)
+    ofr = np.ascontiguousarray(obs_frame, dtype=np.int32)
+    uv = _f64(obs_uv).reshape(-1, 2)
+    F, m, n_obs = len(fp) if n_frames is None else n_frames, len(pg), len(ofr)
+    pb = BaSparse()
+    pb.n_frames, pb.n_points, pb.n_obs = F, m, n_obs
+    pb.K, pb.frame_pose, pb.frame_prior_var, pb.points = (_ptr(Kc, C.c_double), _ptr(fp, C.c_double), _ptr(fv, C.c_double),
+                                                          _ptr(pg, C.c_double))
+    pc = None if point_prior_cov is None else _f64(point_prior_cov, (m, 9))
+    oc = None if obs_cov is None else _f64(obs_cov, (n_obs, 4))
+    pb.point_prior_cov, pb.obs_cov = _ptr(pc, C.c_double), _ptr(oc, C.c_double)
+    pb.obs_off, pb.obs_frame, pb.obs_uv = _ptr(off, C.c_int32), _ptr(ofr, C.c_int32), _ptr(uv, C.c_double)
+    return pb, (Kc, fp, fv, pg, pc, oc, off, ofr, uv), F, m, n_obs
+
+
 class Context:
     """One mvs_ctx: one HIP stream on one GPU."""
 
@@ -523,6 +550,12 @@ class Context:
         (MVS_ERR_INVALID_ARG) and leaves the previous one in force."""
         self._check(lib().mvs_ctx_set_pose_graph_loss(self._h, C.c_int(loss), C.c_double(k), C.c_int32(first_edge)),
                     "mvs_ctx_set_pose_graph_loss")
+
+    def set_ba_loss(self, loss, k=1.0):
+        """The robust loss of the observation terms of ba_refine_sparse and Sequence.refine_global (mvs_ctx_set_ba_loss):
+        MVS_BA_LOSS_NONE (default), MVS_BA_LOSS_HUBER or MVS_BA_LOSS_CAUCHY with the constant k.  Every other bundle adjustment
+        ignores it.  A refused setting raises MvsError (MVS_ERR_INVALID_ARG) and leaves the earlier one in place."""
+        self._check(lib().mvs_ctx_set_ba_loss(self._h, C.c_int(loss), C.c_double(k)), "mvs_ctx_set_ba_loss")
 
     def pose_graph_edge_stats(self, graph, poses=None):
         """mvs_pose_graph_edge_stats: (status, chi2 [E], weight [E]) at `poses` (None: the graph's node_pose) -- the squared norm
@@ -1000,20 +1033,8 @@ class Context:
         MVS_NO_MODEL the output arrays are as they were allocated (zero).  n_frames overrides the count taken from
         frame_pose (the refusal tests)."""
         params = params or default_refine_params()
-        fp, fv = _f64(frame_pose).reshape(-1, 12), _f64(frame_prior_var).reshape(-1, 6)
-        pg, Kc = _f64(points).reshape(-1, 3), _f64(K, (9,))
-        off = np.ascontiguousarray(obs_off, dtype=np.int32)
-        ofr = np.ascontiguousarray(obs_frame, dtype=np.int32)
-        uv = _f64(obs_uv).reshape(-1, 2)
-        F, m, n_obs = len(fp) if n_frames is None else n_frames, len(pg), len(ofr)
-        pb = BaSparse()
-        pb.n_frames, pb.n_points, pb.n_obs = F, m, n_obs
-        pb.K, pb.frame_pose, pb.frame_prior_var, pb.points = (_ptr(Kc, C.c_double), _ptr(fp, C.c_double), _ptr(fv, C.c_double),
-                                                              _ptr(pg, C.c_double))
-        pc = None if point_prior_cov is None else _f64(point_prior_cov, (m, 9))
-        oc = None if obs_cov is None else _f64(obs_cov, (n_obs, 4))
-        pb.point_prior_cov, pb.obs_cov = _ptr(pc, C.c_double), _ptr(oc, C.c_double)
-        pb.obs_off, pb.obs_frame, pb.obs_uv = _ptr(off, C.c_int32), _ptr(ofr, C.c_int32), _ptr(uv, C.c_double)
+        pb, _keep, F, m, n_obs = _ba_sparse_problem(K, frame_pose, frame_prior_var, points, point_prior_cov, obs_off, obs_frame,
+                                                    obs_uv, obs_cov, n_frames)
         res = BaSparseResult()
         poses, pts = np.zeros((max(F, 1), 12)), np.zeros((max(m, 1), 3))
         pcv = np.zeros((max(F, 1), 6, 6)) if pose_cov else None
@@ -1026,6 +1047,24 @@ class Context:
                    pose_cov=pcv, point_cov=ptc,
                    raw=b"".join(a.tobytes() for a in (poses, pts, pcv, ptc) if a is not None) + bytes(res))
         return out
+
+    def ba_sparse_obs_stats(self, K, frame_pose, frame_prior_var, points, point_prior_cov, obs_off, obs_frame, obs_uv,
+                            obs_cov=None, poses=None, points_at=None, n_frames=None, weight=True):
+        """mvs_ba_sparse_obs_stats: (status, chi2 [n_obs], weight [n_obs]) of the problem ba_refine_sparse's arguments describe,
+        at `poses` [F, 12] and `points_at` [P, 3] (None: the problem's frame_pose / points): s_o = r_o^T W_o r_o and w(s_o)
+        under the context's loss (set_ba_loss; 1.0 without one).  weight=False passes NULL and returns None for it.  A refused
+        call returns its status with both arrays as they were allocated (zero)."""
+        pb, _keep, F, m, n_obs = _ba_sparse_problem(K, frame_pose, frame_prior_var, points, point_prior_cov, obs_off, obs_frame,
+                                                    obs_uv, obs_cov, n_frames)
+        X = None if poses is None else _f64(poses).reshape(-1, 12)
+        Y = None if points_at is None else _f64(points_at).reshape(-1, 3)
+        chi2 = np.zeros(max(n_obs, 1))
+        wt = np.zeros(max(n_obs, 1)) if weight else None
+        st = lib().mvs_ba_sparse_obs_stats(self._h, C.byref(pb), _ptr(X, C.c_double), _ptr(Y, C.c_double), _ptr(chi2, C.c_double),
+                                           _ptr(wt, C.c_double))
+        if st not in (MVS_OK, MVS_ERR_INVALID_ARG, MVS_ERR_CAPACITY):
+            self._check(st, "mvs_ba_sparse_obs_stats")
+        return st, chi2[:n_obs], None if wt is None else wt[:n_obs]
 
     def find_fundamental_matrix(self, p1, p2):
         p1, p2 = _f64(p1, (16,)), _f64(p2, (16,))
@@ -1446,6 +1485,16 @@ class Sequence:
         self.ctx._check(st, "mvs_seq_download_global", allow_no_model=True)
         return dict(status=st, R=poses[:, :9].reshape(-1, 3, 3).copy(), t=poses[:, 9:].copy(), points=pts, pose_cov=pcv,
                     point_cov=ptc, raw=b"".join(a.tobytes() for a in (poses, pts, pcv, ptc) if a is not None))
+
+    def global_obs_stats(self):
+        """mvs_seq_global_obs_stats: (chi2 [n_obs], weight [n_obs]) of the resident global problem's observations at the
+        estimate of the last refine_global(), under the context's loss (Context.set_ba_loss).  Raises MvsError
+        (MVS_ERR_INVALID_ARG) unless that call ended with ok."""
+        _, O = self.global_counts()   # refuses (MVS_ERR_INVALID_ARG) where there has been no refine_global()
+        chi2, wt = np.zeros(max(O, 1)), np.zeros(max(O, 1))
+        st = lib().mvs_seq_global_obs_stats(self._h, _ptr(chi2, C.c_double), _ptr(wt, C.c_double))
+        self.ctx._check(st, "mvs_seq_global_obs_stats")
+        return chi2[:O], wt[:O]
 
     def download_global_problem(self):
         """the problem the last refine_global() assembled: obs_off [P + 1], obs_frame / obs_kp [O], head_frame / head_kp [P],

@@ -380,6 +380,14 @@ inline RansacConfig &ransac_config()
 #ifndef MVSLAM_POSE_GRAPH_LOSS_FIRST_EDGE
 #define MVSLAM_POSE_GRAPH_LOSS_FIRST_EDGE 0
 #endif
+// the robust loss of ba_frame_pose_and_point's reprojection terms (mvs_ctx_set_ba_loss): 0 none, 1
+// Huber, 2 Cauchy, with its constant.  With a loss every frame set goes through the sparse entry, which honours it
+#ifndef MVSLAM_BA_LOSS
+#define MVSLAM_BA_LOSS 0
+#endif
+#ifndef MVSLAM_BA_LOSS_K
+#define MVSLAM_BA_LOSS_K 1.0
+#endif
 // one mvs_ctx per host thread; throws if there is no HIP device (there is no CPU fallback)
 inline mvs_ctx *context()
 {
@@ -406,6 +414,9 @@ inline mvs_ctx *context()
             mvs_ctx_set_pose_graph_loss(h.ctx, MVSLAM_POSE_GRAPH_LOSS, MVSLAM_POSE_GRAPH_LOSS_K, MVSLAM_POSE_GRAPH_LOSS_FIRST_EDGE) != MVS_OK)
             throw std::runtime_error("mvSLAM HIP backend: MVSLAM_POSE_GRAPH_LOSS must be 0 (none), 1 (Huber) or 2 (Cauchy), with "
                                      "MVSLAM_POSE_GRAPH_LOSS_K > 0 and MVSLAM_POSE_GRAPH_LOSS_FIRST_EDGE >= 0");
+        if (mvs_ctx_set_ba_loss(h.ctx, MVSLAM_BA_LOSS, MVSLAM_BA_LOSS_K) != MVS_OK)
+            throw std::runtime_error("mvSLAM HIP backend: MVSLAM_BA_LOSS must be 0 (none), 1 (Huber) or 2 (Cauchy), with "
+                                     "MVSLAM_BA_LOSS_K > 0");
     }
     return h.ctx;
 }
@@ -851,7 +862,8 @@ inline void ba_sparse_(const CameraIntrinsics &ci, const std::vector<Id::Type> &
 
 // Same signature as the reference.  Supported: 1 to 4096 frames (the reference itself builds one or two: sfm_refine,
 // pnp_refine, VisualOdometer::track_refine; up to eight go through mvs_ba_refine_window, nine and more through
-// mvs_ba_refine_sparse); diagonal frame priors.  With this one function forwarded,
+// mvs_ba_refine_sparse; with MVSLAM_BA_LOSS != 0 every frame set does, the window kernel having no loss); diagonal frame
+// priors.  With this one function forwarded,
 // sfm-refine.cpp, pnp-refine.cpp and visual-odometer.cpp stay untouched and GTSAM leaves the link line.
 inline void ba_frame_pose_and_point(const CameraIntrinsics &ci, const std::unordered_set<Id::Type> &frame_id,
                                     const std::unordered_set<Id::Type> &point_id,
@@ -874,7 +886,9 @@ inline void ba_frame_pose_and_point(const CameraIntrinsics &ci, const std::unord
     std::unordered_map<Id::Type, int> pidx;
     for (int i = 0; i < m; ++i)
         pidx[pids[i]] = i;
-    if (F > 8) {   // nine frames and more: the sparse entry, an observation a frame lacks is simply absent
+    // nine frames and more, or any frame set under a loss (the window kernel has none): the sparse entry, where an observation
+    // a frame lacks is simply absent
+    if (F > 8 || MVSLAM_BA_LOSS != 0) {
         hip::ba_sparse_(ci, fids, pids, pidx, frame_pose_guess, frame_pose_prior, point_guess, point_prior, frame_observation,
                         frame_pose_estimate, point_estimate, final_error);
         return;

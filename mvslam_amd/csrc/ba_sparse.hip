@@ -20,6 +20,10 @@
 //   covariances at the estimate: bas_selinv_kernel (ONE workgroup: the blocks of the scaled S^-1 inside the envelope by the
 //   selected-inversion recurrence, columns in descending order), bas_pose_cov_kernel, bas_zs_kernel, bas_y_kernel,
 //   bas_point_cov_kernel.
+//   robust losses (mvs_ctx_set_ba_loss) enter through three kernels of their own and nothing else:
+//   bas_robust_lin_kernel (bas_lin_kernel's statements, plus w(s_o) W_o into the array BasDev::oinfo then points at),
+//   bas_robust_terms_kernel (bas_terms_kernel's, with rho2(s_o) for an observation's term) and bas_obs_stats_kernel (s_o and
+//   w(s_o) at given values).  Every other kernel reads what those left; without a loss the launches are the ones they were.
 // One owner per entry everywhere, no floating-point atomics, binary64 with explicit FMAs: the same input gives the same bytes.
 //
 // Cam / fd2 / fd3 / fx2 / so3_exp / so3_log / so3_jrinv / pose_prior / project_lin and the 3 x 3 Cholesky of bas_point_kernel
@@ -501,6 +505,121 @@ __global__ __launch_bounds__(kBasThreads) void bas_terms_kernel(BasDev d, int wh
     d.terms[gid] = c;
 }
 
+// ---- robust losses (mvs_ctx_set_ba_loss) -----------------------------------------------------------
+// s = r^T W r of one observation: bas_terms_kernel's statements
+__device__ __forceinline__ double obs_chi2(const double (&r)[2], double W0, double W1, double W2)
+{
+    const double wr0 = fd2(W0, r[0], W1, r[1]), wr1 = fd2(W1, r[0], W2, r[1]);
+    return fma(r[1], wr1, r[0] * wr0);
+}
+// weight w(s) from s and x = sqrt(s): Huber 1 or k / x, Cauchy k^2 / (k^2 + s) -- posegraph.hip's pg_loss_weight
+__device__ __forceinline__ double bas_loss_weight(int loss, double k, double s, double x)
+{
+    if (loss == 1)
+        return x <= k ? 1.0 : k / x;
+    const double k2 = k * k;
+    return k2 / (k2 + s);
+}
+// rho2(s), the observation's term of twice the cost: one sqrt (the Cauchy cost: log1p of one quotient)
+__device__ __forceinline__ double bas_loss_rho2(int loss, double k, double s)
+{
+    if (loss == 1) {
+        const double x = sqrt(s);
+        return x <= k ? s : (2.0 * k) * x - k * k;
+    }
+    const double k2 = k * k;
+    return k2 * log1p(s / k2);
+}
+
+// bas_lin_kernel under a loss: the same 20 doubles of lin, and w(s_o) W_o for the build kernels
+__global__ __launch_bounds__(kBasThreads) void bas_robust_lin_kernel(BasDev d, int cur)
+{
+    const int o = blockIdx.x * kBasThreads + threadIdx.x;
+    if (o >= d.n_obs)
+        return;
+    if (o == 0)
+        d.state->bad_point = 0;   // bas_point_kernel, the next launch, sets it
+    const Cam cam = cam_of(d);
+    double R[9], t[3], p[3], r[2], Jc[12], Jp[6];
+    load_pose(d.pose[cur], d.obs_frame[o], R, t);
+    const double *pp = d.pts[cur] + 3 * (int64_t)d.obs_point[o];
+    p[0] = pp[0], p[1] = pp[1], p[2] = pp[2];
+    project_lin<true>(cam, R, t, p, d.obs_uv[2 * (int64_t)o], d.obs_uv[2 * (int64_t)o + 1], r, Jc, Jp);
+    double *L = d.lin + (int64_t)kBasLin * o;
+#pragma unroll
+    for (int k = 0; k < 12; ++k)
+        L[k] = Jc[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+        L[12 + k] = Jp[k];
+    L[18] = r[0];
+    L[19] = r[1];
+    const double W0 = d.oinfo0[3 * (int64_t)o], W1 = d.oinfo0[3 * (int64_t)o + 1], W2 = d.oinfo0[3 * (int64_t)o + 2];
+    const double s = obs_chi2(r, W0, W1, W2);
+    const double w = bas_loss_weight(d.loss, d.loss_k, s, sqrt(s));
+    double *Ww = d.oinfo_w + 3 * (int64_t)o;
+    Ww[0] = w * W0;
+    Ww[1] = w * W1;
+    Ww[2] = w * W2;
+}
+
+// bas_terms_kernel under a loss: rho2(s_o) for an observation, the priors as they are
+__global__ __launch_bounds__(kBasThreads) void bas_robust_terms_kernel(BasDev d, int which)
+{
+    const int64_t gid = (int64_t)blockIdx.x * kBasThreads + threadIdx.x;
+    const int64_t n = (int64_t)d.n_obs + d.n_points + d.n_frames;
+    if (gid >= n)
+        return;
+    double c = 0.0;
+    if (gid < d.n_obs) {
+        const int o = (int)gid;
+        const Cam cam = cam_of(d);
+        double R[9], t[3], p[3], r[2], Jc[12], Jp[6];
+        load_pose(d.pose[which], d.obs_frame[o], R, t);
+        const double *pp = d.pts[which] + 3 * (int64_t)d.obs_point[o];
+        p[0] = pp[0], p[1] = pp[1], p[2] = pp[2];
+        project_lin<false>(cam, R, t, p, d.obs_uv[2 * (int64_t)o], d.obs_uv[2 * (int64_t)o + 1], r, Jc, Jp);
+        const double W0 = d.oinfo0[3 * (int64_t)o], W1 = d.oinfo0[3 * (int64_t)o + 1], W2 = d.oinfo0[3 * (int64_t)o + 2];
+        c = bas_loss_rho2(d.loss, d.loss_k, obs_chi2(r, W0, W1, W2));
+    } else if (gid < (int64_t)d.n_obs + d.n_points) {
+        const int64_t i = gid - d.n_obs;
+        const double *p = d.pts[which] + 3 * i, *p0 = d.pts0 + 3 * i, *L = d.pinfo + 6 * i;
+        const double d0 = p[0] - p0[0], d1 = p[1] - p0[1], d2 = p[2] - p0[2];
+        c = fd3(d0, fd3(L[0], d0, L[1], d1, L[2], d2), d1, fd3(L[1], d0, L[3], d1, L[4], d2), d2,
+                fd3(L[2], d0, L[4], d1, L[5], d2));
+    } else {
+        const int f = (int)(gid - d.n_obs - d.n_points);
+        double R0[9], t0[3], R[9], t[3], e[6], Jw[9], Jv[9];
+        load_pose(d.pose0, f, R0, t0);
+        load_pose(d.pose[which], f, R, t);
+        pose_prior<false>(R0, t0, R, t, e, Jw, Jv);
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+            c = c + (e[k] * e[k]) * d.w[6 * (int64_t)f + k];
+    }
+    d.terms[gid] = c;
+}
+
+// s_o and w(s_o) of every observation at the given poses and points; w = 1 without a loss
+__global__ __launch_bounds__(kBasThreads) void bas_obs_stats_kernel(BasDev d, const double *poses, const double *points,
+                                                                    double *chi2, double *weight)
+{
+    const int o = blockIdx.x * kBasThreads + threadIdx.x;
+    if (o >= d.n_obs)
+        return;
+    const Cam cam = cam_of(d);
+    double R[9], t[3], p[3], r[2], Jc[12], Jp[6];
+    load_pose(poses, d.obs_frame[o], R, t);
+    const double *pp = points + 3 * (int64_t)d.obs_point[o];
+    p[0] = pp[0], p[1] = pp[1], p[2] = pp[2];
+    project_lin<false>(cam, R, t, p, d.obs_uv[2 * (int64_t)o], d.obs_uv[2 * (int64_t)o + 1], r, Jc, Jp);
+    const double W0 = d.oinfo0[3 * (int64_t)o], W1 = d.oinfo0[3 * (int64_t)o + 1], W2 = d.oinfo0[3 * (int64_t)o + 2];
+    const double s = obs_chi2(r, W0, W1, W2);
+    chi2[o] = s;
+    if (weight)
+        weight[o] = d.loss != 0 ? bas_loss_weight(d.loss, d.loss_k, s, sqrt(s)) : 1.0;
+}
+
 // out[blockIdx.x] = the sum of in[blockIdx.x * chunk .. + chunk) (clipped to n): thread t takes t, t + 256, ... in order, then
 // a fixed tree over the 256 partial sums.  The second stage is one workgroup with chunk >= n.
 __global__ __launch_bounds__(kBasThreads) void bas_reduce_kernel(const double *in, int64_t n, int64_t chunk, double *out)
@@ -713,7 +832,10 @@ void launch_bas_cost(const BasDev &d, int which, hipStream_t stream)
 {
     const int64_t n = (int64_t)d.n_obs + d.n_points + d.n_frames;
     const int chunks = (int)((n + kBasRedChunk - 1) / kBasRedChunk);
-    hipLaunchKernelGGL(bas_terms_kernel, dim3(grid_of(n)), dim3(kBasThreads), 0, stream, d, which);
+    if (d.loss != 0)
+        hipLaunchKernelGGL(bas_robust_terms_kernel, dim3(grid_of(n)), dim3(kBasThreads), 0, stream, d, which);
+    else
+        hipLaunchKernelGGL(bas_terms_kernel, dim3(grid_of(n)), dim3(kBasThreads), 0, stream, d, which);
     hipLaunchKernelGGL(bas_reduce_kernel, dim3(chunks), dim3(kBasThreads), 0, stream, d.terms, n, (int64_t)kBasRedChunk, d.partial);
     hipLaunchKernelGGL(bas_reduce_kernel, dim3(1), dim3(kBasThreads), 0, stream, d.partial, (int64_t)chunks, (int64_t)chunks,
                        &d.state->cost);
@@ -721,7 +843,10 @@ void launch_bas_cost(const BasDev &d, int which, hipStream_t stream)
 
 void launch_bas_build(const BasDev &d, int cur, double lam, hipStream_t stream)
 {
-    hipLaunchKernelGGL(bas_lin_kernel, dim3(grid_of(d.n_obs)), dim3(kBasThreads), 0, stream, d, cur);
+    if (d.loss != 0)
+        hipLaunchKernelGGL(bas_robust_lin_kernel, dim3(grid_of(d.n_obs)), dim3(kBasThreads), 0, stream, d, cur);
+    else
+        hipLaunchKernelGGL(bas_lin_kernel, dim3(grid_of(d.n_obs)), dim3(kBasThreads), 0, stream, d, cur);
     hipLaunchKernelGGL(bas_point_kernel, dim3(grid_of(d.n_points)), dim3(kBasThreads), 0, stream, d, cur, lam);
     hipLaunchKernelGGL(bas_z_kernel, dim3(grid_of(d.n_obs)), dim3(kBasThreads), 0, stream, d);
     hipLaunchKernelGGL(bas_prior_kernel, dim3((d.n_frames + 63) / 64), dim3(64), 0, stream, d, cur);
@@ -733,6 +858,12 @@ void launch_bas_update(const BasDev &d, int cur, hipStream_t stream)
 {
     hipLaunchKernelGGL(bas_zd_kernel, dim3(grid_of(d.n_obs)), dim3(kBasThreads), 0, stream, d);
     hipLaunchKernelGGL(bas_update_kernel, dim3(grid_of((int64_t)d.n_points + d.n_frames)), dim3(kBasThreads), 0, stream, d, cur);
+}
+
+void launch_bas_obs_stats(const BasDev &d, const double *poses, const double *points, double *chi2, double *weight,
+                          hipStream_t stream)
+{
+    hipLaunchKernelGGL(bas_obs_stats_kernel, dim3(grid_of(d.n_obs)), dim3(kBasThreads), 0, stream, d, poses, points, chi2, weight);
 }
 
 void launch_bas_cov(const BasDev &d, hipStream_t stream)

@@ -11,6 +11,7 @@
 
 #include "ba_envelope.hpp"
 #include "capi_internal.hpp"
+#include "pg_host.hpp"
 #include "seq_global_host.hpp"
 
 using namespace mvs_host;
@@ -47,7 +48,7 @@ double prior_weight(double var) { return var > 0.0 ? 1.0 / var : 0.0; }
 
 // the solver's own arrays as offsets into a workspace, laid out behind whatever the entry has laid out for its inputs and lists
 struct BasWork {
-    size_t pose[2], pts[2], lin, Li, gh, Z, zd, prior, D, g, sky, Cinv, y, x, terms, part, pst, bst, inv, colm, pcov, ptcov;
+    size_t pose[2], pts[2], lin, oinfo_w, Li, gh, Z, zd, prior, D, g, sky, Cinv, y, x, terms, part, pst, bst, inv, colm, pcov, ptcov;
     bool want_cov, pose_cov, point_cov;
 };
 BasWork carve_work(Carve &L, size_t F, size_t P, size_t O, size_t B, bool pose_cov, bool point_cov)
@@ -59,6 +60,7 @@ BasWork carve_work(Carve &L, size_t F, size_t P, size_t O, size_t B, bool pose_c
     k.pose[0] = L.take(12 * F * 8), k.pose[1] = L.take(12 * F * 8);
     k.pts[0] = L.take(3 * P * 8), k.pts[1] = L.take(3 * P * 8);
     k.lin = L.take((size_t)kBasLin * O * 8), k.Li = L.take(6 * P * 8), k.gh = L.take(3 * P * 8);
+    k.oinfo_w = L.take(3 * O * 8);   // w(s_o) W_o of a robust loss; not touched without one
     k.Z = L.take(18 * O * 8), k.zd = L.take(3 * O * 8);
     k.prior = L.take(27 * F * 8);
     k.D = L.take(21 * F * 8), k.g = L.take(6 * F * 8), k.sky = L.take(36 * B * 8);
@@ -71,10 +73,14 @@ BasWork carve_work(Carve &L, size_t F, size_t P, size_t O, size_t B, bool pose_c
     return k;
 }
 // d's counts, inputs and lists are set: this adds the solver's arrays, and pd, the step (pg_direct.hip's kernels on their
-// second source)
-void bind_work(char *base, const BasWork &k, BasDev &d, PgdDev &pd)
+// second source), and the context's robust loss: with one, the build kernels read the reweighted information matrices
+void bind_work(const mvs_ctx *ctx, char *base, const BasWork &k, BasDev &d, PgdDev &pd)
 {
     auto dp = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
+    d.loss = ctx->ba_loss, d.loss_k = ctx->ba_loss_k;
+    d.oinfo0 = d.oinfo, d.oinfo_w = dp(k.oinfo_w);
+    if (d.loss != MVS_BA_LOSS_NONE)
+        d.oinfo = d.oinfo_w;
     d.pose[0] = dp(k.pose[0]), d.pose[1] = dp(k.pose[1]), d.pts[0] = dp(k.pts[0]), d.pts[1] = dp(k.pts[1]);
     d.lin = dp(k.lin), d.Li = dp(k.Li), d.gh = dp(k.gh), d.Z = dp(k.Z), d.zd = dp(k.zd), d.D = dp(k.D), d.g = dp(k.g);
     d.prior = dp(k.prior);
@@ -92,8 +98,9 @@ void bind_work(char *base, const BasWork &k, BasDev &d, PgdDev &pd)
 
 // The solver over a problem whose inputs and lists lie in device memory (or are on their way there on the context's stream):
 // the LM loop from the guesses pose0 / pts0, then the factorisation at the estimate with lambda = 0, which decides ok and is
-// what launch_bas_cov continues from.  *result is filled whenever MVS_OK or MVS_NO_MODEL is returned; the estimate is then
-// d.pose[*cur_out] / d.pts[*cur_out].
+// what launch_bas_cov continues from.  Under a robust loss (d.loss) the cost is the robust one and every build the reweighted
+// one (IRLS), so that factorisation is the reweighted system's; the rule and the exits below do not know.  *result is filled
+// whenever MVS_OK or MVS_NO_MODEL is returned; the estimate is then d.pose[*cur_out] / d.pts[*cur_out].
 mvs_status bas_solve(mvs_ctx *ctx, const BasDev &d, const PgdDev &pd, const mvs_refine_params *params, int widest,
                      mvs_ba_sparse_result *result, int *cur_out)
 {
@@ -190,16 +197,9 @@ mvs_status bas_solve(mvs_ctx *ctx, const BasDev &d, const PgdDev &pd, const mvs_
     return ok ? MVS_OK : MVS_NO_MODEL;
 }
 
-}  // namespace
-
-extern "C" {
-
-mvs_status mvs_ba_refine_sparse(mvs_ctx *ctx, const mvs_ba_sparse *pb, const mvs_refine_params *params,
-                                mvs_ba_sparse_result *result, double *poses_out, double *points_out, double *pose_cov_out,
-                                double *point_cov_out)
+// the checks mvs_ba_refine_sparse and mvs_ba_sparse_obs_stats make of a problem before anything runs (the plan's limits apart)
+mvs_status sparse_problem_status(const mvs_ba_sparse *pb)
 {
-    if (!ctx || !pb || !result || !poses_out || !refine_params_ok(params))
-        return MVS_ERR_INVALID_ARG;
     if (pb->n_frames < 1 || pb->n_points < 1 || pb->n_obs < 1)
         return MVS_ERR_INVALID_ARG;
     if (pb->n_frames > mvs_bas::kMaxFrames || pb->n_points > mvs_bas::kMaxPoints || pb->n_obs > mvs_bas::kMaxObs)
@@ -214,6 +214,35 @@ mvs_status mvs_ba_refine_sparse(mvs_ctx *ctx, const mvs_ba_sparse *pb, const mvs
         return MVS_ERR_INVALID_ARG;
     if (mvs_bas::check_csr(F, P, O, pb->obs_off, pb->obs_frame) != 0)
         return MVS_ERR_INVALID_ARG;
+    return MVS_OK;
+}
+// the information matrices the kernels read of the observations: identity without covariances
+void pack_obs_info(const mvs_ba_sparse *pb, std::vector<double> &oinfo)
+{
+    const size_t O = (size_t)pb->n_obs;
+    oinfo.assign(3 * O, 0.0);
+    for (size_t o = 0; o < O; ++o) {
+        if (!pb->obs_cov)
+            oinfo[3 * o] = 1.0, oinfo[3 * o + 2] = 1.0;
+        else
+            obs_info(pb->obs_cov + 4 * o, oinfo.data() + 3 * o);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+mvs_status mvs_ba_refine_sparse(mvs_ctx *ctx, const mvs_ba_sparse *pb, const mvs_refine_params *params,
+                                mvs_ba_sparse_result *result, double *poses_out, double *points_out, double *pose_cov_out,
+                                double *point_cov_out)
+{
+    if (!ctx || !pb || !result || !poses_out || !refine_params_ok(params))
+        return MVS_ERR_INVALID_ARG;
+    mvs_status st = sparse_problem_status(pb);
+    if (st != MVS_OK)
+        return st;
+    const int F = pb->n_frames, P = pb->n_points, O = pb->n_obs;
     const mvs_bas::Plan plan = mvs_bas::plan(F, P, O, pb->obs_off, pb->obs_frame);
     if (!plan.fits())
         return MVS_ERR_CAPACITY;
@@ -221,18 +250,13 @@ mvs_status mvs_ba_refine_sparse(mvs_ctx *ctx, const mvs_ba_sparse *pb, const mvs
     const bool want_cov = pose_cov_out || point_cov_out;
 
     // the uploaded doubles: weights and information matrices are derived here
-    std::vector<double> w(6 * (size_t)F), pinfo(6 * (size_t)P, 0.0), oinfo(3 * (size_t)O, 0.0);
+    std::vector<double> w(6 * (size_t)F), pinfo(6 * (size_t)P, 0.0), oinfo;
     for (size_t k = 0; k < w.size(); ++k)
         w[k] = prior_weight(pb->frame_prior_var[k]);
     for (size_t i = 0; i < (size_t)P && pb->point_prior_cov; ++i)
         if (pb->point_prior_cov[9 * i] > 0.0)
             point_info(pb->point_prior_cov + 9 * i, pinfo.data() + 6 * i);
-    for (size_t o = 0; o < (size_t)O; ++o) {
-        if (!pb->obs_cov)
-            oinfo[3 * o] = 1.0, oinfo[3 * o + 2] = 1.0;
-        else
-            obs_info(pb->obs_cov + 4 * o, oinfo.data() + 3 * o);
-    }
+    pack_obs_info(pb, oinfo);
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Carve L{64};
@@ -243,8 +267,7 @@ mvs_status mvs_ba_refine_sparse(mvs_ctx *ctx, const mvs_ba_sparse *pb, const mvs
     const size_t o_first = L.take((size_t)F * 4), o_row = L.take(((size_t)F + 1) * 4), o_brow = L.take(B * 4);
     const size_t o_last = L.take((size_t)F * 4), o_poff = L.take((B + 1) * 4), o_pa = L.take(NP * 4), o_pc = L.take(NP * 4);
     const BasWork wk = carve_work(L, (size_t)F, (size_t)P, (size_t)O, B, pose_cov_out != nullptr, point_cov_out != nullptr);
-    mvs_status st = ws_grow(ctx, ctx->bas, L.total());
-    if (st != MVS_OK)
+    if ((st = ws_grow(ctx, ctx->bas, L.total())) != MVS_OK)
         return st;
     char *base = ctx->bas.ptr();
     hipStream_t s = ctx_stream(ctx);
@@ -281,7 +304,7 @@ mvs_status mvs_ba_refine_sparse(mvs_ctx *ctx, const mvs_ba_sparse *pb, const mvs
     d.first = ip(o_first), d.row_off = ip(o_row), d.blk_row = ip(o_brow), d.last = ip(o_last);
     d.pair_off = ip(o_poff), d.pair_a = ip(o_pa), d.pair_c = ip(o_pc);
     PgdDev pd{};
-    bind_work(base, wk, d, pd);
+    bind_work(ctx, base, wk, d, pd);
     int cb = 0;
     // the plan's lists and the packed inputs have been read once the solver has read its first cost
     if ((st = bas_solve(ctx, d, pd, params, plan.widest, result, &cb)) != MVS_OK)
@@ -296,6 +319,56 @@ mvs_status mvs_ba_refine_sparse(mvs_ctx *ctx, const mvs_ba_sparse *pb, const mvs
         HIP_TRY(ctx, hipMemcpyAsync(pose_cov_out, d.pose_cov, 36 * (size_t)F * 8, hipMemcpyDeviceToHost, s));
     if (point_cov_out)
         HIP_TRY(ctx, hipMemcpyAsync(point_cov_out, d.point_cov, 9 * (size_t)P * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    return MVS_OK;
+}
+
+// ---- per-observation statistics ------------------------------------------------------------------
+mvs_status mvs_ba_sparse_obs_stats(mvs_ctx *ctx, const mvs_ba_sparse *pb, const double *poses, const double *points, double *chi2,
+                                   double *weight)
+{
+    if (!ctx || !pb || !chi2)
+        return MVS_ERR_INVALID_ARG;
+    mvs_status st = sparse_problem_status(pb);
+    if (st != MVS_OK)
+        return st;
+    const size_t F = (size_t)pb->n_frames, P = (size_t)pb->n_points, O = (size_t)pb->n_obs;
+    if ((poses && !all_finite(poses, 12 * F)) || (points && !all_finite(points, 3 * P)))
+        return MVS_ERR_INVALID_ARG;
+    std::vector<double> oinfo;
+    pack_obs_info(pb, oinfo);
+    std::vector<int32_t> obs_point(O);
+    for (size_t i = 0; i < P; ++i)
+        for (int32_t o = pb->obs_off[i]; o < pb->obs_off[i + 1]; ++o)
+            obs_point[(size_t)o] = (int32_t)i;
+
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Carve L{64};
+    const size_t o_pose = L.take(12 * F * 8), o_pts = L.take(3 * P * 8), o_uv = L.take(2 * O * 8), o_oinfo = L.take(3 * O * 8);
+    const size_t o_ofr = L.take(O * 4), o_opt = L.take(O * 4), o_chi2 = L.take(O * 8), o_wt = L.take(O * 8);
+    if ((st = ws_grow(ctx, ctx->bas, L.total())) != MVS_OK)
+        return st;
+    char *base = ctx->bas.ptr();
+    hipStream_t s = ctx_stream(ctx);
+    auto dp = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
+    auto ip = [&](size_t o) { return reinterpret_cast<int32_t *>(base + o); };
+    auto up = [&](size_t o, const void *src, size_t bytes) { return hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s); };
+    HIP_TRY(ctx, up(o_pose, poses ? poses : pb->frame_pose, 12 * F * 8));
+    HIP_TRY(ctx, up(o_pts, points ? points : pb->points, 3 * P * 8));
+    HIP_TRY(ctx, up(o_uv, pb->obs_uv, 2 * O * 8));
+    HIP_TRY(ctx, up(o_oinfo, oinfo.data(), 3 * O * 8));
+    HIP_TRY(ctx, up(o_ofr, pb->obs_frame, O * 4));
+    HIP_TRY(ctx, up(o_opt, obs_point.data(), O * 4));
+    BasDev d{};
+    d.n_frames = (int)F, d.n_points = (int)P, d.n_obs = (int)O;
+    d.cam[0] = pb->K[0], d.cam[1] = pb->K[1], d.cam[2] = pb->K[2], d.cam[3] = pb->K[4], d.cam[4] = pb->K[5];
+    d.obs_frame = ip(o_ofr), d.obs_point = ip(o_opt), d.obs_uv = dp(o_uv), d.oinfo = d.oinfo0 = dp(o_oinfo);
+    d.loss = ctx->ba_loss, d.loss_k = ctx->ba_loss_k;
+    launch_bas_obs_stats(d, dp(o_pose), dp(o_pts), dp(o_chi2), weight ? dp(o_wt) : nullptr, s);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(chi2, dp(o_chi2), O * 8, hipMemcpyDeviceToHost, s));
+    if (weight)
+        HIP_TRY(ctx, hipMemcpyAsync(weight, dp(o_wt), O * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }
@@ -427,7 +500,7 @@ mvs_status mvs_seq_refine_global(mvs_seq *q, const mvs_seq_global_params *gp, co
     d.first = g.first, d.row_off = g.row_off, d.blk_row = g.blk_row, d.last = g.last;
     d.pair_off = g.pair_off, d.pair_a = g.pair_a, d.pair_c = g.pair_c;
     PgdDev pd{};
-    bind_work(base, wk, d, pd);
+    bind_work(ctx, base, wk, d, pd);
     int cb = 0;
     st = bas_solve(ctx, d, pd, params, hs.widest, result, &cb);
     if (st != MVS_OK && st != MVS_NO_MODEL)
@@ -474,6 +547,28 @@ mvs_status mvs_seq_download_global(mvs_seq *q, double *poses, double *points, do
         HIP_TRY(ctx, hipMemcpyAsync(pose_cov, d.pose_cov, 36 * F * 8, hipMemcpyDeviceToHost, s));
     if (point_cov)
         HIP_TRY(ctx, hipMemcpyAsync(point_cov, d.point_cov, 9 * P * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_global_obs_stats(mvs_seq *q, double *chi2, double *weight)
+{
+    if (!q || !chi2 || !q->glob_solved || !q->glob_res.ok)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the resident problem at the resident estimate under the context's loss as it is NOW; zd, which nothing reads behind the
+    // solver's last update, takes the two result arrays
+    BasDev d = q->glob_bas;
+    d.loss = ctx->ba_loss, d.loss_k = ctx->ba_loss_k;
+    const size_t O = (size_t)d.n_obs;
+    hipStream_t s = ctx_stream(ctx);
+    double *d_chi2 = d.zd, *d_wt = d.zd + O;
+    launch_bas_obs_stats(d, d.pose[q->glob_cur], d.pts[q->glob_cur], d_chi2, weight ? d_wt : nullptr, s);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(chi2, d_chi2, O * 8, hipMemcpyDeviceToHost, s));
+    if (weight)
+        HIP_TRY(ctx, hipMemcpyAsync(weight, d_wt, O * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }

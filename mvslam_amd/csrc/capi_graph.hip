@@ -46,6 +46,15 @@ mvs_status mvs_ctx_set_pose_graph_loss(mvs_ctx *ctx, int loss, double k, int32_t
     return MVS_OK;
 }
 
+mvs_status mvs_ctx_set_ba_loss(mvs_ctx *ctx, int loss, double k)
+{
+    if (!ctx || !ba_loss_args_ok(loss, k))
+        return MVS_ERR_INVALID_ARG;
+    ctx->ba_loss = loss;
+    ctx->ba_loss_k = k;
+    return MVS_OK;
+}
+
 mvs_status mvs_ctx_pose_graph_direct_info(mvs_ctx *ctx, mvs_pose_graph_direct_info *info)
 {
     if (!ctx || !info || !ctx->pgd_ran)

@@ -56,6 +56,9 @@ struct mvs_ctx {
     int pg_loss = MVS_PG_LOSS_NONE;
     double pg_loss_k = 1.0;
     int32_t pg_loss_first = 0;
+    // mvs_ctx_set_ba_loss: the robust loss of the observation terms of mvs_ba_refine_sparse and mvs_seq_refine_global, its constant
+    int ba_loss = MVS_BA_LOSS_NONE;
+    double ba_loss_k = 1.0;
     bool pgd_ran = false;               // a graph has gone through the direct solver: pgd_info is that of the last one
     mvs_pose_graph_direct_info pgd_info{};
     // n_run of the last single-shot five-point call: none yet, or that call failed before its RANSAC was enqueued (-1); in

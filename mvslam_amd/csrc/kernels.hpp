@@ -419,7 +419,19 @@ struct BasDev {
     double *inv, *colm;          // [n_blocks][36] blocks of the scaled S^-1, [F][36] (covariance pass)
     double *pose_cov, *point_cov;   // [F][36], [P][9]; either may be null
     BasState *state;
+    // robust loss of the observation terms (mvs_ctx_set_ba_loss): 0 none, 1 Huber, 2 Cauchy, with the
+    // constant loss_k.  0 issues the launches there were before there was one and reads oinfo alone.  With a loss, oinfo is
+    // the array the robust linearisation writes, w(s_o) W_o, which is all the build kernels see of it; the cost and the
+    // statistics read the caller's W_o through oinfo0.
+    int loss;
+    double loss_k;
+    const double *oinfo0;        // [O][3]
+    double *oinfo_w;             // [O][3]: what oinfo points at under a loss
 };
+// s_o and w(s_o) of every observation at the given poses and points (device pointers; weight may be null): reads n_obs, cam,
+// obs_frame, obs_point, obs_uv, oinfo0, loss and loss_k of d
+void launch_bas_obs_stats(const BasDev &d, const double *poses, const double *points, double *chi2, double *weight,
+                          hipStream_t stream);
 // cost at pose[which], pts[which] -> state->cost
 void launch_bas_cost(const BasDev &d, int which, hipStream_t stream);
 // linearise at [cur] with damping lam: Li, gh, Z, D, g and the off-diagonal blocks of sky; clears state->bad_point first

@@ -26,6 +26,12 @@ inline bool loss_args_ok(int loss, double k, int32_t first_edge)
         return false;
     return loss == 0 || (std::isfinite(k) && k > 0.0);
 }
+// mvs_ctx_set_ba_loss's arguments: the same rule for the loss and its constant; a bundle
+// adjustment has no first_edge
+inline bool ba_loss_args_ok(int loss, double k)
+{
+    return loss_args_ok(loss, k, 0);
+}
 // may a call on a host graph run under this setting?  It has no loop edges for first_edge = -1 to stand for.
 inline bool loss_fits_host_graph(int loss, int32_t first_edge)
 {
