@@ -26,9 +26,8 @@
 //   w(s_o) at given values).  Every other kernel reads what those left; without a loss the launches are the ones they were.
 // One owner per entry everywhere, no floating-point atomics, binary64 with explicit FMAs: the same input gives the same bytes.
 //
-// Cam / fd2 / fd3 / fx2 / so3_exp / so3_log / so3_jrinv / pose_prior / project_lin and the 3 x 3 Cholesky of bas_point_kernel
-// are COPIES of refine.hip's (same statements, same order), for the reason posegraph.hip gives.
-#include "kernels.hpp"
+// The projection, the pose prior, the 3 x 3 Cholesky of bas_point_kernel and the loss functions are lm_math.hpp's, shared with refine.hip.
+#include "lm_math.hpp"
 
 namespace mvs {
 
@@ -36,150 +35,6 @@ namespace {
 
 constexpr int kBasThreads = 256;
 constexpr int kBasPerWg = 7;   // blocks of the envelope one workgroup of bas_schur_kernel owns: 7 * 36 = 252 threads
-constexpr double kBasPivotTol = 1.0 / (double)(1ll << 42);   // refine.hip's kWinPivotTol
-
-__host__ __device__ constexpr int lidx(int r, int c) { return r * (r + 1) / 2 + c; }  // r >= c
-
-struct Cam {
-    double fx, fy, sk, cx, cy;
-};
-
-__device__ __forceinline__ double fd2(double a0, double b0, double a1, double b1) { return fma(a1, b1, a0 * b0); }
-__device__ __forceinline__ double fd3(double a0, double b0, double a1, double b1, double a2, double b2)
-{
-    return fma(a2, b2, fma(a1, b1, a0 * b0));
-}
-__device__ __forceinline__ double fx2(double a, double b, double c, double d) { return fma(a, b, -(c * d)); }  // a b - c d
-
-__device__ __forceinline__ void so3_exp(const double (&w)[3], double (&R)[9])
-{
-    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
-    const double th = sqrt(th2);
-    double A, B;
-    if (th < 1e-4) {
-        A = 1.0 - th2 / 6.0;
-        B = 0.5 - th2 / 24.0;
-    } else {
-        A = sin(th) / th;
-        B = (1.0 - cos(th)) / th2;
-    }
-    const double x = w[0], y = w[1], z = w[2];
-    R[0] = 1.0 - B * (y * y + z * z);
-    R[1] = B * (x * y) - A * z;
-    R[2] = B * (x * z) + A * y;
-    R[3] = B * (x * y) + A * z;
-    R[4] = 1.0 - B * (x * x + z * z);
-    R[5] = B * (y * z) - A * x;
-    R[6] = B * (x * z) - A * y;
-    R[7] = B * (y * z) + A * x;
-    R[8] = 1.0 - B * (x * x + y * y);
-}
-
-__device__ __forceinline__ void so3_log(const double (&R)[9], double (&w)[6])
-{
-    const double vx = 0.5 * (R[7] - R[5]), vy = 0.5 * (R[2] - R[6]), vz = 0.5 * (R[3] - R[1]);
-    const double s = sqrt((vx * vx + vy * vy) + vz * vz);
-    const double c = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
-    const double th = atan2(s, c);
-    double k;
-    if (s < 1e-4 && c > 0.0)
-        k = 1.0 + (s * s) / 6.0;
-    else
-        k = th / s;
-    w[0] = k * vx;
-    w[1] = k * vy;
-    w[2] = k * vz;
-}
-
-__device__ __forceinline__ void so3_jrinv(const double (&w)[6], double (&J)[9])
-{
-    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
-    const double th = sqrt(th2);
-    double g;
-    if (th < 1e-4)
-        g = 1.0 / 12.0 + th2 / 720.0;
-    else
-        g = 1.0 / th2 - (1.0 + cos(th)) / ((2.0 * th) * sin(th));
-    const double x = w[0], y = w[1], z = w[2];
-    J[0] = 1.0 + g * (x * x - th2);
-    J[1] = g * (x * y) - 0.5 * z;
-    J[2] = g * (x * z) + 0.5 * y;
-    J[3] = g * (x * y) + 0.5 * z;
-    J[4] = 1.0 + g * (y * y - th2);
-    J[5] = g * (y * z) - 0.5 * x;
-    J[6] = g * (x * z) - 0.5 * y;
-    J[7] = g * (y * z) + 0.5 * x;
-    J[8] = 1.0 + g * (z * z - th2);
-}
-
-// pose prior of one frame: error e = (Log(R0^T R), R0^T (t - t0)); Jw = Jr^-1(e_w), Jv = R0^T R
-template <bool JAC>
-__device__ __forceinline__ void pose_prior(const double (&R0)[9], const double (&t0)[3], const double (&R)[9],
-                                           const double (&t)[3], double (&e)[6], double (&Jw)[9], double (&Jv)[9])
-{
-    double Re[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            Re[3 * i + j] = (R0[i] * R[j] + R0[3 + i] * R[3 + j]) + R0[6 + i] * R[6 + j];
-    so3_log(Re, e);
-    const double d0 = t[0] - t0[0], d1 = t[1] - t0[1], d2 = t[2] - t0[2];
-    e[3] = (R0[0] * d0 + R0[3] * d1) + R0[6] * d2;
-    e[4] = (R0[1] * d0 + R0[4] * d1) + R0[7] * d2;
-    e[5] = (R0[2] * d0 + R0[5] * d1) + R0[8] * d2;
-    if (JAC) {
-        so3_jrinv(e, Jw);
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-            Jv[k] = Re[k];
-    }
-}
-
-// residual of one observation (and its Jacobians): GenericProjectionFactor with throwCheirality = false
-template <bool JAC>
-__device__ __forceinline__ void project_lin(const Cam &cam, const double (&R)[9], const double (&t)[3],
-                                            const double (&p)[3], double u, double v, double (&r)[2], double (&Jc)[12],
-                                            double (&Jp)[6])
-{
-    const double d0 = p[0] - t[0], d1 = p[1] - t[1], d2 = p[2] - t[2];
-    const double q0 = fd3(R[0], d0, R[3], d1, R[6], d2);
-    const double q1 = fd3(R[1], d0, R[4], d1, R[7], d2);
-    const double q2 = fd3(R[2], d0, R[5], d1, R[8], d2);
-    if (!(q2 > 0.0)) {
-        r[0] = 2.0 * cam.fx;
-        r[1] = 2.0 * cam.fx;
-        if (JAC) {
-#pragma unroll
-            for (int k = 0; k < 12; ++k)
-                Jc[k] = 0.0;
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-                Jp[k] = 0.0;
-        }
-        return;
-    }
-    const double iz = 1.0 / q2, xn = q0 * iz, yn = q1 * iz;
-    const double un = fd2(cam.fx, xn, cam.sk, yn), vn = cam.fy * yn;
-    r[0] = (un + cam.cx) - u;
-    r[1] = (vn + cam.cy) - v;
-    if (JAC) {
-        const double A[6] = {cam.fx * iz, cam.sk * iz, -(un * iz), 0.0, cam.fy * iz, -(vn * iz)};
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            const double a0 = A[3 * a], a1 = A[3 * a + 1], a2 = A[3 * a + 2];
-            Jc[6 * a + 0] = fx2(a1, q2, a2, q1);
-            Jc[6 * a + 1] = fx2(a2, q0, a0, q2);
-            Jc[6 * a + 2] = fx2(a0, q1, a1, q0);
-            Jc[6 * a + 3] = -a0;
-            Jc[6 * a + 4] = -a1;
-            Jc[6 * a + 5] = -a2;
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                Jp[3 * a + k] = fd3(a0, R[3 * k], a1, R[3 * k + 1], a2, R[3 * k + 2]);
-        }
-    }
-}
 
 __device__ __forceinline__ Cam cam_of(const BasDev &d)
 {
@@ -271,25 +126,8 @@ __global__ __launch_bounds__(kBasThreads) void bas_point_kernel(BasDev d, int cu
     const double g2 = fd3(L[2], d0, L[4], d1, L[5], d2) + gp[2];
     const double v0 = V[0] + lam, v3 = V[3] + lam, v5 = V[5] + lam;
     // V = L L^T, then L^-1
-    const double inf = __builtin_inf();
-    bool ok = v0 > 0.0 && v0 < inf;
-    const double i0 = 1.0 / sqrt(v0);
-    const double l10 = V[1] * i0, l20 = V[2] * i0;
-    const double e1 = fma(-l10, l10, v3);
-    ok = ok && e1 > kBasPivotTol * v3 && e1 < inf;
-    const double i1 = 1.0 / sqrt(e1);
-    const double l21 = fma(-l20, l10, V[4]) * i1;
-    const double e2 = fma(-l21, l21, fma(-l20, l20, v5));
-    ok = ok && e2 > kBasPivotTol * v5 && e2 < inf;
-    const double i2 = 1.0 / sqrt(e2);
-    const double m10 = -(l10 * i0) * i1, m21 = -(l21 * i1) * i2, m20 = -fd2(l20, i0, l21, m10) * i2;
     double Li[6];
-    Li[0] = ok ? i0 : 0.0;
-    Li[1] = ok ? m10 : 0.0;
-    Li[2] = ok ? i1 : 0.0;
-    Li[3] = ok ? m20 : 0.0;
-    Li[4] = ok ? m21 : 0.0;
-    Li[5] = ok ? i2 : 0.0;
+    const bool ok = chol3_pivot(V, v0, v3, v5, Li);
     double gh[3];
     gh[0] = Li[0] * g0;
     gh[1] = fd2(Li[1], g0, Li[2], g1);
@@ -512,24 +350,6 @@ __device__ __forceinline__ double obs_chi2(const double (&r)[2], double W0, doub
     const double wr0 = fd2(W0, r[0], W1, r[1]), wr1 = fd2(W1, r[0], W2, r[1]);
     return fma(r[1], wr1, r[0] * wr0);
 }
-// weight w(s) from s and x = sqrt(s): Huber 1 or k / x, Cauchy k^2 / (k^2 + s) -- posegraph.hip's pg_loss_weight
-__device__ __forceinline__ double bas_loss_weight(int loss, double k, double s, double x)
-{
-    if (loss == 1)
-        return x <= k ? 1.0 : k / x;
-    const double k2 = k * k;
-    return k2 / (k2 + s);
-}
-// rho2(s), the observation's term of twice the cost: one sqrt (the Cauchy cost: log1p of one quotient)
-__device__ __forceinline__ double bas_loss_rho2(int loss, double k, double s)
-{
-    if (loss == 1) {
-        const double x = sqrt(s);
-        return x <= k ? s : (2.0 * k) * x - k * k;
-    }
-    const double k2 = k * k;
-    return k2 * log1p(s / k2);
-}
 
 // bas_lin_kernel under a loss: the same 20 doubles of lin, and w(s_o) W_o for the build kernels
 __global__ __launch_bounds__(kBasThreads) void bas_robust_lin_kernel(BasDev d, int cur)
@@ -556,7 +376,7 @@ __global__ __launch_bounds__(kBasThreads) void bas_robust_lin_kernel(BasDev d, i
     L[19] = r[1];
     const double W0 = d.oinfo0[3 * (int64_t)o], W1 = d.oinfo0[3 * (int64_t)o + 1], W2 = d.oinfo0[3 * (int64_t)o + 2];
     const double s = obs_chi2(r, W0, W1, W2);
-    const double w = bas_loss_weight(d.loss, d.loss_k, s, sqrt(s));
+    const double w = loss_weight(d.loss, d.loss_k, s, sqrt(s));
     double *Ww = d.oinfo_w + 3 * (int64_t)o;
     Ww[0] = w * W0;
     Ww[1] = w * W1;
@@ -580,7 +400,8 @@ __global__ __launch_bounds__(kBasThreads) void bas_robust_terms_kernel(BasDev d,
         p[0] = pp[0], p[1] = pp[1], p[2] = pp[2];
         project_lin<false>(cam, R, t, p, d.obs_uv[2 * (int64_t)o], d.obs_uv[2 * (int64_t)o + 1], r, Jc, Jp);
         const double W0 = d.oinfo0[3 * (int64_t)o], W1 = d.oinfo0[3 * (int64_t)o + 1], W2 = d.oinfo0[3 * (int64_t)o + 2];
-        c = bas_loss_rho2(d.loss, d.loss_k, obs_chi2(r, W0, W1, W2));
+        const double s = obs_chi2(r, W0, W1, W2);
+        c = ba_loss_rho2(d.loss, d.loss_k, s, sqrt(s));
     } else if (gid < (int64_t)d.n_obs + d.n_points) {
         const int64_t i = gid - d.n_obs;
         const double *p = d.pts[which] + 3 * i, *p0 = d.pts0 + 3 * i, *L = d.pinfo + 6 * i;
@@ -617,7 +438,7 @@ __global__ __launch_bounds__(kBasThreads) void bas_obs_stats_kernel(BasDev d, co
     const double s = obs_chi2(r, W0, W1, W2);
     chi2[o] = s;
     if (weight)
-        weight[o] = d.loss != 0 ? bas_loss_weight(d.loss, d.loss_k, s, sqrt(s)) : 1.0;
+        weight[o] = d.loss != 0 ? loss_weight(d.loss, d.loss_k, s, sqrt(s)) : 1.0;
 }
 
 // out[blockIdx.x] = the sum of in[blockIdx.x * chunk .. + chunk) (clipped to n): thread t takes t, t + 256, ... in order, then

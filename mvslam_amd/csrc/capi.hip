@@ -2601,13 +2601,13 @@ static mvs_status window_check(const mvs_ba_window *w)
 
 // covariance -> information with refine_prep_kernel's formulas: a 2 x 2 observation covariance (row-major) to (xx xy yy), a
 // 3 x 3 point prior covariance to (xx xy xz yy yz zz)
-static void obs_cov_to_info(const double *cv, double *o)
+extern "C++" void mvs_host::obs_cov_to_info(const double *cv, double *o)
 {
     const double a = cv[0], b = 0.5 * (cv[1] + cv[2]), dd = cv[3];
     const double id = 1.0 / (a * dd - b * b);
     o[0] = dd * id, o[1] = -(b * id), o[2] = a * id;
 }
-static void point_cov_to_info(const double *C, double *L)
+extern "C++" void mvs_host::point_cov_to_info(const double *C, double *L)
 {
     const double a[6] = {C[0], 0.5 * (C[1] + C[3]), 0.5 * (C[2] + C[6]), C[4], 0.5 * (C[5] + C[7]), C[8]};
     const double c00 = a[3] * a[5] - a[4] * a[4], c01 = a[2] * a[4] - a[1] * a[5], c02 = a[1] * a[4] - a[2] * a[3];

@@ -18,8 +18,6 @@ using namespace mvs_host;
 
 namespace {
 
-constexpr double kPivotTol = 1.0 / (double)(1ll << 42);   // refine.hip's kWinPivotTol
-
 bool all_finite(const double *v, size_t n)
 {
     for (size_t k = 0; k < n; ++k)
@@ -28,21 +26,6 @@ bool all_finite(const double *v, size_t n)
     return true;
 }
 
-// capi.hip's obs_cov_to_info / point_cov_to_info (same statements)
-void obs_info(const double *cv, double *o)
-{
-    const double a = cv[0], b = 0.5 * (cv[1] + cv[2]), dd = cv[3];
-    const double id = 1.0 / (a * dd - b * b);
-    o[0] = dd * id, o[1] = -(b * id), o[2] = a * id;
-}
-void point_info(const double *C, double *L)
-{
-    const double a[6] = {C[0], 0.5 * (C[1] + C[3]), 0.5 * (C[2] + C[6]), C[4], 0.5 * (C[5] + C[7]), C[8]};
-    const double c00 = a[3] * a[5] - a[4] * a[4], c01 = a[2] * a[4] - a[1] * a[5], c02 = a[1] * a[4] - a[2] * a[3];
-    const double id = 1.0 / ((a[0] * c00 + a[1] * c01) + a[2] * c02);
-    L[0] = c00 * id, L[1] = c01 * id, L[2] = c02 * id;
-    L[3] = (a[0] * a[5] - a[2] * a[2]) * id, L[4] = (a[1] * a[2] - a[0] * a[4]) * id, L[5] = (a[0] * a[3] - a[1] * a[1]) * id;
-}
 // a prior variance as the weight the kernels read: none where the variance is not positive
 double prior_weight(double var) { return var > 0.0 ? 1.0 / var : 0.0; }
 
@@ -93,7 +76,7 @@ void bind_work(const mvs_ctx *ctx, char *base, const BasWork &k, BasDev &d, PgdD
     pd.first = d.first, pd.row_off = d.row_off, pd.blk_row = d.blk_row;
     pd.D = d.D, pd.g = d.g, pd.Cinv = dp(k.Cinv), pd.sky = d.sky, pd.y = dp(k.y), pd.x = dp(k.x);
     pd.state = reinterpret_cast<PgdState *>(base + k.pst);
-    pd.pre = d.sky, pd.pivot_tol = kPivotTol;
+    pd.pre = d.sky, pd.pivot_tol = kBaPivotTol;
 }
 
 // The solver over a problem whose inputs and lists lie in device memory (or are on their way there on the context's stream):
@@ -225,7 +208,7 @@ void pack_obs_info(const mvs_ba_sparse *pb, std::vector<double> &oinfo)
         if (!pb->obs_cov)
             oinfo[3 * o] = 1.0, oinfo[3 * o + 2] = 1.0;
         else
-            obs_info(pb->obs_cov + 4 * o, oinfo.data() + 3 * o);
+            obs_cov_to_info(pb->obs_cov + 4 * o, oinfo.data() + 3 * o);
     }
 }
 
@@ -255,7 +238,7 @@ mvs_status mvs_ba_refine_sparse(mvs_ctx *ctx, const mvs_ba_sparse *pb, const mvs
         w[k] = prior_weight(pb->frame_prior_var[k]);
     for (size_t i = 0; i < (size_t)P && pb->point_prior_cov; ++i)
         if (pb->point_prior_cov[9 * i] > 0.0)
-            point_info(pb->point_prior_cov + 9 * i, pinfo.data() + 6 * i);
+            point_cov_to_info(pb->point_prior_cov + 9 * i, pinfo.data() + 6 * i);
     pack_obs_info(pb, oinfo);
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -427,11 +410,11 @@ mvs_status mvs_seq_refine_global(mvs_seq *q, const mvs_seq_global_params *gp, co
     }
     const double pv = params->point_sigma * params->point_sigma;
     const double pc[9] = {pv, 0.0, 0.0, 0.0, pv, 0.0, 0.0, 0.0, pv};
-    point_info(pc, g.w.pinfo);
+    point_cov_to_info(pc, g.w.pinfo);
     for (int oc = 0; oc <= kSeqWinMaxOctave; ++oc) {
         const double sd = std::ldexp(gp->sigma_px, oc);
         const double cv[4] = {sd * sd, 0.0, 0.0, sd * sd};
-        obs_info(cv, g.w.oinfo[oc]);
+        obs_cov_to_info(cv, g.w.oinfo[oc]);
     }
     g.T = gp->max_track_frames;
     g.depth = ti(a_depth), g.rank = ti(a_rank), g.oofs = ti(a_oofs), g.kp_obs = ti(a_kpo);

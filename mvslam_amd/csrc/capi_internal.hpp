@@ -301,6 +301,8 @@ mvs_status batch_create_impl(mvs_ctx *ctx, int n_pairs, int max_kp, int desc_byt
 mvs_status check_params(const mvs_params *p);
 mvs_status run_pairs(mvs_batch *b, Estimator est, const RunParams &rp, int n);
 bool refine_params_ok(const mvs_refine_params *p);
+void obs_cov_to_info(const double *cv, double *o);
+void point_cov_to_info(const double *C, double *L);
 
 // capi_orb.hip
 mvs_status orb_run(mvs_ctx *ctx, const uint8_t *images, int n, int w, int h, const mvs_orb_params &prm, uint8_t *d_desc_ext,

@@ -392,6 +392,9 @@ void launch_pgd_step(const PgdDev &d, double lam, hipStream_t stream);
 // launch_pgd_step's with PgdDev::pre = sky, D and g the arrays below.  The host drives the LM loop.
 constexpr int kBasLin = 20;      // doubles of one linearised observation: Jc 12 (2 x 6), Jp 6 (2 x 3), r 2
 constexpr int kBasRedChunk = 4096;   // terms one workgroup of the cost's first reduction stage sums
+// the pivot rule of the bundle adjustments (refine_window_kernel, the point blocks, PgdDev::pivot_tol of the sparse path): a
+// pivot must exceed this times the entry before elimination.  2.3e-13 ~ 16 x 48 x 2^-52
+constexpr double kBaPivotTol = 1.0 / (double)(1ll << 42);
 struct BasState {        // what the host reads once per LM iteration
     double cost;         // sum of the squared Mahalanobis norms at the values of the last cost launch (no 1/2)
     int32_t bad_point;   // some point's V failed the pivot rule in the last build

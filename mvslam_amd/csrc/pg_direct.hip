@@ -20,8 +20,8 @@
 // the off-diagonal blocks already summed, D and g are its own, PgdDev::pivot_tol its pivot rule.  Both are zero for the pose
 // graphs, whose statements and bytes are what they were.
 //
-// chol_packed / coldot are COPIES of posegraph.hip's (same statements, same order), for the reason pg_marginals.hip gives.
-#include "kernels.hpp"
+// chol_packed is lm_math.hpp's and coldot pg_edge.hpp's, shared with the other solvers.
+#include "pg_edge.hpp"
 
 namespace mvs {
 
@@ -29,36 +29,6 @@ namespace {
 
 constexpr int kPgdThreads = 256;
 constexpr int kPgdPerWg = 7;   // blocks of the envelope one workgroup of pgd_assemble_kernel owns: 7 * 36 = 252 threads
-
-__host__ __device__ constexpr int lidx(int r, int c) { return r * (r + 1) / 2 + c; }  // r >= c
-
-// in-place Cholesky of the packed lower triangle; false if not positive definite.  The diagonal holds 1 / l_jj.  `min_d`
-// follows the smallest pivot (l_jj squared).
-template <int N>
-__device__ __forceinline__ bool chol_packed(double (&S)[N * (N + 1) / 2], double &min_d)
-{
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        double d = S[lidx(j, j)];
-#pragma unroll
-        for (int k = 0; k < j; ++k)
-            d = fma(-S[lidx(j, k)], S[lidx(j, k)], d);
-        ok = ok && (d > 0.0) && (d < __builtin_inf());
-        min_d = d < min_d ? d : min_d;
-        const double inv = 1.0 / sqrt(d);
-        S[lidx(j, j)] = inv;
-#pragma unroll
-        for (int i = j + 1; i < N; ++i) {
-            double v = S[lidx(i, j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k)
-                v = fma(-S[lidx(i, k)], S[lidx(j, k)], v);
-            S[lidx(i, j)] = v * inv;
-        }
-    }
-    return ok;
-}
 
 // W = L^-1 (packed lower) of the factor chol_packed left in S: column c by forward substitution of the unit vector e_c
 __device__ __forceinline__ void tri_inverse(const double (&S)[21], double (&W)[21])
@@ -79,16 +49,6 @@ __device__ __forceinline__ void tri_inverse(const double (&S)[21], double (&W)[2
     }
 }
 
-// column i of A . column j of B (A, B row-major 6 x 6)
-__device__ __forceinline__ double coldot(const double *A, int i, const double *B, int j)
-{
-    double s = A[i] * B[j];
-#pragma unroll
-    for (int m = 1; m < 6; ++m)
-        s = fma(A[6 * m + i], B[6 * m + j], s);
-    return s;
-}
-
 // ---- scaling of the diagonal ----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void pgd_scale_kernel(PgdDev d, double lam)
 {
@@ -104,8 +64,7 @@ __global__ __launch_bounds__(64) void pgd_scale_kernel(PgdDev d, double lam)
         S[lidx(k, k)] = S[lidx(k, k)] + lam;
         g[k] = d.g[6 * (int64_t)i + k];
     }
-    double unused = __builtin_inf();
-    if (!chol_packed<6>(S, unused)) {
+    if (!chol_packed<6>(S)) {
         d.state->status = 2;   // every writer stores the same word (the host clears it before the launch)
         atomicMax(&d.state->bad_code, d.n_nodes - i);
     }

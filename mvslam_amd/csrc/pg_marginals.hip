@@ -18,10 +18,8 @@
 //                      other queries, and Sigma_ji is the byte transpose of Sigma_ij.
 // Every kernel leaves at once when the status word is set.
 //
-// so3_log / so3_jrinv / pose_prior / chol_packed / edge_prep / whiten / edge_eval / coldot are COPIES of posegraph.hip's
-// (same statements, same order), for the reason posegraph.hip copied refine.hip's: sharing them through a header would
-// recompile its kernels from another inclusion order.
-#include "kernels.hpp"
+// The prior and Cholesky functions are lm_math.hpp's and the edge functions pg_edge.hpp's, shared with the other solvers.
+#include "pg_edge.hpp"
 
 namespace mvs {
 
@@ -29,207 +27,6 @@ namespace {
 
 constexpr int kPgmThreads = 256;
 constexpr int kPgmY = 72;   // doubles of one block row of y: 6 rows x 12 columns
-
-__host__ __device__ constexpr int lidx(int r, int c) { return r * (r + 1) / 2 + c; }  // r >= c
-
-__device__ __forceinline__ void so3_log(const double (&R)[9], double (&w)[6])
-{
-    const double vx = 0.5 * (R[7] - R[5]), vy = 0.5 * (R[2] - R[6]), vz = 0.5 * (R[3] - R[1]);
-    const double s = sqrt((vx * vx + vy * vy) + vz * vz);
-    const double c = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
-    const double th = atan2(s, c);
-    double k;
-    if (s < 1e-4 && c > 0.0)
-        k = 1.0 + (s * s) / 6.0;
-    else
-        k = th / s;
-    w[0] = k * vx;
-    w[1] = k * vy;
-    w[2] = k * vz;
-}
-
-__device__ __forceinline__ void so3_jrinv(const double (&w)[6], double (&J)[9])
-{
-    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
-    const double th = sqrt(th2);
-    double g;
-    if (th < 1e-4)
-        g = 1.0 / 12.0 + th2 / 720.0;
-    else
-        g = 1.0 / th2 - (1.0 + cos(th)) / ((2.0 * th) * sin(th));
-    const double x = w[0], y = w[1], z = w[2];
-    J[0] = 1.0 + g * (x * x - th2);
-    J[1] = g * (x * y) - 0.5 * z;
-    J[2] = g * (x * z) + 0.5 * y;
-    J[3] = g * (x * y) + 0.5 * z;
-    J[4] = 1.0 + g * (y * y - th2);
-    J[5] = g * (y * z) - 0.5 * x;
-    J[6] = g * (x * z) - 0.5 * y;
-    J[7] = g * (y * z) + 0.5 * x;
-    J[8] = 1.0 + g * (z * z - th2);
-}
-
-// pose prior of one node: error e = (Log(R0^T R), R0^T (t - t0)); Jw = Jr^-1(e_w), Jv = R0^T R
-__device__ __forceinline__ void pose_prior(const double (&R0)[9], const double (&t0)[3], const double (&R)[9],
-                                           const double (&t)[3], double (&e)[6], double (&Jw)[9], double (&Jv)[9])
-{
-    double Re[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            Re[3 * i + j] = (R0[i] * R[j] + R0[3 + i] * R[3 + j]) + R0[6 + i] * R[6 + j];
-    so3_log(Re, e);
-    const double d0 = t[0] - t0[0], d1 = t[1] - t0[1], d2 = t[2] - t0[2];
-    e[3] = (R0[0] * d0 + R0[3] * d1) + R0[6] * d2;
-    e[4] = (R0[1] * d0 + R0[4] * d1) + R0[7] * d2;
-    e[5] = (R0[2] * d0 + R0[5] * d1) + R0[8] * d2;
-    so3_jrinv(e, Jw);
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-        Jv[k] = Re[k];
-}
-
-// in-place Cholesky of the packed lower triangle; false if not positive definite.  The diagonal holds 1 / l_jj.  `min_d`
-// follows the smallest pivot (l_jj squared).
-template <int N>
-__device__ __forceinline__ bool chol_packed(double (&S)[N * (N + 1) / 2], double &min_d)
-{
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        double d = S[lidx(j, j)];
-#pragma unroll
-        for (int k = 0; k < j; ++k)
-            d = fma(-S[lidx(j, k)], S[lidx(j, k)], d);
-        ok = ok && (d > 0.0) && (d < __builtin_inf());
-        min_d = d < min_d ? d : min_d;
-        const double inv = 1.0 / sqrt(d);
-        S[lidx(j, j)] = inv;
-#pragma unroll
-        for (int i = j + 1; i < N; ++i) {
-            double v = S[lidx(i, j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k)
-                v = fma(-S[lidx(i, k)], S[lidx(j, k)], v);
-            S[lidx(i, j)] = v * inv;
-        }
-    }
-    return ok;
-}
-
-// whitening factor of one edge: S = L L^T, W = L^-1 (packed lower).  False if S (its lower triangle) is not positive
-// definite; nothing is repaired.
-__device__ __forceinline__ bool edge_prep(const double *cov, double *Wout)
-{
-    double S[21];
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c <= r; ++c)
-            S[lidx(r, c)] = cov[6 * r + c];
-    double unused = __builtin_inf();
-    const bool ok = chol_packed<6>(S, unused);
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {   // column c of L^-1: forward substitution of the unit vector e_c
-        double b[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            double v = (i == c) ? 1.0 : 0.0;
-#pragma unroll
-            for (int k = c; k < i; ++k)
-                v = fma(-S[lidx(i, k)], b[k], v);
-            b[i] = v * S[lidx(i, i)];
-            if (i >= c)
-                Wout[lidx(i, c)] = b[i];
-        }
-    }
-    return ok;
-}
-
-// out = W v, W packed lower 6 x 6
-__device__ __forceinline__ void whiten(const double (&W)[21], const double (&v)[6], double *out, int stride)
-{
-#pragma unroll
-    for (int m = 0; m < 6; ++m) {
-        double s = W[lidx(m, 0)] * v[0];
-#pragma unroll
-        for (int c = 1; c <= m; ++c)
-            s = fma(W[lidx(m, c)], v[c], s);
-        out[m * stride] = s;
-    }
-}
-
-// whitened residual and Jacobians of edge (Z, W) between (Rs, ts) and (Rd, td): lin = {r[6], A_src[6][6], A_dst[6][6]}
-// (row-major), column by column so that no 6 x 6 block ever lives in registers
-__device__ __forceinline__ void edge_eval(const double *Zp, const double (&W)[21], const double *ps, const double *pd, double *lin)
-{
-    double Rz[9], Rsd[9], E[9], e[6], r[6];
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-        Rz[k] = Zp[k];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            Rsd[3 * i + j] = (ps[i] * pd[j] + ps[3 + i] * pd[3 + j]) + ps[6 + i] * pd[6 + j];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            E[3 * i + j] = (Rz[i] * Rsd[j] + Rz[3 + i] * Rsd[3 + j]) + Rz[6 + i] * Rsd[6 + j];
-    so3_log(E, e);
-    const double d0 = pd[9] - ps[9], d1 = pd[10] - ps[10], d2 = pd[11] - ps[11];
-    double q[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        q[i] = (ps[i] * d0 + ps[3 + i] * d1) + ps[6 + i] * d2;
-    const double m0 = q[0] - Zp[9], m1 = q[1] - Zp[10], m2 = q[2] - Zp[11];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        e[3 + i] = (Rz[i] * m0 + Rz[3 + i] * m1) + Rz[6 + i] * m2;
-    whiten(W, e, r, 1);
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-        lin[k] = r[k];
-    double Jri[9];
-    so3_jrinv(e, Jri);
-    // [q]x by columns
-    const double qx[3][3] = {{0.0, q[2], -q[1]}, {-q[2], 0.0, q[0]}, {q[1], -q[0], 0.0}};
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double cs[6], cd[6];   // column i of d e / d src and d e / d dst
-        if (i < 3) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                cs[c] = -((Jri[3 * c] * Rsd[3 * i] + Jri[3 * c + 1] * Rsd[3 * i + 1]) + Jri[3 * c + 2] * Rsd[3 * i + 2]);
-                cs[3 + c] = (Rz[c] * qx[i][0] + Rz[3 + c] * qx[i][1]) + Rz[6 + c] * qx[i][2];
-                cd[c] = Jri[3 * c + i];
-                cd[3 + c] = 0.0;
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                cs[c] = 0.0;
-                cs[3 + c] = -Rz[3 * (i - 3) + c];
-                cd[c] = 0.0;
-                cd[3 + c] = E[3 * c + (i - 3)];
-            }
-        }
-        whiten(W, cs, lin + 6 + i, 6);
-        whiten(W, cd, lin + 42 + i, 6);
-    }
-}
-
-// column i of A . column j of B (A, B row-major 6 x 6)
-__device__ __forceinline__ double coldot(const double *A, int i, const double *B, int j)
-{
-    double s = A[i] * B[j];
-#pragma unroll
-    for (int m = 1; m < 6; ++m)
-        s = fma(A[6 * m + i], B[6 * m + j], s);
-    return s;
-}
 
 // the anchor prior's block of H at pose P with mean P0: entry (i, j) as posegraph.hip's anchor_h
 __device__ __forceinline__ void anchor_block(const double (&w)[2], const double *P0, const double *P, double *Ha)
@@ -245,7 +42,7 @@ __device__ __forceinline__ void anchor_block(const double (&w)[2], const double 
         t0[k] = P0[9 + k];
         t[k] = P[9 + k];
     }
-    pose_prior(R0, t0, R, t, e, Jw, Jv);
+    pose_prior<true>(R0, t0, R, t, e, Jw, Jv);
 #pragma unroll
     for (int i = 0; i < 6; ++i)
 #pragma unroll
@@ -271,11 +68,11 @@ __global__ __launch_bounds__(kPgmThreads) void pgm_lin_kernel(PgmDev d)
     }
     if (k >= d.n_edges)
         return;
-    double W[21];
+    double W[21], r[6];
     if (!edge_prep(d.edge_cov + 36 * (int64_t)k, W))
         d.state->status = 1;   // every writer stores the same word (the host clears it before the launch)
-    edge_eval(d.edge_pose + 12 * (int64_t)k, W, d.X + 12 * (int64_t)d.edge_src[k], d.X + 12 * (int64_t)d.edge_dst[k],
-              d.lin + (int64_t)kPgLin * k);
+    edge_eval<true>(d.edge_pose + 12 * (int64_t)k, W, d.X + 12 * (int64_t)d.edge_src[k], d.X + 12 * (int64_t)d.edge_dst[k], r,
+                    d.lin + (int64_t)kPgLin * k);
 }
 
 __global__ __launch_bounds__(kPgmThreads) void pgm_gather_kernel(PgmDev d)

@@ -25,11 +25,8 @@
 // the cost becomes rho2(|r|^2) and its linearisation is multiplied by sqrt(w), in pg_dense_kernel and pg_edge_kernel; every
 // other kernel, pg_direct.hip's included, reads what those two left.  Without a loss the kernels are the ones they were.
 //
-// so3_exp / so3_log / so3_jrinv / pose_prior / chol_packed / chol_solve are COPIES of the functions in refine.hip's
-// anonymous namespace (same statements, same order): moving them to device_math.hpp would recompile every refine kernel
-// from a different inclusion order, and keeping their resource figures identical to the parent build's could not be
-// promised, so refine.hip is left alone.
-#include "kernels.hpp"
+// The SO(3), prior, Cholesky and loss functions are lm_math.hpp's and the edge functions pg_edge.hpp's, shared with the other solvers.
+#include "pg_edge.hpp"
 
 namespace mvs {
 
@@ -38,268 +35,12 @@ namespace {
 constexpr int kPgThreads = 256;
 constexpr int kPgDim = 6 * kPgDenseMaxNodes;   // 96
 
-__host__ __device__ constexpr int lidx(int r, int c) { return r * (r + 1) / 2 + c; }  // r >= c
-
-__device__ __forceinline__ void so3_exp(const double (&w)[3], double (&R)[9])
-{
-    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
-    const double th = sqrt(th2);
-    double A, B;
-    if (th < 1e-4) {
-        A = 1.0 - th2 / 6.0;
-        B = 0.5 - th2 / 24.0;
-    } else {
-        A = sin(th) / th;
-        B = (1.0 - cos(th)) / th2;
-    }
-    const double x = w[0], y = w[1], z = w[2];
-    R[0] = 1.0 - B * (y * y + z * z);
-    R[1] = B * (x * y) - A * z;
-    R[2] = B * (x * z) + A * y;
-    R[3] = B * (x * y) + A * z;
-    R[4] = 1.0 - B * (x * x + z * z);
-    R[5] = B * (y * z) - A * x;
-    R[6] = B * (x * z) - A * y;
-    R[7] = B * (y * z) + A * x;
-    R[8] = 1.0 - B * (x * x + y * y);
-}
-
-__device__ __forceinline__ void so3_log(const double (&R)[9], double (&w)[6])
-{
-    const double vx = 0.5 * (R[7] - R[5]), vy = 0.5 * (R[2] - R[6]), vz = 0.5 * (R[3] - R[1]);
-    const double s = sqrt((vx * vx + vy * vy) + vz * vz);
-    const double c = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
-    const double th = atan2(s, c);
-    double k;
-    if (s < 1e-4 && c > 0.0)
-        k = 1.0 + (s * s) / 6.0;
-    else
-        k = th / s;
-    w[0] = k * vx;
-    w[1] = k * vy;
-    w[2] = k * vz;
-}
-
-__device__ __forceinline__ void so3_jrinv(const double (&w)[6], double (&J)[9])
-{
-    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
-    const double th = sqrt(th2);
-    double g;
-    if (th < 1e-4)
-        g = 1.0 / 12.0 + th2 / 720.0;
-    else
-        g = 1.0 / th2 - (1.0 + cos(th)) / ((2.0 * th) * sin(th));
-    const double x = w[0], y = w[1], z = w[2];
-    J[0] = 1.0 + g * (x * x - th2);
-    J[1] = g * (x * y) - 0.5 * z;
-    J[2] = g * (x * z) + 0.5 * y;
-    J[3] = g * (x * y) + 0.5 * z;
-    J[4] = 1.0 + g * (y * y - th2);
-    J[5] = g * (y * z) - 0.5 * x;
-    J[6] = g * (x * z) - 0.5 * y;
-    J[7] = g * (y * z) + 0.5 * x;
-    J[8] = 1.0 + g * (z * z - th2);
-}
-
-// pose prior of one node: error e = (Log(R0^T R), R0^T (t - t0)); Jw = Jr^-1(e_w), Jv = R0^T R
-template <bool JAC>
-__device__ __forceinline__ void pose_prior(const double (&R0)[9], const double (&t0)[3], const double (&R)[9],
-                                           const double (&t)[3], double (&e)[6], double (&Jw)[9], double (&Jv)[9])
-{
-    double Re[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            Re[3 * i + j] = (R0[i] * R[j] + R0[3 + i] * R[3 + j]) + R0[6 + i] * R[6 + j];
-    so3_log(Re, e);
-    const double d0 = t[0] - t0[0], d1 = t[1] - t0[1], d2 = t[2] - t0[2];
-    e[3] = (R0[0] * d0 + R0[3] * d1) + R0[6] * d2;
-    e[4] = (R0[1] * d0 + R0[4] * d1) + R0[7] * d2;
-    e[5] = (R0[2] * d0 + R0[5] * d1) + R0[8] * d2;
-    if (JAC) {
-        so3_jrinv(e, Jw);
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-            Jv[k] = Re[k];
-    }
-}
-
-// in-place Cholesky of the packed lower triangle; false if not positive definite.  The diagonal holds 1 / l_jj.
-template <int N>
-__device__ __forceinline__ bool chol_packed(double (&S)[N * (N + 1) / 2])
-{
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        double d = S[lidx(j, j)];
-#pragma unroll
-        for (int k = 0; k < j; ++k)
-            d = fma(-S[lidx(j, k)], S[lidx(j, k)], d);
-        ok = ok && (d > 0.0) && (d < __builtin_inf());
-        const double inv = 1.0 / sqrt(d);
-        S[lidx(j, j)] = inv;
-#pragma unroll
-        for (int i = j + 1; i < N; ++i) {
-            double v = S[lidx(i, j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k)
-                v = fma(-S[lidx(i, k)], S[lidx(j, k)], v);
-            S[lidx(i, j)] = v * inv;
-        }
-    }
-    return ok;
-}
-
-template <int N>
-__device__ __forceinline__ void chol_solve(const double (&Lc)[N * (N + 1) / 2], double (&b)[N])
-{
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double v = b[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k)
-            v = fma(-Lc[lidx(i, k)], b[k], v);
-        b[i] = v * Lc[lidx(i, i)];
-    }
-#pragma unroll
-    for (int i = N - 1; i >= 0; --i) {
-        double v = b[i];
-#pragma unroll
-        for (int k = i + 1; k < N; ++k)
-            v = fma(-Lc[lidx(k, i)], b[k], v);
-        b[i] = v * Lc[lidx(i, i)];
-    }
-}
-
-// ---- one edge ---------------------------------------------------------------------------------------------------------
-// whitening factor of one edge: S = L L^T, W = L^-1 (packed lower).  False if S (its lower triangle) is not positive
-// definite; nothing is repaired.
-__device__ __forceinline__ bool edge_prep(const double *cov, double *Wout)
-{
-    double S[21];
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c <= r; ++c)
-            S[lidx(r, c)] = cov[6 * r + c];
-    const bool ok = chol_packed<6>(S);
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {   // column c of L^-1: forward substitution of the unit vector e_c
-        double b[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            double v = (i == c) ? 1.0 : 0.0;
-#pragma unroll
-            for (int k = c; k < i; ++k)
-                v = fma(-S[lidx(i, k)], b[k], v);
-            b[i] = v * S[lidx(i, i)];
-            if (i >= c)
-                Wout[lidx(i, c)] = b[i];
-        }
-    }
-    return ok;
-}
-
-// out = W v, W packed lower 6 x 6
-__device__ __forceinline__ void whiten(const double (&W)[21], const double (&v)[6], double *out, int stride)
-{
-#pragma unroll
-    for (int m = 0; m < 6; ++m) {
-        double s = W[lidx(m, 0)] * v[0];
-#pragma unroll
-        for (int c = 1; c <= m; ++c)
-            s = fma(W[lidx(m, c)], v[c], s);
-        out[m * stride] = s;
-    }
-}
-
-// whitened residual of edge (Z, W) between (Rs, ts) and (Rd, td); when JAC, its whitened Jacobians too, written column by
-// column so that no 6 x 6 block ever lives in registers: lin = {r[6], A_src[6][6], A_dst[6][6]} (row-major)
-//   d e / d dst = [ Jr^-1(e_w)          0 ]      d e / d src = [ -Jr^-1(e_w) (Rs^T Rd)^T      0    ]
-//                 [ 0                   E ]                    [  Rz^T [q]x                  -Rz^T ]
-// with E = Rz^T Rs^T Rd and q = Rs^T (td - ts).
-template <bool JAC>
-__device__ __forceinline__ void edge_eval(const double *Zp, const double *Wp, const double *ps, const double *pd,
-                                          double (&r)[6], double *lin)
-{
-    double Rz[9], W[21], Rsd[9], E[9], e[6];
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-        Rz[k] = Zp[k];
-#pragma unroll
-    for (int k = 0; k < 21; ++k)
-        W[k] = Wp[k];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            Rsd[3 * i + j] = (ps[i] * pd[j] + ps[3 + i] * pd[3 + j]) + ps[6 + i] * pd[6 + j];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            E[3 * i + j] = (Rz[i] * Rsd[j] + Rz[3 + i] * Rsd[3 + j]) + Rz[6 + i] * Rsd[6 + j];
-    so3_log(E, e);
-    const double d0 = pd[9] - ps[9], d1 = pd[10] - ps[10], d2 = pd[11] - ps[11];
-    double q[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        q[i] = (ps[i] * d0 + ps[3 + i] * d1) + ps[6 + i] * d2;
-    const double m0 = q[0] - Zp[9], m1 = q[1] - Zp[10], m2 = q[2] - Zp[11];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        e[3 + i] = (Rz[i] * m0 + Rz[3 + i] * m1) + Rz[6 + i] * m2;
-    whiten(W, e, r, 1);
-    if (JAC) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            lin[k] = r[k];
-        double Jri[9];
-        so3_jrinv(e, Jri);
-        // [q]x by columns
-        const double qx[3][3] = {{0.0, q[2], -q[1]}, {-q[2], 0.0, q[0]}, {q[1], -q[0], 0.0}};
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            double cs[6], cd[6];   // column i of d e / d src and d e / d dst
-            if (i < 3) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    cs[c] = -((Jri[3 * c] * Rsd[3 * i] + Jri[3 * c + 1] * Rsd[3 * i + 1]) + Jri[3 * c + 2] * Rsd[3 * i + 2]);
-                    cs[3 + c] = (Rz[c] * qx[i][0] + Rz[3 + c] * qx[i][1]) + Rz[6 + c] * qx[i][2];
-                    cd[c] = Jri[3 * c + i];
-                    cd[3 + c] = 0.0;
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    cs[c] = 0.0;
-                    cs[3 + c] = -Rz[3 * (i - 3) + c];
-                    cd[c] = 0.0;
-                    cd[3 + c] = E[3 * c + (i - 3)];
-                }
-            }
-            whiten(W, cs, lin + 6 + i, 6);
-            whiten(W, cd, lin + 42 + i, 6);
-        }
-    }
-}
-
 __device__ __forceinline__ double sq6(const double (&r)[6])
 {
     return fma(r[5], r[5], fma(r[4], r[4], fma(r[3], r[3], fma(r[2], r[2], fma(r[1], r[1], r[0] * r[0])))));
 }
 
 // ---- robust losses (mvs_ctx_set_pose_graph_loss) ----------------------------------------------
-// weight w(s) of a robustified edge from s = |r|^2 and x = sqrt(s): Huber 1 or k / x, Cauchy k^2 / (k^2 + s)
-__device__ __forceinline__ double pg_loss_weight(const PgCfg &cfg, double s, double x)
-{
-    const double k = cfg.loss_k;
-    if (cfg.loss == 1)
-        return x <= k ? 1.0 : k / x;
-    const double k2 = k * k;
-    return k2 / (k2 + s);
-}
 // edge k_index with s = |r|^2: rho2(s), its term of twice the cost, and sqrt(w(s)), the factor of its residual and Jacobians.
 // Below cfg.loss_first: s and 1.  The order is the contract's: one sqrt, one division (the Cauchy cost: log1p of one
 // quotient), one sqrt.
@@ -310,39 +51,14 @@ __device__ __forceinline__ void pg_loss(const PgCfg &cfg, int k_index, double s,
     if (k_index < cfg.loss_first)
         return;
     const double k = cfg.loss_k, x = sqrt(s);
-    if (cfg.loss == 1) {
-        if (!(x <= k))
-            rho2 = (2.0 * k) * x - k * k;
-    } else {
-        const double k2 = k * k;
-        rho2 = k2 * log1p(s / k2);
-    }
-    sqrt_w = sqrt(pg_loss_weight(cfg, s, x));
+    rho2 = pg_loss_rho2(cfg.loss, k, s, x);
+    sqrt_w = sqrt(loss_weight(cfg.loss, k, s, x));
 }
 // the linearised edge {r, A_src, A_dst} times sqrt(w): what makes the normal equations those of the reweighted problem
 __device__ __forceinline__ void pg_scale_lin(double *lin, double sqrt_w)
 {
     for (int i = 0; i < kPgLin; ++i)
         lin[i] = lin[i] * sqrt_w;
-}
-
-// column i of A . column j of B (A, B row-major 6 x 6)
-__device__ __forceinline__ double coldot(const double *A, int i, const double *B, int j)
-{
-    double s = A[i] * B[j];
-#pragma unroll
-    for (int m = 1; m < 6; ++m)
-        s = fma(A[6 * m + i], B[6 * m + j], s);
-    return s;
-}
-// column i of A . r
-__device__ __forceinline__ double colvec(const double *A, int i, const double *r)
-{
-    double s = A[i] * r[0];
-#pragma unroll
-    for (int m = 1; m < 6; ++m)
-        s = fma(A[6 * m + i], r[m], s);
-    return s;
 }
 
 // anchor prior at pose P with mean P0: cost, and when JAC the error and the two Jacobians into anc = {e[6], Jw[9], Jv[9]}
@@ -690,7 +406,7 @@ __global__ __launch_bounds__(kPgThreads) void pg_edge_stats_kernel(PgStatsDev d)
     const double s = sq6(r);
     d.chi2[k] = s;
     if (d.weight)
-        d.weight[k] = d.cfg.loss != 0 && k >= d.cfg.loss_first ? pg_loss_weight(d.cfg, s, sqrt(s)) : 1.0;
+        d.weight[k] = d.cfg.loss != 0 && k >= d.cfg.loss_first ? loss_weight(d.cfg.loss, d.cfg.loss_k, s, sqrt(s)) : 1.0;
 }
 
 // sum of the edges' costs (thread t: edges t, t + 256, ... in order; then the workgroup tree) + the anchor -> *dst

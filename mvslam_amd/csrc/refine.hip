@@ -17,88 +17,14 @@
 //   covariance = P + P Hcp^T S^-1 Hcp P.
 // The CPU oracle (oracle/mvs_refine_oracle.c) follows the same summation order; sin / cos / atan2 come from different
 // libraries on the two sides, so parity for this row is by tolerance.
-#include "kernels.hpp"
+// The SO(3) maps, the pose prior, the projection and the Cholesky routines are lm_math.hpp's, shared with the other solvers.
+#include "lm_math.hpp"
 
 namespace mvs {
 
 namespace {
 
 constexpr int kRefineThreads = 256;
-
-__host__ __device__ constexpr int lidx(int r, int c) { return r * (r + 1) / 2 + c; }  // r >= c
-
-struct Cam {
-    double fx, fy, sk, cx, cy;
-};
-
-// fused building blocks (one v_fma_f64 each); the oracle uses the same ones in the same places
-__device__ __forceinline__ double fd2(double a0, double b0, double a1, double b1) { return fma(a1, b1, a0 * b0); }
-__device__ __forceinline__ double fd3(double a0, double b0, double a1, double b1, double a2, double b2)
-{
-    return fma(a2, b2, fma(a1, b1, a0 * b0));
-}
-__device__ __forceinline__ double fx2(double a, double b, double c, double d) { return fma(a, b, -(c * d)); }  // a b - c d
-
-__device__ __forceinline__ void so3_exp(const double (&w)[3], double (&R)[9])
-{
-    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
-    const double th = sqrt(th2);
-    double A, B;
-    if (th < 1e-4) {
-        A = 1.0 - th2 / 6.0;
-        B = 0.5 - th2 / 24.0;
-    } else {
-        A = sin(th) / th;
-        B = (1.0 - cos(th)) / th2;
-    }
-    const double x = w[0], y = w[1], z = w[2];
-    R[0] = 1.0 - B * (y * y + z * z);
-    R[1] = B * (x * y) - A * z;
-    R[2] = B * (x * z) + A * y;
-    R[3] = B * (x * y) + A * z;
-    R[4] = 1.0 - B * (x * x + z * z);
-    R[5] = B * (y * z) - A * x;
-    R[6] = B * (x * z) - A * y;
-    R[7] = B * (y * z) + A * x;
-    R[8] = 1.0 - B * (x * x + y * y);
-}
-
-__device__ __forceinline__ void so3_log(const double (&R)[9], double (&w)[6])
-{
-    const double vx = 0.5 * (R[7] - R[5]), vy = 0.5 * (R[2] - R[6]), vz = 0.5 * (R[3] - R[1]);
-    const double s = sqrt((vx * vx + vy * vy) + vz * vz);
-    const double c = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
-    const double th = atan2(s, c);
-    double k;
-    if (s < 1e-4 && c > 0.0)
-        k = 1.0 + (s * s) / 6.0;
-    else
-        k = th / s;
-    w[0] = k * vx;
-    w[1] = k * vy;
-    w[2] = k * vz;
-}
-
-__device__ __forceinline__ void so3_jrinv(const double (&w)[6], double (&J)[9])
-{
-    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
-    const double th = sqrt(th2);
-    double g;
-    if (th < 1e-4)
-        g = 1.0 / 12.0 + th2 / 720.0;
-    else
-        g = 1.0 / th2 - (1.0 + cos(th)) / ((2.0 * th) * sin(th));
-    const double x = w[0], y = w[1], z = w[2];
-    J[0] = 1.0 + g * (x * x - th2);
-    J[1] = g * (x * y) - 0.5 * z;
-    J[2] = g * (x * z) + 0.5 * y;
-    J[3] = g * (x * y) + 0.5 * z;
-    J[4] = 1.0 + g * (y * y - th2);
-    J[5] = g * (y * z) - 0.5 * x;
-    J[6] = g * (x * z) - 0.5 * y;
-    J[7] = g * (y * z) + 0.5 * x;
-    J[8] = 1.0 + g * (z * z - th2);
-}
 
 __device__ __forceinline__ void sym3_inverse(const double (&a)[6], double (&o)[6])
 {
@@ -113,75 +39,6 @@ __device__ __forceinline__ void sym3_inverse(const double (&a)[6], double (&o)[6
     o[3] = fx2(a[0], a[5], a[2], a[2]) * id;
     o[4] = fx2(a[1], a[2], a[0], a[4]) * id;
     o[5] = fx2(a[0], a[3], a[1], a[1]) * id;
-}
-
-// pose prior of one frame: error e = (Log(R0^T R), R0^T (t - t0)); Jw = Jr^-1(e_w), Jv = R0^T R
-template <bool JAC>
-__device__ __forceinline__ void pose_prior(const double (&R0)[9], const double (&t0)[3], const double (&R)[9],
-                                           const double (&t)[3], double (&e)[6], double (&Jw)[9], double (&Jv)[9])
-{
-    double Re[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            Re[3 * i + j] = (R0[i] * R[j] + R0[3 + i] * R[3 + j]) + R0[6 + i] * R[6 + j];
-    so3_log(Re, e);
-    const double d0 = t[0] - t0[0], d1 = t[1] - t0[1], d2 = t[2] - t0[2];
-    e[3] = (R0[0] * d0 + R0[3] * d1) + R0[6] * d2;
-    e[4] = (R0[1] * d0 + R0[4] * d1) + R0[7] * d2;
-    e[5] = (R0[2] * d0 + R0[5] * d1) + R0[8] * d2;
-    if (JAC) {
-        so3_jrinv(e, Jw);
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-            Jv[k] = Re[k];
-    }
-}
-
-// residual of one observation (and its Jacobians): GenericProjectionFactor with throwCheirality = false
-template <bool JAC>
-__device__ __forceinline__ void project_lin(const Cam &cam, const double (&R)[9], const double (&t)[3],
-                                            const double (&p)[3], double u, double v, double (&r)[2], double (&Jc)[12],
-                                            double (&Jp)[6])
-{
-    const double d0 = p[0] - t[0], d1 = p[1] - t[1], d2 = p[2] - t[2];
-    const double q0 = fd3(R[0], d0, R[3], d1, R[6], d2);
-    const double q1 = fd3(R[1], d0, R[4], d1, R[7], d2);
-    const double q2 = fd3(R[2], d0, R[5], d1, R[8], d2);
-    if (!(q2 > 0.0)) {
-        r[0] = 2.0 * cam.fx;
-        r[1] = 2.0 * cam.fx;
-        if (JAC) {
-#pragma unroll
-            for (int k = 0; k < 12; ++k)
-                Jc[k] = 0.0;
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-                Jp[k] = 0.0;
-        }
-        return;
-    }
-    const double iz = 1.0 / q2, xn = q0 * iz, yn = q1 * iz;
-    const double un = fd2(cam.fx, xn, cam.sk, yn), vn = cam.fy * yn;
-    r[0] = (un + cam.cx) - u;
-    r[1] = (vn + cam.cy) - v;
-    if (JAC) {
-        const double A[6] = {cam.fx * iz, cam.sk * iz, -(un * iz), 0.0, cam.fy * iz, -(vn * iz)};
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            const double a0 = A[3 * a], a1 = A[3 * a + 1], a2 = A[3 * a + 2];
-            Jc[6 * a + 0] = fx2(a1, q2, a2, q1);
-            Jc[6 * a + 1] = fx2(a2, q0, a0, q2);
-            Jc[6 * a + 2] = fx2(a0, q1, a1, q0);
-            Jc[6 * a + 3] = -a0;
-            Jc[6 * a + 4] = -a1;
-            Jc[6 * a + 5] = -a2;
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                Jp[3 * a + k] = fd3(a0, R[3 * k], a1, R[3 * k + 1], a2, R[3 * k + 2]);
-        }
-    }
 }
 
 template <int F>
@@ -441,54 +298,6 @@ __device__ __forceinline__ double prior_cost(const RefineCfg &cfg, const double 
             c = c + (e[k] * e[k]) * cfg.w[f][k];
     }
     return c;
-}
-
-// in-place Cholesky of the packed lower triangle; false if not positive definite.  The diagonal holds 1 / l_jj (one
-// division per column; the other 78 divisions of a factorisation + solve are multiplications by it, as in the oracle)
-template <int N>
-__device__ __forceinline__ bool chol_packed(double (&S)[N * (N + 1) / 2])
-{
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        double d = S[lidx(j, j)];
-#pragma unroll
-        for (int k = 0; k < j; ++k)
-            d = fma(-S[lidx(j, k)], S[lidx(j, k)], d);
-        ok = ok && (d > 0.0) && (d < __builtin_inf());
-        const double inv = 1.0 / sqrt(d);
-        S[lidx(j, j)] = inv;
-#pragma unroll
-        for (int i = j + 1; i < N; ++i) {
-            double v = S[lidx(i, j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k)
-                v = fma(-S[lidx(i, k)], S[lidx(j, k)], v);
-            S[lidx(i, j)] = v * inv;
-        }
-    }
-    return ok;
-}
-
-template <int N>
-__device__ __forceinline__ void chol_solve(const double (&Lc)[N * (N + 1) / 2], double (&b)[N])
-{
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double v = b[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k)
-            v = fma(-Lc[lidx(i, k)], b[k], v);
-        b[i] = v * Lc[lidx(i, i)];
-    }
-#pragma unroll
-    for (int i = N - 1; i >= 0; --i) {
-        double v = b[i];
-#pragma unroll
-        for (int k = i + 1; k < N; ++k)
-            v = fma(-Lc[lidx(k, i)], b[k], v);
-        b[i] = v * Lc[lidx(i, i)];
-    }
 }
 
 // one pass over the thread's points adding the entries [LO, HI) of {S packed, b, cost} (per-thread partial sums)
@@ -922,7 +731,7 @@ __global__ __launch_bounds__(kRefineThreads) void refine_kernel(RefineDev d)
 //   summed over il at its end: xor 8, 16, 32 inside the wavefront, then (w0 + w1) + (w2 + w3) through LDS.
 //   S is factored in LDS by the whole workgroup (right-looking Cholesky, the trailing update spread over the entry owners);
 //   the triangular solves run in one wavefront, lane k holding component k (readlane, no barrier).
-// A pivot must exceed kWinPivotTol times the entry's value before elimination (the accumulated rounding error of the
+// A pivot must exceed kBaPivotTol (kernels.hpp) times the entry's value before elimination (the accumulated rounding error of the
 // eliminations is of that size): a gauge that no prior fixes, or a point that nothing determines, leaves pivots that are
 // rounding noise of either sign, and they are reported as "not positive definite" whichever sign they have.
 constexpr int kWinThreads = 256;
@@ -931,7 +740,6 @@ constexpr int kWinNC = 6 * kWinMaxFrames;                // 48
 constexpr int kWinNL = kWinNC * (kWinNC + 1) / 2;        // 1176
 constexpr int kWinRows = kWinNC + 1;                     // Z rows of one point: the camera rows, then L^-1 g_p
 constexpr int kWinEnt = (kWinNL + kWinNC + kWinThreads - 1) / kWinThreads;   // entries per thread: 5
-constexpr double kWinPivotTol = 1.0 / (double)(1ll << 42);   // 2.3e-13 ~ 16 x 48 x 2^-52
 
 // sum over the eight lanes tid / 8 shares (the frames of one point), the same value in each of them
 __device__ __forceinline__ double oct_sum(double x)
@@ -1012,24 +820,7 @@ __device__ __forceinline__ bool win_linearize(const Cam &cam, bool on, const dou
     const double g2 = fd3(L[2], d0, L[4], d1, L[5], d2) + oct_sum(gp[2]);
     const double v0 = V[0] + lam, v3 = V[3] + lam, v5 = V[5] + lam;
     // V = L L^T, then L^-1
-    const double inf = __builtin_inf();
-    bool ok = v0 > 0.0 && v0 < inf;
-    const double i0 = 1.0 / sqrt(v0);
-    const double l10 = V[1] * i0, l20 = V[2] * i0;
-    const double e1 = fma(-l10, l10, v3);
-    ok = ok && e1 > kWinPivotTol * v3 && e1 < inf;
-    const double i1 = 1.0 / sqrt(e1);
-    const double l21 = fma(-l20, l10, V[4]) * i1;
-    const double e2 = fma(-l21, l21, fma(-l20, l20, v5));
-    ok = ok && e2 > kWinPivotTol * v5 && e2 < inf;
-    const double i2 = 1.0 / sqrt(e2);
-    const double m10 = -(l10 * i0) * i1, m21 = -(l21 * i1) * i2, m20 = -fd2(l20, i0, l21, m10) * i2;
-    Li[0] = ok ? i0 : 0.0;
-    Li[1] = ok ? m10 : 0.0;
-    Li[2] = ok ? i1 : 0.0;
-    Li[3] = ok ? m20 : 0.0;
-    Li[4] = ok ? m21 : 0.0;
-    Li[5] = ok ? i2 : 0.0;
+    const bool ok = chol3_pivot(V, v0, v3, v5, Li);
     gh[0] = Li[0] * g0;
     gh[1] = fd2(Li[1], g0, Li[2], g1);
     gh[2] = fd3(Li[3], g0, Li[4], g1, Li[5], g2);
@@ -1321,7 +1112,7 @@ __global__ __launch_bounds__(kWinThreads) void refine_window_kernel(WinDev d)
         // right-looking Cholesky; column j is final when step j starts
         for (int j = 0; j < NC; ++j) {
             const double dj = sS[lidx(j, j)];
-            if (!(dj > kWinPivotTol * sDiag[j] && dj < __builtin_inf()))
+            if (!(dj > kBaPivotTol * sDiag[j] && dj < __builtin_inf()))
                 return false;   // uniform: every thread reads the same value
             const double inv = 1.0 / sqrt(dj);
             if (tid == j)

@@ -12,41 +12,14 @@
 //                             slot order, ascending (d, k).
 //   loop_edges_kernel         one workgroup: the verified loop-closure candidates (loop.hip) through the same rule, appended
 //                             behind the built edges in candidate order.
-#include "kernels.hpp"
+// The positive-definiteness test of an edge covariance is lm_math.hpp's chol_packed<6>, the one the solver's pg_prep_kernel runs.
+#include "lm_math.hpp"
 
 namespace mvs {
 
 namespace {
 
 constexpr int kSgThreads = 256;
-
-__host__ __device__ constexpr int lidx(int r, int c) { return r * (r + 1) / 2 + c; }  // r >= c
-
-// pg_prep_kernel's test (chol_packed<6> of posegraph.hip, the same statements in the same order): is the packed lower
-// triangle positive definite?  Fully unrolled over constant indices: S stays in registers.
-__device__ __forceinline__ bool chol6_ok(double (&S)[21])
-{
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double d = S[lidx(j, j)];
-#pragma unroll
-        for (int k = 0; k < j; ++k)
-            d = fma(-S[lidx(j, k)], S[lidx(j, k)], d);
-        ok = ok && (d > 0.0) && (d < __builtin_inf());
-        const double inv = 1.0 / sqrt(d);
-        S[lidx(j, j)] = inv;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = S[lidx(i, j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k)
-                v = fma(-S[lidx(i, k)], S[lidx(j, k)], v);
-            S[lidx(i, j)] = v * inv;
-        }
-    }
-    return ok;
-}
 
 __global__ __launch_bounds__(kSgThreads) void seq_graph_edges_kernel(SeqGraphDev g)
 {
@@ -90,7 +63,7 @@ __global__ __launch_bounds__(kSgThreads) void seq_graph_edges_kernel(SeqGraphDev
 #pragma unroll
                 for (int c = 0; c <= r; ++c)
                     S[lidx(r, c)] = ((r < 3 ? 1.0 : s) * rr.pose_cov[6 * r + c]) * (c < 3 ? 1.0 : s);
-            if (chol6_ok(S)) {
+            if (chol_packed<6>(S)) {   // pg_prep_kernel's test: is the packed lower triangle positive definite?
                 keep = 1;
                 scale = s;
 #pragma unroll
@@ -219,7 +192,7 @@ __global__ __launch_bounds__(kSgThreads) void loop_edges_kernel(SeqGraphDev g, L
                                 v = v + e.var[r / 3];
                             S[lidx(r, cc)] = v;
                         }
-                    keep = chol6_ok(S) ? 1 : 0;
+                    keep = chol_packed<6>(S) ? 1 : 0;
                 }
             }
         }
