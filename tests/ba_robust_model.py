@@ -17,6 +17,10 @@ Observation o has the whitened residual r_o (2), s_o = |r_o|^2, x = sqrt(s_o):
     residuals, nothing is reweighted.  (scipy's own loss= acts per scalar residual, not per 2-vector: it is not this cost.)
     Its covariances are (A)'s formula evaluated at ITS minimiser: the contract defines them by the reweighted linearisation.
 
+full=True (tests/ba_fullcov_model.py's problems): pb["cov"] and pb["pcov"] hold full covariances, and every observation is
+whitened by the Cholesky factor of its own information matrix W = L L^T, r_w = L^T r, s = r^T W r (_obs_lin_full); with the
+default every function computes what it did.
+
 It also holds the outlier fixtures the host and the GPU tests share, each computed once."""
 import functools
 import os
@@ -120,17 +124,27 @@ def _obs_lin(pb, Rs, ts, P, f):
     return v, r / sig, np.concatenate([Aq @ Sq, -Aq], axis=2) / sig, (Aq @ Rs[f].T) / sig
 
 
+def _obs_lin_full(pb, Rs, ts, P, f, Lo):
+    """_obs_lin for full covariances: every observation is whitened by the Cholesky factor L of its own information matrix
+    W = L L^T (Lo: test_ba_window.full_whiteners), r_w = L^T r, so that s = |r_w|^2 = r^T W r, and the Jacobians likewise"""
+    v, r, Jc, Jp = _obs_lin(dict(pb, sig=1.0), Rs, ts, P, f)
+    LT = Lo[f][v].transpose(0, 2, 1)
+    return v, np.einsum("nij,nj->ni", LT, r), LT @ Jc, LT @ Jp
+
+
 def _prior_only(pb):
     return dict(pb, valid=[np.zeros(len(pb["Xg"]), np.uint8)] * len(pb["poses"]))
 
 
-def robust_blocks(pb, Rs, ts, P, kind, k):
-    """test_ba_window.model_blocks under a loss: the robust error and the blocks of the REWEIGHTED normal equations"""
+def robust_blocks(pb, Rs, ts, P, kind, k, full=False):
+    """test_ba_window.model_blocks under a loss: the robust error and the blocks of the REWEIGHTED normal equations.
+    full: pb["cov"] and pb["pcov"] are full covariances (test_ba_window.model_blocks' `full`; _obs_lin_full)"""
     F = len(pb["poses"])
-    cost, A, gc, D, gp, W = tw.model_blocks(_prior_only(pb), Rs, ts, P)   # the priors, never robustified
+    cost, A, gc, D, gp, W = tw.model_blocks(_prior_only(pb), Rs, ts, P, full)   # the priors, never robustified
     cost = 2.0 * cost
+    Lo = tw.full_whiteners(pb)[0] if full else None
     for f in range(F):
-        v, r, Jc, Jp = _obs_lin(pb, Rs, ts, P, f)
+        v, r, Jc, Jp = _obs_lin_full(pb, Rs, ts, P, f, Lo) if full else _obs_lin(pb, Rs, ts, P, f)
         w, rho = loss(np.sum(r * r, axis=1), kind, k)
         A[f] += np.einsum("n,nia,nib->ab", w, Jc, Jc)
         gc[f] += np.einsum("n,nia,ni->a", w, Jc, r)
@@ -141,19 +155,25 @@ def robust_blocks(pb, Rs, ts, P, kind, k):
     return 0.5 * cost, A, gc, D, gp, W
 
 
-def robust_cost(pb, Rs, ts, P, kind, k):
-    return robust_blocks(pb, Rs, ts, P, kind, k)[0]
+def robust_cost(pb, Rs, ts, P, kind, k, full=False):
+    return robust_blocks(pb, Rs, ts, P, kind, k, full)[0]
 
 
-def obs_stats(pb, Rs, ts, P, kind=NONE, k=1.0):
+def obs_stats(pb, Rs, ts, P, kind=NONE, k=1.0, full=False):
     """(chi2, weight) of every observation in CSR order at the given values: mvs_ba_sparse_obs_stats.  An observation whose
-    point is not in front of its camera has the fixed residual (2 fx, 2 fx)."""
+    point is not in front of its camera has the fixed residual (2 fx, 2 fx).  full: s = r^T W r with W the inverse of the
+    symmetric part of the observation's own pb["cov"] entry (None: identity), no factorisation."""
     F, m = len(pb["poses"]), len(P)
     s = np.zeros((F, m))
     for f in range(F):
         with np.errstate(divide="ignore", invalid="ignore"):
-            v, r, _, _ = _obs_lin(pb, Rs, ts, P, f)
+            v, r, _, _ = _obs_lin(dict(pb, sig=1.0) if full else pb, Rs, ts, P, f)
         behind = ~(((P[v] - ts[f]) @ Rs[f])[:, 2] > 0.0)
+        if full:
+            r[behind] = 2.0 * pb["K"][0, 0]
+            C = np.tile(np.eye(2), (len(v), 1, 1)) if pb["cov"][f] is None else np.asarray(pb["cov"][f], float)[v].reshape(-1, 2, 2)
+            s[f, v] = np.einsum("ni,nij,nj->n", r, np.linalg.inv(0.5 * (C + C.transpose(0, 2, 1))), r)
+            continue
         r[behind] = 2.0 * pb["K"][0, 0] / pb["sig"]
         s[f, v] = np.sum(r * r, axis=1)
     s = csr_order(pb, s)
@@ -175,21 +195,21 @@ def _reduce(F, A, D, W):
     return Di, Y, S
 
 
-def reweighted_cov(pb, sol, kind, k):
+def reweighted_cov(pb, sol, kind, k, full=False):
     """pose_cov / point_cov of the reweighted linearisation at sol's values (test_ba_window.model_solve_blocks' statements)"""
     F, m = len(pb["poses"]), len(pb["Xg"])
-    _, A, gc, D, gp, W = robust_blocks(pb, sol["R"], sol["t"], sol["points"], kind, k)
+    _, A, gc, D, gp, W = robust_blocks(pb, sol["R"], sol["t"], sol["points"], kind, k, full)
     Di, Y, S = _reduce(F, A, D, W)
     Si = np.linalg.inv(S)
     Yn = Y.transpose(1, 0, 2, 3).reshape(m, 6 * F, 3)
     return (np.stack([Si[6 * f:6 * f + 6, 6 * f:6 * f + 6] for f in range(F)]), Di + np.einsum("nac,ab,nbd->ncd", Yn, Si, Yn))
 
 
-def newton_step(pb, sol, kind, k):
+def newton_step(pb, sol, kind, k, full=False):
     """ba_sparse_model.newton_step on the weighted system: the largest entry of the step of the poses and of the points that
     the reweighted normal equations still ask for at sol, and the condition number of the reduced camera system"""
     F = len(pb["poses"])
-    _, A, gc, D, gp, W = robust_blocks(pb, sol["R"], sol["t"], sol["points"], kind, k)
+    _, A, gc, D, gp, W = robust_blocks(pb, sol["R"], sol["t"], sol["points"], kind, k, full)
     Di, Y, S = _reduce(F, A, D, W)
     dc = np.linalg.solve(S, -(gc - np.einsum("fnac,nc->fa", Y, gp)).reshape(6 * F)).reshape(F, 6)
     dp = -np.einsum("nab,nb->na", Di, gp + np.einsum("fnab,fa->nb", W, dc))
@@ -197,11 +217,11 @@ def newton_step(pb, sol, kind, k):
 
 
 # ---- (A) IRLS under bas_solve's LM rule --------------------------------------------------------------------------------
-def solve_irls(pb, kind=NONE, k=1.0, lm=None):
+def solve_irls(pb, kind=NONE, k=1.0, lm=None, full=False):
     lm = dict(LM, **(lm or {}))
     F = len(pb["poses"])
     Rs, ts, P = _guess(pb)
-    cur, A, gc, D, gp, W = robust_blocks(pb, Rs, ts, P, kind, k)
+    cur, A, gc, D, gp, W = robust_blocks(pb, Rs, ts, P, kind, k, full)
     guess, lam, it, rejected = cur, lm["lambda_initial"], 0, 0
     while it < lm["max_iterations"]:
         it += 1
@@ -213,7 +233,7 @@ def solve_irls(pb, kind=NONE, k=1.0, lm=None):
             Rn = np.stack([Rs[f] @ Rot.from_rotvec(dc[f, :3]).as_matrix() for f in range(F)])
             tn = np.stack([ts[f] + Rs[f] @ dc[f, 3:] for f in range(F)])
             Pn = P + dp
-            new = robust_blocks(pb, Rn, tn, Pn, kind, k)
+            new = robust_blocks(pb, Rn, tn, Pn, kind, k, full)
             cand = new[0]
         except np.linalg.LinAlgError:   # a failed solve: lambda grows (bas_solve counts it in failed_solves)
             cand = np.inf
@@ -239,13 +259,14 @@ def solve_irls(pb, kind=NONE, k=1.0, lm=None):
             if lam > lm["lambda_upper"]:
                 break
     out = dict(error=cur, error_guess=guess, R=Rs, t=ts, points=P, iterations=it, rejected_steps=rejected)
-    out["pose_cov"], out["point_cov"] = reweighted_cov(pb, out, kind, k)
+    out["pose_cov"], out["point_cov"] = reweighted_cov(pb, out, kind, k, full)
     return out
 
 
 # ---- (B) scipy on the rescaled residuals -------------------------------------------------------------------------------
-def solve_scipy(pb, kind=NONE, k=1.0):
+def solve_scipy(pb, kind=NONE, k=1.0, full=False):
     F, m = len(pb["poses"]), len(pb["Xg"])
+    Lo, Lp = tw.full_whiteners(pb) if full else (None, None)
     Rg, tg, _ = _guess(pb)
     wsd = [np.where(pb["var"][f] > 0, 1.0 / np.sqrt(np.where(pb["var"][f] > 0, pb["var"][f], 1.0)), 0.0) for f in range(F)]
     hp = pb["has_prior"].astype(float)
@@ -277,7 +298,7 @@ def solve_scipy(pb, kind=NONE, k=1.0):
                 J[row:row + 3, 6 * f:6 * f + 3] = np.diag(wsd[f][:3])
                 J[row + 3:row + 6, 6 * f + 3:6 * f + 6] = wsd[f][3:, None] * Rg[f].T
             row += 6
-            v, r, Jc, Jp = _obs_lin(pb, Rs, ts, P, f)
+            v, r, Jc, Jp = _obs_lin_full(pb, Rs, ts, P, f, Lo) if full else _obs_lin(pb, Rs, ts, P, f)
             g, c = rescale(r)
             res[row:row + 2 * len(v)] = (g[:, None] * r).ravel()
             if want_jac:
@@ -291,6 +312,13 @@ def solve_scipy(pb, kind=NONE, k=1.0):
                     J[row + 2 * a:row + 2 * a + 2, 6 * f:6 * f + 6] = Jcg[a]
                     J[row + 2 * a:row + 2 * a + 2, 6 * F + 3 * v[a]:6 * F + 3 * v[a] + 3] = Jpg[a]
             row += 2 * len(v)
+        if full:   # the point priors whitened as the observations are: L^T (P - Xg)
+            res[row:] = np.einsum("mji,mj->mi", Lp, P - pb["Xg"]).ravel()
+            if want_jac:
+                for i in range(m):
+                    J[row + 3 * i:row + 3 * i + 3, 6 * F + 3 * i:6 * F + 3 * i + 3] = Lp[i].T
+                return J
+            return res
         res[row:] = (((P - pb["Xg"]) / 1e-2) * hp[:, None]).ravel()
         if want_jac:
             J[row:, 6 * F:] = np.kron(np.diag(hp / 1e-2), np.eye(3))
@@ -301,7 +329,7 @@ def solve_scipy(pb, kind=NONE, k=1.0):
     sol = least_squares(fun, x0, jac=lambda x: fun(x, True), xtol=1e-15, ftol=1e-15, gtol=1e-15, method="trf", x_scale="jac")
     Rs, ts, P = unpack(sol.x)
     out = dict(error=0.5 * np.sum(sol.fun ** 2), error_guess=0.5 * np.sum(fun(x0) ** 2), R=Rs, t=ts, points=P.copy())
-    out["pose_cov"], out["point_cov"] = reweighted_cov(pb, out, kind, k)
+    out["pose_cov"], out["point_cov"] = reweighted_cov(pb, out, kind, k, full)
     return out
 
 
