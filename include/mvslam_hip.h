@@ -53,6 +53,8 @@ extern "C" {
 /* still 4: mvs_seq_loop_scores, mvs_seq_download_loop_scores, mvs_loop_select_params, mvs_loop_candidate, mvs_seq_select_loops,
  * mvs_seq_verify_loops, mvs_loop_edge_params, mvs_seq_add_loop_edges and mvs_seq_download_loop_candidates are additions (new
  * symbols only): loop closures of a resident sequence */
+/* still 4: mvs_seq_scale_params, mvs_seq_scale_step, mvs_seq_rescale and mvs_seq_download_scale_steps are additions (new
+ * symbols only): the scale of a resident sequence from depth ratios of shared points */
 #define MVS_ABI_VERSION 4
 
 typedef enum mvs_status {
@@ -998,6 +1000,39 @@ mvs_status mvs_seq_upload_images(mvs_seq *s, int first, int count, const uint8_t
  *   R / t          = pose of frame k in frame 0: G_0 = I, G_1 = pair 0, G_{q+2} = G_q o (R_track_q, pair_scale[q] t_track_q)
  * (a failed track keeps the scale and falls back to the two-view pose of pair q+1).  Any pointer may be NULL. */
 mvs_status mvs_seq_download_trajectory(mvs_seq *s, double *R, double *t, double *pair_scale, double *track_scale);
+
+/* The scale of a sequence that has been run, again, by another rule.  mvs_seq_run keeps the rule
+ * above; mvs_seq_rescale overwrites the resident R / t / pair_scale / track_scale, which mvs_seq_download_trajectory then
+ * returns, and retires what was derived from the old trajectory as a new run does: window results, the pose graph and its
+ * optimised nodes, the global problem.  Pairs, tracks, refined pairs, lags, tracking and odometry stay valid.
+ *   MVS_SEQ_SCALE_CHAIN        the fold of mvs_seq_run again: the bytes it left; the step records are zero.
+ *   MVS_SEQ_SCALE_DEPTH_RATIO  step q = 0 .. n_frames - 3, from pairs q and q + 1.  Point j of a valid pair k: match row
+ *     point_idx[k][j], base keypoint a = trainIdx, new keypoint b = queryIdx, position x in frame k's camera (a row or a
+ *     keypoint outside the frame arrays: no point).  Keypoint c of frame q + 1 is SHARED when a point j of pair q has b = c
+ *     and a point j' of pair q + 1 has a = c; of several j' with a = c the smallest counts.  Shared points in ascending j';
+ *     with (R, t) of pair q and d = x_j - t:   z_a = (R[0][2] d0 + R[1][2] d1) + R[2][2] d2,   z_b = x_j'[2];
+ *     the point is USED when both are finite and > 0, and then rho = z_a / z_b.  n_common / n_used count the shared / used
+ *     points; scale = the lower median of the used rho (element (n_used - 1) / 2 in ascending order).  flag 1: pair q or
+ *     q + 1 is invalid (no points: both counts 0); flag 2: n_used < min_common; both: scale = 1.  flag 0 otherwise.
+ *     track_scale[q] = scale_q;  pair_scale[0] = 1, pair_scale[q+1] = pair_scale[q] * scale_q, in this order;
+ *     G_0 = I, G_{k+1} = G_k o (R_k, pair_scale[k] t_k) from the pairs alone (an invalid pair: the identity; the PnP tracks
+ *     are not read), composed as above: s = pair_scale[k] t_k first, then (A0 c0 + A1 c1) + A2 c2 (+ A.t).
+ * Binary64, + - * / with one rounding each, no atomics on values: the same pairs give the same bytes.
+ * Asynchronous on the ctx stream.  MVS_ERR_INVALID_ARG, nothing touched: a null pointer, a sequence that has not been run, a
+ * rule that is neither of the two, min_common < 1. */
+#define MVS_SEQ_SCALE_CHAIN 0
+#define MVS_SEQ_SCALE_DEPTH_RATIO 1
+typedef struct mvs_seq_scale_params {
+    int32_t rule;        /* MVS_SEQ_SCALE_CHAIN, MVS_SEQ_SCALE_DEPTH_RATIO */
+    int32_t min_common;  /* >= 1; below it a step keeps the scale */
+} mvs_seq_scale_params;
+typedef struct mvs_seq_scale_step {
+    int32_t n_common, n_used, flag, reserved;
+    double scale;
+} mvs_seq_scale_step;
+mvs_status mvs_seq_rescale(mvs_seq *s, const mvs_seq_scale_params *p);
+/* steps[n_frames - 2] of the last mvs_seq_rescale on the current run; waits for the ctx stream.  MVS_ERR_INVALID_ARG before it. */
+mvs_status mvs_seq_download_scale_steps(mvs_seq *s, mvs_seq_scale_step *steps);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * The back end: pose graphs.  Replaces Graph / GraphOptimizer of back-end/graph.{hpp,cpp}, i.e. GTSAM's

@@ -134,6 +134,15 @@ class SeqGlobalParams(C.Structure):
     _fields_ = [("max_track_frames", C.c_int32), ("reserved", C.c_int32), ("sigma_px", C.c_double)]
 
 
+class SeqScaleParams(C.Structure):
+    """mvs_seq_scale_params: rule SEQ_SCALE_CHAIN / SEQ_SCALE_DEPTH_RATIO; min_common >= 1"""
+    _fields_ = [("rule", C.c_int32), ("min_common", C.c_int32)]
+
+
+SEQ_SCALE_CHAIN, SEQ_SCALE_DEPTH_RATIO = 0, 1
+SCALE_STEP_DTYPE = np.dtype([("n_common", "<i4"), ("n_used", "<i4"), ("flag", "<i4"), ("reserved", "<i4"), ("scale", "<f8")])
+
+
 class VoParams(C.Structure):
     """mvs_vo_params: the tracking loop of Sequence.track"""
     _fields_ = [("init_pair", C.c_int32), ("use_refined_init", C.c_int32), ("min_pnp_point_count", C.c_int32),
@@ -290,6 +299,7 @@ EXPORTS = [
     "mvs_ctx_set_pose_graph_loss", "mvs_pose_graph_edge_stats", "mvs_seq_pose_graph_edge_stats",
     "mvs_ctx_set_ba_loss", "mvs_ba_sparse_obs_stats", "mvs_seq_global_obs_stats",
     "mvs_seq_refine_global", "mvs_seq_global_counts", "mvs_seq_download_global", "mvs_seq_download_global_problem",
+    "mvs_seq_rescale", "mvs_seq_download_scale_steps",
 ]
 
 
@@ -367,6 +377,8 @@ def lib():
         _lib.mvs_seq_global_counts.argtypes = [C.c_void_p] * 3
         _lib.mvs_seq_download_global.argtypes = [C.c_void_p] * 5
         _lib.mvs_seq_download_global_problem.argtypes = [C.c_void_p] * 8
+        _lib.mvs_seq_rescale.argtypes = [C.c_void_p] * 2
+        _lib.mvs_seq_download_scale_steps.argtypes = [C.c_void_p] * 2
         _lib.mvs_ctx_set_ba_loss.restype = C.c_int
         _lib.mvs_ctx_set_ba_loss.argtypes = [C.c_void_p, C.c_int, C.c_double]
         _lib.mvs_ba_sparse_obs_stats.restype = C.c_int
@@ -1394,6 +1406,21 @@ class Sequence:
                                                _ptr(ts, C.c_double))
         self.ctx._check(st, "mvs_seq_download_trajectory")
         return dict(R=R, t=t, pair_scale=ps, track_scale=ts)
+
+    def rescale(self, rule=SEQ_SCALE_DEPTH_RATIO, min_common=1):
+        """the resident trajectory and scales of the last run again, by `rule` (mvs_seq_rescale; asynchronous):
+        SEQ_SCALE_DEPTH_RATIO takes every step's scale from the depth ratios of the points two consecutive pairs share (a
+        step with fewer than min_common of them keeps the scale), SEQ_SCALE_CHAIN restores what run() left.  Windows, the pose
+        graph and the global problem of the old trajectory are retired."""
+        sp = SeqScaleParams(int(rule), int(min_common))
+        self.ctx._check(lib().mvs_seq_rescale(self._h, C.byref(sp)), "mvs_seq_rescale")
+
+    def download_scale_steps(self):
+        """the n_frames - 2 step records of the last rescale() (SCALE_STEP_DTYPE: n_common, n_used, flag, scale)"""
+        steps = np.zeros(self.n_frames - 2, dtype=SCALE_STEP_DTYPE)
+        st = lib().mvs_seq_download_scale_steps(self._h, steps.ctypes.data_as(C.c_void_p))
+        self.ctx._check(st, "mvs_seq_download_scale_steps")
+        return steps
 
     def upload_octaves(self, first, octave):
         octave = np.ascontiguousarray(octave, dtype=np.uint8)

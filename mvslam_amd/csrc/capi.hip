@@ -1919,6 +1919,7 @@ mvs_status mvs_seq_create(mvs_ctx *ctx, int n_frames, int max_kp, int desc_bytes
     int64_t *gidx = nullptr;
     PnpOut *po = nullptr;
     double *traj_R = nullptr, *traj_t = nullptr, *traj_s = nullptr, *trk_s = nullptr;   // scale-propagation fold outputs
+    mvs_seq_scale_step *steps = nullptr;
     DevGroup grp(ctx, q->blocks);
     grp.add(X, T * S * 3);
     grp.add(uv, T * S * 2);
@@ -1934,6 +1935,7 @@ mvs_status mvs_seq_create(mvs_ctx *ctx, int n_frames, int max_kp, int desc_bytes
     grp.add(traj_t, (size_t)n_frames * 3);
     grp.add(traj_s, (size_t)n_frames);
     grp.add(trk_s, (size_t)n_frames);
+    grp.add(steps, T);
     if ((st = grp.commit()) != MVS_OK) {
         mvs_seq_destroy(q);
         return st;
@@ -1985,6 +1987,7 @@ mvs_status mvs_seq_create(mvs_ctx *ctx, int n_frames, int max_kp, int desc_bytes
     q->chain.traj_t = traj_t;
     q->chain.traj_sigma = traj_s;
     q->chain.track_scale = trk_s;
+    q->scale_steps = steps;
     q->pnp.rec = nullptr;
     q->pnp.max_groups = 0;
     *out = q;
@@ -2112,6 +2115,7 @@ static mvs_status seq_enqueue(mvs_seq *q, Estimator est, const RunParams &rp, hi
     q->odo_ran = false;
     q->graph_built = q->graph_opt = false;   // nor is a pose graph
     q->glob_counted = q->glob_built = q->glob_solved = q->glob_cov = false;   // nor is a global problem
+    q->rescaled = false;     // nor are the step records of a rescale
     return MVS_OK;
 }
 
@@ -2837,6 +2841,55 @@ mvs_status mvs_seq_download_trajectory(mvs_seq *q, double *R, double *t, double 
         HIP_TRY(ctx, hipMemcpyAsync(pair_scale, q->chain.traj_sigma, (F - 1) * sizeof(double), hipMemcpyDeviceToHost, s));
     if (track_scale)
         HIP_TRY(ctx, hipMemcpyAsync(track_scale, q->chain.track_scale, (F - 2) * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, sync_stream(ctx));
+    return MVS_OK;
+}
+
+// The trajectory of the last run by another rule, over the chain's outputs.  What read the old trajectory is retired as
+// seq_enqueue retires it; what does not read it (pairs, tracks, refined pairs, lags, tracking, odometry) stays.
+mvs_status mvs_seq_rescale(mvs_seq *q, const mvs_seq_scale_params *p)
+{
+    if (!q || !p || !q->ran || (p->rule != MVS_SEQ_SCALE_CHAIN && p->rule != MVS_SEQ_SCALE_DEPTH_RATIO) || p->min_common < 1)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx_stream(ctx);
+    if (p->rule == MVS_SEQ_SCALE_CHAIN) {
+        HIP_TRY(ctx, hipMemsetAsync(q->scale_steps, 0, (size_t)q->n_tracks * sizeof(mvs_seq_scale_step), s));
+        launch_seq_chain(q->chain, s);
+    } else {
+        const BatchDev &bd = q->batch->d;
+        SeqScaleDev d{};
+        d.n_frames = q->n_frames;
+        d.max_kp = bd.max_kp;
+        d.min_common = p->min_common;
+        d.results = bd.results;
+        d.matches = bd.matches;
+        d.point_idx = bd.point_idx;
+        d.points = bd.points;
+        d.steps = q->scale_steps;
+        d.traj_R = q->chain.traj_R;
+        d.traj_t = q->chain.traj_t;
+        d.traj_sigma = q->chain.traj_sigma;
+        d.track_scale = q->chain.track_scale;
+        launch_seq_rescale(d, s);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    q->rescaled = true;
+    q->wd.n_windows = 0;                                                       // windows of the old trajectory
+    q->graph_built = q->graph_opt = false;                                     // its pose graph
+    q->glob_counted = q->glob_built = q->glob_solved = q->glob_cov = false;    // its global problem
+    return MVS_OK;
+}
+
+mvs_status mvs_seq_download_scale_steps(mvs_seq *q, mvs_seq_scale_step *steps)
+{
+    if (!q || !steps || !q->rescaled)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(steps, q->scale_steps, (size_t)q->n_tracks * sizeof(mvs_seq_scale_step), hipMemcpyDeviceToHost,
+                                ctx_stream(ctx)));
     HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }

@@ -139,6 +139,9 @@ struct mvs_seq {
     bool refit_on = false;
     DevBlocks blocks;
     bool ran = false;           // mvs_seq_run has filled the pairs, the tracks and the trajectory
+    // mvs_seq_rescale: the step records [n_tracks], resident until the next run
+    mvs_seq_scale_step *scale_steps = nullptr;
+    bool rescaled = false;      // the records are those of a rescale of the last run
     // mvs_seq_refine_windows: link tables, the windows' problems and their results, resident until the next call
     DevWorkspace win;
     SeqWinDev wd{};             // n_windows = 0 until the first call

@@ -203,6 +203,21 @@ struct SeqChainDev {
 };
 void launch_seq_chain(const SeqChainDev &c, hipStream_t stream);
 
+// mvs_seq_rescale, MVS_SEQ_SCALE_DEPTH_RATIO: the scale steps from depth ratios of the points consecutive pairs share, then
+// sigma and the trajectory from the pairs alone, over SeqChainDev's outputs (pnp.hip)
+struct SeqScaleDev {
+    int n_frames;
+    int max_kp;
+    int min_common;                  // fewer used points: the step keeps the scale
+    const mvs_pair_result *results;  // [n_frames - 1]
+    const mvs_match *matches;        // [n_frames - 1][max_kp]
+    const int32_t *point_idx;        // [n_frames - 1][max_kp]
+    const double *points;            // [n_frames - 1][max_kp][3]
+    mvs_seq_scale_step *steps;       // [n_frames - 2]
+    double *traj_R, *traj_t, *traj_sigma, *track_scale;   // SeqChainDev's
+};
+void launch_seq_rescale(const SeqScaleDev &d, hipStream_t stream);
+
 // ---- sfm_refine / pnp_refine (row f4): batched Schur-complement Levenberg-Marquardt ---------------------------
 struct RefineCfg {
     int max_iterations;

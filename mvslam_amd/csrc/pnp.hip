@@ -1503,4 +1503,208 @@ void launch_seq_chain(const SeqChainDev &c, hipStream_t stream)
     hipLaunchKernelGGL(seq_chain_kernel, dim3(1), dim3(256), 0, stream, c);
 }
 
+// ---- the scale of a sequence from depth ratios of shared points (mvs_seq_rescale) ---------------
+// Step q, pairs q and q + 1.  Keypoint c of frame q + 1 is shared when it is the new keypoint of a point j of pair q and the
+// base keypoint of a point j' of pair q + 1 (the smallest j' per keypoint: seq_link_kernel's rule).  Both pairs know the depth
+// of that point in frame q + 1, each in its own unit baseline, so
+//   rho = z_a / z_b = baseline(pair q+1) / baseline(pair q),   z_a = (R_q^T (x_j - t_q))[2],   z_b = x_j'[2]
+// and scale_q = the lower median of rho over the shared points with two finite positive depths.  The operations and their
+// order are the header's (tests/seq_rescale_model.py restates them): + - * /, one rounding each.
+//
+// grid n_frames - 2, block 256.  Pass 1: s_at[c] = point of pair q at keypoint c (b is unique per match row: plain stores of
+// distinct addresses).  Pass 2: s_first[c] = smallest point of pair q + 1 with base keypoint c (an integer minimum does not
+// depend on the order of arrival).  Pass 3 walks pair q + 1's points in ascending order in chunks of 256 and compacts the
+// ratios of the used points into LDS by ballot (seq_join_kernel's scan); a bitonic sort of the list padded with +inf to a
+// power of two (seq_glob_sort_kernel's network) puts the lower median at (n_used - 1) / 2.  Equal ratios are equal bit
+// patterns, so the result does not depend on how the network orders them.  Every index read from a table is range-checked.
+__global__ __launch_bounds__(256) void seq_ratio_kernel(SeqScaleDev d)
+{
+    __shared__ double s_rho[kMaxKp];
+    __shared__ int s_first[kMaxKp];
+    __shared__ int16_t s_at[kMaxKp];
+    __shared__ int s_tot[4], s_tot2[4];
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, N = d.max_kp;
+    const mvs_pair_result &pq = d.results[q], &pn = d.results[q + 1];
+    const bool valid = pq.valid != 0 && pn.valid != 0;
+    const int nq = valid ? min(max(pq.n_points, 0), N) : 0, nn = valid ? min(max(pn.n_points, 0), N) : 0;
+    const size_t oq = (size_t)q * N, on = oq + N;
+    // point j of the pair at offset o: base keypoint a, new keypoint b
+    auto point = [&](size_t o, int j, int &a, int &b) {
+        const int r = d.point_idx[o + j];
+        if ((unsigned)r >= (unsigned)N)
+            return false;
+        const mvs_match mt = d.matches[o + r];
+        a = mt.trainIdx;
+        b = mt.queryIdx;
+        return (unsigned)a < (unsigned)N && (unsigned)b < (unsigned)N;
+    };
+    for (int i = tid; i < N; i += 256) {
+        s_at[i] = -1;
+        s_first[i] = INT_MAX;
+    }
+    __syncthreads();
+    for (int j = tid; j < nq; j += 256) {
+        int a, b;
+        if (point(oq, j, a, b))
+            s_at[b] = (int16_t)j;
+    }
+    for (int j = tid; j < nn; j += 256) {
+        int a, b;
+        if (point(on, j, a, b))
+            atomicMin(&s_first[a], j);
+    }
+    __syncthreads();
+    const double R02 = pq.R[2], R12 = pq.R[5], R22 = pq.R[8], t0 = pq.t[0], t1 = pq.t[1], t2 = pq.t[2];
+    int n_common = 0, n_used = 0;
+    for (int start = 0; start < nn; start += 256) {
+        const int jn = start + tid;
+        bool shared = false, used = false;
+        double rho = 0.0;
+        if (jn < nn) {
+            int a, b;
+            if (point(on, jn, a, b) && s_first[a] == jn && s_at[a] >= 0) {
+                shared = true;
+                const double *x = d.points + 3 * (oq + (size_t)s_at[a]);
+                const double d0 = x[0] - t0, d1 = x[1] - t1, d2 = x[2] - t2;
+                const double za = (R02 * d0 + R12 * d1) + R22 * d2;
+                const double zb = d.points[3 * (on + (size_t)jn) + 2];
+                used = za > 0.0 && za < HUGE_VAL && zb > 0.0 && zb < HUGE_VAL;   // finite and positive (a NaN fails both)
+                if (used)
+                    rho = za / zb;
+            }
+        }
+        const unsigned long long bs = __ballot(shared), bu = __ballot(used);
+        const int pre = __popcll(bu & ((1ull << lane) - 1ull));
+        if (lane == 0) {
+            s_tot[w] = __popcll(bu);
+            s_tot2[w] = __popcll(bs);
+        }
+        __syncthreads();
+        int off = n_used;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int v = s_tot[k];
+            off += (k < w) ? v : 0;
+            n_used += v;
+            n_common += s_tot2[k];
+        }
+        if (used)
+            s_rho[off + pre] = rho;   // off + pre < nn <= N: one slot per point of pair q + 1 at the most
+        __syncthreads();
+    }
+    int n2 = 2;
+    while (n2 < n_used)
+        n2 <<= 1;
+    for (int k = n_used + tid; k < n2; k += 256)
+        s_rho[k] = HUGE_VAL;
+    for (int size = 2; size <= n2; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            __syncthreads();
+            for (int k = tid; k < (n2 >> 1); k += 256) {
+                const int lo = 2 * k - (k & (stride - 1)), hi = lo + stride;
+                const bool up = (lo & size) == 0;
+                const double a = s_rho[lo], b = s_rho[hi];
+                if ((a > b) == up) {
+                    s_rho[lo] = b;
+                    s_rho[hi] = a;
+                }
+            }
+        }
+    __syncthreads();
+    if (tid == 0) {
+        const int flag = !valid ? 1 : (n_used < d.min_common ? 2 : 0);
+        const double scale = flag == 0 ? s_rho[(n_used - 1) >> 1] : 1.0;
+        mvs_seq_scale_step st;
+        st.n_common = n_common;
+        st.n_used = n_used;
+        st.flag = flag;
+        st.reserved = 0;
+        st.scale = scale;
+        d.steps[q] = st;
+        d.track_scale[q] = scale;
+    }
+}
+
+// grid 1, block 256.  sigma_0 = 1, sigma_{q+1} = sigma_q * scale_q: a sequential product (its order is the contract), by one
+// thread per chunk.  G_0 = I, G_{k+1} = G_k o (R_k, sigma_k t_k) from the pairs alone (an invalid pair is the identity), in
+// seq_chain_kernel's compose order.  Per chunk of kChunk steps the workgroup loads the operands into LDS, thread 0 extends the
+// product, the workgroup scales the translations, and the sixteen fold lanes of seq_chain_kernel (quad i = row i of the running
+// rotation and t_i; the factors are quad broadcasts) walk the chunk; the running pose stays in their registers across chunks.
+__global__ __launch_bounds__(256) void seq_sigma_fold_kernel(SeqScaleDev d)
+{
+    constexpr int kChunk = 128;
+    __shared__ double s_op[kChunk * 12];    // R_k (9), sigma_k t_k (3)
+    __shared__ double s_sig[kChunk];        // in: scale_{k-1}; out: sigma_k
+    __shared__ double s_out[kChunk * 12];   // G_{k+1}
+    const int F = d.n_frames, tid = threadIdx.x, P = F - 1;
+    if (tid < 12) {
+        const double v = (tid < 9 && tid % 4 == 0) ? 1.0 : 0.0;   // G_0 = I
+        if (tid < 9)
+            d.traj_R[tid] = v;
+        else
+            d.traj_t[tid - 9] = v;
+    }
+    // fold lanes: tid = 4 i + j; j < 3: element (i, j) of the rotation, j = 3: t_i; quad 3 idles (its results are not stored)
+    const int fi = min(tid >> 2, 2), fj = tid & 3;
+    const bool fold_lane = tid < 12, is_t = fj == 3;
+    const int elem = is_t ? 9 + fi : 3 * fi + fj;
+    const int o0 = is_t ? 9 : fj, o1 = is_t ? 10 : 3 + fj, o2 = is_t ? 11 : 6 + fj;
+    double g = (!is_t && fi == fj) ? 1.0 : 0.0;   // this lane's element of G_k
+    double sigma = 1.0;                           // thread 0: sigma_k
+    for (int k0 = 0; k0 < P; k0 += kChunk) {
+        const int n = min(kChunk, P - k0);
+        __syncthreads();
+        for (int i = tid; i < n * 12; i += 256) {
+            const int j = i / 12, e = i - 12 * j;
+            const mvs_pair_result &p = d.results[k0 + j];
+            s_op[i] = p.valid ? (e < 9 ? p.R[e] : p.t[e - 9]) : ((e < 9 && e % 4 == 0) ? 1.0 : 0.0);
+        }
+        for (int j = tid; j < n; j += 256)
+            s_sig[j] = k0 + j > 0 ? d.track_scale[k0 + j - 1] : 1.0;
+        __syncthreads();
+        if (tid == 0)
+            for (int j = 0; j < n; ++j) {
+                if (k0 + j > 0)
+                    sigma = sigma * s_sig[j];
+                s_sig[j] = sigma;
+            }
+        __syncthreads();
+        for (int i = tid; i < n * 3; i += 256) {
+            const int j = i / 3, e = i - 3 * j;
+            s_op[12 * j + 9 + e] = s_sig[j] * s_op[12 * j + 9 + e];
+        }
+        __syncthreads();
+        if (tid < 64) {   // the whole first wavefront walks the loop (the DPP moves need their source lanes active)
+            double c0 = s_op[o0], c1 = s_op[o1], c2 = s_op[o2];
+            for (int j = 0; j < n; ++j) {
+                const int jn = min(j + 1, n - 1);
+                const double n0 = s_op[12 * jn + o0], n1 = s_op[12 * jn + o1], n2 = s_op[12 * jn + o2];
+                const double a0 = quad_bcast<0>(g), a1 = quad_bcast<1>(g), a2 = quad_bcast<2>(g);
+                const double r = (a0 * c0 + a1 * c1) + a2 * c2;
+                g = is_t ? r + g : r;   // ... + A.t_i on the translation lanes
+                if (fold_lane)
+                    s_out[12 * j + elem] = g;
+                c0 = n0; c1 = n1; c2 = n2;
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < n * 12; i += 256) {
+            const int j = i / 12, e = i - 12 * j, k = k0 + j;
+            if (e < 9)
+                d.traj_R[9 * (size_t)(k + 1) + e] = s_out[i];
+            else
+                d.traj_t[3 * (size_t)(k + 1) + (e - 9)] = s_out[i];
+        }
+        for (int j = tid; j < n; j += 256)
+            d.traj_sigma[k0 + j] = s_sig[j];
+    }
+}
+
+void launch_seq_rescale(const SeqScaleDev &d, hipStream_t stream)
+{
+    if (d.n_frames > 2)
+        hipLaunchKernelGGL(seq_ratio_kernel, dim3(d.n_frames - 2), dim3(256), 0, stream, d);
+    hipLaunchKernelGGL(seq_sigma_fold_kernel, dim3(1), dim3(256), 0, stream, d);
+}
+
 }  // namespace mvs
