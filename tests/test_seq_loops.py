@@ -159,15 +159,7 @@ def test_gpu_selection_equals_the_model(ctx):
         table = s.download_loop_scores()
         assert np.array_equal(table, lm.scores(desc, counts, 0.7, 64.0, 1))
         assert all(table[1, j] == table[2, j] for j in range(3, F)) and table[1, 5] > 0, "no ties in the table"
-        for min_score, top_k, cap in ((1, 3, 1000), (14, 2, 1000), (1, 3, 11), (20, 20, 5), (1000, 2, 4)):
-            s.select_loops(min_score, top_k, cap)
-            got = s.download_loop_candidates()
-            want, found = lm.select(table, min_score, top_k, cap)
-            print((min_score, top_k, cap), "kept", got["n_kept"], "found", got["n_found"])
-            assert got["n_found"] == found and got["n_kept"] == len(want)
-            assert [(int(c["i"]), int(c["j"]), int(c["score"])) for c in got["cand"]] == want
-            assert not got["cand"]["accepted"].any()
-            assert got["cand_all"][got["n_kept"]:].tobytes() == bytes(16 * (cap - got["n_kept"]))
+        check_selection_equals_the_model(s, table, ((1, 3, 1000), (14, 2, 1000), (1, 3, 11), (20, 20, 5), (1000, 2, 4)))
         _, found = lm.select(table, 1, 3, 11)
         assert found > 11, "the cut case cuts nothing"
         rows = lm.select(table, 14, 2, 1000)[0]
@@ -176,6 +168,20 @@ def test_gpu_selection_equals_the_model(ctx):
         assert any(c[0] == 1 for c in lm.select(table, 1, 3, 1000)[0]), "the tie is never selected"
     finally:
         s.close()
+
+
+def check_selection_equals_the_model(s, table, settings):
+    """mvs_seq_select_loops on the scored sequence `s` against the model on its downloaded table, for every
+    (min_score, top_k, max_candidates) of `settings`; the rows behind the kept candidates are zero"""
+    for min_score, top_k, cap in settings:
+        s.select_loops(min_score, top_k, cap)
+        got = s.download_loop_candidates()
+        want, found = lm.select(table, min_score, top_k, cap)
+        print((min_score, top_k, cap), "kept", got["n_kept"], "found", got["n_found"])
+        assert got["n_found"] == found and got["n_kept"] == len(want)
+        assert [(int(c["i"]), int(c["j"]), int(c["score"])) for c in got["cand"]] == want
+        assert not got["cand"]["accepted"].any()
+        assert got["cand_all"][got["n_kept"]:].tobytes() == bytes(16 * (cap - got["n_kept"]))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -231,9 +237,10 @@ def test_gpu_verification_equals_an_uploaded_batch(ctx, loop_seq, essential):
     check_verification_equals_an_uploaded_batch(ctx, s, data, essential)
 
 
-def check_verification_equals_an_uploaded_batch(ctx, s, data, essential, desc_bytes=32):
-    """the verification of the selected candidates of `s` (which holds `data` and st._octaves) against a batch of the same
-    (i, j) frames uploaded from the host: every byte of the pair results and of the refinement records"""
+def check_verification_equals_an_uploaded_batch(ctx, s, data, essential, desc_bytes=32, n_kp=N_KP):
+    """the verification of the selected candidates of `s` (which holds `data` and st._octaves at `n_kp` keypoints a frame)
+    against a batch of the same (i, j) frames uploaded from the host: every byte of the pair results and of the refinement
+    records"""
     from mvslam_amd import capi
 
     prm = _two_view()
@@ -241,9 +248,9 @@ def check_verification_equals_an_uploaded_batch(ctx, s, data, essential, desc_by
     got = s.download_loop_candidates(pairs=True)
     k = got["n_kept"]
     ci, cj = got["cand"]["i"], got["cand"]["j"]
-    b = capi.Batch(ctx, k, N_KP, desc_bytes)
+    b = capi.Batch(ctx, k, n_kp, desc_bytes)
     try:
-        oct_ = st._octaves(s.n_frames)
+        oct_ = st._octaves(s.n_frames, n_kp)
         b.upload(0, data["desc"][ci], data["kp"][ci], data["n_kp"][ci], data["desc"][cj], data["kp"][cj], data["n_kp"][cj],
                  np.tile(data["K"].reshape(1, 9), (k, 1)), np.arange(k, dtype=np.int64))
         b.upload_octaves(0, oct_[ci], oct_[cj])
@@ -262,24 +269,29 @@ def check_verification_equals_an_uploaded_batch(ctx, s, data, essential, desc_by
     assert np.array_equal(got["results"]["n_matches"], got["cand"]["score"]), "score != n_matches of the pair pipeline"
 
 
-def _built(s):
+def _built(s, n_frames=LOOP_FRAMES):
     s.build_pose_graph(2)
     g = s.download_pose_graph()
-    assert g["n_edges"] > LOOP_FRAMES - 1 and not (g["edge_kind"] == 2).any()
+    assert g["n_edges"] > n_frames - 1 and not (g["edge_kind"] == 2).any()
     return g
 
 
 @pytest.mark.gpu
 def test_gpu_loop_edges_equal_the_model_and_optimise(ctx, loop_seq):
+    s, _ = loop_seq
+    check_loop_edges_equal_the_model_and_optimise(ctx, s)
+
+
+def check_loop_edges_equal_the_model_and_optimise(ctx, s, n_frames=LOOP_FRAMES):
+    """`s`: a sequence of n_frames frames that is scored, selected, run and holds lags up to 2"""
     from mvslam_amd import capi
 
-    s, _ = loop_seq
     s.verify_loops(_two_view())
     cd = s.download_loop_candidates(pairs=True)
     cand = [(int(c["i"]), int(c["j"]), int(c["score"])) for c in cd["cand"]]
     recs = lm.records(cd["results"], cd["refined"])
     traj = s.download_trajectory()
-    built = _built(s)
+    built = _built(s, n_frames)
     last = None
     for kw in (dict(), dict(loop_sigma=(0.02, 0.2)), dict(loop_sigma=(0.0, 0.3), min_points=30), dict(loop_sigma=(0.02, 0.2))):
         s.add_loop_edges(**kw)      # every call after the first replaces the edges of the call before

@@ -167,14 +167,14 @@ def _far(value, gate):
     return not np.isfinite(gate) or abs(value - gate) >= 1e-6 * max(abs(value), abs(gate))
 
 
-def _replay(ctx, s, seq, vo, ip, pnp, refine):
+def _replay(ctx, s, seq, vo, ip, pnp, refine, n_frames=N_FRAMES, octaves=None):
     """the device's run against the definition: the integer side exact from the downloaded lag tables and the device's own
     step verdicts; every initialisation and every tracking step from the device's own previous state.  Returns
-    (snapshot, odo records)."""
+    (snapshot, odo records).  n_frames, octaves: of the sequence `s` holds (default: this file's, _octaves())."""
     Q = ip.frame_queue_size
-    _, tables, pairs = _lags(s, min(Q, N_FRAMES - 1))
+    _, tables, pairs = _lags(s, min(Q, n_frames - 1))
     snap, odo = st._snapshot(s), s.download_odometry_frames()
-    fr, K, kp, octv = snap["frames"], seq["K"], seq["kp"], _octaves()
+    fr, K, kp, octv = snap["frames"], seq["K"], seq["kp"], _octaves() if octaves is None else octaves
     gates = dict(min_inliers=ip.min_match_inlier_count, max_error=vo.max_error, max_rot=ip.max_rotation_magnitude,
                  max_tz=ip.max_translation_z)
     # no gate decides a case in the last place
@@ -185,7 +185,7 @@ def _replay(ctx, s, seq, vo, ip, pnp, refine):
                 assert _far(abs(e["t"][2]), gates["max_tz"])
     assert all(_far(float(r["error"]), vo.max_error) for r in fr if r["state"] in (TRACKED, LOST_ERROR))
     inits = []
-    states, recs, _ = om.odo_run(tables, N_FRAMES, Q, gates, lambda f: int(fr[f]["state"]), lambda f, b, lag: inits.append((f, b, lag)))
+    states, recs, _ = om.odo_run(tables, n_frames, Q, gates, lambda f: int(fr[f]["state"]), lambda f, b, lag: inits.append((f, b, lag)))
     print("states", fr["state"].tolist(), "segments", odo["segment"].tolist(), "inits", inits)
     assert fr["state"].tolist() == states
     for f, r in enumerate(recs):
@@ -197,7 +197,7 @@ def _replay(ctx, s, seq, vo, ip, pnp, refine):
     zero_step = lambda f: snap["steps"][f]["raw"] == bytes(len(snap["steps"][f]["raw"]))
     init_of = {f: (b, lag) for f, b, lag in inits}
     next_id = 0
-    for f in range(N_FRAMES):
+    for f in range(n_frames):
         rec, stp = fr[f], snap["steps"][f]
         if rec["state"] in (NOT_REACHED, INITIALIZING):
             want = np.zeros(1, fr.dtype)

@@ -249,8 +249,8 @@ def test_model_on_a_hand_written_pair_table():
 # ---------------------------------------------------------------------------------------------------------------------
 # GPU
 
-def _octaves(n_frames=N_FRAMES):
-    return (np.arange(n_frames * N_KP).reshape(n_frames, N_KP) % 3).astype(np.uint8)
+def _octaves(n_frames=N_FRAMES, n_kp=N_KP):
+    return (np.arange(n_frames * n_kp).reshape(n_frames, n_kp) % 3).astype(np.uint8)
 
 
 def _pnp_params(refit=0, seed=None):
