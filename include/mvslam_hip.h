@@ -1258,6 +1258,83 @@ mvs_status mvs_pose_graph_edge_stats(mvs_ctx *ctx, const mvs_pose_graph *graph, 
  * succeeded. */
 mvs_status mvs_seq_pose_graph_edge_stats(mvs_seq *s, double *chi2, double *weight);
 
+/* ---- Pose graphs over Sim(3) -----------------------------------------------------------------------
+ * The same graph with one more degree of freedom per node: every node carries a scale.  A monocular sequence fixes every edge's
+ * length from its (drifted) trajectory, so an SE(3) graph can bend a trajectory and cannot change the scale drift along it; with
+ * a scale per node, sequential edges say "my neighbour has my scale, to within sigma" and a loop's position constraint
+ * redistributes scale around the loop (Strasdat et al. 2010).  The reference has no counterpart; the contract is the library's
+ * own and tests/sim3graph_model.py restates it in numpy.
+ *   Node      X = (R, t, s), 13 doubles: R row-major (9), t (3), s > 0.  It maps local to world by x_w = s R x + t.
+ *   Relative  Xs^-1 Xd = (Rs^T Rd,  Rs^T (td - ts) / ss,  sd / ss).
+ *   Edge      k = (src, dst, Z = (Rz, tz, sz), S_k 7 x 7 row-major), tangent order (rotation, translation, log-scale).  With
+ *             q = Rs^T (td - ts) / ss:   e = ( Log(Rz^T Rs^T Rd),  Rz^T (q - tz),  log sd - log ss - log sz ).
+ *   Update    the right perturbation of Sim(3): R <- R Exp(dw), t <- t + s R dv, s <- s exp(ds).
+ *   Jacobians with E = Rz^T Rs^T Rd and Jr^-1 the inverse right Jacobian of SO(3) at e_w:
+ *               d e_w / d dw:  dst Jr^-1,        src -Jr^-1 (Rs^T Rd)^T
+ *               d e_t / d dv:  dst (sd / ss) E,  src -Rz^T
+ *               d e_t / d dw:  dst 0,            src Rz^T [q]x
+ *               d e_t / d ds:  dst 0,            src -Rz^T q
+ *               d e_s / d ds:  dst +1,           src -1
+ *             and zero everywhere else.  With every s = 1 and ds = 0 this is the SE(3) edge above, computed by the same
+ *             operations on the same operands in the same order.
+ *   Cost      1/2 [ |e_a|^2_Sa + sum_k |e_k|^2_Sk ].  The anchor is a 7-dimensional prior at the anchor node's initial value
+ *             X0: e_a = ( Log(R0^T R), R0^T (t - t0), log s - log s0 ), Sa = diag(sigma_rot^2 I3, sigma_trans^2 I3,
+ *             sigma_scale^2); its Jacobians are Jr^-1, s R0^T R and 1.
+ *   LM        the rule of mvs_pose_graph_optimize unchanged: lambda ADDED to the diagonal, the same acceptance and termination,
+ *             the LM fields of mvs_refine_params.
+ * Graphs of up to 16 nodes are solved by one workgroup with a dense Cholesky in LDS: 7 * 16 = 112 unknowns, a packed triangle
+ * of 112 * 113 / 2 = 6328 doubles = 50624 B, plus 4 * 112 doubles of solve vectors, 2 * 16 * 13 of node tables, 26 of the
+ * anchor's record and 4 reduction cells: 57776 B, 58032 B as compiled with its padding, of the 65536 B of static LDS and no
+ * scratch, so the boundary between the paths is the SE(3) solver's.  A linearised edge is 7 + 2 * 49 = 105 doubles in global memory; every entry of H is summed by one thread in edge
+ * order.  Graphs of 17 .. 4096 nodes and up to 65536 edges: linearise per edge, gather per node in edge order, a block-Jacobi
+ * (7 x 7) preconditioned conjugate gradient whose budget is enqueued behind a status word; cg_max_iterations = 0 means
+ * 7 n_nodes and cg_chunk_iterations has the meaning, and the "every byte equals chunk 0" property, it has above.  Binary64,
+ * explicit FMAs where the SE(3) solver has them, fixed summation orders, no floating-point atomics: the same input gives the
+ * same bytes, and a graph in a batch gets the bytes of the single call.
+ * mvs_ctx_set_pose_graph_solver and mvs_ctx_set_pose_graph_loss do NOT apply to the calls of this section: they always run the
+ * conjugate gradient with no loss.  (A direct solver, marginals and robust losses for 7-DoF graphs do not exist yet.) */
+typedef struct mvs_sim3_graph {            /* all host pointers */
+    int32_t n_nodes, n_edges;
+    const double *node_sim3;               /* n_nodes x 13: initial values, R row-major (9), t (3), s */
+    const int32_t *edge_src, *edge_dst;    /* n_edges */
+    const double *edge_sim3;               /* n_edges x 13: Z */
+    const double *edge_cov;                /* n_edges x 49: row-major 7 x 7, order (rotation, translation, log-scale) */
+    int32_t anchor_node;
+} mvs_sim3_graph;
+typedef struct mvs_sim3_graph_params {
+    mvs_refine_params lm;                  /* only the LM fields */
+    double anchor_sigma[3];                /* rotation, translation, log-scale: 1e-4 each */
+    double cg_rel_tol;                     /* 1e-10 */
+    int32_t cg_max_iterations;             /* 0 = 7 n_nodes */
+    int32_t cg_chunk_iterations;           /* as in mvs_pose_graph_params */
+} mvs_sim3_graph_params;
+void mvs_sim3_graph_params_default(mvs_sim3_graph_params *p);
+/* nodes_out: n_nodes x 13.  The refusals are those of mvs_pose_graph_optimize, code for code: MVS_ERR_INVALID_ARG (null
+ * pointers, indices out of range, src == dst, non-finite input, a node or edge scale <= 0) and MVS_ERR_CAPACITY (more than
+ * 4096 nodes or 65536 edges) before anything runs; MVS_NO_MODEL with ok = 0, every other field of the result zero and nodes_out
+ * untouched for a covariance that fails the solver's 7 x 7 Cholesky test on its lower triangle (nothing is repaired), a node no
+ * path of edges joins to the anchor, or finite input whose cost at the initial values is not finite. */
+mvs_status mvs_sim3_graph_optimize(mvs_ctx *ctx, const mvs_sim3_graph *graph, const mvs_sim3_graph_params *params,
+                                   mvs_pose_graph_result *result, double *nodes_out);
+/* n_graphs graphs; graph i's nodes at nodes_out + i * 13 * (largest n_nodes of the batch), rows beyond its own node count are
+ * not written.  Graphs of up to 16 nodes share one launch, larger ones run one after another; every graph gets the bytes the
+ * single call returns for it.  MVS_NO_MODEL if some graph failed (results[i].ok tells which). */
+mvs_status mvs_sim3_graph_optimize_batch(mvs_ctx *ctx, const mvs_sim3_graph *graphs, int n_graphs,
+                                         const mvs_sim3_graph_params *params, mvs_pose_graph_result *results,
+                                         double *nodes_out);
+/* The resident graph of a sequence (mvs_seq_build_pose_graph, with the loop edges of mvs_seq_add_loop_edges when present)
+ * lifted to Sim(3) on the device and optimised there through device pointers: node k becomes (G_k, 1), edge e becomes
+ * Z = (Rz, tz, 1) with S7 = blockdiag(S'_6, scale_sigma[kind_e] * scale_sigma[kind_e]) and zero cross terms, kind 0 measured,
+ * 1 fallback, 2 loop.  The lift is copies and that one multiply: result and nodes are, byte for byte, those of
+ * mvs_sim3_graph_optimize on the lifted downloaded graph with anchor_node 0.  The SE(3) optimised nodes and everything else of
+ * the graph stay as they are.  Waits for the ctx stream.  MVS_ERR_INVALID_ARG before mvs_seq_build_pose_graph, for parameters
+ * mvs_sim3_graph_optimize refuses, or for a scale_sigma that is not finite and > 0; MVS_NO_MODEL as there. */
+mvs_status mvs_seq_optimize_pose_graph_sim3(mvs_seq *s, const mvs_sim3_graph_params *p, const double scale_sigma[3],
+                                            mvs_pose_graph_result *result);
+/* nodes13: n_frames x 13, the Sim(3) optimised nodes.  MVS_ERR_INVALID_ARG unless the last mvs_seq_optimize_pose_graph_sim3 on
+ * the current graph succeeded; whatever retires or changes the graph (a run, a rebuild, added loop edges) retires them. */
+mvs_status mvs_seq_download_pose_graph_sim3(mvs_seq *s, double *nodes13);
+
 /* ---- Loop closures of a resident sequence -------------------------------------------------------
  * Every edge of the graph above joins frames at most max_lag apart: it smooths a trajectory and cannot remove its drift.  These
  * calls find frames that see the same place again, verify the pairs with the two-view pipeline and the refinement, and append

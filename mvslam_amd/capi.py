@@ -185,6 +185,18 @@ class PoseGraphResult(C.Structure):
                 ("rejected_steps", C.c_int32), ("error_initial", C.c_double), ("error", C.c_double)]
 
 
+class Sim3Graph(C.Structure):
+    """mvs_sim3_graph: one pose graph over Sim(3), every pointer a host pointer"""
+    _fields_ = [("n_nodes", C.c_int32), ("n_edges", C.c_int32), ("node_sim3", C.POINTER(C.c_double)),
+                ("edge_src", C.POINTER(C.c_int32)), ("edge_dst", C.POINTER(C.c_int32)),
+                ("edge_sim3", C.POINTER(C.c_double)), ("edge_cov", C.POINTER(C.c_double)), ("anchor_node", C.c_int32)]
+
+
+class Sim3GraphParams(C.Structure):
+    _fields_ = [("lm", RefineParams), ("anchor_sigma", C.c_double * 3), ("cg_rel_tol", C.c_double),
+                ("cg_max_iterations", C.c_int32), ("cg_chunk_iterations", C.c_int32)]
+
+
 POSE_GRAPH_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("iterations", "<i4"), ("cg_iterations", "<i4"),
                                     ("rejected_steps", "<i4"), ("error_initial", "<f8"), ("error", "<f8")])
 assert POSE_GRAPH_RESULT_DTYPE.itemsize == C.sizeof(PoseGraphResult)
@@ -300,6 +312,8 @@ EXPORTS = [
     "mvs_ctx_set_ba_loss", "mvs_ba_sparse_obs_stats", "mvs_seq_global_obs_stats",
     "mvs_seq_refine_global", "mvs_seq_global_counts", "mvs_seq_download_global", "mvs_seq_download_global_problem",
     "mvs_seq_rescale", "mvs_seq_download_scale_steps",
+    "mvs_sim3_graph_params_default", "mvs_sim3_graph_optimize", "mvs_sim3_graph_optimize_batch",
+    "mvs_seq_optimize_pose_graph_sim3", "mvs_seq_download_pose_graph_sim3",
 ]
 
 
@@ -455,6 +469,20 @@ def default_pose_graph_params(**kw):
     for k, v in kw.items():
         if k == "anchor_sigma":
             p.anchor_sigma[0], p.anchor_sigma[1] = float(v[0]), float(v[1])
+        elif k in ("cg_rel_tol", "cg_max_iterations", "cg_chunk_iterations"):
+            setattr(p, k, v)
+        else:
+            setattr(p.lm, k, v)
+    return p
+
+
+def default_sim3_graph_params(**kw):
+    """mvs_sim3_graph_params_default; keywords name a field of the struct or an LM field of its `lm` member"""
+    p = Sim3GraphParams()
+    lib().mvs_sim3_graph_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k == "anchor_sigma":
+            p.anchor_sigma[0], p.anchor_sigma[1], p.anchor_sigma[2] = float(v[0]), float(v[1]), float(v[2])
         elif k in ("cg_rel_tol", "cg_max_iterations", "cg_chunk_iterations"):
             setattr(p, k, v)
         else:
@@ -688,6 +716,56 @@ class Context:
             poses_out = poses_out.reshape(1, -1, 12)
         st, res, poses = self._pose_graph_call([graph], params, poses_out, True)
         return st, res[0], poses[0]
+
+    def _sim3_graph_call(self, graphs, params, nodes_out, single):
+        """one graph through mvs_sim3_graph_optimize (`single`) or a list through mvs_sim3_graph_optimize_batch"""
+        params = params or default_sim3_graph_params()
+        G = len(graphs)
+        arr = (Sim3Graph * max(G, 1))()
+        keep = []
+        nmax = 0
+        for i, g in enumerate(graphs):
+            node = _f64(g["node_sim3"]).reshape(-1, 13)
+            src = np.ascontiguousarray(g["edge_src"], dtype=np.int32).reshape(-1)
+            dst = np.ascontiguousarray(g["edge_dst"], dtype=np.int32).reshape(-1)
+            ez = _f64(g["edge_sim3"]).reshape(-1, 13)
+            ec = _f64(g["edge_cov"]).reshape(-1, 49)
+            if not (len(src) == len(dst) == len(ez) == len(ec)):
+                raise ValueError("sim3 graph %d: the per-edge arrays differ in length" % i)
+            keep.append((node, src, dst, ez, ec))
+            arr[i].n_nodes, arr[i].n_edges = int(g.get("n_nodes", node.shape[0])), int(g.get("n_edges", len(src)))
+            arr[i].node_sim3 = _ptr(node, C.c_double)
+            arr[i].edge_src, arr[i].edge_dst = _ptr(src, C.c_int32), _ptr(dst, C.c_int32)
+            arr[i].edge_sim3, arr[i].edge_cov = _ptr(ez, C.c_double), _ptr(ec, C.c_double)
+            arr[i].anchor_node = int(g.get("anchor", 0))
+            nmax = max(nmax, node.shape[0])
+        if nodes_out is None:
+            nodes_out = np.zeros((G, nmax, 13))
+        assert nodes_out.dtype == np.float64 and nodes_out.flags.c_contiguous and nodes_out.shape == (G, nmax, 13)
+        res = np.zeros(G, dtype=POSE_GRAPH_RESULT_DTYPE)
+        if single:
+            st = lib().mvs_sim3_graph_optimize(self._h, arr, C.byref(params), res.ctypes.data_as(C.c_void_p),
+                                               _ptr(nodes_out, C.c_double))
+        else:
+            st = lib().mvs_sim3_graph_optimize_batch(self._h, arr, C.c_int(G), C.byref(params),
+                                                     res.ctypes.data_as(C.c_void_p), _ptr(nodes_out, C.c_double))
+        self._check(st, "mvs_sim3_graph_optimize", allow_no_model=True)
+        return st, res, nodes_out
+
+    def sim3_graph_optimize_batch(self, graphs, params=None, nodes_out=None):
+        """mvs_sim3_graph_optimize_batch.  graphs: dicts with node_sim3 (N x 13: R row-major, t, s), edge_src, edge_dst,
+        edge_sim3 (E x 13), edge_cov (E x 7 x 7) and anchor (default 0); n_nodes / n_edges, when present, override the counts
+        the arrays imply.  Returns (status, results[POSE_GRAPH_RESULT_DTYPE], nodes n_graphs x Nmax x 13); `nodes_out`
+        (that shape, float64, contiguous) is written in place when given, rows the library does not write keep their bytes.
+        Argument and capacity errors raise MvsError; MVS_NO_MODEL is returned."""
+        return self._sim3_graph_call(graphs, params, nodes_out, False)
+
+    def sim3_graph_optimize(self, graph, params=None, nodes_out=None):
+        """mvs_sim3_graph_optimize: (status, result record, nodes N x 13)"""
+        if nodes_out is not None:
+            nodes_out = nodes_out.reshape(1, -1, 13)
+        st, res, nodes = self._sim3_graph_call([graph], params, nodes_out, True)
+        return st, res[0], nodes[0]
 
     def pose_graph_marginals(self, graph, poses=None, queries=None, anchor_sigma=None, cov_out=None):
         """mvs_pose_graph_marginals: blocks of Sigma = H^-1 at `poses` (None: the graph's node_pose).  queries: pairs (i, j),
@@ -1652,6 +1730,24 @@ class Sequence:
         st = lib().mvs_seq_optimize_pose_graph(self._h, C.byref(params), res.ctypes.data_as(C.c_void_p))
         self.ctx._check(st, "mvs_seq_optimize_pose_graph", allow_no_model=True)
         return st, res[0]
+
+    def optimize_pose_graph_sim3(self, params=None, scale_sigma=(0.05, 0.05, 0.05)):
+        """mvs_seq_optimize_pose_graph_sim3: the resident graph lifted to Sim(3) -- scale_sigma: the log-scale standard deviation
+        of a measured, a fallback and a loop edge -- and optimised on the device; (status, result record);
+        download_pose_graph_sim3() fetches the nodes"""
+        params = params or default_sim3_graph_params()
+        sig = (C.c_double * 3)(float(scale_sigma[0]), float(scale_sigma[1]), float(scale_sigma[2]))
+        res = np.zeros(1, dtype=POSE_GRAPH_RESULT_DTYPE)
+        st = lib().mvs_seq_optimize_pose_graph_sim3(self._h, C.byref(params), sig, res.ctypes.data_as(C.c_void_p))
+        self.ctx._check(st, "mvs_seq_optimize_pose_graph_sim3", allow_no_model=True)
+        return st, res[0]
+
+    def download_pose_graph_sim3(self):
+        """the Sim(3) optimised nodes [n_frames, 13] of the last successful optimize_pose_graph_sim3()"""
+        nodes = np.zeros((self.n_frames, 13))
+        st = lib().mvs_seq_download_pose_graph_sim3(self._h, _ptr(nodes, C.c_double))
+        self.ctx._check(st, "mvs_seq_download_pose_graph_sim3")
+        return nodes
 
     def download_pose_graph(self):
         """the resident graph, cut to its edge count: node_pose [n_frames, 12], edge_src, edge_dst, edge_pose [E, 12],

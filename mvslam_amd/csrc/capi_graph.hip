@@ -1,5 +1,5 @@
 // capi_graph.hip -- host side of libmvslam_hip.so: the back end.  Pose graphs (posegraph.hip; the direct
-// LM step of pg_direct.hip, section 4.10.4), the
+// LM step of pg_direct.hip, section 4.10.4; the Sim(3) graphs of sim3graph.hip, section 4.10.6), the
 // graph of a resident sequence (seq_graph.hip), marginal covariances (pg_marginals.hip) and loop closures (loop.hip).  What it
 // decides about a graph without the device is in pg_host.hpp and pg_envelope.hpp.
 #include <algorithm>
@@ -679,7 +679,7 @@ mvs_status mvs_seq_build_pose_graph(mvs_seq *q, const mvs_seq_graph_params *p)
         return MVS_ERR_INVALID_ARG;
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    q->graph_built = q->graph_opt = false;
+    q->graph_built = q->graph_opt = q->graph_sim3 = false;
     const size_t S = (size_t)slots64;
     // room behind the slots for the loop edges of the current selection (mvs_seq_add_loop_edges grows the block otherwise)
     const size_t want = S + (q->loop_selected ? (size_t)q->ld.max_candidates : 0);
@@ -792,6 +792,441 @@ mvs_status mvs_seq_download_pose_graph_poses(mvs_seq *q, double *poses)
     mvs_ctx *ctx = q->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemcpyAsync(poses, q->graph_opt_pose, (size_t)q->n_frames * 96, hipMemcpyDeviceToHost, ctx_stream(ctx)));
+    HIP_TRY(ctx, sync_stream(ctx));
+    return MVS_OK;
+}
+
+// ---- pose graphs over Sim(3) (sim3graph.hip) -----------------------------------------------------
+// The SE(3) entries' host side with 13-double records and 49-double covariances; always the conjugate gradient with no loss.
+// The connectivity check and the CSR list are the SE(3) ones.
+
+void mvs_sim3_graph_params_default(mvs_sim3_graph_params *p)
+{
+    if (!p)
+        return;
+    mvs_refine_params_default(&p->lm);
+    p->anchor_sigma[0] = p->anchor_sigma[1] = p->anchor_sigma[2] = 1e-4;
+    p->cg_rel_tol = 1e-10;
+    p->cg_max_iterations = 0;                         // 7 n_nodes
+    p->cg_chunk_iterations = 0;                       // the whole budget at once
+}
+
+static S3Cfg to_s3_cfg(const mvs_sim3_graph_params &p)
+{
+    S3Cfg c{};
+    c.max_iterations = p.lm.max_iterations;
+    c.lambda_initial = p.lm.lambda_initial;
+    c.lambda_factor = p.lm.lambda_factor;
+    c.lambda_upper = p.lm.lambda_upper;
+    c.rel_tol = p.lm.rel_tol;
+    c.abs_tol = p.lm.abs_tol;
+    for (int k = 0; k < 3; ++k)
+        c.w_anchor[k] = 1.0 / (p.anchor_sigma[k] * p.anchor_sigma[k]);
+    c.cg_rel_tol = p.cg_rel_tol;
+    c.cg_max_iterations = p.cg_max_iterations;
+    return c;
+}
+
+static bool sim3_graph_params_ok(const mvs_sim3_graph_params *params)
+{
+    return params && params->lm.max_iterations >= 0 && params->lm.lambda_initial >= 0.0 && params->lm.lambda_factor > 1.0 &&
+           params->lm.lambda_upper > 0.0 && params->anchor_sigma[0] > 0.0 && params->anchor_sigma[1] > 0.0 &&
+           params->anchor_sigma[2] > 0.0 && params->cg_rel_tol >= 0.0 && params->cg_max_iterations >= 0;
+}
+
+// arguments of one graph: MVS_ERR_INVALID_ARG / MVS_ERR_CAPACITY before anything runs, in pose_graph_check's order
+static mvs_status sim3_graph_check(const mvs_sim3_graph &g)
+{
+    if (g.n_nodes < 1 || g.n_edges < 0 || !g.node_sim3)
+        return MVS_ERR_INVALID_ARG;
+    if (g.n_edges > 0 && (!g.edge_src || !g.edge_dst || !g.edge_sim3 || !g.edge_cov))
+        return MVS_ERR_INVALID_ARG;
+    if (g.n_nodes > kPgMaxNodes || g.n_edges > kPgMaxEdges)
+        return MVS_ERR_CAPACITY;
+    if (g.anchor_node < 0 || g.anchor_node >= g.n_nodes)
+        return MVS_ERR_INVALID_ARG;
+    if (!edges_in_range(g.n_nodes, g.n_edges, g.edge_src, g.edge_dst))
+        return MVS_ERR_INVALID_ARG;
+    if (!all_finite(g.node_sim3, kS3Node * (size_t)g.n_nodes) || !all_finite(g.edge_sim3, kS3Node * (size_t)g.n_edges) ||
+        !all_finite(g.edge_cov, kS3Cov * (size_t)g.n_edges))
+        return MVS_ERR_INVALID_ARG;
+    if (!sim3_scales_positive(g.node_sim3, (size_t)g.n_nodes) || !sim3_scales_positive(g.edge_sim3, (size_t)g.n_edges))
+        return MVS_ERR_INVALID_ARG;
+    return MVS_OK;
+}
+
+// scratch of the large path for N nodes and E edges, as offsets from one base
+struct S3LargeLayout {
+    size_t o_state, o_off, o_inc, o_pa, o_pb, o_W, o_lin, o_u, o_ec, o_D, o_Mf, o_vec[6], o_pq, o_Ha, total;
+    S3LargeLayout(size_t N, size_t E)
+    {
+        Carve L{64};
+        o_state = L.take(sizeof(PgState));
+        o_off = L.take((N + 1) * 4), o_inc = L.take(2 * E * 4);
+        o_pa = L.take(N * kS3Node * 8), o_pb = L.take(N * kS3Node * 8);
+        o_W = L.take(E * kS3W * 8), o_lin = L.take(E * kS3Lin * 8), o_u = L.take(E * 7 * 8), o_ec = L.take(E * 8);
+        o_D = L.take(N * kS3W * 8), o_Mf = L.take(N * kS3W * 8);
+        for (size_t &o : o_vec)
+            o = L.take(N * 7 * 8);
+        o_pq = L.take(N * 8), o_Ha = L.take(kS3Cov * 8);
+        total = L.total();
+    }
+};
+
+// one graph of 17 .. 4096 nodes: pose_graph_large_dev's LM loop on the host over the s3_* kernels.  h_src / h_dst: the edges
+// on the host; every d_* pointer is device memory that stays valid through the call; `base` is scratch of
+// S3LargeLayout(N, E).total bytes.  The optimised nodes go to nodes_out with a copy of kind `out_kind`, only when ok.
+static mvs_status sim3_graph_large_dev(mvs_ctx *ctx, char *base, int n_nodes, int n_edges, int anchor, const int32_t *h_src,
+                                       const int32_t *h_dst, const int32_t *d_src, const int32_t *d_dst, const double *d_node,
+                                       const double *d_z, const double *d_cov, const mvs_sim3_graph_params &params,
+                                       mvs_pose_graph_result *res, double *nodes_out, hipMemcpyKind out_kind)
+{
+    const size_t N = (size_t)n_nodes, E = (size_t)n_edges;
+    std::vector<int32_t> off, inc;
+    incidence_csr(n_nodes, n_edges, h_src, h_dst, off, inc);
+    const S3LargeLayout L(N, E);
+    hipStream_t s = ctx_stream(ctx);
+    HIP_TRY(ctx, hipMemsetAsync(base + L.o_state, 0, sizeof(PgState), s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + L.o_off, off.data(), (N + 1) * 4, hipMemcpyHostToDevice, s));
+    if (E)
+        HIP_TRY(ctx, hipMemcpyAsync(base + L.o_inc, inc.data(), 2 * E * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + L.o_pa, d_node, N * kS3Node * 8, hipMemcpyDeviceToDevice, s));
+    auto dp = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
+    auto ip = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o); };
+    S3LargeDev d{};
+    d.n_nodes = n_nodes, d.n_edges = n_edges, d.anchor = anchor;
+    d.cfg = to_s3_cfg(params);
+    d.edge_src = d_src, d.edge_dst = d_dst, d.csr_off = ip(L.o_off), d.csr_inc = ip(L.o_inc);
+    d.edge_z = d_z, d.edge_cov = d_cov, d.node0 = d_node;
+    d.node[0] = dp(L.o_pa), d.node[1] = dp(L.o_pb);
+    d.W = dp(L.o_W), d.lin = dp(L.o_lin), d.u = dp(L.o_u), d.ecost = dp(L.o_ec), d.D = dp(L.o_D), d.Mf = dp(L.o_Mf);
+    d.g = dp(L.o_vec[0]), d.x = dp(L.o_vec[1]), d.r = dp(L.o_vec[2]), d.z = dp(L.o_vec[3]), d.p = dp(L.o_vec[4]), d.q = dp(L.o_vec[5]);
+    d.pq = dp(L.o_pq), d.Ha = dp(L.o_Ha);
+    d.state = reinterpret_cast<PgState *>(base + L.o_state);
+    const int cg_max = params.cg_max_iterations > 0 ? params.cg_max_iterations : 7 * n_nodes;
+    const int chunk = params.cg_chunk_iterations;
+    PgState h{};
+    mvs_status st;
+    // the status word behind what has been launched so far: the one place this function waits for the device
+    auto read_state = [&]() -> mvs_status {
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(&h, d.state, sizeof(h), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, sync_stream(ctx));
+        return MVS_OK;
+    };
+    launch_s3_prep(d, s);
+    if ((st = read_state()) != MVS_OK)   // `off` and `inc` have been read by here, too
+        return st;
+    if (h.bad_cov) {
+        *res = mvs_pose_graph_result{};
+        return MVS_OK;
+    }
+    const S3Cfg &cfg = d.cfg;
+    int cb = 0, it = 0, rejected = 0, cg_total = 0;
+    double cur = 0.0, cost0 = 0.0, lam = cfg.lambda_initial;
+    bool ok0 = true, have0 = false;
+    // one iteration on the device and its status; the first one also gives the cost at the initial values
+    auto iterate = [&](bool with_cg) -> mvs_status {
+        launch_s3_begin(d, cb, lam, !have0, s);
+        if (with_cg && chunk <= 0) {
+            launch_s3_cg(d, lam, cg_max, s);
+        } else if (with_cg) {
+            // chunk by chunk: the iterations not enqueued are the ones the status word would have sent away at once
+            for (int left = cg_max; left > 0;) {
+                const int n = std::min(chunk, left);
+                launch_s3_cg(d, lam, n, s);
+                left -= n;
+                if (left > 0) {
+                    if ((st = read_state()) != MVS_OK)
+                        return st;
+                    if (h.done)
+                        break;
+                }
+            }
+        }
+        launch_s3_end(d, cb, s);
+        if ((st = read_state()) != MVS_OK)
+            return st;
+        if (!have0) {
+            have0 = true;
+            cost0 = cur = h.cost0;
+            ok0 = std::isfinite(cur);
+        }
+        return MVS_OK;
+    };
+    while (ok0 && it < cfg.max_iterations) {
+        if ((st = iterate(true)) != MVS_OK)
+            return st;
+        if (!ok0)
+            break;
+        cg_total += h.cg_iters;
+        // the linear solve counts as done when the CG converged, or ran out of iterations with a smaller residual
+        const bool solved = h.done == 1 || (h.done == 0 && h.rr < h.gnorm2);
+        const double cand = h.cand;
+        const bool accepted = solved && cand <= cur;
+        ++it;
+        if (accepted) {
+            cb ^= 1;
+            const double dec = 0.5 * (cur - cand);
+            const bool done = dec <= cfg.abs_tol || dec <= cfg.rel_tol * (0.5 * cur);
+            cur = cand;
+            lam = lam / cfg.lambda_factor;
+            if (done)
+                break;
+        } else {
+            ++rejected;
+            const double inc_e = 0.5 * (cand - cur);
+            if (solved && (inc_e <= cfg.abs_tol || inc_e <= cfg.rel_tol * (0.5 * cur)))
+                break;
+            lam = lam * cfg.lambda_factor;
+            if (lam > cfg.lambda_upper)
+                break;
+        }
+    }
+    // max_iterations = 0: the cost at the initial values alone (an iteration with no CG steps leaves x = 0)
+    if (!have0 && (st = iterate(false)) != MVS_OK)
+        return st;
+    res->ok = ok0 ? 1 : 0;
+    res->iterations = it;
+    res->cg_iterations = cg_total;
+    res->rejected_steps = rejected;
+    res->error_initial = ok0 ? 0.5 * cost0 : 0.0;
+    res->error = ok0 ? 0.5 * cur : 0.0;
+    if (ok0) {
+        HIP_TRY(ctx, hipMemcpyAsync(nodes_out, d.node[cb], N * kS3Node * 8, out_kind, s));
+        HIP_TRY(ctx, sync_stream(ctx));
+    }
+    return MVS_OK;
+}
+
+// scratch of a dense-path batch of G graphs with sumN nodes and sumE edges.  Outputs first and contiguous (results, nodes): a
+// download is their prefix.
+struct S3DenseLayout {
+    size_t o_out, o_po, down, o_W, o_lin, total;
+    S3DenseLayout(size_t G, size_t sumN, size_t sumE)
+    {
+        Carve L{64};
+        o_out = L.take(G * sizeof(mvs_pose_graph_result)), o_po = L.take(sumN * kS3Node * 8);
+        down = L.total();
+        o_W = L.take(sumE * kS3W * 8), o_lin = L.take(sumE * kS3Lin * 8);
+        total = L.total();
+    }
+};
+
+// graphs of up to 16 nodes over device-resident inputs: one launch.  `base`: scratch of S3DenseLayout::total bytes.
+static mvs_status sim3_graph_dense_dev(mvs_ctx *ctx, char *base, const S3DenseLayout &L, int n_graphs,
+                                       const mvs_sim3_graph_params &params, const PgProblem *d_prob, const double *d_node,
+                                       const int32_t *d_src, const int32_t *d_dst, const double *d_z, const double *d_cov)
+{
+    S3DenseDev d{};
+    d.n_problems = n_graphs;
+    d.cfg = to_s3_cfg(params);
+    d.prob = d_prob;
+    d.node = d_node;
+    d.edge_z = d_z;
+    d.edge_cov = d_cov;
+    d.edge_src = d_src;
+    d.edge_dst = d_dst;
+    d.W = reinterpret_cast<double *>(base + L.o_W);
+    d.lin = reinterpret_cast<double *>(base + L.o_lin);
+    d.nodes_out = reinterpret_cast<double *>(base + L.o_po);
+    d.out = reinterpret_cast<mvs_pose_graph_result *>(base + L.o_out);
+    launch_s3_dense(d, ctx_stream(ctx));
+    HIP_TRY(ctx, hipGetLastError());
+    return MVS_OK;
+}
+
+mvs_status mvs_sim3_graph_optimize_batch(mvs_ctx *ctx, const mvs_sim3_graph *graphs, int n_graphs,
+                                         const mvs_sim3_graph_params *params, mvs_pose_graph_result *results, double *nodes_out)
+{
+    if (!ctx || !graphs || n_graphs < 1 || !params || !results || !nodes_out)
+        return MVS_ERR_INVALID_ARG;
+    if (!sim3_graph_params_ok(params))
+        return MVS_ERR_INVALID_ARG;
+    int Nmax = 0;
+    for (int i = 0; i < n_graphs; ++i) {
+        const mvs_status st = sim3_graph_check(graphs[i]);
+        if (st != MVS_OK)
+            return st;
+        Nmax = std::max(Nmax, graphs[i].n_nodes);
+    }
+    std::memset(results, 0, (size_t)n_graphs * sizeof(mvs_pose_graph_result));
+    std::vector<char> joined((size_t)n_graphs);
+    for (int i = 0; i < n_graphs; ++i) {
+        const mvs_sim3_graph &g = graphs[i];
+        joined[(size_t)i] = pose_graph_connected(g.n_nodes, g.n_edges, g.edge_src, g.edge_dst, g.anchor_node) ? 1 : 0;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx_stream(ctx);
+    // the batch's graphs of up to 16 nodes: one upload, one launch, one download
+    std::vector<PgProblem> desc;
+    std::vector<int> which;
+    size_t sumN = 0, sumE = 0;
+    for (int i = 0; i < n_graphs; ++i) {
+        const mvs_sim3_graph &g = graphs[i];
+        if (!joined[(size_t)i] || g.n_nodes > kS3DenseMaxNodes)
+            continue;
+        PgProblem p{};
+        p.n_nodes = g.n_nodes, p.n_edges = g.n_edges, p.anchor = g.anchor_node;
+        p.node_off = (int64_t)sumN, p.edge_off = (int64_t)sumE;
+        sumN += (size_t)g.n_nodes;
+        sumE += (size_t)g.n_edges;
+        desc.push_back(p);
+        which.push_back(i);
+    }
+    if (!desc.empty()) {
+        const size_t G = desc.size();
+        const S3DenseLayout L(G, sumN, sumE);
+        const size_t o_up = L.total;   // the uploaded block: descriptors, nodes, edge measurements, covariances, src, dst
+        Carve U{64};
+        const size_t u_desc = U.take(G * sizeof(PgProblem)), u_np = U.take(sumN * kS3Node * 8), u_z = U.take(sumE * kS3Node * 8);
+        const size_t u_cov = U.take(sumE * kS3Cov * 8), u_src = U.take(sumE * 4), u_dst = U.take(sumE * 4);
+        mvs_status st = ws_grow(ctx, ctx->pg, o_up + U.total());
+        if (st != MVS_OK)
+            return st;
+        std::vector<char> up(U.total());
+        std::memcpy(up.data() + u_desc, desc.data(), G * sizeof(PgProblem));
+        for (size_t k = 0; k < G; ++k) {
+            const mvs_sim3_graph &g = graphs[which[k]];
+            const size_t n = (size_t)g.n_nodes, e = (size_t)g.n_edges, no = (size_t)desc[k].node_off, eo = (size_t)desc[k].edge_off;
+            std::memcpy(up.data() + u_np + no * kS3Node * 8, g.node_sim3, n * kS3Node * 8);
+            if (e) {
+                std::memcpy(up.data() + u_z + eo * kS3Node * 8, g.edge_sim3, e * kS3Node * 8);
+                std::memcpy(up.data() + u_cov + eo * kS3Cov * 8, g.edge_cov, e * kS3Cov * 8);
+                std::memcpy(up.data() + u_src + eo * 4, g.edge_src, e * 4);
+                std::memcpy(up.data() + u_dst + eo * 4, g.edge_dst, e * 4);
+            }
+        }
+        char *base = ctx->pg.ptr();
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_up, up.data(), up.size(), hipMemcpyHostToDevice, s));
+        auto dp = [&](size_t o) { return reinterpret_cast<const double *>(base + o_up + o); };
+        auto ip = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o_up + o); };
+        st = sim3_graph_dense_dev(ctx, base, L, (int)G, *params, reinterpret_cast<const PgProblem *>(base + o_up + u_desc), dp(u_np),
+                                  ip(u_src), ip(u_dst), dp(u_z), dp(u_cov));
+        if (st != MVS_OK)
+            return st;
+        std::vector<char> host(L.down);
+        HIP_TRY(ctx, hipMemcpyAsync(host.data(), base, L.down, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, sync_stream(ctx));
+        for (size_t k = 0; k < G; ++k) {
+            const int i = which[k];
+            std::memcpy(&results[i], host.data() + L.o_out + k * sizeof(mvs_pose_graph_result), sizeof(mvs_pose_graph_result));
+            if (results[i].ok)
+                std::memcpy(nodes_out + (size_t)i * Nmax * kS3Node, host.data() + L.o_po + (size_t)desc[k].node_off * kS3Node * 8,
+                            (size_t)graphs[i].n_nodes * kS3Node * 8);
+        }
+    }
+    // larger graphs, one after another: upload in front of the solver's scratch
+    for (int i = 0; i < n_graphs; ++i) {
+        const mvs_sim3_graph &g = graphs[i];
+        if (!joined[(size_t)i] || g.n_nodes <= kS3DenseMaxNodes)
+            continue;
+        const size_t N = (size_t)g.n_nodes, E = (size_t)g.n_edges;
+        const struct {
+            const void *host;
+            size_t bytes;
+        } parts[] = {{g.edge_src, E * 4}, {g.edge_dst, E * 4}, {g.edge_sim3, E * kS3Node * 8}, {g.edge_cov, E * kS3Cov * 8},
+                     {g.node_sim3, N * kS3Node * 8}};
+        Carve U{64};
+        size_t o[5];
+        for (int k = 0; k < 5; ++k)
+            o[k] = U.take(parts[k].bytes);
+        mvs_status st = ws_grow(ctx, ctx->pg, U.total() + S3LargeLayout(N, E).total);
+        if (st != MVS_OK)
+            return st;
+        char *base = ctx->pg.ptr();
+        for (int k = 0; k < 5; ++k)
+            if (parts[k].bytes)
+                HIP_TRY(ctx, hipMemcpyAsync(base + o[k], parts[k].host, parts[k].bytes, hipMemcpyHostToDevice, s));
+        auto dp = [&](int k) { return reinterpret_cast<const double *>(base + o[k]); };
+        auto ip = [&](int k) { return reinterpret_cast<const int32_t *>(base + o[k]); };
+        st = sim3_graph_large_dev(ctx, base + U.total(), g.n_nodes, g.n_edges, g.anchor_node, g.edge_src, g.edge_dst, ip(0), ip(1), dp(4),
+                                  dp(2), dp(3), *params, &results[i], nodes_out + (size_t)i * Nmax * kS3Node, hipMemcpyDeviceToHost);
+        if (st != MVS_OK)
+            return st;
+    }
+    bool all_ok = true;
+    for (int i = 0; i < n_graphs; ++i)
+        all_ok = all_ok && results[i].ok;
+    return all_ok ? MVS_OK : MVS_NO_MODEL;
+}
+
+mvs_status mvs_sim3_graph_optimize(mvs_ctx *ctx, const mvs_sim3_graph *graph, const mvs_sim3_graph_params *params,
+                                   mvs_pose_graph_result *result, double *nodes_out)
+{
+    return mvs_sim3_graph_optimize_batch(ctx, graph, 1, params, result, nodes_out);
+}
+
+mvs_status mvs_seq_optimize_pose_graph_sim3(mvs_seq *q, const mvs_sim3_graph_params *params, const double scale_sigma[3],
+                                            mvs_pose_graph_result *result)
+{
+    if (!q || !q->graph_built || !result || !scale_sigma || !sim3_graph_params_ok(params) || !scale_sigmas_ok(scale_sigma))
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const SeqGraphDev &g = q->gd;
+    hipStream_t s = ctx_stream(ctx);
+    q->graph_sim3 = false;
+    *result = mvs_pose_graph_result{};
+    SeqGraphHead head;
+    mvs_status st = seq_graph_head(q, "mvs_seq_optimize_pose_graph_sim3", head);
+    if (st != MVS_OK)
+        return st;
+    const int N = g.n_frames, E = head.n_edges;
+    if (!pose_graph_connected(N, E, head.src, head.dst, 0))
+        return MVS_NO_MODEL;
+    const size_t Nz = (size_t)N, Ez = (size_t)E;
+    const bool dense = N <= kS3DenseMaxNodes;
+    const S3DenseLayout Ld(1, Nz, Ez);
+    // the lifted graph in front of the solver's scratch, the dense path's descriptor behind it
+    Carve U{64};
+    const size_t o_node = U.take(Nz * kS3Node * 8), o_z = U.take(Ez * kS3Node * 8), o_cov = U.take(Ez * kS3Cov * 8);
+    const size_t o_scratch = U.total(), scratch = dense ? Ld.total + sizeof(PgProblem) : S3LargeLayout(Nz, Ez).total;
+    if ((st = ws_grow(ctx, ctx->pg, o_scratch + scratch)) != MVS_OK)
+        return st;
+    if ((st = ws_grow(ctx, q->graph_s3, Nz * kS3Node * 8)) != MVS_OK)
+        return st;
+    char *base = ctx->pg.ptr();
+    S3LiftDev lf{};
+    lf.n_nodes = N, lf.n_edges = E;
+    for (int k = 0; k < 3; ++k)
+        lf.scale_sigma[k] = scale_sigma[k];
+    lf.node_pose = g.node_pose, lf.edge_pose = g.edge_pose, lf.edge_cov = g.edge_cov, lf.edge_kind = g.edge_kind;
+    lf.node = reinterpret_cast<double *>(base + o_node), lf.edge_z = reinterpret_cast<double *>(base + o_z);
+    lf.cov = reinterpret_cast<double *>(base + o_cov);
+    launch_s3_lift(lf, s);
+    HIP_TRY(ctx, hipGetLastError());
+    double *nodes = q->graph_s3.ptr<double>();
+    if (dense) {
+        PgProblem pr{};
+        pr.n_nodes = N, pr.n_edges = E, pr.anchor = 0;
+        char *sb = base + o_scratch;
+        HIP_TRY(ctx, hipMemcpyAsync(sb + Ld.total, &pr, sizeof(pr), hipMemcpyHostToDevice, s));
+        st = sim3_graph_dense_dev(ctx, sb, Ld, 1, *params, reinterpret_cast<const PgProblem *>(sb + Ld.total), lf.node, g.edge_src,
+                                  g.edge_dst, lf.edge_z, lf.cov);
+        if (st != MVS_OK)
+            return st;
+        HIP_TRY(ctx, hipMemcpyAsync(result, sb + Ld.o_out, sizeof(*result), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, sync_stream(ctx));   // `pr` lives on this frame
+        if (result->ok)
+            HIP_TRY(ctx, hipMemcpyAsync(nodes, sb + Ld.o_po, Nz * kS3Node * 8, hipMemcpyDeviceToDevice, s));
+    } else {
+        st = sim3_graph_large_dev(ctx, base + o_scratch, N, E, 0, head.src, head.dst, g.edge_src, g.edge_dst, lf.node, lf.edge_z, lf.cov,
+                                  *params, result, nodes, hipMemcpyDeviceToDevice);
+        if (st != MVS_OK)
+            return st;
+    }
+    q->graph_sim3 = result->ok != 0;
+    return result->ok ? MVS_OK : MVS_NO_MODEL;
+}
+
+mvs_status mvs_seq_download_pose_graph_sim3(mvs_seq *q, double *nodes13)
+{
+    if (!q || !nodes13 || !q->graph_built || !q->graph_sim3)
+        return MVS_ERR_INVALID_ARG;
+    mvs_ctx *ctx = q->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(nodes13, q->graph_s3.ptr(), (size_t)q->n_frames * kS3Node * 8, hipMemcpyDeviceToHost, ctx_stream(ctx)));
     HIP_TRY(ctx, sync_stream(ctx));
     return MVS_OK;
 }
@@ -1208,7 +1643,7 @@ mvs_status mvs_seq_add_loop_edges(mvs_seq *q, const mvs_loop_edge_params *p)
     launch_loop_edges(q->gd, e, s);
     HIP_TRY(ctx, hipGetLastError());
     q->loop_edges_added = true;
-    q->graph_opt = false;
+    q->graph_opt = q->graph_sim3 = false;
     return MVS_OK;
 }
 

@@ -166,6 +166,9 @@ struct mvs_seq {
     double *graph_opt_pose = nullptr;   // [n_frames][12] in `graph`
     bool graph_built = false;   // the graph is that of the last run and its lags
     bool graph_opt = false;     // mvs_seq_optimize_pose_graph has succeeded on it
+    // mvs_seq_optimize_pose_graph_sim3: the Sim(3) optimised nodes [n_frames][13]; graph_sim3 only while graph_built
+    DevWorkspace graph_s3;
+    bool graph_sim3 = false;    // it has succeeded on the current graph (a build or added loop edges clear it)
     int graph_edge_cap = 0;     // rows of the graph's edge arrays: the build's slots, plus room for loop edges
     int32_t *graph_n_built = nullptr;   // [1] in `graph`: edges of the built graph, behind which the loop edges go
     // loop closures (mvs_seq_loop_scores .. mvs_seq_add_loop_edges): the score table, the selection's block (counts,

@@ -369,6 +369,64 @@ struct PgStatsDev {
 };
 void launch_pg_edge_stats(const PgStatsDev &d, hipStream_t stream);
 
+// ---- pose graphs over Sim(3) (sim3graph.hip) ------------------------------------------------------
+// The same two paths with 7 degrees of freedom per node: a node is (R, t, s) in 13 doubles, an edge's covariance 7 x 7, its
+// whitening factor 28 doubles.  PgProblem and PgState are the SE(3) solver's.
+constexpr int kS3DenseMaxNodes = 16;     // 7 * 16 = 112 unknowns: a packed triangle of 6328 doubles = 50624 B of LDS
+constexpr int kS3Node = 13, kS3Cov = 49, kS3W = 28;
+constexpr int kS3Lin = 105;              // whitened residual 7, A_src 49, A_dst 49 (row-major)
+struct S3Cfg {
+    int max_iterations;
+    double lambda_initial, lambda_factor, lambda_upper, rel_tol, abs_tol;
+    double w_anchor[3];                  // 1 / sigma^2 of the anchor prior: rotation, translation, log-scale
+    double cg_rel_tol;
+    int cg_max_iterations;
+};
+struct S3DenseDev {
+    int n_problems;
+    S3Cfg cfg;
+    const PgProblem *prob;
+    const double *node;          // [sum N][13] initial values; the anchor's is its prior mean
+    const int32_t *edge_src, *edge_dst;
+    const double *edge_z;        // [sum E][13]
+    const double *edge_cov;      // [sum E][49]
+    double *W;                   // [sum E][28]
+    double *lin;                 // [sum E][kS3Lin]
+    double *nodes_out;           // [sum N][13]
+    mvs_pose_graph_result *out;  // [G]
+};
+void launch_s3_dense(const S3DenseDev &d, hipStream_t stream);
+struct S3LargeDev {
+    int n_nodes, n_edges, anchor;
+    S3Cfg cfg;
+    const int32_t *edge_src, *edge_dst;
+    const double *edge_z, *edge_cov;
+    const int32_t *csr_off, *csr_inc;   // PgLargeDev's
+    const double *node0;         // [N][13] initial values
+    double *node[2];             // [N][13] current / candidate
+    double *W, *lin, *u, *ecost; // [E][28], [E][kS3Lin], [E][7], [E]
+    double *D, *Mf;              // [N][28]
+    double *g, *x, *r, *z, *p, *q;   // [N][7]
+    double *pq;                  // [N]
+    double *Ha;                  // [49] the anchor prior's block of H
+    PgState *state;
+};
+// the parts of one LM iteration, as launch_pg_prep / _begin / _cg / _end
+void launch_s3_prep(const S3LargeDev &d, hipStream_t stream);
+void launch_s3_begin(const S3LargeDev &d, int cur, double lam, bool first, hipStream_t stream);
+void launch_s3_cg(const S3LargeDev &d, double lam, int n, hipStream_t stream);
+void launch_s3_end(const S3LargeDev &d, int cur, hipStream_t stream);
+// an SE(3) graph lifted to Sim(3) (mvs_seq_optimize_pose_graph_sim3): node k -> (pose, 1), edge e -> (Z, 1) and
+// blockdiag(cov, scale_sigma[kind_e] * scale_sigma[kind_e]); copies and one multiply
+struct S3LiftDev {
+    int n_nodes, n_edges;
+    double scale_sigma[3];
+    const double *node_pose, *edge_pose, *edge_cov;   // [N][12], [E][12], [E][36]
+    const int32_t *edge_kind;                         // [E]
+    double *node, *edge_z, *cov;                      // [N][13], [E][13], [E][49]
+};
+void launch_s3_lift(const S3LiftDev &d, hipStream_t stream);
+
 // ---- the direct LM step of the large path (pg_direct.hip) ------------------------------------
 // (H + lambda I) x = -g by a block-scaled skyline Cholesky.  The diagonal blocks D and the gradient g are pg_gather_kernel's;
 // C_i C_i^T = D_i + lambda I, the scaled matrix C_i^-1 A_ij C_j^-T (unit diagonal blocks) is assembled into the envelope of

@@ -1,5 +1,5 @@
 // lm_math.hpp -- the small-matrix device math the Levenberg-Marquardt solvers share: refine.hip, posegraph.hip,
-// pg_marginals.hip, pg_direct.hip, ba_sparse.hip and seq_graph.hip include it, and nothing else does.  SO(3) maps, the pose
+// sim3graph.hip, pg_marginals.hip, pg_direct.hip, ba_sparse.hip and seq_graph.hip include it, and nothing else does.  SO(3) maps, the pose
 // prior, the pinhole projection with its Jacobians, packed Cholesky factorisation and solves, the point block's 3 x 3
 // Cholesky under the pivot rule, the robust-loss weight and rho2.  Device only; everything is forced inline into an anonymous
 // namespace, so a file's kernels are compiled from these statements in this order exactly as if they stood in the file.

@@ -18,6 +18,23 @@ inline bool all_finite(const double *v, size_t n)
     return true;
 }
 
+// the scale of every Sim(3) record (13 doubles: R, t, s) is > 0 (mvs_sim3_graph_optimize; the records are finite already)
+inline bool sim3_scales_positive(const double *v, size_t n)
+{
+    for (size_t i = 0; i < n; ++i)
+        if (!(v[13 * i + 12] > 0.0))
+            return false;
+    return true;
+}
+// mvs_seq_optimize_pose_graph_sim3's scale_sigma: one per edge kind, each finite and > 0
+inline bool scale_sigmas_ok(const double *sigma)
+{
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(sigma[i]) || !(sigma[i] > 0.0))
+            return false;
+    return true;
+}
+
 // mvs_ctx_set_pose_graph_loss's arguments: a loss of 0 (none), 1 (Huber) or 2 (Cauchy); with a loss, a constant k that is
 // finite and > 0; first_edge >= -1 (-1: the loop edges of a resident graph)
 inline bool loss_args_ok(int loss, double k, int32_t first_edge)
